@@ -10,10 +10,20 @@ in contiguous blocks (cape_amd.dist.shard_range), rank r extracts frames [a_r, b
 ncclAllGather of the packed primitive lists, issued by libcape_hip itself (cape_gather_primitives) on its own stream so
 that it runs under the next step's kernels.  `--scaling strong` keeps the stream at 8 x 2 048 frames for every N.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task description) with two extra objects:
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs is given, and prints
+ONE JSON line on rank 0: metric, value (frames/s), unit, higher_is_better, dtype, ms_per_step (one timed step), the
+configuration and the per-rank clocks.  Everything else moves behind --full, which adds to the same line:
   roofline     -- the dominant kernel's algorithmic bytes per launch / its mean launch duration (HIP events on the
-                  launch stream, inside the timed region) against the 8 TB/s HBM peak;
-  cpu_baseline -- the CPU oracle (a port of the reference algorithm, NOT the product) timed on this host.
+                  launch stream, from a second pass of the same steps with the handle's timing on) against the 8 TB/s HBM peak;
+  cpu_baseline -- the CPU oracle (a port of the reference algorithm, NOT the product) timed on this host;
+  parity_check, gather, boundary_polygons, cylinders_on, find_primitives_equivalent, two_handles_overlapped,
+  beyond_fixed_capacities -- the in-run comparisons with the oracles and the extra legs (each has a --no-* switch).
+
+--dump-outputs DIR writes what the timed path hands its caller after the last timed step (records, plane label grid,
+boundary points; the cylinder grid and labels with --cylinders; matches with --match; the gathered primitive lists at
+N > 1) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: a fixed, seeded sample of the frames when the whole
+batch would not fit.  An output with no element (no cylinder in the sampled frames, say) is not written.  The inputs
+depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -24,7 +34,8 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "rgb-d-slam_amd", "python"))
 
-HBM_PEAK_BYTES_S = 8.0e12  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak BW, spec
+HBM_PEAK_BYTES_S = 8.0e12  # MI355X HBM3E peak bandwidth, spec
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 class _DevMem:
@@ -256,6 +267,114 @@ def parity_ok(pc):
     return bool(pc["labels_equal"] and pc["counts_equal"] and pc["segments_bitwise"] and pc["cylinders_bitwise"])
 
 
+# --dump-outputs: the fields of the result records, as columns.  Left out: where a frame's spill records and a segment's
+# boundary points lie in the handle's buffers (next_record, segment_base, boundary_offset) -- spill records are handed
+# out by an atomic counter, so those indices may differ from run to run while the results themselves do not.
+DUMP_HEADER_FIELDS = ("n_plane_segments", "n_planes", "n_cylinder_labels", "n_cylinders", "n_boundary_points", "n_seeds", "status",
+                      "n_planar_cells")
+DUMP_SEGMENT_FIELDS = ("normal", "d", "centroid", "mse", "score", "sums", "out_normal", "cov", "point_count", "merge_label", "planar",
+                       "is_output", "boundary_count")
+DUMP_CYLINDER_FIELDS = ("axis", "radius", "kept", "region")
+DUMP_MATCH_FIELDS = ("n_prev", "n_cur", "match", "area_prev", "area_cur", "inter")
+DUMP_PACKED_PLANE_FIELDS = ("normal", "d", "centroid", "mse", "score", "sums", "point_count", "segment")
+
+
+def _columns(rows, fields, lead=None, dtype=None):
+    """structured rows -> 2-D float array, one column per scalar of `fields` (after the leading columns `lead`)."""
+    import numpy as np
+
+    dtype = dtype or np.float64
+    n = len(rows)
+    cols = [] if lead is None else [np.asarray(c, dtype).reshape(n, 1) for c in lead]
+    cols += [np.asarray(rows[k], dtype).reshape(n, int(np.prod(rows.dtype[k].shape, dtype=np.int64))) for k in fields]
+    return np.concatenate(cols, axis=1)
+
+
+def _frame_sample(n, k):
+    """Every frame if k >= n, else a fixed, seeded sample of k of them (sorted)."""
+    import numpy as np
+
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def _batch_outputs(res, matches, frames, cylinders=True):
+    """What the caller of the timed path receives for the frames `frames` of the last step: header counts, the plane label
+    grid, the plane segments (chains followed), the boundary points of every output plane (sorted within the plane: the set
+    is the result, the order in which the waves wrote it is not), with `cylinders` the cylinder label grid and the cylinder
+    labels, and, with --match, the matcher's records."""
+    import numpy as np
+
+    out = {"frames": frames.astype(np.float64),
+           "header": _columns(res.records["header"][frames], DUMP_HEADER_FIELDS),
+           "plane_labels": res.plane_labels[frames].astype(np.float32)}
+    if cylinders:
+        out["cyl_labels"] = res.cyl_labels[frames].astype(np.float32)
+    segs, cyls, bnds = [], [], []
+    for f in frames:
+        s = res.segments(f)
+        segs.append(_columns(s, DUMP_SEGMENT_FIELDS, lead=[np.full(len(s), f)]))
+        c = res.cylinder_labels(f)
+        cyls.append(_columns(c, DUMP_CYLINDER_FIELDS, lead=[np.full(len(c), f)]))
+        for p, b in enumerate(res.plane_boundaries(f)):
+            b = b[np.lexsort(b.T[::-1])] if len(b) else b.reshape(0, 3)
+            bnds.append(np.concatenate([np.full((len(b), 1), f, np.float64), np.full((len(b), 1), p, np.float64), b], axis=1))
+    out["segments"] = np.concatenate(segs) if segs else np.zeros((0, 1), np.float64)
+    if cylinders:
+        out["cylinders"] = np.concatenate(cyls) if cyls else np.zeros((0, 1), np.float64)
+    out["boundary_points"] = np.concatenate(bnds) if bnds else np.zeros((0, 5), np.float64)
+    if matches is not None:
+        out["matches"] = _columns(matches[frames], DUMP_MATCH_FIELDS, lead=[frames], dtype=np.float32)  # (integers below 2^24)
+    return out
+
+
+def _gathered_outputs(shards, frames, cylinders=True):
+    """The gathered packed lists as every rank receives them, for the stream frames `frames`: per frame (frame, status,
+    n_plane_segments, planes, cylinders), then the planes and, with `cylinders`, the cylinders themselves."""
+    import numpy as np
+
+    by_frame = {}
+    for sh in shards:
+        for k in range(len(sh.frames)):
+            by_frame[sh.first_frame + k] = (sh.frames[k], sh.frame_planes(k), sh.frame_cylinders(k))
+    hdr, pls, cys = [], [], []
+    for f in frames:
+        fr, pl, cy = by_frame[int(f)]
+        hdr.append([f, fr["status"], fr["n_plane_segments"], len(pl), len(cy)])
+        pls.append(_columns(pl, DUMP_PACKED_PLANE_FIELDS, lead=[np.full(len(pl), f)]))
+        cys.append(_columns(cy, ("axis", "radius"), lead=[np.full(len(cy), f)]))
+    out = {"gathered_frames": np.asarray(hdr, np.float64).reshape(-1, 5),
+           "gathered_planes": np.concatenate(pls) if pls else np.zeros((0, 1), np.float64)}
+    if cylinders:
+        out["gathered_cylinders"] = np.concatenate(cys) if cys else np.zeros((0, 1), np.float64)
+    return out
+
+
+def dump_outputs(out_dir, make, n_frames, budget, prefix=""):
+    """Writes make(frames) as out_dir/<prefix><name>.npy for as many frames as fit `budget` bytes: the whole batch, else a seeded
+    sample of at most 1 024 frames, halved until it fits.  An output without a single element (a table of primitives none of
+    the sampled frames holds) is not written."""
+    import numpy as np
+
+    k = n_frames if n_frames <= 1024 else 1024
+    while True:
+        arrays = make(_frame_sample(n_frames, k))
+        total = sum(a.nbytes for a in arrays.values())
+        if total <= budget or k == 1:
+            break
+        k = max(1, k // 2)
+    if total > budget:
+        raise SystemExit(f"bench.py: --dump-outputs: one frame's outputs take {total} bytes, more than the {budget} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.size == 0:
+            continue
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -294,6 +413,11 @@ def main():
     ap.add_argument("--no-polygons", action="store_true", help="skip the extra boundary-polygon leg (cape_build_polygons)")
     ap.add_argument("--no-cylinders-on", action="store_true",
                     help="N=1 default workload: skip the extra 'cylinders_on' leg (same stream with the reference's unconditional cylinder branch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: per-kernel / roofline figures, the CPU baseline, "
+                         "the in-run comparisons with the oracles, the gather check and the extra legs (the --no-* switches trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -432,7 +556,7 @@ def main():
     # what RCCL itself reports per rank (cape_comm_info: ncclCommCount / ncclCommUserRank / ncclCommCuDevice next to the values
     # cape_comm_init was given): the evidence that an N-GPU run had N ranks on N devices.  None when torch.distributed moved the bytes.
     comm_infos = None
-    if gather == "native":
+    if gather == "native" and args.full:
         comm_infos = [None] * world
         dist.all_gather_object(comm_infos, dict(ex.comm_info(), local_rank=dev_index))
     step_no = [0]
@@ -501,16 +625,36 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    ex.reset_timings()
-    ex.enable_timing(True)
     elapsed, own = timed(args.steps, step)
-    ex.enable_timing(False)
-    tm = ex.timings()
     elapsed, _, _ = over_ranks(elapsed)                  # the contract's clock: max over ranks, barriers inside
     own_max, own_min, own_all = over_ranks(own)
 
+    if args.dump_outputs:
+        # outside the timed region: the last timed step's results are still in the handle (and in the receive buffer)
+        budget = DUMP_LIMIT_BYTES // world
+        res = ex.results(B)
+        mt = ex.matches(B) if args.match else None
+        got = recv[(step_no[0] - 1) & 1] if gather != "none" and recv is not None else None
+        if got is not None and rank == 0:
+            budget //= 2
+            shards = cdist.unpack_gathered(got.cpu().numpy(), world, lay)
+            dump_outputs(args.dump_outputs, lambda fr: _gathered_outputs(shards, fr, args.cylinders), total, budget)
+        dump_outputs(args.dump_outputs, lambda fr: _batch_outputs(res, mt, fr, args.cylinders), B, budget,
+                     prefix=f"rank{rank}_" if world > 1 else "")
+        del res
+
+    tm = None
+    if args.full:
+        # per-kernel launch times for the roofline block: the same steps once more with the handle's HIP events around its
+        # kernels (and the grow kernel's phase counters) switched on -- instrumentation the headline clock above does not carry
+        ex.reset_timings()
+        ex.enable_timing(True)
+        timed(args.steps, step)
+        ex.enable_timing(False)
+        tm = ex.timings()
+
     gather_check = None
-    if gather != "none":
+    if gather != "none" and args.full:
         # outside the timed region: what arrived is every rank's shard, in rank order, nothing dropped
         got = recv[(step_no[0] - 1) & 1]
         if got is None:
@@ -548,7 +692,7 @@ def main():
 
     # ---- the work proves itself: first frames of the last timed step vs the CPU oracle (every rank checks its own shard)
     parity = None
-    if not args.no_parity_check:
+    if args.full and not args.no_parity_check:
         # EVERY distinct frame of the step (64 of 4 096 used to be checked): the oracle does ~500 frames/s per core and
         # the box has dozens of cores -- a few seconds outside every timed region.  (--parity-frames bounds it.)
         n_chk = min(U, args.parity_frames if args.parity_frames > 0 else U)
@@ -573,62 +717,6 @@ def main():
     if rank == 0:
         frames_total = total * args.steps if multi else B * args.steps
         cells = (W // 20) * (H // 20)
-        calls = max(1, tm["calls"])
-        fpl = tm["frames"] / calls  # frames per kernel launch (= B unless the batch is cut in sub-batches)
-        a1_ms = 1e3 * tm["cell_moments_s"] / calls
-        a2_ms = 1e3 * tm["cell_plane_s"] / calls
-        b_ms = 1e3 * tm["grow_s"] / calls
-        # algorithmic bytes per launch (DESIGN.md "Measurement"):
-        #   A1 cell moments : reads every depth pixel once, writes 96 B per cell (10 f64 sums + 16 B hand-over)
-        #   A2 cell plane   : reads those 96 B, writes 88 B per cell (plane, score, tolerance, flags, bin)
-        #   B  grow         : reads 112 B per cell (sums 80, flags 4, bin 4, MSE 8, centre-pixel record 16; the cell planes stay
-        #                     in stage A2, which hands over four edge bits per cell), writes label grids + primitive lists
-        kernels = {
-            "cape_cell_moments_kernel": (a1_ms, fpl * (W * H * (2 if args.u16 else 4) + cells * 96)),
-            "cape_cell_plane_kernel": (a2_ms, fpl * (cells * (96 + 88))),
-            "cape_grow_kernel": (b_ms, fpl * (cells * 112 + 2 * cells * 4 + 32 * 128)),
-        }
-        dom = max(kernels, key=lambda k: kernels[k][0])
-        dom_ms, dom_bytes = kernels[dom]
-        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-        traffic, traffic_source = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("kernel") == dom and tj.get("frames_per_launch") == fpl and tj.get("width") == W:
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_source = ("profiles/traffic.json: static, from the separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
-                                      "profiles/collect.sh over this same command -- not measured by this run")
-            except Exception:
-                traffic = None
-        # The bound that actually holds the dominant kernel: A1 moves 1.0001 x its algorithmic bytes at about half the
-        # HBM peak because the ONE VALU port of a SIMD is busy.  profiles/valu_issue.py counts the vector instructions of the
-        # shipped ISA per class, prices them with the issue costs measured on gfx950 (profiles/r02_valu_rates.txt), and checks
-        # the count against a rocprofv3 --pmc SQ_INSTS_VALU pass of this command; the fraction below uses THIS run's launch time.
-        valu_issue = None
-        vpath = os.path.join(ROOT, "profiles", "valu_issue.json")
-        if dom == "cape_cell_moments_kernel" and os.path.exists(vpath):
-            try:
-                vj = json.load(open(vpath))
-                vv = vj["variants"]["u16" if args.u16 else "f32"]
-                if vj.get("width") == W and vj.get("height") == H:
-                    sc = fpl / vj["frames_per_launch"]
-                    valu_issue = {"floor_ms": vv["floor_ms"] * sc, "frac_of_issue_floor": vv["floor_ms"] * sc / dom_ms,
-                                  "f64_rate_insts_per_launch": vv["f64_rate_insts_per_launch"] * sc,
-                                  "other_valu_insts_per_launch": vv["other_insts_per_launch"] * sc,
-                                  "f64_rate_share_of_floor": vv["f64_rate_share_of_floor"],
-                                  "valu_insts_per_wave": vv["valu_per_wave"], "waves_per_launch": vj["waves_per_launch"] * sc,
-                                  "pmc_SQ_INSTS_VALU_per_launch": (vv.get("pmc") or {}).get("SQ_INSTS_VALU_per_launch"),
-                                  "ns_per_wave_instruction": vj["rate_ns_per_wave_instruction"],
-                                  "source": "profiles/valu_issue.json (profiles/valu_issue.py: ISA of the shipped kernel x the measured issue costs of "
-                                            "profiles/r02_valu_rates.txt, checked against the SQ_INSTS_VALU pass " +
-                                            str((vv.get("pmc") or {}).get("source")) + "); static, the fraction uses this run's launch_ms",
-                                  "note": "one VALU port per SIMD: f64-rate and other vector instructions of different waves add up "
-                                          "(profiles/r02_valu_mix.txt); the f64 conversions and adds are the reference's operand types"}
-            except Exception:
-                valu_issue = None
-        e2e_bytes_per_frame = W * H * (2 if args.u16 else 4) + 2 * cells * 4 + 32 * 128  # 1 239 040 B at 640x480
         if multi:
             workload = (f"{W}x{H} synthetic TUM-like depth stream of {total} frames sharded in contiguous blocks over {world} GPU(s), "
                         f"planes" + (" + cylinder RANSAC" if args.cylinders else " only") +
@@ -662,7 +750,65 @@ def main():
                 **({"backend": f"gloo: {world} ranks on {torch.cuda.device_count()} visible device(s) -- a dry run of the N > 1 code "
                                "paths, NOT a scaling measurement (CAPE_BENCH_BACKEND)"} if backend == "gloo" else {}),
             },
-            "roofline": {
+        }
+        if tm is not None:
+            calls = max(1, tm["calls"])
+            fpl = tm["frames"] / calls  # frames per kernel launch (= B unless the batch is cut in sub-batches)
+            a1_ms = 1e3 * tm["cell_moments_s"] / calls
+            a2_ms = 1e3 * tm["cell_plane_s"] / calls
+            b_ms = 1e3 * tm["grow_s"] / calls
+            # algorithmic bytes per launch (DESIGN.md "Measurement"):
+            #   A1 cell moments : reads every depth pixel once, writes 96 B per cell (10 f64 sums + 16 B hand-over)
+            #   A2 cell plane   : reads those 96 B, writes 88 B per cell (plane, score, tolerance, flags, bin)
+            #   B  grow         : reads 112 B per cell (sums 80, flags 4, bin 4, MSE 8, centre-pixel record 16; the cell planes stay
+            #                     in stage A2, which hands over four edge bits per cell), writes label grids + primitive lists
+            kernels = {
+                "cape_cell_moments_kernel": (a1_ms, fpl * (W * H * (2 if args.u16 else 4) + cells * 96)),
+                "cape_cell_plane_kernel": (a2_ms, fpl * (cells * (96 + 88))),
+                "cape_grow_kernel": (b_ms, fpl * (cells * 112 + 2 * cells * 4 + 32 * 128)),
+            }
+            dom = max(kernels, key=lambda k: kernels[k][0])
+            dom_ms, dom_bytes = kernels[dom]
+            achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+            traffic, traffic_source = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    if tj.get("kernel") == dom and tj.get("frames_per_launch") == fpl and tj.get("width") == W:
+                        traffic = tj.get("hbm_bytes_per_launch")
+                        traffic_source = ("profiles/traffic.json: static, from the separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of "
+                                          "profiles/collect.sh over this same command -- not measured by this run")
+                except Exception:
+                    traffic = None
+            # The bound that actually holds the dominant kernel: A1 moves 1.0001 x its algorithmic bytes at about half the
+            # HBM peak because the ONE VALU port of a SIMD is busy.  profiles/valu_issue.py counts the vector instructions of the
+            # shipped ISA per class, prices them with the issue costs measured on gfx950 (profiles/r02_valu_rates.txt), and checks
+            # the count against a rocprofv3 --pmc SQ_INSTS_VALU pass of this command; the fraction below uses THIS run's launch time.
+            valu_issue = None
+            vpath = os.path.join(ROOT, "profiles", "valu_issue.json")
+            if dom == "cape_cell_moments_kernel" and os.path.exists(vpath):
+                try:
+                    vj = json.load(open(vpath))
+                    vv = vj["variants"]["u16" if args.u16 else "f32"]
+                    if vj.get("width") == W and vj.get("height") == H:
+                        sc = fpl / vj["frames_per_launch"]
+                        valu_issue = {"floor_ms": vv["floor_ms"] * sc, "frac_of_issue_floor": vv["floor_ms"] * sc / dom_ms,
+                                      "f64_rate_insts_per_launch": vv["f64_rate_insts_per_launch"] * sc,
+                                      "other_valu_insts_per_launch": vv["other_insts_per_launch"] * sc,
+                                      "f64_rate_share_of_floor": vv["f64_rate_share_of_floor"],
+                                      "valu_insts_per_wave": vv["valu_per_wave"], "waves_per_launch": vj["waves_per_launch"] * sc,
+                                      "pmc_SQ_INSTS_VALU_per_launch": (vv.get("pmc") or {}).get("SQ_INSTS_VALU_per_launch"),
+                                      "ns_per_wave_instruction": vj["rate_ns_per_wave_instruction"],
+                                      "source": "profiles/valu_issue.json (profiles/valu_issue.py: ISA of the shipped kernel x the measured issue costs of "
+                                                "profiles/r02_valu_rates.txt, checked against the SQ_INSTS_VALU pass " +
+                                                str((vv.get("pmc") or {}).get("source")) + "); static, the fraction uses this run's launch_ms",
+                                      "note": "one VALU port per SIMD: f64-rate and other vector instructions of different waves add up "
+                                              "(profiles/r02_valu_mix.txt); the f64 conversions and adds are the reference's operand types"}
+                except Exception:
+                    valu_issue = None
+            e2e_bytes_per_frame = W * H * (2 if args.u16 else 4) + 2 * cells * 4 + 32 * 128  # 1 239 040 B at 640x480
+            out["roofline"] = {
                 "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_BYTES_S / 1e9, "unit": "GB/s",
                 "frac": achieved * 1e9 / HBM_PEAK_BYTES_S, "traffic": traffic, "traffic_source": traffic_source,
                 # also against the 6.29 TB/s a streaming kernel can actually reach (MI355X_MICROARCH.md)
@@ -674,8 +820,7 @@ def main():
                             "note": "one wavefront per frame, latency bound; ~0 HBM bytes beyond the 112 B/cell it reads"},
                 "end_to_end_GBps": frames_total / world * e2e_bytes_per_frame / elapsed / 1e9,
                 "end_to_end_frac": frames_total / world * e2e_bytes_per_frame / elapsed / HBM_PEAK_BYTES_S,
-            },
-        }
+            }
         out["ranks"] = {"ms_per_step_max": 1e3 * own_max / args.steps, "ms_per_step_min": 1e3 * own_min / args.steps,
                         "ms_per_step": [1e3 * v / args.steps for v in own_all],
                         "note": "each rank's own clock around its K steps (device-synchronised, before the closing barrier); "
@@ -697,7 +842,7 @@ def main():
                 gather_check["rccl_ranks_seen"] = sorted({int(c["nranks"]) for c in comm_infos})
                 gather_check["rccl_devices_seen"] = sorted({(int(c["rank"]), int(c["device"])) for c in comm_infos})
             out["gather"] = gather_check
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             n_host = min(U, 64)
             if args.u16:
                 sample = unique_dev[:n_host].cpu().numpy().view(np.uint16).astype(np.float32) * np.float32(0.2)
@@ -708,7 +853,7 @@ def main():
         out = None
 
     polygons_leg = None
-    if rank == 0 and not args.no_polygons:
+    if rank == 0 and args.full and not args.no_polygons:
         # "Next" row N1 on the device, outside the main timed region: boundary polygons of every output plane of the last
         # batch (one wavefront per plane), timed with events on the launch stream
         ex.build_polygons(B, stream)
@@ -744,7 +889,7 @@ def main():
         ex.comm_destroy()
     ex.close()
 
-    if (rank == 0 and world == 1 and not multi and not args.cylinders and not args.no_cylinders_on and not args.u16
+    if (rank == 0 and world == 1 and not multi and args.full and not args.cylinders and not args.no_cylinders_on and not args.u16
             and not args.match and scene == "room"):
         # The headline workload once more on TWO handles, each on a stream of its own, fed alternately (outside the timed region of
         # `value`, which stays one handle, one stream): the per-cell fits and the one-wave-per-frame grow kernel of one batch issue
@@ -947,8 +1092,8 @@ def main():
         for h in pair:
             h.close()
         out["find_primitives_equivalent"] = fpe
-    if (rank == 0 and world == 1 and not multi and out is not None and not args.no_wide_grid and not args.cylinders and not args.u16
-            and not args.match and scene == "room" and (W, H) == (640, 480)):
+    if (rank == 0 and world == 1 and not multi and out is not None and args.full and not args.no_wide_grid and not args.cylinders
+            and not args.u16 and not args.match and scene == "room" and (W, H) == (640, 480)):
         # Round 6: what lay beyond the fast kernels' fixed shapes through round 5, in the driver-visible line.  (a) 1920 x 1080 (96 x 54
         # cells: rows of two mask words in the fast kernels), frames resident in HBM, every frame of the step checked against the oracle;
         # (b) a frame of more than 64 plane segments (a checkerboard of tilted facets) inside an ordinary 1280 x 960 batch: its record

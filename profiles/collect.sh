@@ -1,6 +1,6 @@
 #!/bin/bash
 # Regenerates the committed evidence of a round on the GPU box (run through gpurun from the repo root):
-#   <tag>_bench_n1.json               python bench.py (default workload, configs[1]; 4096 distinct frames)
+#   <tag>_bench_n1.json               python bench.py --full (default workload, configs[1]; 4096 distinct frames)
 #   <tag>_kernel_stats.csv            rocprofv3 --kernel-trace --stats of the same command
 #   <tag>_pmc_fetch.csv / _pmc_write.csv          separate --pmc passes (FETCH_SIZE / WRITE_SIZE), never mixed with tracing
 #   <tag>_pmc_calibration_fetch.csv / _write.csv  the same counters over a known byte count (microbench/stream_read.hip)
@@ -18,8 +18,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/collect_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/${TAG}_bench_n1.json 2> $OUT/bench.err
-CAPE_BENCH_FORCE_GATHER=1 python $R/bench.py --gpus 1 --no-cpu-baseline > $OUT/${TAG}_configs3_bench.json 2> $OUT/bench3.err
+python $R/bench.py --full > $OUT/${TAG}_bench_n1.json 2> $OUT/bench.err
+CAPE_BENCH_FORCE_GATHER=1 python $R/bench.py --full --gpus 1 --no-cpu-baseline > $OUT/${TAG}_configs3_bench.json 2> $OUT/bench3.err
 BARGS="--no-cpu-baseline --steps 60 --warmup 3 --no-cylinders-on --no-polygons --no-parity-check --no-wide-grid"
 stats() { # name, bench args...
     local name=$1; shift
@@ -38,7 +38,7 @@ stats cyl_ --scene tunnel --cylinders --frames 2048
 stats 1280_ --width 1280 --height 960 --frames 1024 --scene tunnel --cylinders --match
 stats u16_ --u16
 stats room_cyl_ --cylinders
-rocprofv3 --kernel-trace --stats -d $OUT/kt_poly -o k -- python $R/bench.py --no-cpu-baseline --steps 3 --warmup 1 --no-cylinders-on --no-parity-check > /dev/null 2> $OUT/kt_poly.err
+rocprofv3 --kernel-trace --stats -d $OUT/kt_poly -o k -- python $R/bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --no-cylinders-on --no-parity-check > /dev/null 2> $OUT/kt_poly.err
 python $R/profiles/summarize_rocprof.py stats $(find $OUT/kt_poly -name "*.db" | head -1) | grep "kernel,\|polygon" > $OUT/${TAG}_polygon_kernel_stats.csv; rm -rf $OUT/kt_poly
 pmc FETCH_SIZE fetch python $R/bench.py $BARGS
 pmc WRITE_SIZE write python $R/bench.py $BARGS

@@ -8,7 +8,7 @@ run() { # label, env assignments...
   for wl in "room 4096 640 480" "tunnel 2048 640 480" "tumlike 2048 640 480" "tunnel 1024 1280 960"; do
     set -- $wl "$@"
     local scene=$1 frames=$2 w=$3 h=$4; shift 4
-    env "$@" python bench.py --cylinders --scene $scene --frames $frames --width $w --height $h --steps 10 --warmup 3 \
+    env "$@" python bench.py --full --cylinders --scene $scene --frames $frames --width $w --height $h --steps 10 --warmup 3 \
         --no-cpu-baseline --no-parity-check > "$OUT/${label}_${scene}_${w}.json" 2> "$OUT/${label}_${scene}_${w}.err" || echo "FAILED $label $scene"
     python - "$OUT/${label}_${scene}_${w}.json" "$label" "$scene" "$w" <<'PY'
 import json,sys

@@ -15,7 +15,7 @@ for spec in sys.argv[1:]:
             env[k] = v
         else:
             args.append(tok)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + args, env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + args, env=env,
                          capture_output=True, text=True)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     if not line:
