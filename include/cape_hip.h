@@ -461,6 +461,64 @@ int cape_match_polygons(cape_handle h, int32_t n_frames, uint32_t flags, void* s
 int cape_match_polygons_pose(cape_handle h, int32_t n_frames, const double* prev_to_cur, uint32_t flags, void* stream);
 int cape_copy_polygon_matches(cape_handle h, int32_t n_frames, cape_frame_match_exact* out);
 
+/* Row N2 against a persistent MAP (Feature_Map::get_matches, feature_map.hpp:638-697): which detected plane of each frame
+ * belongs to which map plane.  The map planes live in world coordinates; their boundary polygons (grown over many frames by
+ * merge_union, so they may be large and have holes) stay on the device from cape_map_upload until the next upload or destroy.
+ * The map is ONE ordered list: the local map's planes first, then the staged map's, sharing one is-matched vector. */
+#define CAPE_MAP_MAX_PLANES 1024 /* map planes per upload */
+#define CAPE_MAP_MAX_RING 512    /* vertices of one map ring (the largest capacity tier of the intersection kernel) */
+#define CAPE_MAP_MAX_HOLES 8     /* interior rings per map plane */
+typedef struct cape_map_ring
+{
+    uint32_t vertex_offset, vertex_count; /* into the upload's vertex array (pairs of doubles), open ring (no repeated closing vertex) */
+} cape_map_ring;
+typedef struct cape_map_plane
+{
+    double normal[3], d;                    /* PlaneWorldCoordinates: unit normal, d in mm */
+    double x_axis[3], y_axis[3], center[3]; /* the WorldPolygon's frame (unit axes) */
+    uint32_t ring_first, ring_count;        /* rings[ring_first] = outer ring, the next ring_count - 1 = holes, in order */
+} cape_map_plane;
+typedef struct cape_frame_map_match
+{
+    int32_t n_map, n_cur;                 /* map planes of the call / kept planes of the frame */
+    uint32_t flags;                       /* CAPE_MATCH_EXACT_OVERFLOW: no match is reported for the frame, use the host class */
+    int32_t n_matched;                    /* map planes that took a plane of this frame */
+    int32_t seg_cur[CAPE_MAX_PLANES];     /* segment index of kept plane i, -1 beyond n_cur */
+    int32_t map_of[CAPE_MAX_PLANES];      /* map plane that took kept plane i, or -1 */
+} cape_frame_map_match;
+enum
+{
+    CAPE_MATCH_MAP_AREAS = 1u << 2 /* cape_match_map: also keep the dense inter-area table (tests, diagnostics) */
+};
+/* Copies the map to the device (host pointers; synchronous).  planes: n_planes entries; rings: n_rings; vertices: n_vertices
+ * (x, y) pairs in the planes' own frames.  The rings are re-oriented like the host class does (outer ring clockwise, holes
+ * counter-clockwise).  Waits for a cape_match_map still running on the previous map.  CAPE_ERR_INVALID_ARGUMENT: a ring of
+ * fewer than 3 vertices, an offset outside the arrays, ring_count == 0, a normal or axis whose norm is not 1 within DBL_EPSILON
+ * (what to_camera_space requires); CAPE_ERR_CAPACITY: beyond CAPE_MAP_MAX_* (simplify the polygon first).  n_planes == 0 is an
+ * empty map. */
+int cape_map_upload(cape_handle h, const cape_map_plane* planes, int32_t n_planes, const cape_map_ring* rings, int32_t n_rings,
+                    const double* vertices, int64_t n_vertices);
+/* MapPlane::find_matches (map_primitive.cpp:91-161) for map planes j = 0 .. n_map-1 in order against the kept planes of frames
+ * [0, n_frames) of the last cape_build_polygons (all kept planes of the frame's first record, up to CAPE_MAX_PLANES).  Per frame f:
+ * the map plane goes through plane_to_camera and its polygon (holes included) through to_camera_space with
+ * world_to_camera[f] (n_frames x 16 doubles in HOST memory, read before the call returns, row-major [R t; 0 0 0 1]; NULL =
+ * identity); a projected area <= 0 matches nothing; the gates |delta d| < 100 mm, |cos| > cos 20 deg come before any
+ * intersection; inter = I(detected, outer) - I(detected, hole_k) in order, clamped at 0; the greatest inter with
+ * inter / area(detected) >= 0.4f (halved with CAPE_MATCH_ADVANCED) wins, the lowest index on a tie, the `selectedIndex <= 0`
+ * quirk unless CAPE_MATCH_ALLOW_INDEX0, and a detected plane taken by map plane j is skipped by j+1 ...
+ * skip: NULL or n_frames x ceil(n_map / 32) words in HOST memory; bit j of frame f set = map plane j is not visited (the caller's
+ * `is_moving() or not is_visible(worldToCamera)`, feature_map.hpp:658, :683).  A frame is flagged CAPE_MATCH_EXACT_OVERFLOW
+ * (no match reported) if it continues in spill records, one of its output planes has CAPE_POLY_OVERFLOW, a pair exceeds the
+ * intersection kernel's capacities or its pairs do not fit the work list.  flags: CAPE_MATCH_ADVANCED, CAPE_MATCH_ALLOW_INDEX0,
+ * CAPE_MATCH_MAP_AREAS (CAPE_ERR_CAPACITY if the table would exceed 1 GiB).  Asynchronous on `stream`. */
+int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camera, const uint32_t* skip, uint32_t flags, void* stream);
+/* Synchronous copy of the last cape_match_map: frames (n_frames entries), match (n_frames x n_map, n_map being the map size of
+ * that cape_match_map call -- not of a map uploaded since: detected kept-plane index matched to map plane j, or -1) and, if the call
+ * kept it, inter_area (n_frames x n_map x CAPE_MAX_PLANES doubles, [f][j][i]
+ * mm^2; -1 where the pair was not gated or the map plane was skipped / has no positive projected area, NaN: capacity).  Either
+ * of match / inter_area may be NULL.  Refuses more frames than the last cape_match_map covered. */
+int cape_copy_map_matches(cape_handle h, int32_t n_frames, cape_frame_map_match* frames, int32_t* match, double* inter_area);
+
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
  * the `stream` argument of the calls below; destroy it before the handle. */

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <random>
 #include <string>
@@ -33,6 +34,7 @@ hipError_t launch_match(const MatchParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_pack(const PackParams& p, hipStream_t stream);
 hipError_t launch_polygons(const PolygonParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_polygons(const MatchPolygonParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -270,6 +272,26 @@ struct cape_handle_s
     bool matchPosesBusy = false;         // ... once it has been recorded
     cape_frame_match_exact* matchesExact = nullptr;
     unsigned* matchLists = nullptr; // counters (padded to 64 entries) + 4 lists of max_batch x 256 pairs
+    // N2 against a persistent map (cape_map_upload / cape_match_map): the map sized at upload, the rest allocated on first use
+    cape_map_plane* mapPlanes = nullptr;
+    cape_map_ring* mapRings = nullptr;
+    double* mapVertices = nullptr;
+    int mapPlanesCap = 0, mapRingsCap = 0;
+    int64_t mapVerticesCap = 0;
+    int mapN = -1;                       // planes of the uploaded map (-1: none yet)
+    double* mapPoses = nullptr;          // max_batch x 16 doubles, then max_batch x 32 skip words
+    void* mapStage = nullptr;            // pinned twin of mapPoses (the caller's poses / skip bits are copied there first)
+    hipEvent_t mapStageFree = nullptr;   // recorded behind the H2D copy out of the twin
+    bool mapStageBusy = false;
+    cape_frame_map_match* mapFrames = nullptr; // max_batch
+    int32_t* mapMatch = nullptr;         // max_batch x CAPE_MAP_MAX_PLANES
+    double* mapAreas = nullptr;          // CAPE_MATCH_MAP_AREAS: frames x n_map x CAPE_MAX_PLANES of the call
+    size_t mapAreasCap = 0;              // doubles
+    unsigned char* mapWork = nullptr;    // counters, frame ranges, gate masks, work list, its areas, the tier lists (map_work_layout)
+    size_t mapWorkCap = 0;               // entries of the work list
+    int mapMatchFrames = 0;              // frames of the last cape_match_map (0: none for the current batch)
+    int mapMatchN = 0;                   // map planes of that call
+    bool mapMatchAreas = false;          // ... and whether it kept the dense table
     int computeUnits = 0;           // CUs of the handle's device (queried on first use)
     int ldsLimit = 0; // LDS bytes one workgroup may use on this device (hipDeviceAttributeMaxSharedMemoryPerBlock)
     cape::StageAParams pa{};
@@ -327,6 +349,18 @@ void free_all(cape_handle_s* h)
     (void)hipFree(h->matchesExact);
     (void)hipFree(h->matchLists);
     (void)hipFree(h->matchPoses);
+    (void)hipFree(h->mapPlanes);
+    (void)hipFree(h->mapRings);
+    (void)hipFree(h->mapVertices);
+    (void)hipFree(h->mapPoses);
+    if (h->mapStage)
+        (void)hipHostFree(h->mapStage);
+    if (h->mapStageFree)
+        (void)hipEventDestroy(h->mapStageFree);
+    (void)hipFree(h->mapFrames);
+    (void)hipFree(h->mapMatch);
+    (void)hipFree(h->mapAreas);
+    (void)hipFree(h->mapWork);
     if (h->matchPosesStage)
         (void)hipHostFree(h->matchPosesStage);
     if (h->matchPosesFree)
@@ -1275,6 +1309,7 @@ static int extract_impl(cape_handle h, const float* depth_dev, const uint16_t* d
     h->logDone = 0;
     h->polygonFrames = 0; // the polygons on the device belong to the previous batch
     h->matchExactFrames = 0; // and so do the polygon matches
+    h->mapMatchFrames = 0;   // and the map matches
     if (n_frames == 0)
         return CAPE_OK;
     CAPE_ON_DEVICE(h); // the handle's device, whatever the calling thread had current
@@ -2275,6 +2310,265 @@ int cape_copy_polygon_matches(cape_handle h, int32_t n_frames, cape_frame_match_
     CAPE_ON_DEVICE(h);
     CAPE_HIP_TRY(drain_handle(h));
     CAPE_HIP_TRY(hipMemcpy(out, h->matchesExact, (size_t)n_frames * sizeof(cape_frame_match_exact), hipMemcpyDeviceToHost));
+    return CAPE_OK;
+}
+
+// ---- N2 against a persistent map ---------------------------------------------------------------------------------------------
+
+namespace {
+// the work buffers of cape_match_map, one allocation: counters, per-frame ranges, the gate masks, the work list, its areas, the
+// tier lists
+struct MapWorkLayout
+{
+    size_t counts, ranges, masks, work, area, tiers, total;
+};
+static MapWorkLayout map_work_layout(int maxBatch, size_t cap)
+{
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    MapWorkLayout l;
+    l.counts = 0;
+    l.ranges = up(16 * sizeof(unsigned));
+    l.masks = l.ranges + up((size_t)maxBatch * sizeof(uint2));
+    l.work = l.masks + up((size_t)maxBatch * CAPE_MAP_MAX_PLANES * sizeof(unsigned long long));
+    l.area = l.work + up(cap * sizeof(unsigned long long));
+    l.tiers = l.area + up(cap * sizeof(double));
+    l.total = l.tiers + up(3 * cap * sizeof(unsigned));
+    return l;
+}
+constexpr size_t kMapWorkMax = (size_t)1 << 24;             // entries of the work list at most (448 MB of buffers)
+constexpr size_t kMapAreasBudget = (size_t)1 << 30;         // bytes of the dense inter-area table at most
+static bool unit_norm(const double* v) // double_equal(norm, 1) as to_camera_space requires (polygon_coordinates.cpp:144-151)
+{
+    return std::abs(std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) - 1.0) <= std::numeric_limits<double>::epsilon();
+}
+static double ring_area_signed_host(const double* r, uint32_t n) // the host class's shoelace, same order
+{
+    double s = 0;
+    for (uint32_t i = 0, j = n - 1; i < n; j = i++)
+        s += (r[2 * j] * r[2 * i + 1] - r[2 * i] * r[2 * j + 1]);
+    return 0.5 * s;
+}
+} // namespace
+
+int cape_map_upload(cape_handle h, const cape_map_plane* planes, int32_t n_planes, const cape_map_ring* rings, int32_t n_rings,
+                    const double* vertices, int64_t n_vertices)
+{
+    if (!h || n_planes < 0 || n_rings < 0 || n_vertices < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative count");
+    if (n_planes > CAPE_MAP_MAX_PLANES)
+        return fail(CAPE_ERR_CAPACITY, "more map planes than CAPE_MAP_MAX_PLANES");
+    if ((n_planes > 0 && !planes) || (n_rings > 0 && !rings) || (n_vertices > 0 && !vertices))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null array");
+    // validation, then the rings re-oriented like the host class does and laid out plane by plane
+    std::vector<cape_map_plane> P(planes, planes + n_planes);
+    std::vector<cape_map_ring> R;
+    std::vector<double> V;
+    for (int32_t j = 0; j < n_planes; ++j)
+    {
+        cape_map_plane& M = P[j];
+        if (M.ring_count == 0 || (uint64_t)M.ring_first + M.ring_count > (uint64_t)n_rings)
+            return fail(CAPE_ERR_INVALID_ARGUMENT, "map plane without an outer ring or with rings outside the ring array");
+        if (M.ring_count > 1u + CAPE_MAP_MAX_HOLES)
+            return fail(CAPE_ERR_CAPACITY, "more holes than CAPE_MAP_MAX_HOLES");
+        if (!unit_norm(M.normal) || !unit_norm(M.x_axis) || !unit_norm(M.y_axis))
+            return fail(CAPE_ERR_INVALID_ARGUMENT, "map plane normal or polygon axis is not unit");
+        const uint32_t first = (uint32_t)R.size();
+        for (uint32_t k = 0; k < M.ring_count; ++k)
+        {
+            const cape_map_ring in = rings[M.ring_first + k];
+            if (in.vertex_count < 3 || (uint64_t)in.vertex_offset + in.vertex_count > (uint64_t)n_vertices)
+                return fail(CAPE_ERR_INVALID_ARGUMENT, "map ring of fewer than 3 vertices or outside the vertex array");
+            if (in.vertex_count > CAPE_MAP_MAX_RING)
+                return fail(CAPE_ERR_CAPACITY, "map ring longer than CAPE_MAP_MAX_RING (simplify the polygon first)");
+            const size_t at = V.size();
+            V.insert(V.end(), vertices + 2 * (size_t)in.vertex_offset, vertices + 2 * ((size_t)in.vertex_offset + in.vertex_count));
+            // outer ring clockwise (OpenRing constructor), holes counter-clockwise (add_hole)
+            const double sa = ring_area_signed_host(V.data() + at, in.vertex_count);
+            if (k == 0 ? sa > 0 : sa < 0)
+                for (uint32_t a = 0, b = in.vertex_count - 1; a < b; ++a, --b)
+                {
+                    std::swap(V[at + 2 * a], V[at + 2 * b]);
+                    std::swap(V[at + 2 * a + 1], V[at + 2 * b + 1]);
+                }
+            R.push_back(cape_map_ring {(uint32_t)(at / 2), in.vertex_count});
+        }
+        M.ring_first = first;
+    }
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h)); // a cape_match_map in flight still reads the old map
+    if ((int)P.size() > h->mapPlanesCap)
+    {
+        (void)hipFree(h->mapPlanes);
+        h->mapPlanes = nullptr;
+        h->mapPlanesCap = 0;
+        CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapPlanes), P.size() * sizeof(cape_map_plane)));
+        h->mapPlanesCap = (int)P.size();
+    }
+    if ((int)R.size() > h->mapRingsCap)
+    {
+        (void)hipFree(h->mapRings);
+        h->mapRings = nullptr;
+        h->mapRingsCap = 0;
+        CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapRings), R.size() * sizeof(cape_map_ring)));
+        h->mapRingsCap = (int)R.size();
+    }
+    if ((int64_t)(V.size() / 2) > h->mapVerticesCap)
+    {
+        (void)hipFree(h->mapVertices);
+        h->mapVertices = nullptr;
+        h->mapVerticesCap = 0;
+        CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapVertices), V.size() * sizeof(double)));
+        h->mapVerticesCap = (int64_t)(V.size() / 2);
+    }
+    h->mapN = -1; // (no map until the copies are through)
+    if (!P.empty())
+    {
+        CAPE_HIP_TRY(hipMemcpy(h->mapPlanes, P.data(), P.size() * sizeof(cape_map_plane), hipMemcpyHostToDevice));
+        CAPE_HIP_TRY(hipMemcpy(h->mapRings, R.data(), R.size() * sizeof(cape_map_ring), hipMemcpyHostToDevice));
+        CAPE_HIP_TRY(hipMemcpy(h->mapVertices, V.data(), V.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    h->mapN = n_planes;
+    return CAPE_OK;
+}
+
+int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camera, const uint32_t* skip, uint32_t flags, void* stream_)
+{
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    if (n_frames > h->polygonFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
+    if (h->mapN < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
+    const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0;
+    const size_t areaDoubles = (size_t)n_frames * h->mapN * CAPE_MAX_PLANES;
+    if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
+        return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer frames per call, or no CAPE_MATCH_MAP_AREAS)");
+    h->mapMatchFrames = 0;
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    const int B = h->cfg.max_batch;
+    const int skipWords = (h->mapN + 31) / 32;
+    const size_t stageBytes = (size_t)B * 16 * sizeof(double) + (size_t)B * (CAPE_MAP_MAX_PLANES / 32) * sizeof(uint32_t);
+    const size_t cap = std::min((size_t)B * (size_t)std::max(h->mapN, 1) * CAPE_MAX_PLANES, kMapWorkMax);
+    const MapWorkLayout lay = map_work_layout(B, cap);
+    if (!h->mapFrames)
+        CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapFrames), (size_t)B * sizeof(cape_frame_map_match)));
+    if (!h->mapMatch)
+        CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapMatch), (size_t)B * CAPE_MAP_MAX_PLANES * sizeof(int32_t)));
+    if (!h->mapPoses)
+        CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapPoses), stageBytes));
+    if (!h->mapStage)
+        CAPE_HIP_TRY(hipHostMalloc(&h->mapStage, stageBytes, hipHostMallocDefault));
+    if (!h->mapStageFree)
+        CAPE_HIP_TRY(hipEventCreateWithFlags(&h->mapStageFree, hipEventDisableTiming));
+    if (h->mapWorkCap < cap || (keepAreas && h->mapAreasCap < areaDoubles))
+    {
+        CAPE_HIP_TRY(drain_handle(h)); // an earlier call may still be working in them
+        if (h->mapWorkCap < cap)
+        {
+            (void)hipFree(h->mapWork);
+            h->mapWork = nullptr;
+            h->mapWorkCap = 0;
+            CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapWork), lay.total));
+            h->mapWorkCap = cap;
+        }
+        if (keepAreas && h->mapAreasCap < areaDoubles)
+        {
+            (void)hipFree(h->mapAreas);
+            h->mapAreas = nullptr;
+            h->mapAreasCap = 0;
+            CAPE_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->mapAreas), areaDoubles * sizeof(double)));
+            h->mapAreasCap = areaDoubles;
+        }
+    }
+    if (h->computeUnits <= 0)
+    {
+        hipDeviceProp_t prop;
+        h->computeUnits = hipGetDeviceProperties(&prop, h->cfg.device) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    // the poses (identity where none are given: the statements stay those of a pose) and the skip bits travel through the pinned
+    // twin, like cape_match_polygons_pose: any host pointer, read before the call returns, no implicit stream sync
+    if (h->mapStageBusy)
+        CAPE_HIP_TRY(hipEventSynchronize(h->mapStageFree));
+    double* poseStage = static_cast<double*>(h->mapStage);
+    uint32_t* skipStage = reinterpret_cast<uint32_t*>(poseStage + (size_t)B * 16);
+    if (world_to_camera)
+        std::memcpy(poseStage, world_to_camera, (size_t)n_frames * 16 * sizeof(double));
+    else
+        for (int f = 0; f < n_frames; ++f)
+            for (int k = 0; k < 16; ++k)
+                poseStage[16 * f + k] = (k % 5 == 0) ? 1.0 : 0.0;
+    CAPE_HIP_TRY(hipMemcpyAsync(h->mapPoses, poseStage, (size_t)n_frames * 16 * sizeof(double), hipMemcpyHostToDevice, stream));
+    uint32_t* skipDev = reinterpret_cast<uint32_t*>(h->mapPoses + (size_t)B * 16);
+    if (skip && skipWords > 0)
+    {
+        std::memcpy(skipStage, skip, (size_t)n_frames * skipWords * sizeof(uint32_t));
+        CAPE_HIP_TRY(hipMemcpyAsync(skipDev, skipStage, (size_t)n_frames * skipWords * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    }
+    CAPE_HIP_TRY(hipEventRecord(h->mapStageFree, stream));
+    h->mapStageBusy = true;
+    cape::MatchMapParams p;
+    p.records = h->records;
+    p.polygons = h->polygons;
+    p.vertices = reinterpret_cast<const double2*>(h->polyVertices);
+    p.boundaryCapacity = h->boundaryCap;
+    p.mapPlanes = h->mapPlanes;
+    p.mapRings = h->mapRings;
+    p.mapVertices = reinterpret_cast<const double2*>(h->mapVertices);
+    p.nMap = h->mapN;
+    p.skipWords = skipWords;
+    p.poses = h->mapPoses;
+    p.skip = (skip && skipWords > 0) ? skipDev : nullptr;
+    p.frames = h->mapFrames;
+    p.match = h->mapMatch;
+    p.areas = keepAreas ? h->mapAreas : nullptr;
+    p.counts = reinterpret_cast<unsigned*>(h->mapWork + lay.counts);
+    p.frameRange = reinterpret_cast<uint2*>(h->mapWork + lay.ranges);
+    p.gateMasks = reinterpret_cast<unsigned long long*>(h->mapWork + lay.masks);
+    p.work = reinterpret_cast<unsigned long long*>(h->mapWork + lay.work);
+    p.workArea = reinterpret_cast<double*>(h->mapWork + lay.area);
+    p.tierLists = reinterpret_cast<unsigned*>(h->mapWork + lay.tiers);
+    p.workCapacity = cap;
+    p.computeUnits = h->computeUnits;
+    p.ldsLimitBytes = h->ldsLimit;
+    p.flags = flags;
+    p.minCosAngle = std::abs(std::cos(20.0 * M_PI / 180.0));
+    p.maxDistance = 100.0;
+    const double planeMinimalOverlap = static_cast<double>(0.4f);
+    p.minOverlap = (flags & CAPE_MATCH_ADVANCED) ? planeMinimalOverlap / 2 : planeMinimalOverlap;
+    CAPE_HIP_TRY(cape::launch_match_map(p, n_frames, stream));
+    h->mapMatchFrames = n_frames;
+    h->mapMatchN = h->mapN;
+    h->mapMatchAreas = keepAreas;
+    return CAPE_OK;
+}
+
+int cape_copy_map_matches(cape_handle h, int32_t n_frames, cape_frame_map_match* frames, int32_t* match, double* inter_area)
+{
+    if (!h || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    if (n_frames > h->mapMatchFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_match_map of the current batch");
+    if (inter_area && n_frames > 0 && !h->mapMatchAreas)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_match_map did not keep the inter-area table (CAPE_MATCH_MAP_AREAS)");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    if (frames)
+        CAPE_HIP_TRY(hipMemcpy(frames, h->mapFrames, (size_t)n_frames * sizeof(cape_frame_map_match), hipMemcpyDeviceToHost));
+    const size_t n = (size_t)n_frames * h->mapMatchN;
+    if (match && n > 0)
+        CAPE_HIP_TRY(hipMemcpy(match, h->mapMatch, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (inter_area && n > 0)
+        CAPE_HIP_TRY(hipMemcpy(inter_area, h->mapAreas, n * CAPE_MAX_PLANES * sizeof(double), hipMemcpyDeviceToHost));
     return CAPE_OK;
 }
 

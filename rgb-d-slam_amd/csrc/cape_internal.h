@@ -214,6 +214,37 @@ struct MatchPolygonParams
     const double* poses = nullptr; // cape_match_polygons_pose: frames x 16, row-major [R t; 0 0 0 1] from camera f-1 to camera f; null = identity
 };
 
+// N2 against a persistent map (cape_match_map.hip)
+struct MatchMapParams
+{
+    const cape_frame_record* records;
+    const cape_polygon* polygons; // frames x CAPE_MAX_PLANES
+    const double2* vertices;      // frames x boundaryCapacity
+    int boundaryCapacity;
+    // the map (cape_map_upload; rings already re-oriented)
+    const cape_map_plane* mapPlanes;
+    const cape_map_ring* mapRings;
+    const double2* mapVertices;
+    int nMap, skipWords;           // skipWords = ceil(nMap / 32)
+    const double* poses;           // frames x 16 (null = identity)
+    const uint32_t* skip;          // frames x skipWords (null = none skipped)
+    cape_frame_map_match* frames;
+    int32_t* match;                // frames x nMap
+    double* areas;                 // frames x nMap x CAPE_MAX_PLANES, or null (CAPE_MATCH_MAP_AREAS off)
+    unsigned long long* work;      // workCapacity entries (frame << 32) | (j << 8) | i, per frame in (j, i) order
+    double* workArea;              // the area of each entry
+    unsigned* tierLists;           // 3 x workCapacity: indices into `work` handed to tiers 1..3
+    unsigned* counts;              // 16 words: [0..1] entries reserved (64-bit), [2..4] entries on the lists of tiers 1..3,
+                                   // [5..7] tickets drawn by tiers 1..3
+    uint2* frameRange;             // frames: (first entry, entries) of the frame's pairs
+    unsigned long long* gateMasks; // frames x nMap: the gated kept planes of each visited map plane with a positive projected area
+    size_t workCapacity;
+    int computeUnits;
+    int ldsLimitBytes;
+    uint32_t flags;
+    double minCosAngle, maxDistance, minOverlap; // as MatchParams
+};
+
 // multi-GPU gather: device-side packing of the ragged primitive lists (cape_gather.hip)
 struct PackParams
 {

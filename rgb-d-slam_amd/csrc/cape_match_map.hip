@@ -1,0 +1,530 @@
+// Row N2 against a persistent MAP: Feature_Map::get_matches (reference src/map_management/feature_map.hpp:638-697) -- every map
+// plane in turn runs MapPlane::find_matches (map_primitive.cpp:91-161) against the detected planes of a frame, seen through the
+// frame's worldToCamera, a detected plane taken by an earlier map plane being skipped by the later ones.  The map planes live
+// in world coordinates and their polygons (grown by merge_union) may have holes; they stay on the device between batches
+// (cape_map_upload).
+//
+//   cape_map_gate_kernel         : one wavefront per frame, lanes over map planes: plane_to_camera of map plane j
+//        (plane_coordinates.cpp:20-24), the gates is_distance_similar / is_normal_similar (shape_primitives.cpp:66-86) against
+//        every kept plane i of the frame; for a map plane with a gated pair, the area of its polygon seen from the camera
+//        (to_camera_space, polygon_coordinates.cpp:135-165, holes included) -- <= 0: it matches nothing and lists no pair --
+//        and the work list of the gated (frame, j, i) triples, per frame in (j, i) order.
+//   cape_map_inter_kernel<TIER>  : persistent waves over the work list, one triple at a time: every ring of the map polygon goes
+//        through to_camera_space and is projected into the detected plane's frame (Polygon::project) and
+//        inter = I(detected, outer) - I(detected, hole_k) in order, clamped at 0 -- Polygon::inter_area of the host class
+//        (host/boundary_polygon.cpp: polygons_inter_area).  The capacity tiers and the intersection are cape_ring_area.h's.
+//   cape_map_select_kernel       : one wavefront per frame: map plane after map plane in order, lanes over the gated pairs of
+//        the plane; wave arg-max of the area above the overlap threshold (lowest index on a tie), the `selectedIndex <= 0`
+//        quirk, the is-matched mask.
+//
+// + - x / and comparisons only, in the host class's association order (-ffp-contract=off): the areas are compared BIT FOR BIT
+// with the host twin cape_host_match_map (tests/test_gpu_map_match.py).
+#include <hip/hip_runtime.h>
+
+#include "cape_internal.h"
+#include "cape_ring_area.h"
+#include "cape_wave.h"
+
+namespace cape {
+
+namespace {
+
+constexpr int kMapGateFrames = 4;   // frames (waves) of a gate workgroup
+constexpr int kMapSelectFrames = 4; // frames (waves) of a select workgroup
+constexpr unsigned long long kNoEntry = ~0ull; // a slot of the work list reserved by a frame that did not fit
+
+__device__ __forceinline__ unsigned long long pack_map_pair(int frame, int j, int i)
+{
+    return ((unsigned long long)(unsigned)frame << 32) | ((unsigned long long)(unsigned)j << 8) | (unsigned long long)(unsigned)i;
+}
+
+// map plane j seen from the frame's camera: PlaneWorldCoordinates::to_camera_coordinates with the plane matrix [R 0; -t^T R 1]
+// (camera_transformation.cpp:53-71); the PlaneCameraCoordinates constructor normalises the rotated normal (host: utils::plane_to_camera)
+__device__ __forceinline__ void plane_to_camera(const double* T, const cape_map_plane& M, double pn[3], double& pd)
+{
+    const double n0 = M.normal[0], n1 = M.normal[1], n2 = M.normal[2];
+    const double r0 = (T[0] * n0 + T[1] * n1) + T[2] * n2, r1 = (T[4] * n0 + T[5] * n1) + T[6] * n2, r2 = (T[8] * n0 + T[9] * n1) + T[10] * n2;
+    const double t0 = T[3], t1 = T[7], t2 = T[11];
+    const double m0 = -((t0 * T[0] + t1 * T[4]) + t2 * T[8]), m1 = -((t0 * T[1] + t1 * T[5]) + t2 * T[9]), m2 = -((t0 * T[2] + t1 * T[6]) + t2 * T[10]);
+    pd = ((m0 * n0 + m1 * n1) + m2 * n2) + M.d;
+    const double nn = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
+    pn[0] = r0, pn[1] = r1, pn[2] = r2;
+    if (nn > 0)
+        pn[0] = r0 / nn, pn[1] = r1 / nn, pn[2] = r2 / nn;
+}
+
+// to_camera_space of the map polygon's frame (polygon_coordinates.cpp:135-165): the centre through the transform, the axes through
+// its rotation, re-normalised -- the statements of the pose path of cape_match_polygon.hip
+struct CameraFrame
+{
+    double qc[3], qx[3], qy[3]; // the map polygon's own frame
+    double nc[3], nx[3], ny[3]; // ... seen from the camera
+};
+__device__ __forceinline__ CameraFrame camera_frame(const double* Tm, const cape_map_plane& M)
+{
+    CameraFrame F;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        F.qc[r] = M.center[r], F.qx[r] = M.x_axis[r], F.qy[r] = M.y_axis[r];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+    {
+        F.nc[r] = ((Tm[4 * r] * F.qc[0] + Tm[4 * r + 1] * F.qc[1]) + Tm[4 * r + 2] * F.qc[2]) + Tm[4 * r + 3];
+        F.nx[r] = (Tm[4 * r] * F.qx[0] + Tm[4 * r + 1] * F.qx[1]) + Tm[4 * r + 2] * F.qx[2];
+        F.ny[r] = (Tm[4 * r] * F.qy[0] + Tm[4 * r + 1] * F.qy[1]) + Tm[4 * r + 2] * F.qy[2];
+    }
+    const double lx = sqrt((F.nx[0] * F.nx[0] + F.nx[1] * F.nx[1]) + F.nx[2] * F.nx[2]), ly = sqrt((F.ny[0] * F.ny[0] + F.ny[1] * F.ny[1]) + F.ny[2] * F.ny[2]);
+    if (lx > 0)
+        F.nx[0] /= lx, F.nx[1] /= lx, F.nx[2] /= lx;
+    if (ly > 0)
+        F.ny[0] /= ly, F.ny[1] /= ly, F.ny[2] /= ly;
+    return F;
+}
+
+// one vertex of a map ring seen from the camera, in the camera-space frame (transform_boundary, polygon.cpp:430-451)
+__device__ __forceinline__ double2 to_camera_vertex(const double* Tm, const CameraFrame& F, double2 q)
+{
+    const double X = F.qc[0] + q.x * F.qx[0] + q.y * F.qy[0], Y = F.qc[1] + q.x * F.qx[1] + q.y * F.qy[1], Z = F.qc[2] + q.x * F.qx[2] + q.y * F.qy[2];
+    const double mx = ((Tm[0] * X + Tm[1] * Y) + Tm[2] * Z) + Tm[3], my = ((Tm[4] * X + Tm[5] * Y) + Tm[6] * Z) + Tm[7],
+                 mz = ((Tm[8] * X + Tm[9] * Y) + Tm[10] * Z) + Tm[11];
+    const double dx = mx - F.nc[0], dy = my - F.nc[1], dz = mz - F.nc[2];
+    return make_double2((F.nx[0] * dx + F.nx[1] * dy) + F.nx[2] * dz, (F.ny[0] * dx + F.ny[1] * dy) + F.ny[2] * dz);
+}
+
+// Polygon::area of the map polygon seen from the camera > 0 (one lane, sequentially): the outer ring's |signed area| minus the
+// holes', each ring measured in the orientation the host class gives it (OpenRing constructor / add_hole reverse a ring, and the
+// area of the reversed ring is summed in the reversed order)
+__device__ inline bool projected_area_positive(const double* Tm, const MatchMapParams& p, int j)
+{
+    const cape_map_plane& M = p.mapPlanes[j];
+    const CameraFrame F = camera_frame(Tm, M);
+    double area = 0.0;
+    for (int k = 0; k < (int)M.ring_count; ++k)
+    {
+        const cape_map_ring R = p.mapRings[M.ring_first + k];
+        const double2* src = p.mapVertices + R.vertex_offset;
+        const int n = (int)R.vertex_count;
+        double s = 0;
+        double2 prev = to_camera_vertex(Tm, F, src[n - 1]);
+        for (int i = 0; i < n; ++i)
+        {
+            const double2 cur = to_camera_vertex(Tm, F, src[i]);
+            s += (prev.x * cur.y - cur.x * prev.y);
+            prev = cur;
+        }
+        double sa = 0.5 * s;
+        if (k == 0 ? sa > 0 : sa < 0)
+        {
+            s = 0;
+            prev = to_camera_vertex(Tm, F, src[0]); // (the reversed ring's last vertex)
+            for (int i = 0; i < n; ++i)
+            {
+                const double2 cur = to_camera_vertex(Tm, F, src[n - 1 - i]);
+                s += (prev.x * cur.y - cur.x * prev.y);
+                prev = cur;
+            }
+            sa = 0.5 * s;
+        }
+        area = k == 0 ? fabs(sa) : area - fabs(sa);
+    }
+    return area > 0.0;
+}
+
+} // namespace
+
+// One wavefront per frame, lanes over the map planes (64 at a time): the detected planes of the frame are read once (lane i: kept
+// plane i) and broadcast; bit i of a lane's mask = pair (j, i) passes the gates.  Pass 1 counts the pairs (one atomic per
+// workgroup reserves the frame's slots) and keeps the masks, pass 2 writes the triples in (j, i) order.
+__global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_kernel(MatchMapParams p, int nFrames)
+{
+    __shared__ unsigned s_count[kMapGateFrames];
+    __shared__ unsigned long long s_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frameRaw = blockIdx.x * kMapGateFrames + wave;
+    const bool live = frameRaw < nFrames;
+    const int frame = live ? frameRaw : nFrames - 1; // (idle waves of the last workgroup shadow a real frame and store nothing)
+    cape_frame_map_match& out = p.frames[frame];
+    const cape_frame_record& rec = p.records[frame];
+    const cape_polygon* pol = p.polygons + (size_t)frame * CAPE_MAX_PLANES;
+    int seg = -1;
+    bool hostOnly = false;
+    const int nCur = valid_planes(rec, pol, lane, seg, hostOnly);
+    const bool fits = !hostOnly;
+    double cn0 = 0, cn1 = 0, cn2 = 0, cd = 0;
+    if (seg >= 0)
+    {
+        const cape_plane_segment& S = rec.segments[seg];
+        cn0 = S.out_normal[0], cn1 = S.out_normal[1], cn2 = S.out_normal[2], cd = S.d;
+    }
+    const double* T = p.poses + (size_t)frame * 16;
+    const uint32_t* skip = p.skip ? p.skip + (size_t)frame * p.skipWords : nullptr;
+    // the gated detected planes of map plane j (lane's), as a mask over i
+    auto gate = [&](int j) -> unsigned long long {
+        if (!fits || j >= p.nMap || (skip && ((skip[j >> 5] >> (j & 31)) & 1u)))
+            return 0ull;
+        double qn[3], qd;
+        plane_to_camera(T, p.mapPlanes[j], qn, qd);
+        unsigned long long m = 0ull;
+        for (int i = 0; i < nCur; ++i)
+        {
+            const double sn0 = readlane_f64(cn0, i), sn1 = readlane_f64(cn1, i), sn2 = readlane_f64(cn2, i), sd = readlane_f64(cd, i);
+            const double cosAngle = (sn0 * qn[0] + sn1 * qn[1]) + sn2 * qn[2];
+            if (fabs(sd - qd) < p.maxDistance && fabs(cosAngle) > p.minCosAngle)
+                m |= 1ull << i;
+        }
+        // a map plane whose projected polygon has no positive area matches nothing (map_primitive.cpp:105-106): its pairs are not
+        // listed (their areas stay -1)
+        if (m && !projected_area_positive(T, p, j))
+            m = 0ull;
+        return m;
+    };
+    unsigned long long* masks = p.gateMasks + (size_t)frame * p.nMap;
+    unsigned myCount = 0;
+    for (int jb = 0; jb < p.nMap; jb += 64)
+    {
+        const int j = jb + lane;
+        const unsigned long long m = gate(j);
+        if (live && j < p.nMap)
+            masks[j] = m;
+        myCount += (unsigned)wave_sum_i32(__popcll(m));
+    }
+    if (lane == 0)
+        s_count[wave] = live ? myCount : 0u;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        unsigned total = 0;
+        for (int w = 0; w < kMapGateFrames; ++w)
+        {
+            const unsigned c = s_count[w];
+            s_count[w] = total;
+            total += c;
+        }
+        s_base = total ? atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)total) : 0ull;
+    }
+    __syncthreads();
+    if (!live)
+        return;
+    const unsigned long long first = s_base + s_count[wave];
+    const bool listed = first + myCount <= p.workCapacity;
+    if (lane == 0)
+    {
+        out.n_map = p.nMap;
+        out.n_cur = nCur;
+        out.flags = (fits && listed) ? 0u : (uint32_t)CAPE_MATCH_EXACT_OVERFLOW;
+        out.n_matched = 0;
+        p.frameRange[frame] = make_uint2((unsigned)(listed ? first : 0ull), listed ? myCount : 0u);
+    }
+    out.seg_cur[lane] = lane < nCur ? seg : -1;
+    out.map_of[lane] = -1;
+    if (!listed)
+    {
+        // the slots the frame reserved inside the list are marked empty: the intersection kernel skips them
+        for (unsigned long long k = first + lane; k < first + myCount && k < p.workCapacity; k += 64)
+            p.work[k] = kNoEntry;
+    }
+    unsigned long long at = first;
+    for (int jb = 0; jb < p.nMap; jb += 64)
+    {
+        const int j = jb + lane;
+        const unsigned long long m = j < p.nMap ? masks[j] : 0ull;
+        if (j < p.nMap)
+            p.match[(size_t)frame * p.nMap + j] = -1;
+        const int c = __popcll(m);
+        const int incl = wave_scan_i32(c);
+        if (listed)
+        {
+            unsigned long long w = at + (unsigned)(incl - c);
+            for (unsigned long long mm = m; mm; mm &= mm - 1, ++w)
+            {
+                p.work[w] = pack_map_pair(frame, j, __ffsll((long long)mm) - 1);
+                p.workArea[w] = nan_code(kNanPending);
+            }
+        }
+        at += (unsigned)__builtin_amdgcn_readlane(incl, 63);
+        if (p.areas)
+        {
+            // the dense table: -1 where the pair is not gated (the intersection kernel overwrites the gated ones; a pair that is
+            // never intersected -- a frame beyond the list -- keeps the NaN)
+            const int rows = p.nMap - jb < 64 ? p.nMap - jb : 64;
+            for (int l = 0; l < rows; ++l)
+            {
+                const unsigned long long ml = readlane_u64(m, l);
+                p.areas[((size_t)frame * p.nMap + jb + l) * CAPE_MAX_PLANES + lane] = ((ml >> lane) & 1ull) ? nan_code(kNanPending) : -1.0;
+            }
+        }
+    }
+}
+
+// Persistent waves over the work list (tier 0) or a tier's list of indices into it (tiers 1..3).  A triple beyond this tier's
+// capacities moves to the next tier's list when that one is larger in the resource that ran out; otherwise its area stays a NaN
+// that names the resource.
+template <int TIER>
+__global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inter_kernel(MatchMapParams p, int ldsPerWave)
+{
+    using T = Tier<TIER>;
+    constexpr bool kHasNext = TIER + 1 < kTiers;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr bool kCoop = T::kCoop;
+    const int tid = kCoop ? (int)threadIdx.x : lane;
+    constexpr int kStride = kCoop ? 256 : 64;
+    unsigned char* smem = smem_all + (kCoop ? (size_t)0 : (size_t)wave * ldsPerWave);
+    MpLds L;
+    L.ringCap = T::kRing;
+    L.ringA = reinterpret_cast<double2*>(smem);
+    L.ringB = L.ringA + T::kRing;
+    L.ea = reinterpret_cast<Edge*>(L.ringB + T::kRing);
+    L.eb = L.ea + T::kRing;
+    L.xs = reinterpret_cast<double*>(L.eb + T::kRing);
+    L.terms = L.xs + T::kXs;
+    L.by = L.terms + 64 * T::kStack;
+    L.elo = reinterpret_cast<int*>(L.by + 128 * T::kStack);
+    L.ehi = L.elo + 2 * T::kRing;
+    L.pre = L.ehi + 2 * T::kRing;
+    L.cnt = L.pre + 2 * T::kRing + 2;
+    L.bk = reinterpret_cast<unsigned short*>(L.cnt + 128);
+    L.inc = L.bk + 128 * T::kStack;
+    L.sidx = reinterpret_cast<unsigned char*>(L.inc + 128 * T::kStack);
+    L.sh = reinterpret_cast<int*>(smem + ldsPerWave - 32);
+    const size_t cap = p.workCapacity;
+    const unsigned long long reserved = *reinterpret_cast<const unsigned long long*>(p.counts);
+    const unsigned long long count = TIER == 0 ? (reserved < cap ? reserved : cap) : (unsigned long long)p.counts[1 + TIER];
+    const unsigned* list = TIER == 0 ? nullptr : p.tierLists + (size_t)(TIER - 1) * cap;
+    // tier 0: a fixed stride over the (many, short) triples; the later tiers draw tickets (few triples of very unequal cost)
+    auto next_index = [&](unsigned long long prev, bool first) -> unsigned long long {
+        if (kCoop)
+        {
+            if (threadIdx.x == 0)
+                L.sh[7] = (int)(TIER > 0 ? atomicAdd(&p.counts[4 + TIER], 1u) : (unsigned)(first ? blockIdx.x : prev + gridDim.x));
+            __syncthreads();
+            const unsigned t = (unsigned)L.sh[7];
+            __syncthreads();
+            return t;
+        }
+        if (TIER == 0)
+            return first ? (unsigned long long)blockIdx.x * T::kWavesPerGroup + wave : prev + (unsigned long long)gridDim.x * T::kWavesPerGroup;
+        unsigned t = 0;
+        if (lane == 0)
+            t = atomicAdd(&p.counts[4 + TIER], 1u);
+        return (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+    };
+    auto sync = [&]() {
+        if (kCoop)
+            __syncthreads();
+        else
+            CAPE_MP_SYNC();
+    };
+    for (unsigned long long t = next_index(0ull, true); t < count; t = next_index(t, false))
+    {
+        const size_t idx = TIER == 0 ? (size_t)t : (size_t)list[t];
+        const unsigned long long e = p.work[idx];
+        if (e == kNoEntry)
+            continue;
+        const int frame = (int)(e >> 32), j = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
+        const int si = p.frames[frame].seg_cur[i];
+        const cape_polygon& PS = p.polygons[(size_t)frame * CAPE_MAX_PLANES + si]; // detected polygon
+        const cape_map_plane& M = p.mapPlanes[j];
+        const int na = (int)PS.vertex_count, nRings = (int)M.ring_count;
+        int nbMax = 0;
+        for (int k = 0; k < nRings; ++k)
+        {
+            const int nb = (int)p.mapRings[M.ring_first + k].vertex_count;
+            nbMax = nb > nbMax ? nb : nbMax;
+        }
+        double result;
+        if (na > T::kRing || nbMax > T::kRing)
+            result = nan_code(kNanRing);
+        else
+        {
+            const double2* vertsC = p.vertices + (size_t)frame * p.boundaryCapacity + PS.vertex_offset;
+            for (int v = tid; v < na; v += kStride)
+                L.ringA[v] = vertsC[v];
+            // to_camera_space (polygon_coordinates.cpp:135-165): the centre through the transform, the axes through its rotation,
+            // re-normalised -- the statements of the pose path of cape_match_polygon.hip
+            const double* Tm = p.poses + (size_t)frame * 16;
+            const CameraFrame F = camera_frame(Tm, M);
+            const double* nc = F.nc;
+            const double* nx = F.nx;
+            const double* ny = F.ny;
+            // a ring in reverse order (lane v swaps v and n - 1 - v)
+            auto reverse_b = [&](int n) {
+                for (int v = tid; v < n / 2; v += kStride)
+                {
+                    const double2 a = L.ringB[v], b = L.ringB[n - 1 - v];
+                    L.ringB[v] = b;
+                    L.ringB[n - 1 - v] = a;
+                }
+                sync();
+            };
+            // the orientation the host class gives a ring: the outer one clockwise (OpenRing constructor), holes counter-clockwise
+            // (add_hole)
+            // (every lane reads the whole ring before any lane of the carve rewrites it)
+            auto orient_b = [&](int n, bool hole) {
+                const double s = ring_area_signed(L.ringB, n);
+                sync();
+                if (hole ? s < 0 : s > 0)
+                    reverse_b(n);
+            };
+            // ring k of the map polygon into L.ringB, seen from the camera (transform_boundary, polygon.cpp:430-451), oriented
+            auto to_camera = [&](int k) {
+                const cape_map_ring R = p.mapRings[M.ring_first + k];
+                const double2* src = p.mapVertices + R.vertex_offset;
+                const int nb = (int)R.vertex_count;
+                for (int v = tid; v < nb; v += kStride)
+                    L.ringB[v] = to_camera_vertex(Tm, F, src[v]);
+                sync();
+                orient_b(nb, k > 0);
+            };
+            // the camera-space ring in L.ringB projected into the detected plane's frame (Polygon::project, polygon.cpp:338-382), oriented
+            auto project = [&](int k) {
+                const int nb = (int)p.mapRings[M.ring_first + k].vertex_count;
+                for (int v = tid; v < nb; v += kStride)
+                {
+                    const double2 q = L.ringB[v];
+                    const double X = nc[0] + q.x * nx[0] + q.y * ny[0];
+                    const double Y = nc[1] + q.x * nx[1] + q.y * ny[1];
+                    const double Z = nc[2] + q.x * nx[2] + q.y * ny[2];
+                    const double dx = X - PS.center[0], dy = Y - PS.center[1], dz = Z - PS.center[2];
+                    L.ringB[v] = make_double2((PS.x_axis[0] * dx + PS.x_axis[1] * dy) + PS.x_axis[2] * dz,
+                                              (PS.y_axis[0] * dx + PS.y_axis[1] * dy) + PS.y_axis[2] * dz);
+                }
+                sync();
+                orient_b(nb, k > 0);
+                return nb;
+            };
+            auto inter = [&](int nb) -> double {
+                double r;
+                if constexpr (kCoop)
+                    r = rings_inter_area_coop<T::kStack, T::kXs>(L, na, nb, tid);
+                else
+                    r = rings_inter_area<T::kStack, T::kXs>(L, na, nb, lane);
+                sync();
+                return r;
+            };
+            // (the projected polygon's area was found positive by the gate kernel: only such map planes list pairs)
+            double acc = 0.0;
+            result = 0.0;
+            for (int k = 0; k < nRings; ++k)
+            {
+                to_camera(k);
+                const double r = inter(project(k));
+                if (r != r)
+                {
+                    result = r;
+                    break;
+                }
+                acc = k == 0 ? r : acc - r; // polygons_inter_area: I(A, B) - I(A, hole_k) in order
+                result = acc < 0 ? 0.0 : acc;
+            }
+        }
+        if (tid == 0)
+        {
+            bool again = false;
+            if (kHasNext)
+                again = (is_nan_code(result, kNanStack) && later_stack<TIER>() > T::kStack) || (is_nan_code(result, kNanSlabs) && later_xs<TIER>() > T::kXs) ||
+                        (is_nan_code(result, kNanRing) && later_ring<TIER>() > T::kRing);
+            if (again)
+                p.tierLists[(size_t)TIER * cap + atomicAdd(&p.counts[2 + TIER], 1u)] = (unsigned)idx; // (an entry visits each tier once)
+            else
+            {
+                p.workArea[idx] = result;
+                if (p.areas)
+                    p.areas[((size_t)frame * p.nMap + j) * CAPE_MAX_PLANES + i] = result;
+            }
+        }
+    }
+}
+
+// One wavefront per frame: the map planes in order, each with the contiguous run of its gated pairs (one run fits the wave: at
+// most 64 kept planes), lanes over the run.
+__global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_kernel(MatchMapParams p, int nFrames)
+{
+    const int lane = threadIdx.x & 63;
+    const int frame = blockIdx.x * kMapSelectFrames + (threadIdx.x >> 6);
+    if (frame >= nFrames)
+        return;
+    cape_frame_map_match& out = p.frames[frame];
+    if (out.flags & CAPE_MATCH_EXACT_OVERFLOW)
+        return; // nothing was intersected
+    const int nc = out.n_cur;
+    const int seg = lane < nc ? out.seg_cur[lane] : -1;
+    const double myArea = lane < nc ? p.polygons[(size_t)frame * CAPE_MAX_PLANES + seg].area : 0.0; // detectedPolygon.get_area()
+    const uint2 range = p.frameRange[frame];
+    const unsigned begin = range.x, end = range.x + range.y;
+    // a pair beyond the intersection kernel's capacities: no match is reported for the frame
+    bool nan = false;
+    for (unsigned k = begin + lane; k < end; k += 64)
+        nan |= p.workArea[k] != p.workArea[k];
+    if (__any(nan))
+    {
+        if (lane == 0)
+            out.flags |= CAPE_MATCH_EXACT_OVERFLOW;
+        return;
+    }
+    unsigned long long taken = 0ull; // is-matched flags of the detected planes
+    int myMapOf = -1, nMatched = 0;
+    for (unsigned at = begin; at < end;)
+    {
+        const unsigned k = at + lane;
+        const bool valid = k < end;
+        const unsigned long long e = valid ? p.work[k] : 0ull;
+        const double ia = valid ? p.workArea[k] : -1.0;
+        const int jl = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
+        const int j = __builtin_amdgcn_readfirstlane(jl);
+        const bool mine = valid && jl == j;
+        const double detArea = __shfl(myArea, i);
+        // interArea > greatestSimilarity (starting at 0) and interArea / newPlaneArea >= threshold (map_primitive.cpp:137-143); the
+        // run is in ascending i and the comparison strict: the lowest index among the largest areas
+        unsigned long long key = 0;
+        if (mine && !((taken >> i) & 1ull) && ia > 0.0 && ia / detArea >= p.minOverlap)
+            key = (unsigned long long)__double_as_longlong(ia);
+        const unsigned long long best = ~wave_min_u64(~key);
+        const unsigned long long winners = __ballot(key != 0 && key == best);
+        int selected = winners ? __shfl(i, __ffsll((long long)winners) - 1) : -1;
+        if (!(p.flags & CAPE_MATCH_ALLOW_INDEX0) && selected <= 0) // map_primitive.cpp:146
+            selected = -1;
+        if (selected >= 0)
+        {
+            taken |= 1ull << selected;
+            ++nMatched;
+            if (lane == selected)
+                myMapOf = j;
+            if (lane == 0)
+                p.match[(size_t)frame * p.nMap + j] = selected;
+        }
+        at += (unsigned)__popcll(__ballot(mine));
+    }
+    if (lane == 0)
+        out.n_matched = nMatched;
+    out.map_of[lane] = myMapOf;
+}
+
+hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream)
+{
+    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(cape_map_gate_kernel, dim3((nFrames + kMapGateFrames - 1) / kMapGateFrames), dim3(64 * kMapGateFrames), 0, stream, p, nFrames);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    // persistent grids: as many workgroups as the chip holds at once (the list's length is only known on the device)
+    const int cus = p.computeUnits > 0 ? p.computeUnits : 256;
+    auto launch = [&](auto kernel, int lds, int wavesPerGroup, bool coop, int groupsPerCu) {
+        hipLaunchKernelGGL(kernel, dim3(cus * groupsPerCu), dim3(64 * wavesPerGroup), (size_t)lds * (coop ? 1 : wavesPerGroup), stream, p, lds);
+        return hipGetLastError();
+    };
+    if (const hipError_t e = launch(cape_map_inter_kernel<0>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
+        return e;
+    if (const hipError_t e = launch(cape_map_inter_kernel<1>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
+        return e;
+    if (const hipError_t e = launch(cape_map_inter_kernel<2>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
+        return e;
+    // (a device without the LDS for the largest tier leaves its triples NaN: their frames are flagged)
+    if (tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes)
+        if (const hipError_t e = launch(cape_map_inter_kernel<3>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu); e != hipSuccess)
+            return e;
+    hipLaunchKernelGGL(cape_map_select_kernel, dim3((nFrames + kMapSelectFrames - 1) / kMapSelectFrames), dim3(64 * kMapSelectFrames), 0, stream, p, nFrames);
+    return hipGetLastError();
+}
+
+} // namespace cape

@@ -629,6 +629,14 @@ Polygon::Polygon(OpenRing, const std::vector<vector2>& ring, const vector3& xAxi
     _area = area();
 }
 
+Polygon::Polygon(const std::vector<vector2>& outer, const std::vector<std::vector<vector2>>& holes, const vector3& xAxis, const vector3& yAxis,
+                 const vector3& center) :
+    Polygon(OpenRing {}, outer, xAxis, yAxis, center)
+{
+    for (const std::vector<vector2>& h : holes)
+        add_hole(h);
+}
+
 Polygon Polygon::project(const vector3& nextNormal, const vector3& nextCenter) const
 {
     const auto axes = get_plane_coordinate_system(nextNormal);

@@ -88,6 +88,11 @@ class Polygon
     bool merge_union(const Polygon& other);
     // polygon from an explicit ring in a given frame (polygon.cpp:236-266)
     Polygon(const std::vector<vector2>& ring, const vector3& xAxis, const vector3& yAxis, const vector3& center);
+    // polygon from an open outer ring (no repeated closing vertex) and its interior rings in a given frame -- a map plane's
+    // polygon after merge_union: the outer ring is oriented clockwise like the OpenRing constructor does, every hole
+    // counter-clockwise like add_hole (a hole of fewer than 3 vertices is dropped, as there)
+    Polygon(const std::vector<vector2>& outer, const std::vector<std::vector<vector2>>& holes, const vector3& xAxis, const vector3& yAxis,
+            const vector3& center);
 
     static std::vector<vector2> compute_concave_hull(const std::vector<vector2>& points) noexcept;
     static std::vector<vector2> compute_convex_hull(const std::vector<vector2>& points) noexcept;

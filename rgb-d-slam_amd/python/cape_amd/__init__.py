@@ -136,6 +136,108 @@ MATCH_EXACT_DTYPE = np.dtype([
 MATCH_EXACT_OVERFLOW = 1
 assert MATCH_EXACT_DTYPE.itemsize == 8 + 3 * 64 + 8 + 8 * 256
 
+# N2 against a persistent map (cape_map_upload / cape_match_map)
+MAP_MAX_PLANES, MAP_MAX_RING, MAP_MAX_HOLES = 1024, 512, 8
+MATCH_MAP_AREAS = 4
+MAP_PLANE_DTYPE = np.dtype([
+    ("normal", "<f8", 3), ("d", "<f8"), ("x_axis", "<f8", 3), ("y_axis", "<f8", 3), ("center", "<f8", 3),
+    ("ring_first", "<u4"), ("ring_count", "<u4")], align=True)
+MAP_RING_DTYPE = np.dtype([("vertex_offset", "<u4"), ("vertex_count", "<u4")], align=True)
+FRAME_MAP_MATCH_DTYPE = np.dtype([
+    ("n_map", "<i4"), ("n_cur", "<i4"), ("flags", "<u4"), ("n_matched", "<i4"), ("seg_cur", "<i4", CAPE_MAX_PLANES),
+    ("map_of", "<i4", CAPE_MAX_PLANES)], align=True)
+assert MAP_PLANE_DTYPE.itemsize == 13 * 8 + 8 and MAP_RING_DTYPE.itemsize == 8 and FRAME_MAP_MATCH_DTYPE.itemsize == 16 + 8 * CAPE_MAX_PLANES
+
+
+def pack_map(planes):
+    """Map planes -> (MAP_PLANE_DTYPE array, MAP_RING_DTYPE array, vertices n x 2) for Extractor.upload_map / host_match_map.
+
+    planes: sequence of (normal, d, x_axis, y_axis, center, outer_ring, holes), rings as (n, 2) arrays in the plane's own frame
+    (open: no repeated closing vertex), holes a (possibly empty) sequence of rings.  Order matters: the local map's planes first,
+    then the staged map's."""
+    P = np.zeros(len(planes), MAP_PLANE_DTYPE)
+    rings, verts, nv = [], [], 0
+    for j, (normal, d, x_axis, y_axis, center, outer, holes) in enumerate(planes):
+        P[j]["normal"], P[j]["d"], P[j]["x_axis"], P[j]["y_axis"], P[j]["center"] = normal, d, x_axis, y_axis, center
+        P[j]["ring_first"] = len(rings)
+        for r in [outer, *holes]:
+            r = np.ascontiguousarray(r, np.float64).reshape(-1, 2)
+            rings.append((nv, len(r)))
+            verts.append(r)
+            nv += len(r)
+        P[j]["ring_count"] = 1 + len(holes)
+    R = np.array(rings, MAP_RING_DTYPE) if rings else np.zeros(0, MAP_RING_DTYPE)
+    V = np.ascontiguousarray(np.concatenate(verts) if verts else np.zeros((0, 2)), np.float64)
+    return P, R, V
+
+
+_host_lib = None
+
+
+def host_match_map(map_arrays, detected, world_to_camera=None, skip=None, flags=0, areas=False):
+    """cape_host_match_map of libcape_primitives.so: MapPlane::find_matches over the map for ONE frame on the host class -- the
+    twin of Extractor.match_map and the answer for a frame the device flags MATCH_EXACT_OVERFLOW.
+
+    map_arrays: pack_map(...); detected: the frame's kept planes, a sequence of (normal[3], d, x_axis, y_axis, center, ring, area)
+    (area: the polygon's get_area(), None: the ring's); world_to_camera: 4 x 4 (None: identity); skip: ceil(n_map / 32) uint32
+    words.  Returns (match[n_map], map_of[n_det]) or, with areas=True, (match, map_of, inter_area[n_map, n_det])."""
+    return host_match_map_call(map_arrays, detected, world_to_camera, skip, flags, areas)()
+
+
+def host_match_map_call(map_arrays, detected, world_to_camera=None, skip=None, flags=0, areas=False):
+    """host_match_map with the arguments packed now and the native call deferred: returns run(), which makes only the call and
+    returns host_match_map's result (timing the twin from several threads without the packing)."""
+    global _host_lib
+    if _host_lib is None:
+        load_library()  # (libcape_primitives links libcape_hip)
+        path = os.path.join(os.path.dirname(LIB_PATH), "libcape_primitives.so")
+        if not os.path.exists(path):
+            raise CapeError(f"{path} is missing: build it with `make -C rgb-d-slam_amd/csrc host`")
+        L = C.CDLL(path)
+        vp = C.c_void_p
+        L.cape_host_match_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
+                                          C.c_uint32, vp, vp, vp]
+        L.cape_host_match_map.restype = C.c_int
+        _host_lib = L
+    P, R, V = map_arrays
+    n_det = len(detected)
+    dp = np.zeros((max(n_det, 1), 4))
+    df = np.zeros((max(n_det, 1), 9))
+    da = np.zeros(max(n_det, 1))
+    dc = np.zeros(max(n_det, 1), np.int32)
+    rings = []
+    have_area = all(det[6] is not None for det in detected)
+    for i, (normal, d, x_axis, y_axis, center, ring, area) in enumerate(detected):
+        dp[i, :3], dp[i, 3] = normal, d
+        df[i, 0:3], df[i, 3:6], df[i, 6:9] = x_axis, y_axis, center
+        da[i] = area if area is not None else 0.0
+        r = np.ascontiguousarray(ring, np.float64).reshape(-1, 2)
+        dc[i] = len(r)
+        rings.append(r)
+    dv = np.ascontiguousarray(np.concatenate(rings) if rings else np.zeros((1, 2)), np.float64)
+    T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(16)
+    S = None if skip is None else np.ascontiguousarray(skip, np.uint32)
+    n_map = len(P)
+    match = np.full(max(n_map, 1), -1, np.int32)
+    map_of = np.full(max(n_det, 1), -1, np.int32)
+    inter = np.full((max(n_map, 1), max(n_det, 1)), -1.0) if areas else None
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    args = (ptr(P), n_map, ptr(R), len(R), ptr(V), len(V), n_det, ptr(dp), ptr(df), ptr(da) if have_area else None, ptr(dv),
+            ptr(dc), ptr(T), ptr(S), flags, ptr(match), ptr(map_of), ptr(inter))
+    keep = (P, R, V, dp, df, da, dv, dc, T, S)
+
+    def run():
+        """the native call alone (ctypes releases the GIL for its duration)"""
+        assert keep is not None
+        rc = _host_lib.cape_host_match_map(*args)
+        if rc != 0:
+            raise CapeError(f"cape_host_match_map failed ({rc})")
+        out = (match[:n_map], map_of[:n_det])
+        return out + (inter[:n_map, :n_det],) if areas else out
+
+    return run
+
+
 CELL_STATS_DTYPE = np.dtype([
     ("sums", "<f8", 9), ("normal", "<f8", 3), ("d", "<f8"), ("centroid", "<f8", 3), ("mse", "<f8"),
     ("score", "<f8"), ("tol", "<f4"), ("point_count", "<u4"), ("bin", "<i4"), ("planar", "<u4"),
@@ -148,6 +250,7 @@ EXPORTED_SYMBOLS = [
     "cape_host_unregister", "cape_copy_cell_stats", "cape_enable_timing", "cape_get_timings",
     "cape_reset_timings", "cape_match_consecutive", "cape_device_matches", "cape_copy_matches",
     "cape_match_polygons", "cape_match_polygons_pose", "cape_copy_polygon_matches",
+    "cape_map_upload", "cape_match_map", "cape_copy_map_matches",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
@@ -216,6 +319,9 @@ def load_library():
     L.cape_match_polygons.argtypes = [vp, C.c_int32, C.c_uint32, vp]
     L.cape_match_polygons_pose.argtypes = [vp, C.c_int32, vp, C.c_uint32, vp]
     L.cape_copy_polygon_matches.argtypes = [vp, C.c_int32, vp]
+    L.cape_map_upload.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64]
+    L.cape_match_map.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, vp]
+    L.cape_copy_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -475,6 +581,41 @@ class Extractor:
         out = np.zeros(n_frames, MATCH_EXACT_DTYPE)
         _check(self.L, self.L.cape_copy_polygon_matches(self.h, n_frames, out.ctypes.data_as(C.c_void_p)), "cape_copy_polygon_matches")
         return out
+
+    # ---- N2 against a persistent map (needs build_polygons of the batch first) -----------------------
+    def upload_map(self, planes, rings=None, vertices=None):
+        """cape_map_upload: `planes` is either pack_map's triple, a MAP_PLANE_DTYPE array (with rings and vertices), or the list
+        pack_map takes.  The map stays on the device until the next upload."""
+        if rings is None:
+            planes, rings, vertices = planes if isinstance(planes, tuple) else pack_map(planes)
+        P = np.ascontiguousarray(planes, MAP_PLANE_DTYPE)
+        R = np.ascontiguousarray(rings, MAP_RING_DTYPE)
+        V = np.ascontiguousarray(vertices, np.float64).reshape(-1, 2)
+        _check(self.L, self.L.cape_map_upload(self.h, P.ctypes.data_as(C.c_void_p), len(P), R.ctypes.data_as(C.c_void_p), len(R),
+                                              V.ctypes.data_as(C.c_void_p), len(V)), "cape_map_upload")
+        self.map_size = len(P)
+
+    def match_map(self, n_frames, world_to_camera=None, skip=None, flags=0, stream=0):
+        """world_to_camera: n_frames x 4 x 4 row-major [R t; 0 0 0 1] (None: identity); skip: n_frames x ceil(n_map / 32) uint32,
+        bit j of frame f set = map plane j is not visited (None: none skipped)."""
+        T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(n_frames, 16)
+        S = None if skip is None else np.ascontiguousarray(skip, np.uint32).reshape(n_frames, -1)
+        _check(self.L, self.L.cape_match_map(self.h, n_frames, None if T is None else T.ctypes.data_as(C.c_void_p),
+                                             None if S is None else S.ctypes.data_as(C.c_void_p), flags, C.c_void_p(stream)),
+               "cape_match_map")
+        self.matched_map_size = self.map_size  # what cape_copy_map_matches writes: the map of THIS call, whatever is uploaded later
+
+    def map_matches(self, n_frames, areas=False):
+        """(frames: FRAME_MAP_MATCH_DTYPE[n_frames], match[n_frames, n_map]) of the last match_map, + inter_area[n_frames, n_map, 64]
+        with areas=True (the call must have had MATCH_MAP_AREAS).  n_map is the map size of that match_map call."""
+        n_map = getattr(self, "matched_map_size", 0)
+        frames = np.zeros(n_frames, FRAME_MAP_MATCH_DTYPE)
+        match = np.zeros((n_frames, max(n_map, 1)), np.int32)
+        inter = np.zeros((n_frames, max(n_map, 1), CAPE_MAX_PLANES)) if areas else None
+        _check(self.L, self.L.cape_copy_map_matches(self.h, n_frames, frames.ctypes.data_as(C.c_void_p), match.ctypes.data_as(C.c_void_p),
+                                                    None if inter is None else inter.ctypes.data_as(C.c_void_p)), "cape_copy_map_matches")
+        out = (frames, match[:, :n_map])
+        return out + (inter[:, :n_map],) if areas else out
 
     def cell_stats(self, frame):
         out = np.zeros(self.cells, CELL_STATS_DTYPE)
