@@ -1,0 +1,527 @@
+// C ABI, host side: depth rectification (N3), plane matching between consecutive frames and against a persistent map (N2), the
+// boundary polygons of the planes (N1) and the matches between them.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "cape_handle.h"
+
+using namespace cape::abi;
+
+namespace {
+
+// parameters::matching (src/parameters.hpp:89-95), evaluated on the host like the reference's function-local statics
+template <typename Params> void set_match_thresholds(Params& p, uint32_t flags)
+{
+    p.flags = flags;
+    p.minCosAngle = std::abs(std::cos(20.0 * M_PI / 180.0));
+    p.maxDistance = 100.0;
+    const double planeMinimalOverlap = static_cast<double>(0.4f);
+    p.minOverlap = (flags & CAPE_MATCH_ADVANCED) ? planeMinimalOverlap / 2 : planeMinimalOverlap;
+}
+
+int match_polygons_impl(cape_handle h, int32_t n_frames, const double* prev_to_cur, uint32_t flags, void* stream_)
+{
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    auto& P = h->poly;
+    if (n_frames > P.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
+    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    const size_t B = (size_t)h->cfg.max_batch;
+    const size_t pairCapacity = B * CAPE_MATCH_MAX_PLANES * CAPE_MATCH_MAX_PLANES;
+    CAPE_HIP_TRY(P.matches.ensure(B));
+    CAPE_HIP_TRY(P.lists.ensure(64 + 4 * pairCapacity));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    cape::MatchPolygonParams p;
+    if (prev_to_cur)
+    {
+        // the poses travel to the device in the caller's memory order: n_frames x 16 doubles (entry 0 is never read).  The
+        // header promises that prev_to_cur is read before the call returns: through the pinned twin
+        const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double);
+        CAPE_HIP_TRY(P.poses.ensure(B * 16));
+        CAPE_HIP_TRY(P.posesTwin.upload(P.poses, poseBytes, B * 16 * sizeof(double), stream,
+                                        [&](void* stage) { std::memcpy(stage, prev_to_cur, poseBytes); }));
+        p.poses = P.poses;
+    }
+    p.records = h->res.records;
+    p.polygons = P.polygons;
+    p.vertices = reinterpret_cast<const double2*>(P.vertices.get());
+    p.matches = P.matches;
+    p.listCounts = P.lists;
+    p.pairLists = P.lists + 64;
+    p.pairCapacity = pairCapacity;
+    p.computeUnits = h->computeUnits;
+    p.ldsLimitBytes = h->ldsLimit;
+    p.boundaryCapacity = h->boundaryCap;
+    set_match_thresholds(p, flags);
+    CAPE_HIP_TRY(cape::launch_match_polygons(p, n_frames, stream));
+    P.matchFrames = n_frames;
+    return CAPE_OK;
+}
+
+// the work buffers of cape_match_map, one allocation: counters, per-frame ranges, the gate masks, the work list, its areas, the
+// tier lists
+struct MapWorkLayout
+{
+    size_t counts, ranges, masks, work, area, tiers, total;
+};
+MapWorkLayout map_work_layout(int maxBatch, size_t cap)
+{
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    MapWorkLayout l;
+    l.counts = 0;
+    l.ranges = up(16 * sizeof(unsigned));
+    l.masks = l.ranges + up((size_t)maxBatch * sizeof(uint2));
+    l.work = l.masks + up((size_t)maxBatch * CAPE_MAP_MAX_PLANES * sizeof(unsigned long long));
+    l.area = l.work + up(cap * sizeof(unsigned long long));
+    l.tiers = l.area + up(cap * sizeof(double));
+    l.total = l.tiers + up(3 * cap * sizeof(unsigned));
+    return l;
+}
+constexpr size_t kMapWorkMax = (size_t)1 << 24;     // entries of the work list at most (448 MB of buffers)
+constexpr size_t kMapAreasBudget = (size_t)1 << 30; // bytes of the dense inter-area table at most
+bool unit_norm(const double* v) // double_equal(norm, 1) as to_camera_space requires (polygon_coordinates.cpp:144-151)
+{
+    return std::abs(std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) - 1.0) <= std::numeric_limits<double>::epsilon();
+}
+double ring_area_signed_host(const double* r, uint32_t n) // the host class's shoelace, same order
+{
+    double s = 0;
+    for (uint32_t i = 0, j = n - 1; i < n; j = i++)
+        s += (r[2 * j] * r[2 * i + 1] - r[2 * i] * r[2 * j + 1]);
+    return 0.5 * s;
+}
+
+} // namespace
+
+extern "C" {
+
+int cape_rectify_depth(cape_handle h, const float* depth_dev, float* rectified_dev, int32_t n_frames,
+                       const double* cam2_to_cam1, void* stream_)
+{
+    if (!h || !depth_dev || !rectified_dev || !cam2_to_cam1 || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument or negative frame count");
+    if (n_frames == 0)
+        return CAPE_OK;
+    if (depth_dev == rectified_dev)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "rectify_depth is not in-place");
+    CAPE_ON_DEVICE(h);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    // (a device-wide synchronisation before the smaller buffer is freed)
+    CAPE_HIP_TRY(h->rectFlags.grow(2 * (size_t)n_frames + 1, [] { return hipDeviceSynchronize(); }));
+    cape::RectifyParams p;
+    p.in = depth_dev;
+    p.out = rectified_dev;
+    p.ldsLimitBytes = h->ldsLimit;
+    p.frameFlag = h->rectFlags;
+    p.flagged = h->rectFlags + h->rectFlags.size() / 2;
+    {
+        const char* eb = std::getenv("CAPE_RECTIFY_BAND");
+        p.bandRows = eb ? std::atoi(eb) : 0;
+    }
+    p.W = h->cfg.width;
+    p.H = h->cfg.height;
+    p.xpre = h->xpre;
+    p.ypre = h->ypre;
+    for (int i = 0; i < 12; ++i)
+        p.T[i] = cam2_to_cam1[i];
+    p.fx = h->cfg.fx;
+    p.fy = h->cfg.fy;
+    p.cx = h->cfg.cx;
+    p.cy = h->cfg.cy;
+    {
+        // Which source rows can land in a band of target rows?  The row displacement of this rig, sampled over the image and over
+        // depths from 0.3 m to 10 m (plain doubles: a prediction, the kernel checks every pixel and flags what escapes it).
+        double lo = 0.0, hi = 0.0;
+        bool any = false;
+        const double zs[] = {300.0, 600.0, 1200.0, 2500.0, 5000.0, 10000.0};
+        for (int ry = 0; ry <= 4; ++ry)
+            for (int rx = 0; rx <= 4; ++rx)
+                for (double z : zs)
+                {
+                    const double row = (h->cfg.height - 1) * ry / 4.0, col = (h->cfg.width - 1) * rx / 4.0;
+                    const double x = (col - h->cfg.cx) / h->cfg.fx * z, y = (row - h->cfg.cy) / h->cfg.fy * z;
+                    const double q1 = p.T[4] * x + p.T[5] * y + p.T[6] * z + p.T[7], q2 = p.T[8] * x + p.T[9] * y + p.T[10] * z + p.T[11];
+                    if (!(q2 > 0))
+                        continue;
+                    const double d = (h->cfg.fy * q1 / q2 + h->cfg.cy) - row;
+                    lo = any ? std::min(lo, d) : d;
+                    hi = any ? std::max(hi, d) : d;
+                    any = true;
+                }
+        const char* em = std::getenv("CAPE_RECTIFY_MARGIN");
+        const int margin = em ? std::atoi(em) : 2;
+        const double cap = 4.0 * h->cfg.height; // (a degenerate rig: everything escapes, the general kernels take over)
+        p.shiftLo = (int)std::floor(std::max(-cap, std::min(cap, lo))) - margin;
+        p.shiftHi = (int)std::ceil(std::max(-cap, std::min(cap, hi))) + margin;
+    }
+    CAPE_HIP_TRY(cape::launch_rectify(p, n_frames, h->computeUnits, stream));
+    return CAPE_OK;
+}
+
+int cape_rectify_depth_host(cape_handle h, const float* depth_host, float* rectified_host, int32_t n_frames,
+                            const double* cam2_to_cam1)
+{
+    if (!h || !depth_host || !rectified_host || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument or negative frame count");
+    CAPE_ON_DEVICE(h);
+    const size_t n = (size_t)n_frames * h->cfg.width * h->cfg.height;
+    Buffer<float> din, dout;
+    CAPE_HIP_TRY(din.alloc(n));
+    if (dout.alloc(n) != hipSuccess)
+        return fail(CAPE_ERR_HIP, "hipMalloc failed");
+    if (hipMemcpy(din, depth_host, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(CAPE_ERR_HIP, "H2D copy failed");
+    if (const int rc = cape_rectify_depth(h, din, dout, n_frames, cam2_to_cam1, nullptr); rc != CAPE_OK)
+        return rc;
+    if (hipStreamSynchronize(nullptr) != hipSuccess)
+        return fail(CAPE_ERR_HIP, "rectify kernels failed");
+    if (copy_out(rectified_host, dout, 0, n) != hipSuccess)
+        return fail(CAPE_ERR_HIP, "D2H copy failed");
+    return CAPE_OK;
+}
+
+int cape_match_consecutive(cape_handle h, int32_t n_frames, uint32_t flags, void* stream_)
+{
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    if (n_frames > h->res.lastFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the last cape_extract batch");
+    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    StreamScope streamScope(h, static_cast<hipStream_t>(stream_));
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    CAPE_HIP_TRY(h->matches.ensure((size_t)h->cfg.max_batch));
+    cape::MatchParams p;
+    p.records = h->res.records;
+    p.plane_labels = h->res.planeLabels;
+    p.matches = h->matches;
+    p.cells = h->cells;
+    set_match_thresholds(p, flags);
+    CAPE_HIP_TRY(cape::launch_match(p, n_frames, static_cast<hipStream_t>(stream_)));
+    return CAPE_OK;
+}
+
+int cape_device_matches(cape_handle h, void** matches)
+{
+    if (!h || !matches)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument");
+    if (!h->matches)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "cape_match_consecutive has not run");
+    *matches = h->matches;
+    return CAPE_OK;
+}
+
+int cape_copy_matches(cape_handle h, int32_t n_frames, cape_frame_match* out)
+{
+    if (!h || !out || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    if (!h->matches)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "cape_match_consecutive has not run");
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(sync_handle(h));
+    CAPE_HIP_TRY(copy_out(out, h->matches, 0, (size_t)n_frames));
+    return CAPE_OK;
+}
+
+int cape_build_polygons(cape_handle h, int32_t n_frames, void* stream_)
+{
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    if (n_frames > h->res.lastFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the last cape_extract batch");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    auto& P = h->poly;
+    const size_t B = (size_t)h->cfg.max_batch + (size_t)h->chain.spillRecords; // a polygon row / vertex slab per record, spill pool included
+    // the records and boundary points of a few-frame handle live in pinned host memory (the kernel reads them over PCIe); the
+    // polygons follow them there
+    if (!P.polygons)
+        CAPE_HIP_TRY(alloc_result(P.polygons, B * CAPE_MAX_PLANES, h->resultsOnHost));
+    if (!P.vertices)
+        CAPE_HIP_TRY(alloc_result(P.vertices, B * (size_t)h->boundaryCap * 2, h->resultsOnHost));
+    CAPE_HIP_TRY(P.ladder.ensure(cape::polygon_scratch_bytes(B, h->boundaryCap)));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    cape::PolygonParams p;
+    cape::polygon_bind_scratch(p, P.ladder, B, h->boundaryCap);
+    p.computeUnits = h->computeUnits;
+    p.originInCentroid = 0;
+    p.records = h->res.records;
+    p.boundary = h->res.boundary;
+    p.polygons = P.polygons;
+    p.vertices = reinterpret_cast<double2*>(P.vertices.get());
+    p.boundaryCapacity = h->boundaryCap;
+    p.prof = h->debugCycles;
+    p.poolBase = h->cfg.max_batch;
+    p.poolCapacity = h->chain.spillRecords;
+    p.poolUsed = h->chain.spillCounters;
+#ifdef CAPE_POLY_PROFILE
+    CAPE_HIP_TRY(hipMemsetAsync(h->debugCycles, 0, (size_t)n_frames * cape::kProfileSlots * 8, stream));
+    CAPE_HIP_TRY(hipMemsetAsync(h->debugCycles + 6, 0xFF, 2 * 8, stream)); // the two minima of the task kernel's timeline
+#endif
+    h->res.doneArmed = false; // the chain's completion word was written before this kernel: results are waited for the slow way
+    CAPE_HIP_TRY(cape::launch_polygons(p, n_frames, stream));
+    P.frames = n_frames;
+    return CAPE_OK;
+}
+
+int cape_match_polygons(cape_handle h, int32_t n_frames, uint32_t flags, void* stream_)
+{
+    return match_polygons_impl(h, n_frames, nullptr, flags, stream_);
+}
+
+int cape_match_polygons_pose(cape_handle h, int32_t n_frames, const double* prev_to_cur, uint32_t flags, void* stream_)
+{
+    return match_polygons_impl(h, n_frames, prev_to_cur, flags, stream_);
+}
+
+int cape_copy_polygon_matches(cape_handle h, int32_t n_frames, cape_frame_match_exact* out)
+{
+    if (!h || !out || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    if (!h->poly.matches)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "cape_match_polygons has not run");
+    if (n_frames > h->poly.matchFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_match_polygons of the current batch");
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(copy_out(out, h->poly.matches, 0, (size_t)n_frames));
+    return CAPE_OK;
+}
+
+int cape_map_upload(cape_handle h, const cape_map_plane* planes, int32_t n_planes, const cape_map_ring* rings, int32_t n_rings,
+                    const double* vertices, int64_t n_vertices)
+{
+    if (!h || n_planes < 0 || n_rings < 0 || n_vertices < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative count");
+    if (n_planes > CAPE_MAP_MAX_PLANES)
+        return fail(CAPE_ERR_CAPACITY, "more map planes than CAPE_MAP_MAX_PLANES");
+    if ((n_planes > 0 && !planes) || (n_rings > 0 && !rings) || (n_vertices > 0 && !vertices))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null array");
+    // validation, then the rings re-oriented like the host class does and laid out plane by plane
+    std::vector<cape_map_plane> P(planes, planes + n_planes);
+    std::vector<cape_map_ring> R;
+    std::vector<double> V;
+    for (int32_t j = 0; j < n_planes; ++j)
+    {
+        cape_map_plane& M = P[j];
+        if (M.ring_count == 0 || (uint64_t)M.ring_first + M.ring_count > (uint64_t)n_rings)
+            return fail(CAPE_ERR_INVALID_ARGUMENT, "map plane without an outer ring or with rings outside the ring array");
+        if (M.ring_count > 1u + CAPE_MAP_MAX_HOLES)
+            return fail(CAPE_ERR_CAPACITY, "more holes than CAPE_MAP_MAX_HOLES");
+        if (!unit_norm(M.normal) || !unit_norm(M.x_axis) || !unit_norm(M.y_axis))
+            return fail(CAPE_ERR_INVALID_ARGUMENT, "map plane normal or polygon axis is not unit");
+        const uint32_t first = (uint32_t)R.size();
+        for (uint32_t k = 0; k < M.ring_count; ++k)
+        {
+            const cape_map_ring in = rings[M.ring_first + k];
+            if (in.vertex_count < 3 || (uint64_t)in.vertex_offset + in.vertex_count > (uint64_t)n_vertices)
+                return fail(CAPE_ERR_INVALID_ARGUMENT, "map ring of fewer than 3 vertices or outside the vertex array");
+            if (in.vertex_count > CAPE_MAP_MAX_RING)
+                return fail(CAPE_ERR_CAPACITY, "map ring longer than CAPE_MAP_MAX_RING (simplify the polygon first)");
+            const size_t at = V.size();
+            V.insert(V.end(), vertices + 2 * (size_t)in.vertex_offset, vertices + 2 * ((size_t)in.vertex_offset + in.vertex_count));
+            // outer ring clockwise (OpenRing constructor), holes counter-clockwise (add_hole)
+            const double sa = ring_area_signed_host(V.data() + at, in.vertex_count);
+            if (k == 0 ? sa > 0 : sa < 0)
+                for (uint32_t a = 0, b = in.vertex_count - 1; a < b; ++a, --b)
+                {
+                    std::swap(V[at + 2 * a], V[at + 2 * b]);
+                    std::swap(V[at + 2 * a + 1], V[at + 2 * b + 1]);
+                }
+            R.push_back(cape_map_ring {(uint32_t)(at / 2), in.vertex_count});
+        }
+        M.ring_first = first;
+    }
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h)); // a cape_match_map in flight still reads the old map
+    auto& map = h->map;
+    map.n = -1; // (no map until the copies are through)
+    const auto drained = [] { return hipSuccess; };
+    CAPE_HIP_TRY(map.planes.grow(P.size(), drained));
+    CAPE_HIP_TRY(map.rings.grow(R.size(), drained));
+    CAPE_HIP_TRY(map.vertices.grow(V.size(), drained));
+    if (!P.empty())
+    {
+        CAPE_HIP_TRY(hipMemcpy(map.planes, P.data(), P.size() * sizeof(cape_map_plane), hipMemcpyHostToDevice));
+        CAPE_HIP_TRY(hipMemcpy(map.rings, R.data(), R.size() * sizeof(cape_map_ring), hipMemcpyHostToDevice));
+        CAPE_HIP_TRY(hipMemcpy(map.vertices, V.data(), V.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    map.n = n_planes;
+    return CAPE_OK;
+}
+
+int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camera, const uint32_t* skip, uint32_t flags, void* stream_)
+{
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    auto& map = h->map;
+    if (n_frames > h->poly.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
+    if (map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
+    const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0;
+    const size_t areaDoubles = (size_t)n_frames * map.n * CAPE_MAX_PLANES;
+    if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
+        return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer frames per call, or no CAPE_MATCH_MAP_AREAS)");
+    map.matchFrames = 0;
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    const int B = h->cfg.max_batch;
+    const int skipWords = (map.n + 31) / 32;
+    const size_t poseCapacity = (size_t)B * 16 * sizeof(double) + (size_t)B * (CAPE_MAP_MAX_PLANES / 32) * sizeof(uint32_t);
+    const size_t cap = std::min((size_t)B * (size_t)std::max(map.n, 1) * CAPE_MAX_PLANES, kMapWorkMax);
+    const MapWorkLayout lay = map_work_layout(B, cap);
+    CAPE_HIP_TRY(map.frames.ensure((size_t)B));
+    CAPE_HIP_TRY(map.match.ensure((size_t)B * CAPE_MAP_MAX_PLANES));
+    CAPE_HIP_TRY(map.poses.ensure(poseCapacity));
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them
+    CAPE_HIP_TRY(map.work.grow(lay.total, drain));
+    if (keepAreas)
+        CAPE_HIP_TRY(map.areas.grow(areaDoubles, drain));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    // the poses (identity where none are given: the statements stay those of a pose), then the skip bits, travel through the
+    // pinned twin like cape_match_polygons_pose's: n_frames x 16 doubles, then n_frames x skipWords words
+    const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double);
+    const size_t skipBytes = skip ? (size_t)n_frames * skipWords * sizeof(uint32_t) : 0;
+    CAPE_HIP_TRY(map.posesTwin.upload(map.poses, poseBytes + skipBytes, poseCapacity, stream, [&](void* stage) {
+        double* pose = static_cast<double*>(stage);
+        if (world_to_camera)
+            std::memcpy(pose, world_to_camera, poseBytes);
+        else
+            for (int f = 0; f < n_frames; ++f)
+                for (int k = 0; k < 16; ++k)
+                    pose[16 * f + k] = (k % 5 == 0) ? 1.0 : 0.0;
+        if (skipBytes)
+            std::memcpy(static_cast<unsigned char*>(stage) + poseBytes, skip, skipBytes);
+    }));
+    cape::MatchMapParams p;
+    p.records = h->res.records;
+    p.polygons = h->poly.polygons;
+    p.vertices = reinterpret_cast<const double2*>(h->poly.vertices.get());
+    p.boundaryCapacity = h->boundaryCap;
+    p.mapPlanes = map.planes;
+    p.mapRings = map.rings;
+    p.mapVertices = reinterpret_cast<const double2*>(map.vertices.get());
+    p.nMap = map.n;
+    p.skipWords = skipWords;
+    p.poses = reinterpret_cast<const double*>(map.poses.get());
+    p.skip = skipBytes ? reinterpret_cast<const uint32_t*>(map.poses + poseBytes) : nullptr;
+    p.frames = map.frames;
+    p.match = map.match;
+    p.areas = keepAreas ? map.areas.get() : nullptr;
+    p.counts = reinterpret_cast<unsigned*>(map.work + lay.counts);
+    p.frameRange = reinterpret_cast<uint2*>(map.work + lay.ranges);
+    p.gateMasks = reinterpret_cast<unsigned long long*>(map.work + lay.masks);
+    p.work = reinterpret_cast<unsigned long long*>(map.work + lay.work);
+    p.workArea = reinterpret_cast<double*>(map.work + lay.area);
+    p.tierLists = reinterpret_cast<unsigned*>(map.work + lay.tiers);
+    p.workCapacity = cap;
+    p.computeUnits = h->computeUnits;
+    p.ldsLimitBytes = h->ldsLimit;
+    set_match_thresholds(p, flags);
+    CAPE_HIP_TRY(cape::launch_match_map(p, n_frames, stream));
+    map.matchFrames = n_frames;
+    map.matchN = map.n;
+    map.matchAreas = keepAreas;
+    return CAPE_OK;
+}
+
+int cape_copy_map_matches(cape_handle h, int32_t n_frames, cape_frame_map_match* frames, int32_t* match, double* inter_area)
+{
+    if (!h || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    const auto& map = h->map;
+    if (n_frames > map.matchFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_match_map of the current batch");
+    if (inter_area && n_frames > 0 && !map.matchAreas)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_match_map did not keep the inter-area table (CAPE_MATCH_MAP_AREAS)");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    const size_t n = (size_t)n_frames * map.matchN;
+    CAPE_HIP_TRY(copy_out(frames, map.frames, 0, (size_t)n_frames));
+    CAPE_HIP_TRY(copy_out(match, map.match, 0, n));
+    CAPE_HIP_TRY(copy_out(inter_area, map.areas, 0, n * CAPE_MAX_PLANES));
+    return CAPE_OK;
+}
+
+int cape_device_polygons(cape_handle h, cape_polygon** polygons, double** vertices)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->poly.frames <= 0)
+        return fail(CAPE_ERR_CAPACITY, "no polygons of the current batch: cape_build_polygons has not run since the last cape_extract");
+    if (polygons)
+        *polygons = h->poly.polygons;
+    if (vertices)
+        *vertices = h->poly.vertices;
+    return CAPE_OK;
+}
+
+int cape_copy_polygons(cape_handle h, int32_t n_frames, cape_polygon* polygons, double* vertices)
+{
+    if (!h || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    const auto& P = h->poly;
+    if (!P.polygons)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no polygons have been built yet");
+    if (n_frames > P.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons of the current batch");
+    CAPE_ON_DEVICE(h);
+    if (const int rc = settle_results(h); rc != CAPE_OK)
+        return rc;
+    const size_t n = (size_t)n_frames;
+    CAPE_HIP_TRY(copy_out(polygons, P.polygons, 0, n * CAPE_MAX_PLANES));
+    CAPE_HIP_TRY(copy_out(vertices, P.vertices, 0, n * (size_t)h->boundaryCap * 2));
+    return CAPE_OK;
+}
+
+int cape_copy_spill_polygons(cape_handle h, int32_t first, int32_t count, cape_polygon* polygons, double* vertices)
+{
+    if (!h || first < 0 || count < 0 || first > h->chain.spillRecords || count > h->chain.spillRecords - first)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / spill record range");
+    const auto& P = h->poly;
+    if (!P.polygons || P.frames <= 0)
+        return fail(CAPE_ERR_CAPACITY, "no cape_build_polygons has run on the current batch");
+    CAPE_ON_DEVICE(h);
+    if (const int rc = settle_results(h); rc != CAPE_OK)
+        return rc;
+    const size_t at = (size_t)h->cfg.max_batch + (size_t)first, n = (size_t)count, cap = (size_t)h->boundaryCap;
+    CAPE_HIP_TRY(copy_out(polygons, P.polygons, at * CAPE_MAX_PLANES, n * CAPE_MAX_PLANES));
+    CAPE_HIP_TRY(copy_out(vertices, P.vertices, at * cap * 2, n * cap * 2));
+    return CAPE_OK;
+}
+
+} // extern "C"

@@ -141,7 +141,7 @@ struct StageBParams
     uint32_t doneSeq;
     // one-frame chain on a grid the fast kernels serve: the general instance is NOT enqueued behind the 64-segment one (a launch on
     // the latency path for a frame in ten thousand) -- the signalling wave leaves the number of frames on spillList in this pinned
-    // word, and whoever reads the results launches the general kernel then, if it is not zero (cape_api.hip: wait_results)
+    // word, and whoever reads the results launches the general kernel then, if it is not zero (cape_api_extract.hip: wait_results)
     uint32_t* spillHost;
 };
 
