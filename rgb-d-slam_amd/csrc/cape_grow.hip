@@ -31,6 +31,53 @@ namespace cape {
 // their fits, the cell lists and the label grid) and carries on from that region: the rest of the record -> segment
 // conversion with cylinder_fitting, then merge_planes, boundaries and records like every other instance.  Without the
 // histogram, the edge masks, the MSE registers and the seed loop this instance is compiled for two waves per SIMD.
+// ---- the LDS carve of one frame-wave, in byte offsets.  The RESUME instance has no histogram, bins or staging chunk of its own
+//      (its ordered passes stage through s_dist), and keeps the centre-pixel depths of the boundary phase where the RANSAC id
+//      arrays were: 17 KB per wave at 640x480.  Arrays of the cylinder instances only are at offset 0 in the others.
+struct GrowLds
+{
+    size_t seg, chunk, adj, hist, bins, list, lab, mlab, cyl, ids, idmask, best, cur, dist, pendCyl, zc, prof, bytes;
+};
+__host__ __device__ inline GrowLds grow_lds(int cells, bool cylinders, int maxPlanes, bool resume)
+{
+    CAPE_LAYOUT_CHECK(cylinders || !resume);
+    const size_t C = (size_t)cells;
+    Layout l;
+    GrowLds o{};
+    o.seg = l.take<double>((size_t)(maxPlanes + 1) * kSegDoubles); // (MAXP + 1) x 20 f64 (one spare slot for the record window)
+    o.chunk = l.take<double>(resume ? 0 : kChunkDoubles(cells));   // kChunk x 10 f64 staging of cell sums
+    o.adj = l.take<unsigned long long>((size_t)maxPlanes + 1);
+    o.hist = l.take<int>(resume ? 0 : kHistBins);
+    o.bins = l.take<short>(resume ? 0 : C);
+    o.list = l.take<unsigned short>(C + 4);                        // 1 pad + C u16 (rounded to 8 B)
+    o.lab = l.take<unsigned char>(C);                              // plane labels
+    o.mlab = l.take<unsigned char>((size_t)maxPlanes);             // merge labels
+    if (cylinders)
+    {
+        o.cyl = l.take<unsigned char>(C);                          // cylinder labels
+        o.ids = l.take<unsigned short>(C, 4);                      // idsLeft
+        o.idmask = l.take<unsigned char>(C);
+        o.best = l.take<unsigned char>(C);
+        // inlier flags of the hypothesis being scored: only the streamed RANSAC path (regions beyond the register cache) uses them
+        o.cur = l.take<unsigned char>(!resume || cells > 64 * kCylCacheRounds ? C : 0);
+        o.dist = l.take<double>(cyl_dist_doubles(cells), 16);      // staging, 18 f64 x kChunk
+        o.pendCyl = l.take<double>((size_t)(resume ? kPendResume : kPendCyl) * kSegDoubles); // region records
+    }
+    // the centre-pixel depths of the boundary phase borrow arrays that are dead after the seed loop / the last cylinder fit
+    if (resume)
+    {
+        o.chunk = l.alias<double>(o.dist, kChunkDoubles(cells), o.pendCyl);
+        o.zc = l.alias<float>(o.ids, C, o.cur);
+    }
+    else
+        o.zc = l.alias<float>(o.bins, C, o.lab); // s_bins + s_list
+#ifdef CAPE_B_PROFILE
+    o.prof = l.take<unsigned long long>(kProfileSlots, 16);
+#endif
+    o.bytes = l.end(16);
+    return o;
+}
+
 // (the kernel's body; the __global__ function below adds the completion signal of the one-frame chain behind it)
 template <typename MaskT, bool CYL, int MAXP, bool RESUME>
 __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFrames, int ldsPerWave)
@@ -79,39 +126,29 @@ __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFram
     };
     const size_t cellBase = (size_t)frame * C;
 
-    // ---- LDS carve (every offset a multiple of 8; grow_lds_bytes() mirrors it).  The RESUME instance has no histogram, bins
-    //      or separate staging chunk (its ordered passes stage through s_dist), and keeps the centre-pixel depths of the
-    //      boundary phase where the RANSAC id arrays were: 17 KB per wave at 640x480.
-    double* s_seg = reinterpret_cast<double*>(smem);                              // (MAXP + 1) x 20 f64 (one spare slot for the record window)
-    double* s_afterSeg = s_seg + (MAXP + 1) * kSegDoubles;
-    double* s_chunkOwn = s_afterSeg;                                               // kChunk x 10 f64 staging of cell sums
-    unsigned long long* s_adj = reinterpret_cast<unsigned long long*>(RESUME ? s_afterSeg : s_chunkOwn + kChunkDoubles(C)); // MAXP + 1 u64
-    int* s_hist = reinterpret_cast<int*>(s_adj + MAXP + 1);                        // 400 i32
-    short* s_bins = reinterpret_cast<short*>(s_hist + (RESUME ? 0 : kHistBins));   // C i16
-    unsigned short* s_list = reinterpret_cast<unsigned short*>(s_bins + (RESUME ? 0 : C)); // 1 pad + C u16 (rounded to 8 B)
-    unsigned char* s_lab = reinterpret_cast<unsigned char*>(s_list + C + 4);      // C u8  plane labels
-    unsigned char* s_mlab = s_lab + C;                                            // MAXP u8 merge labels
-    // cylinder variant only (see grow_lds_bytes)
-    unsigned char* s_cyl = s_mlab + MAXP;                                         // C u8  cylinder labels
-    unsigned short* s_ids = reinterpret_cast<unsigned short*>(smem + (((size_t)(s_cyl + C - smem) + 3) & ~(size_t)3)); // C u16 idsLeft
-    unsigned char* s_idmask = reinterpret_cast<unsigned char*>(s_ids + C);        // C u8
-    unsigned char* s_best = s_idmask + C;                                         // C u8
-    // inlier flags of the hypothesis being scored: only the streamed RANSAC path (regions beyond the register cache) uses them
-    const bool needCur = !RESUME || C > 64 * kCylCacheRounds;
-    unsigned char* s_cur = s_best + C;                                            // C u8 (absent when !needCur)
-    // (aligned through the OFFSET, not through an integer cast of the pointer: the cast loses the LDS address space and every
-    // access through s_dist / s_pendCyl becomes a flat_load that waits for vmcnt AND lgkmcnt)
-    double* s_dist = reinterpret_cast<double*>(smem + (((size_t)(s_cur + (needCur ? C : 0) - smem) + 15) & ~(size_t)15)); // staging, 18 f64 x kChunk
-    double* s_pendCyl = s_dist + cyl_dist_doubles(C);                             // kPendSlots region records (cylinder instances)
-    double* s_chunk = RESUME ? s_dist : s_chunkOwn;
+    // ---- LDS carve (grow_lds)
+    const GrowLds lds = grow_lds(C, CYL, MAXP, RESUME);
+    double* s_seg = carve_at<double>(smem, lds.seg);
+    double* s_chunk = carve_at<double>(smem, lds.chunk);
+    unsigned long long* s_adj = carve_at<unsigned long long>(smem, lds.adj);
+    int* s_hist = carve_at<int>(smem, lds.hist);
+    short* s_bins = carve_at<short>(smem, lds.bins);
+    unsigned short* s_list = carve_at<unsigned short>(smem, lds.list);
+    unsigned char* s_lab = carve_at<unsigned char>(smem, lds.lab);
+    unsigned char* s_mlab = carve_at<unsigned char>(smem, lds.mlab);
+    unsigned char* s_cyl = carve_at<unsigned char>(smem, lds.cyl);
+    unsigned short* s_ids = carve_at<unsigned short>(smem, lds.ids);
+    unsigned char* s_idmask = carve_at<unsigned char>(smem, lds.idmask);
+    unsigned char* s_best = carve_at<unsigned char>(smem, lds.best);
+    unsigned char* s_cur = carve_at<unsigned char>(smem, lds.cur);
+    double* s_dist = carve_at<double>(smem, lds.dist);
+    double* s_pendCyl = carve_at<double>(smem, lds.pendCyl);
+    float* s_zc = carve_at<float>(smem, lds.zc);
 #ifdef CAPE_B_PROFILE
-    unsigned long long* s_prof = reinterpret_cast<unsigned long long*>(smem + ldsPerWave - 8 * kProfileSlots);
+    unsigned long long* s_prof = carve_at<unsigned long long>(smem, lds.prof);
     if (lane < kProfileSlots)
         s_prof[lane] = 0ull;
 #endif
-    // centre-pixel depths of the boundary phase: C f32 = exactly the bytes of s_bins + s_list (RESUME: of s_ids + s_idmask +
-    // s_best), all dead after the seed loop / the last cylinder fit
-    float* s_zc = RESUME ? reinterpret_cast<float*>(s_ids) : reinterpret_cast<float*>(s_bins);
 
 
     if constexpr (!RESUME)
@@ -436,12 +473,8 @@ __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFram
     if constexpr (RESUME)
     {
         // ---- pick the frame up where the plane-only pass parked it
-        const unsigned char* st = p.growState + (size_t)frame * p.growStateStride;
-        const GrowStateHeader hd = *reinterpret_cast<const GrowStateHeader*>(st);
-        const double* gseg = reinterpret_cast<const double*>(st + grow_state_seg_off());
-        const unsigned long long* gadj = reinterpret_cast<const unsigned long long*>(st + grow_state_adj_off());
-        const unsigned short* glist = reinterpret_cast<const unsigned short*>(st + grow_state_list_off());
-        const unsigned char* glab = st + grow_state_lab_off(C);
+        const GrowStateView g = grow_state_view(p.growState + (size_t)frame * p.growStateStride, C);
+        const GrowStateHeader hd = *g.hd;
         nSeg = hd.nSeg;
         nSeeds = hd.nSeeds;
         nPlanar = hd.nPlanar;
@@ -449,16 +482,16 @@ __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFram
         status = status_resume(hd.status, lane == 0);
         const int nRec = hd.pendCount - hd.pendFrom;
         for (int i = lane; i < nSeg * kSegDoubles; i += 64)
-            s_seg[i] = gseg[i];
+            s_seg[i] = g.seg[i];
         for (int i = lane; i < nRec * kSegDoubles; i += 64)
-            s_pendCyl[i] = gseg[(hd.pendBaseSlot + hd.pendFrom) * kSegDoubles + i];
+            s_pendCyl[i] = g.seg[(hd.pendBaseSlot + hd.pendFrom) * kSegDoubles + i];
         if (lane < nRec)
-            s_adj[lane] = gadj[hd.pendFrom + lane];
+            s_adj[lane] = g.adj[hd.pendFrom + lane];
         for (int i = lane; i < C + 4; i += 64)
-            s_list[i] = glist[i];
+            s_list[i] = g.list[i];
         for (int i = lane; i < C; i += 64)
         {
-            s_lab[i] = glab[i];
+            s_lab[i] = g.lab[i];
             s_cyl[i] = 0;
         }
         pendCount = nRec;
@@ -761,7 +794,7 @@ __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFram
                     const bool parked = MAXP == kFastPlanes && p.resumeList != nullptr && !moreSeeds && pendCount - j <= kPendResume;
                     if (parked)
                     {
-                        unsigned char* st = p.growState + (size_t)frame * p.growStateStride;
+                        const GrowStateView g = grow_state_view(p.growState + (size_t)frame * p.growStateStride, C);
                         const uint32_t statusAll = wave_or_u32(status);
                         const int baseSlot = (int)((s_pend - s_seg) / kSegDoubles);
                         if (lane == 0)
@@ -775,20 +808,16 @@ __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFram
                             hd.nPlanar = nPlanar;
                             hd.status = statusAll;
                             hd.pad = 0;
-                            *reinterpret_cast<GrowStateHeader*>(st) = hd;
+                            *g.hd = hd;
                         }
-                        double* gseg = reinterpret_cast<double*>(st + grow_state_seg_off());
-                        unsigned long long* gadj = reinterpret_cast<unsigned long long*>(st + grow_state_adj_off());
-                        unsigned short* glist = reinterpret_cast<unsigned short*>(st + grow_state_list_off());
-                        unsigned char* glab = st + grow_state_lab_off(C);
                         for (int i = lane; i < (baseSlot + pendCount) * kSegDoubles; i += 64)
-                            gseg[i] = s_seg[i];
+                            g.seg[i] = s_seg[i];
                         if (lane < pendCount)
-                            gadj[lane] = s_adj[lane];
+                            g.adj[lane] = s_adj[lane];
                         for (int i = lane; i < C + 4; i += 64)
-                            glist[i] = s_list[i];
+                            g.list[i] = s_list[i];
                         for (int i = lane; i < C; i += 64)
-                            glab[i] = s_lab[i];
+                            g.lab[i] = s_lab[i];
                         // cost class of what is left to do: the cells of the records that will go to cylinder_fitting
                         int candCells = 0;
                         if (lane < pendCount - j)
@@ -943,37 +972,7 @@ __global__ __launch_bounds__(64 * kWavesPerGroup, CYL ? (RESUME ? CAPE_B_RESUME_
     }
 }
 
-size_t grow_lds_bytes(int cells, bool cylinders, int maxPlanes, bool resume)
-{
-    size_t b = 0;
-    b += (size_t)(maxPlanes + 1) * kSegDoubles * 8; // s_seg (+ one spare slot for the record window)
-    if (!resume)
-        b += (size_t)kChunkDoubles(cells) * 8;      // s_chunk (the RESUME instance stages through s_dist)
-    b += (size_t)(maxPlanes + 1) * 8;               // s_adj
-    if (!resume)
-    {
-        b += (size_t)kHistBins * 4;                 // s_hist
-        b += (size_t)cells * 2;                     // s_bins  } after the seed loop these two hold s_zc
-    }
-    b += (size_t)cells * 2 + 8;                     // s_list  } (+ pad entry)
-    b += (size_t)cells;                             // s_lab
-    b += maxPlanes;                                 // s_mlab
-    if (cylinders)
-    {
-        b += (size_t)cells;                         // s_cyl
-        b = (b + 3) & ~(size_t)3;
-        b += (size_t)cells * 2 + (size_t)cells * 2; // s_ids, s_idmask, s_best
-        if (!resume || cells > 64 * kCylCacheRounds)
-            b += (size_t)cells;                     // s_cur
-        b = (b + 15) & ~(size_t)15;
-        b += (size_t)cyl_dist_doubles(cells) * 8;   // s_dist
-        b += (size_t)(resume ? kPendResume : kPendCyl) * kSegDoubles * 8; // s_pendCyl
-    }
-#ifdef CAPE_B_PROFILE
-    b = ((b + 15) & ~(size_t)15) + 8 * kProfileSlots; // s_prof
-#endif
-    return (b + 15) & ~(size_t)15;
-}
+size_t grow_lds_bytes(int cells, bool cylinders, int maxPlanes, bool resume) { return grow_lds(cells, cylinders, maxPlanes, resume).bytes; }
 size_t grow_lds_bytes(int cells, bool cylinders, int maxPlanes) { return grow_lds_bytes(cells, cylinders, maxPlanes, false); }
 size_t grow_state_bytes(int cells) { return grow_state_bytes_(cells); }
 

@@ -9,6 +9,7 @@
 #include "cape_wave.h"
 #include "cape_device.h"
 #include "cape_internal.h"
+#include "cape_layout.h"
 
 namespace cape {
 
@@ -201,6 +202,21 @@ __host__ __device__ constexpr size_t grow_state_adj_off() { return grow_state_se
 __host__ __device__ constexpr size_t grow_state_list_off() { return grow_state_adj_off() + (size_t)(kFastPlanes + 1) * 8; }
 __host__ __device__ inline size_t grow_state_lab_off(int cells) { return grow_state_list_off() + (((size_t)cells + 4) * 2 + 7) / 8 * 8; }
 __host__ __device__ inline size_t grow_state_bytes_(int cells) { return (grow_state_lab_off(cells) + (size_t)cells + 15) / 16 * 16; }
+// the parked state of one frame (st = p.growState + frame * p.growStateStride) as typed pointers
+struct GrowStateView
+{
+    GrowStateHeader* hd;
+    double* seg;             // (kFastPlanes + 1) x 20 f64: the segments, then the record window
+    unsigned long long* adj; // the window's adjacency words
+    unsigned short* list;    // 1 pad + C u16 cell lists
+    unsigned char* lab;      // C u8 plane labels
+};
+__host__ __device__ inline GrowStateView grow_state_view(unsigned char* st, int cells)
+{
+    return {reinterpret_cast<GrowStateHeader*>(st), reinterpret_cast<double*>(st + grow_state_seg_off()),
+            reinterpret_cast<unsigned long long*>(st + grow_state_adj_off()), reinterpret_cast<unsigned short*>(st + grow_state_list_off()),
+            st + grow_state_lab_off(cells)};
+}
 
 // ---- the parked frames by cost class (StageBParams::resumeBucketStride): the k-th frame of the finisher, dearest class first
 __device__ __forceinline__ int resume_cost_class(int candidateCells, int cells)

@@ -270,23 +270,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inte
     const int tid = kCoop ? (int)threadIdx.x : lane;
     constexpr int kStride = kCoop ? 256 : 64;
     unsigned char* smem = smem_all + (kCoop ? (size_t)0 : (size_t)wave * ldsPerWave);
-    MpLds L;
-    L.ringCap = T::kRing;
-    L.ringA = reinterpret_cast<double2*>(smem);
-    L.ringB = L.ringA + T::kRing;
-    L.ea = reinterpret_cast<Edge*>(L.ringB + T::kRing);
-    L.eb = L.ea + T::kRing;
-    L.xs = reinterpret_cast<double*>(L.eb + T::kRing);
-    L.terms = L.xs + T::kXs;
-    L.by = L.terms + 64 * T::kStack;
-    L.elo = reinterpret_cast<int*>(L.by + 128 * T::kStack);
-    L.ehi = L.elo + 2 * T::kRing;
-    L.pre = L.ehi + 2 * T::kRing;
-    L.cnt = L.pre + 2 * T::kRing + 2;
-    L.bk = reinterpret_cast<unsigned short*>(L.cnt + 128);
-    L.inc = L.bk + 128 * T::kStack;
-    L.sidx = reinterpret_cast<unsigned char*>(L.inc + 128 * T::kStack);
-    L.sh = reinterpret_cast<int*>(smem + ldsPerWave - 32);
+    const MpLds L = mp_carve<TIER>(smem);
     const size_t cap = p.workCapacity;
     const unsigned long long reserved = *reinterpret_cast<const unsigned long long*>(p.counts);
     const unsigned long long count = TIER == 0 ? (reserved < cap ? reserved : cap) : (unsigned long long)p.counts[1 + TIER];

@@ -167,23 +167,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_polygon_
     const int tid = kCoop ? (int)threadIdx.x : lane;
     constexpr int kStride = kCoop ? 256 : 64;
     unsigned char* smem = smem_all + (kCoop ? (size_t)0 : (size_t)wave * ldsPerWave);
-    MpLds L;
-    L.ringCap = T::kRing;
-    L.ringA = reinterpret_cast<double2*>(smem);
-    L.ringB = L.ringA + T::kRing;
-    L.ea = reinterpret_cast<Edge*>(L.ringB + T::kRing);
-    L.eb = L.ea + T::kRing;
-    L.xs = reinterpret_cast<double*>(L.eb + T::kRing);
-    L.terms = L.xs + T::kXs;
-    L.by = L.terms + 64 * T::kStack;
-    L.elo = reinterpret_cast<int*>(L.by + 128 * T::kStack);
-    L.ehi = L.elo + 2 * T::kRing;
-    L.pre = L.ehi + 2 * T::kRing;
-    L.cnt = L.pre + 2 * T::kRing + 2;
-    L.bk = reinterpret_cast<unsigned short*>(L.cnt + 128);
-    L.inc = L.bk + 128 * T::kStack;
-    L.sidx = reinterpret_cast<unsigned char*>(L.inc + 128 * T::kStack);
-    L.sh = reinterpret_cast<int*>(smem + ldsPerWave - 32); // the carve's last 32 bytes (tier_lds_bytes)
+    const MpLds L = mp_carve<TIER>(smem);
     const unsigned* list = p.pairLists + (size_t)TIER * p.pairCapacity;
     const unsigned count = p.listCounts[TIER];
     // The tiers behind the first hold few pairs of very unequal cost (an outline of 70 vertices over 145 slabs keeps a lone wave busy

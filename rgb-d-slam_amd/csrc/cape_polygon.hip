@@ -23,6 +23,7 @@
 
 #include "cape_device.h"
 #include "cape_internal.h"
+#include "cape_layout.h"
 #include "cape_wave.h"
 
 #include <algorithm>
@@ -1095,15 +1096,35 @@ template <int CAP> __device__ inline void finish_polygon(const PolygonParams& p,
     CAPE_POLY_SYNC();
 }
 
+// ---- the LDS carve of one polygon wave, in byte offsets
+struct PolyLdsLayout
+{
+    size_t pts, hull, ring, stack, used, keep, bytes;
+};
+__host__ __device__ constexpr PolyLdsLayout poly_lds(int cap)
+{
+    const size_t n = (size_t)cap;
+    Layout l;
+    PolyLdsLayout o{};
+    o.pts = l.take<double2>(n + kPolyCutPoints); // (+ the crossing points of a dissolved hull)
+    o.hull = l.take<unsigned short>(n + 2 + kPolyCutPoints);
+    o.ring = l.take<unsigned short>(n + 2 + kPolyCutPoints);
+    o.stack = l.take<unsigned int>(n);
+    o.used = l.take<unsigned char>(n);
+    o.keep = l.take<unsigned char>(n + 2);
+    o.bytes = l.end(16);
+    return o;
+}
 template <int CAP> __device__ inline PolyLds carve_lds(unsigned char* smem)
 {
+    constexpr PolyLdsLayout o = poly_lds(CAP);
     PolyLds L;
-    L.pts = reinterpret_cast<double2*>(smem);
-    L.hull = reinterpret_cast<unsigned short*>(L.pts + CAP + kPolyCutPoints);
-    L.ring = L.hull + CAP + 2 + kPolyCutPoints;
-    L.stack = reinterpret_cast<unsigned int*>(L.ring + CAP + 2 + kPolyCutPoints);
-    L.used = reinterpret_cast<unsigned char*>(L.stack + CAP);
-    L.keep = L.used + CAP;
+    L.pts = carve_at<double2>(smem, o.pts);
+    L.hull = carve_at<unsigned short>(smem, o.hull);
+    L.ring = carve_at<unsigned short>(smem, o.ring);
+    L.stack = carve_at<unsigned int>(smem, o.stack);
+    L.used = carve_at<unsigned char>(smem, o.used);
+    L.keep = carve_at<unsigned char>(smem, o.keep);
     return L;
 }
 
@@ -1650,32 +1671,41 @@ size_t polygon_queue_slots(size_t) { return CAPE_POLY_QUEUE_LEN; }
 size_t polygon_queue_slots(size_t frames) { return frames * kPolyQueuePerFrame + kPolyQuitSlots; }
 #endif
 
-size_t polygon_lds_bytes(int cap)
-{
-    size_t b = ((size_t)cap + kPolyCutPoints) * 16;            // pts (+ the crossing points of a dissolved hull)
-    b += 2 * ((size_t)cap + 2 + kPolyCutPoints) * 2;         // hull, ring
-    b += (size_t)cap * 4;                   // stack
-    b += (size_t)cap + cap + 2;             // used, keep
-    return (b + 15) & ~(size_t)15;
-}
+size_t polygon_lds_bytes(int cap) { return poly_lds(cap).bytes; }
 
-// scratch of a polygon pass over `frames` frames: three work lists, the state words, the parking area
-size_t polygon_scratch_bytes(size_t frames, int boundaryCapacity)
+// scratch of a polygon pass over `frames` frames: two work lists and the task queue (each behind a header), the state words,
+// the parking area
+struct PolyScratch
 {
-    const size_t lists = (2 * (frames * CAPE_MAX_PLANES + kPolyListHeader) + kPolyListHeader + polygon_queue_slots(frames)) * sizeof(uint32_t);
-    const size_t state = frames * CAPE_MAX_PLANES * sizeof(uint32_t);
-    const size_t park = frames * kParkRungs * ((size_t)boundaryCapacity + 2 * CAPE_MAX_PLANES) * sizeof(unsigned short);
-    return lists + state + park + 64;
+    size_t listStride, queueSlots, parkStride; // in elements
+    size_t queue, state, park, bytes;          // byte offsets (the lists at 0: list m at m * listStride)
+};
+static PolyScratch polygon_scratch(size_t frames, int boundaryCapacity)
+{
+    PolyScratch o;
+    o.listStride = frames * CAPE_MAX_PLANES + kPolyListHeader;
+    o.queueSlots = polygon_queue_slots(frames);
+    o.parkStride = (size_t)boundaryCapacity + 2 * CAPE_MAX_PLANES;
+    Layout l;
+    l.take<uint32_t>(2 * o.listStride);
+    o.queue = l.take<uint32_t>(kPolyListHeader + o.queueSlots);
+    o.state = l.take<uint32_t>(frames * CAPE_MAX_PLANES);
+    o.park = l.take<unsigned short>(frames * kParkRungs * o.parkStride);
+    o.bytes = l.off + 64;
+    return o;
 }
+size_t polygon_scratch_bytes(size_t frames, int boundaryCapacity) { return polygon_scratch(frames, boundaryCapacity).bytes; }
 void polygon_bind_scratch(PolygonParams& p, void* base, size_t frames, int boundaryCapacity)
 {
-    p.lists = static_cast<uint32_t*>(base);
-    p.listStride = (uint32_t)(frames * CAPE_MAX_PLANES + kPolyListHeader);
-    p.queue = p.lists + 2 * (size_t)p.listStride;
-    p.queueCapacity = (uint32_t)polygon_queue_slots(frames);
-    p.state = p.queue + kPolyListHeader + p.queueCapacity;
-    p.park = reinterpret_cast<unsigned short*>(p.state + frames * CAPE_MAX_PLANES);
-    p.parkStride = (uint32_t)(boundaryCapacity + 2 * CAPE_MAX_PLANES);
+    const PolyScratch o = polygon_scratch(frames, boundaryCapacity);
+    unsigned char* b = static_cast<unsigned char*>(base);
+    p.lists = reinterpret_cast<uint32_t*>(b);
+    p.listStride = (uint32_t)o.listStride;
+    p.queue = reinterpret_cast<uint32_t*>(b + o.queue);
+    p.queueCapacity = (uint32_t)o.queueSlots;
+    p.state = reinterpret_cast<uint32_t*>(b + o.state);
+    p.park = reinterpret_cast<unsigned short*>(b + o.park);
+    p.parkStride = (uint32_t)o.parkStride;
 }
 
 hipError_t launch_polygons(const PolygonParams& p, int nFrames, hipStream_t stream)

@@ -827,27 +827,38 @@ __device__ inline void cylinder_fitting_group(const GroupCtx& g, int& nSeg, int&
     }
 }
 
-size_t resume_group_lds_bytes(int cells)
+// ---- the LDS carve of the finisher workgroup, in byte offsets
+struct ResumeGroupLds
 {
-    size_t b = 0;
-    b += (size_t)(kFastPlanes + 1) * kSegDoubles * 8;   // s_seg
-    b += (size_t)kPendResume * kSegDoubles * 8;         // s_pend
-    b += (size_t)(kFastPlanes + 1) * 8;                 // s_adj
-    b = (b + 15) & ~(size_t)15;
-    b += kXchDoubles * 8;                               // s_xch
-    b += (size_t)2 * kStageDoubles * 8;                 // s_stage (two halves)
-    b += ((size_t)cells + 4) * 2;                       // s_list (+ pad entry)
-    b = (b + 7) & ~(size_t)7;
-    b += (size_t)cells + kFastPlanes + (size_t)cells;   // s_lab, s_mlab, s_cyl
-    b = (b + 3) & ~(size_t)3;
-    b += (size_t)cells * 4;                             // s_ids, s_idmask, s_best (the boundary phase's s_zc afterwards)
-    b = (b + 7) & ~(size_t)7;
-    b += (size_t)2 * 4 * kHypPerWave * (size_t)ransac_ballot_words(cells) * 8; // s_inl
+    size_t seg, pend, adj, xch, stage, list, lab, mlab, cyl, ids, idmask, best, inl, zc, prof, bytes;
+};
+__host__ __device__ inline ResumeGroupLds resume_group_lds(int cells)
+{
+    const size_t C = (size_t)cells;
+    Layout l;
+    ResumeGroupLds o{};
+    o.seg = l.take<double>((size_t)(kFastPlanes + 1) * kSegDoubles);
+    o.pend = l.take<double>((size_t)kPendResume * kSegDoubles);
+    o.adj = l.take<unsigned long long>((size_t)kFastPlanes + 1);
+    o.xch = l.take<double>(kXchDoubles, 16);
+    o.stage = l.take<double>((size_t)2 * kStageDoubles); // two halves
+    o.list = l.take<unsigned short>(C + 4);              // 1 pad + C
+    o.lab = l.take<unsigned char>(C, 8);
+    o.mlab = l.take<unsigned char>(kFastPlanes);
+    o.cyl = l.take<unsigned char>(C);
+    o.ids = l.take<unsigned short>(C, 4);
+    o.idmask = l.take<unsigned char>(C);
+    o.best = l.take<unsigned char>(C);
+    o.inl = l.take<unsigned long long>( // inlier ballots of the four waves' hypotheses, two buffers
+        (size_t)2 * 4 * kHypPerWave * (size_t)ransac_ballot_words(cells));
+    o.zc = l.alias<float>(o.ids, C, o.best + C);         // the boundary phase's centre-pixel depths
 #ifdef CAPE_B_PROFILE
-    b = ((b + 15) & ~(size_t)15) + 8 * kProfileSlots;
+    o.prof = l.take<unsigned long long>(kProfileSlots, 16);
 #endif
-    return (b + 15) & ~(size_t)15;
+    o.bytes = l.end(16);
+    return o;
 }
+size_t resume_group_lds_bytes(int cells) { return resume_group_lds(cells).bytes; }
 
 template <typename MaskT> __global__ __launch_bounds__(kGroupThreads, 2) void cape_resume_group_kernel(StageBParams p, int ldsBytes)
 {
@@ -861,23 +872,24 @@ template <typename MaskT> __global__ __launch_bounds__(kGroupThreads, 2) void ca
     const int C = p.cells;
     const size_t cellBase = (size_t)frame * C;
 
-    // ---- LDS carve (resume_group_lds_bytes mirrors it)
-    double* s_seg = reinterpret_cast<double*>(smem);
-    double* s_pend = s_seg + (MAXP + 1) * kSegDoubles;
-    unsigned long long* s_adj = reinterpret_cast<unsigned long long*>(s_pend + kPendResume * kSegDoubles);
-    double* s_xch = reinterpret_cast<double*>(smem + (((size_t)(reinterpret_cast<unsigned char*>(s_adj + MAXP + 1) - smem) + 15) & ~(size_t)15));
-    double* s_stage = s_xch + kXchDoubles;
-    unsigned short* s_list = reinterpret_cast<unsigned short*>(s_stage + 2 * kStageDoubles);
-    unsigned char* s_lab = smem + (((size_t)(reinterpret_cast<unsigned char*>(s_list + C + 4) - smem) + 7) & ~(size_t)7);
-    unsigned char* s_mlab = s_lab + C;
-    unsigned char* s_cyl = s_mlab + MAXP;
-    unsigned short* s_ids = reinterpret_cast<unsigned short*>(smem + (((size_t)(s_cyl + C - smem) + 3) & ~(size_t)3));
-    unsigned char* s_idmask = reinterpret_cast<unsigned char*>(s_ids + C);
-    unsigned char* s_best = s_idmask + C;
-    unsigned long long* s_inl = reinterpret_cast<unsigned long long*>(smem + (((size_t)(s_best + C - smem) + 7) & ~(size_t)7));
-    float* s_zc = reinterpret_cast<float*>(s_ids);
+    // ---- LDS carve (resume_group_lds)
+    const ResumeGroupLds lds = resume_group_lds(C);
+    double* s_seg = carve_at<double>(smem, lds.seg);
+    double* s_pend = carve_at<double>(smem, lds.pend);
+    unsigned long long* s_adj = carve_at<unsigned long long>(smem, lds.adj);
+    double* s_xch = carve_at<double>(smem, lds.xch);
+    double* s_stage = carve_at<double>(smem, lds.stage);
+    unsigned short* s_list = carve_at<unsigned short>(smem, lds.list);
+    unsigned char* s_lab = carve_at<unsigned char>(smem, lds.lab);
+    unsigned char* s_mlab = carve_at<unsigned char>(smem, lds.mlab);
+    unsigned char* s_cyl = carve_at<unsigned char>(smem, lds.cyl);
+    unsigned short* s_ids = carve_at<unsigned short>(smem, lds.ids);
+    unsigned char* s_idmask = carve_at<unsigned char>(smem, lds.idmask);
+    unsigned char* s_best = carve_at<unsigned char>(smem, lds.best);
+    unsigned long long* s_inl = carve_at<unsigned long long>(smem, lds.inl);
+    float* s_zc = carve_at<float>(smem, lds.zc);
 #ifdef CAPE_B_PROFILE
-    unsigned long long* s_prof = reinterpret_cast<unsigned long long*>(smem + ldsBytes - 8 * kProfileSlots);
+    unsigned long long* s_prof = carve_at<unsigned long long>(smem, lds.prof);
     if (tid < kProfileSlots)
         s_prof[tid] = 0ull;
 #else
@@ -885,31 +897,27 @@ template <typename MaskT> __global__ __launch_bounds__(kGroupThreads, 2) void ca
 #endif
 
     // ---- pick the frame up where the plane-only pass parked it
-    const unsigned char* st = p.growState + (size_t)frame * p.growStateStride;
-    const GrowStateHeader hd = *reinterpret_cast<const GrowStateHeader*>(st);
-    const double* gseg = reinterpret_cast<const double*>(st + grow_state_seg_off());
-    const unsigned long long* gadj = reinterpret_cast<const unsigned long long*>(st + grow_state_adj_off());
-    const unsigned short* glist = reinterpret_cast<const unsigned short*>(st + grow_state_list_off());
-    const unsigned char* glab = st + grow_state_lab_off(C);
+    const GrowStateView g = grow_state_view(p.growState + (size_t)frame * p.growStateStride, C);
+    const GrowStateHeader hd = *g.hd;
     int nSeg = hd.nSeg;
     const int nSeeds = hd.nSeeds, nPlanar = hd.nPlanar;
     uint32_t status = status_resume(hd.status, tid == 0);
     const int nRec = hd.pendCount - hd.pendFrom;
     for (int i = tid; i < nSeg * kSegDoubles; i += kGroupThreads)
-        s_seg[i] = gseg[i];
+        s_seg[i] = g.seg[i];
     for (int i = tid; i < nRec * kSegDoubles; i += kGroupThreads)
-        s_pend[i] = gseg[(hd.pendBaseSlot + hd.pendFrom) * kSegDoubles + i];
+        s_pend[i] = g.seg[(hd.pendBaseSlot + hd.pendFrom) * kSegDoubles + i];
     for (int i = tid; i < MAXP + 1; i += kGroupThreads)
     {
-        s_adj[i] = i < nRec ? gadj[hd.pendFrom + i] : 0ull;
+        s_adj[i] = i < nRec ? g.adj[hd.pendFrom + i] : 0ull;
         if (i < MAXP)
             s_mlab[i] = (unsigned char)i;
     }
     for (int i = tid; i < C + 4; i += kGroupThreads)
-        s_list[i] = glist[i];
+        s_list[i] = g.list[i];
     for (int i = tid; i < C; i += kGroupThreads)
     {
-        s_lab[i] = glab[i];
+        s_lab[i] = g.lab[i];
         s_cyl[i] = 0;
     }
     __syncthreads();

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cape_internal.h"
+#include "cape_layout.h"
 #include "cape_wave.h"
 
 namespace cape {
@@ -99,6 +100,57 @@ struct MpLds
     unsigned char* sidx;  // 2 x 64 x CAP: positions in sorted order
     int* sh;              // 8 words the waves of a cooperative workgroup hand uniform values over in (kCoop tiers)
 };
+
+// ---- the LDS carve of a tier (one per wave; one per workgroup in the cooperative tiers), in byte offsets
+struct MpLdsLayout
+{
+    size_t ringA, ringB, ea, eb, xs, terms, by, elo, ehi, pre, cnt, bk, inc, sidx, sh, bytes;
+};
+template <int TIER> __host__ __device__ constexpr MpLdsLayout mp_layout()
+{
+    using T = Tier<TIER>;
+    Layout l;
+    MpLdsLayout o{};
+    o.ringA = l.take<double2>(T::kRing);
+    o.ringB = l.take<double2>(T::kRing);
+    o.ea = l.take<Edge>(T::kRing);
+    o.eb = l.take<Edge>(T::kRing);
+    o.xs = l.take<double>(T::kXs);
+    o.terms = l.take<double>(64 * T::kStack);
+    o.by = l.take<double>(128 * T::kStack);
+    o.elo = l.take<int>(2 * T::kRing);
+    o.ehi = l.take<int>(2 * T::kRing);
+    o.pre = l.take<int>(2 * T::kRing + 2);
+    o.cnt = l.take<int>(128);
+    o.bk = l.take<unsigned short>(128 * T::kStack);
+    o.inc = l.take<unsigned short>(128 * T::kStack);
+    o.sidx = l.take<unsigned char>(128 * T::kStack);
+    o.sh = l.take<int>(8, 16);
+    o.bytes = l.end(16);
+    return o;
+}
+template <int TIER> __device__ inline MpLds mp_carve(unsigned char* smem)
+{
+    constexpr MpLdsLayout o = mp_layout<TIER>();
+    MpLds L;
+    L.ringCap = Tier<TIER>::kRing;
+    L.ringA = carve_at<double2>(smem, o.ringA);
+    L.ringB = carve_at<double2>(smem, o.ringB);
+    L.ea = carve_at<Edge>(smem, o.ea);
+    L.eb = carve_at<Edge>(smem, o.eb);
+    L.xs = carve_at<double>(smem, o.xs);
+    L.terms = carve_at<double>(smem, o.terms);
+    L.by = carve_at<double>(smem, o.by);
+    L.elo = carve_at<int>(smem, o.elo);
+    L.ehi = carve_at<int>(smem, o.ehi);
+    L.pre = carve_at<int>(smem, o.pre);
+    L.cnt = carve_at<int>(smem, o.cnt);
+    L.bk = carve_at<unsigned short>(smem, o.bk);
+    L.inc = carve_at<unsigned short>(smem, o.inc);
+    L.sidx = carve_at<unsigned char>(smem, o.sidx);
+    L.sh = carve_at<int>(smem, o.sh);
+    return L;
+}
 
 __device__ __forceinline__ double y_at(const Edge& e, double x) { return e.a.y + (e.b.y - e.a.y) * ((x - e.a.x) / (e.b.x - e.a.x)); }
 
@@ -756,12 +808,6 @@ __device__ __forceinline__ int valid_planes(const cape_frame_record& rec, const 
 
 } // namespace
 
-template <int TIER> static size_t tier_lds_bytes()
-{
-    using T = Tier<TIER>;
-    const size_t b = (size_t)2 * T::kRing * sizeof(double2) + (size_t)2 * T::kRing * sizeof(Edge) + (size_t)T::kXs * 8 +
-                     (size_t)64 * T::kStack * 8 + (size_t)128 * T::kStack * (8 + 2 + 2 + 1) + (size_t)(6 * T::kRing + 2 + 128) * 4;
-    return ((b + 15) & ~(size_t)15) + 32; // + MpLds::sh
-}
+template <int TIER> static size_t tier_lds_bytes() { return mp_layout<TIER>().bytes; }
 
 } // namespace cape
