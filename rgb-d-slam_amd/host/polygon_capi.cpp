@@ -1,12 +1,19 @@
-// Test hook: the host boundary-polygon class behind a C entry point, so that tests/test_gpu_polygon.py can compare the
-// device polygons (cape_build_polygons) with it vertex for vertex through ctypes.  Not part of the product's C ABI.
+// C entry points of libcape_primitives.so over the host boundary-polygon class.  None of them is part of libcape_hip's C ABI
+// (include/cape_hip.h).  cape_host_polygon, cape_host_polygon_inter_area* and the cape_host_covariance / kalman hooks at the
+// end are test hooks: the tests compare the device (or a numpy restatement) with them through ctypes.  cape_host_match_map and
+// cape_host_map_update are host twins a caller may use: the first answers the frames cape_match_map flags, the second is the
+// map update (declared in cape_host_map.h), which runs on the host only.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <vector>
 
 #include "boundary_polygon.hpp"
+#include "map_tracking.hpp"
 #include "cape_hip.h"
+#include "cape_host_map.h"
 
 extern "C" int cape_host_polygon(const double* points3, int n, const double* normal, const double* center, double* ring_out, int capacity,
                                  int* count_out, double* area_out, double* x_axis_out, double* y_axis_out, int* valid_out)
@@ -197,4 +204,311 @@ extern "C" int cape_host_match_map(const cape_map_plane* planes, int32_t n_plane
     {
         return CAPE_ERR_INVALID_ARGUMENT;
     }
+}
+
+namespace {
+
+// Eigen's isApprox on 3-vectors: |a - b|^2 <= prec^2 min(|a|^2, |b|^2)
+bool is_approx3(const rgbd_slam::vector3& a, const rgbd_slam::vector3& b)
+{
+    const double e0 = a[0] - b[0], e1 = a[1] - b[1], e2 = a[2] - b[2];
+    const double diff = (e0 * e0 + e1 * e1) + e2 * e2;
+    const double na = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], nb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+    const double prec = 1e-12;
+    return diff <= prec * prec * std::min(na, nb);
+}
+
+// CameraPolygon::to_world_space (polygon_coordinates.cpp:48-75): its norm and orthogonality checks, then the transform that
+// to_camera_space restates with the camera-to-world matrix.  False where the reference throws.
+bool to_world_space(const rgbd_slam::utils::Polygon& p, const double* T, rgbd_slam::utils::Polygon& out)
+{
+    using rgbd_slam::map_tracking::norm3;
+    using rgbd_slam::map_tracking::normalize3;
+    const rgbd_slam::vector3 x = p.get_x_axis(), y = p.get_y_axis();
+    double nx[3] = {(T[0] * x[0] + T[1] * x[1]) + T[2] * x[2], (T[4] * x[0] + T[5] * x[1]) + T[6] * x[2], (T[8] * x[0] + T[9] * x[1]) + T[10] * x[2]};
+    double ny[3] = {(T[0] * y[0] + T[1] * y[1]) + T[2] * y[2], (T[4] * y[0] + T[5] * y[1]) + T[6] * y[2], (T[8] * y[0] + T[9] * y[1]) + T[10] * y[2]};
+    normalize3(nx);
+    normalize3(ny);
+    const double eps = std::numeric_limits<double>::epsilon();
+    if (!(std::abs(norm3(nx) - 1.0) <= eps) || !(std::abs(norm3(ny) - 1.0) <= eps))
+        return false;
+    if (std::abs((ny[0] * nx[0] + ny[1] * nx[1]) + ny[2] * nx[2]) > .01)
+        return false;
+    out = p.to_camera_space(T);
+    return true;
+}
+
+struct MapEntry
+{
+    cape_map_plane plane;
+    cape_map_track track;
+    rgbd_slam::utils::Polygon polygon;
+};
+
+} // namespace
+
+// Feature_Map::update_map (feature_map.hpp:367-384, :701-830) for ONE frame on the host class, over the ordered map list of
+// cape_map_upload (local planes first, then staged; CAPE_MAP_TRACK_STAGED tells them apart): the twin of the device map update.
+// Inputs: the map as cape_host_match_map takes it plus its tracking state (n_planes entries); match[n_planes] = the detected
+// kept-plane index matched to map plane j (cape_host_match_map / cape_copy_map_matches), or -1; the frame's kept planes as
+// cape_host_match_map takes them plus det_cov = n_det x 9 doubles (cape_plane_segment.cov); camera_to_world: 16 doubles
+// row-major; pose_covariance: 9 doubles; flags: CAPE_MAP_ADD_STAGED; next_id: the id of the first appended plane (advanced).
+// Per map plane in list order: MapPlane::update_with_match if matched (map_primitive.cpp:204-251 with track,
+// plane_with_tracking.cpp:15-82), then update_matched / update_unmatched, the result bits of cape_map_track.  Then, with
+// CAPE_MAP_ADD_STAGED, every kept plane that no map plane used (a local plane uses its detection only on success, a staged
+// plane either way, feature_map.hpp:790-797) becomes a StagedMapPlane (map_primitive.cpp:262-285) in kept-plane order, unless
+// its constructor would throw or its ring exceeds CAPE_MAP_MAX_RING.  Outputs: the new map in cape_map_upload's layout (every
+// polygon as the host class stores it: outer ring clockwise, holes counter-clockwise, rings plane after plane), the new
+// tracking state, and used_out[n_det] (NULL: not written).  Returns 0; CAPE_ERR_INVALID_ARGUMENT for a ring outside its array /
+// of fewer than 3 vertices, a match out of range, or an invalid pose covariance (update_map throws); CAPE_ERR_CAPACITY if an
+// output array is too small -- nothing is written then but the three sizes the call needs (next_id unchanged).
+extern "C" int cape_host_map_update(const cape_map_plane* planes, int32_t n_planes, const cape_map_ring* rings, int32_t n_rings,
+                                    const double* vertices, int64_t n_vertices, const cape_map_track* tracks, const int32_t* match,
+                                    int32_t n_det, const double* det_planes, const double* det_cov, const double* det_frames,
+                                    const double* det_vertices, const int32_t* det_counts, const double* camera_to_world,
+                                    const double* pose_covariance, uint32_t flags, uint64_t* next_id, cape_map_plane* planes_out,
+                                    int32_t planes_capacity, cape_map_ring* rings_out, int32_t rings_capacity, double* vertices_out,
+                                    int64_t vertices_capacity, cape_map_track* tracks_out, int32_t* n_planes_out, int32_t* n_rings_out,
+                                    int64_t* n_vertices_out, int32_t* used_out)
+{
+    using rgbd_slam::vector2;
+    using rgbd_slam::vector3;
+    using rgbd_slam::utils::Polygon;
+    namespace mt = rgbd_slam::map_tracking;
+    if (n_planes < 0 || n_det < 0 || n_det > CAPE_MAX_PLANES || !camera_to_world || !pose_covariance || !next_id || !n_planes_out ||
+        !n_rings_out || !n_vertices_out || (n_planes > 0 && (!planes || !tracks || !match)) || (flags & ~(uint32_t)CAPE_MAP_ADD_STAGED))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const double* T = camera_to_world;
+    if (!mt::is_covariance_valid(pose_covariance, 3))
+        return CAPE_ERR_INVALID_ARGUMENT; // update_map: "The given pose covariance is invalid, map wont be update"
+    try
+    {
+        std::vector<Polygon> det;
+        size_t at = 0;
+        for (int32_t i = 0; i < n_det; ++i)
+        {
+            if (det_counts[i] < 3)
+                return CAPE_ERR_INVALID_ARGUMENT;
+            std::vector<vector2> ring;
+            for (int32_t v = 0; v < det_counts[i]; ++v, ++at)
+                ring.emplace_back(det_vertices[2 * at], det_vertices[2 * at + 1]);
+            const double* F = det_frames + 9 * i;
+            det.emplace_back(ring, vector3(F[0], F[1], F[2]), vector3(F[3], F[4], F[5]), vector3(F[6], F[7], F[8]));
+        }
+        auto ring_of = [&](uint32_t r, std::vector<vector2>& out) {
+            if (r >= (uint32_t)n_rings || rings[r].vertex_count < 3 || (int64_t)rings[r].vertex_offset + rings[r].vertex_count > n_vertices)
+                return false;
+            out.clear();
+            for (uint32_t v = 0; v < rings[r].vertex_count; ++v)
+            {
+                const double* q = vertices + 2 * ((size_t)rings[r].vertex_offset + v);
+                out.emplace_back(q[0], q[1]);
+            }
+            return true;
+        };
+        std::vector<char> used(n_det, 0);
+        std::vector<MapEntry> out;
+        out.reserve(n_planes + n_det);
+        for (int32_t j = 0; j < n_planes; ++j)
+        {
+            const cape_map_plane& M = planes[j];
+            if (M.ring_count == 0 || match[j] < -1 || match[j] >= n_det)
+                return CAPE_ERR_INVALID_ARGUMENT;
+            std::vector<vector2> outer;
+            std::vector<std::vector<vector2>> holes(M.ring_count - 1);
+            if (!ring_of(M.ring_first, outer))
+                return CAPE_ERR_INVALID_ARGUMENT;
+            for (uint32_t k = 1; k < M.ring_count; ++k)
+                if (!ring_of(M.ring_first + k, holes[k - 1]))
+                    return CAPE_ERR_INVALID_ARGUMENT;
+            MapEntry e {M, tracks[j], Polygon(outer, holes, vector3(M.x_axis[0], M.x_axis[1], M.x_axis[2]),
+                                              vector3(M.y_axis[0], M.y_axis[1], M.y_axis[2]), vector3(M.center[0], M.center[1], M.center[2]))};
+            uint32_t result = 0;
+            const bool staged = (e.track.flags & CAPE_MAP_TRACK_STAGED) != 0;
+            const int32_t i = match[j];
+            if (i >= 0)
+            {
+                result |= CAPE_MAP_RESULT_MATCHED;
+                const double* dp = det_planes + 4 * i;
+                double planeCov[16], worldCov[16], nw[3], dw;
+                if (!mt::plane_covariance(dp, dp[3], det_cov + 9 * i, planeCov) ||
+                    !mt::world_plane_covariance(dp, dp[3], T, planeCov, pose_covariance, worldCov))
+                    result |= CAPE_MAP_RESULT_FAIL_DETECTION;
+                else if (!mt::is_covariance_valid(e.track.covariance, 4))
+                    result |= CAPE_MAP_RESULT_FAIL_STATE;
+                else
+                {
+                    mt::plane_to_world(dp, dp[3], T, nw, &dw);
+                    const double x[4] = {M.normal[0], M.normal[1], M.normal[2], M.d}, z[4] = {nw[0], nw[1], nw[2], dw};
+                    double xn[4], Pn[16];
+                    const mt::KalmanStatus st = mt::kalman_update(x, e.track.covariance, z, worldCov, xn, Pn);
+                    if (st == mt::KALMAN_SINGULAR)
+                        result |= CAPE_MAP_RESULT_FAIL_SINGULAR;
+                    else if (st != mt::KALMAN_OK)
+                        result |= CAPE_MAP_RESULT_FAIL_KALMAN;
+                    else
+                    {
+                        // PlaneWorldCoordinates(vector4), its copy and the assignment each normalise the normal (plane_coordinates.hpp:19-32)
+                        double n[3] = {xn[0], xn[1], xn[2]};
+                        mt::normalize3(n);
+                        mt::normalize3(n);
+                        mt::normalize3(n);
+                        std::memcpy(e.track.covariance, Pn, sizeof(Pn));
+                        std::memcpy(e.plane.normal, n, sizeof(n));
+                        e.plane.d = xn[3];
+                        // Plane::update_boundary_polygon (plane_with_tracking.cpp:63-82)
+                        const vector3 normal(n[0], n[1], n[2]), center(n[0] * -xn[3], n[1] * -xn[3], n[2] * -xn[3]);
+                        bool ok = std::abs(mt::norm3(n) - 1.0) <= std::numeric_limits<double>::epsilon(); // Polygon::project's check
+                        Polygon poly = e.polygon;
+                        if (ok)
+                        {
+                            const auto axes = rgbd_slam::utils::get_plane_coordinate_system(normal);
+                            // Polygon::project returns the polygon itself if its frame is already the target (isApprox)
+                            if (!(is_approx3(poly.get_center(), center) && is_approx3(poly.get_x_axis(), axes.first) &&
+                                  is_approx3(poly.get_y_axis(), axes.second)))
+                                poly = poly.project(axes.first, axes.second, center);
+                            Polygon detWorld;
+                            ok = is_approx3(poly.get_center(), center) && to_world_space(det[i], T, detWorld);
+                            if (ok)
+                            {
+                                // WorldPolygon::merge: merge_union of the detection projected into this frame (merge_union projects
+                                // it; the reference's second projection onto the same frame returns it unchanged)
+                                Polygon merged = poly;
+                                (void)merged.merge_union(detWorld);
+                                bool fits = merged.boundary().size() <= CAPE_MAP_MAX_RING && merged.interior_rings().size() <= CAPE_MAP_MAX_HOLES;
+                                for (const auto& h : merged.interior_rings())
+                                    fits = fits && h.size() <= CAPE_MAP_MAX_RING;
+                                if (fits)
+                                    poly = merged;
+                                else
+                                {
+                                    poly = e.polygon;
+                                    result |= CAPE_MAP_RESULT_OVERFLOW;
+                                }
+                                result |= CAPE_MAP_RESULT_UPDATED;
+                            }
+                        }
+                        if (!ok)
+                            result |= CAPE_MAP_RESULT_FAIL_POLYGON;
+                        e.polygon = poly;
+                    }
+                }
+                if ((result & CAPE_MAP_RESULT_UPDATED) || staged)
+                    used[i] = 1;
+            }
+            if (result & CAPE_MAP_RESULT_UPDATED)
+            {
+                e.track.failed_tracking = 0;
+                ++e.track.successive_matched;
+            }
+            else
+            {
+                ++e.track.failed_tracking;
+                e.track.successive_matched -= 1;
+            }
+            if (staged && e.track.successive_matched >= 4)
+                result |= CAPE_MAP_RESULT_PROMOTE;
+            else if (staged && e.track.failed_tracking >= 2)
+                result |= CAPE_MAP_RESULT_DROP;
+            else if (!staged && e.track.failed_tracking >= 10)
+                result |= CAPE_MAP_RESULT_LOST;
+            e.track.result = result;
+            out.push_back(std::move(e));
+        }
+        uint64_t id = *next_id;
+        if (flags & CAPE_MAP_ADD_STAGED)
+            for (int32_t i = 0; i < n_det; ++i)
+            {
+                if (used[i])
+                    continue;
+                const double* dp = det_planes + 4 * i;
+                MapEntry e {};
+                double planeCov[16];
+                if (!mt::plane_covariance(dp, dp[3], det_cov + 9 * i, planeCov) ||
+                    !mt::world_plane_covariance(dp, dp[3], T, planeCov, pose_covariance, e.track.covariance))
+                    continue;
+                mt::plane_to_world(dp, dp[3], T, e.plane.normal, &e.plane.d);
+                mt::normalize3(e.plane.normal); // the assignment to _parametrization
+                if (!to_world_space(det[i], T, e.polygon) || !(std::abs(mt::norm3(e.plane.normal) - 1.0) <= std::numeric_limits<double>::epsilon()) ||
+                    e.polygon.boundary().size() > CAPE_MAP_MAX_RING)
+                    continue;
+                e.track.flags = CAPE_MAP_TRACK_STAGED;
+                e.track.result = CAPE_MAP_RESULT_APPENDED;
+                e.track.id = id++;
+                out.push_back(std::move(e));
+            }
+        // sizes, then the arrays
+        int32_t nr = 0;
+        int64_t nv = 0;
+        for (const MapEntry& e : out)
+        {
+            nr += 1 + (int32_t)e.polygon.interior_rings().size();
+            nv += (int64_t)e.polygon.boundary().size();
+            for (const auto& h : e.polygon.interior_rings())
+                nv += (int64_t)h.size();
+        }
+        *n_planes_out = (int32_t)out.size();
+        *n_rings_out = nr;
+        *n_vertices_out = nv;
+        if ((int64_t)out.size() > planes_capacity || nr > rings_capacity || nv > vertices_capacity || !planes_out || !tracks_out ||
+            !rings_out || !vertices_out)
+            return CAPE_ERR_CAPACITY;
+        int32_t r = 0;
+        int64_t v = 0;
+        for (size_t j = 0; j < out.size(); ++j)
+        {
+            MapEntry& e = out[j];
+            const vector3 x = e.polygon.get_x_axis(), y = e.polygon.get_y_axis(), c = e.polygon.get_center();
+            for (int k = 0; k < 3; ++k)
+            {
+                e.plane.x_axis[k] = x[k];
+                e.plane.y_axis[k] = y[k];
+                e.plane.center[k] = c[k];
+            }
+            e.plane.ring_first = (uint32_t)r;
+            e.plane.ring_count = 1 + (uint32_t)e.polygon.interior_rings().size();
+            auto put = [&](const std::vector<vector2>& ring) {
+                rings_out[r].vertex_offset = (uint32_t)v;
+                rings_out[r].vertex_count = (uint32_t)ring.size();
+                ++r;
+                for (const vector2& p : ring)
+                {
+                    vertices_out[2 * v] = p[0];
+                    vertices_out[2 * v + 1] = p[1];
+                    ++v;
+                }
+            };
+            put(e.polygon.boundary());
+            for (const auto& h : e.polygon.interior_rings())
+                put(h);
+            planes_out[j] = e.plane;
+            tracks_out[j] = e.track;
+        }
+        if (used_out)
+            for (int32_t i = 0; i < n_det; ++i)
+                used_out[i] = used[i];
+        *next_id = id;
+        return 0;
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
+}
+
+// Test hooks of the covariance and Kalman algebra (tests/test_map_update_host.py restates them in numpy).  Each returns 1 on
+// success, 0 where the reference throws; cape_host_kalman_update returns the KalmanStatus.
+extern "C" int cape_host_covariance_valid(const double* M, int n) { return (n == 3 || n == 4) && rgbd_slam::map_tracking::is_covariance_valid(M, n); }
+extern "C" int cape_host_plane_covariance(const double* normal, double d, const double* cov9, double* out16)
+{
+    return rgbd_slam::map_tracking::plane_covariance(normal, d, cov9, out16);
+}
+extern "C" int cape_host_world_plane_covariance(const double* normal, double d, const double* camera_to_world, const double* plane_cov16,
+                                                const double* pose_cov9, double* out16)
+{
+    return rgbd_slam::map_tracking::world_plane_covariance(normal, d, camera_to_world, plane_cov16, pose_cov9, out16);
+}
+extern "C" int cape_host_kalman_update(const double* x, const double* P, const double* z, const double* R, double* x_out, double* P_out)
+{
+    return rgbd_slam::map_tracking::kalman_update(x, P, z, R, x_out, P_out);
 }

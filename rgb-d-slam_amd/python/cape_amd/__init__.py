@@ -171,7 +171,97 @@ def pack_map(planes):
     return P, R, V
 
 
+# cape_map_track (rgb-d-slam_amd/host/cape_host_map.h): the tracking state of a map plane, parallel to MAP_PLANE_DTYPE, for
+# host_map_update (the map update runs on the host only)
+MAP_TRACK_DTYPE = np.dtype([
+    ("covariance", "<f8", (4, 4)), ("successive_matched", "<i4"), ("failed_tracking", "<u4"), ("flags", "<u4"),
+    ("result", "<u4"), ("id", "<u8")], align=True)
+assert MAP_TRACK_DTYPE.itemsize == 16 * 8 + 4 * 4 + 8
+MAP_TRACK_STAGED, MAP_TRACK_MOVING = 1, 2
+(MAP_RESULT_MATCHED, MAP_RESULT_UPDATED, MAP_RESULT_FAIL_DETECTION, MAP_RESULT_FAIL_STATE, MAP_RESULT_FAIL_SINGULAR,
+ MAP_RESULT_FAIL_KALMAN, MAP_RESULT_FAIL_POLYGON, MAP_RESULT_OVERFLOW, MAP_RESULT_PROMOTE, MAP_RESULT_DROP, MAP_RESULT_LOST,
+ MAP_RESULT_APPENDED) = (1 << k for k in range(12))
+MAP_ADD_STAGED = 1
+
 _host_lib = None
+
+
+def _host_library():
+    """libcape_primitives.so (the host twins), loaded once"""
+    global _host_lib
+    if _host_lib is None:
+        load_library()  # (libcape_primitives links libcape_hip)
+        path = os.path.join(os.path.dirname(LIB_PATH), "libcape_primitives.so")
+        if not os.path.exists(path):
+            raise CapeError(f"{path} is missing: build it with `make -C rgb-d-slam_amd/csrc host`")
+        L = C.CDLL(path)
+        vp = C.c_void_p
+        L.cape_host_match_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
+                                          C.c_uint32, vp, vp, vp]
+        L.cape_host_match_map.restype = C.c_int
+        L.cape_host_map_update.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp,
+                                           vp, C.c_uint32, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp]
+        L.cape_host_map_update.restype = C.c_int
+        _host_lib = L
+    return _host_lib
+
+
+def host_map_update(map_arrays, tracks, match, detected, camera_to_world, pose_covariance, flags=0, next_id=0):
+    """cape_host_map_update of libcape_primitives.so: Feature_Map::update_map for ONE frame on the host class -- every matched
+    map plane goes through update_with_match (covariance, Kalman step, polygon union), every plane's counters follow, and with
+    flags=MAP_ADD_STAGED the unused kept planes are appended as staged planes.
+
+    map_arrays: pack_map(...); tracks: MAP_TRACK_DTYPE array parallel to the planes; match: n_map kept-plane indices or -1
+    (host_match_map's first result); detected: the frame's kept planes as host_match_map takes them, each with an 8th item, the
+    3 x 3 point-cloud covariance (cape_plane_segment.cov); camera_to_world: 4 x 4; pose_covariance: 3 x 3.
+    Returns ((planes, rings, vertices), tracks, used[n_det] bool, next_id) -- the new map in pack_map's layout."""
+    L = _host_library()
+    P, R, V = map_arrays
+    P = np.ascontiguousarray(P, MAP_PLANE_DTYPE)
+    R = np.ascontiguousarray(R, MAP_RING_DTYPE)
+    V = np.ascontiguousarray(V, np.float64).reshape(-1, 2)
+    Tr = np.ascontiguousarray(tracks, MAP_TRACK_DTYPE)
+    n_map, n_det = len(P), len(detected)
+    if len(Tr) != n_map:
+        raise CapeError("host_map_update: one track per map plane")
+    M = np.ascontiguousarray(match, np.int32).reshape(-1)
+    if len(M) != n_map:
+        raise CapeError("host_map_update: one match per map plane")
+    dp = np.zeros((max(n_det, 1), 4))
+    dcov = np.zeros((max(n_det, 1), 9))
+    df = np.zeros((max(n_det, 1), 9))
+    dc = np.zeros(max(n_det, 1), np.int32)
+    rings = []
+    for i, (normal, d, x_axis, y_axis, center, ring, _area, cov) in enumerate(detected):
+        dp[i, :3], dp[i, 3] = normal, d
+        dcov[i] = np.asarray(cov, np.float64).reshape(9)
+        df[i, 0:3], df[i, 3:6], df[i, 6:9] = x_axis, y_axis, center
+        r = np.ascontiguousarray(ring, np.float64).reshape(-1, 2)
+        dc[i] = len(r)
+        rings.append(r)
+    dv = np.ascontiguousarray(np.concatenate(rings) if rings else np.zeros((1, 2)), np.float64)
+    T = np.ascontiguousarray(camera_to_world, np.float64).reshape(16)
+    S = np.ascontiguousarray(pose_covariance, np.float64).reshape(9)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    nid = C.c_uint64(next_id)
+    n_p, n_r, n_v = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    used = np.zeros(max(n_det, 1), np.int32)
+    cap_p, cap_r, cap_v = n_map + n_det, 2 * (len(R) + n_det) + 8, 2 * (len(V) + int(dc[:n_det].sum())) + 64
+    for _ in range(2):  # the second pass with the sizes the first one reported
+        Po = np.zeros(max(cap_p, 1), MAP_PLANE_DTYPE)
+        Ro = np.zeros(max(cap_r, 1), MAP_RING_DTYPE)
+        Vo = np.zeros((max(cap_v, 1), 2))
+        To = np.zeros(max(cap_p, 1), MAP_TRACK_DTYPE)
+        rc = L.cape_host_map_update(ptr(P), n_map, ptr(R), len(R), ptr(V), len(V), ptr(Tr), ptr(M), n_det, ptr(dp), ptr(dcov),
+                                    ptr(df), ptr(dv), ptr(dc), ptr(T), ptr(S), flags, C.byref(nid), ptr(Po), len(Po), ptr(Ro),
+                                    len(Ro), ptr(Vo), len(Vo), ptr(To), C.byref(n_p), C.byref(n_r), C.byref(n_v), ptr(used))
+        if rc != -4:  # CAPE_ERR_CAPACITY
+            break
+        cap_p, cap_r, cap_v = n_p.value, n_r.value, n_v.value
+    if rc != 0:
+        raise CapeError(f"cape_host_map_update failed ({rc})")
+    return ((Po[:n_p.value].copy(), Ro[:n_r.value].copy(), Vo[:n_v.value].copy()), To[:n_p.value].copy(),
+            used[:n_det].astype(bool), nid.value)
 
 
 def host_match_map(map_arrays, detected, world_to_camera=None, skip=None, flags=0, areas=False):
@@ -187,18 +277,7 @@ def host_match_map(map_arrays, detected, world_to_camera=None, skip=None, flags=
 def host_match_map_call(map_arrays, detected, world_to_camera=None, skip=None, flags=0, areas=False):
     """host_match_map with the arguments packed now and the native call deferred: returns run(), which makes only the call and
     returns host_match_map's result (timing the twin from several threads without the packing)."""
-    global _host_lib
-    if _host_lib is None:
-        load_library()  # (libcape_primitives links libcape_hip)
-        path = os.path.join(os.path.dirname(LIB_PATH), "libcape_primitives.so")
-        if not os.path.exists(path):
-            raise CapeError(f"{path} is missing: build it with `make -C rgb-d-slam_amd/csrc host`")
-        L = C.CDLL(path)
-        vp = C.c_void_p
-        L.cape_host_match_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
-                                          C.c_uint32, vp, vp, vp]
-        L.cape_host_match_map.restype = C.c_int
-        _host_lib = L
+    _host_library()
     P, R, V = map_arrays
     n_det = len(detected)
     dp = np.zeros((max(n_det, 1), 4))
