@@ -172,23 +172,51 @@ typedef struct cape_frame_record
  * so each rank PACKS its shard on the device into one buffer of a fixed byte count (what ncclAllGather needs):
  *
  *   cape_packed_header | frames_capacity x cape_packed_frame | planes_capacity x cape_packed_plane |
- *   cylinders_capacity x cape_packed_cylinder | [frames_capacity x cells u8 plane labels | same, cylinder labels]
+ *   cylinders_capacity x cape_packed_cylinder | [frames_capacity x cells u8 plane labels | same, cylinder labels] |
+ *   [cape_packed_polygon_header | polygons_capacity x cape_polygon | vertices_capacity x 2 doubles]
  *
  * planes_capacity = frames_capacity x planes_per_frame is a budget for the whole shard, not per frame: nothing is
  * truncated unless the shard's TOTAL exceeds it, which the header reports (planes_per_frame = CAPE_MAX_PLANES can never
  * overflow).  Sections start on 16-byte boundaries; cape_gather_layout has the offsets.
+ *
+ * The label grids travel with CAPE_GATHER_LABELS.  The last three sections travel with CAPE_GATHER_POLYGONS (they come last,
+ * behind the label grids when both flags are set; every other section keeps the offset and the bytes it has without the flag):
+ * the boundary polygon of every packed plane as cape_build_polygons built it, so that a receiver can tell which planes the
+ * reference keeps (CAPE_POLY_VALID and >= 3 vertices: the indices of its plane_container) and hand the rings to find_matches /
+ * the map update.  polygons_capacity = planes_capacity: polygon k belongs to plane k of the planes section, so
+ * cape_packed_frame.plane_offset / n_planes index both.  A packed cape_polygon is the record cape_copy_polygons shows for that
+ * segment, bit for bit, except that `segment` is the index in the FRAME's segment list (= cape_packed_plane.segment) and
+ * `vertex_offset` counts from the start of the shard's vertex section.  The rings lie in that section in plane order, without
+ * gaps.  vertices_capacity = frames_capacity x vertices_per_frame is a budget for the shard like planes_capacity, and a ring
+ * travels whole or not at all: the rings that travel are exactly the longest prefix, in packed-plane order, of the rings whose
+ * vertices fit the budget together.  A ring beyond it leaves its polygon with vertex_count = 0 and vertex_offset = UINT32_MAX
+ * (flags, axes, centre and area are kept), and the header says CAPE_PACKED_VERTICES_DROPPED.  A polygon that has no ring on the
+ * producing GPU either (CAPE_POLY_OVERFLOW, CAPE_POLY_REJECTED) has vertex_count = 0 and vertex_offset = 0.  A plane that was
+ * dropped itself (CAPE_PACKED_PLANES_DROPPED) has no polygon.  vertices_per_frame = boundary_capacity can never overflow for
+ * frames of one record (a ring's vertices are boundary points of its record's slab); a frame that continues in spill records
+ * holds at most boundary_capacity vertices per record of its chain, so boundary_capacity x (1 + spill_records) per frame --
+ * or, for the shard, boundary_capacity x (frames_capacity + spill_records) vertices in all -- can never overflow.
  */
 #define CAPE_PACKED_MAGIC 0x43415045u /* "CAPE" */
 enum
 {
-    CAPE_GATHER_LABELS = 1u << 0 /* also ship _gridPlaneSegmentMap / _gridCylinderSegMap, one byte per cell each */
+    CAPE_GATHER_LABELS = 1u << 0, /* also ship _gridPlaneSegmentMap / _gridCylinderSegMap, one byte per cell each */
+    CAPE_GATHER_POLYGONS = 1u << 1 /* also ship the boundary polygon of every packed plane (cape_build_polygons of the batch first) */
 };
+/* vertices_per_frame when none is asked for (0, or cape_gather_configure with CAPE_GATHER_POLYGONS).  Measured with
+ * cape_count_polygon_vertices on 640 x 480 batches (profiles/r08_gather_polygons.txt): 32.5 vertices per frame on the 4 096-frame
+ * room batch (at most 102 in one frame), 8.0 on the tunnel batch (51), 57.3 on the 2 048-frame TUM-like stream (156).  The default
+ * covers the largest of the three means with 25 % headroom, ceil(1.25 x 57.34) = 72 -- the rule INTEGRATION.md gives for
+ * planes_per_frame; a caller with other scenes sizes the budget from its own previous batch the same way. */
+#define CAPE_GATHER_DEFAULT_VERTICES_PER_FRAME 72
 enum
 {
     CAPE_PACKED_PLANES_DROPPED = 1u << 0,   /* cape_packed_header.overflow */
     CAPE_PACKED_CYLINDERS_DROPPED = 1u << 1,
-    CAPE_PACKED_LABELS_CLIPPED = 1u << 2    /* a frame of the shard holds more than 255 plane segments / cylinder labels: its label
+    CAPE_PACKED_LABELS_CLIPPED = 1u << 2,   /* a frame of the shard holds more than 255 plane segments / cylinder labels: its label
                                                grids (one byte per cell on the wire) read 255 where the label is larger */
+    CAPE_PACKED_VERTICES_DROPPED = 1u << 3  /* CAPE_GATHER_POLYGONS: the rings of the shard hold more vertices than vertices_capacity;
+                                               the longest prefix of rings that fits travels, the others have vertex_count = 0 */
 };
 typedef struct cape_packed_header
 {
@@ -208,13 +236,16 @@ typedef struct cape_packed_header
 typedef struct cape_packed_frame
 {
     int32_t plane_offset;       /* first plane of the frame in the planes section */
-    int32_t n_planes;           /* planeContainer.size() before the polygon validity test */
+    int32_t n_planes;           /* planeContainer.size() before the polygon validity test (primitive_detection.cpp:623-631); with
+                                   CAPE_GATHER_POLYGONS the planes the reference keeps are those whose packed polygon has
+                                   CAPE_POLY_VALID and >= 3 vertices, in this order */
     int32_t cylinder_offset;
     int32_t n_cylinders;        /* cylinderContainer.size() */
     uint32_t status;            /* CAPE_FRAME_* */
     int32_t n_plane_segments;
 } cape_packed_frame;
-typedef struct cape_packed_plane /* SURVEY.md 8e record: what Plane(planeSeg, polygon) is built from, minus the polygon */
+typedef struct cape_packed_plane /* SURVEY.md 8e record: the planeSeg of Plane(planeSeg, polygon); the polygon is entry k of the
+                                    polygons section for plane k with CAPE_GATHER_POLYGONS, and does not travel without it */
 {
     double normal[3];           /* Plane::get_normal() */
     double d;                   /* Plane::get_d() */
@@ -236,7 +267,7 @@ typedef struct cape_gather_config
     int32_t frames_capacity;     /* largest shard (frames per rank) this handle will pack; <= max_batch */
     int32_t planes_per_frame;    /* budget: planes_capacity = frames_capacity x planes_per_frame; 0 = 16; <= 4096 */
     int32_t cylinders_per_frame; /* 0 = 8 */
-    uint32_t flags;              /* CAPE_GATHER_LABELS */
+    uint32_t flags;              /* CAPE_GATHER_LABELS | CAPE_GATHER_POLYGONS */
 } cape_gather_config;
 typedef struct cape_gather_layout
 {
@@ -244,6 +275,20 @@ typedef struct cape_gather_layout
     uint64_t frames_offset, planes_offset, cylinders_offset, plane_labels_offset, cyl_labels_offset; /* labels: 0 if absent */
     int32_t frames_capacity, planes_capacity, cylinders_capacity, cells;
 } cape_gather_layout;
+/* the sections CAPE_GATHER_POLYGONS appends (cape_gather_configure_polygons) */
+typedef struct cape_packed_polygon_header
+{
+    int64_t n_vertices_total;   /* vertices of the rings of every plane found in the shard (= cape_count_polygon_vertices); only the
+                                   rings of the longest prefix that fits vertices_capacity are listed */
+    int32_t vertices_capacity;
+    int32_t n_polygons_valid;   /* planes found in the shard that the reference keeps (CAPE_POLY_VALID and >= 3 vertices) */
+} cape_packed_polygon_header;
+typedef struct cape_gather_polygon_layout
+{
+    uint64_t polygon_header_offset, polygons_offset, vertices_offset;
+    int32_t polygons_capacity;  /* = planes_capacity */
+    int32_t vertices_capacity;  /* = frames_capacity x vertices_per_frame */
+} cape_gather_polygon_layout;
 
 /* Per-cell statistics (debug / parity access to Primitive_Detection::_planeGrid, _cellDistanceTols,
  * Histogram::_bins; primitive_detection.hpp:205-218).  One struct per cell, cell-row-major. */
@@ -540,9 +585,18 @@ int cape_device_results(cape_handle h, void** records, int32_t** plane_labels, i
 /* Sizes the packed buffer (two staging slots of bytes_per_rank on the device) and reports its layout.  May be called
  * again to change the capacities (synchronises). */
 int cape_gather_configure(cape_handle h, const cape_gather_config* cfg, cape_gather_layout* layout_out);
+/* The same with CAPE_GATHER_POLYGONS implied and the vertex budget of the polygon sections: vertices_capacity = frames_capacity x
+ * vertices_per_frame (0 = CAPE_GATHER_DEFAULT_VERTICES_PER_FRAME; the product must fit an int32).  layout_out is filled as by
+ * cape_gather_configure, bytes_per_rank including the appended sections; polygon_layout_out has their offsets.  Either may be NULL.
+ * cape_gather_configure with the flag in cfg->flags is this call with vertices_per_frame = 0. */
+int cape_gather_configure_polygons(cape_handle h, const cape_gather_config* cfg, int32_t vertices_per_frame, cape_gather_layout* layout_out,
+                                   cape_gather_polygon_layout* polygon_layout_out);
 /* Packs the results of the last cape_extract (frames [0, n_frames) of it) into the next staging slot, asynchronously on
  * `stream`; first_frame goes into the header.  *packed_dev (optional) receives the slot's device address. */
 int cape_pack_primitives(cape_handle h, int32_t n_frames, int32_t first_frame, void** packed_dev, void* stream);
+/* (With CAPE_GATHER_POLYGONS, cape_pack_primitives and the two gathers need the polygons of the frames they pack: CAPE_ERR_CAPACITY,
+ * and nothing is packed, when n_frames exceeds the frames of the last cape_build_polygons of the current batch -- the rule of
+ * cape_device_polygons / cape_copy_polygons.) */
 /* Synchronous copy of the slot filled by the last cape_pack_primitives / cape_gather_primitives (bytes_per_rank bytes). */
 int cape_copy_packed(cape_handle h, void* packed_host);
 
@@ -581,6 +635,10 @@ int cape_gather_primitives_root(cape_handle h, int32_t n_frames, int32_t first_f
  * with -- e.g. ceil(1.25 x n_planes / n_frames) + 1 from the previous batch of the same stream -- instead of the default
  * budget.  Synchronous (waits for the batch).  Any output pointer may be NULL. */
 int cape_count_primitives(cape_handle h, int32_t n_frames, int32_t* n_planes, int32_t* n_cylinders, int32_t* max_planes_per_frame);
+/* Its companion for the vertex budget of CAPE_GATHER_POLYGONS: the ring vertices of every output plane of frames [0, n_frames) of the
+ * last cape_build_polygons (record chains followed), and the most one frame holds.  Synchronous.  CAPE_ERR_CAPACITY when
+ * cape_build_polygons of the current batch does not cover n_frames.  Either output pointer may be NULL. */
+int cape_count_polygon_vertices(cape_handle h, int32_t n_frames, int64_t* n_vertices, int32_t* max_vertices_per_frame);
 /* Orders after the last cape_gather_primitives: with host_sync != 0 the call returns when the gather has landed,
  * otherwise `stream` is made to wait for it (hipStreamWaitEvent). */
 int cape_gather_wait(cape_handle h, void* stream, int32_t host_sync);

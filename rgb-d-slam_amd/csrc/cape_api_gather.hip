@@ -1,6 +1,7 @@
 // C ABI, host side: the multi-GPU gather of the packed primitive lists (see cape_gather.hip) -- packing, the RCCL communicator,
 // the gathers and the primitive count.
 #include <cstring>
+#include <limits>
 
 #include "cape_handle.h"
 
@@ -10,9 +11,11 @@ namespace {
 
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-void fill_layout(const cape_handle_s* h, const cape_gather_config& c, cape_gather_layout& L)
+void fill_layout(const cape_handle_s* h, const cape_gather_config& c, int vertices_per_frame, cape_gather_layout& L,
+                 cape_gather_polygon_layout& PL)
 {
     L = cape_gather_layout{};
+    PL = cape_gather_polygon_layout{};
     L.frames_capacity = c.frames_capacity;
     L.planes_capacity = c.frames_capacity * c.planes_per_frame;
     L.cylinders_capacity = c.frames_capacity * c.cylinders_per_frame;
@@ -31,7 +34,99 @@ void fill_layout(const cape_handle_s* h, const cape_gather_config& c, cape_gathe
         L.cyl_labels_offset = off;
         off = align16(off + (size_t)L.frames_capacity * h->cells);
     }
+    if (c.flags & CAPE_GATHER_POLYGONS)
+    {
+        // appended behind everything the buffer holds without the flag: those sections keep their offsets
+        PL.polygons_capacity = L.planes_capacity;
+        PL.vertices_capacity = c.frames_capacity * vertices_per_frame;
+        PL.polygon_header_offset = off;
+        off = align16(off + sizeof(cape_packed_polygon_header));
+        PL.polygons_offset = off;
+        off = align16(off + (size_t)PL.polygons_capacity * sizeof(cape_polygon));
+        PL.vertices_offset = off;
+        off = align16(off + (size_t)PL.vertices_capacity * 2 * sizeof(double));
+    }
     L.bytes_per_rank = off;
+}
+
+// scratch of the pack kernels with CAPE_GATHER_POLYGONS: per frame an int2 (ring vertices, kept polygons) and a 64-bit vertex offset,
+// then one 64-bit word (vertices of the shipped rings)
+size_t ring_scratch_bytes(int frames) { return (size_t)frames * (sizeof(int2) + sizeof(long long)) + sizeof(unsigned long long); }
+
+// the polygons of cape_build_polygons cover frames [0, n_frames) of the current batch (the rule of cape_copy_polygons)
+int require_polygons(const cape_handle_s* h, int n_frames, const char* who)
+{
+    if (n_frames > h->poly.frames)
+        return fail(CAPE_ERR_CAPACITY, std::string(who) + ": n_frames exceeds the frames of the last cape_build_polygons of the current batch "
+                                                          "(call cape_build_polygons after cape_extract first)");
+    return CAPE_OK;
+}
+
+// what the pack and count kernels read of the batch: its records and, with polygons, their rows and vertex slabs
+void bind_batch(const cape_handle_s* h, int n_frames, bool polygons, cape::PackParams& p)
+{
+    p.records = h->res.records;
+    p.recordsBase = h->res.records;
+    p.poolBase = h->cfg.max_batch;
+    p.nFrames = n_frames;
+    if (polygons)
+    {
+        p.polygonsIn = h->poly.polygons;
+        p.verticesIn = reinterpret_cast<const double2*>(h->poly.vertices.get());
+        p.boundaryCapacity = h->boundaryCap;
+    }
+}
+
+int configure_impl(cape_handle h, const cape_gather_config* cfg, int32_t vertices_per_frame, bool polygons, cape_gather_layout* layout_out,
+                   cape_gather_polygon_layout* polygon_layout_out)
+{
+    if (!h || !cfg)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument");
+    cape_gather_config c = *cfg;
+    if (polygons)
+        c.flags |= CAPE_GATHER_POLYGONS;
+    if (c.planes_per_frame == 0)
+        c.planes_per_frame = 16;
+    if (c.cylinders_per_frame == 0)
+        c.cylinders_per_frame = 8;
+    if (vertices_per_frame == 0)
+        vertices_per_frame = CAPE_GATHER_DEFAULT_VERTICES_PER_FRAME;
+    if (c.frames_capacity <= 0 || c.frames_capacity > h->cfg.max_batch || c.planes_per_frame < 0 ||
+        c.planes_per_frame > 4096 || c.cylinders_per_frame < 0 || c.cylinders_per_frame > 4096 ||
+        (c.flags & ~(uint32_t)(CAPE_GATHER_LABELS | CAPE_GATHER_POLYGONS)))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "frames_capacity in [1, max_batch], planes/cylinders per frame in [1, 4096], known flags");
+    if (vertices_per_frame < 0 || (int64_t)c.frames_capacity * vertices_per_frame > std::numeric_limits<int32_t>::max())
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "vertices_per_frame >= 0 and frames_capacity x vertices_per_frame within an int32");
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(hipDeviceSynchronize()); // nothing may still read the old slots
+    auto& G = h->gather;
+    cape_gather_layout L;
+    cape_gather_polygon_layout PL;
+    fill_layout(h, c, vertices_per_frame, L, PL);
+    for (int k = 0; k < 2; ++k)
+    {
+        G.packed[k].reset();
+        G.packedBusy[k] = false;
+    }
+    G.pending = false;
+    for (int k = 0; k < 2; ++k)
+    {
+        CAPE_HIP_TRY(G.packed[k].alloc(L.bytes_per_rank));
+        CAPE_HIP_TRY(hipMemset(G.packed[k], 0, L.bytes_per_rank));
+        CAPE_HIP_TRY(G.packedFree[k].ensure());
+    }
+    if (c.flags & CAPE_GATHER_POLYGONS)
+        CAPE_HIP_TRY(G.ringScratch.alloc(ring_scratch_bytes(c.frames_capacity)));
+    CAPE_HIP_TRY(G.packReady.ensure());
+    CAPE_HIP_TRY(G.done.ensure());
+    G.cfg = c;
+    G.layout = L;
+    G.polygonLayout = PL;
+    if (layout_out)
+        *layout_out = L;
+    if (polygon_layout_out)
+        *polygon_layout_out = PL;
+    return CAPE_OK;
 }
 
 // default capacities the first time a pack / gather is asked for without cape_gather_configure
@@ -47,6 +142,10 @@ int ensure_gather_configured(cape_handle_s* h)
 int pack_into_next_slot(cape_handle_s* h, int n_frames, int first_frame, hipStream_t stream)
 {
     auto& G = h->gather;
+    const bool polygons = (G.cfg.flags & CAPE_GATHER_POLYGONS) != 0;
+    if (polygons)
+        if (const int rc = require_polygons(h, n_frames, "packing with CAPE_GATHER_POLYGONS"); rc != CAPE_OK)
+            return rc; // (before anything is written: nothing is packed)
     const int slot = G.packSlot ^ 1;
     // the slot may still be read by the all-gather of two batches ago
     if (G.packedBusy[slot])
@@ -57,9 +156,7 @@ int pack_into_next_slot(cape_handle_s* h, int n_frames, int first_frame, hipStre
     const cape_gather_layout& L = G.layout;
     unsigned char* base = G.packed[slot];
     cape::PackParams p{};
-    p.records = h->res.records;
-    p.recordsBase = h->res.records;
-    p.poolBase = h->cfg.max_batch;
+    bind_batch(h, n_frames, polygons, p);
     p.planeLabelsIn = h->res.planeLabels;
     p.cylLabelsIn = h->res.cylLabels;
     p.header = reinterpret_cast<cape_packed_header*>(base);
@@ -68,13 +165,24 @@ int pack_into_next_slot(cape_handle_s* h, int n_frames, int first_frame, hipStre
     p.cylinders = reinterpret_cast<cape_packed_cylinder*>(base + L.cylinders_offset);
     p.planeLabels8 = L.plane_labels_offset ? base + L.plane_labels_offset : nullptr;
     p.cylLabels8 = L.cyl_labels_offset ? base + L.cyl_labels_offset : nullptr;
-    p.nFrames = n_frames;
     p.firstFrame = first_frame;
     p.framesCapacity = L.frames_capacity;
     p.planesCapacity = L.planes_capacity;
     p.cylindersCapacity = L.cylinders_capacity;
     p.cells = h->cells;
     p.flags = G.cfg.flags;
+    if (polygons)
+    {
+        const cape_gather_polygon_layout& PL = G.polygonLayout;
+        p.polygonHeader = reinterpret_cast<cape_packed_polygon_header*>(base + PL.polygon_header_offset);
+        p.polygons = reinterpret_cast<cape_polygon*>(base + PL.polygons_offset);
+        p.vertices = reinterpret_cast<double2*>(base + PL.vertices_offset);
+        p.verticesCapacity = PL.vertices_capacity;
+        unsigned char* scratch = G.ringScratch;
+        p.frameRings = reinterpret_cast<int2*>(scratch);
+        p.frameVertexOffset = reinterpret_cast<long long*>(scratch + (size_t)L.frames_capacity * sizeof(int2));
+        p.verticesUsed = reinterpret_cast<unsigned long long*>(scratch + (size_t)L.frames_capacity * (sizeof(int2) + sizeof(long long)));
+    }
     CAPE_HIP_TRY(cape::launch_pack(p, stream));
     G.packSlot = slot;
     return CAPE_OK;
@@ -134,41 +242,15 @@ extern "C" {
 
 int cape_gather_configure(cape_handle h, const cape_gather_config* cfg, cape_gather_layout* layout_out)
 {
-    if (!h || !cfg)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument");
-    cape_gather_config c = *cfg;
-    if (c.planes_per_frame == 0)
-        c.planes_per_frame = 16;
-    if (c.cylinders_per_frame == 0)
-        c.cylinders_per_frame = 8;
-    if (c.frames_capacity <= 0 || c.frames_capacity > h->cfg.max_batch || c.planes_per_frame < 0 ||
-        c.planes_per_frame > 4096 || c.cylinders_per_frame < 0 || c.cylinders_per_frame > 4096 ||
-        (c.flags & ~(uint32_t)CAPE_GATHER_LABELS))
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "frames_capacity in [1, max_batch], planes/cylinders per frame in [1, 4096], known flags");
-    CAPE_ON_DEVICE(h);
-    CAPE_HIP_TRY(hipDeviceSynchronize()); // nothing may still read the old slots
-    auto& G = h->gather;
-    cape_gather_layout L;
-    fill_layout(h, c, L);
-    for (int k = 0; k < 2; ++k)
-    {
-        G.packed[k].reset();
-        G.packedBusy[k] = false;
-    }
-    G.pending = false;
-    for (int k = 0; k < 2; ++k)
-    {
-        CAPE_HIP_TRY(G.packed[k].alloc(L.bytes_per_rank));
-        CAPE_HIP_TRY(hipMemset(G.packed[k], 0, L.bytes_per_rank));
-        CAPE_HIP_TRY(G.packedFree[k].ensure());
-    }
-    CAPE_HIP_TRY(G.packReady.ensure());
-    CAPE_HIP_TRY(G.done.ensure());
-    G.cfg = c;
-    G.layout = L;
-    if (layout_out)
-        *layout_out = L;
-    return CAPE_OK;
+    return configure_impl(h, cfg, 0, false, layout_out, nullptr);
+}
+
+int cape_gather_configure_polygons(cape_handle h, const cape_gather_config* cfg, int32_t vertices_per_frame, cape_gather_layout* layout_out,
+                                   cape_gather_polygon_layout* polygon_layout_out)
+{
+    if (vertices_per_frame < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "negative vertices_per_frame");
+    return configure_impl(h, cfg, vertices_per_frame, true, layout_out, polygon_layout_out);
 }
 
 int cape_pack_primitives(cape_handle h, int32_t n_frames, int32_t first_frame, void** packed_dev, void* stream_)
@@ -320,6 +402,35 @@ int cape_count_primitives(cape_handle h, int32_t n_frames, int32_t* n_planes, in
         *n_cylinders = tot[1];
     if (max_planes_per_frame)
         *max_planes_per_frame = tot[2];
+    return CAPE_OK;
+}
+
+int cape_count_polygon_vertices(cape_handle h, int32_t n_frames, int64_t* n_vertices, int32_t* max_vertices_per_frame)
+{
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    if (n_frames > h->res.lastFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the last cape_extract batch");
+    if (const int rc = require_polygons(h, n_frames, "cape_count_polygon_vertices"); rc != CAPE_OK)
+        return rc;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    unsigned long long tot[2] = {0ull, 0ull};
+    if (n_frames > 0)
+    {
+        CAPE_HIP_TRY(h->gather.vertexCountScratch.ensure(2));
+        CAPE_HIP_TRY(sync_handle(h)); // behind the batch and its polygons, wherever they were enqueued (as cape_count_primitives)
+        hipStream_t st = nullptr;
+        cape::PackParams p{};
+        bind_batch(h, n_frames, true, p);
+        CAPE_HIP_TRY(cape::launch_count_polygon_vertices(p, h->gather.vertexCountScratch, st));
+        CAPE_HIP_TRY(hipMemcpyAsync(tot, h->gather.vertexCountScratch, sizeof(tot), hipMemcpyDeviceToHost, st));
+        CAPE_HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (n_vertices)
+        *n_vertices = (int64_t)tot[0];
+    if (max_vertices_per_frame)
+        *max_vertices_per_frame = (int32_t)tot[1];
     return CAPE_OK;
 }
 

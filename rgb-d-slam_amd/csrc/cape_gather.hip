@@ -7,13 +7,18 @@
 //
 //   [cape_packed_header][frames_capacity x cape_packed_frame][planes_capacity x cape_packed_plane]
 //   [cylinders_capacity x cape_packed_cylinder][frames_capacity x cells u8 plane labels][same, cylinder labels]
+//   [cape_packed_polygon_header][planes_capacity x cape_polygon][vertices_capacity x double2]      (CAPE_GATHER_POLYGONS)
 //
 // with the capacities sized per BATCH (frames_capacity x planes_per_frame), so a frame with 40 planes costs nothing as
 // long as the batch average stays under planes_per_frame; planes_per_frame = CAPE_MAX_PLANES can never overflow, and an
 // overflow is reported in the header, never silent.  Every rank sends the same byte count, which is what one
 // ncclAllGather needs.  Two kernels: an exclusive scan of the per-frame counts (one workgroup), then one wavefront per
 // frame that copies its primitives -- CAPE_MAX_PLANES = CAPE_MAX_CYLINDERS = 64 = the wave width, so the rank of a
-// kept primitive among its frame's is a ballot + popcount.
+// kept primitive among its frame's is a ballot + popcount.  With CAPE_GATHER_POLYGONS the boundary polygon of every packed plane
+// travels too (what a receiver needs to rebuild the reference's plane_container and to run find_matches on a remote frame): a
+// count kernel (one wavefront per frame) sums the ring vertices of each frame, the scan turns them into the frame's first vertex,
+// and the frame's wavefront ranks its rings with a wave prefix sum and copies them ring after ring, all 64 lanes over the 16-byte
+// vertices of one ring.
 //
 // The collective is RCCL, called from this layer (north_star: "host code stays C++ and calls into a thin extern-C HIP
 // layer ... RCCL-over-xGMI gather"): librccl is resolved with dlopen at the first cape_comm_* call, so single-GPU users
@@ -26,34 +31,97 @@
 #include <string>
 
 #include "cape_internal.h"
+#include "cape_wave.h"
 
 namespace cape {
 
 constexpr int kScanThreads = 1024;
 
-// exclusive scan of (n_planes, n_cylinders) over the frames of the shard; writes the frame table and the header
-__global__ __launch_bounds__(kScanThreads) void cape_pack_scan_kernel(PackParams p)
+// vertices of a polygon's ring as the pack kernels read it: none for a row that does not describe a ring inside its record's slab
+__device__ __forceinline__ uint32_t ring_vertices(const cape_polygon& g, int boundaryCapacity)
+{
+    return (unsigned long long)g.vertex_offset + g.vertex_count <= (unsigned long long)boundaryCapacity ? g.vertex_count : 0u;
+}
+
+// the record that continues `rec` (cape_frame_header::next_record), or null
+__device__ __forceinline__ const cape_frame_record* next_record(const PackParams& p, const cape_frame_record& rec)
+{
+    return rec.header.next_record >= p.poolBase ? p.recordsBase + rec.header.next_record : nullptr;
+}
+
+// CAPE_GATHER_POLYGONS, one wavefront per frame: (ring vertices, polygons the reference keeps) of the frame's output planes over every
+// record of its chain -- the polygon row of a record lies at the record's own index, like its vertex slab.  Feeds the scan below
+// (frameRings) and cape_count_polygon_vertices (totals: [0] sum, [1] largest frame).
+__global__ __launch_bounds__(256) void cape_count_polygon_vertices_kernel(PackParams p, unsigned long long* totals)
+{
+    const int lane = threadIdx.x & 63;
+    const int frame = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (frame >= p.nFrames)
+        return;
+    int verts = 0, valid = 0;
+    for (const cape_frame_record* recp = &p.records[frame]; recp; recp = next_record(p, *recp))
+    {
+        const cape_frame_record& rec = *recp;
+        if (lane < rec.header.n_plane_segments && rec.segments[lane].is_output != 0)
+        {
+            const cape_polygon& g = p.polygonsIn[(size_t)(recp - p.recordsBase) * CAPE_MAX_PLANES + lane];
+            const uint32_t c = ring_vertices(g, p.boundaryCapacity);
+            verts += (int)c;
+            valid += ((g.flags & CAPE_POLY_VALID) && c >= 3u) ? 1 : 0;
+        }
+    }
+    verts = wave_sum_i32(verts);
+    valid = wave_sum_i32(valid);
+    if (lane == 0)
+    {
+        if (p.frameRings)
+            p.frameRings[frame] = make_int2(verts, valid);
+        if (totals)
+        {
+            atomicAdd(&totals[0], (unsigned long long)verts);
+            atomicMax(&totals[1], (unsigned long long)verts);
+        }
+    }
+}
+
+// exclusive scan of (n_planes, n_cylinders) -- and, with CAPE_GATHER_POLYGONS, of the frames' ring vertices -- over the frames of the
+// shard; writes the frame table and the header(s)
+template <bool kPolygons> __global__ __launch_bounds__(kScanThreads) void cape_pack_scan_kernel(PackParams p)
 {
     __shared__ int s_p[kScanThreads], s_c[kScanThreads];
+    __shared__ long long s_v[kPolygons ? kScanThreads : 1];
+    __shared__ int s_q[kPolygons ? kScanThreads : 1];
     __shared__ unsigned s_status;
     const int t = threadIdx.x;
     const int per = (p.nFrames + kScanThreads - 1) / kScanThreads;
     const int f0 = t * per, f1 = min(f0 + per, p.nFrames);
     if (t == 0)
         s_status = 0u;
-    int sp = 0, sc = 0;
+    int sp = 0, sc = 0, sq = 0;
+    long long sv = 0;
     unsigned st = 0;
     for (int f = f0; f < f1; ++f)
     {
         const cape_frame_header& h = p.records[f].header; // (a frame's first record holds the whole frame's counts)
         sp += h.n_planes;
         sc += h.n_cylinders;
+        if constexpr (kPolygons)
+        {
+            const int2 r = p.frameRings[f];
+            sv += r.x;
+            sq += r.y;
+        }
         st |= h.status & 0xFFu; // the flag bits; bits 8..15 are a per-frame COUNT (not-planar-after-merge), which an OR would garble
         if (h.n_plane_segments > 255 || h.n_cylinder_labels > 255)
             st |= 1u << 31; // label grids travel as bytes: folded into hd.overflow below
     }
     s_p[t] = sp;
     s_c[t] = sc;
+    if constexpr (kPolygons)
+    {
+        s_v[t] = sv;
+        s_q[t] = sq;
+    }
     __syncthreads();
     if (st)
         atomicOr(&s_status, st);
@@ -61,12 +129,25 @@ __global__ __launch_bounds__(kScanThreads) void cape_pack_scan_kernel(PackParams
     for (int o = 1; o < kScanThreads; o <<= 1)
     {
         const int ap = (t >= o) ? s_p[t - o] : 0, ac = (t >= o) ? s_c[t - o] : 0;
+        long long av = 0;
+        int aq = 0;
+        if constexpr (kPolygons)
+        {
+            av = (t >= o) ? s_v[t - o] : 0;
+            aq = (t >= o) ? s_q[t - o] : 0;
+        }
         __syncthreads();
         s_p[t] += ap;
         s_c[t] += ac;
+        if constexpr (kPolygons)
+        {
+            s_v[t] += av;
+            s_q[t] += aq;
+        }
         __syncthreads();
     }
     int op = s_p[t] - sp, oc = s_c[t] - sc; // exclusive offsets of this thread's first frame
+    long long ov = kPolygons ? s_v[t] - sv : 0;
     for (int f = f0; f < f1; ++f)
     {
         const cape_frame_header& h = p.records[f].header;
@@ -80,6 +161,11 @@ __global__ __launch_bounds__(kScanThreads) void cape_pack_scan_kernel(PackParams
         p.frames[f] = pf;
         op += h.n_planes;
         oc += h.n_cylinders;
+        if constexpr (kPolygons)
+        {
+            p.frameVertexOffset[f] = ov; // first vertex of the frame's rings in the vertex section
+            ov += p.frameRings[f].x;
+        }
     }
     // the table entries past the shard's own frames stay zero so that equal inputs give equal bytes on the wire
     for (int f = p.nFrames + t; f < p.framesCapacity; f += kScanThreads)
@@ -100,6 +186,17 @@ __global__ __launch_bounds__(kScanThreads) void cape_pack_scan_kernel(PackParams
         hd.overflow = (s_p[t] > p.planesCapacity ? CAPE_PACKED_PLANES_DROPPED : 0u) |
                       (s_c[t] > p.cylindersCapacity ? CAPE_PACKED_CYLINDERS_DROPPED : 0u) |
                       (((s_status >> 31) && (p.flags & CAPE_GATHER_LABELS)) ? CAPE_PACKED_LABELS_CLIPPED : 0u);
+        if constexpr (kPolygons)
+        {
+            cape_packed_polygon_header ph;
+            ph.n_vertices_total = s_v[t];
+            ph.vertices_capacity = p.verticesCapacity;
+            ph.n_polygons_valid = s_q[t];
+            *p.polygonHeader = ph;
+            *p.verticesUsed = 0ull;
+            if (s_v[t] > (long long)p.verticesCapacity)
+                hd.overflow |= CAPE_PACKED_VERTICES_DROPPED;
+        }
         hd.status_or = s_status & 0xFFu;
         hd.cells = p.cells;
         hd.frames_capacity = p.framesCapacity;
@@ -109,7 +206,7 @@ __global__ __launch_bounds__(kScanThreads) void cape_pack_scan_kernel(PackParams
 }
 
 // one wavefront per frame: lane i looks at plane segment i / cylinder label i of the frame
-__global__ __launch_bounds__(256) void cape_pack_copy_kernel(PackParams p)
+template <bool kPolygons> __global__ __launch_bounds__(256) void cape_pack_copy_kernel(PackParams p)
 {
     const int lane = threadIdx.x & 63;
     const int frame = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -131,7 +228,15 @@ __global__ __launch_bounds__(256) void cape_pack_copy_kernel(PackParams p)
     // a frame of more than 64 plane segments / cylinder labels is a chain of records (cape_frame_header::next_record, an index into
     // the handle's record array): the planes and cylinders of every record of the chain, in order
     int planesBefore = 0, cylsBefore = 0;
-    for (const cape_frame_record* recp = &p.records[frame]; recp; recp = recp->header.next_record >= p.poolBase ? p.recordsBase + recp->header.next_record : nullptr)
+    // CAPE_GATHER_POLYGONS: where the frame's next ring goes in the vertex section, and whether the shard's rings exceed its budget
+    long long vertsBefore = 0;
+    bool vertsOverflow = false;
+    if constexpr (kPolygons)
+    {
+        vertsBefore = p.frameVertexOffset[frame];
+        vertsOverflow = p.polygonHeader->n_vertices_total > (long long)p.verticesCapacity;
+    }
+    for (const cape_frame_record* recp = &p.records[frame]; recp; recp = next_record(p, *recp))
     {
     const cape_frame_record& rec = *recp;
     // planes: k-th kept segment (is_output) -> planes[plane_offset + k]
@@ -156,6 +261,42 @@ __global__ __launch_bounds__(256) void cape_pack_copy_kernel(PackParams p)
             o.point_count = s.point_count;
             o.segment = (uint32_t)(rec.header.segment_base + lane);
             p.planes[dst] = o;
+        }
+        if constexpr (kPolygons)
+        {
+            // the plane's polygon goes to the same index k; its ring starts where the rings of the planes before it end (a wave prefix
+            // sum of the vertex counts).  A ring travels whole or not at all: offsets grow with k, so the rings that fit the budget are
+            // a prefix of the shard's rings in plane order, whatever the frame.
+            const size_t record = (size_t)(recp - p.recordsBase);
+            cape_polygon g{};
+            if (keep)
+                g = p.polygonsIn[record * CAPE_MAX_PLANES + lane];
+            const uint32_t count = keep ? ring_vertices(g, p.boundaryCapacity) : 0u;
+            const uint32_t from = g.vertex_offset;
+            const int incl = wave_scan_i32((int)count);
+            const long long to = vertsBefore + (incl - (int)count);
+            vertsBefore += (int)readlane_u32((unsigned)incl, 63);
+            const bool listed = keep && dst < p.planesCapacity;
+            const bool ship = listed && count > 0u && to + (long long)count <= (long long)p.verticesCapacity;
+            if (listed)
+            {
+                g.segment = (uint32_t)(rec.header.segment_base + lane);
+                g.vertex_count = ship ? count : 0u;
+                g.vertex_offset = ship ? (uint32_t)to : (count > 0u ? UINT32_MAX : 0u);
+                p.polygons[dst] = g;
+            }
+            if (vertsOverflow && ship)
+                atomicMax(p.verticesUsed, (unsigned long long)to + count); // (what the tail clear starts from; rare path)
+            // ring after ring, the whole wave over one ring's vertices: 16 bytes per lane, source and destination 16-byte aligned
+            const double2* slab = p.verticesIn + record * (size_t)p.boundaryCapacity;
+            for (unsigned long long rings = __ballot(ship); rings; rings &= rings - 1ull)
+            {
+                const int owner = __ffsll((long long)rings) - 1;
+                const uint32_t n = readlane_u32(count, owner), src = readlane_u32(from, owner);
+                const unsigned long long dstv = readlane_u64((unsigned long long)to, owner);
+                for (uint32_t i = (uint32_t)lane; i < n; i += 64u)
+                    p.vertices[dstv + i] = slab[src + i];
+            }
         }
     }
     // cylinders: k-th kept label -> cylinders[cylinder_offset + k]
@@ -204,6 +345,21 @@ __global__ __launch_bounds__(256) void cape_pack_clear_tail_kernel(PackParams p)
         pw[i] = 0ull;
     for (size_t i = cUsed + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cAll; i += stride)
         cw[i] = 0ull;
+    if (p.flags & CAPE_GATHER_POLYGONS)
+    {
+        // a polygon per listed plane; the vertices of the shipped rings: all of them, or what the copy kernel reports when rings were dropped
+        const long long total = p.polygonHeader->n_vertices_total;
+        const size_t gUsed = (size_t)min(hd.n_planes_total, p.planesCapacity) * (sizeof(cape_polygon) / 8);
+        const size_t gAll = (size_t)p.planesCapacity * (sizeof(cape_polygon) / 8);
+        const size_t vUsed = (total <= (long long)p.verticesCapacity ? (size_t)total : (size_t)*p.verticesUsed) * (sizeof(double2) / 8);
+        const size_t vAll = (size_t)p.verticesCapacity * (sizeof(double2) / 8);
+        unsigned long long* gw = reinterpret_cast<unsigned long long*>(p.polygons);
+        unsigned long long* vw = reinterpret_cast<unsigned long long*>(p.vertices);
+        for (size_t i = gUsed + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < gAll; i += stride)
+            gw[i] = 0ull;
+        for (size_t i = vUsed + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < vAll; i += stride)
+            vw[i] = 0ull;
+    }
 }
 
 // totals of a batch (what sizes a tight payload budget): one wave-reduced atomic per workgroup
@@ -240,12 +396,34 @@ hipError_t launch_count_primitives(const cape_frame_record* records, int nFrames
     return hipGetLastError();
 }
 
+// totals: two 64-bit words, [0] ring vertices of frames [0, nFrames), [1] the most in one frame
+hipError_t launch_count_polygon_vertices(const PackParams& p, unsigned long long* totals, hipStream_t stream)
+{
+    if (totals)
+        if (const hipError_t e = hipMemsetAsync(totals, 0, 2 * sizeof(unsigned long long), stream); e != hipSuccess)
+            return e;
+    if (p.nFrames <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(cape_count_polygon_vertices_kernel, dim3((p.nFrames + 3) / 4), dim3(256), 0, stream, p, totals);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack(const PackParams& p, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cape_pack_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, p);
+    const bool polygons = (p.flags & CAPE_GATHER_POLYGONS) != 0;
+    if (polygons)
+        if (const hipError_t e = launch_count_polygon_vertices(p, nullptr, stream); e != hipSuccess)
+            return e;
+    if (polygons)
+        hipLaunchKernelGGL(cape_pack_scan_kernel<true>, dim3(1), dim3(kScanThreads), 0, stream, p);
+    else
+        hipLaunchKernelGGL(cape_pack_scan_kernel<false>, dim3(1), dim3(kScanThreads), 0, stream, p);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(cape_pack_copy_kernel, dim3((p.framesCapacity + 3) / 4), dim3(256), 0, stream, p);
+    if (polygons)
+        hipLaunchKernelGGL(cape_pack_copy_kernel<true>, dim3((p.framesCapacity + 3) / 4), dim3(256), 0, stream, p);
+    else
+        hipLaunchKernelGGL(cape_pack_copy_kernel<false>, dim3((p.framesCapacity + 3) / 4), dim3(256), 0, stream, p);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(cape_pack_clear_tail_kernel, dim3(256), dim3(256), 0, stream, p);

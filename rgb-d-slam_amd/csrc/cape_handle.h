@@ -39,6 +39,7 @@ void rccl_comm_query(void* comm, int* count, int* rank, int* device);
 bool rccl_has_gather();
 int rccl_gather_bytes(const void* send, void* recv, size_t bytes, int root, void* comm, hipStream_t stream);
 hipError_t launch_count_primitives(const cape_frame_record* records, int nFrames, int32_t* out, hipStream_t stream);
+hipError_t launch_count_polygon_vertices(const PackParams& p, unsigned long long* totals, hipStream_t stream);
 int grow_waves_per_group();
 int grow_waves_per_cu(const StageBParams& p);
 } // namespace cape
@@ -288,6 +289,8 @@ struct cape_handle_s
     {
         cape_gather_config cfg{};
         cape_gather_layout layout{};
+        cape_gather_polygon_layout polygonLayout{}; // CAPE_GATHER_POLYGONS: the appended sections (all zero without the flag)
+        Buffer<unsigned char> ringScratch;          // ... and the pack kernels' scratch (ring_scratch_bytes)
         Buffer<unsigned char> packed[2];
         Event packedFree[2]; // recorded behind the gather that read the slot
         bool packedBusy[2] = {false, false};
@@ -299,6 +302,7 @@ struct cape_handle_s
         Event done;
         bool pending = false;
         Buffer<int32_t> countScratch; // cape_count_primitives
+        Buffer<unsigned long long> vertexCountScratch; // cape_count_polygon_vertices
     } gather;
 
     // rectify_depth (N3): a flag per frame, then the count + list of flagged frames (2 F + 1 words for F frames)

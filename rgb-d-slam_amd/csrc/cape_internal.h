@@ -261,6 +261,20 @@ struct PackParams
     uint8_t* cylLabels8;
     int nFrames, firstFrame, framesCapacity, planesCapacity, cylindersCapacity, cells;
     uint32_t flags;
+    // CAPE_GATHER_POLYGONS: the polygon rows and vertex slabs of cape_build_polygons, both indexed by the RECORD index (spill records
+    // included), and the three sections appended to the packed buffer
+    const cape_polygon* polygonsIn = nullptr;
+    const double2* verticesIn = nullptr;
+    int boundaryCapacity = 0;
+    cape_packed_polygon_header* polygonHeader = nullptr;
+    cape_polygon* polygons = nullptr; // planesCapacity entries
+    double2* vertices = nullptr;      // verticesCapacity entries
+    int verticesCapacity = 0;
+    // scratch of the handle: per frame (ring vertices, kept polygons) from the count kernel, the exclusive scan of the former (the
+    // frame's first vertex in the section), and the vertices the shipped rings take when the budget overflows
+    int2* frameRings = nullptr;
+    long long* frameVertexOffset = nullptr;
+    unsigned long long* verticesUsed = nullptr;
 };
 
 // N1 on the device: boundary polygons (cape_polygon.hip)

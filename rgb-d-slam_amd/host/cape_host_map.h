@@ -65,6 +65,23 @@ int cape_host_map_update(const cape_map_plane* planes, int32_t n_planes, const c
                          double* vertices_out, int64_t vertices_capacity, cape_map_track* tracks_out, int32_t* n_planes_out,
                          int32_t* n_rings_out, int64_t* n_vertices_out, int32_t* used_out);
 
+/* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
+ * cape_gather_primitives[_root] or any other transport -- as the detected planes cape_host_match_map and cape_host_map_update take: no
+ * handle, no device.  `frame` counts from the shard's first frame.  The planes are those Primitive_Detection keeps (packed polygon with
+ * CAPE_POLY_VALID and >= 3 vertices, primitive_detection.cpp:623-631) in order, i.e. the reference's plane_container; each goes
+ * through the host class's Polygon(ring, xAxis, yAxis, center) constructor, which is where ring, axes and area come from.
+ * Outputs (each may be NULL; `capacity` planes, `vertices_capacity` (x, y) pairs): det_planes n x (normal[3], d); det_cov n x 9, the
+ * point-cloud covariance restated from the packed sums (the inverse of their second-moment matrix by cofactors, plane_segment.cpp:192-203:
+ * cape_plane_segment.cov bit for bit); det_frames n x (x_axis, y_axis, center); det_areas; the rings one after the other in
+ * det_vertices with det_counts[i] vertices each; det_segments[i] = index of the plane in the frame's segment list.
+ * Returns 0; CAPE_ERR_INVALID_ARGUMENT for a buffer that is no shard of this layout (size, magic, no polygon sections, frame out of
+ * range, an offset outside its section) or whose header reports dropped planes or rings (the kept-plane indices would not be the
+ * reference's); CAPE_ERR_CAPACITY if an output is too small -- *n_det_out and *n_vertices_out say what the frame needs either way. */
+int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, const cape_gather_layout* layout, const cape_gather_polygon_layout* polygon_layout,
+                          int32_t frame, int32_t capacity, int64_t vertices_capacity, double* det_planes, double* det_cov, double* det_frames,
+                          double* det_areas, double* det_vertices, int32_t* det_counts, int32_t* det_segments, int32_t* n_det_out,
+                          int64_t* n_vertices_out);
+
 #ifdef __cplusplus
 }
 #endif

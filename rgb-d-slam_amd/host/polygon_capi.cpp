@@ -206,6 +206,122 @@ extern "C" int cape_host_match_map(const cape_map_plane* planes, int32_t n_plane
     }
 }
 
+// One frame of a packed shard as the detected planes of the two calls around it (cape_host_map.h): the proof that what
+// CAPE_GATHER_POLYGONS ships is enough to track planes on a rank that never saw the frame.
+extern "C" int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, const cape_gather_layout* layout,
+                                     const cape_gather_polygon_layout* polygon_layout, int32_t frame, int32_t capacity, int64_t vertices_capacity,
+                                     double* det_planes, double* det_cov, double* det_frames, double* det_areas, double* det_vertices,
+                                     int32_t* det_counts, int32_t* det_segments, int32_t* n_det_out, int64_t* n_vertices_out)
+{
+    using rgbd_slam::vector2;
+    using rgbd_slam::vector3;
+    using rgbd_slam::utils::Polygon;
+    if (!shard || !layout || !polygon_layout || !n_det_out || !n_vertices_out || frame < 0 || capacity < 0 || vertices_capacity < 0)
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const cape_gather_layout& L = *layout;
+    const cape_gather_polygon_layout& PL = *polygon_layout;
+    const auto section_fits = [&](uint64_t offset, uint64_t count, uint64_t size) { return offset <= shard_bytes && count * size <= shard_bytes - offset; };
+    if (shard_bytes != L.bytes_per_rank || PL.polygons_offset == 0 || L.frames_capacity < 0 || L.planes_capacity < 0 || PL.vertices_capacity < 0 ||
+        PL.polygons_capacity != L.planes_capacity || !section_fits(0, 1, sizeof(cape_packed_header)) ||
+        !section_fits(L.frames_offset, (uint64_t)L.frames_capacity, sizeof(cape_packed_frame)) ||
+        !section_fits(L.planes_offset, (uint64_t)L.planes_capacity, sizeof(cape_packed_plane)) ||
+        !section_fits(PL.polygons_offset, (uint64_t)PL.polygons_capacity, sizeof(cape_polygon)) ||
+        !section_fits(PL.vertices_offset, (uint64_t)PL.vertices_capacity, 2 * sizeof(double)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const unsigned char* base = static_cast<const unsigned char*>(shard);
+    cape_packed_header hd;
+    std::memcpy(&hd, base, sizeof(hd));
+    if (hd.magic != CAPE_PACKED_MAGIC || !(hd.flags & CAPE_GATHER_POLYGONS) || frame >= hd.n_frames || hd.n_frames > L.frames_capacity ||
+        (hd.overflow & (CAPE_PACKED_PLANES_DROPPED | CAPE_PACKED_VERTICES_DROPPED)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    cape_packed_frame fr;
+    std::memcpy(&fr, base + L.frames_offset + (size_t)frame * sizeof(fr), sizeof(fr));
+    if (fr.plane_offset < 0 || fr.n_planes < 0 || (int64_t)fr.plane_offset + fr.n_planes > L.planes_capacity)
+        return CAPE_ERR_INVALID_ARGUMENT;
+    int32_t n = 0;
+    int64_t nv = 0;
+    bool fits = true;
+    try
+    {
+        for (int32_t k = fr.plane_offset; k < fr.plane_offset + fr.n_planes; ++k)
+        {
+            cape_polygon g;
+            std::memcpy(&g, base + PL.polygons_offset + (size_t)k * sizeof(g), sizeof(g));
+            if (!(g.flags & CAPE_POLY_VALID) || g.vertex_count < 3)
+                continue; // Primitive_Detection drops the plane
+            if ((uint64_t)g.vertex_offset + g.vertex_count > (uint64_t)PL.vertices_capacity)
+                return CAPE_ERR_INVALID_ARGUMENT;
+            fits = fits && n < capacity && nv + g.vertex_count <= vertices_capacity;
+            if (fits)
+            {
+                cape_packed_plane pl;
+                std::memcpy(&pl, base + L.planes_offset + (size_t)k * sizeof(pl), sizeof(pl));
+                std::vector<double> xy(2 * (size_t)g.vertex_count);
+                std::memcpy(xy.data(), base + PL.vertices_offset + (size_t)g.vertex_offset * 2 * sizeof(double), xy.size() * sizeof(double));
+                std::vector<vector2> ring;
+                for (uint32_t v = 0; v < g.vertex_count; ++v)
+                    ring.emplace_back(xy[2 * v], xy[2 * v + 1]);
+                const Polygon polygon(ring, vector3(g.x_axis[0], g.x_axis[1], g.x_axis[2]), vector3(g.y_axis[0], g.y_axis[1], g.y_axis[2]),
+                                      vector3(g.center[0], g.center[1], g.center[2]));
+                if (polygon.boundary().size() != g.vertex_count)
+                    return CAPE_ERR_INVALID_ARGUMENT; // (the constructor keeps an open ring as it is)
+                if (det_planes)
+                {
+                    std::memcpy(det_planes + 4 * n, pl.normal, 3 * sizeof(double));
+                    det_planes[4 * n + 3] = pl.d;
+                }
+                if (det_cov)
+                {
+                    // Plane_Segment::get_point_cloud_covariance: Matrix3d::inverse (cofactors) of {{Sxs,Sxy,Szx},{Sxy,Sys,Syz},{Szx,Syz,Szs}},
+                    // statement for statement what the grow kernels store in cape_plane_segment.cov
+                    const double* S = pl.sums;
+                    const double m[3][3] = {{S[3], S[6], S[8]}, {S[6], S[4], S[7]}, {S[8], S[7], S[5]}};
+                    const auto cof = [&](int i, int j) {
+                        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+                        return m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
+                    };
+                    const double c00 = cof(0, 0), c10 = cof(1, 0), c20 = cof(2, 0);
+                    const double det = (c00 * m[0][0] + c10 * m[1][0]) + c20 * m[2][0];
+                    const double invdet = 1.0 / det;
+                    double* r = det_cov + 9 * n;
+                    r[0] = c00 * invdet; r[1] = c10 * invdet; r[2] = c20 * invdet;
+                    for (int j = 1; j < 3; ++j)
+                        for (int i = 0; i < 3; ++i)
+                            r[3 * j + i] = cof(i, j) * invdet;
+                }
+                if (det_frames)
+                    for (int c = 0; c < 3; ++c)
+                    {
+                        det_frames[9 * n + c] = polygon.get_x_axis()[c];
+                        det_frames[9 * n + 3 + c] = polygon.get_y_axis()[c];
+                        det_frames[9 * n + 6 + c] = g.center[c];
+                    }
+                if (det_areas)
+                    det_areas[n] = polygon.get_area();
+                if (det_vertices)
+                    for (uint32_t v = 0; v < g.vertex_count; ++v)
+                    {
+                        det_vertices[2 * (nv + v)] = polygon.boundary()[v][0];
+                        det_vertices[2 * (nv + v) + 1] = polygon.boundary()[v][1];
+                    }
+                if (det_counts)
+                    det_counts[n] = (int32_t)g.vertex_count;
+                if (det_segments)
+                    det_segments[n] = (int32_t)g.segment;
+            }
+            ++n;
+            nv += g.vertex_count;
+        }
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
+    *n_det_out = n;
+    *n_vertices_out = nv;
+    return fits ? 0 : CAPE_ERR_CAPACITY;
+}
+
 namespace {
 
 // Eigen's isApprox on 3-vectors: |a - b|^2 <= prec^2 min(|a|^2, |b|^2)

@@ -81,9 +81,12 @@ FRAME_RECORD_DTYPE = np.dtype([
 # packed gather payload (include/cape_hip.h: cape_packed_*)
 PACKED_MAGIC = 0x43415045
 GATHER_LABELS = 1
+GATHER_POLYGONS = 2
+GATHER_DEFAULT_VERTICES_PER_FRAME = 72  # CAPE_GATHER_DEFAULT_VERTICES_PER_FRAME
 PACKED_PLANES_DROPPED = 1
 PACKED_CYLINDERS_DROPPED = 2
 PACKED_LABELS_CLIPPED = 4
+PACKED_VERTICES_DROPPED = 8
 COMM_ID_BYTES = 128
 PACKED_HEADER_DTYPE = np.dtype([
     ("magic", "<u4"), ("n_frames", "<i4"), ("first_frame", "<i4"), ("n_planes_total", "<i4"),
@@ -96,8 +99,10 @@ PACKED_PLANE_DTYPE = np.dtype([
     ("normal", "<f8", 3), ("d", "<f8"), ("centroid", "<f8", 3), ("mse", "<f8"), ("score", "<f8"), ("sums", "<f8", 9),
     ("point_count", "<u4"), ("segment", "<u4")], align=True)
 PACKED_CYLINDER_DTYPE = np.dtype([("axis", "<f8", 3), ("radius", "<f8")], align=True)
+# the header of the sections CAPE_GATHER_POLYGONS appends (then POLYGON_DTYPE records, then (x, y) vertices)
+PACKED_POLYGON_HEADER_DTYPE = np.dtype([("n_vertices_total", "<i8"), ("vertices_capacity", "<i4"), ("n_polygons_valid", "<i4")], align=True)
 assert (PACKED_HEADER_DTYPE.itemsize, PACKED_FRAME_DTYPE.itemsize, PACKED_PLANE_DTYPE.itemsize,
-        PACKED_CYLINDER_DTYPE.itemsize) == (48, 24, 152, 32)
+        PACKED_CYLINDER_DTYPE.itemsize, PACKED_POLYGON_HEADER_DTYPE.itemsize) == (48, 24, 152, 32, 16)
 
 
 class cape_comm_info_t(C.Structure):
@@ -114,6 +119,11 @@ class cape_gather_layout(C.Structure):
                 ("cylinders_offset", C.c_uint64), ("plane_labels_offset", C.c_uint64), ("cyl_labels_offset", C.c_uint64),
                 ("frames_capacity", C.c_int32), ("planes_capacity", C.c_int32), ("cylinders_capacity", C.c_int32),
                 ("cells", C.c_int32)]
+
+
+class cape_gather_polygon_layout(C.Structure):
+    _fields_ = [("polygon_header_offset", C.c_uint64), ("polygons_offset", C.c_uint64), ("vertices_offset", C.c_uint64),
+                ("polygons_capacity", C.c_int32), ("vertices_capacity", C.c_int32)]
 
 
 POLYGON_DTYPE = np.dtype([
@@ -202,6 +212,9 @@ def _host_library():
         L.cape_host_map_update.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp,
                                            vp, C.c_uint32, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp]
         L.cape_host_map_update.restype = C.c_int
+        L.cape_host_shard_frame.argtypes = [vp, C.c_uint64, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout), C.c_int32,
+                                            C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.cape_host_shard_frame.restype = C.c_int
         _host_lib = L
     return _host_lib
 
@@ -262,6 +275,35 @@ def host_map_update(map_arrays, tracks, match, detected, camera_to_world, pose_c
         raise CapeError(f"cape_host_map_update failed ({rc})")
     return ((Po[:n_p.value].copy(), Ro[:n_r.value].copy(), Vo[:n_v.value].copy()), To[:n_p.value].copy(),
             used[:n_det].astype(bool), nid.value)
+
+
+def host_shard_frame(buf, layout, k):
+    """cape_host_shard_frame of libcape_primitives.so: the kept planes of frame k of one rank's packed bytes (packed with
+    polygons=True; `layout` is the dict of Extractor.gather_configure / dist.packed_layout) through the host class's Polygon
+    constructor, as the `detected` list host_match_map and host_map_update take -- (normal, d, x_axis, y_axis, center, ring, area,
+    cov) per plane -- and their segment indices.  No handle, no device."""
+    L = _host_library()
+    buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+    lay = cape_gather_layout(**{f: int(layout.get(f, 0)) for f, _ in cape_gather_layout._fields_})
+    pl = cape_gather_polygon_layout(**{f: int(layout.get(f, 0)) for f, _ in cape_gather_polygon_layout._fields_})
+    n, nv = C.c_int32(0), C.c_int64(0)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    cap, vcap = 0, 0
+    for _ in range(2):  # the second pass with the sizes the first one reported
+        dp, dcov, df = np.zeros((max(cap, 1), 4)), np.zeros((max(cap, 1), 9)), np.zeros((max(cap, 1), 9))
+        da, dc, ds = np.zeros(max(cap, 1)), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+        dv = np.zeros((max(vcap, 1), 2))
+        rc = L.cape_host_shard_frame(ptr(buf), buf.size, C.byref(lay), C.byref(pl), k, cap, vcap, ptr(dp), ptr(dcov), ptr(df), ptr(da),
+                                     ptr(dv), ptr(dc), ptr(ds), C.byref(n), C.byref(nv))
+        if rc != -4:  # CAPE_ERR_CAPACITY
+            break
+        cap, vcap = n.value, nv.value
+    if rc != 0:
+        raise CapeError(f"cape_host_shard_frame failed ({rc})")
+    at = np.concatenate([[0], np.cumsum(dc[:n.value])])
+    detected = [(dp[i, :3].copy(), float(dp[i, 3]), df[i, 0:3].copy(), df[i, 3:6].copy(), df[i, 6:9].copy(), dv[at[i]:at[i + 1]].copy(),
+                 float(da[i]), dcov[i].reshape(3, 3).copy()) for i in range(n.value)]
+    return detected, ds[:n.value].copy()
 
 
 def host_match_map(map_arrays, detected, world_to_camera=None, skip=None, flags=0, areas=False):
@@ -325,7 +367,8 @@ CELL_STATS_DTYPE = np.dtype([
 EXPORTED_SYMBOLS = [
     "cape_device_count", "cape_create", "cape_destroy", "cape_get_layout", "cape_extract", "cape_extract_u16", "cape_extract_host", "cape_extract_u16_host", "cape_stream_create", "cape_stream_destroy", "cape_rectify_depth", "cape_rectify_depth_host", "cape_device_results",
     "cape_gather_configure", "cape_pack_primitives", "cape_copy_packed", "cape_comm_unique_id", "cape_comm_init",
-    "cape_comm_destroy", "cape_gather_primitives", "cape_gather_primitives_root", "cape_count_primitives", "cape_gather_wait", "cape_copy_results", "cape_sync_results", "cape_host_results", "cape_host_alloc", "cape_host_free", "cape_host_register",
+    "cape_comm_destroy", "cape_gather_primitives", "cape_gather_primitives_root", "cape_count_primitives", "cape_gather_wait",
+    "cape_gather_configure_polygons", "cape_count_polygon_vertices", "cape_copy_results", "cape_sync_results", "cape_host_results", "cape_host_alloc", "cape_host_free", "cape_host_register",
     "cape_host_unregister", "cape_copy_cell_stats", "cape_enable_timing", "cape_get_timings",
     "cape_reset_timings", "cape_match_consecutive", "cape_device_matches", "cape_copy_matches",
     "cape_match_polygons", "cape_match_polygons_pose", "cape_copy_polygon_matches",
@@ -382,6 +425,9 @@ def load_library():
     L.cape_set_log_callback.argtypes = [vp, LOG_FN, vp]
     L.cape_log_records.argtypes = [vp, C.c_int32, LOG_FN, vp]
     L.cape_gather_configure.argtypes = [vp, C.POINTER(cape_gather_config), C.POINTER(cape_gather_layout)]
+    L.cape_gather_configure_polygons.argtypes = [vp, C.POINTER(cape_gather_config), C.c_int32, C.POINTER(cape_gather_layout),
+                                                 C.POINTER(cape_gather_polygon_layout)]
+    L.cape_count_polygon_vertices.argtypes = [vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.cape_pack_primitives.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp), vp]
     L.cape_copy_packed.argtypes = [vp, vp]
     L.cape_comm_unique_id.argtypes = [vp]
@@ -744,11 +790,22 @@ class Extractor:
         _check(self.L, self.L.cape_reset_timings(self.h), "cape_reset_timings")
 
     # ---- multi-GPU gather of the packed primitive lists -------------------------------------------
-    def gather_configure(self, frames_capacity, planes_per_frame=0, cylinders_per_frame=0, labels=False):
+    def gather_configure(self, frames_capacity, planes_per_frame=0, cylinders_per_frame=0, labels=False, polygons=False,
+                         vertices_per_frame=0):
+        """The layout of the packed buffer as a dict.  polygons=True (CAPE_GATHER_POLYGONS) appends the boundary polygons of the
+        packed planes -- build_polygons of the batch has to run before pack / gather -- and adds the fields of
+        cape_gather_polygon_layout to the dict; vertices_per_frame sizes their vertex budget (0: the library's default)."""
         cfg = cape_gather_config(frames_capacity, planes_per_frame, cylinders_per_frame, GATHER_LABELS if labels else 0)
         lay = cape_gather_layout()
-        _check(self.L, self.L.cape_gather_configure(self.h, C.byref(cfg), C.byref(lay)), "cape_gather_configure")
+        if polygons:
+            pl = cape_gather_polygon_layout()
+            _check(self.L, self.L.cape_gather_configure_polygons(self.h, C.byref(cfg), vertices_per_frame, C.byref(lay), C.byref(pl)),
+                   "cape_gather_configure_polygons")
+        else:
+            _check(self.L, self.L.cape_gather_configure(self.h, C.byref(cfg), C.byref(lay)), "cape_gather_configure")
         self.gather_layout = {f: int(getattr(lay, f)) for f, _ in cape_gather_layout._fields_}
+        if polygons:
+            self.gather_layout.update({f: int(getattr(pl, f)) for f, _ in cape_gather_polygon_layout._fields_})
         return self.gather_layout
 
     def _ensure_gather_layout(self):
@@ -806,6 +863,12 @@ class Extractor:
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         _check(self.L, self.L.cape_count_primitives(self.h, n_frames, C.byref(a), C.byref(b), C.byref(c)), "cape_count_primitives")
         return a.value, b.value, c.value
+
+    def count_polygon_vertices(self, n_frames):
+        """(ring vertices of all output planes, most in one frame) over the last build_polygons -- sizes vertices_per_frame."""
+        a, b = C.c_int64(0), C.c_int32(0)
+        _check(self.L, self.L.cape_count_polygon_vertices(self.h, n_frames, C.byref(a), C.byref(b)), "cape_count_polygon_vertices")
+        return a.value, b.value
 
     def gather_wait(self, stream=0, host_sync=True):
         _check(self.L, self.L.cape_gather_wait(self.h, C.c_void_p(stream), 1 if host_sync else 0), "cape_gather_wait")

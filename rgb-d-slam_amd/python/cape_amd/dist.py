@@ -18,9 +18,11 @@ def largest_shard(n_frames, world):
     return -(-n_frames // world)
 
 
-def packed_layout(frames_capacity, cells, planes_per_frame=16, cylinders_per_frame=8, labels=False):
-    """Host restatement of cape_gather_configure's layout arithmetic (sections on 16-byte boundaries)."""
-    from . import PACKED_CYLINDER_DTYPE, PACKED_FRAME_DTYPE, PACKED_HEADER_DTYPE, PACKED_PLANE_DTYPE
+def packed_layout(frames_capacity, cells, planes_per_frame=16, cylinders_per_frame=8, labels=False, polygons=False, vertices_per_frame=0):
+    """Host restatement of cape_gather_configure's layout arithmetic (sections on 16-byte boundaries).  polygons=True: that of
+    cape_gather_configure_polygons -- the polygon sections behind everything else, their fields added to the dict."""
+    from . import (GATHER_DEFAULT_VERTICES_PER_FRAME, PACKED_CYLINDER_DTYPE, PACKED_FRAME_DTYPE, PACKED_HEADER_DTYPE, PACKED_PLANE_DTYPE,
+                   PACKED_POLYGON_HEADER_DTYPE, POLYGON_DTYPE)
 
     def a16(v):
         return (v + 15) & ~15
@@ -40,6 +42,15 @@ def packed_layout(frames_capacity, cells, planes_per_frame=16, cylinders_per_fra
         off = a16(off + frames_capacity * cells)
         lay["cyl_labels_offset"] = off
         off = a16(off + frames_capacity * cells)
+    if polygons:
+        lay["polygons_capacity"] = lay["planes_capacity"]
+        lay["vertices_capacity"] = frames_capacity * (vertices_per_frame or GATHER_DEFAULT_VERTICES_PER_FRAME)
+        lay["polygon_header_offset"] = off
+        off = a16(off + PACKED_POLYGON_HEADER_DTYPE.itemsize)
+        lay["polygons_offset"] = off
+        off = a16(off + lay["polygons_capacity"] * POLYGON_DTYPE.itemsize)
+        lay["vertices_offset"] = off
+        off = a16(off + lay["vertices_capacity"] * 16)
     lay["bytes_per_rank"] = off
     return lay
 
@@ -48,7 +59,8 @@ class Shard:
     """One rank's packed buffer, parsed (views into the bytes, no copies)."""
 
     def __init__(self, buf, layout):
-        from . import (PACKED_CYLINDER_DTYPE, PACKED_FRAME_DTYPE, PACKED_HEADER_DTYPE, PACKED_MAGIC, PACKED_PLANE_DTYPE)
+        from . import (GATHER_POLYGONS, PACKED_CYLINDER_DTYPE, PACKED_FRAME_DTYPE, PACKED_HEADER_DTYPE, PACKED_MAGIC, PACKED_PLANE_DTYPE,
+                       PACKED_POLYGON_HEADER_DTYPE, POLYGON_DTYPE)
 
         buf = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf)
         assert buf.size == layout["bytes_per_rank"], (buf.size, layout["bytes_per_rank"])
@@ -69,6 +81,17 @@ class Shard:
             self.plane_labels = buf[o: o + F * cells].reshape(F, cells)[: len(self.frames)]
             o = layout["cyl_labels_offset"]
             self.cyl_labels = buf[o: o + F * cells].reshape(F, cells)[: len(self.frames)]
+        # CAPE_GATHER_POLYGONS: polygon k belongs to plane k; the rings are (x, y) pairs in the polygon's plane frame
+        self.polygon_header = self.polygons = self.vertices = None
+        if "polygons_offset" in layout:
+            if not int(self.header["flags"]) & GATHER_POLYGONS:
+                raise ValueError("the layout has polygon sections, the shard was packed without CAPE_GATHER_POLYGONS")
+            o = layout["polygon_header_offset"]
+            self.polygon_header = buf[o: o + PACKED_POLYGON_HEADER_DTYPE.itemsize].view(PACKED_POLYGON_HEADER_DTYPE)[0]
+            o = layout["polygons_offset"]
+            self.polygons = buf[o: o + layout["polygons_capacity"] * POLYGON_DTYPE.itemsize].view(POLYGON_DTYPE)
+            o = layout["vertices_offset"]
+            self.vertices = buf[o: o + layout["vertices_capacity"] * 16].view("<f8").reshape(-1, 2)
 
     @property
     def first_frame(self):
@@ -88,6 +111,37 @@ class Shard:
         return self.cylinders[a:max(a, b)]
 
 
+    def frame_polygons(self, k):
+        """(polygon records, [ring as an (n, 2) view]) of the shard's k-th frame, aligned with frame_planes(k).  A ring that did not
+        travel (PACKED_VERTICES_DROPPED: vertex_offset = 0xFFFFFFFF) or that the producer did not build is an empty (0, 2) view."""
+        if self.polygons is None:
+            raise ValueError("the shard was packed without CAPE_GATHER_POLYGONS")
+        fr = self.frames[k]
+        a = int(fr["plane_offset"])
+        b = min(a + int(fr["n_planes"]), len(self.polygons))
+        pol = self.polygons[a:max(a, b)]
+        rings = []
+        for g in pol:
+            n, o = int(g["vertex_count"]), int(g["vertex_offset"])
+            if n and o + n > len(self.vertices):
+                raise ValueError("a packed ring lies outside the vertex section")
+            rings.append(self.vertices[o:o + n] if n else self.vertices[:0])
+        return pol, rings
+
+    def kept_planes(self, k):
+        """[(plane, polygon, ring)] of the frame's planes that Primitive_Detection keeps -- CAPE_POLY_VALID and >= 3 vertices
+        (primitive_detection.cpp:623-631) -- in order: entry i is plane i of the reference's plane_container, the index every matcher
+        result is expressed in.  Refuses a shard that dropped planes or rings: its indices would not be the reference's."""
+        from . import PACKED_PLANES_DROPPED, PACKED_VERTICES_DROPPED, POLY_VALID
+
+        if int(self.header["overflow"]) & (PACKED_PLANES_DROPPED | PACKED_VERTICES_DROPPED):
+            raise ValueError("the shard dropped planes or rings (header.overflow): the kept planes are not known")
+        planes = self.frame_planes(k)
+        pol, rings = self.frame_polygons(k)
+        return [(planes[i], pol[i], rings[i]) for i in range(len(pol))
+                if int(pol[i]["flags"]) & POLY_VALID and int(pol[i]["vertex_count"]) >= 3]
+
+
 def unpack_gathered(buf, world, layout):
     """world x bytes_per_rank gathered bytes -> list of Shard, rank order."""
     buf = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf).reshape(-1)
@@ -102,6 +156,15 @@ def primitives_by_frame(shards):
     for sh in shards:
         for k in range(len(sh.frames)):
             out[sh.first_frame + k] = (sh.frame_planes(k), sh.frame_cylinders(k))
+    return out
+
+
+def primitives_by_frame_with_polygons(shards):
+    """{global frame index: (planes, cylinders, polygons, rings)} over shards packed with CAPE_GATHER_POLYGONS."""
+    out = {}
+    for sh in shards:
+        for k in range(len(sh.frames)):
+            out[sh.first_frame + k] = (sh.frame_planes(k), sh.frame_cylinders(k)) + sh.frame_polygons(k)
     return out
 
 
