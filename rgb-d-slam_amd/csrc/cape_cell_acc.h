@@ -125,4 +125,34 @@ __device__ __forceinline__ bool is_continuous_flat(float pixelDepth, float& last
     return !positive | close;
 }
 
+// The same step decided in f32 wherever f32 can decide it: eleven instructions against the sixteen of the f64 form.  Returns
+// the verdict and raises `unsure` when it might differ from is_continuous_flat's; the caller then runs the f64 scan.
+//   The f64 verdict is d <= R with d = |z - last| (an f32 difference in both forms: the same bits) and
+// R = 4 max(P(z), 0.5), P = c0 + c1 z + c2 z^2 evaluated in f64 (relative error ~2^-50, nothing at the scale below).
+//   r below is max(4 P, 2) by two f32 fma on the constants rounded to f32 (u = 2^-24 each): its distance from the exact value
+// is at most 3 u (4 |c0| + 4 c1 z + 4 c2 z^2) = 3 u (4 P + 8 |c0|) for z > 0.  Where 4 P >= 2 that is 3 u (1 + 4.24 / 2) R
+// = 9.4 u R, and where 4 P < 2 both sides are clamped to 2 (max is 1-Lipschitz): |r - R| <= 2^-20 R for every z > 0 whose
+// polynomial does not overflow.
+//   t = fl(d - r) has the sign of d - r and at most (1 + u) times its magnitude.  If |t| > 2^-16 r then
+//     |d - r| > 2^-16 r / (1 + u) >= 2^-16 (1 - 2^-20) R / (1 + 2^-24) > 2^-20 R >= |r - R|,
+// so d - R = (d - r) + (r - R) has the sign of d - r, which is the sign of t: `t <= 0` IS the f64 verdict.
+//   Everything else is `unsure`: d within 2^-16 of the threshold, d NaN (then t is NaN and the compare fails), and z so large
+// that the f32 polynomial overflows -- then r = +inf and t is -inf or NaN, never beyond 2^-16 r = +inf.  z <= 0 or NaN
+// passes whatever d is, like the reference's `if`, and never raises `unsure`.
+__device__ __forceinline__ bool is_continuous_flat_f32(float pixelDepth, float& last, bool& unsure)
+{
+    // depth_quantization's constants (cape_device.h) times the 4 of the test
+    constexpr float c2 = (float)(4.0 * (2.73 * ((1.0 / 1000.0) * (1.0 / 1000.0))));
+    constexpr float c1 = (float)(4.0 * (0.74 / 1000.0));
+    constexpr float c0 = (float)(4.0 * -0.53);
+    const bool positive = pixelDepth > 0;
+    const float r = fmaxf(fmaf(fmaf(c2, pixelDepth, c1), pixelDepth, c0), 2.0f);
+    const float t = fabsf(pixelDepth - last) - r;
+    const bool notSure = !(fabsf(t) > r * 0x1p-16f);
+    const bool close = t <= 0;
+    unsure |= positive & notSure;
+    last = (positive & close) ? pixelDepth : last;
+    return !positive | close;
+}
+
 } // namespace cape

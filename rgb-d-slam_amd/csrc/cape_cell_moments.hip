@@ -45,13 +45,29 @@ template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void c
     const int pair = blockIdx.x - frame * p.pairsPerFrame;
     const size_t frameOff = (size_t)frame * p.W * p.H;
 
+    // The workgroup's two bands are consecutive, so the second one's cell row and 640-pixel segment follow from the first's
+    // without a second division -- and both are uniform: they live in scalar registers, for the streaming lanes (which pick
+    // theirs with one select per quantity) and for the reduce and aux stores behind the barrier alike.
+    const int band0 = pair * 2;
+    const int cellRow0 = band0 / p.segsPerRow;
+    const int seg0 = band0 - cellRow0 * p.segsPerRow;
+    const bool wrap = seg0 + 1 == p.segsPerRow;
+    const int cellRowOf[2] = {cellRow0, cellRow0 + (wrap ? 1 : 0)};
+    const int segOf[2] = {seg0, wrap ? 0 : seg0 + 1};
+    const bool bandExists[2] = {band0 < p.bandsPerFrame, band0 + 1 < p.bandsPerFrame};
+    // what a streaming lane needs of its band, multiplied out per band (scalar) before the lane picks one
+    // (readfirstlane of a uniform value is a scalar move; it keeps the compiler from turning "select of two products" back
+    // into "product of a select", a vector multiply)
+    const int firstRowOf[2] = {__builtin_amdgcn_readfirstlane(cellRowOf[0] * kCell), __builtin_amdgcn_readfirstlane(cellRowOf[1] * kCell)};
+    const int firstColOf[2] = {__builtin_amdgcn_readfirstlane(segOf[0] * 640), __builtin_amdgcn_readfirstlane(segOf[1] * 640)};
+    const uint32_t firstPixOf[2] = {(uint32_t)__builtin_amdgcn_readfirstlane(firstRowOf[0] * p.W), (uint32_t)__builtin_amdgcn_readfirstlane(firstRowOf[1] * p.W)};
+    const int colLimitOf[2] = {bandExists[0] ? p.W : 0, bandExists[1] ? p.W : 0};
+
     const int bsel = t / kBandThreads;
     const int q = t - bsel * kBandThreads;
-    const int band = pair * 2 + bsel;
-    const int cellRow = band / p.segsPerRow;
-    const int seg = band - cellRow * p.segsPerRow;
-    const int col0 = seg * 640 + q * 4;
-    const bool active = (band < p.bandsPerFrame) && (col0 < p.W);
+    const int row0 = bsel ? firstRowOf[1] : firstRowOf[0];
+    const int col0 = (bsel ? firstColOf[1] : firstColOf[0]) + q * 4;
+    const bool active = col0 < (bsel ? colLimitOf[1] : colLimitOf[0]);
     const int cseg = q / 5;          // cell within the band segment
     const int j = q - cseg * 5;      // float4 within the cell row
     const int lcell = bsel * 32 + cseg;
@@ -69,11 +85,11 @@ template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void c
         const double a0 = p.acol[col0], a1 = p.acol[col0 + 1], a2 = p.acol[col0 + 2], a3 = p.acol[col0 + 3];
         // addresses = one base per FRAME (uniform: it lives in scalar registers and advances row by row with scalar adds)
         // + one 32-bit element offset per thread (its column inside the frame): no 64-bit vector address arithmetic per load
-        const uint32_t pixOff32 = (uint32_t)(cellRow * kCell) * (uint32_t)p.W + (uint32_t)col0;
+        const uint32_t pixOff32 = (bsel ? firstPixOf[1] : firstPixOf[0]) + (uint32_t)col0;
         const float* frameBase = p.depth + frameOff;                 // float32 millimetres
         const uint16_t* frameBase16 = p.depth_u16 + frameOff;        // raw sensor units (U16 variant)
         const float scale16 = p.u16_scale;
-        const double* brow = p.brow + cellRow * kCell;
+        const double* brow = p.brow + row0;
         const size_t W = (size_t)p.W;
 
         // rows in groups of kGroup, ping-pong buffered: the loads of group g+1 are in flight while group g is summed
@@ -179,38 +195,42 @@ template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void c
     // ------------------------------------------------------------------ behind the barrier: wave 4 sums, waves 0..3 scan
     // The workgroup's LDS and wave slots are held until its last wave leaves, so the work behind the last pixel is spread for
     // LATENCY: the 5-partials sums on one wave beside the scans, the scans cut in four (below) -- profiles/r04_a1_phases.txt.
-    if (t >= 256)
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6); // the wave: uniform, so what follows from it stays in scalar registers
+    if (w == 4)
     {
-        // 5 partials -> one cell (exact, any order): 64 cells x 10 quantities = 640 tasks, ten per lane, consecutive lanes store
-        // consecutive doubles (AoS [cell][10])
-        const int l = t - 256;
-        size_t base[2];
+        // 5 partials -> one cell (exact, any order).  A band's 32 cells are consecutive in cell_sums, so its output is one
+        // block of 320 doubles ([cell][10]) and lane l takes doubles l, l + 64, .. of BOTH bands: consecutive lanes store
+        // consecutive doubles from a uniform base, and the LDS source of double o = 10 cell + quantity,
+        // s_part[5 cell * kPartStride + quantity] = s_part[o + (5 kPartStride - 10) cell], is shared by the two bands.
+        const int l = t & 63;
+        static_assert(kBandThreads == 32 * 5 && kSumStride == 10, "a band is 32 cells of 5 partials, a cell 10 sums");
+        double* dst[2];
         int lim[2];
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
         {
-            const int bnd = pair * 2 + cb;
-            const int cr = bnd / p.segsPerRow;
-            const int sg = bnd - cr * p.segsPerRow;
-            base[cb] = (size_t)frame * p.cells + cr * p.hCells + sg * 32;
-            lim[cb] = bnd < p.bandsPerFrame ? p.hCells - sg * 32 : 0; // cells of the band that exist
+            dst[cb] = p.cell_sums + ((size_t)frame * p.cells + cellRowOf[cb] * p.hCells + segOf[cb] * 32) * kSumStride;
+            lim[cb] = bandExists[cb] ? p.hCells - segOf[cb] * 32 : 0; // cells of the band that exist
         }
 #pragma unroll
-        for (int k = 0; k < 10; ++k)
+        for (int k = 0; k < 5; ++k)
         {
-            const int e = l + 64 * k;
-            const int cell = e / 10;
-            const int m = e - cell * 10;
-            const int cb = cell >> 5, cs = cell & 31;
-            if (cs < (cb ? lim[1] : lim[0]))
+            const int o = l + 64 * k;
+            const int cs = o / kSumStride;
+            const double* src = s_part + o + (5 * kPartStride - kSumStride) * cs;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
             {
-                const double* src = s_part + (cb * kBandThreads + cs * 5) * kPartStride + m;
-                double acc = src[0];
-                acc += src[kPartStride];
-                acc += src[2 * kPartStride];
-                acc += src[3 * kPartStride];
-                acc += src[4 * kPartStride];
-                p.cell_sums[((cb ? base[1] : base[0]) + cs) * kSumStride + m] = acc;
+                if (cs < lim[cb])
+                {
+                    const double* sp = src + cb * kBandThreads * kPartStride;
+                    double acc = sp[0];
+                    acc += sp[kPartStride];
+                    acc += sp[2 * kPartStride];
+                    acc += sp[3 * kPartStride];
+                    acc += sp[4 * kPartStride];
+                    dst[cb][o] = acc;
+                }
             }
         }
         return;
@@ -223,10 +243,12 @@ template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void c
     // A step only needs `last`, the latest depth that passed.  If the first half (seed test, steps 1..9) passes, every positive
     // depth in it has become `last` in turn, so the second half (steps 10..) starts from the last positive depth among steps
     // 1..9, else from the seed max(z[0], z[1]) -- and if the first half fails the cell is discontinuous whatever the second
-    // half says.  The steps are straight-line code (is_continuous_flat), so all four tasks are one instruction stream of ten
-    // steps.  (Through round 4 wave 0 ran both scans of all 64 cells one behind the other, 37 branching steps on a lone wave;
-    // round 3's other extreme -- one lane per TEST on all five waves, a look-back loop per test -- measured slower.)
-    const int w = t >> 6, l = t & 63;
+    // half says.  The steps are straight-line code, so all four tasks are one instruction stream of ten steps: in f32
+    // (is_continuous_flat_f32), and once more in f64 (is_continuous_flat) if some step of some lane of the wave sits too close
+    // to its threshold for f32 to call.  (Through round 4 wave 0 ran both scans of all 64 cells one behind the other, 37
+    // branching steps on a lone wave; round 3's other extreme -- one lane per TEST on all five waves, a look-back loop per
+    // test -- measured slower.)
+    const int l = t & 63;
     const int c64 = w * 16 + (l & 15);   // cell of the workgroup (= lcell of the lanes that streamed it)
     const bool vertical = (l & 32) != 0;
     const bool second = (l & 16) != 0;
@@ -234,32 +256,51 @@ template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void c
     {
         const float* zs = (vertical ? s_col : s_row) + c64 * kCell;
         const float seed = std_maxf(zs[0], zs[1]);
-        float last = seed;
+        float start = seed;
 #pragma unroll
         for (int i = 1; i <= 9; ++i)
         {
             const float z = zs[i];
-            last = (second && z > 0) ? z : last;
+            start = (second && z > 0) ? z : start;
         }
-        continuous = second || !(seed <= 0);
+        const bool seeded = second || !(seed <= 0);
         const float* zt = zs + (second ? 10 : 1);
         const int steps = second ? (vertical ? 9 : 10) : 9;
+        float zk[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k)
+            zk[k] = zt[k];
+        float last = start;
+        bool unsure = false;
+        continuous = seeded;
 #pragma unroll
         for (int k = 0; k < 10; ++k)
         {
-            const bool pass = is_continuous_flat(zt[k], last);
+            // a step beyond the scan's last neither counts nor may ask for the f64 pass
+            bool stepUnsure = false;
+            const bool pass = is_continuous_flat_f32(zk[k], last, stepUnsure);
             continuous &= pass | (k >= steps);
+            unsure |= stepUnsure & (k < steps);
+        }
+        if (__any(unsure))
+        {
+            last = start;
+            continuous = seeded;
+#pragma unroll
+            for (int k = 0; k < 10; ++k)
+            {
+                const bool pass = is_continuous_flat(zk[k], last);
+                continuous &= pass | (k >= steps);
+            }
         }
         continuous &= __shfl_xor((int)continuous, 16) != 0;
         continuous &= __shfl_xor((int)continuous, 32) != 0;
     }
-    const int fb = c64 >> 5, fs = c64 & 31;
-    const int fband = pair * 2 + fb;
-    if ((l >> 4) != 0 || fband >= p.bandsPerFrame)
+    const int fb = w >> 1, fs = (w & 1) * 16 + (l & 15); // c64 >> 5, c64 & 31
+    if ((l >> 4) != 0 || !(fb ? bandExists[1] : bandExists[0]))
         return;
-    const int fRow = fband / p.segsPerRow;
-    const int fSeg = fband - fRow * p.segsPerRow;
-    const int fCol = fSeg * 32 + fs;
+    const int fRow = fb ? cellRowOf[1] : cellRowOf[0];
+    const int fCol = (fb ? segOf[1] : segOf[0]) * 32 + fs;
     if (fCol >= p.hCells)
         return;
     // exactness guard: all addends of every sum within 2^20 of each other (see header)
