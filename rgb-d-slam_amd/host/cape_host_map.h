@@ -1,6 +1,6 @@
-/* cape_host_map.h -- the host map update of libcape_primitives.so (host/polygon_capi.cpp): Feature_Map::update_map for one frame
- * on the host class, over a map in the layout of cape_map_upload (include/cape_hip.h).  Not part of libcape_hip's C ABI: no
- * function of libcape_hip takes these types. */
+/* cape_host_map.h -- the host twins of libcape_primitives.so (host/polygon_capi.cpp) that track planes without the device: the map
+ * matcher, the map update and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
+ * frame's kept planes.  Not part of libcape_hip's C ABI: no function of libcape_hip takes these types. */
 #ifndef CAPE_HOST_MAP_H
 #define CAPE_HOST_MAP_H
 
@@ -11,10 +11,8 @@ extern "C" {
 #endif
 
 /* Tracking state of one map plane, parallel to cape_map_plane: what Feature_Map::update_map (feature_map.hpp:367-384, :701-830)
- * reads and changes besides the plane and its polygon.  cape_host_map_update fuses one frame's matched planes into the map with it: MapPlane::update_with_match (map_primitive.cpp:204-251) per matched plane, the
- * counters of update_matched / update_unmatched (feature_map.hpp:112-129) for every plane, and optionally the StagedMapPlane
- * appends (map_primitive.cpp:262-285).  Promotion from staged to local, removal from staged and the loss of a local plane
- * reorder or delete entries of the ordered list: they are reported in `result` and left to the caller. */
+ * reads and changes besides the plane and its polygon.  Promotion from staged to local, removal from staged and the loss of a local
+ * plane reorder or delete entries of the ordered list: cape_host_map_update reports them in `result` and leaves them to the caller. */
 typedef struct cape_map_track
 {
     double covariance[16];      /* 4 x 4 covariance of (normal, d), row-major */
@@ -57,30 +55,71 @@ enum
                                      StagedMapPlane constructor would throw, nor one whose ring exceeds CAPE_MAP_MAX_RING) */
 };
 
-int cape_host_map_update(const cape_map_plane* planes, int32_t n_planes, const cape_map_ring* rings, int32_t n_rings, const double* vertices,
-                         int64_t n_vertices, const cape_map_track* tracks, const int32_t* match, int32_t n_det, const double* det_planes,
-                         const double* det_cov, const double* det_frames, const double* det_vertices, const int32_t* det_counts,
-                         const double* camera_to_world, const double* pose_covariance, uint32_t flags, uint64_t* next_id,
-                         cape_map_plane* planes_out, int32_t planes_capacity, cape_map_ring* rings_out, int32_t rings_capacity,
-                         double* vertices_out, int64_t vertices_capacity, cape_map_track* tracks_out, int32_t* n_planes_out,
-                         int32_t* n_rings_out, int64_t* n_vertices_out, int32_t* used_out);
+/* A map in the layout of cape_map_upload, with the tracking state parallel to the planes.  As an input the counts say what each
+ * array holds, the capacities are not read, and `tracks` may be NULL where the call does not read it (cape_host_match_map).  As an
+ * output (hence no const) the capacities say what each array takes, planes_capacity for `planes` and `tracks` alike, and the call
+ * writes the counts: what it produced or, with CAPE_ERR_CAPACITY, what it needs. */
+typedef struct cape_host_map
+{
+    cape_map_plane* planes;
+    cape_map_ring* rings;
+    double* vertices; /* (x, y) pairs */
+    cape_map_track* tracks;
+    int32_t n_planes, n_rings, planes_capacity, rings_capacity;
+    int64_t n_vertices, vertices_capacity;
+} cape_host_map;
+
+/* A frame's kept planes: those Primitive_Detection keeps (polygon with CAPE_POLY_VALID and >= 3 vertices,
+ * primitive_detection.cpp:623-631) in order, i.e. the reference's plane_container, whose indices every matcher result uses; n rows
+ * per column.  As an input the capacities are not read; cape_host_match_map does not read cov, cape_host_map_update not areas,
+ * neither segments.  As an output (cape_host_shard_frame) any column may be NULL, and n and n_vertices are written. */
+typedef struct cape_host_planes
+{
+    int32_t n, capacity;
+    int64_t n_vertices, vertices_capacity; /* (x, y) pairs of `vertices` */
+    double* planes;                        /* (normal[3], d) */
+    double* cov;                           /* 9 doubles: the point-cloud covariance (cape_plane_segment.cov) */
+    double* frames;                        /* (x_axis[3], y_axis[3], center[3]) of the polygon */
+    double* areas;                         /* the polygons' get_area(); as an input NULL = the area of each ring */
+    double* vertices;                      /* the rings one after the other */
+    int32_t* counts;                       /* the vertices of ring i */
+    int32_t* segments;                     /* the index of plane i in the frame's segment list */
+} cape_host_planes;
+
+/* MapPlane::find_matches (map_primitive.cpp:91-161) as Feature_Map::get_matches drives it (feature_map.hpp:647-670), for ONE frame on
+ * the host class: the twin of cape_match_map (tests/test_gpu_map_match.py compares them bit for bit) and the answer for a frame the
+ * device flags CAPE_MATCH_EXACT_OVERFLOW.  world_to_camera: 16 doubles row-major (NULL = identity); skip: ceil(n_planes / 32) words
+ * (NULL: none skipped); flags: CAPE_MATCH_*.  Outputs: match[n_planes], map_of[detected->n], inter_area[n_planes x detected->n]
+ * (NULL: not kept) -- the area of every gated pair of a visited map plane with a positive projected area, -1 elsewhere.  Returns 0,
+ * or CAPE_ERR_INVALID_ARGUMENT for a ring outside its array / of fewer than 3 vertices or a map plane without rings. */
+int cape_host_match_map(const cape_host_map* map, const cape_host_planes* detected, const double* world_to_camera, const uint32_t* skip,
+                        uint32_t flags, int32_t* match, int32_t* map_of, double* inter_area);
+
+/* Feature_Map::update_map (feature_map.hpp:367-384, :701-830) for ONE frame on the host class, over the ordered list of
+ * cape_map_upload (local planes first, then staged; CAPE_MAP_TRACK_STAGED tells them apart).  match[map->n_planes]: the kept plane
+ * matched to map plane j (cape_host_match_map / cape_copy_map_matches) or -1; camera_to_world: 16 doubles row-major;
+ * pose_covariance: 9 doubles; flags: CAPE_MAP_ADD_STAGED; next_id: the id of the first appended plane (advanced).  Per map plane in
+ * list order: MapPlane::update_with_match if matched (map_primitive.cpp:204-251 with track, plane_with_tracking.cpp:15-82), then
+ * update_matched / update_unmatched, the result bits of cape_map_track.  Then, with CAPE_MAP_ADD_STAGED, every kept plane that no map
+ * plane used (a local plane uses its detection only on success, a staged plane either way, feature_map.hpp:790-797) becomes a
+ * StagedMapPlane (map_primitive.cpp:262-285) in kept-plane order.  Outputs: map_out (every polygon as the host class stores it: outer
+ * ring clockwise, holes counter-clockwise, rings plane after plane) and used_out[detected->n] (NULL: not written).  Returns 0;
+ * CAPE_ERR_INVALID_ARGUMENT for a ring outside its array / of fewer than 3 vertices, a match out of range, or an invalid pose
+ * covariance (update_map throws); CAPE_ERR_CAPACITY if an array of map_out is too small or NULL -- nothing is written then but the
+ * three counts of map_out (next_id unchanged). */
+int cape_host_map_update(const cape_host_map* map, const int32_t* match, const cape_host_planes* detected, const double* camera_to_world,
+                         const double* pose_covariance, uint32_t flags, uint64_t* next_id, cape_host_map* map_out, int32_t* used_out);
 
 /* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
- * cape_gather_primitives[_root] or any other transport -- as the detected planes cape_host_match_map and cape_host_map_update take: no
- * handle, no device.  `frame` counts from the shard's first frame.  The planes are those Primitive_Detection keeps (packed polygon with
- * CAPE_POLY_VALID and >= 3 vertices, primitive_detection.cpp:623-631) in order, i.e. the reference's plane_container; each goes
- * through the host class's Polygon(ring, xAxis, yAxis, center) constructor, which is where ring, axes and area come from.
- * Outputs (each may be NULL; `capacity` planes, `vertices_capacity` (x, y) pairs): det_planes n x (normal[3], d); det_cov n x 9, the
- * point-cloud covariance restated from the packed sums (the inverse of their second-moment matrix by cofactors, plane_segment.cpp:192-203:
- * cape_plane_segment.cov bit for bit); det_frames n x (x_axis, y_axis, center); det_areas; the rings one after the other in
- * det_vertices with det_counts[i] vertices each; det_segments[i] = index of the plane in the frame's segment list.
- * Returns 0; CAPE_ERR_INVALID_ARGUMENT for a buffer that is no shard of this layout (size, magic, no polygon sections, frame out of
- * range, an offset outside its section) or whose header reports dropped planes or rings (the kept-plane indices would not be the
- * reference's); CAPE_ERR_CAPACITY if an output is too small -- *n_det_out and *n_vertices_out say what the frame needs either way. */
+ * cape_gather_primitives[_root] or any other transport -- as the kept planes the two calls above take: no handle, no device.
+ * `frame` counts from the shard's first frame.  Each plane goes through the host class's Polygon(ring, xAxis, yAxis, center)
+ * constructor, which is where ring, axes and area come from; cov is restated from the packed sums (the inverse of their
+ * second-moment matrix by cofactors, plane_segment.cpp:192-203: cape_plane_segment.cov bit for bit).  Returns 0;
+ * CAPE_ERR_INVALID_ARGUMENT for a buffer that is no shard of this layout (size, magic, no polygon sections, frame out of range, an
+ * offset outside its section) or whose header reports dropped planes or rings (the kept-plane indices would not be the
+ * reference's); CAPE_ERR_CAPACITY if detected_out is too small -- its n and n_vertices say what the frame needs either way. */
 int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, const cape_gather_layout* layout, const cape_gather_polygon_layout* polygon_layout,
-                          int32_t frame, int32_t capacity, int64_t vertices_capacity, double* det_planes, double* det_cov, double* det_frames,
-                          double* det_areas, double* det_vertices, int32_t* det_counts, int32_t* det_segments, int32_t* n_det_out,
-                          int64_t* n_vertices_out);
+                          int32_t frame, cape_host_planes* detected_out);
 
 #ifdef __cplusplus
 }

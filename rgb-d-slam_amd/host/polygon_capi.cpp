@@ -1,8 +1,9 @@
 // C entry points of libcape_primitives.so over the host boundary-polygon class.  None of them is part of libcape_hip's C ABI
 // (include/cape_hip.h).  cape_host_polygon, cape_host_polygon_inter_area* and the cape_host_covariance / kalman hooks at the
-// end are test hooks: the tests compare the device (or a numpy restatement) with them through ctypes.  cape_host_match_map and
-// cape_host_map_update are host twins a caller may use: the first answers the frames cape_match_map flags, the second is the
-// map update (declared in cape_host_map.h), which runs on the host only.
+// end are test hooks: the tests compare the device (or a numpy restatement) with them through ctypes.  cape_host_match_map,
+// cape_host_map_update and cape_host_shard_frame are host twins a caller may use, declared and described in cape_host_map.h: the
+// first answers the frames cape_match_map flags, the second is the map update, which runs on the host only, the third reads a
+// gathered shard.  They share the conversions of the anonymous namespace below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,17 +16,205 @@
 #include "cape_hip.h"
 #include "cape_host_map.h"
 
+namespace {
+
+using rgbd_slam::vector2;
+using rgbd_slam::vector3;
+using rgbd_slam::utils::Polygon;
+
+vector3 vec3(const double* p) { return vector3(p[0], p[1], p[2]); }
+void put3(double* out, const vector3& v) { out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; }
+
+// n (x, y) pairs as a ring of the host class
+std::vector<vector2> ring_from(const double* xy, size_t n)
+{
+    std::vector<vector2> ring;
+    for (size_t v = 0; v < n; ++v)
+        ring.emplace_back(xy[2 * v], xy[2 * v + 1]);
+    return ring;
+}
+
+// The polygon of map plane M: outer ring, holes, axes, centre (out NULL: the rings are checked, no polygon is built).  False for a
+// plane without rings, a ring outside its array or one of fewer than 3 vertices.
+bool map_polygon(const cape_host_map& map, const cape_map_plane& M, Polygon* out)
+{
+    if (M.ring_count == 0 || (uint64_t)M.ring_first + M.ring_count > (uint64_t)std::max(map.n_rings, 0))
+        return false;
+    std::vector<std::vector<vector2>> rings(M.ring_count);
+    for (uint32_t k = 0; k < M.ring_count; ++k)
+    {
+        const cape_map_ring& R = map.rings[M.ring_first + k];
+        if (R.vertex_count < 3 || (int64_t)R.vertex_offset + R.vertex_count > map.n_vertices)
+            return false;
+        rings[k] = ring_from(map.vertices + 2 * (size_t)R.vertex_offset, R.vertex_count);
+    }
+    if (out)
+        *out = Polygon(rings[0], {rings.begin() + 1, rings.end()}, vec3(M.x_axis), vec3(M.y_axis), vec3(M.center));
+    return true;
+}
+
+// A frame's kept planes as the host class's polygons.  False for a ring of fewer than min_count vertices or one that ends beyond
+// n_vertices.
+bool kept_polygons(const cape_host_planes& planes, int32_t min_count, std::vector<Polygon>& out)
+{
+    int64_t at = 0;
+    for (int32_t i = 0; i < planes.n; ++i)
+    {
+        if (planes.counts[i] < min_count || at + planes.counts[i] > planes.n_vertices)
+            return false;
+        const double* F = planes.frames + 9 * i;
+        out.emplace_back(ring_from(planes.vertices + 2 * at, planes.counts[i]), vec3(F), vec3(F + 3), vec3(F + 6));
+        at += planes.counts[i];
+    }
+    return true;
+}
+
+// Row n of a frame's kept planes (its ring from vertex nv on) from the packed plane, its packed polygon and the host class's
+// polygon of it; a NULL column is not written.
+void put_kept_plane(const cape_host_planes& out, int32_t n, int64_t nv, const cape_packed_plane& pl, const cape_polygon& g, const Polygon& polygon)
+{
+    if (out.planes)
+    {
+        std::memcpy(out.planes + 4 * n, pl.normal, 3 * sizeof(double));
+        out.planes[4 * n + 3] = pl.d;
+    }
+    if (out.cov)
+    {
+        // Plane_Segment::get_point_cloud_covariance: Matrix3d::inverse (cofactors) of {{Sxs,Sxy,Szx},{Sxy,Sys,Syz},{Szx,Syz,Szs}},
+        // statement for statement what the grow kernels store in cape_plane_segment.cov
+        const double* S = pl.sums;
+        const double m[3][3] = {{S[3], S[6], S[8]}, {S[6], S[4], S[7]}, {S[8], S[7], S[5]}};
+        const auto cof = [&](int i, int j) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            return m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
+        };
+        const double c00 = cof(0, 0), c10 = cof(1, 0), c20 = cof(2, 0);
+        const double det = (c00 * m[0][0] + c10 * m[1][0]) + c20 * m[2][0];
+        const double invdet = 1.0 / det;
+        double* r = out.cov + 9 * n;
+        r[0] = c00 * invdet; r[1] = c10 * invdet; r[2] = c20 * invdet;
+        for (int j = 1; j < 3; ++j)
+            for (int i = 0; i < 3; ++i)
+                r[3 * j + i] = cof(i, j) * invdet;
+    }
+    if (out.frames)
+    {
+        put3(out.frames + 9 * n, polygon.get_x_axis());
+        put3(out.frames + 9 * n + 3, polygon.get_y_axis());
+        std::memcpy(out.frames + 9 * n + 6, g.center, 3 * sizeof(double));
+    }
+    if (out.areas)
+        out.areas[n] = polygon.get_area();
+    if (out.vertices)
+        for (uint32_t v = 0; v < g.vertex_count; ++v)
+        {
+            out.vertices[2 * (nv + v)] = polygon.boundary()[v][0];
+            out.vertices[2 * (nv + v) + 1] = polygon.boundary()[v][1];
+        }
+    if (out.counts)
+        out.counts[n] = (int32_t)g.vertex_count;
+    if (out.segments)
+        out.segments[n] = (int32_t)g.segment;
+}
+
+struct MapEntry
+{
+    cape_map_plane plane;
+    cape_map_track track;
+    Polygon polygon;
+};
+
+// The entries as a map in cape_map_upload's layout, each plane's frame and rings from its polygon.  The three counts are
+// written either way; false, and nothing else written, if an array of `out` is too small or NULL.
+bool put_map(std::vector<MapEntry>& entries, cape_host_map& out)
+{
+    int32_t nr = 0;
+    int64_t nv = 0;
+    for (const MapEntry& e : entries)
+    {
+        nr += 1 + (int32_t)e.polygon.interior_rings().size();
+        nv += (int64_t)e.polygon.boundary().size();
+        for (const auto& h : e.polygon.interior_rings())
+            nv += (int64_t)h.size();
+    }
+    out.n_planes = (int32_t)entries.size();
+    out.n_rings = nr;
+    out.n_vertices = nv;
+    if ((int64_t)entries.size() > out.planes_capacity || nr > out.rings_capacity || nv > out.vertices_capacity || !out.planes || !out.tracks ||
+        !out.rings || !out.vertices)
+        return false;
+    int32_t r = 0;
+    int64_t v = 0;
+    for (size_t j = 0; j < entries.size(); ++j)
+    {
+        MapEntry& e = entries[j];
+        put3(e.plane.x_axis, e.polygon.get_x_axis());
+        put3(e.plane.y_axis, e.polygon.get_y_axis());
+        put3(e.plane.center, e.polygon.get_center());
+        e.plane.ring_first = (uint32_t)r;
+        e.plane.ring_count = 1 + (uint32_t)e.polygon.interior_rings().size();
+        auto put = [&](const std::vector<vector2>& ring) {
+            out.rings[r].vertex_offset = (uint32_t)v;
+            out.rings[r].vertex_count = (uint32_t)ring.size();
+            ++r;
+            for (const vector2& p : ring)
+            {
+                out.vertices[2 * v] = p[0];
+                out.vertices[2 * v + 1] = p[1];
+                ++v;
+            }
+        };
+        put(e.polygon.boundary());
+        for (const auto& h : e.polygon.interior_rings())
+            put(h);
+        out.planes[j] = e.plane;
+        out.tracks[j] = e.track;
+    }
+    return true;
+}
+
+// Eigen's isApprox on 3-vectors: |a - b|^2 <= prec^2 min(|a|^2, |b|^2)
+bool is_approx3(const vector3& a, const vector3& b)
+{
+    const double e0 = a[0] - b[0], e1 = a[1] - b[1], e2 = a[2] - b[2];
+    const double diff = (e0 * e0 + e1 * e1) + e2 * e2;
+    const double na = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], nb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+    const double prec = 1e-12;
+    return diff <= prec * prec * std::min(na, nb);
+}
+
+// CameraPolygon::to_world_space (polygon_coordinates.cpp:48-75): its norm and orthogonality checks, then the transform that
+// to_camera_space restates with the camera-to-world matrix.  False where the reference throws.
+bool to_world_space(const Polygon& p, const double* T, Polygon& out)
+{
+    using rgbd_slam::map_tracking::norm3;
+    using rgbd_slam::map_tracking::normalize3;
+    const vector3 x = p.get_x_axis(), y = p.get_y_axis();
+    double nx[3] = {(T[0] * x[0] + T[1] * x[1]) + T[2] * x[2], (T[4] * x[0] + T[5] * x[1]) + T[6] * x[2], (T[8] * x[0] + T[9] * x[1]) + T[10] * x[2]};
+    double ny[3] = {(T[0] * y[0] + T[1] * y[1]) + T[2] * y[2], (T[4] * y[0] + T[5] * y[1]) + T[6] * y[2], (T[8] * y[0] + T[9] * y[1]) + T[10] * y[2]};
+    normalize3(nx);
+    normalize3(ny);
+    const double eps = std::numeric_limits<double>::epsilon();
+    if (!(std::abs(norm3(nx) - 1.0) <= eps) || !(std::abs(norm3(ny) - 1.0) <= eps))
+        return false;
+    if (std::abs((ny[0] * nx[0] + ny[1] * nx[1]) + ny[2] * nx[2]) > .01)
+        return false;
+    out = p.to_camera_space(T);
+    return true;
+}
+
+} // namespace
+
 extern "C" int cape_host_polygon(const double* points3, int n, const double* normal, const double* center, double* ring_out, int capacity,
                                  int* count_out, double* area_out, double* x_axis_out, double* y_axis_out, int* valid_out)
 {
-    using rgbd_slam::vector3;
     try
     {
         std::vector<vector3> pts;
         pts.reserve(n);
         for (int i = 0; i < n; ++i)
             pts.emplace_back(points3[3 * i], points3[3 * i + 1], points3[3 * i + 2]);
-        const rgbd_slam::utils::Polygon poly(pts, vector3(normal[0], normal[1], normal[2]), vector3(center[0], center[1], center[2]));
+        const Polygon poly(pts, vec3(normal), vec3(center));
         const auto& ring = poly.boundary();
         *count_out = static_cast<int>(ring.size());
         for (size_t i = 0; i < ring.size() && static_cast<int>(i) < capacity; ++i)
@@ -34,11 +223,8 @@ extern "C" int cape_host_polygon(const double* points3, int n, const double* nor
             ring_out[2 * i + 1] = ring[i][1];
         }
         *area_out = poly.get_area();
-        for (int k = 0; k < 3; ++k)
-        {
-            x_axis_out[k] = poly.get_x_axis()[k];
-            y_axis_out[k] = poly.get_y_axis()[k];
-        }
+        put3(x_axis_out, poly.get_x_axis());
+        put3(y_axis_out, poly.get_y_axis());
         *valid_out = (poly.is_valid() && poly.boundary_length() >= 3) ? 1 : 0;
         return 0;
     }
@@ -57,15 +243,7 @@ extern "C" double cape_host_polygon_inter_area(const double* ring_a, int na, con
                                                const double* ring_b, int nb, const double* x_b, const double* y_b, const double* c_b,
                                                double* area_a_out, double* area_b_out)
 {
-    using rgbd_slam::vector2;
-    using rgbd_slam::vector3;
-    std::vector<vector2> ra, rb;
-    for (int i = 0; i < na; ++i)
-        ra.emplace_back(ring_a[2 * i], ring_a[2 * i + 1]);
-    for (int i = 0; i < nb; ++i)
-        rb.emplace_back(ring_b[2 * i], ring_b[2 * i + 1]);
-    const rgbd_slam::utils::Polygon a(ra, vector3(x_a[0], x_a[1], x_a[2]), vector3(y_a[0], y_a[1], y_a[2]), vector3(c_a[0], c_a[1], c_a[2]));
-    const rgbd_slam::utils::Polygon b(rb, vector3(x_b[0], x_b[1], x_b[2]), vector3(y_b[0], y_b[1], y_b[2]), vector3(c_b[0], c_b[1], c_b[2]));
+    const Polygon a(ring_from(ring_a, na), vec3(x_a), vec3(y_a), vec3(c_a)), b(ring_from(ring_b, nb), vec3(x_b), vec3(y_b), vec3(c_b));
     if (area_a_out)
         *area_a_out = a.get_area();
     if (area_b_out)
@@ -80,94 +258,44 @@ extern "C" double cape_host_polygon_inter_area_pose(const double* ring_a, int na
                                                     const double* ring_b, int nb, const double* x_b, const double* y_b, const double* c_b,
                                                     const double* world_to_camera, const double* plane_in, double* plane_out)
 {
-    using rgbd_slam::vector2;
-    using rgbd_slam::vector3;
-    std::vector<vector2> ra, rb;
-    for (int i = 0; i < na; ++i)
-        ra.emplace_back(ring_a[2 * i], ring_a[2 * i + 1]);
-    for (int i = 0; i < nb; ++i)
-        rb.emplace_back(ring_b[2 * i], ring_b[2 * i + 1]);
-    const rgbd_slam::utils::Polygon a(ra, vector3(x_a[0], x_a[1], x_a[2]), vector3(y_a[0], y_a[1], y_a[2]), vector3(c_a[0], c_a[1], c_a[2]));
-    const rgbd_slam::utils::Polygon b(rb, vector3(x_b[0], x_b[1], x_b[2]), vector3(y_b[0], y_b[1], y_b[2]), vector3(c_b[0], c_b[1], c_b[2]));
+    const Polygon a(ring_from(ring_a, na), vec3(x_a), vec3(y_a), vec3(c_a)), b(ring_from(ring_b, nb), vec3(x_b), vec3(y_b), vec3(c_b));
     if (plane_in && plane_out)
         rgbd_slam::utils::plane_to_camera(plane_in, plane_in[3], world_to_camera, plane_out, plane_out + 3);
     return a.inter_area(b.to_camera_space(world_to_camera));
 }
 
-// MapPlane::find_matches (map_primitive.cpp:91-161) as Feature_Map::get_matches drives it (feature_map.hpp:647-670), for ONE
-// frame on the host class: the twin of cape_match_map (tests/test_gpu_map_match.py compares them bit for bit) and the answer
-// for a frame the device flags CAPE_MATCH_EXACT_OVERFLOW.  The map is given as to cape_map_upload; the detected planes as the
-// frame's kept planes: det_planes = n_det x (normal[3], d), det_frames = n_det x (x_axis[3], y_axis[3], center[3]), their rings
-// one after the other in det_vertices (det_counts[i] vertices each), det_areas = the polygons' get_area() (NULL: the area of the
-// ring).  world_to_camera: 16 doubles row-major (NULL = identity); skip: ceil(n_planes / 32) words (NULL: none skipped).
-// Outputs: match[n_planes], map_of[n_det], inter_area[n_planes x n_det] (NULL: not kept) -- the area of every gated pair of a
-// visited map plane with a positive projected area, -1 elsewhere.  Returns 0, or CAPE_ERR_INVALID_ARGUMENT for a ring outside
-// its array / of fewer than 3 vertices or a map plane without rings.
-extern "C" int cape_host_match_map(const cape_map_plane* planes, int32_t n_planes, const cape_map_ring* rings, int32_t n_rings,
-                                   const double* vertices, int64_t n_vertices, int32_t n_det, const double* det_planes,
-                                   const double* det_frames, const double* det_areas, const double* det_vertices, const int32_t* det_counts,
-                                   const double* world_to_camera, const uint32_t* skip, uint32_t flags, int32_t* match, int32_t* map_of,
-                                   double* inter_area)
+// The map matcher's host twin (cape_host_map.h).
+extern "C" int cape_host_match_map(const cape_host_map* map, const cape_host_planes* detected, const double* world_to_camera,
+                                   const uint32_t* skip, uint32_t flags, int32_t* match, int32_t* map_of, double* inter_area)
 {
-    using rgbd_slam::vector2;
-    using rgbd_slam::vector3;
-    using rgbd_slam::utils::Polygon;
     static const double kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     const double* T = world_to_camera ? world_to_camera : kIdentity;
     const double minCos = std::abs(std::cos(20.0 * M_PI / 180.0)); // parameters.hpp:92-93, shape_primitives.cpp:72-73
     const double maxDistance = 100.0;                              // parameters.hpp:94-95
     const double overlap = (flags & CAPE_MATCH_ADVANCED) ? static_cast<double>(0.4f) / 2 : static_cast<double>(0.4f);
+    const int32_t n_planes = map->n_planes, n_det = detected->n;
     try
     {
         std::vector<Polygon> det;
+        if (!kept_polygons(*detected, 0, det))
+            return CAPE_ERR_INVALID_ARGUMENT;
         std::vector<double> detArea;
-        size_t at = 0;
         for (int32_t i = 0; i < n_det; ++i)
-        {
-            std::vector<vector2> ring;
-            for (int32_t v = 0; v < det_counts[i]; ++v, ++at)
-                ring.emplace_back(det_vertices[2 * at], det_vertices[2 * at + 1]);
-            const double* F = det_frames + 9 * i;
-            det.emplace_back(ring, vector3(F[0], F[1], F[2]), vector3(F[3], F[4], F[5]), vector3(F[6], F[7], F[8]));
-            detArea.push_back(det_areas ? det_areas[i] : det.back().get_area());
-        }
-        auto ring_of = [&](uint32_t r, std::vector<vector2>& out) {
-            if (r >= (uint32_t)n_rings || rings[r].vertex_count < 3 || (int64_t)rings[r].vertex_offset + rings[r].vertex_count > n_vertices)
-                return false;
-            out.clear();
-            for (uint32_t v = 0; v < rings[r].vertex_count; ++v)
-            {
-                const double* q = vertices + 2 * ((size_t)rings[r].vertex_offset + v);
-                out.emplace_back(q[0], q[1]);
-            }
-            return true;
-        };
+            detArea.push_back(detected->areas ? detected->areas[i] : det[i].get_area());
         std::vector<char> matched(n_det, 0);
-        for (int32_t i = 0; i < n_det; ++i)
-            map_of[i] = -1;
+        std::fill_n(map_of, n_det, -1);
+        std::fill_n(match, n_planes, -1);
+        if (inter_area)
+            std::fill_n(inter_area, (size_t)n_planes * n_det, -1.0);
         for (int32_t j = 0; j < n_planes; ++j)
         {
-            match[j] = -1;
-            if (inter_area)
-                for (int32_t i = 0; i < n_det; ++i)
-                    inter_area[(size_t)j * n_det + i] = -1.0;
-        }
-        for (int32_t j = 0; j < n_planes; ++j)
-        {
-            const cape_map_plane& M = planes[j];
-            if (M.ring_count == 0)
+            const cape_map_plane& M = map->planes[j];
+            const bool skipped = skip && ((skip[j >> 5] >> (j & 31)) & 1u); // is_moving() or not is_visible(worldToCamera): not visited
+            Polygon mapPolygon;
+            if (!map_polygon(*map, M, skipped ? nullptr : &mapPolygon))
                 return CAPE_ERR_INVALID_ARGUMENT;
-            std::vector<vector2> outer;
-            std::vector<std::vector<vector2>> holes(M.ring_count - 1);
-            if (!ring_of(M.ring_first, outer))
-                return CAPE_ERR_INVALID_ARGUMENT;
-            for (uint32_t k = 1; k < M.ring_count; ++k)
-                if (!ring_of(M.ring_first + k, holes[k - 1]))
-                    return CAPE_ERR_INVALID_ARGUMENT;
-            if (skip && ((skip[j >> 5] >> (j & 31)) & 1u)) // is_moving() or not is_visible(worldToCamera): not visited
+            if (skipped)
                 continue;
-            const Polygon mapPolygon(outer, holes, vector3(M.x_axis[0], M.x_axis[1], M.x_axis[2]), vector3(M.y_axis[0], M.y_axis[1], M.y_axis[2]),
-                                     vector3(M.center[0], M.center[1], M.center[2]));
             double pn[3], pd;
             rgbd_slam::utils::plane_to_camera(M.normal, M.d, T, pn, &pd);
             const Polygon projected = mapPolygon.to_camera_space(T);
@@ -177,7 +305,7 @@ extern "C" int cape_host_match_map(const cape_map_plane* planes, int32_t n_plane
             double greatest = 0.0;
             for (int32_t i = 0; i < n_det; ++i)
             {
-                const double* dn = det_planes + 4 * i;
+                const double* dn = detected->planes + 4 * i;
                 const double cosAngle = (dn[0] * pn[0] + dn[1] * pn[1]) + dn[2] * pn[2];
                 if (!(std::abs(dn[3] - pd) < maxDistance) || !(std::abs(cosAngle) > minCos))
                     continue;
@@ -206,17 +334,12 @@ extern "C" int cape_host_match_map(const cape_map_plane* planes, int32_t n_plane
     }
 }
 
-// One frame of a packed shard as the detected planes of the two calls around it (cape_host_map.h): the proof that what
+// One frame of a packed shard as the kept planes of the two calls around it (cape_host_map.h): the proof that what
 // CAPE_GATHER_POLYGONS ships is enough to track planes on a rank that never saw the frame.
 extern "C" int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, const cape_gather_layout* layout,
-                                     const cape_gather_polygon_layout* polygon_layout, int32_t frame, int32_t capacity, int64_t vertices_capacity,
-                                     double* det_planes, double* det_cov, double* det_frames, double* det_areas, double* det_vertices,
-                                     int32_t* det_counts, int32_t* det_segments, int32_t* n_det_out, int64_t* n_vertices_out)
+                                     const cape_gather_polygon_layout* polygon_layout, int32_t frame, cape_host_planes* detected_out)
 {
-    using rgbd_slam::vector2;
-    using rgbd_slam::vector3;
-    using rgbd_slam::utils::Polygon;
-    if (!shard || !layout || !polygon_layout || !n_det_out || !n_vertices_out || frame < 0 || capacity < 0 || vertices_capacity < 0)
+    if (!shard || !layout || !polygon_layout || !detected_out || frame < 0 || detected_out->capacity < 0 || detected_out->vertices_capacity < 0)
         return CAPE_ERR_INVALID_ARGUMENT;
     const cape_gather_layout& L = *layout;
     const cape_gather_polygon_layout& PL = *polygon_layout;
@@ -251,63 +374,17 @@ extern "C" int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, co
                 continue; // Primitive_Detection drops the plane
             if ((uint64_t)g.vertex_offset + g.vertex_count > (uint64_t)PL.vertices_capacity)
                 return CAPE_ERR_INVALID_ARGUMENT;
-            fits = fits && n < capacity && nv + g.vertex_count <= vertices_capacity;
+            fits = fits && n < detected_out->capacity && nv + g.vertex_count <= detected_out->vertices_capacity;
             if (fits)
             {
                 cape_packed_plane pl;
                 std::memcpy(&pl, base + L.planes_offset + (size_t)k * sizeof(pl), sizeof(pl));
                 std::vector<double> xy(2 * (size_t)g.vertex_count);
                 std::memcpy(xy.data(), base + PL.vertices_offset + (size_t)g.vertex_offset * 2 * sizeof(double), xy.size() * sizeof(double));
-                std::vector<vector2> ring;
-                for (uint32_t v = 0; v < g.vertex_count; ++v)
-                    ring.emplace_back(xy[2 * v], xy[2 * v + 1]);
-                const Polygon polygon(ring, vector3(g.x_axis[0], g.x_axis[1], g.x_axis[2]), vector3(g.y_axis[0], g.y_axis[1], g.y_axis[2]),
-                                      vector3(g.center[0], g.center[1], g.center[2]));
+                const Polygon polygon(ring_from(xy.data(), g.vertex_count), vec3(g.x_axis), vec3(g.y_axis), vec3(g.center));
                 if (polygon.boundary().size() != g.vertex_count)
                     return CAPE_ERR_INVALID_ARGUMENT; // (the constructor keeps an open ring as it is)
-                if (det_planes)
-                {
-                    std::memcpy(det_planes + 4 * n, pl.normal, 3 * sizeof(double));
-                    det_planes[4 * n + 3] = pl.d;
-                }
-                if (det_cov)
-                {
-                    // Plane_Segment::get_point_cloud_covariance: Matrix3d::inverse (cofactors) of {{Sxs,Sxy,Szx},{Sxy,Sys,Syz},{Szx,Syz,Szs}},
-                    // statement for statement what the grow kernels store in cape_plane_segment.cov
-                    const double* S = pl.sums;
-                    const double m[3][3] = {{S[3], S[6], S[8]}, {S[6], S[4], S[7]}, {S[8], S[7], S[5]}};
-                    const auto cof = [&](int i, int j) {
-                        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-                        return m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
-                    };
-                    const double c00 = cof(0, 0), c10 = cof(1, 0), c20 = cof(2, 0);
-                    const double det = (c00 * m[0][0] + c10 * m[1][0]) + c20 * m[2][0];
-                    const double invdet = 1.0 / det;
-                    double* r = det_cov + 9 * n;
-                    r[0] = c00 * invdet; r[1] = c10 * invdet; r[2] = c20 * invdet;
-                    for (int j = 1; j < 3; ++j)
-                        for (int i = 0; i < 3; ++i)
-                            r[3 * j + i] = cof(i, j) * invdet;
-                }
-                if (det_frames)
-                    for (int c = 0; c < 3; ++c)
-                    {
-                        det_frames[9 * n + c] = polygon.get_x_axis()[c];
-                        det_frames[9 * n + 3 + c] = polygon.get_y_axis()[c];
-                        det_frames[9 * n + 6 + c] = g.center[c];
-                    }
-                if (det_areas)
-                    det_areas[n] = polygon.get_area();
-                if (det_vertices)
-                    for (uint32_t v = 0; v < g.vertex_count; ++v)
-                    {
-                        det_vertices[2 * (nv + v)] = polygon.boundary()[v][0];
-                        det_vertices[2 * (nv + v) + 1] = polygon.boundary()[v][1];
-                    }
-                if (det_counts)
-                    det_counts[n] = (int32_t)g.vertex_count;
-                if (det_segments)
-                    det_segments[n] = (int32_t)g.segment;
+                put_kept_plane(*detected_out, n, nv, pl, g, polygon);
             }
             ++n;
             nv += g.vertex_count;
@@ -317,128 +394,39 @@ extern "C" int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, co
     {
         return CAPE_ERR_INVALID_ARGUMENT;
     }
-    *n_det_out = n;
-    *n_vertices_out = nv;
+    detected_out->n = n;
+    detected_out->n_vertices = nv;
     return fits ? 0 : CAPE_ERR_CAPACITY;
 }
 
-namespace {
-
-// Eigen's isApprox on 3-vectors: |a - b|^2 <= prec^2 min(|a|^2, |b|^2)
-bool is_approx3(const rgbd_slam::vector3& a, const rgbd_slam::vector3& b)
+// The host map update (cape_host_map.h).
+extern "C" int cape_host_map_update(const cape_host_map* map, const int32_t* match, const cape_host_planes* detected,
+                                    const double* camera_to_world, const double* pose_covariance, uint32_t flags, uint64_t* next_id,
+                                    cape_host_map* map_out, int32_t* used_out)
 {
-    const double e0 = a[0] - b[0], e1 = a[1] - b[1], e2 = a[2] - b[2];
-    const double diff = (e0 * e0 + e1 * e1) + e2 * e2;
-    const double na = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], nb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
-    const double prec = 1e-12;
-    return diff <= prec * prec * std::min(na, nb);
-}
-
-// CameraPolygon::to_world_space (polygon_coordinates.cpp:48-75): its norm and orthogonality checks, then the transform that
-// to_camera_space restates with the camera-to-world matrix.  False where the reference throws.
-bool to_world_space(const rgbd_slam::utils::Polygon& p, const double* T, rgbd_slam::utils::Polygon& out)
-{
-    using rgbd_slam::map_tracking::norm3;
-    using rgbd_slam::map_tracking::normalize3;
-    const rgbd_slam::vector3 x = p.get_x_axis(), y = p.get_y_axis();
-    double nx[3] = {(T[0] * x[0] + T[1] * x[1]) + T[2] * x[2], (T[4] * x[0] + T[5] * x[1]) + T[6] * x[2], (T[8] * x[0] + T[9] * x[1]) + T[10] * x[2]};
-    double ny[3] = {(T[0] * y[0] + T[1] * y[1]) + T[2] * y[2], (T[4] * y[0] + T[5] * y[1]) + T[6] * y[2], (T[8] * y[0] + T[9] * y[1]) + T[10] * y[2]};
-    normalize3(nx);
-    normalize3(ny);
-    const double eps = std::numeric_limits<double>::epsilon();
-    if (!(std::abs(norm3(nx) - 1.0) <= eps) || !(std::abs(norm3(ny) - 1.0) <= eps))
-        return false;
-    if (std::abs((ny[0] * nx[0] + ny[1] * nx[1]) + ny[2] * nx[2]) > .01)
-        return false;
-    out = p.to_camera_space(T);
-    return true;
-}
-
-struct MapEntry
-{
-    cape_map_plane plane;
-    cape_map_track track;
-    rgbd_slam::utils::Polygon polygon;
-};
-
-} // namespace
-
-// Feature_Map::update_map (feature_map.hpp:367-384, :701-830) for ONE frame on the host class, over the ordered map list of
-// cape_map_upload (local planes first, then staged; CAPE_MAP_TRACK_STAGED tells them apart): the twin of the device map update.
-// Inputs: the map as cape_host_match_map takes it plus its tracking state (n_planes entries); match[n_planes] = the detected
-// kept-plane index matched to map plane j (cape_host_match_map / cape_copy_map_matches), or -1; the frame's kept planes as
-// cape_host_match_map takes them plus det_cov = n_det x 9 doubles (cape_plane_segment.cov); camera_to_world: 16 doubles
-// row-major; pose_covariance: 9 doubles; flags: CAPE_MAP_ADD_STAGED; next_id: the id of the first appended plane (advanced).
-// Per map plane in list order: MapPlane::update_with_match if matched (map_primitive.cpp:204-251 with track,
-// plane_with_tracking.cpp:15-82), then update_matched / update_unmatched, the result bits of cape_map_track.  Then, with
-// CAPE_MAP_ADD_STAGED, every kept plane that no map plane used (a local plane uses its detection only on success, a staged
-// plane either way, feature_map.hpp:790-797) becomes a StagedMapPlane (map_primitive.cpp:262-285) in kept-plane order, unless
-// its constructor would throw or its ring exceeds CAPE_MAP_MAX_RING.  Outputs: the new map in cape_map_upload's layout (every
-// polygon as the host class stores it: outer ring clockwise, holes counter-clockwise, rings plane after plane), the new
-// tracking state, and used_out[n_det] (NULL: not written).  Returns 0; CAPE_ERR_INVALID_ARGUMENT for a ring outside its array /
-// of fewer than 3 vertices, a match out of range, or an invalid pose covariance (update_map throws); CAPE_ERR_CAPACITY if an
-// output array is too small -- nothing is written then but the three sizes the call needs (next_id unchanged).
-extern "C" int cape_host_map_update(const cape_map_plane* planes, int32_t n_planes, const cape_map_ring* rings, int32_t n_rings,
-                                    const double* vertices, int64_t n_vertices, const cape_map_track* tracks, const int32_t* match,
-                                    int32_t n_det, const double* det_planes, const double* det_cov, const double* det_frames,
-                                    const double* det_vertices, const int32_t* det_counts, const double* camera_to_world,
-                                    const double* pose_covariance, uint32_t flags, uint64_t* next_id, cape_map_plane* planes_out,
-                                    int32_t planes_capacity, cape_map_ring* rings_out, int32_t rings_capacity, double* vertices_out,
-                                    int64_t vertices_capacity, cape_map_track* tracks_out, int32_t* n_planes_out, int32_t* n_rings_out,
-                                    int64_t* n_vertices_out, int32_t* used_out)
-{
-    using rgbd_slam::vector2;
-    using rgbd_slam::vector3;
-    using rgbd_slam::utils::Polygon;
     namespace mt = rgbd_slam::map_tracking;
-    if (n_planes < 0 || n_det < 0 || n_det > CAPE_MAX_PLANES || !camera_to_world || !pose_covariance || !next_id || !n_planes_out ||
-        !n_rings_out || !n_vertices_out || (n_planes > 0 && (!planes || !tracks || !match)) || (flags & ~(uint32_t)CAPE_MAP_ADD_STAGED))
+    if (!map || !detected || !map_out || map->n_planes < 0 || detected->n < 0 || detected->n > CAPE_MAX_PLANES || !camera_to_world ||
+        !pose_covariance || !next_id || (map->n_planes > 0 && (!map->planes || !map->tracks || !match)) || (flags & ~(uint32_t)CAPE_MAP_ADD_STAGED))
         return CAPE_ERR_INVALID_ARGUMENT;
+    const int32_t n_planes = map->n_planes, n_det = detected->n;
+    const double *det_planes = detected->planes, *det_cov = detected->cov;
     const double* T = camera_to_world;
     if (!mt::is_covariance_valid(pose_covariance, 3))
         return CAPE_ERR_INVALID_ARGUMENT; // update_map: "The given pose covariance is invalid, map wont be update"
     try
     {
         std::vector<Polygon> det;
-        size_t at = 0;
-        for (int32_t i = 0; i < n_det; ++i)
-        {
-            if (det_counts[i] < 3)
-                return CAPE_ERR_INVALID_ARGUMENT;
-            std::vector<vector2> ring;
-            for (int32_t v = 0; v < det_counts[i]; ++v, ++at)
-                ring.emplace_back(det_vertices[2 * at], det_vertices[2 * at + 1]);
-            const double* F = det_frames + 9 * i;
-            det.emplace_back(ring, vector3(F[0], F[1], F[2]), vector3(F[3], F[4], F[5]), vector3(F[6], F[7], F[8]));
-        }
-        auto ring_of = [&](uint32_t r, std::vector<vector2>& out) {
-            if (r >= (uint32_t)n_rings || rings[r].vertex_count < 3 || (int64_t)rings[r].vertex_offset + rings[r].vertex_count > n_vertices)
-                return false;
-            out.clear();
-            for (uint32_t v = 0; v < rings[r].vertex_count; ++v)
-            {
-                const double* q = vertices + 2 * ((size_t)rings[r].vertex_offset + v);
-                out.emplace_back(q[0], q[1]);
-            }
-            return true;
-        };
+        if (!kept_polygons(*detected, 3, det))
+            return CAPE_ERR_INVALID_ARGUMENT;
         std::vector<char> used(n_det, 0);
         std::vector<MapEntry> out;
         out.reserve(n_planes + n_det);
         for (int32_t j = 0; j < n_planes; ++j)
         {
-            const cape_map_plane& M = planes[j];
-            if (M.ring_count == 0 || match[j] < -1 || match[j] >= n_det)
+            const cape_map_plane& M = map->planes[j];
+            MapEntry e {M, map->tracks[j], Polygon()};
+            if (match[j] < -1 || match[j] >= n_det || !map_polygon(*map, M, &e.polygon))
                 return CAPE_ERR_INVALID_ARGUMENT;
-            std::vector<vector2> outer;
-            std::vector<std::vector<vector2>> holes(M.ring_count - 1);
-            if (!ring_of(M.ring_first, outer))
-                return CAPE_ERR_INVALID_ARGUMENT;
-            for (uint32_t k = 1; k < M.ring_count; ++k)
-                if (!ring_of(M.ring_first + k, holes[k - 1]))
-                    return CAPE_ERR_INVALID_ARGUMENT;
-            MapEntry e {M, tracks[j], Polygon(outer, holes, vector3(M.x_axis[0], M.x_axis[1], M.x_axis[2]),
-                                              vector3(M.y_axis[0], M.y_axis[1], M.y_axis[2]), vector3(M.center[0], M.center[1], M.center[2]))};
             uint32_t result = 0;
             const bool staged = (e.track.flags & CAPE_MAP_TRACK_STAGED) != 0;
             const int32_t i = match[j];
@@ -553,56 +541,10 @@ extern "C" int cape_host_map_update(const cape_map_plane* planes, int32_t n_plan
                 e.track.id = id++;
                 out.push_back(std::move(e));
             }
-        // sizes, then the arrays
-        int32_t nr = 0;
-        int64_t nv = 0;
-        for (const MapEntry& e : out)
-        {
-            nr += 1 + (int32_t)e.polygon.interior_rings().size();
-            nv += (int64_t)e.polygon.boundary().size();
-            for (const auto& h : e.polygon.interior_rings())
-                nv += (int64_t)h.size();
-        }
-        *n_planes_out = (int32_t)out.size();
-        *n_rings_out = nr;
-        *n_vertices_out = nv;
-        if ((int64_t)out.size() > planes_capacity || nr > rings_capacity || nv > vertices_capacity || !planes_out || !tracks_out ||
-            !rings_out || !vertices_out)
+        if (!put_map(out, *map_out))
             return CAPE_ERR_CAPACITY;
-        int32_t r = 0;
-        int64_t v = 0;
-        for (size_t j = 0; j < out.size(); ++j)
-        {
-            MapEntry& e = out[j];
-            const vector3 x = e.polygon.get_x_axis(), y = e.polygon.get_y_axis(), c = e.polygon.get_center();
-            for (int k = 0; k < 3; ++k)
-            {
-                e.plane.x_axis[k] = x[k];
-                e.plane.y_axis[k] = y[k];
-                e.plane.center[k] = c[k];
-            }
-            e.plane.ring_first = (uint32_t)r;
-            e.plane.ring_count = 1 + (uint32_t)e.polygon.interior_rings().size();
-            auto put = [&](const std::vector<vector2>& ring) {
-                rings_out[r].vertex_offset = (uint32_t)v;
-                rings_out[r].vertex_count = (uint32_t)ring.size();
-                ++r;
-                for (const vector2& p : ring)
-                {
-                    vertices_out[2 * v] = p[0];
-                    vertices_out[2 * v + 1] = p[1];
-                    ++v;
-                }
-            };
-            put(e.polygon.boundary());
-            for (const auto& h : e.polygon.interior_rings())
-                put(h);
-            planes_out[j] = e.plane;
-            tracks_out[j] = e.track;
-        }
         if (used_out)
-            for (int32_t i = 0; i < n_det; ++i)
-                used_out[i] = used[i];
+            std::copy(used.begin(), used.end(), used_out);
         *next_id = id;
         return 0;
     }

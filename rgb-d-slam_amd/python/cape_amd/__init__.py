@@ -192,6 +192,22 @@ MAP_TRACK_STAGED, MAP_TRACK_MOVING = 1, 2
  MAP_RESULT_FAIL_KALMAN, MAP_RESULT_FAIL_POLYGON, MAP_RESULT_OVERFLOW, MAP_RESULT_PROMOTE, MAP_RESULT_DROP, MAP_RESULT_LOST,
  MAP_RESULT_APPENDED) = (1 << k for k in range(12))
 MAP_ADD_STAGED = 1
+CAPE_ERR_CAPACITY = -4
+
+
+class cape_host_map(C.Structure):
+    """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
+    _fields_ = [("planes", C.c_void_p), ("rings", C.c_void_p), ("vertices", C.c_void_p), ("tracks", C.c_void_p),
+                ("n_planes", C.c_int32), ("n_rings", C.c_int32), ("planes_capacity", C.c_int32), ("rings_capacity", C.c_int32),
+                ("n_vertices", C.c_int64), ("vertices_capacity", C.c_int64)]
+
+
+class cape_host_planes(C.Structure):
+    """a frame's kept planes, column by column (cape_host_map.h)"""
+    _fields_ = [("n", C.c_int32), ("capacity", C.c_int32), ("n_vertices", C.c_int64), ("vertices_capacity", C.c_int64),
+                ("planes", C.c_void_p), ("cov", C.c_void_p), ("frames", C.c_void_p), ("areas", C.c_void_p), ("vertices", C.c_void_p),
+                ("counts", C.c_void_p), ("segments", C.c_void_p)]
+
 
 _host_lib = None
 
@@ -205,18 +221,63 @@ def _host_library():
         if not os.path.exists(path):
             raise CapeError(f"{path} is missing: build it with `make -C rgb-d-slam_amd/csrc host`")
         L = C.CDLL(path)
-        vp = C.c_void_p
-        L.cape_host_match_map.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp,
-                                          C.c_uint32, vp, vp, vp]
-        L.cape_host_match_map.restype = C.c_int
-        L.cape_host_map_update.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp,
-                                           vp, C.c_uint32, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp, vp, vp, vp, vp]
-        L.cape_host_map_update.restype = C.c_int
-        L.cape_host_shard_frame.argtypes = [vp, C.c_uint64, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout), C.c_int32,
-                                            C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-        L.cape_host_shard_frame.restype = C.c_int
+        f64, i32, Map, Planes = (C.POINTER(t) for t in (C.c_double, C.c_int32, cape_host_map, cape_host_planes))
+        L.cape_host_match_map.argtypes = [Map, Planes, f64, C.POINTER(C.c_uint32), C.c_uint32, i32, i32, f64]
+        L.cape_host_map_update.argtypes = [Map, i32, Planes, f64, f64, C.c_uint32, C.POINTER(C.c_uint64), Map, i32]
+        L.cape_host_shard_frame.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout),
+                                            C.c_int32, Planes]
         _host_lib = L
     return _host_lib
+
+
+def _as(a, ctype):
+    """numpy array (or None) -> POINTER(ctype) into it"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+
+
+def _view(struct, arrays, **sizes):
+    """`struct` over numpy arrays given by field name (None: NULL), with its counts or capacities; the caller keeps the arrays alive"""
+    return struct(**{k: a.ctypes.data for k, a in arrays.items() if a is not None}, **sizes)
+
+
+def _map_arrays(map_arrays, tracks=None):
+    """pack_map's triple (+ tracks) as contiguous arrays by cape_host_map's field names, and the struct over them"""
+    P, R, V = map_arrays
+    arrays = dict(planes=np.ascontiguousarray(P, MAP_PLANE_DTYPE), rings=np.ascontiguousarray(R, MAP_RING_DTYPE),
+                  vertices=np.ascontiguousarray(V, np.float64).reshape(-1, 2), tracks=tracks)
+    return arrays, _view(cape_host_map, arrays, n_planes=len(P), n_rings=len(R), n_vertices=len(arrays["vertices"]))
+
+
+def _pack_detected(detected, with_cov):
+    """The `detected` list of the host twins -- (normal, d, x_axis, y_axis, center, ring, area[, cov]) per kept plane -- as arrays by
+    cape_host_planes' field names, and the struct over them.  areas is NULL unless every plane brings one."""
+    rings = [np.ascontiguousarray(det[5], np.float64).reshape(-1, 2) for det in detected]
+    cols = dict(planes=np.array([[*det[0], det[1]] for det in detected], np.float64).reshape(-1, 4),
+                frames=np.array([np.concatenate(det[2:5]) for det in detected], np.float64).reshape(-1, 9),
+                counts=np.array([len(r) for r in rings], np.int32), vertices=np.concatenate(rings + [np.zeros((0, 2))]),
+                cov=np.array([det[7] for det in detected], np.float64).reshape(-1, 9) if with_cov else None,
+                areas=np.array([det[6] for det in detected], np.float64) if all(det[6] is not None for det in detected) else None)
+    return cols, _view(cape_host_planes, cols, n=len(detected), n_vertices=len(cols["vertices"]))
+
+
+def _unpack_detected(cols, n):
+    """the first n rows of cape_host_planes' columns, all present, as (the `detected` list with covariances, segments)"""
+    at = np.concatenate([[0], np.cumsum(cols["counts"][:n])])
+    P, F = cols["planes"], cols["frames"]
+    detected = [(P[i, :3].copy(), float(P[i, 3]), F[i, 0:3].copy(), F[i, 3:6].copy(), F[i, 6:9].copy(), cols["vertices"][at[i]:at[i + 1]].copy(),
+                 float(cols["areas"][i]), cols["cov"][i].reshape(3, 3).copy()) for i in range(n)]
+    return detected, cols["segments"][:n].copy()
+
+
+def _retry_on_capacity(what, call, sizes):
+    """call(*sizes) -> (status, result, the sizes the call reports); once more with those on CAPE_ERR_CAPACITY"""
+    for _ in range(2):
+        rc, result, sizes = call(*sizes)
+        if rc != CAPE_ERR_CAPACITY:
+            break
+    if rc != 0:
+        raise CapeError(f"{what} failed ({rc})")
+    return result
 
 
 def host_map_update(map_arrays, tracks, match, detected, camera_to_world, pose_covariance, flags=0, next_id=0):
@@ -229,52 +290,31 @@ def host_map_update(map_arrays, tracks, match, detected, camera_to_world, pose_c
     3 x 3 point-cloud covariance (cape_plane_segment.cov); camera_to_world: 4 x 4; pose_covariance: 3 x 3.
     Returns ((planes, rings, vertices), tracks, used[n_det] bool, next_id) -- the new map in pack_map's layout."""
     L = _host_library()
-    P, R, V = map_arrays
-    P = np.ascontiguousarray(P, MAP_PLANE_DTYPE)
-    R = np.ascontiguousarray(R, MAP_RING_DTYPE)
-    V = np.ascontiguousarray(V, np.float64).reshape(-1, 2)
-    Tr = np.ascontiguousarray(tracks, MAP_TRACK_DTYPE)
-    n_map, n_det = len(P), len(detected)
-    if len(Tr) != n_map:
+    src, src_view = _map_arrays(map_arrays, np.ascontiguousarray(tracks, MAP_TRACK_DTYPE))
+    n_map, n_det = len(src["planes"]), len(detected)
+    if len(src["tracks"]) != n_map:
         raise CapeError("host_map_update: one track per map plane")
     M = np.ascontiguousarray(match, np.int32).reshape(-1)
     if len(M) != n_map:
         raise CapeError("host_map_update: one match per map plane")
-    dp = np.zeros((max(n_det, 1), 4))
-    dcov = np.zeros((max(n_det, 1), 9))
-    df = np.zeros((max(n_det, 1), 9))
-    dc = np.zeros(max(n_det, 1), np.int32)
-    rings = []
-    for i, (normal, d, x_axis, y_axis, center, ring, _area, cov) in enumerate(detected):
-        dp[i, :3], dp[i, 3] = normal, d
-        dcov[i] = np.asarray(cov, np.float64).reshape(9)
-        df[i, 0:3], df[i, 3:6], df[i, 6:9] = x_axis, y_axis, center
-        r = np.ascontiguousarray(ring, np.float64).reshape(-1, 2)
-        dc[i] = len(r)
-        rings.append(r)
-    dv = np.ascontiguousarray(np.concatenate(rings) if rings else np.zeros((1, 2)), np.float64)
+    cols, det_view = _pack_detected(detected, with_cov=True)
     T = np.ascontiguousarray(camera_to_world, np.float64).reshape(16)
     S = np.ascontiguousarray(pose_covariance, np.float64).reshape(9)
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     nid = C.c_uint64(next_id)
-    n_p, n_r, n_v = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     used = np.zeros(max(n_det, 1), np.int32)
-    cap_p, cap_r, cap_v = n_map + n_det, 2 * (len(R) + n_det) + 8, 2 * (len(V) + int(dc[:n_det].sum())) + 64
-    for _ in range(2):  # the second pass with the sizes the first one reported
-        Po = np.zeros(max(cap_p, 1), MAP_PLANE_DTYPE)
-        Ro = np.zeros(max(cap_r, 1), MAP_RING_DTYPE)
-        Vo = np.zeros((max(cap_v, 1), 2))
-        To = np.zeros(max(cap_p, 1), MAP_TRACK_DTYPE)
-        rc = L.cape_host_map_update(ptr(P), n_map, ptr(R), len(R), ptr(V), len(V), ptr(Tr), ptr(M), n_det, ptr(dp), ptr(dcov),
-                                    ptr(df), ptr(dv), ptr(dc), ptr(T), ptr(S), flags, C.byref(nid), ptr(Po), len(Po), ptr(Ro),
-                                    len(Ro), ptr(Vo), len(Vo), ptr(To), C.byref(n_p), C.byref(n_r), C.byref(n_v), ptr(used))
-        if rc != -4:  # CAPE_ERR_CAPACITY
-            break
-        cap_p, cap_r, cap_v = n_p.value, n_r.value, n_v.value
-    if rc != 0:
-        raise CapeError(f"cape_host_map_update failed ({rc})")
-    return ((Po[:n_p.value].copy(), Ro[:n_r.value].copy(), Vo[:n_v.value].copy()), To[:n_p.value].copy(),
-            used[:n_det].astype(bool), nid.value)
+
+    def call(cap_p, cap_r, cap_v):
+        out = dict(planes=np.zeros(max(cap_p, 1), MAP_PLANE_DTYPE), rings=np.zeros(max(cap_r, 1), MAP_RING_DTYPE),
+                   vertices=np.zeros((max(cap_v, 1), 2)), tracks=np.zeros(max(cap_p, 1), MAP_TRACK_DTYPE))
+        v = _view(cape_host_map, out, planes_capacity=len(out["planes"]), rings_capacity=len(out["rings"]), vertices_capacity=len(out["vertices"]))
+        rc = L.cape_host_map_update(C.byref(src_view), _as(M, C.c_int32), C.byref(det_view), _as(T, C.c_double), _as(S, C.c_double), flags,
+                                    C.byref(nid), C.byref(v), _as(used, C.c_int32))
+        return rc, (out, v), (v.n_planes, v.n_rings, v.n_vertices)
+
+    out, v = _retry_on_capacity("cape_host_map_update", call, (n_map + n_det, 2 * (len(src["rings"]) + n_det) + 8,
+                                                               2 * (len(src["vertices"]) + len(cols["vertices"])) + 64))
+    return ((out["planes"][:v.n_planes].copy(), out["rings"][:v.n_rings].copy(), out["vertices"][:v.n_vertices].copy()),
+            out["tracks"][:v.n_planes].copy(), used[:n_det].astype(bool), nid.value)
 
 
 def host_shard_frame(buf, layout, k):
@@ -286,24 +326,16 @@ def host_shard_frame(buf, layout, k):
     buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
     lay = cape_gather_layout(**{f: int(layout.get(f, 0)) for f, _ in cape_gather_layout._fields_})
     pl = cape_gather_polygon_layout(**{f: int(layout.get(f, 0)) for f, _ in cape_gather_polygon_layout._fields_})
-    n, nv = C.c_int32(0), C.c_int64(0)
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    cap, vcap = 0, 0
-    for _ in range(2):  # the second pass with the sizes the first one reported
-        dp, dcov, df = np.zeros((max(cap, 1), 4)), np.zeros((max(cap, 1), 9)), np.zeros((max(cap, 1), 9))
-        da, dc, ds = np.zeros(max(cap, 1)), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
-        dv = np.zeros((max(vcap, 1), 2))
-        rc = L.cape_host_shard_frame(ptr(buf), buf.size, C.byref(lay), C.byref(pl), k, cap, vcap, ptr(dp), ptr(dcov), ptr(df), ptr(da),
-                                     ptr(dv), ptr(dc), ptr(ds), C.byref(n), C.byref(nv))
-        if rc != -4:  # CAPE_ERR_CAPACITY
-            break
-        cap, vcap = n.value, nv.value
-    if rc != 0:
-        raise CapeError(f"cape_host_shard_frame failed ({rc})")
-    at = np.concatenate([[0], np.cumsum(dc[:n.value])])
-    detected = [(dp[i, :3].copy(), float(dp[i, 3]), df[i, 0:3].copy(), df[i, 3:6].copy(), df[i, 6:9].copy(), dv[at[i]:at[i + 1]].copy(),
-                 float(da[i]), dcov[i].reshape(3, 3).copy()) for i in range(n.value)]
-    return detected, ds[:n.value].copy()
+
+    def call(cap, vcap):
+        n = max(cap, 1)
+        cols = dict(planes=np.zeros((n, 4)), cov=np.zeros((n, 9)), frames=np.zeros((n, 9)), areas=np.zeros(n), vertices=np.zeros((max(vcap, 1), 2)),
+                    counts=np.zeros(n, np.int32), segments=np.zeros(n, np.int32))
+        v = _view(cape_host_planes, cols, capacity=cap, vertices_capacity=vcap)
+        rc = L.cape_host_shard_frame(buf.ctypes.data, buf.size, C.byref(lay), C.byref(pl), k, C.byref(v))
+        return rc, (cols, v.n), (v.n, v.n_vertices)
+
+    return _unpack_detected(*_retry_on_capacity("cape_host_shard_frame", call, (0, 0)))
 
 
 def host_match_map(map_arrays, detected, world_to_camera=None, skip=None, flags=0, areas=False):
@@ -320,32 +352,17 @@ def host_match_map_call(map_arrays, detected, world_to_camera=None, skip=None, f
     """host_match_map with the arguments packed now and the native call deferred: returns run(), which makes only the call and
     returns host_match_map's result (timing the twin from several threads without the packing)."""
     _host_library()
-    P, R, V = map_arrays
-    n_det = len(detected)
-    dp = np.zeros((max(n_det, 1), 4))
-    df = np.zeros((max(n_det, 1), 9))
-    da = np.zeros(max(n_det, 1))
-    dc = np.zeros(max(n_det, 1), np.int32)
-    rings = []
-    have_area = all(det[6] is not None for det in detected)
-    for i, (normal, d, x_axis, y_axis, center, ring, area) in enumerate(detected):
-        dp[i, :3], dp[i, 3] = normal, d
-        df[i, 0:3], df[i, 3:6], df[i, 6:9] = x_axis, y_axis, center
-        da[i] = area if area is not None else 0.0
-        r = np.ascontiguousarray(ring, np.float64).reshape(-1, 2)
-        dc[i] = len(r)
-        rings.append(r)
-    dv = np.ascontiguousarray(np.concatenate(rings) if rings else np.zeros((1, 2)), np.float64)
+    src, src_view = _map_arrays(map_arrays)
+    cols, det_view = _pack_detected(detected, with_cov=False)
     T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(16)
     S = None if skip is None else np.ascontiguousarray(skip, np.uint32)
-    n_map = len(P)
+    n_map, n_det = len(src["planes"]), len(detected)
     match = np.full(max(n_map, 1), -1, np.int32)
     map_of = np.full(max(n_det, 1), -1, np.int32)
     inter = np.full((max(n_map, 1), max(n_det, 1)), -1.0) if areas else None
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    args = (ptr(P), n_map, ptr(R), len(R), ptr(V), len(V), n_det, ptr(dp), ptr(df), ptr(da) if have_area else None, ptr(dv),
-            ptr(dc), ptr(T), ptr(S), flags, ptr(match), ptr(map_of), ptr(inter))
-    keep = (P, R, V, dp, df, da, dv, dc, T, S)
+    args = (C.byref(src_view), C.byref(det_view), _as(T, C.c_double), _as(S, C.c_uint32), flags, _as(match, C.c_int32),
+            _as(map_of, C.c_int32), _as(inter, C.c_double))
+    keep = (src, cols, T, S)
 
     def run():
         """the native call alone (ctypes releases the GIL for its duration)"""

@@ -132,14 +132,27 @@ class Shard:
         """[(plane, polygon, ring)] of the frame's planes that Primitive_Detection keeps -- CAPE_POLY_VALID and >= 3 vertices
         (primitive_detection.cpp:623-631) -- in order: entry i is plane i of the reference's plane_container, the index every matcher
         result is expressed in.  Refuses a shard that dropped planes or rings: its indices would not be the reference's."""
-        from . import PACKED_PLANES_DROPPED, PACKED_VERTICES_DROPPED, POLY_VALID
+        from . import PACKED_PLANES_DROPPED, PACKED_VERTICES_DROPPED
 
         if int(self.header["overflow"]) & (PACKED_PLANES_DROPPED | PACKED_VERTICES_DROPPED):
             raise ValueError("the shard dropped planes or rings (header.overflow): the kept planes are not known")
         planes = self.frame_planes(k)
         pol, rings = self.frame_polygons(k)
-        return [(planes[i], pol[i], rings[i]) for i in range(len(pol))
-                if int(pol[i]["flags"]) & POLY_VALID and int(pol[i]["vertex_count"]) >= 3]
+        return [(planes[i], pol[i], rings[i]) for i in range(len(pol)) if polygon_is_kept(pol[i])]
+
+
+def polygon_is_kept(polygon):
+    """The kept-plane rule on one POLYGON_DTYPE record: Primitive_Detection keeps the plane if its polygon is CAPE_POLY_VALID with
+    >= 3 vertices (primitive_detection.cpp:623-631)."""
+    from . import POLY_VALID
+
+    return bool(int(polygon["flags"]) & POLY_VALID) and int(polygon["vertex_count"]) >= 3
+
+
+def kept_segments(results, polygons, f):
+    """Segment indices of the planes of frame f that Primitive_Detection keeps, in order (the index every matcher result is expressed
+    in counts these): results = Extractor.results(n), polygons = the records of Extractor.polygons(n)."""
+    return [i for i, s in enumerate(results.segments(f)) if s["is_output"] and polygon_is_kept(polygons[f, i])]
 
 
 def unpack_gathered(buf, world, layout):

@@ -35,6 +35,7 @@ def test_struct_sizes_match_header(hip_library):
     assert cape_amd.PACKED_PLANE_DTYPE.itemsize == 152 and cape_amd.PACKED_CYLINDER_DTYPE.itemsize == 32
     assert cape_amd.CELL_STATS_DTYPE.itemsize == 18 * 8 + 6 * 4
     assert cape_amd.MATCH_DTYPE.itemsize == 8 + 64 * 4 + 2 * 64 * 2 + 64 * 64 * 2
+    assert C.sizeof(cape_amd.cape_host_map) == 4 * 8 + 4 * 4 + 2 * 8 and C.sizeof(cape_amd.cape_host_planes) == 2 * 4 + 2 * 8 + 7 * 8
 
 
 def test_no_cpu_fallback(hip_library):

@@ -42,7 +42,7 @@ def _w2c(R, o):
 
 def _kept(ex, n):
     """per frame: the kept planes as host_match_map takes them, and their segment indices"""
-    import cape_amd
+    from cape_amd.dist import kept_segments
 
     res = ex.results(n)
     pol, ver = ex.polygons(n)
@@ -50,12 +50,11 @@ def _kept(ex, n):
     for f in range(n):
         segs = res.segments(f)
         kept = []
-        for i, s in enumerate(segs):
-            p = pol[f, i]
-            if s["is_output"] and (p["flags"] & cape_amd.POLY_VALID) and p["vertex_count"] >= 3:
-                ring = ver[f, p["vertex_offset"]: p["vertex_offset"] + p["vertex_count"]].copy()
-                kept.append((i, (s["out_normal"].copy(), float(s["d"]), p["x_axis"].copy(), p["y_axis"].copy(), p["center"].copy(), ring,
-                                 float(p["area"]))))
+        for i in kept_segments(res, pol, f):
+            s, p = segs[i], pol[f, i]
+            ring = ver[f, p["vertex_offset"]: p["vertex_offset"] + p["vertex_count"]].copy()
+            kept.append((i, (s["out_normal"].copy(), float(s["d"]), p["x_axis"].copy(), p["y_axis"].copy(), p["center"].copy(), ring,
+                             float(p["area"]))))
         out.append(kept)
     return out
 

@@ -44,10 +44,9 @@ def _bits(a):
 
 def _kept(res, pol, f):
     """Segment indices of the planes Primitive_Detection keeps (primitive_detection.cpp:623-631), in order."""
-    import cape_amd
+    from cape_amd.dist import kept_segments
 
-    segs = res.segments(f)
-    return [i for i, s in enumerate(segs) if s["is_output"] and (pol[f, i]["flags"] & cape_amd.POLY_VALID) and pol[f, i]["vertex_count"] >= 3]
+    return kept_segments(res, pol, f)
 
 
 def _expected(res, pol, ver, f, host_inter, flags):

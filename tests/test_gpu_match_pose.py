@@ -62,9 +62,9 @@ def _strided(scene, seed, start, stride, n):
 
 
 def _kept(res, pol, f):
-    import cape_amd
+    from cape_amd.dist import kept_segments
 
-    return [i for i, s in enumerate(res.segments(f)) if s["is_output"] and (pol[f, i]["flags"] & cape_amd.POLY_VALID) and pol[f, i]["vertex_count"] >= 3]
+    return kept_segments(res, pol, f)
 
 
 def _run(scene, seed, start, stride, n, poses=True, flags=0, cyl=False):
