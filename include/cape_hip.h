@@ -483,6 +483,10 @@ enum
     CAPE_MATCH_EXACT_HOST = 1u << 1     /* never set by the library: the C++ overlay marks the entries its host class computed (frame
                                            pairs across a chunk / shard boundary, frames the device flagged); match[] is filled,
                                            seg_prev / seg_cur / inter_area are not */
+    ,
+    CAPE_MATCH_EXACT_BAD_SHARD = 1u << 3 /* cape_match_map_shards only, next to CAPE_MATCH_EXACT_OVERFLOW: the shard's header or the frame's
+                                           indices do not fit the layout the caller gave; nothing of it was read (bit 2 is taken by the
+                                           INPUT flag CAPE_MATCH_MAP_AREAS) */
 };
 typedef struct cape_frame_match_exact
 {
@@ -526,7 +530,8 @@ typedef struct cape_map_plane
 typedef struct cape_frame_map_match
 {
     int32_t n_map, n_cur;                 /* map planes of the call / kept planes of the frame */
-    uint32_t flags;                       /* CAPE_MATCH_EXACT_OVERFLOW: no match is reported for the frame, use the host class */
+    uint32_t flags;                       /* CAPE_MATCH_EXACT_OVERFLOW: no match is reported for the frame, use the host class
+                                             (+ CAPE_MATCH_EXACT_BAD_SHARD from cape_match_map_shards) */
     int32_t n_matched;                    /* map planes that took a plane of this frame */
     int32_t seg_cur[CAPE_MAX_PLANES];     /* segment index of kept plane i, -1 beyond n_cur */
     int32_t map_of[CAPE_MAX_PLANES];      /* map plane that took kept plane i, or -1 */
@@ -563,6 +568,44 @@ int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camer
  * mm^2; -1 where the pair was not gated or the map plane was skipped / has no positive projected area, NaN: capacity).  Either
  * of match / inter_area may be NULL.  Refuses more frames than the last cape_match_map covered. */
 int cape_copy_map_matches(cape_handle h, int32_t n_frames, cape_frame_map_match* frames, int32_t* match, double* inter_area);
+
+/* cape_match_map for the frames of GATHERED SHARDS: what the rank that owns the map does with the world x bytes_per_rank bytes a
+ * gather left in its device memory, without a host read of them.  shards_dev: n_shards shards of layout->bytes_per_rank bytes, rank
+ * after rank, packed with CAPE_GATHER_POLYGONS -- the recv_dev of cape_gather_primitives[_root], or the slot cape_pack_primitives
+ * returns (n_shards = 1); 16-byte aligned.  layout / polygon_layout: what cape_gather_configure_polygons reported on the PRODUCERS;
+ * this handle needs no gather configuration of its own, need never have run cape_extract and may have any max_batch: the call uses
+ * the map of cape_map_upload and nothing else of the handle.
+ * Results, world_to_camera (n_slots x 16 doubles) and skip (n_slots x ceil(n_map / 32) words; both HOST memory, read before the call
+ * returns, NULL as for cape_match_map) are indexed by SLOT s = shard x frames_capacity + k, n_slots = n_shards x frames_capacity:
+ * how many frames a shard holds is known on the device only.  A slot with k >= the shard's n_frames is EMPTY: n_map set, n_cur = 0,
+ * n_matched = 0, flags = 0, its match row all -1.
+ * Per served slot the semantics are cape_match_map's (gates, projected-area rule, tiers, selection, flags, CAPE_MATCH_MAP_AREAS with
+ * its 1 GiB cap).  Kept plane i of a frame is the i-th of its packed planes whose packed polygon has CAPE_POLY_VALID and >= 3
+ * vertices; seg_cur[i] is that plane's cape_packed_plane.segment, the index in the FRAME's segment list (>= 64 in a frame that
+ * continued in spill records on its producer: the packed lists follow the chain, so such a frame is served here whenever it keeps at
+ * most 64 planes).  A slot is flagged CAPE_MATCH_EXACT_OVERFLOW, and reports no match, when its frame keeps more than 64 planes,
+ * holds a polygon with CAPE_POLY_OVERFLOW, has planes beyond planes_capacity (CAPE_PACKED_PLANES_DROPPED) or a polygon whose ring
+ * did not travel (vertex_offset == UINT32_MAX: with vertex_count = 0 the kept rule cannot be evaluated), or exceeds the intersection
+ * capacities / the work list as in cape_match_map.  The frames of a shard that dropped rings which lie wholly before the first
+ * dropped ring are served -- cape_host_shard_frame (host/cape_host_map.h), the answer for a flagged slot, refuses that whole shard.
+ * The shard bytes come from another process: every index read from a shard is checked against its section before it is used and
+ * the kernels never read outside n_shards x bytes_per_rank.  All slots of a shard are flagged CAPE_MATCH_EXACT_BAD_SHARD |
+ * CAPE_MATCH_EXACT_OVERFLOW, and nothing beyond the header is read, when its header has a wrong magic, no CAPE_GATHER_POLYGONS,
+ * frames_capacity / planes_capacity / cells or the polygon header's vertices_capacity other than the layouts', or n_frames outside
+ * [0, frames_capacity]; one frame is flagged the same way, and not read, when its plane_offset / n_planes lie outside the plane
+ * section (without the header's CAPE_PACKED_PLANES_DROPPED) or one of its rings ends beyond vertices_capacity.
+ * CAPE_ERR_INVALID_ARGUMENT: a NULL handle / shards / layout, n_shards < 1, an unknown flag, no map uploaded, a layout whose
+ * sections do not fit bytes_per_rank, overlap or are not 16-byte aligned; CAPE_ERR_CAPACITY: more than INT32_MAX slots, the area table beyond
+ * 1 GiB.  Asynchronous on `stream`; the shard memory is the caller's and must stay untouched until that work has been waited for.
+ * Behind a gather the caller orders the call with cape_gather_wait(h, stream, 0) first.
+ * The results live in buffers of their own, sized by the call's slots: cape_match_map / cape_copy_map_matches and this pair do not
+ * disturb each other's results, and a cape_extract does not invalidate these. */
+int cape_match_map_shards(cape_handle h, const void* shards_dev, int32_t n_shards, const cape_gather_layout* layout,
+                          const cape_gather_polygon_layout* polygon_layout, const double* world_to_camera, const uint32_t* skip,
+                          uint32_t flags, void* stream);
+/* Synchronous copy of the last cape_match_map_shards, slots [0, n_slots): the arrays of cape_copy_map_matches, indexed by slot.
+ * CAPE_ERR_CAPACITY: more slots than that call covered. */
+int cape_copy_shard_map_matches(cape_handle h, int32_t n_slots, cape_frame_map_match* frames, int32_t* match, double* inter_area);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as

@@ -91,6 +91,40 @@ MapWorkLayout map_work_layout(int maxBatch, size_t cap)
 }
 constexpr size_t kMapWorkMax = (size_t)1 << 24;     // entries of the work list at most (448 MB of buffers)
 constexpr size_t kMapAreasBudget = (size_t)1 << 30; // bytes of the dense inter-area table at most
+// what cape_match_map and cape_match_map_shards pass to their kernels alike: the uploaded map, the work buffers inside `work`, the
+// device's limits
+void bind_map_call(cape::MatchMapParams& p, const cape_handle_s* h, unsigned char* work, const MapWorkLayout& lay, size_t cap)
+{
+    const auto& map = h->map;
+    p.mapPlanes = map.planes;
+    p.mapRings = map.rings;
+    p.mapVertices = reinterpret_cast<const double2*>(map.vertices.get());
+    p.nMap = map.n;
+    p.skipWords = (map.n + 31) / 32;
+    p.counts = reinterpret_cast<unsigned*>(work + lay.counts);
+    p.frameRange = reinterpret_cast<uint2*>(work + lay.ranges);
+    p.gateMasks = reinterpret_cast<unsigned long long*>(work + lay.masks);
+    p.work = reinterpret_cast<unsigned long long*>(work + lay.work);
+    p.workArea = reinterpret_cast<double*>(work + lay.area);
+    p.tierLists = reinterpret_cast<unsigned*>(work + lay.tiers);
+    p.workCapacity = cap;
+    p.computeUnits = h->computeUnits;
+    p.ldsLimitBytes = h->ldsLimit;
+}
+// the pinned twin's bytes of such a call: n x 16 doubles (the identity where no poses are given: the statements stay those of a pose),
+// then the skip words
+void fill_poses(void* stage, int n, const double* world_to_camera, size_t poseBytes, const uint32_t* skip, size_t skipBytes)
+{
+    double* pose = static_cast<double*>(stage);
+    if (world_to_camera)
+        std::memcpy(pose, world_to_camera, poseBytes);
+    else
+        for (int f = 0; f < n; ++f)
+            for (int k = 0; k < 16; ++k)
+                pose[16 * f + k] = (k % 5 == 0) ? 1.0 : 0.0;
+    if (skipBytes)
+        std::memcpy(static_cast<unsigned char*>(stage) + poseBytes, skip, skipBytes);
+}
 bool unit_norm(const double* v) // double_equal(norm, 1) as to_camera_space requires (polygon_coordinates.cpp:144-151)
 {
     return std::abs(std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) - 1.0) <= std::numeric_limits<double>::epsilon();
@@ -410,45 +444,23 @@ int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camer
     StreamScope streamScope(h, stream);
     if (streamScope.rc() != CAPE_OK)
         return streamScope.rc();
-    // the poses (identity where none are given: the statements stay those of a pose), then the skip bits, travel through the
-    // pinned twin like cape_match_polygons_pose's: n_frames x 16 doubles, then n_frames x skipWords words
+    // the poses, then the skip bits, travel through the pinned twin like cape_match_polygons_pose's: n_frames x 16 doubles, then
+    // n_frames x skipWords words
     const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double);
     const size_t skipBytes = skip ? (size_t)n_frames * skipWords * sizeof(uint32_t) : 0;
-    CAPE_HIP_TRY(map.posesTwin.upload(map.poses, poseBytes + skipBytes, poseCapacity, stream, [&](void* stage) {
-        double* pose = static_cast<double*>(stage);
-        if (world_to_camera)
-            std::memcpy(pose, world_to_camera, poseBytes);
-        else
-            for (int f = 0; f < n_frames; ++f)
-                for (int k = 0; k < 16; ++k)
-                    pose[16 * f + k] = (k % 5 == 0) ? 1.0 : 0.0;
-        if (skipBytes)
-            std::memcpy(static_cast<unsigned char*>(stage) + poseBytes, skip, skipBytes);
-    }));
+    CAPE_HIP_TRY(map.posesTwin.upload(map.poses, poseBytes + skipBytes, poseCapacity, stream,
+                                      [&](void* stage) { fill_poses(stage, n_frames, world_to_camera, poseBytes, skip, skipBytes); }));
     cape::MatchMapParams p;
     p.records = h->res.records;
     p.polygons = h->poly.polygons;
     p.vertices = reinterpret_cast<const double2*>(h->poly.vertices.get());
     p.boundaryCapacity = h->boundaryCap;
-    p.mapPlanes = map.planes;
-    p.mapRings = map.rings;
-    p.mapVertices = reinterpret_cast<const double2*>(map.vertices.get());
-    p.nMap = map.n;
-    p.skipWords = skipWords;
+    bind_map_call(p, h, map.work, lay, cap);
     p.poses = reinterpret_cast<const double*>(map.poses.get());
     p.skip = skipBytes ? reinterpret_cast<const uint32_t*>(map.poses + poseBytes) : nullptr;
     p.frames = map.frames;
     p.match = map.match;
     p.areas = keepAreas ? map.areas.get() : nullptr;
-    p.counts = reinterpret_cast<unsigned*>(map.work + lay.counts);
-    p.frameRange = reinterpret_cast<uint2*>(map.work + lay.ranges);
-    p.gateMasks = reinterpret_cast<unsigned long long*>(map.work + lay.masks);
-    p.work = reinterpret_cast<unsigned long long*>(map.work + lay.work);
-    p.workArea = reinterpret_cast<double*>(map.work + lay.area);
-    p.tierLists = reinterpret_cast<unsigned*>(map.work + lay.tiers);
-    p.workCapacity = cap;
-    p.computeUnits = h->computeUnits;
-    p.ldsLimitBytes = h->ldsLimit;
     set_match_thresholds(p, flags);
     CAPE_HIP_TRY(cape::launch_match_map(p, n_frames, stream));
     map.matchFrames = n_frames;
@@ -474,6 +486,119 @@ int cape_copy_map_matches(cape_handle h, int32_t n_frames, cape_frame_map_match*
     CAPE_HIP_TRY(copy_out(frames, map.frames, 0, (size_t)n_frames));
     CAPE_HIP_TRY(copy_out(match, map.match, 0, n));
     CAPE_HIP_TRY(copy_out(inter_area, map.areas, 0, n * CAPE_MAX_PLANES));
+    return CAPE_OK;
+}
+
+int cape_match_map_shards(cape_handle h, const void* shards_dev, int32_t n_shards, const cape_gather_layout* layout,
+                          const cape_gather_polygon_layout* polygon_layout, const double* world_to_camera, const uint32_t* skip,
+                          uint32_t flags, void* stream_)
+{
+    if (!h || !shards_dev || !layout || !polygon_layout || n_shards < 1)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, shards or layout, or fewer than one shard");
+    if (h->map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
+    // the sections the kernels read lie inside one shard, on 16-byte boundaries and one behind the other in the order the pack writes
+    // them (the shards follow each other at bytes_per_rank)
+    const cape_gather_layout& L = *layout;
+    const cape_gather_polygon_layout& PL = *polygon_layout;
+    uint64_t end = 0; // of the sections accepted so far
+    const auto section_fits = [&](uint64_t offset, int64_t count, uint64_t size) {
+        if (offset % 16 != 0 || count < 0 || offset < end || offset > L.bytes_per_rank || (uint64_t)count > (L.bytes_per_rank - offset) / size)
+            return false;
+        end = offset + (uint64_t)count * size;
+        return true;
+    };
+    if (L.bytes_per_rank % 16 != 0 || reinterpret_cast<uintptr_t>(shards_dev) % 16 != 0 || L.frames_capacity < 1 || L.cells < 0 ||
+        PL.polygons_capacity != L.planes_capacity || !section_fits(0, 1, sizeof(cape_packed_header)) ||
+        !section_fits(L.frames_offset, L.frames_capacity, sizeof(cape_packed_frame)) ||
+        !section_fits(L.planes_offset, L.planes_capacity, sizeof(cape_packed_plane)) ||
+        !section_fits(PL.polygon_header_offset, 1, sizeof(cape_packed_polygon_header)) ||
+        !section_fits(PL.polygons_offset, PL.polygons_capacity, sizeof(cape_polygon)) ||
+        !section_fits(PL.vertices_offset, PL.vertices_capacity, 2 * sizeof(double)))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "the layout's sections do not fit bytes_per_rank, overlap or are not 16-byte aligned (pass the layouts "
+                                               "of cape_gather_configure_polygons, and 16-byte aligned shards)");
+    if ((int64_t)n_shards * L.frames_capacity > std::numeric_limits<int32_t>::max())
+        return fail(CAPE_ERR_CAPACITY, "n_shards x frames_capacity exceeds an int32");
+    const int nSlots = n_shards * L.frames_capacity;
+    auto& S = h->shardMatch;
+    const int nMap = h->map.n;
+    const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0;
+    const size_t areaDoubles = (size_t)nSlots * nMap * CAPE_MAX_PLANES;
+    if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
+        return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer shards per call, or no CAPE_MATCH_MAP_AREAS)");
+    CAPE_ON_DEVICE(h);
+    S.slots = 0; // (the buffers of the last call's results may be replaced below)
+    const int skipWords = (nMap + 31) / 32;
+    const size_t poseBytes = (size_t)nSlots * 16 * sizeof(double);
+    const size_t skipBytes = skip ? (size_t)nSlots * skipWords * sizeof(uint32_t) : 0;
+    const size_t cap = std::min((size_t)nSlots * (size_t)std::max(nMap, 1) * CAPE_MAX_PLANES, kMapWorkMax);
+    const MapWorkLayout lay = map_work_layout(nSlots, cap);
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them
+    if (S.poses.size() < poseBytes + skipBytes)
+    {
+        // (the pinned twin has the size of its device buffer: both are replaced)
+        CAPE_HIP_TRY(drain());
+        S.posesTwin = cape::abi::PinnedTwin{};
+        CAPE_HIP_TRY(S.poses.alloc(poseBytes + (size_t)nSlots * (CAPE_MAP_MAX_PLANES / 32) * sizeof(uint32_t)));
+    }
+    CAPE_HIP_TRY(S.frames.grow((size_t)nSlots, drain));
+    CAPE_HIP_TRY(S.match.grow((size_t)nSlots * std::max(nMap, 1), drain));
+    CAPE_HIP_TRY(S.kept.grow((size_t)nSlots * CAPE_MAX_PLANES, drain));
+    CAPE_HIP_TRY(S.work.grow(lay.total, drain));
+    if (keepAreas)
+        CAPE_HIP_TRY(S.areas.grow(areaDoubles, drain));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    CAPE_HIP_TRY(S.posesTwin.upload(S.poses, poseBytes + skipBytes, S.poses.size(), stream,
+                                    [&](void* stage) { fill_poses(stage, nSlots, world_to_camera, poseBytes, skip, skipBytes); }));
+    cape::MatchMapParams p{};
+    bind_map_call(p, h, S.work, lay, cap);
+    p.poses = reinterpret_cast<const double*>(S.poses.get());
+    p.skip = skipBytes ? reinterpret_cast<const uint32_t*>(S.poses + poseBytes) : nullptr;
+    p.frames = S.frames;
+    p.match = S.match;
+    p.areas = keepAreas ? S.areas.get() : nullptr;
+    p.shards = static_cast<const unsigned char*>(shards_dev);
+    p.shardBytes = (size_t)L.bytes_per_rank;
+    p.framesOffset = (size_t)L.frames_offset;
+    p.planesOffset = (size_t)L.planes_offset;
+    p.polygonHeaderOffset = (size_t)PL.polygon_header_offset;
+    p.polygonsOffset = (size_t)PL.polygons_offset;
+    p.verticesOffset = (size_t)PL.vertices_offset;
+    p.framesCapacity = L.frames_capacity;
+    p.planesCapacity = L.planes_capacity;
+    p.verticesCapacity = PL.vertices_capacity;
+    p.cells = L.cells;
+    p.keptIndex = S.kept;
+    set_match_thresholds(p, flags);
+    CAPE_HIP_TRY(cape::launch_match_map(p, nSlots, stream));
+    S.slots = nSlots;
+    S.matchN = nMap;
+    S.matchAreas = keepAreas;
+    return CAPE_OK;
+}
+
+int cape_copy_shard_map_matches(cape_handle h, int32_t n_slots, cape_frame_map_match* frames, int32_t* match, double* inter_area)
+{
+    if (!h || n_slots < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    const auto& S = h->shardMatch;
+    if (n_slots > S.slots)
+        return fail(CAPE_ERR_CAPACITY, "n_slots exceeds the slots of the last cape_match_map_shards");
+    if (inter_area && n_slots > 0 && !S.matchAreas)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_match_map_shards did not keep the inter-area table (CAPE_MATCH_MAP_AREAS)");
+    if (n_slots == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    const size_t n = (size_t)n_slots * S.matchN;
+    CAPE_HIP_TRY(copy_out(frames, S.frames, 0, (size_t)n_slots));
+    CAPE_HIP_TRY(copy_out(match, S.match, 0, n));
+    CAPE_HIP_TRY(copy_out(inter_area, S.areas, 0, n * CAPE_MAX_PLANES));
     return CAPE_OK;
 }
 

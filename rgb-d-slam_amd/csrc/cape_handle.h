@@ -342,6 +342,23 @@ struct cape_handle_s
         bool matchAreas = false;             // ... and whether it kept the dense table
     } map;
 
+    // cape_match_map_shards: the uploaded map against gathered shards.  Results and work buffers of its own, sized by the call's
+    // slots and grown on demand behind drain_handle -- nothing here depends on max_batch or on the batch of the last cape_extract,
+    // and cape_match_map's state above is not touched
+    struct ShardMatch
+    {
+        Buffer<unsigned char> poses; // the poses of the call (slots x 16 doubles), then its skip words
+        cape::abi::PinnedTwin posesTwin;
+        Buffer<cape_frame_map_match> frames; // slots
+        Buffer<int32_t> match;               // slots x n_map
+        Buffer<uint2> kept;                  // slots x CAPE_MAX_PLANES: MatchMapParams::keptIndex
+        Buffer<double> areas;                // CAPE_MATCH_MAP_AREAS: slots x n_map x CAPE_MAX_PLANES
+        Buffer<unsigned char> work;          // map_work_layout
+        int slots = 0;                       // slots of the last cape_match_map_shards (0: none yet)
+        int matchN = 0;                      // map planes of that call
+        bool matchAreas = false;             // ... and whether it kept the dense table
+    } shardMatch;
+
     // Per-handle scratch (depth staging, rectify keys, hand-over feedback, result buffers) is reused from call to call
     // without per-buffer events: ONE stream is in flight per handle.  Every enqueueing call leaves a handle-owned event
     // behind its work (StreamScope); a call that arrives on ANOTHER stream makes that stream wait for the event

@@ -243,6 +243,15 @@ struct MatchMapParams
     int ldsLimitBytes;
     uint32_t flags;
     double minCosAngle, maxDistance, minOverlap; // as MatchParams
+    // cape_match_map_shards: the detected planes come out of gathered shards (cape_gather.hip's packed buffer, CAPE_GATHER_POLYGONS)
+    // instead of the handle's records.  `frames`, `poses`, `skip`, `match` ... are then indexed by SLOT = shard x framesCapacity + k
+    // and records / polygons / vertices are not read.
+    const unsigned char* shards = nullptr; // shards x shardBytes, or null: the record source
+    size_t shardBytes = 0;
+    size_t framesOffset = 0, planesOffset = 0, polygonHeaderOffset = 0, polygonsOffset = 0, verticesOffset = 0; // sections of a shard
+    int framesCapacity = 0, planesCapacity = 0, verticesCapacity = 0, cells = 0;                              // ... and what its header must say
+    uint2* keptIndex = nullptr; // slots x CAPE_MAX_PLANES, written by the gate kernel: (packed plane = polygon index of kept plane i, the slot's
+                                // shard) -- one load tells the later kernels where the polygon lies, without dividing the slot by framesCapacity
 };
 
 // multi-GPU gather: device-side packing of the ragged primitive lists (cape_gather.hip)

@@ -4,7 +4,8 @@
 // in world coordinates and their polygons (grown by merge_union) may have holes; they stay on the device between batches
 // (cape_map_upload).
 //
-//   cape_map_gate_kernel         : one wavefront per frame, lanes over map planes: plane_to_camera of map plane j
+//   cape_map_gate_kernel /
+//   cape_map_gate_shards_kernel  : one wavefront per frame, lanes over map planes: plane_to_camera of map plane j
 //        (plane_coordinates.cpp:20-24), the gates is_distance_similar / is_normal_similar (shape_primitives.cpp:66-86) against
 //        every kept plane i of the frame; for a map plane with a gated pair, the area of its polygon seen from the camera
 //        (to_camera_space, polygon_coordinates.cpp:135-165, holes included) -- <= 0: it matches nothing and lists no pair --
@@ -16,6 +17,13 @@
 //   cape_map_select_kernel       : one wavefront per frame: map plane after map plane in order, lanes over the gated pairs of
 //        the plane; wave arg-max of the area above the overlap threshold (lowest index on a tie), the `selectedIndex <= 0`
 //        quirk, the is-matched mask.
+//
+// The detected planes come from one of two SOURCES, a template parameter of the kernels (detected_polygon): the records and polygon
+// rows of the handle's last batch (cape_match_map), or gathered shards in device memory (cape_match_map_shards: the packed lists of
+// cape_gather.hip with CAPE_GATHER_POLYGONS, a "frame" being a slot shard x frames_capacity + k).  The shard source has a gate
+// kernel of its own, cape_map_gate_shards_kernel, which finds the kept planes among the frame's packed polygons and checks every
+// index it reads from the shard -- the bytes come from another process -- before the shared part of the gate kernels
+// (gate_kept_planes) takes over.
 //
 // + - x / and comparisons only, in the host class's association order (-ffp-contract=off): the areas are compared BIT FOR BIT
 // with the host twin cape_host_match_map (tests/test_gpu_map_match.py).
@@ -130,32 +138,39 @@ __device__ inline bool projected_area_positive(const double* Tm, const MatchMapP
     return area > 0.0;
 }
 
-} // namespace
-
-// One wavefront per frame, lanes over the map planes (64 at a time): the detected planes of the frame are read once (lane i: kept
-// plane i) and broadcast; bit i of a lane's mask = pair (j, i) passes the gates.  Pass 1 counts the pairs (one atomic per
-// workgroup reserves the frame's slots) and keeps the masks, pass 2 writes the triples in (j, i) order.
-__global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_kernel(MatchMapParams p, int nFrames)
+// Kept plane i of a frame as the intersection and selection kernels see it: its polygon record and the vertex array its
+// vertex_offset counts in.  kShards false: the polygon row and vertex slab of the frame's record; true: the polygon and vertex
+// sections of the slot's shard, through the kept-plane table the shard gate kernel filled (and checked).
+struct DetectedPolygon
 {
-    __shared__ unsigned s_count[kMapGateFrames];
-    __shared__ unsigned long long s_base;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int frameRaw = blockIdx.x * kMapGateFrames + wave;
-    const bool live = frameRaw < nFrames;
-    const int frame = live ? frameRaw : nFrames - 1; // (idle waves of the last workgroup shadow a real frame and store nothing)
-    cape_frame_map_match& out = p.frames[frame];
-    const cape_frame_record& rec = p.records[frame];
-    const cape_polygon* pol = p.polygons + (size_t)frame * CAPE_MAX_PLANES;
-    int seg = -1;
-    bool hostOnly = false;
-    const int nCur = valid_planes(rec, pol, lane, seg, hostOnly);
-    const bool fits = !hostOnly;
-    double cn0 = 0, cn1 = 0, cn2 = 0, cd = 0;
-    if (seg >= 0)
+    const cape_polygon* polygon;
+    const double2* vertices;
+    __device__ __forceinline__ const double2* ring() const { return vertices + polygon->vertex_offset; }
+};
+template <bool kShards> __device__ __forceinline__ DetectedPolygon detected_polygon(const MatchMapParams& p, int frame, int i)
+{
+    if constexpr (kShards)
     {
-        const cape_plane_segment& S = rec.segments[seg];
-        cn0 = S.out_normal[0], cn1 = S.out_normal[1], cn2 = S.out_normal[2], cd = S.d;
+        const uint2 at = p.keptIndex[(size_t)frame * CAPE_MAX_PLANES + i]; // (packed index, shard)
+        const unsigned char* shard = p.shards + (size_t)at.y * p.shardBytes;
+        return {reinterpret_cast<const cape_polygon*>(shard + p.polygonsOffset) + at.x, reinterpret_cast<const double2*>(shard + p.verticesOffset)};
     }
+    else
+    {
+        const int si = p.frames[frame].seg_cur[i];
+        return {p.polygons + (size_t)frame * CAPE_MAX_PLANES + si, p.vertices + (size_t)frame * p.boundaryCapacity};
+    }
+}
+
+// The part the gate kernels share, one wavefront per frame with lane i holding kept plane i (its segment index, normal and d; nCur
+// of them), lanes over the map planes (64 at a time): the detected planes are broadcast; bit i of a lane's mask = pair (j, i) passes
+// the gates.  Pass 1 counts the pairs (one atomic per workgroup reserves the frame's slots) and keeps the masks, pass 2 writes the
+// triples in (j, i) order.  A frame that does not fit (`fits` false) gates nothing and is flagged `flagged | CAPE_MATCH_EXACT_OVERFLOW`.
+__device__ __forceinline__ void gate_kept_planes(const MatchMapParams& p, int frame, bool live, int nCur, bool fits, uint32_t flagged, int seg,
+                                                 double cn0, double cn1, double cn2, double cd, unsigned* s_count, unsigned long long& s_base)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    cape_frame_map_match& out = p.frames[frame];
     const double* T = p.poses + (size_t)frame * 16;
     const uint32_t* skip = p.skip ? p.skip + (size_t)frame * p.skipWords : nullptr;
     // the gated detected planes of map plane j (lane's), as a mask over i
@@ -211,7 +226,7 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_kernel(Matc
     {
         out.n_map = p.nMap;
         out.n_cur = nCur;
-        out.flags = (fits && listed) ? 0u : (uint32_t)CAPE_MATCH_EXACT_OVERFLOW;
+        out.flags = (fits && listed) ? 0u : flagged | (uint32_t)CAPE_MATCH_EXACT_OVERFLOW;
         out.n_matched = 0;
         p.frameRange[frame] = make_uint2((unsigned)(listed ? first : 0ull), listed ? myCount : 0u);
     }
@@ -256,10 +271,114 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_kernel(Matc
     }
 }
 
+} // namespace
+
+// The gate kernel of the record source: the kept planes of the frame's first record (valid_planes), normal and d out of its segments.
+__global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_kernel(MatchMapParams p, int nFrames)
+{
+    __shared__ unsigned s_count[kMapGateFrames];
+    __shared__ unsigned long long s_base;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frameRaw = blockIdx.x * kMapGateFrames + wave;
+    const bool live = frameRaw < nFrames;
+    const int frame = live ? frameRaw : nFrames - 1; // (idle waves of the last workgroup shadow a real frame and store nothing)
+    const cape_frame_record& rec = p.records[frame];
+    const cape_polygon* pol = p.polygons + (size_t)frame * CAPE_MAX_PLANES;
+    int seg = -1;
+    bool hostOnly = false;
+    const int nCur = valid_planes(rec, pol, lane, seg, hostOnly);
+    double cn0 = 0, cn1 = 0, cn2 = 0, cd = 0;
+    if (seg >= 0)
+    {
+        const cape_plane_segment& S = rec.segments[seg];
+        cn0 = S.out_normal[0], cn1 = S.out_normal[1], cn2 = S.out_normal[2], cd = S.d;
+    }
+    gate_kept_planes(p, frame, live, nCur, !hostOnly, 0u, seg, cn0, cn1, cn2, cd, s_count, s_base);
+}
+
+// The gate kernel of the shard source, one wavefront per slot (shard x framesCapacity + k).  The shard's bytes were written by
+// another process: the header is compared with the layout the caller gave (a mismatch flags every slot of the shard
+// CAPE_MATCH_EXACT_BAD_SHARD and nothing else of it is read), and every index read from the shard -- the frame's run of planes, the
+// end of each ring -- is checked against its section before it is used; what the intersection and selection kernels dereference later
+// (keptIndex, the rings of the kept polygons) has passed here.  The frame's packed polygons are walked 64 at a time: a ballot of
+// the kept ones (CAPE_POLY_VALID, >= 3 vertices) plus the running count ranks them, kept plane i's packed index goes to lane i
+// through LDS, and lane i reads its normal, d and segment out of the plane section.
+__global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_shards_kernel(MatchMapParams p, int nSlots)
+{
+    __shared__ unsigned s_count[kMapGateFrames];
+    __shared__ unsigned long long s_base;
+    __shared__ int s_kept[kMapGateFrames][CAPE_MAX_PLANES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slotRaw = blockIdx.x * kMapGateFrames + wave;
+    const bool live = slotRaw < nSlots;
+    const int slot = live ? slotRaw : nSlots - 1; // (idle waves of the last workgroup shadow a real slot and store nothing)
+    const int shardIndex = slot / p.framesCapacity, k = slot - shardIndex * p.framesCapacity;
+    const unsigned char* shard = p.shards + (size_t)shardIndex * p.shardBytes;
+    const cape_packed_header hd = *reinterpret_cast<const cape_packed_header*>(shard);
+    bool bad = hd.magic != CAPE_PACKED_MAGIC || !(hd.flags & CAPE_GATHER_POLYGONS) || hd.frames_capacity != p.framesCapacity ||
+               hd.planes_capacity != p.planesCapacity || hd.cells != p.cells || hd.n_frames < 0 || hd.n_frames > p.framesCapacity;
+    if (!bad)
+        bad = reinterpret_cast<const cape_packed_polygon_header*>(shard + p.polygonHeaderOffset)->vertices_capacity != p.verticesCapacity;
+    // (every condition below is uniform over the wave: header and frame entry are, the per-polygon ones go through a ballot)
+    bool overflow = false; // the frame is left to the host: more than 64 kept planes, a polygon the host class builds, dropped planes / rings
+    int kept = 0;
+    s_kept[wave][lane] = -1;
+    if (!bad && k < hd.n_frames)
+    {
+        const cape_packed_frame fr = reinterpret_cast<const cape_packed_frame*>(shard + p.framesOffset)[k];
+        // planes beyond the section: the shard dropped them when its header says so, otherwise the entry is not a frame of this shard
+        const bool dropped = (long long)fr.plane_offset + fr.n_planes > (long long)p.planesCapacity;
+        if (fr.plane_offset < 0 || fr.n_planes < 0 || (dropped && !(hd.overflow & CAPE_PACKED_PLANES_DROPPED)))
+            bad = true;
+        else
+        {
+            overflow = dropped;
+            const int first = fr.plane_offset;
+            const int listed = !dropped ? fr.n_planes : (first < p.planesCapacity ? p.planesCapacity - first : 0);
+            const cape_polygon* polygons = reinterpret_cast<const cape_polygon*>(shard + p.polygonsOffset);
+            for (int b = 0; b < listed; b += 64)
+            {
+                const bool has = b + lane < listed;
+                uint32_t flags = 0u, count = 0u, offset = 0u;
+                if (has)
+                {
+                    const cape_polygon& g = polygons[first + b + lane];
+                    flags = g.flags, count = g.vertex_count, offset = g.vertex_offset;
+                }
+                const bool away = offset == UINT32_MAX; // the ring did not travel (CAPE_PACKED_VERTICES_DROPPED): kept or not cannot be told
+                const bool outside = !away && count > 0u && (unsigned long long)offset + count > (unsigned long long)p.verticesCapacity;
+                const bool ok = (flags & CAPE_POLY_VALID) != 0u && count >= 3u;
+                bad = bad || __any(outside);
+                overflow = overflow || __any(away || (flags & CAPE_POLY_OVERFLOW) != 0u);
+                const unsigned long long m = __ballot(ok);
+                const int rank = kept + __popcll(m & ((1ull << lane) - 1ull));
+                if (ok && rank < CAPE_MAX_PLANES)
+                    s_kept[wave][rank] = first + b + lane;
+                kept += __popcll(m);
+            }
+            overflow = overflow || kept > CAPE_MAX_PLANES;
+        }
+    }
+    CAPE_MP_SYNC(); // (the table is read by other lanes of the wave than wrote it)
+    const int nCur = bad ? 0 : (kept < CAPE_MAX_PLANES ? kept : CAPE_MAX_PLANES);
+    const int mine = lane < nCur ? s_kept[wave][lane] : -1;
+    if (live)
+        p.keptIndex[(size_t)slot * CAPE_MAX_PLANES + lane] = make_uint2((unsigned)mine, (unsigned)shardIndex);
+    int seg = -1;
+    double cn0 = 0, cn1 = 0, cn2 = 0, cd = 0;
+    if (mine >= 0)
+    {
+        const cape_packed_plane& P = reinterpret_cast<const cape_packed_plane*>(shard + p.planesOffset)[mine];
+        cn0 = P.normal[0], cn1 = P.normal[1], cn2 = P.normal[2], cd = P.d;
+        seg = (int)P.segment;
+    }
+    gate_kept_planes(p, slot, live, nCur, !bad && !overflow, bad ? (uint32_t)CAPE_MATCH_EXACT_BAD_SHARD : 0u, seg, cn0, cn1, cn2, cd, s_count, s_base);
+}
+
 // Persistent waves over the work list (tier 0) or a tier's list of indices into it (tiers 1..3).  A triple beyond this tier's
 // capacities moves to the next tier's list when that one is larger in the resource that ran out; otherwise its area stays a NaN
 // that names the resource.
-template <int TIER>
+template <int TIER, bool kShards>
 __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inter_kernel(MatchMapParams p, int ldsPerWave)
 {
     using T = Tier<TIER>;
@@ -306,8 +425,8 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inte
         if (e == kNoEntry)
             continue;
         const int frame = (int)(e >> 32), j = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
-        const int si = p.frames[frame].seg_cur[i];
-        const cape_polygon& PS = p.polygons[(size_t)frame * CAPE_MAX_PLANES + si]; // detected polygon
+        const DetectedPolygon D = detected_polygon<kShards>(p, frame, i);
+        const cape_polygon& PS = *D.polygon; // detected polygon
         const cape_map_plane& M = p.mapPlanes[j];
         const int na = (int)PS.vertex_count, nRings = (int)M.ring_count;
         int nbMax = 0;
@@ -321,7 +440,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inte
             result = nan_code(kNanRing);
         else
         {
-            const double2* vertsC = p.vertices + (size_t)frame * p.boundaryCapacity + PS.vertex_offset;
+            const double2* vertsC = D.ring();
             for (int v = tid; v < na; v += kStride)
                 L.ringA[v] = vertsC[v];
             // to_camera_space (polygon_coordinates.cpp:135-165): the centre through the transform, the axes through its rotation,
@@ -422,7 +541,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inte
 
 // One wavefront per frame: the map planes in order, each with the contiguous run of its gated pairs (one run fits the wave: at
 // most 64 kept planes), lanes over the run.
-__global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_kernel(MatchMapParams p, int nFrames)
+template <bool kShards> __global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_kernel(MatchMapParams p, int nFrames)
 {
     const int lane = threadIdx.x & 63;
     const int frame = blockIdx.x * kMapSelectFrames + (threadIdx.x >> 6);
@@ -432,8 +551,7 @@ __global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_kernel(
     if (out.flags & CAPE_MATCH_EXACT_OVERFLOW)
         return; // nothing was intersected
     const int nc = out.n_cur;
-    const int seg = lane < nc ? out.seg_cur[lane] : -1;
-    const double myArea = lane < nc ? p.polygons[(size_t)frame * CAPE_MAX_PLANES + seg].area : 0.0; // detectedPolygon.get_area()
+    const double myArea = lane < nc ? detected_polygon<kShards>(p, frame, lane).polygon->area : 0.0; // detectedPolygon.get_area()
     const uint2 range = p.frameRange[frame];
     const unsigned begin = range.x, end = range.x + range.y;
     // a pair beyond the intersection kernel's capacities: no match is reported for the frame
@@ -484,11 +602,14 @@ __global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_kernel(
     out.map_of[lane] = myMapOf;
 }
 
-hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream)
+namespace {
+
+template <bool kShards> hipError_t launch_match_map_from(const MatchMapParams& p, int nFrames, hipStream_t stream)
 {
     if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(cape_map_gate_kernel, dim3((nFrames + kMapGateFrames - 1) / kMapGateFrames), dim3(64 * kMapGateFrames), 0, stream, p, nFrames);
+    hipLaunchKernelGGL(kShards ? cape_map_gate_shards_kernel : cape_map_gate_kernel, dim3((nFrames + kMapGateFrames - 1) / kMapGateFrames),
+                       dim3(64 * kMapGateFrames), 0, stream, p, nFrames);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
     // persistent grids: as many workgroups as the chip holds at once (the list's length is only known on the device)
@@ -497,18 +618,26 @@ hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t st
         hipLaunchKernelGGL(kernel, dim3(cus * groupsPerCu), dim3(64 * wavesPerGroup), (size_t)lds * (coop ? 1 : wavesPerGroup), stream, p, lds);
         return hipGetLastError();
     };
-    if (const hipError_t e = launch(cape_map_inter_kernel<0>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch(cape_map_inter_kernel<0, kShards>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_inter_kernel<1>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch(cape_map_inter_kernel<1, kShards>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_inter_kernel<2>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch(cape_map_inter_kernel<2, kShards>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
         return e;
     // (a device without the LDS for the largest tier leaves its triples NaN: their frames are flagged)
     if (tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes)
-        if (const hipError_t e = launch(cape_map_inter_kernel<3>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu); e != hipSuccess)
+        if (const hipError_t e = launch(cape_map_inter_kernel<3, kShards>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu); e != hipSuccess)
             return e;
-    hipLaunchKernelGGL(cape_map_select_kernel, dim3((nFrames + kMapSelectFrames - 1) / kMapSelectFrames), dim3(64 * kMapSelectFrames), 0, stream, p, nFrames);
+    hipLaunchKernelGGL(cape_map_select_kernel<kShards>, dim3((nFrames + kMapSelectFrames - 1) / kMapSelectFrames), dim3(64 * kMapSelectFrames), 0, stream, p, nFrames);
     return hipGetLastError();
+}
+
+} // namespace
+
+// nFrames: frames of the handle's batch, or slots when p.shards is set (cape_match_map_shards)
+hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream)
+{
+    return p.shards ? launch_match_map_from<true>(p, nFrames, stream) : launch_match_map_from<false>(p, nFrames, stream);
 }
 
 } // namespace cape

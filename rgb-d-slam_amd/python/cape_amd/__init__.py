@@ -144,6 +144,8 @@ MATCH_EXACT_DTYPE = np.dtype([
     ("seg_cur", "<i4", MATCH_MAX_PLANES), ("flags", "<u4"), ("pad", "<u4"),
     ("inter_area", "<f8", (MATCH_MAX_PLANES, MATCH_MAX_PLANES))], align=True)
 MATCH_EXACT_OVERFLOW = 1
+MATCH_EXACT_HOST = 2
+MATCH_EXACT_BAD_SHARD = 8  # match_map_shards only, next to MATCH_EXACT_OVERFLOW (4 is the input flag MATCH_MAP_AREAS)
 assert MATCH_EXACT_DTYPE.itemsize == 8 + 3 * 64 + 8 + 8 * 256
 
 # N2 against a persistent map (cape_map_upload / cape_match_map)
@@ -389,7 +391,7 @@ EXPORTED_SYMBOLS = [
     "cape_host_unregister", "cape_copy_cell_stats", "cape_enable_timing", "cape_get_timings",
     "cape_reset_timings", "cape_match_consecutive", "cape_device_matches", "cape_copy_matches",
     "cape_match_polygons", "cape_match_polygons_pose", "cape_copy_polygon_matches",
-    "cape_map_upload", "cape_match_map", "cape_copy_map_matches",
+    "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_shards", "cape_copy_shard_map_matches",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
@@ -464,6 +466,9 @@ def load_library():
     L.cape_map_upload.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64]
     L.cape_match_map.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, vp]
     L.cape_copy_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.cape_match_map_shards.argtypes = [vp, vp, C.c_int32, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout), vp, vp,
+                                        C.c_uint32, vp]
+    L.cape_copy_shard_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -756,6 +761,36 @@ class Extractor:
         inter = np.zeros((n_frames, max(n_map, 1), CAPE_MAX_PLANES)) if areas else None
         _check(self.L, self.L.cape_copy_map_matches(self.h, n_frames, frames.ctypes.data_as(C.c_void_p), match.ctypes.data_as(C.c_void_p),
                                                     None if inter is None else inter.ctypes.data_as(C.c_void_p)), "cape_copy_map_matches")
+        out = (frames, match[:, :n_map])
+        return out + (inter[:, :n_map],) if areas else out
+
+    # ---- the same against gathered shards in device memory (the map owner's side of the multi-GPU gather) ----
+    def match_map_shards(self, ptr, n_shards, layout, world_to_camera=None, skip=None, flags=0, stream=0):
+        """cape_match_map_shards: match_map for the frames of n_shards packed shards at device address `ptr` (the receive buffer of
+        gather / gather_root, or what pack returns with n_shards=1).  layout: the dict gather_configure(..., polygons=True) returned on
+        the PRODUCERS; this handle needs only upload_map.  world_to_camera (n_slots x 4 x 4) and skip (n_slots x ceil(n_map / 32)) are
+        indexed by slot = dist.slot_of(shard, k, layout), n_slots = n_shards x frames_capacity."""
+        n_slots = n_shards * int(layout["frames_capacity"])
+        lay = cape_gather_layout(**{f: int(layout.get(f, 0)) for f, _ in cape_gather_layout._fields_})
+        pl = cape_gather_polygon_layout(**{f: int(layout.get(f, 0)) for f, _ in cape_gather_polygon_layout._fields_})
+        T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(n_slots, 16)
+        S = None if skip is None else np.ascontiguousarray(skip, np.uint32).reshape(n_slots, -1)
+        _check(self.L, self.L.cape_match_map_shards(self.h, C.c_void_p(ptr), n_shards, C.byref(lay), C.byref(pl),
+                                                    None if T is None else T.ctypes.data_as(C.c_void_p),
+                                                    None if S is None else S.ctypes.data_as(C.c_void_p), flags, C.c_void_p(stream)),
+               "cape_match_map_shards")
+        self.shard_matched_map_size = self.map_size  # what cape_copy_shard_map_matches writes: the map of THIS call
+
+    def shard_map_matches(self, n_slots, areas=False):
+        """map_matches for the last match_map_shards: (frames[n_slots], match[n_slots, n_map]) + inter_area[n_slots, n_map, 64] with
+        areas=True, indexed by slot."""
+        n_map = getattr(self, "shard_matched_map_size", 0)
+        frames = np.zeros(n_slots, FRAME_MAP_MATCH_DTYPE)
+        match = np.zeros((n_slots, max(n_map, 1)), np.int32)
+        inter = np.zeros((n_slots, max(n_map, 1), CAPE_MAX_PLANES)) if areas else None
+        _check(self.L, self.L.cape_copy_shard_map_matches(self.h, n_slots, frames.ctypes.data_as(C.c_void_p), match.ctypes.data_as(C.c_void_p),
+                                                          None if inter is None else inter.ctypes.data_as(C.c_void_p)),
+               "cape_copy_shard_map_matches")
         out = (frames, match[:, :n_map])
         return out + (inter[:, :n_map],) if areas else out
 

@@ -18,6 +18,22 @@ def largest_shard(n_frames, world):
     return -(-n_frames // world)
 
 
+def slot_of(shard, k, layout):
+    """The slot of frame k of shard `shard` (rank order) in the arrays of Extractor.match_map_shards / shard_map_matches: a shard owns
+    frames_capacity slots whatever it holds, because how many frames it holds is known on the device only."""
+    F = int(layout["frames_capacity"])
+    if shard < 0 or not 0 <= k < F:
+        raise ValueError(f"frame {k} of shard {shard}: outside [0, {F}) frames per shard")
+    return shard * F + k
+
+
+def shard_of(slot, layout):
+    """(shard, k) of a slot: the inverse of slot_of."""
+    if slot < 0:
+        raise ValueError("negative slot")
+    return divmod(slot, int(layout["frames_capacity"]))
+
+
 def packed_layout(frames_capacity, cells, planes_per_frame=16, cylinders_per_frame=8, labels=False, polygons=False, vertices_per_frame=0):
     """Host restatement of cape_gather_configure's layout arithmetic (sections on 16-byte boundaries).  polygons=True: that of
     cape_gather_configure_polygons -- the polygon sections behind everything else, their fields added to the dict."""
