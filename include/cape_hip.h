@@ -607,6 +607,37 @@ int cape_match_map_shards(cape_handle h, const void* shards_dev, int32_t n_shard
  * CAPE_ERR_CAPACITY: more slots than that call covered. */
 int cape_copy_shard_map_matches(cape_handle h, int32_t n_slots, cape_frame_map_match* frames, int32_t* match, double* inter_area);
 
+/* The skip words of cape_match_map / cape_match_map_shards, decided on the device: bit j of frame f = map plane j is not visited,
+ * i.e. bit j of `moving` is set or MapPlane::is_visible(world_to_camera[f]) is false (map_primitive.cpp:186-189) -- the first
+ * statement of the get_matches loop (feature_map.hpp:658, :683).  n_frames counts frames or, for cape_match_map_shards, slots; the
+ * call uses the map of cape_map_upload and the handle's width, height, fx, fy, cx, cy and nothing else of the handle (no cape_extract
+ * is needed, max_batch does not bound n_frames).  world_to_camera: n_frames x 16 doubles in HOST memory, read before the call
+ * returns, NULL = identity; moving: ceil(n_map / 32) words in HOST memory, one bit per MAP PLANE (the caller's is_moving()), NULL =
+ * none.  Per pair: the map polygon goes through to_camera_space as in cape_match_map, every vertex (a, b) of its OUTER ring (holes
+ * are not read, as in to_screen_space) becomes the camera point centre + a xAxis + b yAxis and the screen point
+ * u = (1 / Z) (fx X + cx Z), v = (1 / Z) (fy Y + cy Z); the plane is visible when the ring intersection of the matchers gives
+ * area(screen ring n rectangle (1, 1) .. (W-1, H-1)) > 0, both rings oriented like the host class orients an outer ring.  Stated
+ * differences to the reference: a ring with a NaN or INFINITE screen coordinate is not visible (the reference drops NaN only and hands
+ * Boost an invalid polygon on infinity); a ring with vertices behind the camera goes through the same statements without clipping
+ * (the reference has a TODO there) and the answer is cape_host_map_visibility's (host/cape_host_map.h), not Boost's; a pair beyond
+ * the intersection kernel's capacities is not decided and counts as VISIBLE.  The words are the host twin's bit for bit.
+ * They live in a buffer of the handle's own that no other call writes; a cape_map_upload discards them (and waits for a call in
+ * flight).  Asynchronous on `stream`.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, n_frames < 1, no map uploaded; CAPE_ERR_CAPACITY:
+ * n_frames x n_map work-list entries would exceed 1 GiB.  An empty map succeeds and writes nothing. */
+int cape_map_visibility(cape_handle h, int32_t n_frames, const double* world_to_camera, const uint32_t* moving, void* stream);
+/* Synchronous copy of the last cape_map_visibility: skip_out (n_frames x ceil(n_map / 32) words; the bits beyond n_map in a frame's
+ * last word are 0) and n_undecided (pairs of that call that exceeded the capacities and count as visible); either may be NULL.
+ * CAPE_ERR_CAPACITY: more frames than that call covered, or none since the last cape_map_upload. */
+int cape_copy_map_visibility(cape_handle h, int32_t n_frames, uint32_t* skip_out, int64_t* n_undecided);
+enum
+{
+    CAPE_MATCH_MAP_DEVICE_SKIP = 1u << 4 /* cape_match_map / cape_match_map_shards: the skip words are those of the last
+                                            cape_map_visibility (frame or slot f of this call = frame f of that one; the poses are
+                                            still passed to this call).  `skip` must be NULL (CAPE_ERR_INVALID_ARGUMENT);
+                                            CAPE_ERR_CAPACITY if no cape_map_visibility has run since the last cape_map_upload or it
+                                            covered fewer frames / slots than this call */
+};
+
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
  * the `stream` argument of the calls below; destroy it before the handle. */

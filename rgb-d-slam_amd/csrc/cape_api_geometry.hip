@@ -125,6 +125,37 @@ void fill_poses(void* stage, int n, const double* world_to_camera, size_t poseBy
     if (skipBytes)
         std::memcpy(static_cast<unsigned char*>(stage) + poseBytes, skip, skipBytes);
 }
+// the work buffers of cape_map_visibility, one allocation: counters, the work list, the tier lists
+struct VisibilityWorkLayout
+{
+    size_t counts, work, tiers, total;
+};
+VisibilityWorkLayout visibility_work_layout(size_t cap)
+{
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    VisibilityWorkLayout l;
+    l.counts = 0;
+    l.work = up(16 * sizeof(unsigned));
+    l.tiers = l.work + up(cap * sizeof(unsigned long long));
+    l.total = l.tiers + up(3 * cap * sizeof(unsigned));
+    return l;
+}
+constexpr size_t kVisibilityWorkBudget = (size_t)1 << 30; // bytes of the visibility work list at most
+// CAPE_MATCH_MAP_DEVICE_SKIP: the skip words of the last cape_map_visibility for a match call over n frames (or slots), or the
+// reason there are none
+int device_skip_words(const cape_handle_s* h, int n, const uint32_t* skip, const uint32_t** words)
+{
+    const auto& V = h->visibility;
+    if (skip)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_MATCH_MAP_DEVICE_SKIP takes the skip words of cape_map_visibility: skip must be NULL");
+    if (V.frames <= 0 || V.n != h->map.n)
+        return fail(CAPE_ERR_CAPACITY, "CAPE_MATCH_MAP_DEVICE_SKIP: no cape_map_visibility has run since the last cape_map_upload");
+    if (n > V.frames)
+        return fail(CAPE_ERR_CAPACITY, "CAPE_MATCH_MAP_DEVICE_SKIP: the last cape_map_visibility covered fewer frames than this call");
+    *words = V.skip;
+    return CAPE_OK;
+}
+constexpr uint32_t kMatchMapFlags = CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS | CAPE_MATCH_MAP_DEVICE_SKIP;
 bool unit_norm(const double* v) // double_equal(norm, 1) as to_camera_space requires (polygon_coordinates.cpp:144-151)
 {
     return std::abs(std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) - 1.0) <= std::numeric_limits<double>::epsilon();
@@ -395,6 +426,7 @@ int cape_map_upload(cape_handle h, const cape_map_plane* planes, int32_t n_plane
     CAPE_HIP_TRY(drain_handle(h)); // a cape_match_map in flight still reads the old map
     auto& map = h->map;
     map.n = -1; // (no map until the copies are through)
+    h->visibility.frames = 0; // (the words of the old map)
     const auto drained = [] { return hipSuccess; };
     CAPE_HIP_TRY(map.planes.grow(P.size(), drained));
     CAPE_HIP_TRY(map.rings.grow(R.size(), drained));
@@ -418,13 +450,17 @@ int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camer
         return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
     if (map.n < 0)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
-    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS))
+    if (flags & ~kMatchMapFlags)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
     const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0;
     const size_t areaDoubles = (size_t)n_frames * map.n * CAPE_MAX_PLANES;
     if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
         return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer frames per call, or no CAPE_MATCH_MAP_AREAS)");
     map.matchFrames = 0;
+    const uint32_t* deviceSkip = nullptr;
+    if (flags & CAPE_MATCH_MAP_DEVICE_SKIP)
+        if (const int rc = device_skip_words(h, n_frames, skip, &deviceSkip); rc != CAPE_OK)
+            return rc;
     if (n_frames == 0)
         return CAPE_OK;
     CAPE_ON_DEVICE(h);
@@ -457,7 +493,7 @@ int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camer
     p.boundaryCapacity = h->boundaryCap;
     bind_map_call(p, h, map.work, lay, cap);
     p.poses = reinterpret_cast<const double*>(map.poses.get());
-    p.skip = skipBytes ? reinterpret_cast<const uint32_t*>(map.poses + poseBytes) : nullptr;
+    p.skip = deviceSkip ? deviceSkip : skipBytes ? reinterpret_cast<const uint32_t*>(map.poses + poseBytes) : nullptr;
     p.frames = map.frames;
     p.match = map.match;
     p.areas = keepAreas ? map.areas.get() : nullptr;
@@ -497,7 +533,7 @@ int cape_match_map_shards(cape_handle h, const void* shards_dev, int32_t n_shard
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, shards or layout, or fewer than one shard");
     if (h->map.n < 0)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
-    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS))
+    if (flags & ~kMatchMapFlags)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
     // the sections the kernels read lie inside one shard, on 16-byte boundaries and one behind the other in the order the pack writes
     // them (the shards follow each other at bytes_per_rank)
@@ -528,6 +564,10 @@ int cape_match_map_shards(cape_handle h, const void* shards_dev, int32_t n_shard
     const size_t areaDoubles = (size_t)nSlots * nMap * CAPE_MAX_PLANES;
     if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
         return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer shards per call, or no CAPE_MATCH_MAP_AREAS)");
+    const uint32_t* deviceSkip = nullptr;
+    if (flags & CAPE_MATCH_MAP_DEVICE_SKIP)
+        if (const int rc = device_skip_words(h, nSlots, skip, &deviceSkip); rc != CAPE_OK)
+            return rc;
     CAPE_ON_DEVICE(h);
     S.slots = 0; // (the buffers of the last call's results may be replaced below)
     const int skipWords = (nMap + 31) / 32;
@@ -558,7 +598,7 @@ int cape_match_map_shards(cape_handle h, const void* shards_dev, int32_t n_shard
     cape::MatchMapParams p{};
     bind_map_call(p, h, S.work, lay, cap);
     p.poses = reinterpret_cast<const double*>(S.poses.get());
-    p.skip = skipBytes ? reinterpret_cast<const uint32_t*>(S.poses + poseBytes) : nullptr;
+    p.skip = deviceSkip ? deviceSkip : skipBytes ? reinterpret_cast<const uint32_t*>(S.poses + poseBytes) : nullptr;
     p.frames = S.frames;
     p.match = S.match;
     p.areas = keepAreas ? S.areas.get() : nullptr;
@@ -599,6 +639,96 @@ int cape_copy_shard_map_matches(cape_handle h, int32_t n_slots, cape_frame_map_m
     CAPE_HIP_TRY(copy_out(frames, S.frames, 0, (size_t)n_slots));
     CAPE_HIP_TRY(copy_out(match, S.match, 0, n));
     CAPE_HIP_TRY(copy_out(inter_area, S.areas, 0, n * CAPE_MAX_PLANES));
+    return CAPE_OK;
+}
+
+int cape_map_visibility(cape_handle h, int32_t n_frames, const double* world_to_camera, const uint32_t* moving, void* stream_)
+{
+    if (!h || n_frames < 1)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or fewer than one frame");
+    if (h->map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    auto& V = h->visibility;
+    const int nMap = h->map.n;
+    V.frames = 0;
+    const size_t cap = (size_t)n_frames * (size_t)nMap;
+    if (cap * sizeof(unsigned long long) > kVisibilityWorkBudget)
+        return fail(CAPE_ERR_CAPACITY, "the work list of this call (n_frames x n_map entries) would exceed 1 GiB (fewer frames per call)");
+    if (nMap == 0)
+    {
+        // an empty map: no words
+        V.frames = n_frames;
+        V.n = 0;
+        return CAPE_OK;
+    }
+    CAPE_ON_DEVICE(h);
+    const int skipWords = (nMap + 31) / 32;
+    const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double);
+    const size_t movingBytes = moving ? (size_t)skipWords * sizeof(uint32_t) : 0;
+    const VisibilityWorkLayout lay = visibility_work_layout(cap);
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them, or a match call reading the words
+    if (V.poses.size() < poseBytes + movingBytes)
+    {
+        // (the pinned twin has the size of its device buffer: both are replaced)
+        CAPE_HIP_TRY(drain());
+        V.posesTwin = cape::abi::PinnedTwin{};
+        CAPE_HIP_TRY(V.poses.alloc(poseBytes + (size_t)(CAPE_MAP_MAX_PLANES / 32) * sizeof(uint32_t)));
+    }
+    CAPE_HIP_TRY(V.skip.grow((size_t)n_frames * (CAPE_MAP_MAX_PLANES / 32), drain));
+    CAPE_HIP_TRY(V.work.grow(lay.total, drain));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    CAPE_HIP_TRY(V.posesTwin.upload(V.poses, poseBytes + movingBytes, V.poses.size(), stream,
+                                    [&](void* stage) { fill_poses(stage, n_frames, world_to_camera, poseBytes, moving, movingBytes); }));
+    cape::MapVisibilityParams p{};
+    p.mapPlanes = h->map.planes;
+    p.mapRings = h->map.rings;
+    p.mapVertices = reinterpret_cast<const double2*>(h->map.vertices.get());
+    p.nMap = nMap;
+    p.skipWords = skipWords;
+    p.poses = reinterpret_cast<const double*>(V.poses.get());
+    p.moving = movingBytes ? reinterpret_cast<const uint32_t*>(V.poses + poseBytes) : nullptr;
+    p.skip = V.skip;
+    p.counts = reinterpret_cast<unsigned*>(V.work + lay.counts);
+    p.work = reinterpret_cast<unsigned long long*>(V.work + lay.work);
+    p.tierLists = reinterpret_cast<unsigned*>(V.work + lay.tiers);
+    p.workCapacity = cap;
+    p.computeUnits = h->computeUnits;
+    p.ldsLimitBytes = h->ldsLimit;
+    p.width = h->cfg.width;
+    p.height = h->cfg.height;
+    p.fx = h->cfg.fx;
+    p.fy = h->cfg.fy;
+    p.cx = h->cfg.cx;
+    p.cy = h->cfg.cy;
+    CAPE_HIP_TRY(cape::launch_map_visibility(p, n_frames, stream));
+    V.frames = n_frames;
+    V.n = nMap;
+    return CAPE_OK;
+}
+
+int cape_copy_map_visibility(cape_handle h, int32_t n_frames, uint32_t* skip_out, int64_t* n_undecided)
+{
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    const auto& V = h->visibility;
+    if (n_frames > V.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_visibility on the current map");
+    if (n_undecided)
+        *n_undecided = 0;
+    if (V.frames == 0 || V.n == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(copy_out(skip_out, V.skip, 0, (size_t)n_frames * ((V.n + 31) / 32)));
+    if (n_undecided)
+    {
+        unsigned long long count = 0;
+        CAPE_HIP_TRY(hipMemcpy(&count, V.work.get() + 8 * sizeof(unsigned), sizeof(count), hipMemcpyDeviceToHost));
+        *n_undecided = (int64_t)count;
+    }
     return CAPE_OK;
 }
 

@@ -29,6 +29,7 @@ hipError_t launch_pack(const PackParams& p, hipStream_t stream);
 hipError_t launch_polygons(const PolygonParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_polygons(const MatchPolygonParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -358,6 +359,19 @@ struct cape_handle_s
         int matchN = 0;                      // map planes of that call
         bool matchAreas = false;             // ... and whether it kept the dense table
     } shardMatch;
+
+    // cape_map_visibility: the skip words of the uploaded map seen from the poses of the last call, for cape_match_map[_shards] with
+    // CAPE_MATCH_MAP_DEVICE_SKIP.  Buffers of its own, sized by the call's frames (or slots) and grown on demand behind drain_handle:
+    // no other call writes them
+    struct Visibility
+    {
+        Buffer<unsigned char> poses; // the poses of the call (frames x 16 doubles), then the moving words
+        cape::abi::PinnedTwin posesTwin;
+        Buffer<uint32_t> skip;       // frames x ceil(n / 32)
+        Buffer<unsigned char> work;  // counters, work list, tier lists (visibility_work_layout)
+        int frames = 0;              // frames of the last cape_map_visibility on the current map (0: none since cape_map_upload)
+        int n = 0;                   // map planes of that call
+    } visibility;
 
     // Per-handle scratch (depth staging, rectify keys, hand-over feedback, result buffers) is reused from call to call
     // without per-buffer events: ONE stream is in flight per handle.  Every enqueueing call leaves a handle-owned event

@@ -254,6 +254,27 @@ struct MatchMapParams
                                 // shard) -- one load tells the later kernels where the polygon lies, without dividing the slot by framesCapacity
 };
 
+// cape_map_visibility (cape_map_visibility.hip): bit j of frame f = map plane j is moving or not visible from the frame's camera
+struct MapVisibilityParams
+{
+    // the map (cape_map_upload; rings already re-oriented)
+    const cape_map_plane* mapPlanes;
+    const cape_map_ring* mapRings;
+    const double2* mapVertices;
+    int nMap, skipWords;      // skipWords = ceil(nMap / 32)
+    const double* poses;      // frames x 16
+    const uint32_t* moving;   // skipWords words, one bit per map plane (null = none)
+    uint32_t* skip;           // frames x skipWords: the result
+    unsigned long long* work; // workCapacity = frames x nMap entries (frame << 32) | j, per frame in j order
+    unsigned* tierLists;      // 3 x workCapacity: indices into `work` handed to tiers 1..3
+    unsigned* counts;         // 16 words, [0..7] as MatchMapParams::counts, [8..9] the undecided pairs (64-bit)
+    size_t workCapacity;
+    int computeUnits;
+    int ldsLimitBytes;
+    int lastTier;             // the largest tier that runs on this device (set by the launcher)
+    double width, height, fx, fy, cx, cy;
+};
+
 // multi-GPU gather: device-side packing of the ragged primitive lists (cape_gather.hip)
 struct PackParams
 {

@@ -1,0 +1,292 @@
+// The first statement of the Feature_Map::get_matches loop (reference src/map_management/feature_map.hpp:658, :683),
+// `if (mapFeature.is_moving() or not mapFeature.is_visible(worldToCamera)) continue;`, for every (frame, map plane) pair: the skip
+// words cape_match_map / cape_match_map_shards read.  MapPlane::is_visible (map_primitive.cpp:186-189) sends the map polygon through
+// to_camera_space (polygon_coordinates.cpp:135-162), every vertex of its OUTER ring to the screen (get_screen_points :77-100 over
+// CameraCoordinate::to_screen_coordinates, point_coordinates.cpp:201-210; holes are not read) and intersects that ring with the
+// screen rectangle (is_visible_in_screen_space :120-127, get_static_screen_boundary_polygon utils/polygon.cpp:24-46): visible <=>
+// the intersection is not empty, here rings_inter_area(screen ring, rectangle) > 0 with the ring intersection of cape_ring_area.h.
+//
+//   cape_map_classify_kernel    : one wavefront per frame, lanes over map planes (64 at a time): each lane walks the outer ring of
+//        its plane once -- are all screen coordinates finite, and their bounding box.  A ring with a non-finite coordinate is not
+//        visible, one whose box misses the rectangle neither (see box_misses_screen); every other plane that is not moving goes to
+//        the work list, per frame in j order.  Every bit j < n_map of the frame's words is set here; the next kernel clears the bits
+//        of the visible planes.
+//   cape_map_visible_kernel<TIER>: persistent waves over the work list (tier 0) or a tier's list of indices into it (tiers 1..3),
+//        as cape_map_inter_kernel: the screen ring as ring A, the rectangle as ring B, each oriented like the host class orients an
+//        outer ring.  Area > 0: the bit of the pair is cleared.  A pair beyond every tier's capacities is not decided: it counts as
+//        visible (a plane visited in vain costs work, a plane skipped in vain loses a match) and is counted.
+//
+// + - x / and comparisons only, in the order of the host twin cape_host_map_visibility (-ffp-contract=off): the words are compared
+// BIT FOR BIT with it (tests/test_gpu_map_visibility.py).  The twin takes no shortcut.
+#include <hip/hip_runtime.h>
+
+#include "cape_internal.h"
+#include "cape_map_camera.h"
+#include "cape_ring_area.h"
+#include "cape_wave.h"
+
+namespace cape {
+
+namespace {
+
+constexpr int kVisFrames = 4; // frames (waves) of a classify workgroup
+
+// A ring vertex (a, b) of the camera-space polygon on the screen: get_point_from_plane_coordinates (polygon.cpp:146-166:
+// `center + point.x() * xAxis + point.y() * yAxis`, i.e. (c + a x) + b y), then to_screen_coordinates (point_coordinates.cpp:203:
+// `1.0 / z() * transform_camera_to_screen(...)`: the reciprocal first, then the product); the handle has no skew
+__device__ __forceinline__ double2 screen_vertex(const MapVisibilityParams& p, const CameraFrame& F, double2 q)
+{
+    const double X = F.nc[0] + q.x * F.nx[0] + q.y * F.ny[0], Y = F.nc[1] + q.x * F.nx[1] + q.y * F.ny[1], Z = F.nc[2] + q.x * F.nx[2] + q.y * F.ny[2];
+    const double inv = 1.0 / Z;
+    return make_double2(inv * (p.fx * X + p.cx * Z), inv * (p.fy * Y + p.cy * Z));
+}
+
+// The one shortcut: the bounding box [minU, maxU] x [minV, maxV] of a screen ring A with finite coordinates lies beside the open
+// rectangle B = (1, W-1) x (1, H-1).  rings_inter_area(A, B) is then exactly 0, because it only adds a term for a slab [x0, x1],
+// x0 < x1, that an edge of A and an edge of B both span (`a.x <= x0 && b.x >= x1`) and in which their height intervals overlap:
+//  * maxU <= 1: an edge of A spans only slabs with x1 <= maxU <= 1, the two non-vertical edges of B (x from 1 to W-1) only slabs
+//    with x0 >= 1 -- no slab has x0 < x1 with both.  minU >= W-1 likewise (x0 >= W-1 against x1 <= W-1).  Comparisons of
+//    coordinates only: no rounding enters.
+//  * maxV <= 1: in a shared slab the heights of B are exactly 1 and H-1 (horizontal edges: 1 + 0 * t), those of A are
+//    y_at = a.y + (b.y - a.y) * t with t in [0, 1] (a.x <= xm <= b.x and rounding is monotone), which rounding can lift above
+//    max(a.y, b.y) by at most 4 x 2^-53 x max(|a.y|, |b.y|).  The test therefore asks for that slack, generously (2^-50): then
+//    every height of A is <= 1, so min(hiA, H-1) <= 1 <= max(loA, 1) and `hi <= lo` drops the pair of intervals.  minV >= H-1
+//    likewise.  Coordinates beyond 2^1000 (xm or b.y - a.y could overflow) take the full computation.
+// A box the test lets through costs an intersection and nothing else.
+__device__ __forceinline__ bool box_misses_screen(const MapVisibilityParams& p, double minU, double maxU, double minV, double maxV)
+{
+    const double right = p.width - 1.0, top = p.height - 1.0;
+    if (maxU <= 1.0 || minU >= right)
+        return true;
+    const double magU = fmax(fabs(minU), fabs(maxU)), magV = fmax(fabs(minV), fabs(maxV));
+    if (!(fmax(magU, magV) <= 0x1p1000))
+        return false;
+    const double slack = magV * 0x1p-50;
+    return maxV + slack <= 1.0 || minV - slack >= top;
+}
+
+// map plane j from the frame's camera, one lane: false = certainly not visible (a non-finite screen coordinate, or the shortcut)
+__device__ inline bool may_be_visible(const double* Tm, const MapVisibilityParams& p, int j)
+{
+    const cape_map_plane& M = p.mapPlanes[j];
+    const CameraFrame F = camera_frame(Tm, M);
+    const cape_map_ring R = p.mapRings[M.ring_first];
+    const double2* src = p.mapVertices + R.vertex_offset;
+    const int n = (int)R.vertex_count;
+    bool finite = true;
+    double minU = __builtin_inf(), maxU = -__builtin_inf(), minV = __builtin_inf(), maxV = -__builtin_inf();
+    for (int i = 0; i < n; ++i)
+    {
+        const double2 s = screen_vertex(p, F, to_camera_vertex(Tm, F, src[i]));
+        finite = finite && isfinite(s.x) && isfinite(s.y);
+        minU = s.x < minU ? s.x : minU;
+        maxU = s.x > maxU ? s.x : maxU;
+        minV = s.y < minV ? s.y : minV;
+        maxV = s.y > maxV ? s.y : maxV;
+    }
+    return finite && !box_misses_screen(p, minU, maxU, minV, maxV);
+}
+
+} // namespace
+
+__global__ __launch_bounds__(64 * kVisFrames) void cape_map_classify_kernel(MapVisibilityParams p, int nFrames)
+{
+    __shared__ unsigned s_count[kVisFrames];
+    __shared__ unsigned long long s_base;
+    __shared__ unsigned long long s_listed[kVisFrames][CAPE_MAP_MAX_PLANES / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frame = blockIdx.x * kVisFrames + wave;
+    const bool live = frame < nFrames; // (idle waves of the last workgroup list nothing and store nothing)
+    unsigned myCount = 0;
+    if (live)
+    {
+        const double* T = p.poses + (size_t)frame * 16;
+        uint32_t* words = p.skip + (size_t)frame * p.skipWords;
+        for (int jb = 0; jb < p.nMap; jb += 64)
+        {
+            const int j = jb + lane;
+            const bool has = j < p.nMap;
+            const bool moving = has && p.moving && ((p.moving[j >> 5] >> (j & 31)) & 1u);
+            const bool listed = has && !moving && may_be_visible(T, p, j);
+            // bit j = moving, or not visible: every listed plane starts as not visible, and only a listed plane can turn out
+            // visible -- so every bit below n_map starts set, and the bits beyond it in the last word are 0
+            const unsigned long long set = __ballot(has), l = __ballot(listed);
+            if (lane == 0)
+            {
+                words[jb >> 5] = (uint32_t)set;
+                if ((jb >> 5) + 1 < p.skipWords)
+                    words[(jb >> 5) + 1] = (uint32_t)(set >> 32);
+                s_listed[wave][jb >> 6] = l;
+            }
+            myCount += (unsigned)__popcll(l);
+        }
+    }
+    if (lane == 0)
+        s_count[wave] = myCount;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        unsigned total = 0;
+        for (int w = 0; w < kVisFrames; ++w)
+        {
+            const unsigned c = s_count[w];
+            s_count[w] = total;
+            total += c;
+        }
+        s_base = total ? atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)total) : 0ull;
+    }
+    __syncthreads();
+    if (!live)
+        return;
+    // (the list holds frames x n_map entries: every pair fits)
+    unsigned long long at = s_base + s_count[wave];
+    for (int jb = 0; jb < p.nMap; jb += 64)
+    {
+        const unsigned long long l = s_listed[wave][jb >> 6];
+        if ((l >> lane) & 1ull)
+            p.work[at + (unsigned)__popcll(l & ((1ull << lane) - 1ull))] = ((unsigned long long)(unsigned)frame << 32) | (unsigned)(jb + lane);
+        at += (unsigned)__popcll(l);
+    }
+}
+
+// A pair beyond this tier's capacities moves to the next tier's list when that one is larger in the resource that ran out (and
+// runs on this device: lastTier); otherwise it is undecided.
+template <int TIER> __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_visible_kernel(MapVisibilityParams p, int ldsPerWave)
+{
+    using T = Tier<TIER>;
+    constexpr bool kHasNext = TIER + 1 < kTiers;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr bool kCoop = T::kCoop;
+    const int tid = kCoop ? (int)threadIdx.x : lane;
+    constexpr int kStride = kCoop ? 256 : 64;
+    unsigned char* smem = smem_all + (kCoop ? (size_t)0 : (size_t)wave * ldsPerWave);
+    const MpLds L = mp_carve<TIER>(smem);
+    const size_t cap = p.workCapacity;
+    const unsigned long long reserved = *reinterpret_cast<const unsigned long long*>(p.counts);
+    const unsigned long long count = TIER == 0 ? (reserved < cap ? reserved : cap) : (unsigned long long)p.counts[1 + TIER];
+    const unsigned* list = TIER == 0 ? nullptr : p.tierLists + (size_t)(TIER - 1) * cap;
+    // tier 0: a fixed stride over the (many, short) pairs; the later tiers draw tickets (few pairs of very unequal cost)
+    auto next_index = [&](unsigned long long prev, bool first) -> unsigned long long {
+        if (kCoop)
+        {
+            if (threadIdx.x == 0)
+                L.sh[7] = (int)(TIER > 0 ? atomicAdd(&p.counts[4 + TIER], 1u) : (unsigned)(first ? blockIdx.x : prev + gridDim.x));
+            __syncthreads();
+            const unsigned t = (unsigned)L.sh[7];
+            __syncthreads();
+            return t;
+        }
+        if (TIER == 0)
+            return first ? (unsigned long long)blockIdx.x * T::kWavesPerGroup + wave : prev + (unsigned long long)gridDim.x * T::kWavesPerGroup;
+        unsigned t = 0;
+        if (lane == 0)
+            t = atomicAdd(&p.counts[4 + TIER], 1u);
+        return (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+    };
+    auto sync = [&]() {
+        if (kCoop)
+            __syncthreads();
+        else
+            CAPE_MP_SYNC();
+    };
+    // the orientation the host class gives an outer ring (OpenRing constructor): reversed when its signed area is positive
+    // (every lane reads the whole ring before any lane of the carve rewrites it)
+    auto orient = [&](double2* ring, int n) {
+        const double s = ring_area_signed(ring, n);
+        sync();
+        if (s > 0)
+        {
+            for (int v = tid; v < n / 2; v += kStride)
+            {
+                const double2 a = ring[v], b = ring[n - 1 - v];
+                ring[v] = b;
+                ring[n - 1 - v] = a;
+            }
+            sync();
+        }
+    };
+    for (unsigned long long t = next_index(0ull, true); t < count; t = next_index(t, false))
+    {
+        const size_t idx = TIER == 0 ? (size_t)t : (size_t)list[t];
+        const unsigned long long e = p.work[idx];
+        const int frame = (int)(e >> 32), j = (int)(e & 0xFFFFFFFFu);
+        const cape_map_plane& M = p.mapPlanes[j];
+        const cape_map_ring R = p.mapRings[M.ring_first];
+        const int na = (int)R.vertex_count;
+        double result;
+        if (na > T::kRing)
+            result = nan_code(kNanRing);
+        else
+        {
+            const double* Tm = p.poses + (size_t)frame * 16;
+            const CameraFrame F = camera_frame(Tm, M);
+            // the outer ring seen from the camera (transform_boundary, polygon.cpp:430-451), oriented as the CameraPolygon holds it ...
+            const double2* src = p.mapVertices + R.vertex_offset;
+            for (int v = tid; v < na; v += kStride)
+                L.ringA[v] = to_camera_vertex(Tm, F, src[v]);
+            sync();
+            orient(L.ringA, na);
+            // ... on the screen, oriented again (boost::geometry::correct in to_screen_space)
+            for (int v = tid; v < na; v += kStride)
+                L.ringA[v] = screen_vertex(p, F, L.ringA[v]);
+            // the screen rectangle (utils/polygon.cpp:27-37)
+            if (tid < 4)
+                L.ringB[tid] = make_double2((tid == 1 || tid == 2) ? p.width - 1.0 : 1.0, tid >= 2 ? p.height - 1.0 : 1.0);
+            sync();
+            orient(L.ringA, na);
+            orient(L.ringB, 4);
+            if constexpr (kCoop)
+                result = rings_inter_area_coop<T::kStack, T::kXs>(L, na, 4, tid);
+            else
+                result = rings_inter_area<T::kStack, T::kXs>(L, na, 4, lane);
+            sync();
+        }
+        if (tid == 0)
+        {
+            const bool stack = is_nan_code(result, kNanStack), slabs = is_nan_code(result, kNanSlabs), ring = is_nan_code(result, kNanRing);
+            bool again = false;
+            if (kHasNext && TIER + 1 <= p.lastTier)
+                again = (stack && later_stack<TIER>() > T::kStack) || (slabs && later_xs<TIER>() > T::kXs) || (ring && later_ring<TIER>() > T::kRing);
+            if (again)
+                p.tierLists[(size_t)TIER * cap + atomicAdd(&p.counts[2 + TIER], 1u)] = (unsigned)idx; // (an entry visits each tier once)
+            else
+            {
+                const bool undecided = stack || slabs || ring;
+                if (result > 0 || undecided)
+                    atomicAnd(&p.skip[(size_t)frame * p.skipWords + (j >> 5)], ~(1u << (j & 31)));
+                if (undecided)
+                    atomicAdd(reinterpret_cast<unsigned long long*>(p.counts + 8), 1ull);
+            }
+        }
+    }
+}
+
+hipError_t launch_map_visibility(const MapVisibilityParams& params, int nFrames, hipStream_t stream)
+{
+    MapVisibilityParams p = params;
+    p.lastTier = tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes ? 3 : 2;
+    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(cape_map_classify_kernel, dim3((nFrames + kVisFrames - 1) / kVisFrames), dim3(64 * kVisFrames), 0, stream, p, nFrames);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    // persistent grids: as many workgroups as the chip holds at once (the list's length is only known on the device)
+    const int cus = p.computeUnits > 0 ? p.computeUnits : 256;
+    auto launch = [&](auto kernel, int lds, int wavesPerGroup, bool coop, int groupsPerCu) {
+        hipLaunchKernelGGL(kernel, dim3(cus * groupsPerCu), dim3(64 * wavesPerGroup), (size_t)lds * (coop ? 1 : wavesPerGroup), stream, p, lds);
+        return hipGetLastError();
+    };
+    if (const hipError_t e = launch(cape_map_visible_kernel<0>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
+        return e;
+    if (const hipError_t e = launch(cape_map_visible_kernel<1>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
+        return e;
+    if (const hipError_t e = launch(cape_map_visible_kernel<2>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
+        return e;
+    // (a device without the LDS for the largest tier: lastTier = 2, the pairs it would take are undecided)
+    if (p.lastTier >= 3)
+        return launch(cape_map_visible_kernel<3>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu);
+    return hipSuccess;
+}
+
+} // namespace cape

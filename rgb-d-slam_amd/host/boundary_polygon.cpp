@@ -802,6 +802,28 @@ Polygon Polygon::to_camera_space(const double* T) const
     return out;
 }
 
+bool Polygon::is_visible_in_screen_space(double width, double height, double fx, double fy, double cx, double cy) const
+{
+    std::vector<vector2> screen;
+    screen.reserve(_ring.size());
+    for (const vector2& q : _ring)
+    {
+        const vector3 p = get_point_from_plane_coordinates(q, _center, _xAxis, _yAxis);
+        const double inv = 1.0 / p[2];
+        const double u = inv * (fx * p[0] + cx * p[2]), v = inv * (fy * p[1] + cy * p[2]);
+        if (!std::isfinite(u) || !std::isfinite(v))
+            return false;
+        screen.push_back({u, v});
+    }
+    std::vector<vector2> rect {{1.0, 1.0}, {width - 1.0, 1.0}, {width - 1.0, height - 1.0}, {1.0, height - 1.0}};
+    // both as the OpenRing constructor orients an outer ring
+    if (ring_area_signed(screen) > 0)
+        std::reverse(screen.begin(), screen.end());
+    if (ring_area_signed(rect) > 0)
+        std::reverse(rect.begin(), rect.end());
+    return rings_inter_area(screen, rect) > 0;
+}
+
 Polygon Polygon::transform(const vector3& nextNormal, const vector3& nextCenter) const
 {
     const auto axes = get_plane_coordinate_system(nextNormal);

@@ -77,6 +77,14 @@ class Polygon
     // the whole transform, the axes through its rotation (re-normalised), every boundary point is lifted to 3-D, moved and
     // re-expressed in the new frame.  Same statements as the device matcher (csrc/cape_match_polygon.hip).
     [[nodiscard]] Polygon to_camera_space(const double* worldToCamera) const;
+    // CameraPolygon::is_visible_in_screen_space (polygon_coordinates.cpp:120-127) of a polygon in camera space, for a camera
+    // without skew: every vertex of the OUTER ring goes to the screen (get_screen_points :77-100: get_point_from_plane_coordinates,
+    // then to_screen_coordinates, point_coordinates.cpp:201-210, `1.0 / z * (K p)`), the ring is oriented like an outer ring
+    // (boost::geometry::correct in to_screen_space :102-118) and intersected with the screen rectangle (1, 1) .. (width - 1,
+    // height - 1) (utils/polygon.cpp:24-46): visible <=> the area of the intersection is > 0, which is when Boost's intersection of
+    // two areal geometries is not empty.  A NaN or infinite screen coordinate: not visible (the reference drops NaN only).  No
+    // clipping of vertices behind the camera, as in the reference.  Same statements as csrc/cape_map_visibility.hip.
+    [[nodiscard]] bool is_visible_in_screen_space(double width, double height, double fx, double fy, double cx, double cy) const;
     // Polygon::merge_union (polygon.cpp:325-336 over union_one :463-493): this polygon becomes (this U other), `other`
     // being projected into this frame first; two disjoint polygons leave the larger one (the reference keeps the biggest
     // piece of the multi-polygon), then simplify().  A region that the two outlines enclose without covering it becomes an

@@ -1,5 +1,5 @@
 /* cape_host_map.h -- the host twins of libcape_primitives.so (host/polygon_capi.cpp) that track planes without the device: the map
- * matcher, the map update and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
+ * matcher, the visibility test in front of it, the map update and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
  * frame's kept planes.  Not part of libcape_hip's C ABI: no function of libcape_hip takes these types. */
 #ifndef CAPE_HOST_MAP_H
 #define CAPE_HOST_MAP_H
@@ -120,6 +120,17 @@ int cape_host_map_update(const cape_host_map* map, const int32_t* match, const c
  * reference's); CAPE_ERR_CAPACITY if detected_out is too small -- its n and n_vertices say what the frame needs either way. */
 int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, const cape_gather_layout* layout, const cape_gather_polygon_layout* polygon_layout,
                           int32_t frame, cape_host_planes* detected_out);
+
+/* The skip words of ONE frame on the host class: bit j = bit j of `moving` is set, or MapPlane::is_visible(world_to_camera) is false
+ * (map_primitive.cpp:186-189: to_camera_space, then Polygon::is_visible_in_screen_space of host/boundary_polygon.hpp with the given
+ * image size and intrinsics).  The twin of cape_map_visibility (tests/test_gpu_map_visibility.py compares them bit for bit; the
+ * device takes a bounding-box shortcut, this function none) and the answer for a caller without a device.  world_to_camera: 16
+ * doubles row-major (NULL = identity); moving: ceil(n_planes / 32) words, one bit per map plane (NULL: none); skip_out:
+ * ceil(n_planes / 32) words, the bits beyond n_planes in the last word 0.  Returns 0, or CAPE_ERR_INVALID_ARGUMENT for a NULL map or
+ * skip_out (with n_planes > 0), a negative n_planes, a width or height below 3, a ring outside its array / of fewer than 3 vertices
+ * or a map plane without rings (nothing is written then). */
+int cape_host_map_visibility(const cape_host_map* map, const double* world_to_camera, int32_t width, int32_t height, double fx, double fy,
+                             double cx, double cy, const uint32_t* moving, uint32_t* skip_out);
 
 #ifdef __cplusplus
 }

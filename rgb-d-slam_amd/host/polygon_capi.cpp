@@ -1,9 +1,9 @@
 // C entry points of libcape_primitives.so over the host boundary-polygon class.  None of them is part of libcape_hip's C ABI
 // (include/cape_hip.h).  cape_host_polygon, cape_host_polygon_inter_area* and the cape_host_covariance / kalman hooks at the
 // end are test hooks: the tests compare the device (or a numpy restatement) with them through ctypes.  cape_host_match_map,
-// cape_host_map_update and cape_host_shard_frame are host twins a caller may use, declared and described in cape_host_map.h: the
-// first answers the frames cape_match_map flags, the second is the map update, which runs on the host only, the third reads a
-// gathered shard.  They share the conversions of the anonymous namespace below.
+// cape_host_map_visibility, cape_host_map_update and cape_host_shard_frame are host twins a caller may use, declared and described in
+// cape_host_map.h: the first answers the frames cape_match_map flags, the second decides which map planes it visits, the third is the
+// map update, which runs on the host only, the fourth reads a gathered shard.  They share the conversions of the anonymous namespace below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -326,6 +326,36 @@ extern "C" int cape_host_match_map(const cape_host_map* map, const cape_host_pla
             matched[selected] = 1;
             map_of[selected] = j;
         }
+        return 0;
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
+}
+
+// The visibility twin (cape_host_map.h).
+extern "C" int cape_host_map_visibility(const cape_host_map* map, const double* world_to_camera, int32_t width, int32_t height, double fx, double fy,
+                                        double cx, double cy, const uint32_t* moving, uint32_t* skip_out)
+{
+    static const double kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    if (!map || map->n_planes < 0 || width < 3 || height < 3 || (map->n_planes > 0 && (!skip_out || !map->planes)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const double* T = world_to_camera ? world_to_camera : kIdentity;
+    const int32_t n_planes = map->n_planes;
+    try
+    {
+        std::vector<uint32_t> words((size_t)(n_planes + 31) / 32, 0u);
+        for (int32_t j = 0; j < n_planes; ++j)
+        {
+            const bool isMoving = moving && ((moving[j >> 5] >> (j & 31)) & 1u);
+            Polygon mapPolygon;
+            if (!map_polygon(*map, map->planes[j], isMoving ? nullptr : &mapPolygon))
+                return CAPE_ERR_INVALID_ARGUMENT;
+            if (isMoving || !mapPolygon.to_camera_space(T).is_visible_in_screen_space(width, height, fx, fy, cx, cy))
+                words[j >> 5] |= 1u << (j & 31);
+        }
+        std::copy(words.begin(), words.end(), skip_out);
         return 0;
     }
     catch (const std::exception&)

@@ -151,6 +151,7 @@ assert MATCH_EXACT_DTYPE.itemsize == 8 + 3 * 64 + 8 + 8 * 256
 # N2 against a persistent map (cape_map_upload / cape_match_map)
 MAP_MAX_PLANES, MAP_MAX_RING, MAP_MAX_HOLES = 1024, 512, 8
 MATCH_MAP_AREAS = 4
+MATCH_MAP_DEVICE_SKIP = 16  # match_map / match_map_shards: the skip words of the last Extractor.map_visibility
 MAP_PLANE_DTYPE = np.dtype([
     ("normal", "<f8", 3), ("d", "<f8"), ("x_axis", "<f8", 3), ("y_axis", "<f8", 3), ("center", "<f8", 3),
     ("ring_first", "<u4"), ("ring_count", "<u4")], align=True)
@@ -226,6 +227,8 @@ def _host_library():
         f64, i32, Map, Planes = (C.POINTER(t) for t in (C.c_double, C.c_int32, cape_host_map, cape_host_planes))
         L.cape_host_match_map.argtypes = [Map, Planes, f64, C.POINTER(C.c_uint32), C.c_uint32, i32, i32, f64]
         L.cape_host_map_update.argtypes = [Map, i32, Planes, f64, f64, C.c_uint32, C.POINTER(C.c_uint64), Map, i32]
+        L.cape_host_map_visibility.argtypes = [Map, f64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.cape_host_shard_frame.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout),
                                             C.c_int32, Planes]
         _host_lib = L
@@ -350,6 +353,40 @@ def host_match_map(map_arrays, detected, world_to_camera=None, skip=None, flags=
     return host_match_map_call(map_arrays, detected, world_to_camera, skip, flags, areas)()
 
 
+def host_map_visibility(map_arrays, world_to_camera, width, height, fx, fy, cx, cy, moving=None):
+    """cape_host_map_visibility of libcape_primitives.so: the skip words of ONE frame on the host class -- bit j set = map plane j
+    is moving or MapPlane::is_visible(world_to_camera) is false.  The twin of Extractor.map_visibility, without its shortcut.
+
+    map_arrays: pack_map(...); world_to_camera: 4 x 4 (None: identity); moving: ceil(n_map / 32) uint32 words, one bit per map
+    plane (None: none).  Returns ceil(n_map / 32) uint32 words."""
+    return host_map_visibility_call(map_arrays, world_to_camera, width, height, fx, fy, cx, cy, moving)()
+
+
+def host_map_visibility_call(map_arrays, world_to_camera, width, height, fx, fy, cx, cy, moving=None):
+    """host_map_visibility with the arguments packed now and the native call deferred (see host_match_map_call)."""
+    _host_library()
+    src, src_view = _map_arrays(map_arrays)
+    T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(16)
+    n_words = (len(src["planes"]) + 31) // 32
+    M = None if moving is None else np.ascontiguousarray(moving, np.uint32).reshape(-1)
+    if M is not None and len(M) != n_words:
+        raise CapeError("host_map_visibility: moving takes ceil(n_map / 32) words")
+    words = np.zeros(max(n_words, 1), np.uint32)
+    args = (C.byref(src_view), _as(T, C.c_double), int(width), int(height), float(fx), float(fy), float(cx), float(cy), _as(M, C.c_uint32),
+            _as(words, C.c_uint32))
+    keep = (src, T, M)
+
+    def run():
+        """the native call alone (ctypes releases the GIL for its duration)"""
+        assert keep is not None
+        rc = _host_lib.cape_host_map_visibility(*args)
+        if rc != 0:
+            raise CapeError(f"cape_host_map_visibility failed ({rc})")
+        return words[:n_words]
+
+    return run
+
+
 def host_match_map_call(map_arrays, detected, world_to_camera=None, skip=None, flags=0, areas=False):
     """host_match_map with the arguments packed now and the native call deferred: returns run(), which makes only the call and
     returns host_match_map's result (timing the twin from several threads without the packing)."""
@@ -392,6 +429,7 @@ EXPORTED_SYMBOLS = [
     "cape_reset_timings", "cape_match_consecutive", "cape_device_matches", "cape_copy_matches",
     "cape_match_polygons", "cape_match_polygons_pose", "cape_copy_polygon_matches",
     "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_shards", "cape_copy_shard_map_matches",
+    "cape_map_visibility", "cape_copy_map_visibility",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
@@ -469,6 +507,8 @@ def load_library():
     L.cape_match_map_shards.argtypes = [vp, vp, C.c_int32, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout), vp, vp,
                                         C.c_uint32, vp]
     L.cape_copy_shard_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.cape_map_visibility.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.cape_copy_map_visibility.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_int64)]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -742,9 +782,34 @@ class Extractor:
                                               V.ctypes.data_as(C.c_void_p), len(V)), "cape_map_upload")
         self.map_size = len(P)
 
+    def map_visibility(self, n_frames, world_to_camera=None, moving=None, stream=0):
+        """cape_map_visibility: the skip words of match_map / match_map_shards decided on the device -- bit j of frame (or slot) f set
+        = map plane j is moving or not visible from world_to_camera[f] (n_frames x 4 x 4, None: identity).  moving: ceil(n_map / 32)
+        uint32 words, one bit per map plane (None: none).  A later match_map(..., skip=None, flags=MATCH_MAP_DEVICE_SKIP) reads the
+        words on the device; map_visibility_words copies them."""
+        T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(n_frames, 16)
+        M = None if moving is None else np.ascontiguousarray(moving, np.uint32).reshape(-1)
+        if M is not None and len(M) != (getattr(self, "map_size", 0) + 31) // 32:
+            raise CapeError("map_visibility: moving takes ceil(n_map / 32) words")
+        _check(self.L, self.L.cape_map_visibility(self.h, n_frames, None if T is None else T.ctypes.data_as(C.c_void_p),
+                                                  None if M is None else M.ctypes.data_as(C.c_void_p), C.c_void_p(stream)),
+               "cape_map_visibility")
+        self.visibility_map_size = self.map_size
+
+    def map_visibility_words(self, n_frames):
+        """(words[n_frames, ceil(n_map / 32)] uint32, n_undecided) of the last map_visibility: n_undecided pairs exceeded the
+        intersection capacities and count as visible."""
+        n_words = (getattr(self, "visibility_map_size", 0) + 31) // 32
+        words = np.zeros((n_frames, max(n_words, 1)), np.uint32)
+        undecided = C.c_int64(0)
+        _check(self.L, self.L.cape_copy_map_visibility(self.h, n_frames, words.ctypes.data_as(C.c_void_p), C.byref(undecided)),
+               "cape_copy_map_visibility")
+        return words[:, :n_words], int(undecided.value)
+
     def match_map(self, n_frames, world_to_camera=None, skip=None, flags=0, stream=0):
         """world_to_camera: n_frames x 4 x 4 row-major [R t; 0 0 0 1] (None: identity); skip: n_frames x ceil(n_map / 32) uint32,
-        bit j of frame f set = map plane j is not visited (None: none skipped)."""
+        bit j of frame f set = map plane j is not visited (None: none skipped; with flags=MATCH_MAP_DEVICE_SKIP: the words of the
+        last map_visibility)."""
         T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(n_frames, 16)
         S = None if skip is None else np.ascontiguousarray(skip, np.uint32).reshape(n_frames, -1)
         _check(self.L, self.L.cape_match_map(self.h, n_frames, None if T is None else T.ctypes.data_as(C.c_void_p),
