@@ -510,6 +510,35 @@ int cape_match_polygons(cape_handle h, int32_t n_frames, uint32_t flags, void* s
 int cape_match_polygons_pose(cape_handle h, int32_t n_frames, const double* prev_to_cur, uint32_t flags, void* stream);
 int cape_copy_polygon_matches(cape_handle h, int32_t n_frames, cape_frame_match_exact* out);
 
+/* cape_match_polygons_pose without its two limits: frames of up to 128 kept planes, counted in record order over the frame's whole
+ * record chain (cape_frame_header.next_record), with result buffers of its own -- cape_match_polygons and its results are not
+ * touched.  Per pair and per frame the statements are cape_match_polygons_pose's: the pose on the previous plane and its polygon,
+ * the gates, Polygon::project into the detected plane's frame, the slab intersection, the overlap threshold, the lowest index on a
+ * tie, the `selectedIndex <= 0` quirk and the is-matched flags carried from previous plane j to j + 1; a frame both calls serve
+ * gets the same matches and bit-identical areas from either.  prev_to_cur as for cape_match_polygons_pose (n_frames x 16 doubles in
+ * HOST memory, read before the call returns, entry 0 not read, NULL = identity).  flags: CAPE_MATCH_ADVANCED,
+ * CAPE_MATCH_ALLOW_INDEX0 and CAPE_MATCH_MAP_AREAS, which keeps the dense area table (CAPE_ERR_CAPACITY if it would exceed 1 GiB).
+ * A frame is flagged CAPE_MATCH_EXACT_OVERFLOW, with all its matches -1, only if it or its predecessor keeps more than 128 planes,
+ * an output plane of either chain has CAPE_POLY_OVERFLOW, a pair is beyond the largest intersection tier, or the frame's pairs do
+ * not fit the work list (4 194 304 gated pairs per call): cape_host_match_planes (host/cape_host_map.h) answers for it.  Needs
+ * cape_build_polygons of the same batch first.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, negative n_frames, unknown flag;
+ * CAPE_ERR_CAPACITY: more frames than the last cape_build_polygons covered, the area table beyond 1 GiB.  Asynchronous on `stream`. */
+#define CAPE_MATCH_WIDE_MAX_PLANES 128
+typedef struct cape_frame_match_wide
+{
+    int32_t n_prev, n_cur;   /* kept planes of frame f-1 / f over their whole record chains */
+    uint32_t flags;          /* CAPE_MATCH_EXACT_OVERFLOW */
+    int32_t n_matched;
+} cape_frame_match_wide;
+int cape_match_polygons_wide(cape_handle h, int32_t n_frames, const double* prev_to_cur, uint32_t flags, void* stream);
+/* Synchronous copy of the last cape_match_polygons_wide, row-major with 128 entries per frame: match[f][j] = the kept plane of frame
+ * f taken by previous kept plane j, or -1; seg_prev[f][j] / seg_cur[f][i] = the plane's position in its frame's concatenated segment
+ * list (the chain's records one after the other), -1 beyond the count; inter_area[f][j][i] in mm^2, -1 for an ungated pair, NaN for
+ * a pair beyond capacity (the call must have had CAPE_MATCH_MAP_AREAS).  Any of the four arrays may be NULL.  CAPE_ERR_CAPACITY:
+ * more frames than that call covered. */
+int cape_copy_polygon_matches_wide(cape_handle h, int32_t n_frames, cape_frame_match_wide* frames, int32_t* match, int32_t* seg_prev,
+                                   int32_t* seg_cur, double* inter_area);
+
 /* Row N2 against a persistent MAP (Feature_Map::get_matches, feature_map.hpp:638-697): which detected plane of each frame
  * belongs to which map plane.  The map planes live in world coordinates; their boundary polygons (grown over many frames by
  * merge_union, so they may be large and have holes) stay on the device from cape_map_upload until the next upload or destroy.

@@ -155,6 +155,26 @@ int device_skip_words(const cape_handle_s* h, int n, const uint32_t* skip, const
     *words = V.skip;
     return CAPE_OK;
 }
+// the work buffers of cape_match_polygons_wide, one allocation: counters, per-frame ranges, the work list, its areas, the tier lists
+struct WideWorkLayout
+{
+    size_t counts, ranges, work, area, tiers, total;
+};
+WideWorkLayout wide_work_layout(int maxBatch, size_t cap)
+{
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    WideWorkLayout l;
+    l.counts = 0;
+    l.ranges = up(16 * sizeof(unsigned));
+    l.work = l.ranges + up((size_t)maxBatch * sizeof(uint2));
+    l.area = l.work + up(cap * sizeof(unsigned long long));
+    l.tiers = l.area + up(cap * sizeof(double));
+    l.total = l.tiers + up(3 * cap * sizeof(unsigned));
+    return l;
+}
+// entries of its work list at most (112 MB of buffers): the GATED pairs of a call, a few per kept plane -- 1 024 per frame of a
+// 4 096-frame batch, where a frame of 128 planes on a checkerboard of facets gates some hundreds; a frame beyond it is flagged
+constexpr size_t kWideWorkMax = (size_t)1 << 22;
 constexpr uint32_t kMatchMapFlags = CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS | CAPE_MATCH_MAP_DEVICE_SKIP;
 bool unit_norm(const double* v) // double_equal(norm, 1) as to_camera_space requires (polygon_coordinates.cpp:144-151)
 {
@@ -375,6 +395,101 @@ int cape_copy_polygon_matches(cape_handle h, int32_t n_frames, cape_frame_match_
     CAPE_ON_DEVICE(h);
     CAPE_HIP_TRY(drain_handle(h));
     CAPE_HIP_TRY(copy_out(out, h->poly.matches, 0, (size_t)n_frames));
+    return CAPE_OK;
+}
+
+int cape_match_polygons_wide(cape_handle h, int32_t n_frames, const double* prev_to_cur, uint32_t flags, void* stream_)
+{
+    constexpr size_t WP = CAPE_MATCH_WIDE_MAX_PLANES;
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    if (n_frames > h->poly.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
+    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
+    const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0;
+    const size_t areaDoubles = (size_t)n_frames * WP * WP;
+    if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
+        return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer frames per call, or no CAPE_MATCH_MAP_AREAS)");
+    auto& W = h->wide;
+    W.matchFrames = 0;
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    const size_t B = (size_t)h->cfg.max_batch;
+    const size_t cap = std::min(B * WP * WP, kWideWorkMax);
+    const WideWorkLayout lay = wide_work_layout(h->cfg.max_batch, cap);
+    CAPE_HIP_TRY(W.frames.ensure(B));
+    CAPE_HIP_TRY(W.match.ensure(3 * B * WP));
+    CAPE_HIP_TRY(W.kept.ensure(B * WP));
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them
+    CAPE_HIP_TRY(W.work.grow(lay.total, drain));
+    if (keepAreas)
+        CAPE_HIP_TRY(W.areas.grow(areaDoubles, drain));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    cape::MatchWideParams p{};
+    if (prev_to_cur)
+    {
+        // through the pinned twin like cape_match_polygons_pose's: n_frames x 16 doubles in the caller's memory order, read before
+        // the call returns (entry 0 is never read)
+        const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double);
+        CAPE_HIP_TRY(W.poses.ensure(B * 16));
+        CAPE_HIP_TRY(W.posesTwin.upload(W.poses, poseBytes, B * 16 * sizeof(double), stream,
+                                        [&](void* stage) { std::memcpy(stage, prev_to_cur, poseBytes); }));
+        p.poses = W.poses;
+    }
+    p.records = h->res.records;
+    p.polygons = h->poly.polygons;
+    p.vertices = reinterpret_cast<const double2*>(h->poly.vertices.get());
+    p.boundaryCapacity = h->boundaryCap;
+    p.maxBatch = h->cfg.max_batch;
+    p.nRecords = h->cfg.max_batch + h->chain.spillRecords;
+    p.frames = W.frames;
+    p.match = W.match;
+    p.segPrev = W.match + B * WP;
+    p.segCur = W.match + 2 * B * WP;
+    p.areas = keepAreas ? W.areas.get() : nullptr;
+    p.kept = W.kept;
+    p.counts = reinterpret_cast<unsigned*>(W.work + lay.counts);
+    p.frameRange = reinterpret_cast<uint2*>(W.work + lay.ranges);
+    p.work = reinterpret_cast<unsigned long long*>(W.work + lay.work);
+    p.workArea = reinterpret_cast<double*>(W.work + lay.area);
+    p.tierLists = reinterpret_cast<unsigned*>(W.work + lay.tiers);
+    p.workCapacity = cap;
+    p.computeUnits = h->computeUnits;
+    p.ldsLimitBytes = h->ldsLimit;
+    set_match_thresholds(p, flags);
+    CAPE_HIP_TRY(cape::launch_match_wide(p, n_frames, stream));
+    W.matchFrames = n_frames;
+    W.matchAreas = keepAreas;
+    return CAPE_OK;
+}
+
+int cape_copy_polygon_matches_wide(cape_handle h, int32_t n_frames, cape_frame_match_wide* frames, int32_t* match, int32_t* seg_prev,
+                                   int32_t* seg_cur, double* inter_area)
+{
+    constexpr size_t WP = CAPE_MATCH_WIDE_MAX_PLANES;
+    if (!h || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    const auto& W = h->wide;
+    if (n_frames > W.matchFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_match_polygons_wide of the current batch");
+    if (inter_area && n_frames > 0 && !W.matchAreas)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_match_polygons_wide did not keep the inter-area table (CAPE_MATCH_MAP_AREAS)");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    const size_t B = (size_t)h->cfg.max_batch, n = (size_t)n_frames * WP;
+    CAPE_HIP_TRY(copy_out(frames, W.frames, 0, (size_t)n_frames));
+    CAPE_HIP_TRY(copy_out(match, W.match, 0, n));
+    CAPE_HIP_TRY(copy_out(seg_prev, W.match, B * WP, n));
+    CAPE_HIP_TRY(copy_out(seg_cur, W.match, 2 * B * WP, n));
+    CAPE_HIP_TRY(copy_out(inter_area, W.areas, 0, n * WP));
     return CAPE_OK;
 }
 

@@ -29,6 +29,7 @@ hipError_t launch_pack(const PackParams& p, hipStream_t stream);
 hipError_t launch_polygons(const PolygonParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_polygons(const MatchPolygonParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_match_wide(const MatchWideParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
@@ -324,6 +325,22 @@ struct cape_handle_s
         Buffer<cape_frame_match_exact> matches;
         Buffer<unsigned> lists; // counters (padded to 64 entries) + 4 lists of max_batch x 256 pairs
     } poly;
+
+    // cape_match_polygons_wide: consecutive frames of up to CAPE_MATCH_WIDE_MAX_PLANES kept planes over their record chains.  Results
+    // and work buffers of its own, allocated on first use (the work list and the area table grown on demand behind drain_handle):
+    // cape_match_polygons' state above is not touched
+    struct WideMatch
+    {
+        Buffer<double> poses; // max_batch x 16 doubles
+        cape::abi::PinnedTwin posesTwin;
+        Buffer<cape_frame_match_wide> frames; // max_batch
+        Buffer<int32_t> match;                // max_batch x 128 match, then as many seg_prev, then seg_cur
+        Buffer<uint2> kept;                   // max_batch x 128: MatchWideParams::kept
+        Buffer<double> areas;                 // CAPE_MATCH_MAP_AREAS: frames x 128 x 128 of the call
+        Buffer<unsigned char> work;           // counters, frame ranges, work list, its areas, the tier lists (wide_work_layout)
+        int matchFrames = 0;                  // frames of the last cape_match_polygons_wide (0: none for the current batch)
+        bool matchAreas = false;              // ... and whether it kept the dense table
+    } wide;
 
     // N2 against a persistent map (cape_map_upload / cape_match_map): the map sized at upload, the rest allocated on first use
     struct Map

@@ -254,6 +254,34 @@ struct MatchMapParams
                                 // shard) -- one load tells the later kernels where the polygon lies, without dividing the slot by framesCapacity
 };
 
+// N2 between consecutive frames of up to CAPE_MATCH_WIDE_MAX_PLANES kept planes, record chains included (cape_match_wide.hip)
+struct MatchWideParams
+{
+    const cape_frame_record* records; // the batch's records, then the spill pool's (what cape_frame_header::next_record indexes)
+    const cape_polygon* polygons;     // records x CAPE_MAX_PLANES, indexed by the RECORD index
+    const double2* vertices;          // records x boundaryCapacity
+    int boundaryCapacity;
+    int maxBatch, nRecords;           // a link of a chain lies in [maxBatch, nRecords)
+    const double* poses;              // frames x 16, row-major [R t; 0 0 0 1] from camera f-1 to camera f; null = identity
+    cape_frame_match_wide* frames;
+    int32_t* match;                   // frames x CAPE_MATCH_WIDE_MAX_PLANES
+    int32_t* segPrev;                 // frames x CAPE_MATCH_WIDE_MAX_PLANES: position of kept plane j of frame f-1 in its frame's segment list
+    int32_t* segCur;
+    double* areas;                    // frames x CAPE_MATCH_WIDE_MAX_PLANES^2, or null (CAPE_MATCH_MAP_AREAS off)
+    uint2* kept;                      // frames x CAPE_MATCH_WIDE_MAX_PLANES, written by the gate kernel: (record index, segment in that record) of
+                                      // kept plane k of the frame -- where its polygon row and vertex slab lie
+    unsigned long long* work;         // workCapacity entries (frame << 32) | (j << 8) | i, per frame in (j, i) order
+    double* workArea;                 // the area of each entry
+    unsigned* tierLists;              // 3 x workCapacity: indices into `work` handed to tiers 1..3
+    unsigned* counts;                 // 16 words, as MatchMapParams::counts
+    uint2* frameRange;                // frames: (first entry, entries) of the frame's pairs
+    size_t workCapacity;
+    int computeUnits;
+    int ldsLimitBytes;
+    uint32_t flags;
+    double minCosAngle, maxDistance, minOverlap; // as MatchParams
+};
+
 // cape_map_visibility (cape_map_visibility.hip): bit j of frame f = map plane j is moving or not visible from the frame's camera
 struct MapVisibilityParams
 {

@@ -1,5 +1,5 @@
 /* cape_host_map.h -- the host twins of libcape_primitives.so (host/polygon_capi.cpp) that track planes without the device: the map
- * matcher, the visibility test in front of it, the map update and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
+ * matcher, the matcher of two consecutive frames, the visibility test in front of it, the map update and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
  * frame's kept planes.  Not part of libcape_hip's C ABI: no function of libcape_hip takes these types. */
 #ifndef CAPE_HOST_MAP_H
 #define CAPE_HOST_MAP_H
@@ -94,6 +94,19 @@ typedef struct cape_host_planes
  * or CAPE_ERR_INVALID_ARGUMENT for a ring outside its array / of fewer than 3 vertices or a map plane without rings. */
 int cape_host_match_map(const cape_host_map* map, const cape_host_planes* detected, const double* world_to_camera, const uint32_t* skip,
                         uint32_t flags, int32_t* match, int32_t* map_of, double* inter_area);
+
+/* MapPlane::find_matches between two CONSECUTIVE frames on the host class, the kept planes of frame f-1 playing the map planes: the
+ * twin of cape_match_polygons_wide and of cape_match_polygons_pose (tests/test_gpu_match_wide.py compares them bit for bit), with no
+ * limit on the number of planes, and the answer for a frame either of them flags CAPE_MATCH_EXACT_OVERFLOW.  prev_to_cur16: 16
+ * doubles row-major taking camera f-1's frame into camera f's; NULL = identity, for which -- like the device -- the previous
+ * planes and polygons are used as they are.  flags: CAPE_MATCH_ADVANCED, CAPE_MATCH_ALLOW_INDEX0.  Per previous plane j in order:
+ * the pose on the plane (plane_to_camera) and on its polygon (to_camera_space), the gates, cur's polygon i .inter_area(projected)
+ * for every gated pair, the greatest area above the overlap threshold among the planes not taken yet (lowest index on a tie), the
+ * `selectedIndex <= 0` quirk.  A previous plane whose own area (prev->areas, NULL: its ring's) is not positive matches nothing, its
+ * areas are still reported.  Outputs: match[prev->n] and inter_area[prev->n x cur->n] (NULL: not kept; -1 for an ungated pair).
+ * Returns 0, or CAPE_ERR_INVALID_ARGUMENT for a NULL argument, an unknown flag or a ring outside its array. */
+int cape_host_match_planes(const cape_host_planes* prev, const cape_host_planes* cur, const double* prev_to_cur16, uint32_t flags,
+                           int32_t* match, double* inter_area);
 
 /* Feature_Map::update_map (feature_map.hpp:367-384, :701-830) for ONE frame on the host class, over the ordered list of
  * cape_map_upload (local planes first, then staged; CAPE_MAP_TRACK_STAGED tells them apart).  match[map->n_planes]: the kept plane

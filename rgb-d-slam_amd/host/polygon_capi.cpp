@@ -1,9 +1,10 @@
 // C entry points of libcape_primitives.so over the host boundary-polygon class.  None of them is part of libcape_hip's C ABI
 // (include/cape_hip.h).  cape_host_polygon, cape_host_polygon_inter_area* and the cape_host_covariance / kalman hooks at the
 // end are test hooks: the tests compare the device (or a numpy restatement) with them through ctypes.  cape_host_match_map,
-// cape_host_map_visibility, cape_host_map_update and cape_host_shard_frame are host twins a caller may use, declared and described in
-// cape_host_map.h: the first answers the frames cape_match_map flags, the second decides which map planes it visits, the third is the
-// map update, which runs on the host only, the fourth reads a gathered shard.  They share the conversions of the anonymous namespace below.
+// cape_host_match_planes, cape_host_map_visibility, cape_host_map_update and cape_host_shard_frame are host twins a caller may use,
+// declared and described in cape_host_map.h: the first answers the frames cape_match_map flags, the second those the matchers of
+// consecutive frames flag, the third decides which map planes cape_match_map visits, the fourth is the map update, which runs on the
+// host only, the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -325,6 +326,66 @@ extern "C" int cape_host_match_map(const cape_host_map* map, const cape_host_pla
             match[j] = selected;
             matched[selected] = 1;
             map_of[selected] = j;
+        }
+        return 0;
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
+}
+
+// The twin of the consecutive-frame matchers (cape_host_map.h): the statements of cape_match_polygons_pose's three kernels in
+// the order of map_primitive.cpp:91-161, frame f-1's kept planes as the map planes.
+extern "C" int cape_host_match_planes(const cape_host_planes* prev, const cape_host_planes* cur, const double* prev_to_cur16, uint32_t flags,
+                                      int32_t* match, double* inter_area)
+{
+    if (!prev || !cur || prev->n < 0 || cur->n < 0 || (prev->n > 0 && !match) || (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const double* T = prev_to_cur16;
+    const double minCos = std::abs(std::cos(20.0 * M_PI / 180.0)); // parameters.hpp:92-93, shape_primitives.cpp:72-73
+    const double maxDistance = 100.0;                              // parameters.hpp:94-95
+    const double overlap = (flags & CAPE_MATCH_ADVANCED) ? static_cast<double>(0.4f) / 2 : static_cast<double>(0.4f);
+    const int32_t n_prev = prev->n, n_cur = cur->n;
+    try
+    {
+        std::vector<Polygon> map, det;
+        if (!kept_polygons(*prev, 0, map) || !kept_polygons(*cur, 0, det))
+            return CAPE_ERR_INVALID_ARGUMENT;
+        std::vector<char> matched(n_cur, 0);
+        std::fill_n(match, n_prev, -1);
+        if (inter_area)
+            std::fill_n(inter_area, (size_t)n_prev * n_cur, -1.0);
+        for (int32_t j = 0; j < n_prev; ++j)
+        {
+            double pn[3] = {prev->planes[4 * j], prev->planes[4 * j + 1], prev->planes[4 * j + 2]}, pd = prev->planes[4 * j + 3];
+            if (T)
+                rgbd_slam::utils::plane_to_camera(prev->planes + 4 * j, prev->planes[4 * j + 3], T, pn, &pd);
+            const Polygon projected = T ? map[j].to_camera_space(T) : map[j];
+            const double projectedArea = prev->areas ? prev->areas[j] : map[j].get_area();
+            int selected = -1;
+            double greatest = 0.0;
+            for (int32_t i = 0; i < n_cur; ++i)
+            {
+                const double* dn = cur->planes + 4 * i;
+                const double cosAngle = (dn[0] * pn[0] + dn[1] * pn[1]) + dn[2] * pn[2];
+                if (!(std::abs(dn[3] - pd) < maxDistance) || !(std::abs(cosAngle) > minCos))
+                    continue;
+                const double ia = det[i].inter_area(projected);
+                if (inter_area)
+                    inter_area[(size_t)j * n_cur + i] = ia;
+                if (matched[i] || !(projectedArea > 0.0))
+                    continue;
+                if (ia > greatest && ia / (cur->areas ? cur->areas[i] : det[i].get_area()) >= overlap)
+                {
+                    selected = i;
+                    greatest = ia;
+                }
+            }
+            if (selected < 0 || (selected == 0 && !(flags & CAPE_MATCH_ALLOW_INDEX0))) // map_primitive.cpp:146
+                continue;
+            match[j] = selected;
+            matched[selected] = 1;
         }
         return 0;
     }

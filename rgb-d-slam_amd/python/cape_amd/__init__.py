@@ -147,6 +147,10 @@ MATCH_EXACT_OVERFLOW = 1
 MATCH_EXACT_HOST = 2
 MATCH_EXACT_BAD_SHARD = 8  # match_map_shards only, next to MATCH_EXACT_OVERFLOW (4 is the input flag MATCH_MAP_AREAS)
 assert MATCH_EXACT_DTYPE.itemsize == 8 + 3 * 64 + 8 + 8 * 256
+# cape_match_polygons_wide: up to 128 kept planes per frame over its whole record chain
+MATCH_WIDE_MAX_PLANES = 128
+FRAME_MATCH_WIDE_DTYPE = np.dtype([("n_prev", "<i4"), ("n_cur", "<i4"), ("flags", "<u4"), ("n_matched", "<i4")], align=True)
+assert FRAME_MATCH_WIDE_DTYPE.itemsize == 16
 
 # N2 against a persistent map (cape_map_upload / cape_match_map)
 MAP_MAX_PLANES, MAP_MAX_RING, MAP_MAX_HOLES = 1024, 512, 8
@@ -226,6 +230,7 @@ def _host_library():
         L = C.CDLL(path)
         f64, i32, Map, Planes = (C.POINTER(t) for t in (C.c_double, C.c_int32, cape_host_map, cape_host_planes))
         L.cape_host_match_map.argtypes = [Map, Planes, f64, C.POINTER(C.c_uint32), C.c_uint32, i32, i32, f64]
+        L.cape_host_match_planes.argtypes = [Planes, Planes, f64, C.c_uint32, i32, f64]
         L.cape_host_map_update.argtypes = [Map, i32, Planes, f64, f64, C.c_uint32, C.POINTER(C.c_uint64), Map, i32]
         L.cape_host_map_visibility.argtypes = [Map, f64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -353,6 +358,40 @@ def host_match_map(map_arrays, detected, world_to_camera=None, skip=None, flags=
     return host_match_map_call(map_arrays, detected, world_to_camera, skip, flags, areas)()
 
 
+def host_match_planes(prev, cur, prev_to_cur=None, flags=0, areas=False):
+    """cape_host_match_planes of libcape_primitives.so: MapPlane::find_matches between two consecutive frames on the host class, with
+    no limit on the planes -- the twin of Extractor.match_polygons_wide / match_polygons_pose and the answer for a frame they flag
+    MATCH_EXACT_OVERFLOW.
+
+    prev, cur: the kept planes of frame f-1 and f as host_match_map takes its `detected` (Extractor.kept_planes gives them);
+    prev_to_cur: 4 x 4 (None: identity, the planes as they are).  Returns match[n_prev] or, with areas=True, (match,
+    inter_area[n_prev, n_cur])."""
+    return host_match_planes_call(prev, cur, prev_to_cur, flags, areas)()
+
+
+def host_match_planes_call(prev, cur, prev_to_cur=None, flags=0, areas=False):
+    """host_match_planes with the arguments packed now and the native call deferred (see host_match_map_call)."""
+    _host_library()
+    pcols, prev_view = _pack_detected(prev, with_cov=False)
+    ccols, cur_view = _pack_detected(cur, with_cov=False)
+    T = None if prev_to_cur is None else np.ascontiguousarray(prev_to_cur, np.float64).reshape(16)
+    n_prev, n_cur = len(prev), len(cur)
+    match = np.full(max(n_prev, 1), -1, np.int32)
+    inter = np.full((max(n_prev, 1), max(n_cur, 1)), -1.0) if areas else None
+    args = (C.byref(prev_view), C.byref(cur_view), _as(T, C.c_double), flags, _as(match, C.c_int32), _as(inter, C.c_double))
+    keep = (pcols, ccols, T)
+
+    def run():
+        """the native call alone (ctypes releases the GIL for its duration)"""
+        assert keep is not None
+        rc = _host_lib.cape_host_match_planes(*args)
+        if rc != 0:
+            raise CapeError(f"cape_host_match_planes failed ({rc})")
+        return (match[:n_prev], inter[:n_prev, :n_cur]) if areas else match[:n_prev]
+
+    return run
+
+
 def host_map_visibility(map_arrays, world_to_camera, width, height, fx, fy, cx, cy, moving=None):
     """cape_host_map_visibility of libcape_primitives.so: the skip words of ONE frame on the host class -- bit j set = map plane j
     is moving or MapPlane::is_visible(world_to_camera) is false.  The twin of Extractor.map_visibility, without its shortcut.
@@ -428,6 +467,7 @@ EXPORTED_SYMBOLS = [
     "cape_host_unregister", "cape_copy_cell_stats", "cape_enable_timing", "cape_get_timings",
     "cape_reset_timings", "cape_match_consecutive", "cape_device_matches", "cape_copy_matches",
     "cape_match_polygons", "cape_match_polygons_pose", "cape_copy_polygon_matches",
+    "cape_match_polygons_wide", "cape_copy_polygon_matches_wide",
     "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_shards", "cape_copy_shard_map_matches",
     "cape_map_visibility", "cape_copy_map_visibility",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
@@ -501,6 +541,8 @@ def load_library():
     L.cape_match_polygons.argtypes = [vp, C.c_int32, C.c_uint32, vp]
     L.cape_match_polygons_pose.argtypes = [vp, C.c_int32, vp, C.c_uint32, vp]
     L.cape_copy_polygon_matches.argtypes = [vp, C.c_int32, vp]
+    L.cape_match_polygons_wide.argtypes = [vp, C.c_int32, vp, C.c_uint32, vp]
+    L.cape_copy_polygon_matches_wide.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
     L.cape_map_upload.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64]
     L.cape_match_map.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, vp]
     L.cape_copy_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
@@ -767,6 +809,55 @@ class Extractor:
     def polygon_matches(self, n_frames):
         out = np.zeros(n_frames, MATCH_EXACT_DTYPE)
         _check(self.L, self.L.cape_copy_polygon_matches(self.h, n_frames, out.ctypes.data_as(C.c_void_p)), "cape_copy_polygon_matches")
+        return out
+
+    # ---- the same for frames of up to 128 kept planes over their whole record chains ----------------------
+    def match_polygons_wide(self, n_frames, prev_to_cur=None, flags=0, stream=0):
+        """cape_match_polygons_wide: match_polygons_pose for frames of up to MATCH_WIDE_MAX_PLANES kept planes, spill records
+        included.  prev_to_cur: n_frames x 4 x 4 (None: identity); flags: MATCH_ADVANCED, MATCH_ALLOW_INDEX0, MATCH_MAP_AREAS (keeps
+        the dense area table for polygon_matches_wide(areas=True))."""
+        T = None if prev_to_cur is None else np.ascontiguousarray(prev_to_cur, np.float64).reshape(n_frames, 16)
+        _check(self.L, self.L.cape_match_polygons_wide(self.h, n_frames, None if T is None else T.ctypes.data_as(C.c_void_p), flags,
+                                                       C.c_void_p(stream)), "cape_match_polygons_wide")
+
+    def polygon_matches_wide(self, n_frames, areas=False):
+        """(frames: FRAME_MATCH_WIDE_DTYPE[n_frames], match[n_frames, 128], seg_prev[n_frames, 128], seg_cur[n_frames, 128]) of the
+        last match_polygons_wide, + inter_area[n_frames, 128, 128] with areas=True (the call must have had MATCH_MAP_AREAS)."""
+        W = MATCH_WIDE_MAX_PLANES
+        frames = np.zeros(n_frames, FRAME_MATCH_WIDE_DTYPE)
+        match, seg_prev, seg_cur = (np.zeros((n_frames, W), np.int32) for _ in range(3))
+        inter = np.zeros((n_frames, W, W)) if areas else None
+        _check(self.L, self.L.cape_copy_polygon_matches_wide(self.h, n_frames, *(a.ctypes.data_as(C.c_void_p) for a in (frames, match, seg_prev, seg_cur)),
+                                                             None if inter is None else inter.ctypes.data_as(C.c_void_p)),
+               "cape_copy_polygon_matches_wide")
+        out = (frames, match, seg_prev, seg_cur)
+        return out + (inter,) if areas else out
+
+    def kept_planes(self, n_frames):
+        """Per frame of the last build_polygons: (detected, segments) -- the planes Primitive_Detection keeps over the frame's whole
+        record chain, in order, as host_match_planes / host_match_map take them ((normal, d, x_axis, y_axis, center, ring, area) per
+        plane), and each plane's position in the frame's segment list (FrameResults.segments)."""
+        res = self.results(n_frames, with_boundary=False)
+        pol, ver = self.polygons(n_frames)
+        spol = sver = None
+        if res.spill_records is not None:
+            spol, sver = self.spill_polygons(0, len(res.spill_records))
+        out = []
+        for f in range(n_frames):
+            detected, segments, base, rec_index = [], [], 0, f
+            for rec, _ in res.chain(f):
+                prow, vslab = (pol[f], ver[f]) if rec_index == f else (spol[rec_index - self.max_batch], sver[rec_index - self.max_batch])
+                n = min(CAPE_MAX_PLANES, max(0, int(rec["header"]["n_plane_segments"])))
+                for i in range(n):
+                    sg, p = rec["segments"][i], prow[i]
+                    if sg["is_output"] and (p["flags"] & POLY_VALID) and p["vertex_count"] >= 3:
+                        ring = vslab[p["vertex_offset"]: p["vertex_offset"] + p["vertex_count"]].copy()
+                        detected.append((sg["out_normal"].copy(), float(sg["d"]), p["x_axis"].copy(), p["y_axis"].copy(), p["center"].copy(),
+                                         ring, float(p["area"])))
+                        segments.append(base + i)
+                base += n
+                rec_index = int(rec["header"]["next_record"])
+            out.append((detected, segments))
         return out
 
     # ---- N2 against a persistent map (needs build_polygons of the batch first) -----------------------
