@@ -598,6 +598,46 @@ int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camer
  * of match / inter_area may be NULL.  Refuses more frames than the last cape_match_map covered. */
 int cape_copy_map_matches(cape_handle h, int32_t n_frames, cape_frame_map_match* frames, int32_t* match, double* inter_area);
 
+/* cape_match_map without its limit on the frame: the detected planes are the frame's kept planes in record order over its whole
+ * record chain (cape_frame_header.next_record), up to 128 -- the frames of more than 64 plane segments the general grow instance
+ * leaves in spill records, which cape_match_map flags.  Per pair and per frame the statements are cape_match_map's
+ * (MapPlane::find_matches, map_primitive.cpp:91-161, for map planes j = 0 .. n_map-1 in order, feature_map.hpp:638-697):
+ * plane_to_camera (plane_coordinates.cpp:20-24) and to_camera_space with holes (polygon_coordinates.cpp:135-165) through
+ * world_to_camera[f]; a projected area <= 0 matches nothing (map_primitive.cpp:105-106); the gates |delta d| < 100 mm,
+ * |cos| > cos 20 deg (shape_primitives.cpp:66-86) before any intersection; inter = I(detected, outer) - I(detected, hole_k) in order,
+ * clamped at 0; inter / area(detected) >= 0.4f, halved with CAPE_MATCH_ADVANCED (map_primitive.cpp:137-143); the lowest index on a
+ * tie; the `selectedIndex <= 0` quirk (map_primitive.cpp:146) unless CAPE_MATCH_ALLOW_INDEX0; the is-matched flags carried from map
+ * plane j to j + 1.  A frame both calls serve gets the same decisions and bit-identical areas from either.
+ * world_to_camera (n_frames x 16 doubles) and skip (n_frames x ceil(n_map / 32) words) as for cape_match_map: HOST memory, read
+ * before the call returns, NULL = identity / none skipped.  flags: CAPE_MATCH_ADVANCED, CAPE_MATCH_ALLOW_INDEX0,
+ * CAPE_MATCH_MAP_AREAS (the dense table [f][j][i] with 128 entries per map plane; CAPE_ERR_CAPACITY if n_frames x n_map x 128 x 8
+ * bytes would exceed 1 GiB) and CAPE_MATCH_MAP_DEVICE_SKIP (the words of the last cape_map_visibility; skip must be NULL).
+ * A frame is flagged CAPE_MATCH_EXACT_OVERFLOW -- no match reported, n_cur the true count -- only if its chain keeps more than 128
+ * planes, an output plane of the chain has CAPE_POLY_OVERFLOW, a pair exceeds the largest intersection tier, or its pairs do not fit
+ * the work list (16 777 216 gated pairs per call): cape_host_match_map (host/cape_host_map.h) answers for it.
+ * Needs cape_build_polygons of the same batch first.  The results live in buffers of the handle's own: cape_match_map /
+ * cape_copy_map_matches and this pair do not disturb each other's results; a cape_map_upload waits for a call in flight.
+ * CAPE_ERR_INVALID_ARGUMENT: NULL handle, negative n_frames, unknown flag, no map uploaded, a non-NULL skip together with
+ * CAPE_MATCH_MAP_DEVICE_SKIP; CAPE_ERR_CAPACITY: more frames than the last cape_build_polygons covered, the area table beyond 1 GiB,
+ * CAPE_MATCH_MAP_DEVICE_SKIP without a cape_map_visibility since the last cape_map_upload that covers n_frames.  An empty map
+ * succeeds with n_matched = 0.  Asynchronous on `stream`. */
+#define CAPE_MATCH_MAP_WIDE_MAX_PLANES CAPE_MATCH_WIDE_MAX_PLANES
+typedef struct cape_frame_map_match_wide
+{
+    int32_t n_map, n_cur;    /* map planes of the call / kept planes of the frame over its whole record chain */
+    uint32_t flags;          /* CAPE_MATCH_EXACT_OVERFLOW */
+    int32_t n_matched;       /* map planes that took a plane of this frame */
+} cape_frame_map_match_wide;
+int cape_match_map_wide(cape_handle h, int32_t n_frames, const double* world_to_camera, const uint32_t* skip, uint32_t flags, void* stream);
+/* Synchronous copy of the last cape_match_map_wide: frames (n_frames entries); match (n_frames x n_map, n_map being the map size of
+ * that call -- not of a map uploaded since): the kept plane matched to map plane j, or -1; seg_cur and map_of (n_frames x 128): kept
+ * plane i's position in the frame's concatenated segment list (the chain's records one after the other) and the map plane that took
+ * it, both -1 beyond n_cur; inter_area (n_frames x n_map x 128, [f][j][i] mm^2; -1 where the pair was not gated or the map plane was
+ * skipped / has no positive projected area, NaN: capacity; the call must have had CAPE_MATCH_MAP_AREAS, else
+ * CAPE_ERR_INVALID_ARGUMENT).  Any array may be NULL.  CAPE_ERR_CAPACITY: more frames than that call covered. */
+int cape_copy_map_matches_wide(cape_handle h, int32_t n_frames, cape_frame_map_match_wide* frames, int32_t* match, int32_t* seg_cur,
+                               int32_t* map_of, double* inter_area);
+
 /* cape_match_map for the frames of GATHERED SHARDS: what the rank that owns the map does with the world x bytes_per_rank bytes a
  * gather left in its device memory, without a host read of them.  shards_dev: n_shards shards of layout->bytes_per_rank bytes, rank
  * after rank, packed with CAPE_GATHER_POLYGONS -- the recv_dev of cape_gather_primitives[_root], or the slot cape_pack_primitives

@@ -70,20 +70,20 @@ int match_polygons_impl(cape_handle h, int32_t n_frames, const double* prev_to_c
     return CAPE_OK;
 }
 
-// the work buffers of cape_match_map, one allocation: counters, per-frame ranges, the gate masks, the work list, its areas, the
-// tier lists
+// the work buffers of cape_match_map, one allocation: counters, per-frame ranges, the gate masks (maskWords 64-bit words per map
+// plane: one for frames of up to 64 kept planes, two for cape_match_map_wide's 128), the work list, its areas, the tier lists
 struct MapWorkLayout
 {
     size_t counts, ranges, masks, work, area, tiers, total;
 };
-MapWorkLayout map_work_layout(int maxBatch, size_t cap)
+MapWorkLayout map_work_layout(int maxBatch, size_t cap, int maskWords = 1)
 {
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     MapWorkLayout l;
     l.counts = 0;
     l.ranges = up(16 * sizeof(unsigned));
     l.masks = l.ranges + up((size_t)maxBatch * sizeof(uint2));
-    l.work = l.masks + up((size_t)maxBatch * CAPE_MAP_MAX_PLANES * sizeof(unsigned long long));
+    l.work = l.masks + up((size_t)maxBatch * CAPE_MAP_MAX_PLANES * maskWords * sizeof(unsigned long long));
     l.area = l.work + up(cap * sizeof(unsigned long long));
     l.tiers = l.area + up(cap * sizeof(double));
     l.total = l.tiers + up(3 * cap * sizeof(unsigned));
@@ -637,6 +637,104 @@ int cape_copy_map_matches(cape_handle h, int32_t n_frames, cape_frame_map_match*
     CAPE_HIP_TRY(copy_out(frames, map.frames, 0, (size_t)n_frames));
     CAPE_HIP_TRY(copy_out(match, map.match, 0, n));
     CAPE_HIP_TRY(copy_out(inter_area, map.areas, 0, n * CAPE_MAX_PLANES));
+    return CAPE_OK;
+}
+
+int cape_match_map_wide(cape_handle h, int32_t n_frames, const double* world_to_camera, const uint32_t* skip, uint32_t flags, void* stream_)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    const auto& map = h->map;
+    auto& W = h->mapWide;
+    if (n_frames > h->poly.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
+    if (map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (flags & ~kMatchMapFlags)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
+    const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0;
+    const size_t areaDoubles = (size_t)n_frames * map.n * WP;
+    if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
+        return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer frames per call, or no CAPE_MATCH_MAP_AREAS)");
+    W.matchFrames = 0;
+    const uint32_t* deviceSkip = nullptr;
+    if (flags & CAPE_MATCH_MAP_DEVICE_SKIP)
+        if (const int rc = device_skip_words(h, n_frames, skip, &deviceSkip); rc != CAPE_OK)
+            return rc;
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    const int B = h->cfg.max_batch;
+    const int skipWords = (map.n + 31) / 32;
+    const size_t poseCapacity = (size_t)B * 16 * sizeof(double) + (size_t)B * (CAPE_MAP_MAX_PLANES / 32) * sizeof(uint32_t);
+    const size_t cap = std::min((size_t)B * (size_t)std::max(map.n, 1) * WP, kMapWorkMax);
+    const MapWorkLayout lay = map_work_layout(B, cap, 2);
+    CAPE_HIP_TRY(W.frames.ensure((size_t)B));
+    CAPE_HIP_TRY(W.match.ensure((size_t)B * CAPE_MAP_MAX_PLANES));
+    CAPE_HIP_TRY(W.planes.ensure(2 * (size_t)B * WP));
+    CAPE_HIP_TRY(W.kept.ensure((size_t)B * WP));
+    CAPE_HIP_TRY(W.poses.ensure(poseCapacity));
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them
+    CAPE_HIP_TRY(W.work.grow(lay.total, drain));
+    if (keepAreas)
+        CAPE_HIP_TRY(W.areas.grow(areaDoubles, drain));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    // the poses, then the skip bits, through the pinned twin as in cape_match_map
+    const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double);
+    const size_t skipBytes = skip ? (size_t)n_frames * skipWords * sizeof(uint32_t) : 0;
+    CAPE_HIP_TRY(W.posesTwin.upload(W.poses, poseBytes + skipBytes, poseCapacity, stream,
+                                    [&](void* stage) { fill_poses(stage, n_frames, world_to_camera, poseBytes, skip, skipBytes); }));
+    cape::MatchMapParams p;
+    p.records = h->res.records;
+    p.polygons = h->poly.polygons;
+    p.vertices = reinterpret_cast<const double2*>(h->poly.vertices.get());
+    p.boundaryCapacity = h->boundaryCap;
+    p.maxBatch = B;
+    p.nRecords = B + h->chain.spillRecords;
+    bind_map_call(p, h, W.work, lay, cap);
+    p.poses = reinterpret_cast<const double*>(W.poses.get());
+    p.skip = deviceSkip ? deviceSkip : skipBytes ? reinterpret_cast<const uint32_t*>(W.poses + poseBytes) : nullptr;
+    p.frames = nullptr;
+    p.framesWide = W.frames;
+    p.match = W.match;
+    p.segCur = W.planes;
+    p.mapOf = W.planes + (size_t)B * WP;
+    p.keptIndex = W.kept;
+    p.areas = keepAreas ? W.areas.get() : nullptr;
+    set_match_thresholds(p, flags);
+    CAPE_HIP_TRY(cape::launch_match_map_wide(p, n_frames, stream));
+    W.matchFrames = n_frames;
+    W.matchN = map.n;
+    W.matchAreas = keepAreas;
+    return CAPE_OK;
+}
+
+int cape_copy_map_matches_wide(cape_handle h, int32_t n_frames, cape_frame_map_match_wide* frames, int32_t* match, int32_t* seg_cur,
+                               int32_t* map_of, double* inter_area)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+    if (!h || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    const auto& W = h->mapWide;
+    if (n_frames > W.matchFrames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_match_map_wide of the current batch");
+    if (inter_area && n_frames > 0 && !W.matchAreas)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_match_map_wide did not keep the inter-area table (CAPE_MATCH_MAP_AREAS)");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    const size_t B = (size_t)h->cfg.max_batch, n = (size_t)n_frames * W.matchN;
+    CAPE_HIP_TRY(copy_out(frames, W.frames, 0, (size_t)n_frames));
+    CAPE_HIP_TRY(copy_out(match, W.match, 0, n));
+    CAPE_HIP_TRY(copy_out(seg_cur, W.planes, 0, (size_t)n_frames * WP));
+    CAPE_HIP_TRY(copy_out(map_of, W.planes, B * WP, (size_t)n_frames * WP));
+    CAPE_HIP_TRY(copy_out(inter_area, W.areas, 0, n * WP));
     return CAPE_OK;
 }
 

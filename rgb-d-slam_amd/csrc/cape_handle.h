@@ -29,6 +29,7 @@ hipError_t launch_pack(const PackParams& p, hipStream_t stream);
 hipError_t launch_polygons(const PolygonParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_polygons(const MatchPolygonParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_match_map_wide(const MatchMapParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_wide(const MatchWideParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
@@ -359,6 +360,24 @@ struct cape_handle_s
         int matchN = 0;                      // map planes of that call
         bool matchAreas = false;             // ... and whether it kept the dense table
     } map;
+
+    // cape_match_map_wide: the uploaded map against frames of up to CAPE_MATCH_MAP_WIDE_MAX_PLANES kept planes over their record
+    // chains.  Results and work buffers of its own, allocated on first use (the work list and the area table grown on demand behind
+    // drain_handle): cape_match_map's state above is not touched
+    struct MapWide
+    {
+        Buffer<unsigned char> poses; // the poses of the call (frames x 16 doubles), then its skip words
+        cape::abi::PinnedTwin posesTwin;
+        Buffer<cape_frame_map_match_wide> frames; // max_batch
+        Buffer<int32_t> match;                    // max_batch x CAPE_MAP_MAX_PLANES
+        Buffer<int32_t> planes;                   // max_batch x 128 seg_cur, then as many map_of
+        Buffer<uint2> kept;                       // max_batch x 128: MatchMapParams::keptIndex of the chain source
+        Buffer<double> areas;                     // CAPE_MATCH_MAP_AREAS: frames x n_map x 128 of the call
+        Buffer<unsigned char> work;               // map_work_layout with two mask words per map plane
+        int matchFrames = 0;                      // frames of the last cape_match_map_wide (0: none for the current batch)
+        int matchN = 0;                           // map planes of that call
+        bool matchAreas = false;                  // ... and whether it kept the dense table
+    } mapWide;
 
     // cape_match_map_shards: the uploaded map against gathered shards.  Results and work buffers of its own, sized by the call's
     // slots and grown on demand behind drain_handle -- nothing here depends on max_batch or on the batch of the last cape_extract,

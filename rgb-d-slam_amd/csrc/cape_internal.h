@@ -252,6 +252,14 @@ struct MatchMapParams
     int framesCapacity = 0, planesCapacity = 0, verticesCapacity = 0, cells = 0;                              // ... and what its header must say
     uint2* keptIndex = nullptr; // slots x CAPE_MAX_PLANES, written by the gate kernel: (packed plane = polygon index of kept plane i, the slot's
                                 // shard) -- one load tells the later kernels where the polygon lies, without dividing the slot by framesCapacity
+    // cape_match_map_wide: the detected planes are the kept planes of the frame's whole record chain, up to CAPE_MATCH_MAP_WIDE_MAX_PLANES
+    // = 128 of them.  records / polygons / vertices then cover the spill pool behind the batch and are indexed by the RECORD index;
+    // keptIndex is frames x 128, (record, segment in that record) of kept plane i; gateMasks holds two words per map plane, areas 128
+    // entries; `frames` is not written: the per-frame results go to framesWide / segCur / mapOf
+    int maxBatch = 0, nRecords = 0; // a link of a chain lies in [maxBatch, nRecords)
+    cape_frame_map_match_wide* framesWide = nullptr;
+    int32_t* segCur = nullptr; // frames x 128: position of kept plane i in the frame's concatenated segment list
+    int32_t* mapOf = nullptr;  // frames x 128: map plane that took kept plane i
 };
 
 // N2 between consecutive frames of up to CAPE_MATCH_WIDE_MAX_PLANES kept planes, record chains included (cape_match_wide.hip)

@@ -18,18 +18,30 @@
 //        the plane; wave arg-max of the area above the overlap threshold (lowest index on a tie), the `selectedIndex <= 0`
 //        quirk, the is-matched mask.
 //
-// The detected planes come from one of two SOURCES, a template parameter of the kernels (detected_polygon): the records and polygon
-// rows of the handle's last batch (cape_match_map), or gathered shards in device memory (cape_match_map_shards: the packed lists of
-// cape_gather.hip with CAPE_GATHER_POLYGONS, a "frame" being a slot shard x frames_capacity + k).  The shard source has a gate
+// The detected planes come from one of three SOURCES, a template parameter of the kernels (detected_polygon): the records and polygon
+// rows of the handle's last batch (cape_match_map), gathered shards in device memory (cape_match_map_shards: the packed lists of
+// cape_gather.hip with CAPE_GATHER_POLYGONS, a "frame" being a slot shard x frames_capacity + k), or the frame's whole record CHAIN
+// (cape_match_map_wide: up to 128 kept planes in record order, those of spill records included).  The shard source has a gate
 // kernel of its own, cape_map_gate_shards_kernel, which finds the kept planes among the frame's packed polygons and checks every
 // index it reads from the shard -- the bytes come from another process -- before the shared part of the gate kernels
-// (gate_kept_planes) takes over.
+// (gate_kept_planes) takes over.  The chain source has a gate and a select kernel of its own, twice as wide:
+//
+//   cape_map_gate_wide_kernel    : one wavefront per frame: the chain is walked into the frame's kept-plane table (walk_chain,
+//        cape_chain_walk.h), a lane holds kept planes k and k + 64; lanes over the map planes, 64 at a time, both gates on all
+//        n_map x n_cur pairs as a 128-bit mask per map plane, the projected polygon measured once per map plane with a gated pair,
+//        the triples appended in (j, i) order with one atomic per workgroup.
+//   cape_map_select_wide_kernel  : cape_map_select_kernel with runs of up to 128 gated pairs (two candidates per lane) and a
+//        128-bit is-matched mask.
+//
+// The intersection kernel is the same for the three: only the accessor differs.
 //
 // + - x / and comparisons only, in the host class's association order (-ffp-contract=off): the areas are compared BIT FOR BIT
 // with the host twin cape_host_match_map (tests/test_gpu_map_match.py).
 #include <hip/hip_runtime.h>
 
+#include "cape_chain_walk.h"
 #include "cape_internal.h"
+#include "cape_layout.h"
 #include "cape_map_camera.h"
 #include "cape_ring_area.h"
 #include "cape_wave.h"
@@ -41,6 +53,20 @@ namespace {
 constexpr int kMapGateFrames = 4;   // frames (waves) of a gate workgroup
 constexpr int kMapSelectFrames = 4; // frames (waves) of a select workgroup
 constexpr unsigned long long kNoEntry = ~0ull; // a slot of the work list reserved by a frame that did not fit
+constexpr int WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+static_assert(WP == 2 * 64, "a lane holds kept planes k and k + 64");
+// a triple is (frame << 32) | (j << 8) | i: i takes 8 bits, j the 24 above them
+static_assert(WP - 1 <= 0xFF && CAPE_MAX_PLANES - 1 <= 0xFF && CAPE_MAP_MAX_PLANES - 1 <= 0xFFFFFF, "the triple packing holds every (j, i)");
+
+// where the detected planes of a call come from
+enum MapSource
+{
+    kFromRecords, // the first record of each frame of the handle's batch (cape_match_map)
+    kFromShards,  // gathered shards (cape_match_map_shards)
+    kFromChain    // the frame's whole record chain (cape_match_map_wide)
+};
+// kept planes a frame of the source holds at most = entries per map plane of the dense area table
+template <MapSource kSource> constexpr int kSourcePlanes = kSource == kFromChain ? WP : CAPE_MAX_PLANES;
 
 __device__ __forceinline__ unsigned long long pack_map_pair(int frame, int j, int i)
 {
@@ -102,17 +128,23 @@ __device__ inline bool projected_area_positive(const double* Tm, const MatchMapP
 }
 
 // Kept plane i of a frame as the intersection and selection kernels see it: its polygon record and the vertex array its
-// vertex_offset counts in.  kShards false: the polygon row and vertex slab of the frame's record; true: the polygon and vertex
-// sections of the slot's shard, through the kept-plane table the shard gate kernel filled (and checked).
+// vertex_offset counts in.  kFromRecords: the polygon row and vertex slab of the frame's record; kFromShards: the polygon and vertex
+// sections of the slot's shard, through the kept-plane table the shard gate kernel filled (and checked); kFromChain: the polygon row
+// and vertex slab of the record the plane lives in, the batch's or a spill record, through the kept-plane table of the wide gate kernel.
 struct DetectedPolygon
 {
     const cape_polygon* polygon;
     const double2* vertices;
     __device__ __forceinline__ const double2* ring() const { return vertices + polygon->vertex_offset; }
 };
-template <bool kShards> __device__ __forceinline__ DetectedPolygon detected_polygon(const MatchMapParams& p, int frame, int i)
+template <MapSource kSource> __device__ __forceinline__ DetectedPolygon detected_polygon(const MatchMapParams& p, int frame, int i)
 {
-    if constexpr (kShards)
+    if constexpr (kSource == kFromChain)
+    {
+        const uint2 at = p.keptIndex[(size_t)frame * WP + i]; // (record, segment in that record)
+        return {p.polygons + (size_t)at.x * CAPE_MAX_PLANES + at.y, p.vertices + (size_t)at.x * p.boundaryCapacity};
+    }
+    else if constexpr (kSource == kFromShards)
     {
         const uint2 at = p.keptIndex[(size_t)frame * CAPE_MAX_PLANES + i]; // (packed index, shard)
         const unsigned char* shard = p.shards + (size_t)at.y * p.shardBytes;
@@ -338,10 +370,188 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_shards_kern
     gate_kept_planes(p, slot, live, nCur, !bad && !overflow, bad ? (uint32_t)CAPE_MATCH_EXACT_BAD_SHARD : 0u, seg, cn0, cn1, cn2, cd, s_count, s_base);
 }
 
+// ---- the LDS carve of a wide gate workgroup, in byte offsets: the reservation's hand-over words, then per wave the frame's
+// kept-plane table (location and position in the segment list)
+struct MapGateWideLayout
+{
+    size_t base, count, kept, seg, bytes;
+};
+__host__ __device__ constexpr MapGateWideLayout map_gate_wide_layout()
+{
+    Layout l;
+    MapGateWideLayout o{};
+    o.base = l.take<unsigned long long>(1);
+    o.count = l.take<unsigned>(kMapGateFrames);
+    o.kept = l.take<uint2>((size_t)kMapGateFrames * WP, 16);
+    o.seg = l.take<int>((size_t)kMapGateFrames * WP, 16);
+    o.bytes = l.end(16);
+    return o;
+}
+
+// The gate kernel of the chain source, one wavefront per frame: the chain is walked into the frame's kept-plane table, lane k reads
+// the normal and d of kept planes k and k + 64 out of the segments of the records they live in; then lanes over the map planes (64
+// at a time) as in gate_kept_planes, the detected planes broadcast out of either half: bit i of a lane's mask pair = pair (j, i)
+// passes the gates.  Pass 1 counts the pairs (one atomic per workgroup reserves the frame's slots) and keeps the masks, pass 2
+// writes the triples in (j, i) order.  A frame that keeps more than WP planes, or one with a plane left to the host class, gates
+// nothing and is flagged with its true count.
+__global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_wide_kernel(MatchMapParams p, int nFrames)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr MapGateWideLayout lay = map_gate_wide_layout();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long& s_base = *carve_at<unsigned long long>(smem, lay.base);
+    unsigned* s_count = carve_at<unsigned>(smem, lay.count);
+    uint2* kept = carve_at<uint2>(smem, lay.kept) + (size_t)wave * WP;
+    int* segs = carve_at<int>(smem, lay.seg) + (size_t)wave * WP;
+    const int frameRaw = blockIdx.x * kMapGateFrames + wave;
+    const bool live = frameRaw < nFrames;
+    const int frame = live ? frameRaw : nFrames - 1; // (idle waves of the last workgroup shadow a real frame and store nothing)
+    bool hostOnly = false;
+    const RecordChains chains{p.records, p.polygons, p.maxBatch, p.nRecords};
+    const int nCurAll = walk_chain(chains, frame, lane, kept, segs, hostOnly);
+    CAPE_MP_SYNC(); // (the table is read by other lanes of the wave than wrote it)
+    const bool fits = nCurAll <= WP && !hostOnly;
+    const int nCur = nCurAll < WP ? nCurAll : WP;
+    // my planes' parametrisations, read once (lane k: kept planes k and k + 64)
+    double cn[2][3] = {{0, 0, 0}, {0, 0, 0}}, cd[2] = {0, 0};
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+    {
+        const int k = lane + 64 * s;
+        if (live)
+        {
+            const size_t at = (size_t)frame * WP + k;
+            p.keptIndex[at] = k < nCur ? kept[k] : make_uint2((unsigned)frame, 0u);
+            p.segCur[at] = k < nCur ? segs[k] : -1;
+            p.mapOf[at] = -1;
+        }
+        if (k < nCur)
+        {
+            const uint2 at = kept[k];
+            const cape_plane_segment& S = p.records[at.x].segments[at.y];
+            cn[s][0] = S.out_normal[0], cn[s][1] = S.out_normal[1], cn[s][2] = S.out_normal[2], cd[s] = S.d;
+        }
+    }
+    const double* T = p.poses + (size_t)frame * 16;
+    const uint32_t* skip = p.skip ? p.skip + (size_t)frame * p.skipWords : nullptr;
+    const int nLo = nCur < 64 ? nCur : 64;
+    // the gated detected planes of map plane j (lane's), as two masks over i: planes 0..63 and 64..127
+    auto gate = [&](int j, unsigned long long& m0, unsigned long long& m1) {
+        m0 = m1 = 0ull;
+        if (!fits || j >= p.nMap || (skip && ((skip[j >> 5] >> (j & 31)) & 1u)))
+            return;
+        double qn[3], qd;
+        plane_to_camera(T, p.mapPlanes[j], qn, qd);
+        for (int i = 0; i < nLo; ++i)
+        {
+            const double sn0 = readlane_f64(cn[0][0], i), sn1 = readlane_f64(cn[0][1], i), sn2 = readlane_f64(cn[0][2], i), sd = readlane_f64(cd[0], i);
+            const double cosAngle = (sn0 * qn[0] + sn1 * qn[1]) + sn2 * qn[2];
+            if (fabs(sd - qd) < p.maxDistance && fabs(cosAngle) > p.minCosAngle)
+                m0 |= 1ull << i;
+        }
+        for (int i = 64; i < nCur; ++i)
+        {
+            const double sn0 = readlane_f64(cn[1][0], i - 64), sn1 = readlane_f64(cn[1][1], i - 64), sn2 = readlane_f64(cn[1][2], i - 64),
+                         sd = readlane_f64(cd[1], i - 64);
+            const double cosAngle = (sn0 * qn[0] + sn1 * qn[1]) + sn2 * qn[2];
+            if (fabs(sd - qd) < p.maxDistance && fabs(cosAngle) > p.minCosAngle)
+                m1 |= 1ull << (i - 64);
+        }
+        // a map plane whose projected polygon has no positive area matches nothing (map_primitive.cpp:105-106): its pairs are not
+        // listed (their areas stay -1)
+        if ((m0 | m1) && !projected_area_positive(T, p, j))
+            m0 = m1 = 0ull;
+    };
+    unsigned long long* masks = p.gateMasks + (size_t)frame * p.nMap * 2; // [j][half of the detected planes]
+    unsigned myCount = 0;
+    for (int jb = 0; jb < p.nMap; jb += 64)
+    {
+        const int j = jb + lane;
+        unsigned long long m0, m1;
+        gate(j, m0, m1);
+        if (live && j < p.nMap)
+            masks[2 * j] = m0, masks[2 * j + 1] = m1;
+        myCount += (unsigned)wave_sum_i32(__popcll(m0) + __popcll(m1));
+    }
+    // ONE atomic per workgroup on the list's counter reserves the slots of its frames
+    if (lane == 0)
+        s_count[wave] = live ? myCount : 0u;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        unsigned total = 0;
+        for (int w = 0; w < kMapGateFrames; ++w)
+        {
+            const unsigned c = s_count[w];
+            s_count[w] = total;
+            total += c;
+        }
+        s_base = total ? atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)total) : 0ull;
+    }
+    __syncthreads();
+    if (!live)
+        return;
+    const unsigned long long first = s_base + s_count[wave];
+    const bool listed = first + myCount <= p.workCapacity;
+    if (lane == 0)
+    {
+        cape_frame_map_match_wide& out = p.framesWide[frame];
+        out.n_map = p.nMap;
+        out.n_cur = nCurAll;
+        out.flags = (fits && listed) ? 0u : (uint32_t)CAPE_MATCH_EXACT_OVERFLOW;
+        out.n_matched = 0;
+        p.frameRange[frame] = make_uint2((unsigned)(listed ? first : 0ull), listed ? myCount : 0u);
+    }
+    if (!listed)
+    {
+        // the slots the frame reserved inside the list are marked empty: the intersection kernel skips them
+        for (unsigned long long k = first + lane; k < first + myCount && k < p.workCapacity; k += 64)
+            p.work[k] = kNoEntry;
+    }
+    unsigned long long at = first;
+    for (int jb = 0; jb < p.nMap; jb += 64)
+    {
+        const int j = jb + lane;
+        const unsigned long long m0 = j < p.nMap ? masks[2 * j] : 0ull, m1 = j < p.nMap ? masks[2 * j + 1] : 0ull;
+        if (j < p.nMap)
+            p.match[(size_t)frame * p.nMap + j] = -1;
+        const int c = __popcll(m0) + __popcll(m1);
+        const int incl = wave_scan_i32(c);
+        if (listed)
+        {
+            unsigned long long w = at + (unsigned)(incl - c);
+            for (unsigned long long mm = m0; mm; mm &= mm - 1, ++w)
+            {
+                p.work[w] = pack_map_pair(frame, j, __ffsll((long long)mm) - 1);
+                p.workArea[w] = nan_code(kNanPending);
+            }
+            for (unsigned long long mm = m1; mm; mm &= mm - 1, ++w)
+            {
+                p.work[w] = pack_map_pair(frame, j, 64 + __ffsll((long long)mm) - 1);
+                p.workArea[w] = nan_code(kNanPending);
+            }
+        }
+        at += (unsigned)__builtin_amdgcn_readlane(incl, 63);
+        if (p.areas)
+        {
+            // the dense table: -1 where the pair is not gated (the intersection kernel overwrites the gated ones; a pair that is
+            // never intersected -- a frame beyond the list -- keeps the NaN)
+            const int rows = p.nMap - jb < 64 ? p.nMap - jb : 64;
+            for (int l = 0; l < rows; ++l)
+            {
+                const unsigned long long l0 = readlane_u64(m0, l), l1 = readlane_u64(m1, l);
+                double* row = p.areas + ((size_t)frame * p.nMap + jb + l) * WP;
+                row[lane] = ((l0 >> lane) & 1ull) ? nan_code(kNanPending) : -1.0;
+                row[lane + 64] = ((l1 >> lane) & 1ull) ? nan_code(kNanPending) : -1.0;
+            }
+        }
+    }
+}
+
 // Persistent waves over the work list (tier 0) or a tier's list of indices into it (tiers 1..3).  A triple beyond this tier's
 // capacities moves to the next tier's list when that one is larger in the resource that ran out; otherwise its area stays a NaN
 // that names the resource.
-template <int TIER, bool kShards>
+template <int TIER, MapSource kSource>
 __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inter_kernel(MatchMapParams p, int ldsPerWave)
 {
     using T = Tier<TIER>;
@@ -388,7 +598,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inte
         if (e == kNoEntry)
             continue;
         const int frame = (int)(e >> 32), j = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
-        const DetectedPolygon D = detected_polygon<kShards>(p, frame, i);
+        const DetectedPolygon D = detected_polygon<kSource>(p, frame, i);
         const cape_polygon& PS = *D.polygon; // detected polygon
         const cape_map_plane& M = p.mapPlanes[j];
         const int na = (int)PS.vertex_count, nRings = (int)M.ring_count;
@@ -496,7 +706,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inte
             {
                 p.workArea[idx] = result;
                 if (p.areas)
-                    p.areas[((size_t)frame * p.nMap + j) * CAPE_MAX_PLANES + i] = result;
+                    p.areas[((size_t)frame * p.nMap + j) * kSourcePlanes<kSource> + i] = result;
             }
         }
     }
@@ -504,7 +714,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inte
 
 // One wavefront per frame: the map planes in order, each with the contiguous run of its gated pairs (one run fits the wave: at
 // most 64 kept planes), lanes over the run.
-template <bool kShards> __global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_kernel(MatchMapParams p, int nFrames)
+template <MapSource kSource> __global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_kernel(MatchMapParams p, int nFrames)
 {
     const int lane = threadIdx.x & 63;
     const int frame = blockIdx.x * kMapSelectFrames + (threadIdx.x >> 6);
@@ -514,7 +724,7 @@ template <bool kShards> __global__ __launch_bounds__(64 * kMapSelectFrames) void
     if (out.flags & CAPE_MATCH_EXACT_OVERFLOW)
         return; // nothing was intersected
     const int nc = out.n_cur;
-    const double myArea = lane < nc ? detected_polygon<kShards>(p, frame, lane).polygon->area : 0.0; // detectedPolygon.get_area()
+    const double myArea = lane < nc ? detected_polygon<kSource>(p, frame, lane).polygon->area : 0.0; // detectedPolygon.get_area()
     const uint2 range = p.frameRange[frame];
     const unsigned begin = range.x, end = range.x + range.y;
     // a pair beyond the intersection kernel's capacities: no match is reported for the frame
@@ -565,14 +775,97 @@ template <bool kShards> __global__ __launch_bounds__(64 * kMapSelectFrames) void
     out.map_of[lane] = myMapOf;
 }
 
+// The select kernel of the chain source, one wavefront per frame: the map planes in order, each with the contiguous run of its gated
+// pairs (at most WP of them: two candidates per lane, at list positions at + lane and at + lane + 64).
+__global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_wide_kernel(MatchMapParams p, int nFrames)
+{
+    const int lane = threadIdx.x & 63;
+    const int frame = blockIdx.x * kMapSelectFrames + (threadIdx.x >> 6);
+    if (frame >= nFrames)
+        return;
+    cape_frame_map_match_wide& out = p.framesWide[frame];
+    if (out.flags & CAPE_MATCH_EXACT_OVERFLOW)
+        return; // nothing was intersected
+    const int nc = out.n_cur; // (<= WP: the frame is not flagged)
+    // detectedPolygon.get_area() of my two planes
+    const double curArea0 = lane < nc ? detected_polygon<kFromChain>(p, frame, lane).polygon->area : 0.0;
+    const double curArea1 = lane + 64 < nc ? detected_polygon<kFromChain>(p, frame, lane + 64).polygon->area : 0.0;
+    const uint2 range = p.frameRange[frame];
+    const unsigned begin = range.x, end = range.x + range.y;
+    // a pair beyond the intersection kernel's capacities: no match is reported for the frame
+    bool nan = false;
+    for (unsigned k = begin + lane; k < end; k += 64)
+        nan |= p.workArea[k] != p.workArea[k];
+    if (__any(nan))
+    {
+        if (lane == 0)
+            out.flags |= CAPE_MATCH_EXACT_OVERFLOW;
+        return;
+    }
+    unsigned long long takenLo = 0ull, takenHi = 0ull; // is-matched flags of the detected planes
+    int myMapOf0 = -1, myMapOf1 = -1, nMatched = 0;
+    for (unsigned at = begin; at < end;)
+    {
+        const unsigned k0 = at + lane, k1 = k0 + 64;
+        const bool valid0 = k0 < end, valid1 = k1 < end;
+        const unsigned long long e0 = valid0 ? p.work[k0] : 0ull, e1 = valid1 ? p.work[k1] : 0ull;
+        const double ia0 = valid0 ? p.workArea[k0] : -1.0, ia1 = valid1 ? p.workArea[k1] : -1.0;
+        const int jl0 = (int)((e0 >> 8) & 0xFFFFFFu), jl1 = (int)((e1 >> 8) & 0xFFFFFFu), i0 = (int)(e0 & 255u), i1 = (int)(e1 & 255u);
+        const int j = __builtin_amdgcn_readfirstlane(jl0); // (lane 0's first candidate is the head of the run)
+        const bool mine0 = valid0 && jl0 == j, mine1 = valid1 && jl1 == j;
+        const double lo0 = __shfl(curArea0, i0 & 63), hi0 = __shfl(curArea1, i0 & 63), lo1 = __shfl(curArea0, i1 & 63), hi1 = __shfl(curArea1, i1 & 63);
+        const double detArea0 = i0 < 64 ? lo0 : hi0, detArea1 = i1 < 64 ? lo1 : hi1;
+        const bool taken0 = ((i0 < 64 ? takenLo >> i0 : takenHi >> (i0 - 64)) & 1ull) != 0ull;
+        const bool taken1 = ((i1 < 64 ? takenLo >> i1 : takenHi >> (i1 - 64)) & 1ull) != 0ull;
+        // interArea > greatestSimilarity (starting at 0) and interArea / newPlaneArea >= threshold (map_primitive.cpp:137-143); the
+        // run is in ascending i and the comparison strict: the lowest index among the largest areas
+        unsigned long long key0 = 0, key1 = 0;
+        if (mine0 && !taken0 && ia0 > 0.0 && ia0 / detArea0 >= p.minOverlap)
+            key0 = (unsigned long long)__double_as_longlong(ia0);
+        if (mine1 && !taken1 && ia1 > 0.0 && ia1 / detArea1 >= p.minOverlap)
+            key1 = (unsigned long long)__double_as_longlong(ia1);
+        const unsigned long long best = ~wave_min_u64(~(key0 > key1 ? key0 : key1)); // maximum of the bit patterns (positive doubles order like them)
+        // the winner's position in the run: my first candidate lies before every second one
+        const unsigned pos = (key0 != 0 && key0 == best) ? (unsigned)lane : ((key1 != 0 && key1 == best) ? (unsigned)lane + 64u : 0xFFFFFFFFu);
+        const unsigned win = wave_min_u32(pos);
+        int selected = -1;
+        if (best)
+            selected = win < 64u ? __builtin_amdgcn_readlane(i0, (int)win) : __builtin_amdgcn_readlane(i1, (int)win - 64);
+        if (!(p.flags & CAPE_MATCH_ALLOW_INDEX0) && selected <= 0) // map_primitive.cpp:146
+            selected = -1;
+        if (selected >= 0)
+        {
+            if (selected < 64)
+                takenLo |= 1ull << selected;
+            else
+                takenHi |= 1ull << (selected - 64);
+            ++nMatched;
+            if (lane == selected)
+                myMapOf0 = j;
+            if (lane + 64 == selected)
+                myMapOf1 = j;
+            if (lane == 0)
+                p.match[(size_t)frame * p.nMap + j] = selected;
+        }
+        at += (unsigned)(__popcll(__ballot(mine0)) + __popcll(__ballot(mine1)));
+    }
+    if (lane == 0)
+        out.n_matched = nMatched;
+    p.mapOf[(size_t)frame * WP + lane] = myMapOf0;
+    p.mapOf[(size_t)frame * WP + lane + 64] = myMapOf1;
+}
+
 namespace {
 
-template <bool kShards> hipError_t launch_match_map_from(const MatchMapParams& p, int nFrames, hipStream_t stream)
+template <MapSource kSource> hipError_t launch_match_map_from(const MatchMapParams& p, int nFrames, hipStream_t stream)
 {
     if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(kShards ? cape_map_gate_shards_kernel : cape_map_gate_kernel, dim3((nFrames + kMapGateFrames - 1) / kMapGateFrames),
-                       dim3(64 * kMapGateFrames), 0, stream, p, nFrames);
+    const dim3 gateGrid((nFrames + kMapGateFrames - 1) / kMapGateFrames), gateGroup(64 * kMapGateFrames);
+    if constexpr (kSource == kFromChain)
+        hipLaunchKernelGGL(cape_map_gate_wide_kernel, gateGrid, gateGroup, map_gate_wide_layout().bytes, stream, p, nFrames);
+    else
+        hipLaunchKernelGGL(kSource == kFromShards ? cape_map_gate_shards_kernel : cape_map_gate_kernel, gateGrid, gateGroup, 0, stream, p, nFrames);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
     // persistent grids: as many workgroups as the chip holds at once (the list's length is only known on the device)
@@ -581,17 +874,21 @@ template <bool kShards> hipError_t launch_match_map_from(const MatchMapParams& p
         hipLaunchKernelGGL(kernel, dim3(cus * groupsPerCu), dim3(64 * wavesPerGroup), (size_t)lds * (coop ? 1 : wavesPerGroup), stream, p, lds);
         return hipGetLastError();
     };
-    if (const hipError_t e = launch(cape_map_inter_kernel<0, kShards>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch(cape_map_inter_kernel<0, kSource>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_inter_kernel<1, kShards>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch(cape_map_inter_kernel<1, kSource>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_inter_kernel<2, kShards>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch(cape_map_inter_kernel<2, kSource>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
         return e;
     // (a device without the LDS for the largest tier leaves its triples NaN: their frames are flagged)
     if (tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes)
-        if (const hipError_t e = launch(cape_map_inter_kernel<3, kShards>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu); e != hipSuccess)
+        if (const hipError_t e = launch(cape_map_inter_kernel<3, kSource>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu); e != hipSuccess)
             return e;
-    hipLaunchKernelGGL(cape_map_select_kernel<kShards>, dim3((nFrames + kMapSelectFrames - 1) / kMapSelectFrames), dim3(64 * kMapSelectFrames), 0, stream, p, nFrames);
+    const dim3 selectGrid((nFrames + kMapSelectFrames - 1) / kMapSelectFrames), selectGroup(64 * kMapSelectFrames);
+    if constexpr (kSource == kFromChain)
+        hipLaunchKernelGGL(cape_map_select_wide_kernel, selectGrid, selectGroup, 0, stream, p, nFrames);
+    else
+        hipLaunchKernelGGL(cape_map_select_kernel<kSource>, selectGrid, selectGroup, 0, stream, p, nFrames);
     return hipGetLastError();
 }
 
@@ -600,7 +897,13 @@ template <bool kShards> hipError_t launch_match_map_from(const MatchMapParams& p
 // nFrames: frames of the handle's batch, or slots when p.shards is set (cape_match_map_shards)
 hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream)
 {
-    return p.shards ? launch_match_map_from<true>(p, nFrames, stream) : launch_match_map_from<false>(p, nFrames, stream);
+    return p.shards ? launch_match_map_from<kFromShards>(p, nFrames, stream) : launch_match_map_from<kFromRecords>(p, nFrames, stream);
+}
+
+// cape_match_map_wide: nFrames frames of the handle's batch, each over its whole record chain
+hipError_t launch_match_map_wide(const MatchMapParams& p, int nFrames, hipStream_t stream)
+{
+    return launch_match_map_from<kFromChain>(p, nFrames, stream);
 }
 
 } // namespace cape

@@ -6,8 +6,8 @@
 //
 //   cape_wide_gate_kernel        : one wavefront per frame: both chains are walked 64 segments at a time, a ballot of the kept ones plus
 //        the running count ranks them, and kept plane k's (record, segment in that record) goes into the frame's kept-plane table --
-//        what the later kernels resolve a plane through.  A lane holds planes k and k + 64 of either frame; the pose goes on the
-//        previous planes; all n_prev x n_cur pairs go through the gates is_distance_similar / is_normal_similar
+//        what the later kernels resolve a plane through (walk_chain, cape_chain_walk.h).  A lane holds planes k and k + 64 of
+//        either frame; the pose goes on the previous planes; all n_prev x n_cur pairs go through the gates is_distance_similar / is_normal_similar
 //        (shape_primitives.cpp:66-86) and the gated (frame, j, i) triples are appended to a 64-bit work list, per frame in (j, i)
 //        order, with one atomic per workgroup on the list's counter.
 //   cape_wide_inter_kernel<TIER> : persistent waves over the work list (tier 0) or a tier's list of indices into it: the previous
@@ -23,6 +23,7 @@
 // cape_match_polygons_pose where both serve a frame and with the host twin cape_host_match_planes (tests/test_gpu_match_wide.py).
 #include <hip/hip_runtime.h>
 
+#include "cape_chain_walk.h"
 #include "cape_internal.h"
 #include "cape_layout.h"
 #include "cape_ring_area.h"
@@ -76,42 +77,6 @@ __device__ __forceinline__ KeptPolygon kept_polygon(const MatchWideParams& p, in
     return {p.polygons + (size_t)at.x * CAPE_MAX_PLANES + at.y, p.vertices + (size_t)at.x * p.boundaryCapacity};
 }
 
-// The kept planes of a frame (output plane whose polygon Primitive_Detection keeps: valid_planes' rule) over its record chain, in
-// record order: table[k] = (record, segment in it) and segs[k] = the position in the frame's concatenated segment list of kept
-// plane k < min(count, WP); returns the count.  hostOnly: an output plane of the chain has no device polygon (CAPE_POLY_OVERFLOW).
-// A link outside the spill pool ends the chain, and a chain is followed through at most as many links as the pool has records.
-__device__ __forceinline__ int walk_chain(const MatchWideParams& p, int frame, int lane, uint2* table, int* segs, bool& hostOnly)
-{
-    int kept = 0, segBase = 0, rec = frame;
-    bool overflow = false;
-    for (int hop = 0; hop <= p.nRecords - p.maxBatch; ++hop)
-    {
-        const cape_frame_record& R = p.records[rec];
-        const cape_polygon* pol = p.polygons + (size_t)rec * CAPE_MAX_PLANES;
-        int nSeg = R.header.n_plane_segments;
-        nSeg = nSeg < 0 ? 0 : (nSeg > CAPE_MAX_PLANES ? CAPE_MAX_PLANES : nSeg);
-        const bool isOut = lane < nSeg && R.segments[lane].is_output != 0;
-        const unsigned flags = isOut ? pol[lane].flags : 0u;
-        const bool ok = isOut && (flags & CAPE_POLY_VALID) != 0 && pol[lane].vertex_count >= 3;
-        overflow = overflow || __ballot(isOut && (flags & CAPE_POLY_OVERFLOW) != 0) != 0ull;
-        const unsigned long long m = __ballot(ok);
-        const int rank = kept + __popcll(m & ((1ull << lane) - 1ull));
-        if (ok && rank < WP)
-        {
-            table[rank] = make_uint2((unsigned)rec, (unsigned)lane);
-            segs[rank] = segBase + lane;
-        }
-        kept += __popcll(m);
-        segBase += nSeg;
-        const int next = R.header.next_record;
-        if (next < p.maxBatch || next >= p.nRecords)
-            break;
-        rec = next;
-    }
-    hostOnly = overflow;
-    return kept;
-}
-
 } // namespace
 
 __global__ __launch_bounds__(64 * kWideGateFrames) void cape_wide_gate_kernel(MatchWideParams p, int nFrames)
@@ -130,8 +95,9 @@ __global__ __launch_bounds__(64 * kWideGateFrames) void cape_wide_gate_kernel(Ma
     const bool live = frameRaw < nFrames;
     const int frame = live ? frameRaw : nFrames - 1; // (idle waves of the last workgroup shadow a real frame and store nothing)
     bool hostOnlyC = false, hostOnlyP = false;
-    const int nCurAll = walk_chain(p, frame, lane, keptC, segsC, hostOnlyC);
-    const int nPrevAll = frame > 0 ? walk_chain(p, frame - 1, lane, keptP, segsP, hostOnlyP) : 0;
+    const RecordChains chains{p.records, p.polygons, p.maxBatch, p.nRecords};
+    const int nCurAll = walk_chain(chains, frame, lane, keptC, segsC, hostOnlyC);
+    const int nPrevAll = frame > 0 ? walk_chain(chains, frame - 1, lane, keptP, segsP, hostOnlyP) : 0;
     CAPE_MP_SYNC(); // (the tables are read by other lanes of the wave than wrote them)
     const bool fits = nCurAll <= WP && nPrevAll <= WP && !hostOnlyC && !hostOnlyP;
     const int nCur = nCurAll < WP ? nCurAll : WP, nPrev = nPrevAll < WP ? nPrevAll : WP;

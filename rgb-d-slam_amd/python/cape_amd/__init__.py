@@ -151,6 +151,10 @@ assert MATCH_EXACT_DTYPE.itemsize == 8 + 3 * 64 + 8 + 8 * 256
 MATCH_WIDE_MAX_PLANES = 128
 FRAME_MATCH_WIDE_DTYPE = np.dtype([("n_prev", "<i4"), ("n_cur", "<i4"), ("flags", "<u4"), ("n_matched", "<i4")], align=True)
 assert FRAME_MATCH_WIDE_DTYPE.itemsize == 16
+# cape_match_map_wide: the map matcher for the same frames
+MATCH_MAP_WIDE_MAX_PLANES = MATCH_WIDE_MAX_PLANES
+FRAME_MAP_MATCH_WIDE_DTYPE = np.dtype([("n_map", "<i4"), ("n_cur", "<i4"), ("flags", "<u4"), ("n_matched", "<i4")], align=True)
+assert FRAME_MAP_MATCH_WIDE_DTYPE.itemsize == 16
 
 # N2 against a persistent map (cape_map_upload / cape_match_map)
 MAP_MAX_PLANES, MAP_MAX_RING, MAP_MAX_HOLES = 1024, 512, 8
@@ -468,7 +472,7 @@ EXPORTED_SYMBOLS = [
     "cape_reset_timings", "cape_match_consecutive", "cape_device_matches", "cape_copy_matches",
     "cape_match_polygons", "cape_match_polygons_pose", "cape_copy_polygon_matches",
     "cape_match_polygons_wide", "cape_copy_polygon_matches_wide",
-    "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_shards", "cape_copy_shard_map_matches",
+    "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_wide", "cape_copy_map_matches_wide", "cape_match_map_shards", "cape_copy_shard_map_matches",
     "cape_map_visibility", "cape_copy_map_visibility",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
@@ -546,6 +550,8 @@ def load_library():
     L.cape_map_upload.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64]
     L.cape_match_map.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, vp]
     L.cape_copy_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.cape_match_map_wide.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, vp]
+    L.cape_copy_map_matches_wide.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
     L.cape_match_map_shards.argtypes = [vp, vp, C.c_int32, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout), vp, vp,
                                         C.c_uint32, vp]
     L.cape_copy_shard_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
@@ -918,6 +924,33 @@ class Extractor:
         _check(self.L, self.L.cape_copy_map_matches(self.h, n_frames, frames.ctypes.data_as(C.c_void_p), match.ctypes.data_as(C.c_void_p),
                                                     None if inter is None else inter.ctypes.data_as(C.c_void_p)), "cape_copy_map_matches")
         out = (frames, match[:, :n_map])
+        return out + (inter[:, :n_map],) if areas else out
+
+    # ---- the same for frames of up to 128 kept planes over their whole record chains ----------------------
+    def match_map_wide(self, n_frames, world_to_camera=None, skip=None, flags=0, stream=0):
+        """cape_match_map_wide: match_map for frames of up to MATCH_MAP_WIDE_MAX_PLANES kept planes, spill records included (what
+        kept_planes lists).  world_to_camera, skip and flags as for match_map; the results are map_matches_wide's and leave
+        match_map's alone."""
+        T = None if world_to_camera is None else np.ascontiguousarray(world_to_camera, np.float64).reshape(n_frames, 16)
+        S = None if skip is None else np.ascontiguousarray(skip, np.uint32).reshape(n_frames, -1)
+        _check(self.L, self.L.cape_match_map_wide(self.h, n_frames, None if T is None else T.ctypes.data_as(C.c_void_p),
+                                                  None if S is None else S.ctypes.data_as(C.c_void_p), flags, C.c_void_p(stream)),
+               "cape_match_map_wide")
+        self.matched_map_wide_size = self.map_size  # what cape_copy_map_matches_wide writes: the map of THIS call
+
+    def map_matches_wide(self, n_frames, areas=False):
+        """(frames: FRAME_MAP_MATCH_WIDE_DTYPE[n_frames], match[n_frames, n_map], seg_cur[n_frames, 128], map_of[n_frames, 128]) of the
+        last match_map_wide, + inter_area[n_frames, n_map, 128] with areas=True (the call must have had MATCH_MAP_AREAS).  n_map is the
+        map size of that match_map_wide call."""
+        W, n_map = MATCH_MAP_WIDE_MAX_PLANES, getattr(self, "matched_map_wide_size", 0)
+        frames = np.zeros(n_frames, FRAME_MAP_MATCH_WIDE_DTYPE)
+        match = np.zeros((n_frames, max(n_map, 1)), np.int32)
+        seg_cur, map_of = (np.zeros((n_frames, W), np.int32) for _ in range(2))
+        inter = np.zeros((n_frames, max(n_map, 1), W)) if areas else None
+        _check(self.L, self.L.cape_copy_map_matches_wide(self.h, n_frames, *(a.ctypes.data_as(C.c_void_p) for a in (frames, match, seg_cur, map_of)),
+                                                         None if inter is None else inter.ctypes.data_as(C.c_void_p)),
+               "cape_copy_map_matches_wide")
+        out = (frames, match[:, :n_map], seg_cur, map_of)
         return out + (inter[:, :n_map],) if areas else out
 
     # ---- the same against gathered shards in device memory (the map owner's side of the multi-GPU gather) ----
