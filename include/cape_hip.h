@@ -517,7 +517,8 @@ int cape_copy_polygon_matches(cape_handle h, int32_t n_frames, cape_frame_match_
  * tie, the `selectedIndex <= 0` quirk and the is-matched flags carried from previous plane j to j + 1; a frame both calls serve
  * gets the same matches and bit-identical areas from either.  prev_to_cur as for cape_match_polygons_pose (n_frames x 16 doubles in
  * HOST memory, read before the call returns, entry 0 not read, NULL = identity).  flags: CAPE_MATCH_ADVANCED,
- * CAPE_MATCH_ALLOW_INDEX0 and CAPE_MATCH_MAP_AREAS, which keeps the dense area table (CAPE_ERR_CAPACITY if it would exceed 1 GiB).
+ * CAPE_MATCH_ALLOW_INDEX0, CAPE_MATCH_MAP_AREAS, which keeps the dense area table (CAPE_ERR_CAPACITY if it would exceed 1 GiB), and
+ * CAPE_MATCH_CARRY (below: frame 0's predecessor is the handle's carried frame, and entry 0 is read).
  * A frame is flagged CAPE_MATCH_EXACT_OVERFLOW, with all its matches -1, only if it or its predecessor keeps more than 128 planes,
  * an output plane of either chain has CAPE_POLY_OVERFLOW, a pair is beyond the largest intersection tier, or the frame's pairs do
  * not fit the work list (4 194 304 gated pairs per call): cape_host_match_planes (host/cape_host_map.h) answers for it.  Needs
@@ -538,6 +539,48 @@ int cape_match_polygons_wide(cape_handle h, int32_t n_frames, const double* prev
  * more frames than that call covered. */
 int cape_copy_polygon_matches_wide(cape_handle h, int32_t n_frames, cape_frame_match_wide* frames, int32_t* match, int32_t* seg_prev,
                                    int32_t* seg_cur, double* inter_area);
+
+/* The CARRIED FRAME of a handle: a compact, handle-owned device copy of what cape_match_polygons_wide reads of ONE frame when that
+ * frame plays the previous frame, so that a depth stream cut into batches (or served one frame per call on a one-frame handle) loses
+ * no frame pair at the cuts.  With CAPE_MATCH_CARRY the predecessor of frame 0 is the carried frame: prev_to_cur entry 0 IS read (it
+ * takes the carried frame's camera into frame 0's; NULL is still the identity for every frame), and frame 0 reports n_prev,
+ * seg_prev[0][j] (the position in the carried frame's segment list), match[0][j] and inter_area[0][j][i] exactly as it would as
+ * frame k of a batch that held both frames -- gates, to_camera_space and project, tiers, selection, the `selectedIndex <= 0` quirk
+ * and the is-matched flags are the same statements.  The carry is read, not consumed.  CAPE_ERR_CAPACITY when no frame is carried.
+ * Only cape_match_polygons_wide takes the bit: the 16-plane calls and the map matchers reject it as an unknown flag, and a pair whose
+ * frames live on different handles (a shard boundary) stays with cape_host_match_planes.
+ *
+ * Order of use for a stream: cape_extract -> cape_build_polygons -> cape_match_polygons_wide(CAPE_MATCH_CARRY) ->
+ * cape_match_carry_save(last frame) -> the next batch; the handle's one-stream rule orders the save behind the match and ahead of
+ * the next cape_extract. */
+enum
+{
+    CAPE_MATCH_CARRY = 1u << 5 /* cape_match_polygons_wide only */
+};
+typedef struct cape_match_carry_info_t
+{
+    int32_t valid;      /* 1: a frame is carried */
+    int32_t n_kept;     /* its kept planes over the whole record chain (the TRUE count, may exceed 128) */
+    uint32_t flags;     /* CAPE_MATCH_EXACT_OVERFLOW: more than 128 kept planes or an output plane with CAPE_POLY_OVERFLOW -- the frame
+                           that follows it is flagged, cape_host_match_planes answers */
+    int32_t n_vertices; /* ring vertices held (0 for a flagged carry: its rings are never read) */
+} cape_match_carry_info_t;
+/* Copies the kept planes of frame `frame` of the last cape_build_polygons, in kept-plane order over the frame's whole record chain:
+ * per kept plane out_normal and d, its position in the frame's concatenated segment list, its cape_polygon and its ring -- into
+ * buffers no other call writes, allocated on the first save.  The copy survives any later call on the handle (cape_extract,
+ * cape_build_polygons, any matcher) until the next save, cape_match_carry_clear or cape_destroy.  A frame that keeps more than 128
+ * planes, or has an output plane with CAPE_POLY_OVERFLOW, is carried as flagged: n_kept is the true count and the first 128 segment
+ * positions are kept, which is what the matcher keeps of such a predecessor inside a batch.
+ * The vertex store holds 128 x min(1024, boundary_capacity) vertices (16 bytes each, 2 MiB at most): at most 128 planes are carried,
+ * and a served ring has at most min(1024, boundary_capacity) vertices -- they are boundary points of its record's slab, and a plane of
+ * more than 1 024 boundary points is CAPE_POLY_OVERFLOW and has no ring.  No frame the matcher would serve is refused.
+ * Asynchronous on `stream`.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, negative frame; CAPE_ERR_CAPACITY: `frame` is not covered by
+ * the last cape_build_polygons of the current batch (the rule of cape_device_polygons). */
+int cape_match_carry_save(cape_handle h, int32_t frame, void* stream);
+/* Forgets the carried frame (the buffers stay allocated). */
+int cape_match_carry_clear(cape_handle h);
+/* Synchronous: waits for the handle's work and describes the carried frame (all zero when none is carried). */
+int cape_match_carry_info(cape_handle h, cape_match_carry_info_t* out);
 
 /* Row N2 against a persistent MAP (Feature_Map::get_matches, feature_map.hpp:638-697): which detected plane of each frame
  * belongs to which map plane.  The map planes live in world coordinates; their boundary polygons (grown over many frames by

@@ -175,6 +175,22 @@ WideWorkLayout wide_work_layout(int maxBatch, size_t cap)
 // entries of its work list at most (112 MB of buffers): the GATED pairs of a call, a few per kept plane -- 1 024 per frame of a
 // 4 096-frame batch, where a frame of 128 planes on a checkerboard of facets gates some hundreds; a frame beyond it is flagged
 constexpr size_t kWideWorkMax = (size_t)1 << 22;
+// the carried frame's buffers as the kernels take them.  A served ring has at most min(kPolyMaxPoints, boundary capacity) vertices
+// (boundary points of its record's slab; a plane of more is CAPE_POLY_OVERFLOW and has no ring) and at most 128 planes are carried:
+// the vertex store holds every frame the matcher would serve
+int carry_ring_capacity(const cape_handle_s* h) { return std::min(cape::kPolyMaxPoints, h->boundaryCap); }
+cape::MatchCarry bind_carry(const cape_handle_s* h)
+{
+    const auto& K = h->carry;
+    cape::MatchCarry c;
+    c.info = K.info;
+    c.planes = K.planes;
+    c.segs = K.segs;
+    c.polygons = K.polygons;
+    c.vertices = reinterpret_cast<double2*>(K.vertices.get());
+    c.ringCapacity = carry_ring_capacity(h);
+    return c;
+}
 constexpr uint32_t kMatchMapFlags = CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS | CAPE_MATCH_MAP_DEVICE_SKIP;
 bool unit_norm(const double* v) // double_equal(norm, 1) as to_camera_space requires (polygon_coordinates.cpp:144-151)
 {
@@ -405,9 +421,11 @@ int cape_match_polygons_wide(cape_handle h, int32_t n_frames, const double* prev
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
     if (n_frames > h->poly.frames)
         return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
-    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS))
+    if (flags & ~(uint32_t)(CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0 | CAPE_MATCH_MAP_AREAS | CAPE_MATCH_CARRY))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match flag");
-    const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0;
+    const bool keepAreas = (flags & CAPE_MATCH_MAP_AREAS) != 0, carried = (flags & CAPE_MATCH_CARRY) != 0;
+    if (carried && !h->carry.saved)
+        return fail(CAPE_ERR_CAPACITY, "CAPE_MATCH_CARRY: no frame is carried (cape_match_carry_save first)");
     const size_t areaDoubles = (size_t)n_frames * WP * WP;
     if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
         return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer frames per call, or no CAPE_MATCH_MAP_AREAS)");
@@ -435,7 +453,7 @@ int cape_match_polygons_wide(cape_handle h, int32_t n_frames, const double* prev
     if (prev_to_cur)
     {
         // through the pinned twin like cape_match_polygons_pose's: n_frames x 16 doubles in the caller's memory order, read before
-        // the call returns (entry 0 is never read)
+        // the call returns (entry 0 is read by a carried call only)
         const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double);
         CAPE_HIP_TRY(W.poses.ensure(B * 16));
         CAPE_HIP_TRY(W.posesTwin.upload(W.poses, poseBytes, B * 16 * sizeof(double), stream,
@@ -462,6 +480,8 @@ int cape_match_polygons_wide(cape_handle h, int32_t n_frames, const double* prev
     p.workCapacity = cap;
     p.computeUnits = h->computeUnits;
     p.ldsLimitBytes = h->ldsLimit;
+    if (carried)
+        p.carry = bind_carry(h);
     set_match_thresholds(p, flags);
     CAPE_HIP_TRY(cape::launch_match_wide(p, n_frames, stream));
     W.matchFrames = n_frames;
@@ -490,6 +510,62 @@ int cape_copy_polygon_matches_wide(cape_handle h, int32_t n_frames, cape_frame_m
     CAPE_HIP_TRY(copy_out(seg_prev, W.match, B * WP, n));
     CAPE_HIP_TRY(copy_out(seg_cur, W.match, 2 * B * WP, n));
     CAPE_HIP_TRY(copy_out(inter_area, W.areas, 0, n * WP));
+    return CAPE_OK;
+}
+
+int cape_match_carry_save(cape_handle h, int32_t frame, void* stream_)
+{
+    constexpr size_t WP = CAPE_MATCH_WIDE_MAX_PLANES;
+    if (!h || frame < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame");
+    if (frame >= h->poly.frames)
+        return fail(CAPE_ERR_CAPACITY, "the frame is not covered by the last cape_build_polygons of the current batch");
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    auto& K = h->carry;
+    CAPE_HIP_TRY(K.info.ensure(1));
+    CAPE_HIP_TRY(K.planes.ensure(WP * 4));
+    CAPE_HIP_TRY(K.segs.ensure(WP));
+    CAPE_HIP_TRY(K.polygons.ensure(WP));
+    CAPE_HIP_TRY(K.vertices.ensure(WP * (size_t)carry_ring_capacity(h) * 2));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    cape::CarrySaveParams p{};
+    p.records = h->res.records;
+    p.polygons = h->poly.polygons;
+    p.vertices = reinterpret_cast<const double2*>(h->poly.vertices.get());
+    p.boundaryCapacity = h->boundaryCap;
+    p.maxBatch = h->cfg.max_batch;
+    p.nRecords = h->cfg.max_batch + h->chain.spillRecords;
+    p.frame = frame;
+    p.carry = bind_carry(h);
+    K.saved = false; // (a launch that fails leaves no carry behind rather than half of one)
+    CAPE_HIP_TRY(cape::launch_carry_save(p, stream));
+    K.saved = true;
+    return CAPE_OK;
+}
+
+int cape_match_carry_clear(cape_handle h)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    h->carry.saved = false;
+    return CAPE_OK;
+}
+
+int cape_match_carry_info(cape_handle h, cape_match_carry_info_t* out)
+{
+    if (!h || !out)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument");
+    *out = cape_match_carry_info_t{};
+    if (!h->carry.saved)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(copy_out(out, h->carry.info, 0, 1));
+    out->valid = 1;
     return CAPE_OK;
 }
 

@@ -31,6 +31,7 @@ hipError_t launch_match_polygons(const MatchPolygonParams& p, int nFrames, hipSt
 hipError_t launch_match_map(const MatchMapParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_map_wide(const MatchMapParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_match_wide(const MatchWideParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_carry_save(const CarrySaveParams& p, hipStream_t stream);
 hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
@@ -342,6 +343,19 @@ struct cape_handle_s
         int matchFrames = 0;                  // frames of the last cape_match_polygons_wide (0: none for the current batch)
         bool matchAreas = false;              // ... and whether it kept the dense table
     } wide;
+
+    // cape_match_carry_save: the carried frame, what cape_match_polygons_wide(CAPE_MATCH_CARRY) reads as the predecessor of frame 0.
+    // Device memory (also on a one-frame handle), allocated on the first save; only the save kernel writes it, so it survives every
+    // other call on the handle
+    struct Carry
+    {
+        Buffer<cape_match_carry_info_t> info; // the save kernel's description of the frame
+        Buffer<double> planes;                // 128 x 4: out_normal, d
+        Buffer<int32_t> segs;                 // 128
+        Buffer<cape_polygon> polygons;        // 128, vertex_offset rebased into `vertices`
+        Buffer<double> vertices;              // 128 x min(kPolyMaxPoints, boundaryCap) x 2: the rings back to back
+        bool saved = false;                   // a frame is carried (cape_match_carry_clear: none)
+    } carry;
 
     // N2 against a persistent map (cape_map_upload / cape_match_map): the map sized at upload, the rest allocated on first use
     struct Map

@@ -262,6 +262,18 @@ struct MatchMapParams
     int32_t* mapOf = nullptr;  // frames x 128: map plane that took kept plane i
 };
 
+// The carried frame of a handle (cape_match_carry_save): what the wide matcher reads of one frame as a PREVIOUS frame, kept plane by
+// kept plane in kept-plane order, in device buffers of the handle that no other call writes
+struct MatchCarry
+{
+    cape_match_carry_info_t* info = nullptr; // written by the save kernel (its `valid` is the host's to report); null: no carry in use
+    double* planes = nullptr;                // CAPE_MATCH_WIDE_MAX_PLANES x 4: out_normal, d
+    int32_t* segs = nullptr;                 // CAPE_MATCH_WIDE_MAX_PLANES: position in the frame's concatenated segment list
+    cape_polygon* polygons = nullptr;        // CAPE_MATCH_WIDE_MAX_PLANES, vertex_offset rebased into `vertices` (the rings back to back)
+    double2* vertices = nullptr;             // CAPE_MATCH_WIDE_MAX_PLANES x ringCapacity
+    int ringCapacity = 0;                    // min(kPolyMaxPoints, boundary capacity): vertices of one served ring at most
+};
+
 // N2 between consecutive frames of up to CAPE_MATCH_WIDE_MAX_PLANES kept planes, record chains included (cape_match_wide.hip)
 struct MatchWideParams
 {
@@ -288,6 +300,19 @@ struct MatchWideParams
     int ldsLimitBytes;
     uint32_t flags;
     double minCosAngle, maxDistance, minOverlap; // as MatchParams
+    MatchCarry carry;                 // CAPE_MATCH_CARRY: the predecessor of frame 0 (carry.info null: frame 0 has none)
+};
+
+// what cape_match_carry_save reads (the sources of MatchWideParams) and where it puts it
+struct CarrySaveParams
+{
+    const cape_frame_record* records;
+    const cape_polygon* polygons;
+    const double2* vertices;
+    int boundaryCapacity;
+    int maxBatch, nRecords;
+    int frame;
+    MatchCarry carry;
 };
 
 // cape_map_visibility (cape_map_visibility.hip): bit j of frame f = map plane j is moving or not visible from the frame's camera

@@ -18,6 +18,9 @@
 //   cape_wide_select_kernel      : one wavefront per frame: the previous planes in order, each with the contiguous run of its gated
 //        pairs (at most 128: two candidates per lane); wave arg-max of the area above the overlap threshold, the lowest index on a
 //        tie, the `selectedIndex <= 0` quirk, a 128-bit is-matched mask.
+//   cape_wide_carry_save_kernel  : one wavefront: the kept planes of ONE frame -- parameters, segment positions, polygons, rings back
+//        to back -- into the handle's carried frame (cape_match_carry_save).  With CAPE_MATCH_CARRY the three kernels above take it
+//        for the previous frame of frame 0 (prev_plane, prev_polygon): a stream cut into batches loses no frame pair at the cuts.
 //
 // + - x / and comparisons only, in the host class's association order (-ffp-contract=off): the areas are compared BIT FOR BIT with
 // cape_match_polygons_pose where both serve a frame and with the host twin cape_host_match_planes (tests/test_gpu_match_wide.py).
@@ -77,7 +80,145 @@ __device__ __forceinline__ KeptPolygon kept_polygon(const MatchWideParams& p, in
     return {p.polygons + (size_t)at.x * CAPE_MAX_PLANES + at.y, p.vertices + (size_t)at.x * p.boundaryCapacity};
 }
 
+// ---- the PREVIOUS frame of `frame`: frame - 1 of the batch, or -- for frame 0 of a call with CAPE_MATCH_CARRY -- the handle's carried
+// frame (cape_wide_carry_save_kernel).  One accessor for the polygon and one for the plane's parameters; `frame` is uniform over the
+// wave in every caller, so the choice is a scalar branch.
+__device__ __forceinline__ bool prev_is_carried(const MatchWideParams& p, int frame) { return frame == 0 && p.carry.info != nullptr; }
+__device__ __forceinline__ KeptPolygon prev_polygon(const MatchWideParams& p, int frame, int j)
+{
+    if (prev_is_carried(p, frame))
+        return {p.carry.polygons + j, p.carry.vertices};
+    return kept_polygon(p, frame - 1, j);
+}
+struct PlaneParams
+{
+    double n0, n1, n2, d; // out_normal, d
+};
+// keptP: the previous frame's kept-plane table of the gate kernel (not read for a carried frame)
+__device__ __forceinline__ PlaneParams prev_plane(const MatchWideParams& p, int frame, int k, const uint2* keptP)
+{
+    if (prev_is_carried(p, frame))
+    {
+        const double* q = p.carry.planes + 4 * (size_t)k;
+        return {q[0], q[1], q[2], q[3]};
+    }
+    const uint2 at = keptP[k];
+    const cape_plane_segment& Q = p.records[at.x].segments[at.y];
+    return {Q.out_normal[0], Q.out_normal[1], Q.out_normal[2], Q.d};
+}
+// the carried frame as walk_chain describes a frame of the batch: its segment positions into `segs`, its true count, its flag
+__device__ __forceinline__ int load_carry(const MatchCarry& c, int lane, int* segs, bool& hostOnly)
+{
+    const int kept = c.info->n_kept;
+    hostOnly = (c.info->flags & CAPE_MATCH_EXACT_OVERFLOW) != 0u;
+    for (int k = lane; k < kept && k < WP; k += 64)
+        segs[k] = c.segs[k];
+    return kept;
+}
+
+// ---- the LDS carve of the save kernel's one wave: the frame's kept-plane table (walk_chain), then per kept plane the first vertex
+// of its ring in the source slab array and in the carry, whose last entry + 1 is the total
+struct CarrySaveLayout
+{
+    size_t kept, seg, src, dst, bytes;
+};
+__host__ __device__ constexpr CarrySaveLayout carry_save_layout()
+{
+    Layout l;
+    CarrySaveLayout o{};
+    o.kept = l.take<uint2>(WP, 16);
+    o.seg = l.take<int>(WP, 16);
+    o.src = l.take<unsigned long long>(WP, 16);
+    o.dst = l.take<int>(WP + 1, 16);
+    o.bytes = l.end(16);
+    return o;
+}
+
 } // namespace
+
+// cape_match_carry_save: ONE wavefront.  The chain walk and the ranks are the gate kernel's; a lane copies the parameters and the
+// polygon of kept planes k and k + 64, a wave prefix sum of the vertex counts places the rings back to back, and the whole wave copies
+// them, one vertex per lane and step over ALL rings (the plane of a vertex is found in the prefix sums).  Loads, stores and integer
+// arithmetic only: nothing here can differ from the host class.  A flagged frame keeps its count and its first WP segment positions.
+__global__ __launch_bounds__(64) void cape_wide_carry_save_kernel(CarrySaveParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr CarrySaveLayout lay = carry_save_layout();
+    const int lane = threadIdx.x;
+    uint2* kept = carve_at<uint2>(smem, lay.kept);
+    int* segs = carve_at<int>(smem, lay.seg);
+    unsigned long long* src = carve_at<unsigned long long>(smem, lay.src);
+    int* dst = carve_at<int>(smem, lay.dst);
+    const MatchCarry& c = p.carry;
+    bool hostOnly = false;
+    const RecordChains chains{p.records, p.polygons, p.maxBatch, p.nRecords};
+    const int nAll = walk_chain(chains, p.frame, lane, kept, segs, hostOnly);
+    CAPE_MP_SYNC(); // (the tables are read by other lanes of the wave than wrote them)
+    const int n = nAll < WP ? nAll : WP;
+    bool flagged = nAll > WP || hostOnly;
+    int count[2] = {0, 0};
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+    {
+        const int k = lane + 64 * s;
+        if (k < n)
+        {
+            c.segs[k] = segs[k];
+            const uint2 at = kept[k];
+            count[s] = (int)p.polygons[(size_t)at.x * CAPE_MAX_PLANES + at.y].vertex_count;
+        }
+    }
+    // a ring beyond the bound the store is sized by cannot come out of the polygon kernels; if one ever did, the frame is carried as
+    // flagged rather than written past the store
+    flagged = flagged || __any((unsigned)count[0] > (unsigned)c.ringCapacity || (unsigned)count[1] > (unsigned)c.ringCapacity);
+    if (flagged)
+        count[0] = count[1] = 0;
+    const int scan0 = wave_scan_i32(count[0]), scan1 = wave_scan_i32(count[1]);
+    const int total0 = __builtin_amdgcn_readlane(scan0, 63), total = total0 + __builtin_amdgcn_readlane(scan1, 63);
+    const int first[2] = {scan0 - count[0], total0 + scan1 - count[1]};
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+    {
+        const int k = lane + 64 * s;
+        dst[k] = k < n ? first[s] : total;
+        if (k < n && !flagged)
+        {
+            const uint2 at = kept[k];
+            const cape_plane_segment& S = p.records[at.x].segments[at.y];
+            double* q = c.planes + 4 * (size_t)k;
+            q[0] = S.out_normal[0], q[1] = S.out_normal[1], q[2] = S.out_normal[2], q[3] = S.d;
+            cape_polygon pol = p.polygons[(size_t)at.x * CAPE_MAX_PLANES + at.y];
+            src[k] = (unsigned long long)at.x * (unsigned long long)p.boundaryCapacity + pol.vertex_offset;
+            pol.vertex_offset = (uint32_t)first[s];
+            c.polygons[k] = pol;
+        }
+    }
+    if (lane == 0)
+    {
+        dst[WP] = total;
+        c.info->valid = 1;
+        c.info->n_kept = nAll;
+        c.info->flags = flagged ? (uint32_t)CAPE_MATCH_EXACT_OVERFLOW : 0u;
+        c.info->n_vertices = total;
+    }
+    CAPE_MP_SYNC();
+    // (total <= n x ringCapacity, the size of the store: every count passed the check above)
+    for (int v = lane; v < total; v += 64)
+    {
+        // the kept plane whose ring holds v: the last one whose first vertex is not beyond it (a kept plane has >= 3 vertices)
+        int lo = 0, hi = n - 1;
+        while (lo < hi)
+        {
+            const int mid = (lo + hi + 1) >> 1;
+            if (dst[mid] <= v)
+                lo = mid;
+            else
+                hi = mid - 1;
+        }
+        c.vertices[v] = p.vertices[src[lo] + (unsigned long long)(v - dst[lo])];
+    }
+}
+
 
 __global__ __launch_bounds__(64 * kWideGateFrames) void cape_wide_gate_kernel(MatchWideParams p, int nFrames)
 {
@@ -97,7 +238,11 @@ __global__ __launch_bounds__(64 * kWideGateFrames) void cape_wide_gate_kernel(Ma
     bool hostOnlyC = false, hostOnlyP = false;
     const RecordChains chains{p.records, p.polygons, p.maxBatch, p.nRecords};
     const int nCurAll = walk_chain(chains, frame, lane, keptC, segsC, hostOnlyC);
-    const int nPrevAll = frame > 0 ? walk_chain(chains, frame - 1, lane, keptP, segsP, hostOnlyP) : 0;
+    int nPrevAll = 0;
+    if (frame > 0)
+        nPrevAll = walk_chain(chains, frame - 1, lane, keptP, segsP, hostOnlyP);
+    else if (prev_is_carried(p, frame))
+        nPrevAll = load_carry(p.carry, lane, segsP, hostOnlyP);
     CAPE_MP_SYNC(); // (the tables are read by other lanes of the wave than wrote them)
     const bool fits = nCurAll <= WP && nPrevAll <= WP && !hostOnlyC && !hostOnlyP;
     const int nCur = nCurAll < WP ? nCurAll : WP, nPrev = nPrevAll < WP ? nPrevAll : WP;
@@ -121,11 +266,10 @@ __global__ __launch_bounds__(64 * kWideGateFrames) void cape_wide_gate_kernel(Ma
             const cape_plane_segment& S = p.records[at.x].segments[at.y];
             cn[s][0] = S.out_normal[0], cn[s][1] = S.out_normal[1], cn[s][2] = S.out_normal[2], cd[s] = S.d;
         }
-        if (k < nPrev)
+        if (k < nPrev) // (the parameters of a flagged carry are stale; its frame gates nothing: nGate below)
         {
-            const uint2 at = keptP[k];
-            const cape_plane_segment& Q = p.records[at.x].segments[at.y];
-            pn[s][0] = Q.out_normal[0], pn[s][1] = Q.out_normal[1], pn[s][2] = Q.out_normal[2], pd[s] = Q.d;
+            const PlaneParams Q = prev_plane(p, frame, k, keptP);
+            pn[s][0] = Q.n0, pn[s][1] = Q.n1, pn[s][2] = Q.n2, pd[s] = Q.d;
             if (p.poses)
             {
                 // the map plane seen from this frame's camera: PlaneWorldCoordinates::to_camera_coordinates (plane_coordinates.cpp:20-24)
@@ -292,7 +436,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_wide_int
         if (e == kNoEntry)
             continue;
         const int frame = (int)(e >> 32), j = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
-        const KeptPolygon D = kept_polygon(p, frame, i), Q = kept_polygon(p, frame - 1, j);
+        const KeptPolygon D = kept_polygon(p, frame, i), Q = prev_polygon(p, frame, j);
         const cape_polygon& PS = *D.polygon; // detected polygon
         const cape_polygon& PQ = *Q.polygon; // projected polygon
         const int na = (int)PS.vertex_count, nb = (int)PQ.vertex_count;
@@ -418,8 +562,8 @@ __global__ __launch_bounds__(64 * kWideSelectFrames) void cape_wide_select_kerne
     // detectedPolygon.get_area() / projectedPolygon.get_area() of my two planes of either frame
     const double curArea0 = lane < nc ? kept_polygon(p, frame, lane).polygon->area : 0.0;
     const double curArea1 = lane + 64 < nc ? kept_polygon(p, frame, lane + 64).polygon->area : 0.0;
-    const double prevArea0 = lane < npv ? kept_polygon(p, frame - 1, lane).polygon->area : 0.0;
-    const double prevArea1 = lane + 64 < npv ? kept_polygon(p, frame - 1, lane + 64).polygon->area : 0.0;
+    const double prevArea0 = lane < npv ? prev_polygon(p, frame, lane).polygon->area : 0.0;
+    const double prevArea1 = lane + 64 < npv ? prev_polygon(p, frame, lane + 64).polygon->area : 0.0;
     const uint2 range = p.frameRange[frame];
     const unsigned begin = range.x, end = range.x + range.y;
     // a pair beyond the intersection kernel's capacities: no match is reported for the frame
@@ -478,6 +622,12 @@ __global__ __launch_bounds__(64 * kWideSelectFrames) void cape_wide_select_kerne
     }
     if (lane == 0)
         out.n_matched = nMatched;
+}
+
+hipError_t launch_carry_save(const CarrySaveParams& p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cape_wide_carry_save_kernel, dim3(1), dim3(64), carry_save_layout().bytes, stream, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_match_wide(const MatchWideParams& p, int nFrames, hipStream_t stream)

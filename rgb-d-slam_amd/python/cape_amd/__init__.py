@@ -151,6 +151,13 @@ assert MATCH_EXACT_DTYPE.itemsize == 8 + 3 * 64 + 8 + 8 * 256
 MATCH_WIDE_MAX_PLANES = 128
 FRAME_MATCH_WIDE_DTYPE = np.dtype([("n_prev", "<i4"), ("n_cur", "<i4"), ("flags", "<u4"), ("n_matched", "<i4")], align=True)
 assert FRAME_MATCH_WIDE_DTYPE.itemsize == 16
+MATCH_CARRY = 32  # match_polygons_wide only: frame 0's predecessor is the handle's carried frame (Extractor.match_carry_save)
+
+
+class cape_match_carry_info_t(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("n_kept", C.c_int32), ("flags", C.c_uint32), ("n_vertices", C.c_int32)]
+
+
 # cape_match_map_wide: the map matcher for the same frames
 MATCH_MAP_WIDE_MAX_PLANES = MATCH_WIDE_MAX_PLANES
 FRAME_MAP_MATCH_WIDE_DTYPE = np.dtype([("n_map", "<i4"), ("n_cur", "<i4"), ("flags", "<u4"), ("n_matched", "<i4")], align=True)
@@ -472,6 +479,7 @@ EXPORTED_SYMBOLS = [
     "cape_reset_timings", "cape_match_consecutive", "cape_device_matches", "cape_copy_matches",
     "cape_match_polygons", "cape_match_polygons_pose", "cape_copy_polygon_matches",
     "cape_match_polygons_wide", "cape_copy_polygon_matches_wide",
+    "cape_match_carry_save", "cape_match_carry_clear", "cape_match_carry_info",
     "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_wide", "cape_copy_map_matches_wide", "cape_match_map_shards", "cape_copy_shard_map_matches",
     "cape_map_visibility", "cape_copy_map_visibility",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
@@ -547,6 +555,9 @@ def load_library():
     L.cape_copy_polygon_matches.argtypes = [vp, C.c_int32, vp]
     L.cape_match_polygons_wide.argtypes = [vp, C.c_int32, vp, C.c_uint32, vp]
     L.cape_copy_polygon_matches_wide.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.cape_match_carry_save.argtypes = [vp, C.c_int32, vp]
+    L.cape_match_carry_clear.argtypes = [vp]
+    L.cape_match_carry_info.argtypes = [vp, C.POINTER(cape_match_carry_info_t)]
     L.cape_map_upload.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64]
     L.cape_match_map.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, vp]
     L.cape_copy_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
@@ -821,7 +832,8 @@ class Extractor:
     def match_polygons_wide(self, n_frames, prev_to_cur=None, flags=0, stream=0):
         """cape_match_polygons_wide: match_polygons_pose for frames of up to MATCH_WIDE_MAX_PLANES kept planes, spill records
         included.  prev_to_cur: n_frames x 4 x 4 (None: identity); flags: MATCH_ADVANCED, MATCH_ALLOW_INDEX0, MATCH_MAP_AREAS (keeps
-        the dense area table for polygon_matches_wide(areas=True))."""
+        the dense area table for polygon_matches_wide(areas=True)) and MATCH_CARRY (frame 0's predecessor is the frame of the last
+        match_carry_save, and prev_to_cur[0] takes that frame's camera into frame 0's)."""
         T = None if prev_to_cur is None else np.ascontiguousarray(prev_to_cur, np.float64).reshape(n_frames, 16)
         _check(self.L, self.L.cape_match_polygons_wide(self.h, n_frames, None if T is None else T.ctypes.data_as(C.c_void_p), flags,
                                                        C.c_void_p(stream)), "cape_match_polygons_wide")
@@ -838,6 +850,21 @@ class Extractor:
                "cape_copy_polygon_matches_wide")
         out = (frames, match, seg_prev, seg_cur)
         return out + (inter,) if areas else out
+
+    def match_carry_save(self, frame, stream=0):
+        """cape_match_carry_save: frame `frame` of the last build_polygons becomes the handle's carried frame -- the predecessor of
+        frame 0 of every later match_polygons_wide(..., flags | MATCH_CARRY), whatever is extracted in between.  For a stream:
+        extract -> build_polygons -> match_polygons_wide(MATCH_CARRY) -> match_carry_save(last frame) -> the next batch."""
+        _check(self.L, self.L.cape_match_carry_save(self.h, frame, C.c_void_p(stream)), "cape_match_carry_save")
+
+    def match_carry_clear(self):
+        _check(self.L, self.L.cape_match_carry_clear(self.h), "cape_match_carry_clear")
+
+    def match_carry_info(self):
+        """dict(valid, n_kept, flags, n_vertices) of the carried frame (all zero: none); waits for the handle's work."""
+        info = cape_match_carry_info_t()
+        _check(self.L, self.L.cape_match_carry_info(self.h, C.byref(info)), "cape_match_carry_info")
+        return {name: int(getattr(info, name)) for name, _ in info._fields_}
 
     def kept_planes(self, n_frames):
         """Per frame of the last build_polygons: (detected, segments) -- the planes Primitive_Detection keeps over the frame's whole
