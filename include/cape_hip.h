@@ -750,6 +750,59 @@ enum
                                             covered fewer frames / slots than this call */
 };
 
+/* The MEASUREMENT half of the map update on the device: what MapPlane::update_with_match computes of a matched detection before
+ * its Kalman step, and the StagedMapPlane constructor of an unmatched one (host: cape_host_map_update, host/polygon_capi.cpp) --
+ * per kept plane of frames [0, n_frames) of the last cape_build_polygons, over each frame's whole record chain and without a limit
+ * on the planes of a frame: plane_covariance of the detection (out_normal, d, the segment's cov), world_plane_covariance with the
+ * frame's pose T = camera_to_world[f] and pose covariance S = pose_covariance[f], the plane in world coordinates (plane_to_world),
+ * the polygon's frame and ring in world space (to_world_space's checks, then to_camera_space with T).  It reads neither the map nor
+ * a match and changes neither: the Kalman step, the counters and merge_union stay with cape_host_map_update.
+ * A segment is a kept plane when it is an output plane whose polygon has CAPE_POLY_VALID and >= 3 vertices (a CAPE_POLY_OVERFLOW
+ * polygon is not kept; the frame's other planes are served).  The rows are indexed like the polygon rows, [record][segment], the
+ * batch's records followed by the spill pool's; the world ring of a kept plane lies in the record's world-vertex slab at the
+ * cape_polygon's vertex_offset / vertex_count.  A row whose segment is not kept is all zero.  For a kept plane that fails a step,
+ * the flags name the first failing step and the fields that step and the later ones would have produced are 0 (its ring too).
+ * The world plane, the polygon frame and the ring are the host twin's bit for bit; the two covariances pass through pow(s, 3 / 2)
+ * (ocml's on the device, the C library's on the host) and agree to rounding (1e-12 relative in the tests). */
+enum
+{
+    CAPE_MEASURE_KEPT = 1u << 0,           /* the segment is a kept plane: the row is filled */
+    CAPE_MEASURE_STAGEABLE = 1u << 1,      /* every check passed and the ring has <= CAPE_MAP_MAX_RING vertices: cape_host_map_update
+                                              with CAPE_MAP_ADD_STAGED would append it */
+    CAPE_MEASURE_FAIL_PLANE_COV = 1u << 2, /* plane_covariance of the detection is false */
+    CAPE_MEASURE_FAIL_WORLD_COV = 1u << 3, /* world_plane_covariance is false */
+    CAPE_MEASURE_FAIL_POLYGON = 1u << 4,   /* to_world_space's checks, or staged_normal not unit */
+    CAPE_MEASURE_RING_TOO_LONG = 1u << 5,  /* more than CAPE_MAP_MAX_RING vertices: a measurement, not a map plane */
+    CAPE_MEASURE_BAD_POSE_COV = 1u << 6    /* the frame's pose covariance is not valid */
+};
+typedef struct cape_plane_measurement
+{
+    double normal[3], d;                    /* world plane = z of the Kalman step */
+    double staged_normal[3];                /* normal through one more normalisation: the staged plane's */
+    double covariance[16];                  /* world plane covariance, row-major = R of the Kalman step / the staged plane's covariance */
+    double x_axis[3], y_axis[3], center[3]; /* the world polygon's frame; its ring: the record's world-vertex slab at the
+                                               cape_polygon's vertex_offset / vertex_count */
+    uint32_t vertex_offset, vertex_count;   /* ... repeated here once the polygon step has passed (0 otherwise), so that the rows and
+                                               the world-vertex slabs can be read without the polygon rows */
+    uint32_t flags, pad;
+} cape_plane_measurement;                   /* 32 doubles + 16 bytes = 272 bytes */
+/* camera_to_world: n_frames x 16 doubles in HOST memory (row-major [R t; 0 0 0 1]), read before the call returns, NULL = identity;
+ * pose_covariance: n_frames x 9 doubles in HOST memory, required (the zero matrix is not a valid covariance).  A frame whose pose
+ * covariance is not valid (is_covariance_valid, as cape_host_map_update refuses it) has CAPE_MEASURE_KEPT | CAPE_MEASURE_BAD_POSE_COV
+ * on every kept plane and nothing else.  Needs cape_build_polygons of the same batch and no map.  Asynchronous on `stream`.  The
+ * results live in buffers of the handle's own (allocated on the first call) that no other call writes; a later cape_extract or
+ * cape_build_polygons invalidates them.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, negative n_frames, NULL pose_covariance;
+ * CAPE_ERR_CAPACITY: more frames than the last cape_build_polygons of the current batch covered. */
+int cape_map_measure(cape_handle h, int32_t n_frames, const double* camera_to_world, const double* pose_covariance, void* stream);
+/* Device pointers: rows = (max_batch + spill records) x CAPE_MAX_PLANES cape_plane_measurement, world_vertices = as many slabs of
+ * boundary_capacity x 2 doubles.  Either may be NULL.  CAPE_ERR_CAPACITY when no cape_map_measure has run on the current batch. */
+int cape_device_map_measurements(cape_handle h, cape_plane_measurement** rows, double** world_vertices);
+/* Synchronous copies, like cape_copy_polygons and cape_copy_spill_polygons (either pointer may be NULL): the rows and slabs of
+ * frames [0, n_frames) -- CAPE_ERR_CAPACITY beyond what the last cape_map_measure of the current batch covered -- and of spill
+ * records [first, first + count) -- CAPE_ERR_CAPACITY when no cape_map_measure has run on the current batch. */
+int cape_copy_map_measurements(cape_handle h, int32_t n_frames, cape_plane_measurement* rows, double* world_vertices);
+int cape_copy_spill_measurements(cape_handle h, int32_t first, int32_t count, cape_plane_measurement* rows, double* world_vertices);
+
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
  * the `stream` argument of the calls below; destroy it before the handle. */
@@ -890,11 +943,15 @@ int cape_reset_timings(cape_handle h);
 /* Debug / parity: evaluate device scalar math (f64 sqrt / div, ocml acos / atan2, the eigen-solver and plane fit)
  * on host operands so tests can compare gfx950 results with the CPU oracle bit for bit.  `a`,`b`,`out` are HOST
  * pointers; EIGEN3: a = n x 6 (m00 m10 m11 m20 m21 m22), out = n x 12 ; FIT_PLANE: a = n x 10 (9 sums, count),
- * out = n x 10 (normal[3], d, centroid[3], mse, score, planar). */
+ * out = n x 10 (normal[3], d, centroid[3], mse, score, planar).  The covariance algebra of cape_map_measure, one row of `a` per
+ * case: COV_VALID: a = n x 17 (size 3 or 4, then the matrix row-major in the first size x size of 16 entries), out = n x 1 (0 / 1) ;
+ * PLANE_COV: a = n x 13 (normal[3], d, cov[9]), out = n x 17 (ok, then 16 entries) ; WORLD_PLANE_COV: a = n x 45 (normal[3], d,
+ * camera_to_world[16], plane covariance[16], pose covariance[9]), out = n x 17 (ok, then 16 entries; all 0 when ok is 0). */
 enum
 {
     CAPE_DEBUG_SQRT = 0, CAPE_DEBUG_DIV = 1, CAPE_DEBUG_ACOS = 2, CAPE_DEBUG_ATAN2 = 3, CAPE_DEBUG_QUANT = 4,
-    CAPE_DEBUG_SQRTF = 5, CAPE_DEBUG_EIGEN3 = 6, CAPE_DEBUG_FIT_PLANE = 7
+    CAPE_DEBUG_SQRTF = 5, CAPE_DEBUG_EIGEN3 = 6, CAPE_DEBUG_FIT_PLANE = 7, CAPE_DEBUG_COV_VALID = 8, CAPE_DEBUG_PLANE_COV = 9,
+    CAPE_DEBUG_WORLD_PLANE_COV = 10
 };
 int cape_debug_eval(int op, const double* a, const double* b, double* out, int n);
 /* Debug: shader-clock ticks spent per phase of the grow kernel, n_frames x 32 (all zero unless the library was built

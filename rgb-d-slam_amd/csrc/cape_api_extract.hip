@@ -294,6 +294,7 @@ int extract_impl(cape_handle h, const float* depth_dev, const uint16_t* depth_u1
     h->map.matchFrames = 0;  // and the map matches
     h->wide.matchFrames = 0; // and the wide polygon matches
     h->mapWide.matchFrames = 0; // and the wide map matches
+    h->measure.frames = 0;      // and the measurements of its kept planes
     if (n_frames == 0)
         return CAPE_OK;
     CAPE_ON_DEVICE(h); // the handle's device, whatever the calling thread had current

@@ -385,6 +385,7 @@ int cape_build_polygons(cape_handle h, int32_t n_frames, void* stream_)
     CAPE_HIP_TRY(hipMemsetAsync(h->debugCycles + 6, 0xFF, 2 * 8, stream)); // the two minima of the task kernel's timeline
 #endif
     h->res.doneArmed = false; // the chain's completion word was written before this kernel: results are waited for the slow way
+    h->measure.frames = 0; // (the measurements index the polygons this call replaces)
     CAPE_HIP_TRY(cape::launch_polygons(p, n_frames, stream));
     P.frames = n_frames;
     return CAPE_OK;
@@ -1018,6 +1019,101 @@ int cape_copy_map_visibility(cape_handle h, int32_t n_frames, uint32_t* skip_out
         CAPE_HIP_TRY(hipMemcpy(&count, V.work.get() + 8 * sizeof(unsigned), sizeof(count), hipMemcpyDeviceToHost));
         *n_undecided = (int64_t)count;
     }
+    return CAPE_OK;
+}
+
+int cape_map_measure(cape_handle h, int32_t n_frames, const double* camera_to_world, const double* pose_covariance, void* stream_)
+{
+    if (!h || n_frames < 0 || !pose_covariance)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, negative frame count or no pose covariance (the zero matrix is not a valid covariance)");
+    if (n_frames > h->poly.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
+    auto& M = h->measure;
+    M.frames = 0;
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    const size_t B = (size_t)h->cfg.max_batch, nRecords = B + (size_t)h->chain.spillRecords; // a row / slab per record, spill pool included
+    const size_t slab = (size_t)h->boundaryCap * 2;
+    const bool fresh = !M.rows || !M.vertices;
+    CAPE_HIP_TRY(M.rows.ensure(nRecords * CAPE_MAX_PLANES));
+    CAPE_HIP_TRY(M.vertices.ensure(nRecords * slab));
+    CAPE_HIP_TRY(M.poses.ensure(B * 25));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    if (fresh)
+    {
+        // (rows and slabs of records outside the chains of a call's frames are never written: they read as zeros)
+        CAPE_HIP_TRY(hipMemsetAsync(M.rows, 0, nRecords * CAPE_MAX_PLANES * sizeof(cape_plane_measurement), stream));
+        CAPE_HIP_TRY(hipMemsetAsync(M.vertices, 0, nRecords * slab * sizeof(double), stream));
+    }
+    // the poses (the identity where none are given), then the pose covariances, through the pinned twin like cape_match_map_wide's
+    const size_t poseBytes = (size_t)n_frames * 16 * sizeof(double), covBytes = (size_t)n_frames * 9 * sizeof(double);
+    CAPE_HIP_TRY(M.posesTwin.upload(M.poses, poseBytes + covBytes, B * 25 * sizeof(double), stream, [&](void* stage) {
+        fill_poses(stage, n_frames, camera_to_world, poseBytes, nullptr, 0);
+        std::memcpy(static_cast<unsigned char*>(stage) + poseBytes, pose_covariance, covBytes);
+    }));
+    cape::MapMeasureParams p{};
+    p.records = h->res.records;
+    p.polygons = h->poly.polygons;
+    p.vertices = reinterpret_cast<const double2*>(h->poly.vertices.get());
+    p.boundaryCapacity = h->boundaryCap;
+    p.maxBatch = h->cfg.max_batch;
+    p.nRecords = (int)nRecords;
+    p.poses = M.poses;
+    p.poseCov = M.poses + (size_t)n_frames * 16;
+    p.rows = M.rows;
+    p.worldVertices = reinterpret_cast<double2*>(M.vertices.get());
+    CAPE_HIP_TRY(cape::launch_map_measure(p, n_frames, stream));
+    M.frames = n_frames;
+    return CAPE_OK;
+}
+
+int cape_device_map_measurements(cape_handle h, cape_plane_measurement** rows, double** world_vertices)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->measure.frames <= 0)
+        return fail(CAPE_ERR_CAPACITY, "no measurements of the current batch: cape_map_measure has not run since the last cape_build_polygons");
+    if (rows)
+        *rows = h->measure.rows;
+    if (world_vertices)
+        *world_vertices = h->measure.vertices;
+    return CAPE_OK;
+}
+
+int cape_copy_map_measurements(cape_handle h, int32_t n_frames, cape_plane_measurement* rows, double* world_vertices)
+{
+    if (!h || n_frames < 0 || n_frames > h->cfg.max_batch)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    const auto& M = h->measure;
+    if (n_frames > M.frames)
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_measure of the current batch");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    const size_t n = (size_t)n_frames;
+    CAPE_HIP_TRY(copy_out(rows, M.rows, 0, n * CAPE_MAX_PLANES));
+    CAPE_HIP_TRY(copy_out(world_vertices, M.vertices, 0, n * (size_t)h->boundaryCap * 2));
+    return CAPE_OK;
+}
+
+int cape_copy_spill_measurements(cape_handle h, int32_t first, int32_t count, cape_plane_measurement* rows, double* world_vertices)
+{
+    if (!h || first < 0 || count < 0 || first > h->chain.spillRecords || count > h->chain.spillRecords - first)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / spill record range");
+    const auto& M = h->measure;
+    if (M.frames <= 0)
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_measure has run on the current batch");
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    const size_t at = (size_t)h->cfg.max_batch + (size_t)first, n = (size_t)count, cap = (size_t)h->boundaryCap;
+    CAPE_HIP_TRY(copy_out(rows, M.rows, at * CAPE_MAX_PLANES, n * CAPE_MAX_PLANES));
+    CAPE_HIP_TRY(copy_out(world_vertices, M.vertices, at * cap * 2, n * cap * 2));
     return CAPE_OK;
 }
 

@@ -1,12 +1,14 @@
 // Debug / parity entry: evaluates device scalar math on caller-supplied operands so tests can compare the
 // gfx950 instruction sequences (f64 div / sqrt expansion, ocml acos / atan2, the restated eigen-solver and plane
-// fit) against the CPU oracle bit for bit.  Not on the hot path.
+// fit) against the CPU oracle bit for bit, and the covariance algebra of cape_map_tracking.h against its host twin
+// (decisions equal, values to rounding: it goes through pow).  Not on the hot path.
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "cape_device.h"
 #include "cape_internal.h"
+#include "cape_map_tracking.h"
 
 namespace cape {
 
@@ -51,6 +53,28 @@ __global__ void debug_eval_kernel(int op, const double* a, const double* b, doub
         o[7] = f.mse; o[8] = f.score; o[9] = f.planar ? 1.0 : 0.0;
         break;
     }
+    case CAPE_DEBUG_COV_VALID:
+    {
+        // a: n x 17 (size, then the matrix row-major in the first size x size entries) ; out: n x 1
+        const double* m = a + (size_t)i * 17;
+        out[i] = m[0] == 3.0 ? (is_covariance_valid<3>(m + 1) ? 1.0 : 0.0) : m[0] == 4.0 ? (is_covariance_valid<4>(m + 1) ? 1.0 : 0.0) : 0.0;
+        break;
+    }
+    case CAPE_DEBUG_PLANE_COV:
+    case CAPE_DEBUG_WORLD_PLANE_COV:
+    {
+        // a: n x 13 (normal, d, cov9) or n x 45 (normal, d, T16, planeCov16, pose9) ; out: n x 17 (ok, 16 entries: 0 unless ok)
+        const bool world = op == CAPE_DEBUG_WORLD_PLANE_COV;
+        const double* s = a + (size_t)i * (world ? 45 : 13);
+        double cov[16];
+        const bool ok = world ? world_plane_covariance(s, s[3], s + 4, s + 20, s + 36, cov) : plane_covariance(s, s[3], s + 4, cov);
+        double* o = out + (size_t)i * 17;
+        o[0] = ok ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            o[1 + k] = ok ? cov[k] : 0.0;
+        break;
+    }
     default: out[i] = 0.0;
     }
 }
@@ -67,6 +91,9 @@ extern "C" int cape_debug_eval(int op, const double* a, const double* b, double*
     size_t inW = 1, outW = 1;
     if (op == CAPE_DEBUG_EIGEN3) { inW = 6; outW = 12; }
     if (op == CAPE_DEBUG_FIT_PLANE) { inW = 10; outW = 10; }
+    if (op == CAPE_DEBUG_COV_VALID) { inW = 17; outW = 1; }
+    if (op == CAPE_DEBUG_PLANE_COV) { inW = 13; outW = 17; }
+    if (op == CAPE_DEBUG_WORLD_PLANE_COV) { inW = 45; outW = 17; }
     double *da = nullptr, *db = nullptr, *dout = nullptr;
     int rc = CAPE_OK;
     if (hipMalloc((void**)&da, n * inW * 8) != hipSuccess || hipMalloc((void**)&dout, n * outW * 8) != hipSuccess)

@@ -33,6 +33,7 @@ hipError_t launch_match_map_wide(const MatchMapParams& p, int nFrames, hipStream
 hipError_t launch_match_wide(const MatchWideParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_carry_save(const CarrySaveParams& p, hipStream_t stream);
 hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_measure(const MapMeasureParams& p, int nFrames, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -422,6 +423,18 @@ struct cape_handle_s
         int frames = 0;              // frames of the last cape_map_visibility on the current map (0: none since cape_map_upload)
         int n = 0;                   // map planes of that call
     } visibility;
+
+    // cape_map_measure: the measurement half of the map update for the kept planes of the last call's frames.  Device memory of its
+    // own, allocated on the first call: a row of CAPE_MAX_PLANES measurements and a world-vertex slab per record (the batch's, then the
+    // spill pool's), like the polygons they index.  No other call writes them
+    struct Measure
+    {
+        Buffer<double> poses; // the call's camera-to-world matrices (frames x 16), then its pose covariances (frames x 9)
+        cape::abi::PinnedTwin posesTwin;
+        Buffer<cape_plane_measurement> rows; // records x CAPE_MAX_PLANES
+        Buffer<double> vertices;             // records x boundary capacity x 2
+        int frames = 0;                      // frames of the last cape_map_measure (0: none for the current batch's polygons)
+    } measure;
 
     // Per-handle scratch (depth staging, rectify keys, hand-over feedback, result buffers) is reused from call to call
     // without per-buffer events: ONE stream is in flight per handle.  Every enqueueing call leaves a handle-owned event

@@ -336,6 +336,21 @@ struct MapVisibilityParams
     double width, height, fx, fy, cx, cy;
 };
 
+// cape_map_measure (cape_map_measure.hip): a measurement row per segment and a world-vertex slab per record, indexed like the polygons
+struct MapMeasureParams
+{
+    // what a chain walk reads (RecordChains, cape_chain_walk.h) and the camera rings
+    const cape_frame_record* records;
+    const cape_polygon* polygons; // records x CAPE_MAX_PLANES
+    const double2* vertices;      // records x boundaryCapacity
+    int boundaryCapacity;
+    int maxBatch, nRecords;
+    const double* poses;          // frames x 16: camera to world
+    const double* poseCov;        // frames x 9
+    cape_plane_measurement* rows; // records x CAPE_MAX_PLANES
+    double2* worldVertices;       // records x boundaryCapacity
+};
+
 // multi-GPU gather: device-side packing of the ragged primitive lists (cape_gather.hip)
 struct PackParams
 {

@@ -1,6 +1,7 @@
-// The map polygon seen from a frame's camera, shared by the map matcher (cape_match_map.hip) and the visibility kernels
-// (cape_map_visibility.hip): to_camera_space of the polygon's frame and of one ring vertex.  Both files compile their own copy
-// (anonymous namespace; no device symbol crosses a file).
+// The map polygon seen from a frame's camera, shared by the map matcher (cape_match_map.hip), the visibility kernels
+// (cape_map_visibility.hip) and -- with the camera-to-world matrix, a detected polygon carried to the world -- the measurement kernel
+// (cape_map_measure.hip): plane_to_camera of the plane, to_camera_space of the polygon's frame and of one ring vertex.  Every file
+// compiles its own copy (anonymous namespace; no device symbol crosses a file).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,22 @@ namespace cape {
 
 namespace {
 
+// A plane (normal, d) through a transform: PlaneWorldCoordinates::to_camera_coordinates with the plane matrix [R 0; -t^T R 1]
+// (camera_transformation.cpp:53-71); the PlaneCameraCoordinates constructor normalises the rotated normal (host:
+// utils::plane_to_camera).  With the camera-to-world matrix it is the host's plane_to_world (cape_map_measure.hip).
+__device__ __forceinline__ void plane_to_camera(const double* T, const double* normal, double d, double pn[3], double& pd)
+{
+    const double n0 = normal[0], n1 = normal[1], n2 = normal[2];
+    const double r0 = (T[0] * n0 + T[1] * n1) + T[2] * n2, r1 = (T[4] * n0 + T[5] * n1) + T[6] * n2, r2 = (T[8] * n0 + T[9] * n1) + T[10] * n2;
+    const double t0 = T[3], t1 = T[7], t2 = T[11];
+    const double m0 = -((t0 * T[0] + t1 * T[4]) + t2 * T[8]), m1 = -((t0 * T[1] + t1 * T[5]) + t2 * T[9]), m2 = -((t0 * T[2] + t1 * T[6]) + t2 * T[10]);
+    pd = ((m0 * n0 + m1 * n1) + m2 * n2) + d;
+    const double nn = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
+    pn[0] = r0, pn[1] = r1, pn[2] = r2;
+    if (nn > 0)
+        pn[0] = r0 / nn, pn[1] = r1 / nn, pn[2] = r2 / nn;
+}
+
 // to_camera_space of the map polygon's frame (polygon_coordinates.cpp:135-165): the centre through the transform, the axes through
 // its rotation, re-normalised -- the statements of the pose path of cape_match_polygon.hip
 struct CameraFrame
@@ -17,12 +34,12 @@ struct CameraFrame
     double qc[3], qx[3], qy[3]; // the map polygon's own frame
     double nc[3], nx[3], ny[3]; // ... seen from the camera
 };
-__device__ __forceinline__ CameraFrame camera_frame(const double* Tm, const cape_map_plane& M)
+__device__ __forceinline__ CameraFrame camera_frame(const double* Tm, const double* center, const double* xAxis, const double* yAxis)
 {
     CameraFrame F;
 #pragma unroll
     for (int r = 0; r < 3; ++r)
-        F.qc[r] = M.center[r], F.qx[r] = M.x_axis[r], F.qy[r] = M.y_axis[r];
+        F.qc[r] = center[r], F.qx[r] = xAxis[r], F.qy[r] = yAxis[r];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
     {
@@ -36,6 +53,10 @@ __device__ __forceinline__ CameraFrame camera_frame(const double* Tm, const cape
     if (ly > 0)
         F.ny[0] /= ly, F.ny[1] /= ly, F.ny[2] /= ly;
     return F;
+}
+__device__ __forceinline__ CameraFrame camera_frame(const double* Tm, const cape_map_plane& M)
+{
+    return camera_frame(Tm, M.center, M.x_axis, M.y_axis);
 }
 
 // one vertex of a map ring seen from the camera, in the camera-space frame (transform_boundary, polygon.cpp:430-451)

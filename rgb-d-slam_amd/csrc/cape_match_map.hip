@@ -73,19 +73,10 @@ __device__ __forceinline__ unsigned long long pack_map_pair(int frame, int j, in
     return ((unsigned long long)(unsigned)frame << 32) | ((unsigned long long)(unsigned)j << 8) | (unsigned long long)(unsigned)i;
 }
 
-// map plane j seen from the frame's camera: PlaneWorldCoordinates::to_camera_coordinates with the plane matrix [R 0; -t^T R 1]
-// (camera_transformation.cpp:53-71); the PlaneCameraCoordinates constructor normalises the rotated normal (host: utils::plane_to_camera)
+// map plane j seen from the frame's camera (plane_to_camera of cape_map_camera.h)
 __device__ __forceinline__ void plane_to_camera(const double* T, const cape_map_plane& M, double pn[3], double& pd)
 {
-    const double n0 = M.normal[0], n1 = M.normal[1], n2 = M.normal[2];
-    const double r0 = (T[0] * n0 + T[1] * n1) + T[2] * n2, r1 = (T[4] * n0 + T[5] * n1) + T[6] * n2, r2 = (T[8] * n0 + T[9] * n1) + T[10] * n2;
-    const double t0 = T[3], t1 = T[7], t2 = T[11];
-    const double m0 = -((t0 * T[0] + t1 * T[4]) + t2 * T[8]), m1 = -((t0 * T[1] + t1 * T[5]) + t2 * T[9]), m2 = -((t0 * T[2] + t1 * T[6]) + t2 * T[10]);
-    pd = ((m0 * n0 + m1 * n1) + m2 * n2) + M.d;
-    const double nn = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
-    pn[0] = r0, pn[1] = r1, pn[2] = r2;
-    if (nn > 0)
-        pn[0] = r0 / nn, pn[1] = r1 / nn, pn[2] = r2 / nn;
+    plane_to_camera(T, M.normal, M.d, pn, pd);
 }
 
 // Polygon::area of the map polygon seen from the camera > 0 (one lane, sequentially): the outer ring's |signed area| minus the

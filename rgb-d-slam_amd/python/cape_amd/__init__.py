@@ -176,6 +176,15 @@ FRAME_MAP_MATCH_DTYPE = np.dtype([
     ("map_of", "<i4", CAPE_MAX_PLANES)], align=True)
 assert MAP_PLANE_DTYPE.itemsize == 13 * 8 + 8 and MAP_RING_DTYPE.itemsize == 8 and FRAME_MAP_MATCH_DTYPE.itemsize == 16 + 8 * CAPE_MAX_PLANES
 
+# cape_map_measure: the measurement half of the map update, a row per segment of every record (cape_plane_measurement)
+PLANE_MEASUREMENT_DTYPE = np.dtype([
+    ("normal", "<f8", 3), ("d", "<f8"), ("staged_normal", "<f8", 3), ("covariance", "<f8", (4, 4)), ("x_axis", "<f8", 3),
+    ("y_axis", "<f8", 3), ("center", "<f8", 3), ("vertex_offset", "<u4"), ("vertex_count", "<u4"), ("flags", "<u4"), ("pad", "<u4")],
+    align=True)
+assert PLANE_MEASUREMENT_DTYPE.itemsize == 32 * 8 + 16 == 272
+(MEASURE_KEPT, MEASURE_STAGEABLE, MEASURE_FAIL_PLANE_COV, MEASURE_FAIL_WORLD_COV, MEASURE_FAIL_POLYGON, MEASURE_RING_TOO_LONG,
+ MEASURE_BAD_POSE_COV) = (1 << k for k in range(7))
+
 
 def pack_map(planes):
     """Map planes -> (MAP_PLANE_DTYPE array, MAP_RING_DTYPE array, vertices n x 2) for Extractor.upload_map / host_match_map.
@@ -200,7 +209,7 @@ def pack_map(planes):
 
 
 # cape_map_track (rgb-d-slam_amd/host/cape_host_map.h): the tracking state of a map plane, parallel to MAP_PLANE_DTYPE, for
-# host_map_update (the map update runs on the host only)
+# host_map_update (the map's state is updated on the host only; Extractor.map_measure computes a frame's measurements on the device)
 MAP_TRACK_DTYPE = np.dtype([
     ("covariance", "<f8", (4, 4)), ("successive_matched", "<i4"), ("failed_tracking", "<u4"), ("flags", "<u4"),
     ("result", "<u4"), ("id", "<u8")], align=True)
@@ -482,12 +491,13 @@ EXPORTED_SYMBOLS = [
     "cape_match_carry_save", "cape_match_carry_clear", "cape_match_carry_info",
     "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_wide", "cape_copy_map_matches_wide", "cape_match_map_shards", "cape_copy_shard_map_matches",
     "cape_map_visibility", "cape_copy_map_visibility",
+    "cape_map_measure", "cape_device_map_measurements", "cape_copy_map_measurements", "cape_copy_spill_measurements",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
     "cape_comm_info", "cape_abi_version", "cape_spill_info", "cape_copy_spill", "cape_copy_spill_polygons", "cape_get_timings_sized",
 ]
-DEBUG_OPS = dict(sqrt=0, div=1, acos=2, atan2=3, quant=4, sqrtf=5, eigen3=6, fit_plane=7)
+DEBUG_OPS = dict(sqrt=0, div=1, acos=2, atan2=3, quant=4, sqrtf=5, eigen3=6, fit_plane=7, cov_valid=8, plane_cov=9, world_plane_cov=10)
 
 _lib = None
 
@@ -568,6 +578,10 @@ def load_library():
     L.cape_copy_shard_map_matches.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.cape_map_visibility.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.cape_copy_map_visibility.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_int64)]
+    L.cape_map_measure.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.cape_device_map_measurements.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.cape_copy_map_measurements.argtypes = [vp, C.c_int32, vp, vp]
+    L.cape_copy_spill_measurements.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -893,6 +907,68 @@ class Extractor:
             out.append((detected, segments))
         return out
 
+    # ---- the measurement half of the map update (needs build_polygons of the batch first; no map) --------------
+    def map_measure(self, n_frames, camera_to_world, pose_covariance, stream=0):
+        """cape_map_measure: per kept plane of frames [0, n_frames), record chains included, the world plane, its 4 x 4 covariance
+        and the polygon in world space -- what update_with_match hands the Kalman step and what the StagedMapPlane constructor
+        stores.  camera_to_world: n_frames x 4 x 4 row-major [R t; 0 0 0 1] (None: identity); pose_covariance: n_frames x 3 x 3,
+        required.  The results are map_measurements'."""
+        T = None if camera_to_world is None else np.ascontiguousarray(camera_to_world, np.float64).reshape(n_frames, 16)
+        S = None if pose_covariance is None else np.ascontiguousarray(pose_covariance, np.float64).reshape(n_frames, 9)
+        _check(self.L, self.L.cape_map_measure(self.h, n_frames, None if T is None else T.ctypes.data_as(C.c_void_p),
+                                               None if S is None else S.ctypes.data_as(C.c_void_p), C.c_void_p(stream)), "cape_map_measure")
+
+    def measurement_rows(self, n_frames):
+        """(rows[n_frames, 64] PLANE_MEASUREMENT_DTYPE, world vertices[n_frames, boundary_capacity, 2]) of the last map_measure:
+        indexed like polygons()."""
+        rows = np.zeros((n_frames, CAPE_MAX_PLANES), PLANE_MEASUREMENT_DTYPE)
+        ver = np.zeros((n_frames, self.boundary_capacity, 2), np.float64)
+        _check(self.L, self.L.cape_copy_map_measurements(self.h, n_frames, rows.ctypes.data_as(C.c_void_p), ver.ctypes.data_as(C.c_void_p)),
+               "cape_copy_map_measurements")
+        return rows, ver
+
+    def spill_measurement_rows(self, first, count):
+        """the same for spill records [first, first + count): indexed like spill_polygons()."""
+        rows = np.zeros((count, CAPE_MAX_PLANES), PLANE_MEASUREMENT_DTYPE)
+        ver = np.zeros((count, self.boundary_capacity, 2), np.float64)
+        _check(self.L, self.L.cape_copy_spill_measurements(self.h, first, count, rows.ctypes.data_as(C.c_void_p), ver.ctypes.data_as(C.c_void_p)),
+               "cape_copy_spill_measurements")
+        return rows, ver
+
+    def map_measurements(self, n_frames):
+        """Per frame of the last map_measure: a list over the frame's whole record chain in kept-plane order (the order of
+        kept_planes), one dict per kept plane -- segment (its position in the frame's segment list), flags (MEASURE_*), normal, d,
+        staged_normal, covariance (4 x 4) and plane, the tuple (staged_normal, d, x_axis, y_axis, center, ring, []) that pack_map
+        takes.  A frame's stageable measurements go to the map with
+            planes = [m["plane"] for m in measurements[f] if m["flags"] & MEASURE_STAGEABLE]
+            ex.upload_map(pack_map(planes))"""
+        res = self.results(n_frames, with_boundary=False)
+        pol, _ = self.polygons(n_frames)
+        rows, ver = self.measurement_rows(n_frames)
+        spol = srows = sver = None
+        if res.spill_records is not None:
+            spol, _ = self.spill_polygons(0, len(res.spill_records))
+            srows, sver = self.spill_measurement_rows(0, len(res.spill_records))
+        out = []
+        for f in range(n_frames):
+            planes, base, rec_index = [], 0, f
+            for rec, _ in res.chain(f):
+                k = rec_index - self.max_batch
+                prow, mrow, vslab = (pol[f], rows[f], ver[f]) if rec_index == f else (spol[k], srows[k], sver[k])
+                n = min(CAPE_MAX_PLANES, max(0, int(rec["header"]["n_plane_segments"])))
+                for i in range(n):
+                    m, p = mrow[i], prow[i]
+                    if m["flags"] & MEASURE_KEPT:
+                        ring = vslab[p["vertex_offset"]: p["vertex_offset"] + p["vertex_count"]].copy()
+                        planes.append(dict(segment=base + i, flags=int(m["flags"]), normal=m["normal"].copy(), d=float(m["d"]),
+                                           staged_normal=m["staged_normal"].copy(), covariance=m["covariance"].copy(),
+                                           plane=(m["staged_normal"].copy(), float(m["d"]), m["x_axis"].copy(), m["y_axis"].copy(),
+                                                  m["center"].copy(), ring, [])))
+                base += n
+                rec_index = int(rec["header"]["next_record"])
+            out.append(planes)
+        return out
+
     # ---- N2 against a persistent map (needs build_polygons of the batch first) -----------------------
     def upload_map(self, planes, rings=None, vertices=None):
         """cape_map_upload: `planes` is either pack_map's triple, a MAP_PLANE_DTYPE array (with rings and vertices), or the list
@@ -1163,7 +1239,7 @@ def debug_eval(op, a, b=None):
     L = load_library()
     a = np.ascontiguousarray(a, np.float64)
     n = a.shape[0]
-    out_w = {"eigen3": 12, "fit_plane": 10}.get(op, 1)
+    out_w = {"eigen3": 12, "fit_plane": 10, "plane_cov": 17, "world_plane_cov": 17}.get(op, 1)
     out = np.zeros((n, out_w) if out_w > 1 else n, np.float64)
     bb = np.ascontiguousarray(b, np.float64) if b is not None else None
     _check(L, L.cape_debug_eval(DEBUG_OPS[op], a.ctypes.data_as(C.c_void_p),
