@@ -756,7 +756,7 @@ enum
  * on the planes of a frame: plane_covariance of the detection (out_normal, d, the segment's cov), world_plane_covariance with the
  * frame's pose T = camera_to_world[f] and pose covariance S = pose_covariance[f], the plane in world coordinates (plane_to_world),
  * the polygon's frame and ring in world space (to_world_space's checks, then to_camera_space with T).  It reads neither the map nor
- * a match and changes neither: the Kalman step, the counters and merge_union stay with cape_host_map_update.
+ * a match and changes neither: the Kalman step and the counters are cape_map_kalman's (below), merge_union stays with cape_host_map_update.
  * A segment is a kept plane when it is an output plane whose polygon has CAPE_POLY_VALID and >= 3 vertices (a CAPE_POLY_OVERFLOW
  * polygon is not kept; the frame's other planes are served).  The rows are indexed like the polygon rows, [record][segment], the
  * batch's records followed by the spill pool's; the world ring of a kept plane lies in the record's world-vertex slab at the
@@ -802,6 +802,127 @@ int cape_device_map_measurements(cape_handle h, cape_plane_measurement** rows, d
  * records [first, first + count) -- CAPE_ERR_CAPACITY when no cape_map_measure has run on the current batch. */
 int cape_copy_map_measurements(cape_handle h, int32_t n_frames, cape_plane_measurement* rows, double* world_vertices);
 int cape_copy_spill_measurements(cape_handle h, int32_t first, int32_t count, cape_plane_measurement* rows, double* world_vertices);
+
+/* Tracking state of one map plane, parallel to cape_map_plane: what Feature_Map::update_map (feature_map.hpp:367-384, :701-830)
+ * reads and changes besides the plane and its polygon.  Promotion from staged to local, removal from staged and the loss of a local
+ * plane reorder or delete entries of the ordered list: cape_host_map_update (host/cape_host_map.h) and cape_map_kalman report them
+ * in `result` and leave them to the caller. */
+typedef struct cape_map_track
+{
+    double covariance[16];      /* 4 x 4 covariance of (normal, d), row-major */
+    int32_t successive_matched; /* _successivMatchedCount (may go negative) */
+    uint32_t failed_tracking;   /* _failedTrackingCount */
+    uint32_t flags;             /* CAPE_MAP_TRACK_* */
+    uint32_t result;            /* CAPE_MAP_RESULT_* of the last update call (output) */
+    uint64_t id;                /* the caller's identifier; appended planes get consecutive ids from the update's next_id */
+} cape_map_track;
+enum
+{
+    CAPE_MAP_TRACK_STAGED = 1u << 0, /* a staged plane (StagedMapPlane): a match counts the detection as used even if the update fails */
+    CAPE_MAP_TRACK_MOVING = 1u << 1  /* is_moving(): informational here, the caller's skip bits of cape_match_map follow it */
+};
+enum
+{
+    CAPE_MAP_RESULT_MATCHED = 1u << 0,        /* a detected plane was matched to this map plane */
+    CAPE_MAP_RESULT_UPDATED = 1u << 1,        /* update_with_match returned true */
+    CAPE_MAP_RESULT_FAIL_DETECTION = 1u << 2, /* the detection's plane / world covariance is invalid: nothing changed */
+    CAPE_MAP_RESULT_FAIL_STATE = 1u << 3,     /* the map plane's covariance is invalid (the reference exits): nothing changed */
+    CAPE_MAP_RESULT_FAIL_SINGULAR = 1u << 4,  /* innovation determinant 0 within DBL_EPSILON, where the reference takes a
+                                                 pseudo-inverse: nothing changed.  Not reached with valid covariances: the
+                                                 detection's world covariance carries 0.01 on its diagonal, so the innovation's
+                                                 eigenvalues are >= 0.01 */
+    CAPE_MAP_RESULT_FAIL_KALMAN = 1u << 5,    /* the Kalman step produced an invalid covariance: nothing changed */
+    CAPE_MAP_RESULT_FAIL_POLYGON = 1u << 6,   /* update_boundary_polygon failed: the plane and covariance ARE updated, the polygon
+                                                 is the projected one or the old one.  Its isApprox centre check fails the update
+                                                 like the reference; a Polygon::project or to_world_space check, which throws inside
+                                                 the noexcept update_boundary_polygon there (std::terminate), fails it here too */
+    CAPE_MAP_RESULT_OVERFLOW = 1u << 7,       /* the merged polygon exceeds CAPE_MAP_MAX_RING / CAPE_MAP_MAX_HOLES after simplify:
+                                                 plane and covariance updated, the old polygon (and its frame) kept */
+    CAPE_MAP_RESULT_PROMOTE = 1u << 8,        /* staged, should_add_to_local_map (successive_matched >= 4) */
+    CAPE_MAP_RESULT_DROP = 1u << 9,           /* staged, not promoted, should_remove_from_staged (failed_tracking >= 2) */
+    CAPE_MAP_RESULT_LOST = 1u << 10,          /* local, is_lost (failed_tracking >= planeUnmatchedCountToLoose = 10) */
+    CAPE_MAP_RESULT_APPENDED = 1u << 11       /* a staged plane appended by this call */
+};
+
+/* The STATE half of the map update on the device, up to but not including the polygon union: per frame f of [0, n_frames) -- every
+ * frame against the uploaded map and the uploaded tracks, independently of the other frames, like cape_match_map_wide -- and per map
+ * plane j, the statements of cape_host_map_update (host/polygon_capi.cpp) that concern the plane's state, on the match of the last
+ * cape_match_map_wide and the rows of the last cape_map_measure.  Nothing is written into the map, the tracks, the matches or the
+ * measurements.  For a matched pair (j, i = match[f][j] >= 0), in the host's order and with its early exits:
+ *   CAPE_MAP_RESULT_MATCHED;
+ *   FAIL_DETECTION if kept plane i's measurement row carries CAPE_MEASURE_FAIL_PLANE_COV, CAPE_MEASURE_FAIL_WORLD_COV or
+ *     CAPE_MEASURE_BAD_POSE_COV (or is no kept plane's row).  The host refuses a whole frame with an invalid pose covariance; here
+ *     each of its matched planes fails this way and the frame's header carries CAPE_KALMAN_BAD_POSE_COV;
+ *   FAIL_STATE if is_covariance_valid of the track's covariance is false;
+ *   kalman_update (host/map_tracking.cpp) with x = the map plane's (normal, d), P = the track's covariance, z, R = the row's
+ *     (normal, d), covariance: FAIL_SINGULAR / FAIL_KALMAN as the host maps the status;
+ *   the new normal through normalize3 three times, the new d = x'[3], the new covariance;
+ *   the frame update_boundary_polygon projects into: | |n| - 1 | <= DBL_EPSILON, the axes of get_plane_coordinate_system(n) (whose
+ *     own 1e-9 norm check throws on the host and fails the polygon step here), the centre n x (-d);
+ *   the detection's polygon is usable iff the row lacks CAPE_MEASURE_FAIL_POLYGON -- the one rule that is coarser than
+ *     to_world_space's alone (the row's bit also covers the staged normal's unit check and a ring outside its slab);
+ *   with both CAPE_MAP_RESULT_UPDATED, otherwise FAIL_POLYGON; plane and covariance are the updated ones either way.
+ * merge_union never decides UPDATED on the host, so the bit is set without the union: merge_union, simplify and
+ * CAPE_MAP_RESULT_OVERFLOW stay with the host, which needs the fusion rows, the world rings of cape_map_measure and the map polygon
+ * for them.  For every map plane, matched or not: the counters after this frame (failed_tracking = 0, ++successive_matched on
+ * UPDATED, else ++failed_tracking, --successive_matched) and PROMOTE / DROP / LOST by the thresholds 4 / 2 / 10.  For every kept
+ * plane: used = matched and (UPDATED or the map plane is staged).
+ * Everything on this path is + - x / sqrt in the order of the host twin cape_host_map_kalman (host/cape_host_map.h), which it equals
+ * bit for bit when fed the same measurement rows. */
+enum
+{
+    CAPE_KALMAN_BAD_POSE_COV = 1u << 8 /* cape_frame_map_kalman.flags: a kept plane of the frame carries CAPE_MEASURE_BAD_POSE_COV */
+};
+enum
+{
+    CAPE_FUSION_USED = 1u << 0,  /* a map plane used this detection: an update with CAPE_MAP_ADD_STAGED does not append it */
+    CAPE_FUSION_STATE = 1u << 1, /* normal, d and covariance hold the matched map plane's new state (the Kalman step passed) */
+    CAPE_FUSION_FRAME = 1u << 2  /* x_axis, y_axis and center hold the frame the polygon step projects into */
+};
+typedef struct cape_frame_map_kalman
+{
+    int32_t n_map, n_cur; /* map planes of the call / kept planes of the frame (the wide match's) */
+    uint32_t flags;       /* CAPE_MATCH_EXACT_OVERFLOW of the wide match: the frame reports nothing, all its rows and track results are
+                             0 and cape_host_map_update answers; CAPE_KALMAN_BAD_POSE_COV */
+    int32_t n_updated;    /* map planes with CAPE_MAP_RESULT_UPDATED */
+} cape_frame_map_kalman;
+/* One row per kept plane i < 128 of a frame, all zero beyond n_cur.  A pair that failed a step keeps zeros in the fields that step
+ * and the later ones would have produced: without CAPE_FUSION_STATE normal, d, covariance and the frame are 0, without
+ * CAPE_FUSION_FRAME the frame is 0.  An unmatched kept plane has map_plane = -1 and nothing else. */
+typedef struct cape_plane_fusion
+{
+    double normal[3], d;                    /* the map plane's new parametrisation */
+    double covariance[16];                  /* ... and covariance, row-major */
+    double x_axis[3], y_axis[3], center[3]; /* the frame the map polygon and the detection are projected into before the union */
+    int32_t map_plane;                      /* the map plane that took this kept plane, or -1 */
+    uint32_t flags;                         /* CAPE_FUSION_* */
+} cape_plane_fusion;                        /* 29 doubles + 8 bytes = 240 bytes */
+typedef struct cape_map_track_result
+{
+    uint32_t result;            /* CAPE_MAP_RESULT_* without OVERFLOW and APPENDED */
+    int32_t successive_matched; /* the counters after this frame */
+    uint32_t failed_tracking;
+    int32_t kept_plane;         /* match[f][j]: the kept plane map plane j took, or -1 */
+} cape_map_track_result;
+/* What cape_map_kalman reads of the tracks, parallel to the planes of the last cape_map_upload: covariance, successive_matched,
+ * failed_tracking, flags.  Host pointer, synchronous.  n must equal the uploaded map's plane count.  A cape_map_upload discards the
+ * tracks (and waits for a call in flight).  CAPE_ERR_INVALID_ARGUMENT: NULL handle, no map uploaded, n other than the map's plane
+ * count, NULL tracks with n > 0. */
+int cape_map_upload_tracks(cape_handle h, const cape_map_track* tracks, int32_t n);
+/* Needs, on the current batch and covering n_frames: a cape_match_map_wide since the last cape_map_upload, a cape_map_measure, and
+ * the uploaded tracks -- otherwise CAPE_ERR_CAPACITY.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, n_frames < 0.  An empty map succeeds
+ * and writes frame headers only.  Kept plane i of frame f is resolved to its measurement row through the kept-plane table the wide
+ * match left on the handle; every index taken from it is checked against the row buffer before use.  Asynchronous on `stream`.  The
+ * results live in buffers of the handle's own, grown on demand, that no other call writes; a later cape_extract,
+ * cape_build_polygons, cape_map_upload, cape_match_map_wide or cape_map_measure invalidates them. */
+int cape_map_kalman(cape_handle h, int32_t n_frames, void* stream);
+/* Synchronous copy of the last cape_map_kalman: frames (n_frames entries), rows (n_frames x 128), track_results (n_frames x n_map,
+ * n_map being the map size of that call).  Any pointer may be NULL.  CAPE_ERR_CAPACITY beyond what the call covered. */
+int cape_copy_map_kalman(cape_handle h, int32_t n_frames, cape_frame_map_kalman* frames, cape_plane_fusion* rows,
+                         cape_map_track_result* track_results);
+/* Device pointers of the same arrays (rows: frames x 128; track_results: frames x n_map of the call).  Any may be NULL.
+ * CAPE_ERR_CAPACITY when no cape_map_kalman has run on the current batch, map and measurements. */
+int cape_device_map_kalman(cape_handle h, cape_frame_map_kalman** frames, cape_plane_fusion** rows, cape_map_track_result** track_results);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
@@ -946,12 +1067,15 @@ int cape_reset_timings(cape_handle h);
  * out = n x 10 (normal[3], d, centroid[3], mse, score, planar).  The covariance algebra of cape_map_measure, one row of `a` per
  * case: COV_VALID: a = n x 17 (size 3 or 4, then the matrix row-major in the first size x size of 16 entries), out = n x 1 (0 / 1) ;
  * PLANE_COV: a = n x 13 (normal[3], d, cov[9]), out = n x 17 (ok, then 16 entries) ; WORLD_PLANE_COV: a = n x 45 (normal[3], d,
- * camera_to_world[16], plane covariance[16], pose covariance[9]), out = n x 17 (ok, then 16 entries; all 0 when ok is 0). */
+ * camera_to_world[16], plane covariance[16], pose covariance[9]), out = n x 17 (ok, then 16 entries; all 0 when ok is 0).  The
+ * algebra of cape_map_kalman: KALMAN: a = n x 40 (x[4], P[16], z[4], R[16]), out = n x 21 (the KalmanStatus of
+ * host/map_tracking.hpp, then x'[4] and P'[16]; zeros unless the status is 0) ; PLANE_FRAME: a = n x 3 (normal), out = n x 7 (ok of
+ * get_plane_coordinate_system's norm check, then x axis and y axis; zeros unless ok). */
 enum
 {
     CAPE_DEBUG_SQRT = 0, CAPE_DEBUG_DIV = 1, CAPE_DEBUG_ACOS = 2, CAPE_DEBUG_ATAN2 = 3, CAPE_DEBUG_QUANT = 4,
     CAPE_DEBUG_SQRTF = 5, CAPE_DEBUG_EIGEN3 = 6, CAPE_DEBUG_FIT_PLANE = 7, CAPE_DEBUG_COV_VALID = 8, CAPE_DEBUG_PLANE_COV = 9,
-    CAPE_DEBUG_WORLD_PLANE_COV = 10
+    CAPE_DEBUG_WORLD_PLANE_COV = 10, CAPE_DEBUG_KALMAN = 11, CAPE_DEBUG_PLANE_FRAME = 12
 };
 int cape_debug_eval(int op, const double* a, const double* b, double* out, int n);
 /* Debug: shader-clock ticks spent per phase of the grow kernel, n_frames x 32 (all zero unless the library was built

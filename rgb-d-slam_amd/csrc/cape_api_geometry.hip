@@ -204,6 +204,14 @@ double ring_area_signed_host(const double* r, uint32_t n) // the host class's sh
     return 0.5 * s;
 }
 
+// the results of the last cape_map_kalman still describe the current batch, match and measurements (a cape_extract clears the latter
+// two; every other call that replaces an input clears kalmanFrames itself)
+bool kalman_results_live(const cape_handle_s* h)
+{
+    const auto& K = h->kalman;
+    return K.kalmanFrames > 0 && h->mapWide.matchFrames >= K.kalmanFrames && h->measure.frames >= K.kalmanFrames;
+}
+
 } // namespace
 
 extern "C" {
@@ -386,6 +394,7 @@ int cape_build_polygons(cape_handle h, int32_t n_frames, void* stream_)
 #endif
     h->res.doneArmed = false; // the chain's completion word was written before this kernel: results are waited for the slow way
     h->measure.frames = 0; // (the measurements index the polygons this call replaces)
+    h->kalman.kalmanFrames = 0;
     CAPE_HIP_TRY(cape::launch_polygons(p, n_frames, stream));
     P.frames = n_frames;
     return CAPE_OK;
@@ -619,6 +628,9 @@ int cape_map_upload(cape_handle h, const cape_map_plane* planes, int32_t n_plane
     auto& map = h->map;
     map.n = -1; // (no map until the copies are through)
     h->visibility.frames = 0; // (the words of the old map)
+    h->kalman.tracksN = -1;   // (its tracks, the wide match against it and what cape_map_kalman made of them)
+    h->kalman.matchedThisMap = false;
+    h->kalman.kalmanFrames = 0;
     const auto drained = [] { return hipSuccess; };
     CAPE_HIP_TRY(map.planes.grow(P.size(), drained));
     CAPE_HIP_TRY(map.rings.grow(R.size(), drained));
@@ -735,6 +747,7 @@ int cape_match_map_wide(cape_handle h, int32_t n_frames, const double* world_to_
     if (keepAreas && areaDoubles * sizeof(double) > kMapAreasBudget)
         return fail(CAPE_ERR_CAPACITY, "the inter-area table of this call would exceed 1 GiB (fewer frames per call, or no CAPE_MATCH_MAP_AREAS)");
     W.matchFrames = 0;
+    h->kalman.kalmanFrames = 0; // (cape_map_kalman's results belong to the match this call replaces)
     const uint32_t* deviceSkip = nullptr;
     if (flags & CAPE_MATCH_MAP_DEVICE_SKIP)
         if (const int rc = device_skip_words(h, n_frames, skip, &deviceSkip); rc != CAPE_OK)
@@ -788,6 +801,7 @@ int cape_match_map_wide(cape_handle h, int32_t n_frames, const double* world_to_
     W.matchFrames = n_frames;
     W.matchN = map.n;
     W.matchAreas = keepAreas;
+    h->kalman.matchedThisMap = true;
     return CAPE_OK;
 }
 
@@ -1030,6 +1044,7 @@ int cape_map_measure(cape_handle h, int32_t n_frames, const double* camera_to_wo
         return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
     auto& M = h->measure;
     M.frames = 0;
+    h->kalman.kalmanFrames = 0; // (cape_map_kalman's results belong to the rows this call replaces)
     if (n_frames == 0)
         return CAPE_OK;
     CAPE_ON_DEVICE(h);
@@ -1114,6 +1129,118 @@ int cape_copy_spill_measurements(cape_handle h, int32_t first, int32_t count, ca
     const size_t at = (size_t)h->cfg.max_batch + (size_t)first, n = (size_t)count, cap = (size_t)h->boundaryCap;
     CAPE_HIP_TRY(copy_out(rows, M.rows, at * CAPE_MAX_PLANES, n * CAPE_MAX_PLANES));
     CAPE_HIP_TRY(copy_out(world_vertices, M.vertices, at * cap * 2, n * cap * 2));
+    return CAPE_OK;
+}
+
+int cape_map_upload_tracks(cape_handle h, const cape_map_track* tracks, int32_t n)
+{
+    if (!h || n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative count");
+    if (h->map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (n != h->map.n)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "the tracks are parallel to the planes of the uploaded map: n must equal its plane count");
+    if (n > 0 && !tracks)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null array");
+    std::vector<cape::MapTrackState> T((size_t)n);
+    for (int32_t j = 0; j < n; ++j)
+    {
+        std::memcpy(T[j].covariance, tracks[j].covariance, sizeof(T[j].covariance));
+        T[j].successiveMatched = tracks[j].successive_matched;
+        T[j].failedTracking = tracks[j].failed_tracking;
+        T[j].flags = tracks[j].flags;
+        T[j].pad = 0;
+    }
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h)); // a cape_map_kalman in flight still reads the old tracks
+    auto& K = h->kalman;
+    K.tracksN = -1;
+    K.kalmanFrames = 0;
+    CAPE_HIP_TRY(K.tracks.grow(T.size(), [] { return hipSuccess; }));
+    if (n > 0)
+        CAPE_HIP_TRY(hipMemcpy(K.tracks, T.data(), T.size() * sizeof(cape::MapTrackState), hipMemcpyHostToDevice));
+    K.tracksN = n;
+    return CAPE_OK;
+}
+
+int cape_map_kalman(cape_handle h, int32_t n_frames, void* stream_)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    auto& K = h->kalman;
+    const auto& W = h->mapWide;
+    const auto& M = h->measure;
+    const int nMap = h->map.n;
+    K.kalmanFrames = 0;
+    if (nMap < 0 || K.tracksN != nMap)
+        return fail(CAPE_ERR_CAPACITY, "no tracks for the uploaded map (cape_map_upload, then cape_map_upload_tracks)");
+    if (!K.matchedThisMap || W.matchN != nMap || n_frames > W.matchFrames)
+        return fail(CAPE_ERR_CAPACITY, "no cape_match_map_wide of the current batch against the uploaded map covers n_frames");
+    if (n_frames > M.frames)
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_measure of the current batch covers n_frames");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be writing them
+    CAPE_HIP_TRY(K.frames.grow((size_t)n_frames, drain));
+    CAPE_HIP_TRY(K.rows.grow((size_t)n_frames * WP, drain));
+    CAPE_HIP_TRY(K.trackResults.grow((size_t)n_frames * (size_t)std::max(nMap, 1), drain));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    cape::MapKalmanParams p{};
+    p.mapPlanes = h->map.planes;
+    p.tracks = K.tracks;
+    p.nMap = nMap;
+    p.matchFrames = W.frames;
+    p.match = W.match;
+    p.mapOf = W.planes + (size_t)h->cfg.max_batch * WP;
+    p.kept = W.kept;
+    p.measurements = M.rows;
+    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows cape_map_measure allocated: a row of CAPE_MAX_PLANES per record)
+    p.frames = K.frames;
+    p.rows = K.rows;
+    p.trackResults = K.trackResults;
+    CAPE_HIP_TRY(cape::launch_map_kalman(p, n_frames, stream));
+    K.kalmanFrames = n_frames;
+    K.kalmanN = nMap;
+    return CAPE_OK;
+}
+
+int cape_device_map_kalman(cape_handle h, cape_frame_map_kalman** frames, cape_plane_fusion** rows, cape_map_track_result** track_results)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    if (!kalman_results_live(h))
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_kalman has run on the current batch, map, match and measurements");
+    if (frames)
+        *frames = h->kalman.frames;
+    if (rows)
+        *rows = h->kalman.rows;
+    if (track_results)
+        *track_results = h->kalman.trackResults;
+    return CAPE_OK;
+}
+
+int cape_copy_map_kalman(cape_handle h, int32_t n_frames, cape_frame_map_kalman* frames, cape_plane_fusion* rows,
+                         cape_map_track_result* track_results)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    const auto& K = h->kalman;
+    if (n_frames > (kalman_results_live(h) ? K.kalmanFrames : 0))
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_kalman on the current batch, map, match and measurements");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(copy_out(frames, K.frames, 0, (size_t)n_frames));
+    CAPE_HIP_TRY(copy_out(rows, K.rows, 0, (size_t)n_frames * WP));
+    CAPE_HIP_TRY(copy_out(track_results, K.trackResults, 0, (size_t)n_frames * (size_t)K.kalmanN));
     return CAPE_OK;
 }
 

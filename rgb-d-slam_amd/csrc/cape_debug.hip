@@ -1,7 +1,8 @@
 // Debug / parity entry: evaluates device scalar math on caller-supplied operands so tests can compare the
 // gfx950 instruction sequences (f64 div / sqrt expansion, ocml acos / atan2, the restated eigen-solver and plane
 // fit) against the CPU oracle bit for bit, and the covariance algebra of cape_map_tracking.h against its host twin
-// (decisions equal, values to rounding: it goes through pow).  Not on the hot path.
+// (decisions equal, values to rounding: it goes through pow; the Kalman step and the plane frame of cape_map_kalman have no pow and
+// equal theirs bit for bit).  Not on the hot path.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -75,6 +76,38 @@ __global__ void debug_eval_kernel(int op, const double* a, const double* b, doub
             o[1 + k] = ok ? cov[k] : 0.0;
         break;
     }
+    case CAPE_DEBUG_KALMAN:
+    {
+        // a: n x 40 (x, P, z, R) ; out: n x 21 (status, x', P': 0 unless the status is 0)
+        const double* s = a + (size_t)i * 40;
+        double xn[4] = {0, 0, 0, 0}, Pn[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            Pn[k] = 0.0;
+        const int st = kalman_update(s, s + 4, s + 20, s + 24, xn, Pn);
+        double* o = out + (size_t)i * 21;
+        o[0] = (double)st;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            o[1 + k] = st == kKalmanOk ? xn[k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            o[5 + k] = st == kKalmanOk ? Pn[k] : 0.0;
+        break;
+    }
+    case CAPE_DEBUG_PLANE_FRAME:
+    {
+        // a: n x 3 (normal) ; out: n x 7 (ok, x axis, y axis: 0 unless ok)
+        const double* s = a + (size_t)i * 3;
+        double ax[3] = {0, 0, 0}, ay[3] = {0, 0, 0};
+        const bool ok = plane_coordinate_system(s, ax, ay);
+        double* o = out + (size_t)i * 7;
+        o[0] = ok ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            o[1 + k] = ok ? ax[k] : 0.0, o[4 + k] = ok ? ay[k] : 0.0;
+        break;
+    }
     default: out[i] = 0.0;
     }
 }
@@ -94,6 +127,8 @@ extern "C" int cape_debug_eval(int op, const double* a, const double* b, double*
     if (op == CAPE_DEBUG_COV_VALID) { inW = 17; outW = 1; }
     if (op == CAPE_DEBUG_PLANE_COV) { inW = 13; outW = 17; }
     if (op == CAPE_DEBUG_WORLD_PLANE_COV) { inW = 45; outW = 17; }
+    if (op == CAPE_DEBUG_KALMAN) { inW = 40; outW = 21; }
+    if (op == CAPE_DEBUG_PLANE_FRAME) { inW = 3; outW = 7; }
     double *da = nullptr, *db = nullptr, *dout = nullptr;
     int rc = CAPE_OK;
     if (hipMalloc((void**)&da, n * inW * 8) != hipSuccess || hipMalloc((void**)&dout, n * outW * 8) != hipSuccess)

@@ -34,6 +34,7 @@ hipError_t launch_match_wide(const MatchWideParams& p, int nFrames, hipStream_t 
 hipError_t launch_carry_save(const CarrySaveParams& p, hipStream_t stream);
 hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_measure(const MapMeasureParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_kalman(const MapKalmanParams& p, int nFrames, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -451,6 +452,21 @@ struct cape_handle_s
     Stream sideStream;
     Event sideFork, sideDone;
     bool sidePending = false;
+
+    // cape_map_upload_tracks / cape_map_kalman: the tracks parallel to the uploaded map's planes and the state half of the map update
+    // for the frames of the last call.  Result buffers of its own, grown on demand behind drain_handle: no other call writes them.
+    // (Declared last: the members above keep their places for the files that do not know this call.)
+    struct Kalman
+    {
+        Buffer<cape::MapTrackState> tracks;       // n planes of the uploaded map
+        int tracksN = -1;                         // tracks uploaded for the current map (-1: none since cape_map_upload)
+        bool matchedThisMap = false;              // a cape_match_map_wide has run since the last cape_map_upload
+        Buffer<cape_frame_map_kalman> frames;     // frames of the call
+        Buffer<cape_plane_fusion> rows;           // frames x 128
+        Buffer<cape_map_track_result> trackResults; // frames x n_map of the call
+        int kalmanFrames = 0;                     // frames of the last cape_map_kalman (0: none for the current batch, map, match and measurements)
+        int kalmanN = 0;                          // map planes of that call
+    } kalman;
 };
 
 namespace cape::abi {

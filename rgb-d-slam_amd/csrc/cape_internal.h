@@ -351,6 +351,35 @@ struct MapMeasureParams
     double2* worldVertices;       // records x boundaryCapacity
 };
 
+// what cape_map_kalman reads of a cape_map_track (cape_map_upload_tracks): 36 words, 16-byte aligned
+struct MapTrackState
+{
+    double covariance[16];
+    int32_t successiveMatched;
+    uint32_t failedTracking;
+    uint32_t flags, pad;
+};
+
+// cape_map_kalman (cape_map_kalman.hip): the state half of the map update, per frame against the uploaded map and tracks
+struct MapKalmanParams
+{
+    const cape_map_plane* mapPlanes;
+    const MapTrackState* tracks;               // nMap
+    int nMap;
+    // the last cape_match_map_wide
+    const cape_frame_map_match_wide* matchFrames;
+    const int32_t* match;                      // frames x nMap
+    const int32_t* mapOf;                      // frames x 128
+    const uint2* kept;                         // frames x 128: (record, segment in that record) of kept plane i
+    // the last cape_map_measure
+    const cape_plane_measurement* measurements; // nRecords x CAPE_MAX_PLANES
+    int nRecords;
+    // results
+    cape_frame_map_kalman* frames;
+    cape_plane_fusion* rows;                   // frames x 128
+    cape_map_track_result* trackResults;       // frames x nMap
+};
+
 // multi-GPU gather: device-side packing of the ragged primitive lists (cape_gather.hip)
 struct PackParams
 {

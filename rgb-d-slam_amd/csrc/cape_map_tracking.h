@@ -291,6 +291,159 @@ __device__ __forceinline__ bool world_plane_covariance(const double* normal, dou
     return plane_covariance(nw, dw, world, out16);
 }
 
+// ---- the state half (cape_map_kalman.hip): no pow on this path, every function below is the host's bit for bit
+
+// 4 x 4 determinant and inverse by cofactors of 2 x 2 minors (map_tracking.cpp:226-258)
+__device__ __forceinline__ double det44(const double* a)
+{
+    const double s0 = a[0] * a[5] - a[4] * a[1], s1 = a[0] * a[6] - a[4] * a[2], s2 = a[0] * a[7] - a[4] * a[3];
+    const double s3 = a[1] * a[6] - a[5] * a[2], s4 = a[1] * a[7] - a[5] * a[3], s5 = a[2] * a[7] - a[6] * a[3];
+    const double c5 = a[10] * a[15] - a[14] * a[11], c4 = a[9] * a[15] - a[13] * a[11], c3 = a[9] * a[14] - a[13] * a[10];
+    const double c2 = a[8] * a[15] - a[12] * a[11], c1 = a[8] * a[14] - a[12] * a[10], c0 = a[8] * a[13] - a[12] * a[9];
+    return s0 * c5 - s1 * c4 + s2 * c3 + s3 * c2 - s4 * c1 + s5 * c0;
+}
+
+__device__ __forceinline__ void inverse44(const double* a, double det, double* b)
+{
+    const double s0 = a[0] * a[5] - a[4] * a[1], s1 = a[0] * a[6] - a[4] * a[2], s2 = a[0] * a[7] - a[4] * a[3];
+    const double s3 = a[1] * a[6] - a[5] * a[2], s4 = a[1] * a[7] - a[5] * a[3], s5 = a[2] * a[7] - a[6] * a[3];
+    const double c5 = a[10] * a[15] - a[14] * a[11], c4 = a[9] * a[15] - a[13] * a[11], c3 = a[9] * a[14] - a[13] * a[10];
+    const double c2 = a[8] * a[15] - a[12] * a[11], c1 = a[8] * a[14] - a[12] * a[10], c0 = a[8] * a[13] - a[12] * a[9];
+    const double inv = 1.0 / det;
+    b[0] = (a[5] * c5 - a[6] * c4 + a[7] * c3) * inv;
+    b[1] = (-a[1] * c5 + a[2] * c4 - a[3] * c3) * inv;
+    b[2] = (a[13] * s5 - a[14] * s4 + a[15] * s3) * inv;
+    b[3] = (-a[9] * s5 + a[10] * s4 - a[11] * s3) * inv;
+    b[4] = (-a[4] * c5 + a[6] * c2 - a[7] * c1) * inv;
+    b[5] = (a[0] * c5 - a[2] * c2 + a[3] * c1) * inv;
+    b[6] = (-a[12] * s5 + a[14] * s2 - a[15] * s1) * inv;
+    b[7] = (a[8] * s5 - a[10] * s2 + a[11] * s1) * inv;
+    b[8] = (a[4] * c4 - a[5] * c2 + a[7] * c0) * inv;
+    b[9] = (-a[0] * c4 + a[1] * c2 - a[3] * c0) * inv;
+    b[10] = (a[12] * s4 - a[13] * s2 + a[15] * s0) * inv;
+    b[11] = (-a[8] * s4 + a[9] * s2 - a[11] * s0) * inv;
+    b[12] = (-a[4] * c3 + a[5] * c1 - a[6] * c0) * inv;
+    b[13] = (a[0] * c3 - a[1] * c1 + a[2] * c0) * inv;
+    b[14] = (-a[12] * s3 + a[13] * s1 - a[14] * s0) * inv;
+    b[15] = (a[8] * s3 - a[9] * s1 + a[10] * s0) * inv;
+}
+
+// KalmanStatus of host/map_tracking.hpp
+enum
+{
+    kKalmanOk = 0,
+    kKalmanInvalidInput = 1,
+    kKalmanSingular = 2,
+    kKalmanInvalidOutput = 3
+};
+
+// kalman_update (map_tracking.cpp:260-314): SharedKalmanFilter<4, 4>::get_new_state with identity dynamics and output, process noise
+// 1e-6 I.  Writes xOut / Pout only on kKalmanOk.
+__device__ __forceinline__ int kalman_update(const double* x, const double* P, const double* z, const double* R, double* xOut, double* Pout)
+{
+    if (!is_covariance_valid<4>(P) || !is_covariance_valid<4>(R))
+        return kKalmanInvalidInput;
+    const double processNoise = 0.000001;
+    // estimateErrorCovariance = propagate(P, I) + 1e-6 I; innovation = propagate(that, I) + R
+    double E[16], S[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            E[i * 4 + j] = sym_lower<4>(P, i, j) + (i == j ? processNoise : 0.0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            S[i * 4 + j] = sym_lower<4>(E, i, j) + R[i * 4 + j];
+    const double det = det44(S);
+    if (double_equal(det, 0.0))
+        return kKalmanSingular;
+    double Si[16], K[16];
+    inverse44(S, det, Si);
+    // kalmanGain = E.selfadjointView<Lower>() * I * S^-1
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+        {
+            double s = sym_lower<4>(E, i, 0) * Si[j];
+#pragma unroll
+            for (int k = 1; k < 4; ++k)
+                s = s + sym_lower<4>(E, i, k) * Si[k * 4 + j];
+            K[i * 4 + j] = s;
+        }
+    double y[4], xn[4], C[16];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        y[k] = z[k] - x[k];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+    {
+        double s = K[i * 4] * y[0];
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            s = s + K[i * 4 + k] * y[k];
+        xn[i] = x[i] + s;
+    }
+    // (I - K) * E.selfadjointView<Lower>(), then its own selfadjointView<Lower>()
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j <= i)
+            {
+                double s = ((i == 0 ? 1.0 : 0.0) - K[i * 4]) * sym_lower<4>(E, 0, j);
+#pragma unroll
+                for (int k = 1; k < 4; ++k)
+                    s = s + ((i == k ? 1.0 : 0.0) - K[i * 4 + k]) * sym_lower<4>(E, k, j);
+                C[i * 4 + j] = s;
+                C[j * 4 + i] = s;
+            }
+    if (!is_covariance_valid<4>(C))
+        return kKalmanInvalidOutput;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        xOut[i] = xn[i];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        Pout[i] = C[i];
+    return kKalmanOk;
+}
+
+// get_plane_coordinate_system (boundary_polygon.cpp:27-39, 505-513): select_correct_transform, two cross products, two
+// normalisations.  false where the host throws (the normal's norm is not 1 within 1e-9); the axes are then not written.
+__device__ __forceinline__ bool plane_coordinate_system(const double* n, double* xAxis, double* yAxis)
+{
+    if (!(fabs(norm3(n) - 1.0) <= 1e-9))
+        return false;
+    // select_correct_transform; std::min(a, b) is b < a ? b : a
+    const double distX = fabs(n[0]), distY = fabs(n[1]), distZ = fabs(n[2]);
+    const double yz = distZ < distY ? distZ : distY;
+    const double res = yz < distX ? yz : distX;
+    double r[3];
+    if (fabs(res - distX) <= 0.1)
+        r[0] = 1, r[1] = 0, r[2] = 0;
+    else if (fabs(res - distY) <= 0.1)
+        r[0] = 0, r[1] = 1, r[2] = 0;
+    else if (fabs(res - distZ) <= 0.1)
+        r[0] = 0, r[1] = 0, r[2] = 1;
+    else
+    {
+        r[0] = n[2], r[1] = n[0], r[2] = n[1];
+        normalize3(r);
+    }
+    xAxis[0] = n[1] * r[2] - n[2] * r[1];
+    xAxis[1] = n[2] * r[0] - n[0] * r[2];
+    xAxis[2] = n[0] * r[1] - n[1] * r[0];
+    normalize3(xAxis);
+    yAxis[0] = n[1] * xAxis[2] - n[2] * xAxis[1];
+    yAxis[1] = n[2] * xAxis[0] - n[0] * xAxis[2];
+    yAxis[2] = n[0] * xAxis[1] - n[1] * xAxis[0];
+    normalize3(yAxis);
+    return true;
+}
+
 } // namespace
 
 } // namespace cape

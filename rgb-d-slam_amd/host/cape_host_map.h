@@ -10,45 +10,7 @@
 extern "C" {
 #endif
 
-/* Tracking state of one map plane, parallel to cape_map_plane: what Feature_Map::update_map (feature_map.hpp:367-384, :701-830)
- * reads and changes besides the plane and its polygon.  Promotion from staged to local, removal from staged and the loss of a local
- * plane reorder or delete entries of the ordered list: cape_host_map_update reports them in `result` and leaves them to the caller. */
-typedef struct cape_map_track
-{
-    double covariance[16];      /* 4 x 4 covariance of (normal, d), row-major */
-    int32_t successive_matched; /* _successivMatchedCount (may go negative) */
-    uint32_t failed_tracking;   /* _failedTrackingCount */
-    uint32_t flags;             /* CAPE_MAP_TRACK_* */
-    uint32_t result;            /* CAPE_MAP_RESULT_* of the last update call (output) */
-    uint64_t id;                /* the caller's identifier; appended planes get consecutive ids from the update's next_id */
-} cape_map_track;
-enum
-{
-    CAPE_MAP_TRACK_STAGED = 1u << 0, /* a staged plane (StagedMapPlane): a match counts the detection as used even if the update fails */
-    CAPE_MAP_TRACK_MOVING = 1u << 1  /* is_moving(): informational here, the caller's skip bits of cape_match_map follow it */
-};
-enum
-{
-    CAPE_MAP_RESULT_MATCHED = 1u << 0,        /* a detected plane was matched to this map plane */
-    CAPE_MAP_RESULT_UPDATED = 1u << 1,        /* update_with_match returned true */
-    CAPE_MAP_RESULT_FAIL_DETECTION = 1u << 2, /* the detection's plane / world covariance is invalid: nothing changed */
-    CAPE_MAP_RESULT_FAIL_STATE = 1u << 3,     /* the map plane's covariance is invalid (the reference exits): nothing changed */
-    CAPE_MAP_RESULT_FAIL_SINGULAR = 1u << 4,  /* innovation determinant 0 within DBL_EPSILON, where the reference takes a
-                                                 pseudo-inverse: nothing changed.  Not reached with valid covariances: the
-                                                 detection's world covariance carries 0.01 on its diagonal, so the innovation's
-                                                 eigenvalues are >= 0.01 */
-    CAPE_MAP_RESULT_FAIL_KALMAN = 1u << 5,    /* the Kalman step produced an invalid covariance: nothing changed */
-    CAPE_MAP_RESULT_FAIL_POLYGON = 1u << 6,   /* update_boundary_polygon failed: the plane and covariance ARE updated, the polygon
-                                                 is the projected one or the old one.  Its isApprox centre check fails the update
-                                                 like the reference; a Polygon::project or to_world_space check, which throws inside
-                                                 the noexcept update_boundary_polygon there (std::terminate), fails it here too */
-    CAPE_MAP_RESULT_OVERFLOW = 1u << 7,       /* the merged polygon exceeds CAPE_MAP_MAX_RING / CAPE_MAP_MAX_HOLES after simplify:
-                                                 plane and covariance updated, the old polygon (and its frame) kept */
-    CAPE_MAP_RESULT_PROMOTE = 1u << 8,        /* staged, should_add_to_local_map (successive_matched >= 4) */
-    CAPE_MAP_RESULT_DROP = 1u << 9,           /* staged, not promoted, should_remove_from_staged (failed_tracking >= 2) */
-    CAPE_MAP_RESULT_LOST = 1u << 10,          /* local, is_lost (failed_tracking >= planeUnmatchedCountToLoose = 10) */
-    CAPE_MAP_RESULT_APPENDED = 1u << 11       /* a staged plane appended by this call */
-};
+/* cape_map_track and its CAPE_MAP_TRACK_* / CAPE_MAP_RESULT_* enums are declared in cape_hip.h (cape_map_upload_tracks takes them). */
 enum
 {
     CAPE_MAP_ADD_STAGED = 1u << 0 /* append every kept plane of the frame that no map plane used as a staged plane (not one whose
@@ -122,6 +84,20 @@ int cape_host_match_planes(const cape_host_planes* prev, const cape_host_planes*
  * three counts of map_out (next_id unchanged). */
 int cape_host_map_update(const cape_host_map* map, const int32_t* match, const cape_host_planes* detected, const double* camera_to_world,
                          const double* pose_covariance, uint32_t flags, uint64_t* next_id, cape_host_map* map_out, int32_t* used_out);
+
+/* The twin of cape_map_kalman (include/cape_hip.h) for ONE frame: the statements of cape_host_map_update above that concern a map
+ * plane's state, up to but not including merge_union, with the detection's measurement given instead of derived -- so the device's own
+ * z and R can be fed to it (tests/test_gpu_map_kalman.py compares the two bit for bit).  map: planes and tracks (rings and vertices
+ * are not read); match[map->n_planes]: the kept plane matched to map plane j or -1; measurements: n_cur rows in KEPT-PLANE order
+ * (cape_plane_measurement of cape_map_measure, or rows built from cape_host_plane_covariance / cape_host_world_plane_covariance /
+ * plane_to_world).  The rules are cape_map_kalman's: a row with CAPE_MEASURE_FAIL_PLANE_COV / FAIL_WORLD_COV / BAD_POSE_COV (or
+ * without CAPE_MEASURE_KEPT) is FAIL_DETECTION, a row with CAPE_MEASURE_FAIL_POLYGON has no usable polygon; the Kalman step,
+ * normalize3 and get_plane_coordinate_system are those of the update.  Outputs: rows_out[n_cur] (cape_plane_fusion),
+ * tracks_out[map->n_planes] (cape_map_track_result), frame_out (n_map, n_cur, CAPE_KALMAN_BAD_POSE_COV, n_updated); any may be
+ * NULL.  Returns 0, or CAPE_ERR_INVALID_ARGUMENT for a NULL map, negative counts, n_cur > 128, a match out of range or a missing
+ * array. */
+int cape_host_map_kalman(const cape_host_map* map, const int32_t* match, const cape_plane_measurement* measurements, int32_t n_cur,
+                         cape_frame_map_kalman* frame_out, cape_plane_fusion* rows_out, cape_map_track_result* tracks_out);
 
 /* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
  * cape_gather_primitives[_root] or any other transport -- as the kept planes the two calls above take: no handle, no device.

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <exception>
 #include <limits>
+#include <stdexcept>
 #include <vector>
 
 #include "boundary_polygon.hpp"
@@ -645,6 +646,116 @@ extern "C" int cape_host_map_update(const cape_host_map* map, const int32_t* mat
     }
 }
 
+// The twin of cape_map_kalman (cape_host_map.h): the statements of cape_host_map_update above that concern a map plane's state, the
+// detection's measurement given as a row of cape_map_measure.
+extern "C" int cape_host_map_kalman(const cape_host_map* map, const int32_t* match, const cape_plane_measurement* measurements, int32_t n_cur,
+                                    cape_frame_map_kalman* frame_out, cape_plane_fusion* rows_out, cape_map_track_result* tracks_out)
+{
+    namespace mt = rgbd_slam::map_tracking;
+    if (!map || map->n_planes < 0 || n_cur < 0 || n_cur > CAPE_MATCH_MAP_WIDE_MAX_PLANES || (n_cur > 0 && !measurements) ||
+        (map->n_planes > 0 && (!map->planes || !map->tracks || !match)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const int32_t n_planes = map->n_planes;
+    for (int32_t j = 0; j < n_planes; ++j)
+        if (match[j] < -1 || match[j] >= n_cur)
+            return CAPE_ERR_INVALID_ARGUMENT;
+    std::vector<cape_plane_fusion> rows((size_t)n_cur, cape_plane_fusion {});
+    for (auto& row : rows)
+        row.map_plane = -1;
+    const uint32_t noDetection = CAPE_MEASURE_FAIL_PLANE_COV | CAPE_MEASURE_FAIL_WORLD_COV | CAPE_MEASURE_BAD_POSE_COV;
+    bool badPose = false;
+    for (int32_t i = 0; i < n_cur; ++i)
+        badPose = badPose || (measurements[i].flags & CAPE_MEASURE_BAD_POSE_COV) != 0;
+    int32_t nUpdated = 0;
+    for (int32_t j = 0; j < n_planes; ++j)
+    {
+        const cape_map_plane& M = map->planes[j];
+        cape_map_track track = map->tracks[j];
+        uint32_t result = 0;
+        const bool staged = (track.flags & CAPE_MAP_TRACK_STAGED) != 0;
+        const int32_t i = match[j];
+        if (i >= 0)
+        {
+            const cape_plane_measurement& m = measurements[i];
+            cape_plane_fusion& row = rows[i];
+            row.map_plane = j;
+            result |= CAPE_MAP_RESULT_MATCHED;
+            if (!(m.flags & CAPE_MEASURE_KEPT) || (m.flags & noDetection))
+                result |= CAPE_MAP_RESULT_FAIL_DETECTION;
+            else if (!mt::is_covariance_valid(track.covariance, 4))
+                result |= CAPE_MAP_RESULT_FAIL_STATE;
+            else
+            {
+                const double x[4] = {M.normal[0], M.normal[1], M.normal[2], M.d}, z[4] = {m.normal[0], m.normal[1], m.normal[2], m.d};
+                double xn[4], Pn[16];
+                const mt::KalmanStatus st = mt::kalman_update(x, track.covariance, z, m.covariance, xn, Pn);
+                if (st == mt::KALMAN_SINGULAR)
+                    result |= CAPE_MAP_RESULT_FAIL_SINGULAR;
+                else if (st != mt::KALMAN_OK)
+                    result |= CAPE_MAP_RESULT_FAIL_KALMAN;
+                else
+                {
+                    double n[3] = {xn[0], xn[1], xn[2]};
+                    mt::normalize3(n);
+                    mt::normalize3(n);
+                    mt::normalize3(n);
+                    std::memcpy(row.normal, n, sizeof(n));
+                    row.d = xn[3];
+                    std::memcpy(row.covariance, Pn, sizeof(Pn));
+                    row.flags |= CAPE_FUSION_STATE;
+                    bool ok = std::abs(mt::norm3(n) - 1.0) <= std::numeric_limits<double>::epsilon(); // Polygon::project's check
+                    if (ok)
+                    {
+                        try
+                        {
+                            const auto axes = rgbd_slam::utils::get_plane_coordinate_system(vector3(n[0], n[1], n[2]));
+                            for (int k = 0; k < 3; ++k)
+                            {
+                                row.x_axis[k] = axes.first[k];
+                                row.y_axis[k] = axes.second[k];
+                                row.center[k] = n[k] * -xn[3];
+                            }
+                            row.flags |= CAPE_FUSION_FRAME;
+                        }
+                        catch (const std::invalid_argument&)
+                        {
+                            ok = false; // (its own 1e-9 norm check)
+                        }
+                    }
+                    ok = ok && !(m.flags & CAPE_MEASURE_FAIL_POLYGON);
+                    result |= ok ? CAPE_MAP_RESULT_UPDATED : CAPE_MAP_RESULT_FAIL_POLYGON;
+                }
+            }
+            if ((result & CAPE_MAP_RESULT_UPDATED) || staged)
+                row.flags |= CAPE_FUSION_USED;
+        }
+        if (result & CAPE_MAP_RESULT_UPDATED)
+        {
+            track.failed_tracking = 0;
+            track.successive_matched = (int32_t)((uint32_t)track.successive_matched + 1u);
+            ++nUpdated;
+        }
+        else
+        {
+            ++track.failed_tracking;
+            track.successive_matched = (int32_t)((uint32_t)track.successive_matched - 1u);
+        }
+        if (staged && track.successive_matched >= 4)
+            result |= CAPE_MAP_RESULT_PROMOTE;
+        else if (staged && track.failed_tracking >= 2)
+            result |= CAPE_MAP_RESULT_DROP;
+        else if (!staged && track.failed_tracking >= 10)
+            result |= CAPE_MAP_RESULT_LOST;
+        if (tracks_out)
+            tracks_out[j] = cape_map_track_result {result, track.successive_matched, track.failed_tracking, i};
+    }
+    if (rows_out)
+        std::copy(rows.begin(), rows.end(), rows_out);
+    if (frame_out)
+        *frame_out = cape_frame_map_kalman {n_planes, n_cur, badPose ? (uint32_t)CAPE_KALMAN_BAD_POSE_COV : 0u, nUpdated};
+    return 0;
+}
+
 // Test hooks of the covariance and Kalman algebra (tests/test_map_update_host.py restates them in numpy).  Each returns 1 on
 // success, 0 where the reference throws; cape_host_kalman_update returns the KalmanStatus.
 extern "C" int cape_host_covariance_valid(const double* M, int n) { return (n == 3 || n == 4) && rgbd_slam::map_tracking::is_covariance_valid(M, n); }
@@ -660,4 +771,27 @@ extern "C" int cape_host_world_plane_covariance(const double* normal, double d, 
 extern "C" int cape_host_kalman_update(const double* x, const double* P, const double* z, const double* R, double* x_out, double* P_out)
 {
     return rgbd_slam::map_tracking::kalman_update(x, P, z, R, x_out, P_out);
+}
+// get_plane_coordinate_system: out6 = x axis, y axis; 0 where it throws (the normal's norm is not 1 within 1e-9)
+extern "C" int cape_host_plane_frame(const double* normal, double* out6)
+{
+    try
+    {
+        const auto axes = rgbd_slam::utils::get_plane_coordinate_system(vector3(normal[0], normal[1], normal[2]));
+        for (int k = 0; k < 3; ++k)
+        {
+            out6[k] = axes.first[k];
+            out6[3 + k] = axes.second[k];
+        }
+        return 1;
+    }
+    catch (const std::invalid_argument&)
+    {
+        return 0;
+    }
+}
+// plane_to_world: out4 = (normal, d) of the plane in world coordinates, z of the Kalman step
+extern "C" void cape_host_plane_to_world(const double* normal, double d, const double* camera_to_world, double* out4)
+{
+    rgbd_slam::map_tracking::plane_to_world(normal, d, camera_to_world, out4, out4 + 3);
 }

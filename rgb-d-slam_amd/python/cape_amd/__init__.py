@@ -208,8 +208,9 @@ def pack_map(planes):
     return P, R, V
 
 
-# cape_map_track (rgb-d-slam_amd/host/cape_host_map.h): the tracking state of a map plane, parallel to MAP_PLANE_DTYPE, for
-# host_map_update (the map's state is updated on the host only; Extractor.map_measure computes a frame's measurements on the device)
+# cape_map_track (include/cape_hip.h): the tracking state of a map plane, parallel to MAP_PLANE_DTYPE, for
+# host_map_update and Extractor.upload_tracks (Extractor.map_measure computes a frame's measurements on the device, Extractor.map_kalman
+# the state half of the update; the polygon union stays with host_map_update)
 MAP_TRACK_DTYPE = np.dtype([
     ("covariance", "<f8", (4, 4)), ("successive_matched", "<i4"), ("failed_tracking", "<u4"), ("flags", "<u4"),
     ("result", "<u4"), ("id", "<u8")], align=True)
@@ -220,6 +221,17 @@ MAP_TRACK_STAGED, MAP_TRACK_MOVING = 1, 2
  MAP_RESULT_APPENDED) = (1 << k for k in range(12))
 MAP_ADD_STAGED = 1
 CAPE_ERR_CAPACITY = -4
+
+# cape_map_kalman: the state half of the map update (cape_frame_map_kalman, cape_plane_fusion, cape_map_track_result)
+FRAME_MAP_KALMAN_DTYPE = np.dtype([("n_map", "<i4"), ("n_cur", "<i4"), ("flags", "<u4"), ("n_updated", "<i4")], align=True)
+PLANE_FUSION_DTYPE = np.dtype([
+    ("normal", "<f8", 3), ("d", "<f8"), ("covariance", "<f8", (4, 4)), ("x_axis", "<f8", 3), ("y_axis", "<f8", 3), ("center", "<f8", 3),
+    ("map_plane", "<i4"), ("flags", "<u4")], align=True)
+MAP_TRACK_RESULT_DTYPE = np.dtype([("result", "<u4"), ("successive_matched", "<i4"), ("failed_tracking", "<u4"), ("kept_plane", "<i4")],
+                                  align=True)
+assert FRAME_MAP_KALMAN_DTYPE.itemsize == 16 and PLANE_FUSION_DTYPE.itemsize == 29 * 8 + 8 == 240 and MAP_TRACK_RESULT_DTYPE.itemsize == 16
+KALMAN_BAD_POSE_COV = 1 << 8
+FUSION_USED, FUSION_STATE, FUSION_FRAME = 1, 2, 4
 
 
 class cape_host_map(C.Structure):
@@ -256,6 +268,11 @@ def _host_library():
                                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.cape_host_shard_frame.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout),
                                             C.c_int32, Planes]
+        L.cape_host_map_kalman.argtypes = [Map, i32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
+        L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
+        L.cape_host_plane_to_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        L.cape_host_plane_to_world.restype = None
         _host_lib = L
     return _host_lib
 
@@ -345,6 +362,46 @@ def host_map_update(map_arrays, tracks, match, detected, camera_to_world, pose_c
                                                                2 * (len(src["vertices"]) + len(cols["vertices"])) + 64))
     return ((out["planes"][:v.n_planes].copy(), out["rings"][:v.n_rings].copy(), out["vertices"][:v.n_vertices].copy()),
             out["tracks"][:v.n_planes].copy(), used[:n_det].astype(bool), nid.value)
+
+
+def _fusion_dicts(rows, n_cur):
+    """the first n_cur rows of a frame's PLANE_FUSION_DTYPE rows as dicts, in kept-plane order"""
+    return [dict(map_plane=int(r["map_plane"]), flags=int(r["flags"]), normal=r["normal"].copy(), d=float(r["d"]),
+                 covariance=r["covariance"].copy(), x_axis=r["x_axis"].copy(), y_axis=r["y_axis"].copy(), center=r["center"].copy())
+            for r in rows[:n_cur]]
+
+
+def host_map_kalman(map_arrays, tracks, match, measurements):
+    """cape_host_map_kalman of libcape_primitives.so: the twin of Extractor.map_kalman for ONE frame -- the state half of
+    host_map_update (Kalman step, counters, decisions; no polygon union) on measurement rows instead of detections.
+
+    map_arrays: pack_map(...); tracks: MAP_TRACK_DTYPE array parallel to the planes; match: n_map kept-plane indices or -1;
+    measurements: the frame's rows in kept-plane order -- a PLANE_MEASUREMENT_DTYPE array, or the dicts of
+    Extractor.map_measurements (normal, d, covariance, flags are read).
+    Returns (frame: FRAME_MAP_KALMAN_DTYPE scalar, rows: PLANE_FUSION_DTYPE[n_cur], track_results: MAP_TRACK_RESULT_DTYPE[n_map])."""
+    L = _host_library()
+    src, src_view = _map_arrays(map_arrays, np.ascontiguousarray(tracks, MAP_TRACK_DTYPE))
+    n_map = len(src["planes"])
+    if len(src["tracks"]) != n_map:
+        raise CapeError("host_map_kalman: one track per map plane")
+    M = np.ascontiguousarray(match, np.int32).reshape(-1)
+    if len(M) != n_map:
+        raise CapeError("host_map_kalman: one match per map plane")
+    if isinstance(measurements, np.ndarray):
+        rows_in = np.ascontiguousarray(measurements, PLANE_MEASUREMENT_DTYPE).reshape(-1)
+    else:
+        rows_in = np.zeros(len(measurements), PLANE_MEASUREMENT_DTYPE)
+        for r, m in zip(rows_in, measurements):
+            r["normal"], r["d"], r["covariance"], r["flags"] = m["normal"], m["d"], m["covariance"], m["flags"]
+    n_cur = len(rows_in)
+    frame = np.zeros(1, FRAME_MAP_KALMAN_DTYPE)
+    rows = np.zeros(max(n_cur, 1), PLANE_FUSION_DTYPE)
+    results = np.zeros(max(n_map, 1), MAP_TRACK_RESULT_DTYPE)
+    rc = L.cape_host_map_kalman(C.byref(src_view), _as(M, C.c_int32), rows_in.ctypes.data, n_cur, frame.ctypes.data, rows.ctypes.data,
+                                results.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_map_kalman failed ({rc})")
+    return frame[0], rows[:n_cur], results[:n_map]
 
 
 def host_shard_frame(buf, layout, k):
@@ -492,12 +549,14 @@ EXPORTED_SYMBOLS = [
     "cape_map_upload", "cape_match_map", "cape_copy_map_matches", "cape_match_map_wide", "cape_copy_map_matches_wide", "cape_match_map_shards", "cape_copy_shard_map_matches",
     "cape_map_visibility", "cape_copy_map_visibility",
     "cape_map_measure", "cape_device_map_measurements", "cape_copy_map_measurements", "cape_copy_spill_measurements",
+    "cape_map_upload_tracks", "cape_map_kalman", "cape_copy_map_kalman", "cape_device_map_kalman",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
     "cape_comm_info", "cape_abi_version", "cape_spill_info", "cape_copy_spill", "cape_copy_spill_polygons", "cape_get_timings_sized",
 ]
-DEBUG_OPS = dict(sqrt=0, div=1, acos=2, atan2=3, quant=4, sqrtf=5, eigen3=6, fit_plane=7, cov_valid=8, plane_cov=9, world_plane_cov=10)
+DEBUG_OPS = dict(sqrt=0, div=1, acos=2, atan2=3, quant=4, sqrtf=5, eigen3=6, fit_plane=7, cov_valid=8, plane_cov=9, world_plane_cov=10,
+                 kalman=11, plane_frame=12)
 
 _lib = None
 
@@ -582,6 +641,10 @@ def load_library():
     L.cape_device_map_measurements.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_map_measurements.argtypes = [vp, C.c_int32, vp, vp]
     L.cape_copy_spill_measurements.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
+    L.cape_map_upload_tracks.argtypes = [vp, vp, C.c_int32]
+    L.cape_map_kalman.argtypes = [vp, C.c_int32, vp]
+    L.cape_copy_map_kalman.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.cape_device_map_kalman.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -982,6 +1045,41 @@ class Extractor:
                                               V.ctypes.data_as(C.c_void_p), len(V)), "cape_map_upload")
         self.map_size = len(P)
 
+    # ---- the state half of the map update (needs upload_map + upload_tracks, match_map_wide and map_measure of the batch) ----
+    def upload_tracks(self, tracks):
+        """cape_map_upload_tracks: a MAP_TRACK_DTYPE array parallel to the planes of the last upload_map (covariance, counters and
+        flags are read).  A later upload_map discards the tracks."""
+        T = np.ascontiguousarray(tracks, MAP_TRACK_DTYPE).reshape(-1)
+        _check(self.L, self.L.cape_map_upload_tracks(self.h, T.ctypes.data_as(C.c_void_p), len(T)), "cape_map_upload_tracks")
+
+    def map_kalman(self, n_frames, stream=0):
+        """cape_map_kalman: per frame of [0, n_frames) and per map plane the Kalman step on the match of the last match_map_wide and
+        the rows of the last map_measure, the counters and the promote / drop / lost decisions.  The results are map_fusions'."""
+        _check(self.L, self.L.cape_map_kalman(self.h, n_frames, C.c_void_p(stream)), "cape_map_kalman")
+        self.kalman_map_size = self.map_size
+
+    def map_kalman_rows(self, n_frames):
+        """(frames: FRAME_MAP_KALMAN_DTYPE[n_frames], rows: PLANE_FUSION_DTYPE[n_frames, 128], track_results:
+        MAP_TRACK_RESULT_DTYPE[n_frames, n_map]) of the last map_kalman; n_map is the map size of that call."""
+        n_map = getattr(self, "kalman_map_size", 0)
+        frames = np.zeros(n_frames, FRAME_MAP_KALMAN_DTYPE)
+        rows = np.zeros((n_frames, MATCH_MAP_WIDE_MAX_PLANES), PLANE_FUSION_DTYPE)
+        results = np.zeros((n_frames, max(n_map, 1)), MAP_TRACK_RESULT_DTYPE)
+        _check(self.L, self.L.cape_copy_map_kalman(self.h, n_frames, *(a.ctypes.data_as(C.c_void_p) for a in (frames, rows, results))),
+               "cape_copy_map_kalman")
+        return frames, rows, results[:, :n_map]
+
+    def map_fusions(self, n_frames):
+        """Per frame of the last map_kalman: (header dict, fusions, track_results) -- fusions a list in kept-plane order, one dict per
+        kept plane (map_plane or -1, flags FUSION_*, the map plane's new normal, d, covariance 4 x 4 and the frame x_axis, y_axis,
+        center the polygon union projects into), track_results the MAP_TRACK_RESULT_DTYPE row of the frame (one entry per map plane)."""
+        frames, rows, results = self.map_kalman_rows(n_frames)
+        out = []
+        for f in range(n_frames):
+            n_cur = 0 if frames[f]["flags"] & MATCH_EXACT_OVERFLOW else min(int(frames[f]["n_cur"]), MATCH_MAP_WIDE_MAX_PLANES)
+            out.append(({name: int(frames[f][name]) for name in frames.dtype.names}, _fusion_dicts(rows[f], n_cur), results[f].copy()))
+        return out
+
     def map_visibility(self, n_frames, world_to_camera=None, moving=None, stream=0):
         """cape_map_visibility: the skip words of match_map / match_map_shards decided on the device -- bit j of frame (or slot) f set
         = map plane j is moving or not visible from world_to_camera[f] (n_frames x 4 x 4, None: identity).  moving: ceil(n_map / 32)
@@ -1239,7 +1337,7 @@ def debug_eval(op, a, b=None):
     L = load_library()
     a = np.ascontiguousarray(a, np.float64)
     n = a.shape[0]
-    out_w = {"eigen3": 12, "fit_plane": 10, "plane_cov": 17, "world_plane_cov": 17}.get(op, 1)
+    out_w = {"eigen3": 12, "fit_plane": 10, "plane_cov": 17, "world_plane_cov": 17, "kalman": 21, "plane_frame": 7}.get(op, 1)
     out = np.zeros((n, out_w) if out_w > 1 else n, np.float64)
     bb = np.ascontiguousarray(b, np.float64) if b is not None else None
     _check(L, L.cape_debug_eval(DEBUG_OPS[op], a.ctypes.data_as(C.c_void_p),
