@@ -924,6 +924,62 @@ int cape_copy_map_kalman(cape_handle h, int32_t n_frames, cape_frame_map_kalman*
  * CAPE_ERR_CAPACITY when no cape_map_kalman has run on the current batch, map and measurements. */
 int cape_device_map_kalman(cape_handle h, cape_frame_map_kalman** frames, cape_plane_fusion** rows, cape_map_track_result** track_results);
 
+/* The POLYGON half of the map update on the device, for the case a running map consists of almost entirely: a map plane without
+ * holes whose union with the detection creates no hole.  Per frame f of [0, n_frames) and per pair cape_map_kalman reports as
+ * UPDATED -- the fusion row of kept plane i has map_plane = j >= 0 and CAPE_FUSION_FRAME, the measurement row has CAPE_MEASURE_KEPT and
+ * lacks CAPE_MEASURE_FAIL_POLYGON, and match[j] == i -- the polygon step of cape_host_map_update (host/polygon_capi.cpp) in the host's order and with its
+ * early exits: the map plane's outer ring, projected into the fusion frame unless Polygon::project's isApprox shortcut holds, the
+ * detection's world ring of cape_map_measure projected into the map polygon's frame, merge_union (the arrangement of the two rings,
+ * the outer face, every other face with its probe point, drop_collinear, the disjoint rule, ring_is_simple) and simplify().  Every
+ * frame sees the same uploaded map and every pair is independent: nothing is written into the map, the tracks, the matches, the
+ * measurements or the fusion rows.  A served ring is the host class's bit for bit (vertex coordinates are + - x / only); sqrt, hypot
+ * and atan2 feed comparisons only, and an angle comparison of the face walk inside a guard band of 1e-10 rad hands the pair to the
+ * host.  Everything else is reported as the host's, per pair: cape_host_map_update remains the answer for those pairs. */
+#define CAPE_MAP_UNION_MAX_RING 128        /* vertices of either operand's outer ring the device serves */
+#define CAPE_MAP_UNION_MAX_NODES 512       /* nodes of the arrangement of the two rings */
+#define CAPE_MAP_UNION_FRAME_VERTICES 2048 /* result vertices of one frame's pairs */
+enum
+{
+    CAPE_UNION_SERVED = 1u << 0,         /* frame, area and ring are the new map polygon's; no OVERFLOW is possible (<= 512 vertices, no hole) */
+    CAPE_UNION_UNCHANGED = 1u << 1,      /* with SERVED: merge_union returned false, the ring is the PROJECTED map ring, not simplified */
+    CAPE_UNION_DISJOINT = 1u << 2,       /* with SERVED: the operands are two disjoint pieces and the ring is the bigger one's -- chosen by
+                                            merge_union's disjoint rule, or because the outer face walked from the leftmost node already
+                                            is the bigger piece (no vertex of the other operand lies inside or on it) */
+    CAPE_UNION_HOST_MAP_HOLES = 1u << 3, /* the map plane has interior rings */
+    CAPE_UNION_HOST_NEW_HOLE = 1u << 4,  /* the union encloses a face merge_union would add as a hole */
+    CAPE_UNION_HOST_CAPACITY = 1u << 5,  /* an operand > MAX_RING, nodes > MAX_NODES, a node of more than 8 neighbours, a walk that
+                                            reaches its guard, or the frame's vertex slab is full */
+    CAPE_UNION_HOST_AMBIGUOUS = 1u << 6  /* an angle comparison of the face walk lies inside the guard band */
+};
+/* One row per kept plane i < 128 of a frame, like the fusion rows.  A pair with a CAPE_UNION_HOST_* bit carries no ring:
+ * vertex_count = 0 and area = 0.  The frame is the new map polygon's: the fusion row's, except where the isApprox shortcut kept the
+ * map polygon's own frame (equal to it within 1e-12). */
+typedef struct cape_plane_union
+{
+    double x_axis[3], y_axis[3], center[3]; /* the fusion row's frame, repeated -- or the map polygon's own frame where the isApprox
+                                               shortcut kept it */
+    double area;                            /* Polygon::_area after the step */
+    uint32_t vertex_offset, vertex_count;   /* in the frame's slab of CAPE_MAP_UNION_FRAME_VERTICES (x, y) pairs */
+    int32_t map_plane;                      /* -1: no pair for this kept plane, row otherwise zero */
+    uint32_t flags;
+    uint32_t n_nodes, pad;                  /* arrangement nodes of a served pair (diagnostic) */
+} cape_plane_union;
+/* Needs a cape_map_kalman on the current batch, map, tracks and measurements covering n_frames -- otherwise CAPE_ERR_CAPACITY.
+ * CAPE_ERR_INVALID_ARGUMENT: NULL handle, n_frames < 0.  A frame the wide match flagged CAPE_MATCH_EXACT_OVERFLOW writes zeros.  The
+ * wave of a frame walks its pairs in kept-plane order and appends each served ring to the frame's slab, so the offsets are
+ * deterministic; a ring that does not fit the rest of the slab is CAPE_UNION_HOST_CAPACITY.  Every count read from the map, a row or
+ * a table is checked against its buffer before use.  Asynchronous on `stream`.  The results live in buffers of the handle's own,
+ * grown on demand, that no other call writes; whatever invalidates cape_map_kalman's results, and cape_map_kalman itself,
+ * invalidates them. */
+int cape_map_union(cape_handle h, int32_t n_frames, void* stream);
+/* Synchronous copy of the last cape_map_union: rows (n_frames x 128), vertices (n_frames x CAPE_MAP_UNION_FRAME_VERTICES x 2
+ * doubles).  Of a frame's slab only the first sum-of-vertex_count vertices are defined: the call writes the served rings back to back
+ * and nothing behind them.  Either pointer may be NULL.  CAPE_ERR_CAPACITY beyond what the call covered. */
+int cape_copy_map_union(cape_handle h, int32_t n_frames, cape_plane_union* rows /* n_frames x 128 */, double* vertices);
+/* Device pointers of the same arrays.  Either may be NULL.  CAPE_ERR_CAPACITY when no cape_map_union has run on the current batch,
+ * map, match, measurements and Kalman results. */
+int cape_device_map_union(cape_handle h, cape_plane_union** rows, double** vertices);
+
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
  * the `stream` argument of the calls below; destroy it before the handle. */
@@ -1091,6 +1147,14 @@ int cape_debug_polygon_queue(cape_handle h, uint32_t* reserved, uint32_t* ticket
  * intersection kernel was handed, [8 + 4 * tier + reason] pairs that left tier `tier` for a larger one because of reason 1 = ring
  * vertices, 2 = slab boundaries, 3 = edges over one slab */
 int cape_debug_match_lists(cape_handle h, uint32_t* words32);
+/* cape_map_union's per-pair device function on a one-pair launch (tests; synchronous; the results of the last cape_map_union are not
+ * disturbed): how disjoint operands, containment, T-junctions and capacity overflows -- pairs the matcher would never make -- reach
+ * the kernel.  All pointers are HOST pointers.  ring_a plays the map plane's outer ring (n_a vertices, (x, y) pairs), ring_b the
+ * detection's world ring; frames27 = (x_axis, y_axis, center) of ring a's frame, of ring b's frame and of the target (fusion) frame,
+ * NULL = the canonical frame (1,0,0), (0,1,0), (0,0,0) for all three.  row_out: one cape_plane_union (map_plane = 0); vertices_out:
+ * room for CAPE_MAP_MAX_RING (x, y) pairs.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, ring or output, n_a or n_b outside [3, 4096]. */
+int cape_debug_ring_union(cape_handle h, const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
+                          cape_plane_union* row_out, double* vertices_out);
 
 /* The seed of the reference's random engine (src/utils/random.hpp:59-64): 0 under MAKE_DETERMINISTIC -- the default here, and the
  * mode BASELINE.json's bit-exactness is stated for --, `std::time(0)` taken once at process start otherwise.  The engine is

@@ -179,4 +179,39 @@ int cape_debug_match_lists(cape_handle h, uint32_t* words32)
     return CAPE_OK;
 }
 
+int cape_debug_ring_union(cape_handle h, const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
+                          cape_plane_union* row_out, double* vertices_out)
+{
+    static const double kCanonical[27] = {1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0};
+    if (!h || !ring_a || !ring_b || !row_out || !vertices_out || n_a < 3 || n_b < 3 || n_a > 4096 || n_b > 4096)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument or a ring of fewer than 3 / more than 4096 vertices");
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    // a one-pair launch over buffers of its own (freed on the way out): the results of the last cape_map_union are not touched
+    Buffer<double> a, b, frames, verts;
+    Buffer<cape_plane_union> row;
+    CAPE_HIP_TRY(a.alloc((size_t)n_a * 2));
+    CAPE_HIP_TRY(b.alloc((size_t)n_b * 2));
+    CAPE_HIP_TRY(frames.alloc(27));
+    CAPE_HIP_TRY(verts.alloc((size_t)CAPE_MAP_MAX_RING * 2));
+    CAPE_HIP_TRY(row.alloc(1));
+    CAPE_HIP_TRY(hipMemcpy(a, ring_a, (size_t)n_a * 2 * sizeof(double), hipMemcpyHostToDevice));
+    CAPE_HIP_TRY(hipMemcpy(b, ring_b, (size_t)n_b * 2 * sizeof(double), hipMemcpyHostToDevice));
+    CAPE_HIP_TRY(hipMemcpy(frames, frames27 ? frames27 : kCanonical, 27 * sizeof(double), hipMemcpyHostToDevice));
+    cape::RingUnionParams p{};
+    p.ringA = reinterpret_cast<const double2*>(a.get());
+    p.ringB = reinterpret_cast<const double2*>(b.get());
+    p.nA = n_a;
+    p.nB = n_b;
+    p.frames27 = frames;
+    p.row = row;
+    p.vertices = reinterpret_cast<double2*>(verts.get());
+    CAPE_HIP_TRY(cape::launch_ring_union(p, nullptr));
+    CAPE_HIP_TRY(hipDeviceSynchronize());
+    CAPE_HIP_TRY(copy_out(row_out, row, 0, 1));
+    const size_t n = row_out->vertex_count <= CAPE_MAP_MAX_RING ? row_out->vertex_count : 0;
+    CAPE_HIP_TRY(copy_out(vertices_out, verts, 0, n * 2));
+    return CAPE_OK;
+}
+
 } // extern "C"

@@ -212,6 +212,13 @@ bool kalman_results_live(const cape_handle_s* h)
     return K.kalmanFrames > 0 && h->mapWide.matchFrames >= K.kalmanFrames && h->measure.frames >= K.kalmanFrames;
 }
 
+// ... and those of the last cape_map_union the Kalman results they were made from
+bool union_results_live(const cape_handle_s* h)
+{
+    const auto& U = h->mapUnion;
+    return U.unionFrames > 0 && kalman_results_live(h) && h->kalman.kalmanFrames >= U.unionFrames && U.kalmanRun == h->kalman.runs;
+}
+
 } // namespace
 
 extern "C" {
@@ -1207,6 +1214,7 @@ int cape_map_kalman(cape_handle h, int32_t n_frames, void* stream_)
     CAPE_HIP_TRY(cape::launch_map_kalman(p, n_frames, stream));
     K.kalmanFrames = n_frames;
     K.kalmanN = nMap;
+    ++K.runs; // (cape_map_union's results belong to the rows this call replaced)
     return CAPE_OK;
 }
 
@@ -1241,6 +1249,82 @@ int cape_copy_map_kalman(cape_handle h, int32_t n_frames, cape_frame_map_kalman*
     CAPE_HIP_TRY(copy_out(frames, K.frames, 0, (size_t)n_frames));
     CAPE_HIP_TRY(copy_out(rows, K.rows, 0, (size_t)n_frames * WP));
     CAPE_HIP_TRY(copy_out(track_results, K.trackResults, 0, (size_t)n_frames * (size_t)K.kalmanN));
+    return CAPE_OK;
+}
+
+int cape_map_union(cape_handle h, int32_t n_frames, void* stream_)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
+    auto& U = h->mapUnion;
+    const auto& K = h->kalman;
+    const auto& W = h->mapWide;
+    const auto& M = h->measure;
+    U.unionFrames = 0;
+    if (!kalman_results_live(h) || n_frames > K.kalmanFrames || K.kalmanN != h->map.n)
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_kalman on the current batch, map, tracks and measurements covers n_frames");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be writing them
+    CAPE_HIP_TRY(U.rows.grow((size_t)n_frames * WP, drain));
+    CAPE_HIP_TRY(U.vertices.grow((size_t)n_frames * SLAB * 2, drain));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StreamScope streamScope(h, stream);
+    if (streamScope.rc() != CAPE_OK)
+        return streamScope.rc();
+    cape::MapUnionParams p{};
+    p.mapPlanes = h->map.planes;
+    p.mapRings = h->map.rings;
+    p.mapVertices = reinterpret_cast<const double2*>(h->map.vertices.get());
+    p.nMap = h->map.n;
+    p.nMapRings = (unsigned)h->map.rings.size();
+    p.nMapVertices = (unsigned long long)(h->map.vertices.size() / 2);
+    p.matchFrames = W.frames;
+    p.match = W.match;
+    p.kept = W.kept;
+    p.measurements = M.rows;
+    p.worldVertices = reinterpret_cast<const double2*>(M.vertices.get());
+    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows and slabs cape_map_measure allocated: one per record)
+    p.boundaryCapacity = h->boundaryCap;
+    p.fusion = K.rows;
+    p.rows = U.rows;
+    p.vertices = reinterpret_cast<double2*>(U.vertices.get());
+    CAPE_HIP_TRY(cape::launch_map_union(p, n_frames, stream));
+    U.unionFrames = n_frames;
+    U.kalmanRun = K.runs;
+    return CAPE_OK;
+}
+
+int cape_device_map_union(cape_handle h, cape_plane_union** rows, double** vertices)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    if (!union_results_live(h))
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_union has run on the current batch, map, match, measurements and Kalman results");
+    if (rows)
+        *rows = h->mapUnion.rows;
+    if (vertices)
+        *vertices = h->mapUnion.vertices;
+    return CAPE_OK;
+}
+
+int cape_copy_map_union(cape_handle h, int32_t n_frames, cape_plane_union* rows, double* vertices)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    const auto& U = h->mapUnion;
+    if (n_frames > (union_results_live(h) ? U.unionFrames : 0))
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_union on the current batch, map, match, measurements and Kalman results");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(copy_out(rows, U.rows, 0, (size_t)n_frames * WP));
+    CAPE_HIP_TRY(copy_out(vertices, U.vertices, 0, (size_t)n_frames * SLAB * 2));
     return CAPE_OK;
 }
 

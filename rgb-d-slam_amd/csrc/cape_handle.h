@@ -35,6 +35,8 @@ hipError_t launch_carry_save(const CarrySaveParams& p, hipStream_t stream);
 hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_measure(const MapMeasureParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_kalman(const MapKalmanParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_ring_union(const RingUnionParams& p, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -466,7 +468,18 @@ struct cape_handle_s
         Buffer<cape_map_track_result> trackResults; // frames x n_map of the call
         int kalmanFrames = 0;                     // frames of the last cape_map_kalman (0: none for the current batch, map, match and measurements)
         int kalmanN = 0;                          // map planes of that call
+        unsigned runs = 0;                        // cape_map_kalman calls that launched: what cape_map_union's results belong to
     } kalman;
+
+    // cape_map_union: the polygon half of the map update for the frames of the last call.  Result buffers of its own, grown on demand
+    // behind drain_handle: no other call writes them.  (Declared last, like the struct above.)
+    struct Union
+    {
+        Buffer<cape_plane_union> rows; // frames x 128
+        Buffer<double> vertices;       // frames x CAPE_MAP_UNION_FRAME_VERTICES x 2
+        int unionFrames = 0;           // frames of the last cape_map_union (0: none)
+        unsigned kalmanRun = 0;        // Kalman::runs when it ran: a later cape_map_kalman invalidates the results
+    } mapUnion;
 };
 
 namespace cape::abi {

@@ -380,6 +380,40 @@ struct MapKalmanParams
     cape_map_track_result* trackResults;       // frames x nMap
 };
 
+// cape_map_union (cape_map_union.hip): the polygon half of the map update, per frame against the uploaded map
+struct MapUnionParams
+{
+    // the map (cape_map_upload; rings already re-oriented) and what its ring and vertex buffers hold
+    const cape_map_plane* mapPlanes;
+    const cape_map_ring* mapRings;
+    const double2* mapVertices;
+    int nMap;
+    unsigned nMapRings;
+    unsigned long long nMapVertices;
+    // the last cape_match_map_wide
+    const cape_frame_map_match_wide* matchFrames;
+    const int32_t* match; // frames x nMap
+    const uint2* kept;    // frames x 128: (record, segment in that record) of kept plane i
+    // the last cape_map_measure: rows and world-vertex slabs per record
+    const cape_plane_measurement* measurements;
+    const double2* worldVertices;
+    int nRecords, boundaryCapacity;
+    // the last cape_map_kalman
+    const cape_plane_fusion* fusion; // frames x 128
+    // results
+    cape_plane_union* rows; // frames x 128
+    double2* vertices;      // frames x CAPE_MAP_UNION_FRAME_VERTICES
+};
+// cape_debug_ring_union: one pair, everything in device memory (frames27: ring a's frame, ring b's, the target)
+struct RingUnionParams
+{
+    const double2 *ringA, *ringB;
+    int nA, nB;
+    const double* frames27;
+    cape_plane_union* row;
+    double2* vertices; // CAPE_MAP_MAX_RING
+};
+
 // multi-GPU gather: device-side packing of the ragged primitive lists (cape_gather.hip)
 struct PackParams
 {

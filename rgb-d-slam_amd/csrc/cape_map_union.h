@@ -1,0 +1,864 @@
+// The polygon half of the map update for one matched pair (cape_map_union.hip, cape_debug_ring_union): the statements of
+// Polygon::project, merge_union, rings_union_outer, drop_collinear, ring_is_simple, simplify, douglas_peucker and segment_distance2 of
+// host/boundary_polygon.cpp in the host's order and with its early exits, for a map polygon without holes, on ONE wavefront.
+//
+// Two parts.  The first holds the plain per-lane functions (projection, cut parameters, crossing points, the angle of the face walk
+// with its guard band, the collinear test, the Douglas-Peucker distance): they need nothing of the wave and compile for the host too
+// (tests/host/map_union_algebra.cpp compares them with the host class under the sanitizers).  The second, under __HIPCC__, is the
+// wave's part: the LDS carve, node_of's search (ballot, lowest set lane), the walks, the point tests, ring_is_simple and the
+// Douglas-Peucker loop.  What the host orders is uniform control flow: node numbering, the walks, drop_collinear's erase loop.
+//
+// segments_intersect, ring_is_simple and the Douglas-Peucker loop are restated here rather than shared with cape_polygon.hip: that
+// file walks rings of indices into a point array, this one rings of coordinates, and cape_polygon.o stays byte for byte what it was.
+//
+// Vertex coordinates are + - x / only (-ffp-contract=off), so a served ring is the host's bit for bit.  sqrt (param_on), hypot
+// (drop_collinear, the probe) and atan2 (next_of) feed comparisons only; the angles carry a guard band of 1e-10 rad that hands the
+// pair to the host (CAPE_UNION_HOST_AMBIGUOUS; union_angle says which comparisons are exact on both sides and exempt); a hypot
+// threshold tie has no guard.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/cape_hip.h"
+
+namespace cape {
+
+namespace {
+
+constexpr int kUnionRing = CAPE_MAP_UNION_MAX_RING;   // vertices of an operand
+constexpr int kUnionNodes = CAPE_MAP_UNION_MAX_NODES; // nodes of the arrangement
+constexpr int kUnionDegree = 8;                       // neighbours of a node
+constexpr int kUnionCuts = 1024;                      // cuts of all segments (each crossing cuts two segments)
+constexpr int kUnionOut = CAPE_MAP_MAX_RING;          // vertices of a walked face; the closed ring of simplify takes one more
+constexpr double kUnionAngleBand = 1e-10;             // rad: the guard band of the face walk's angle comparisons
+constexpr double kUnionTwoPi = 2 * 3.14159265358979323846;
+
+struct UnionFrame
+{
+    double x[3], y[3], c[3];
+};
+
+__device__ __forceinline__ double umin(double a, double b) { return (b < a) ? b : a; } // std::min
+__device__ __forceinline__ double umax(double a, double b) { return (a < b) ? b : a; } // std::max
+__device__ __forceinline__ double ucross2(const double2& o, const double2& a, const double2& b)
+{
+    return (a.x - o.x) * (b.y - o.y) - (a.y - o.y) * (b.x - o.x);
+}
+__device__ __forceinline__ bool usame(const double2& a, const double2& b, double eps) { return fabs(a.x - b.x) <= eps && fabs(a.y - b.y) <= eps; }
+
+// Eigen's isApprox on 3-vectors (host/polygon_capi.cpp: is_approx3)
+__device__ __forceinline__ bool union_is_approx3(const double* a, const double* b)
+{
+    const double e0 = a[0] - b[0], e1 = a[1] - b[1], e2 = a[2] - b[2];
+    const double diff = (e0 * e0 + e1 * e1) + e2 * e2;
+    const double na = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], nb = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+    const double prec = 1e-12;
+    return diff <= prec * prec * umin(na, nb);
+}
+
+// get_projected_plan_coordinates(get_point_from_plane_coordinates(p, from), to): one vertex of Polygon::project
+__device__ __forceinline__ double2 union_project(const double2& p, const UnionFrame& from, const UnionFrame& to)
+{
+    const double q0 = from.c[0] + p.x * from.x[0] + p.y * from.y[0];
+    const double q1 = from.c[1] + p.x * from.x[1] + p.y * from.y[1];
+    const double q2 = from.c[2] + p.x * from.x[2] + p.y * from.y[2];
+    const double d0 = q0 - to.c[0], d1 = q1 - to.c[1], d2 = q2 - to.c[2];
+    return make_double2((to.x[0] * d0 + to.x[1] * d1) + to.x[2] * d2, (to.y[0] * d0 + to.y[1] * d1) + to.y[2] * d2);
+}
+
+// param_on of rings_union_outer: is p on the segment (a, b) within eps, strictly between its ends?  t = its position
+__device__ __forceinline__ bool union_param_on(const double2& a, const double2& b, const double2& p, double eps, double& t)
+{
+    const double dx = b.x - a.x, dy = b.y - a.y;
+    const double len2 = dx * dx + dy * dy;
+    const double c = ucross2(a, b, p);
+    if (fabs(c) > eps * sqrt(len2))
+        return false;
+    t = ((p.x - a.x) * dx + (p.y - a.y) * dy) / len2;
+    return t > 0 && t < 1 && !usame(p, a, eps) && !usame(p, b, eps);
+}
+
+// the proper crossing of (sa, sb) and (ua, ub): the two cut parameters, and whether each is kept (the crossing point is not within
+// eps of an end of its segment).  False without a proper crossing.
+__device__ __forceinline__ bool union_crossing(const double2& sa, const double2& sb, const double2& ua, const double2& ub, double eps, double& ts,
+                                               bool& keepS, double& tu, bool& keepU)
+{
+    const double d1 = ucross2(ua, ub, sa), d2 = ucross2(ua, ub, sb);
+    const double d3 = ucross2(sa, sb, ua), d4 = ucross2(sa, sb, ub);
+    if (!(((d1 > 0 && d2 < 0) || (d1 < 0 && d2 > 0)) && ((d3 > 0 && d4 < 0) || (d3 < 0 && d4 > 0))))
+        return false;
+    ts = d1 / (d1 - d2);
+    tu = d3 / (d3 - d4);
+    const double2 x = make_double2(sa.x + ts * (sb.x - sa.x), sa.y + ts * (sb.y - sa.y));
+    keepS = !usame(x, sa, eps) && !usame(x, sb, eps);
+    keepU = !usame(x, ua, eps) && !usame(x, ub, eps);
+    return true;
+}
+
+// the point of a cut: a + t (b - a)
+__device__ __forceinline__ double2 union_cut_point(const double2& a, const double2& b, double t)
+{
+    return make_double2(a.x + t * (b.x - a.x), a.y + t * (b.y - a.y));
+}
+
+// One candidate of next_of: the counter-clockwise angle from the direction `ba` (an atan2) to the neighbour at (dx, dy), wrapped into
+// (1e-12, 2 pi + 1e-12] like the host's while loop.  `ambiguous` is set when the unwrapped angle lies within the guard band of the
+// wrap line, unless the candidate is `exact`: the node the walk came from (its direction IS `back`, the same atan2 of the same bits
+// twice), or a candidate whose direction and `back` are both axis-parallel (union_axis_parallel: every atan2 involved is one of
+// +-0, +-pi/2, +-pi by the C and OpenCL standards alike -- the vertical edge above the start node is the everyday case).
+__device__ __forceinline__ bool union_axis_parallel(double dx, double dy, double bx, double by) { return (dx == 0 || dy == 0) && (bx == 0 || by == 0); }
+__device__ __forceinline__ double union_angle(double dy, double dx, double ba, bool cameFrom, bool& ambiguous)
+{
+    double ang = atan2(dy, dx) - ba;
+    for (int turn = 0; turn < 3 && ang <= 1e-12; ++turn) // (the angle starts above -2 pi - 1e-12: two turns at most)
+    {
+        if (!cameFrom && fabs(ang - 1e-12) < kUnionAngleBand)
+            ambiguous = true;
+        ang += kUnionTwoPi;
+    }
+    if (!cameFrom && fabs(ang - 1e-12) < kUnionAngleBand)
+        ambiguous = true;
+    return ang;
+}
+
+// drop_collinear's test: b lies on the segment joining its neighbours a and c
+__device__ __forceinline__ bool union_collinear(const double2& a, const double2& b, const double2& c)
+{
+    const double cr = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x);
+    const double len = hypot(c.x - a.x, c.y - a.y);
+    return fabs(cr) <= 1e-9 * umax(1.0, len * len);
+}
+
+// segments_intersect: proper or touching intersection of the open segments; shared endpoints do not count
+__device__ __forceinline__ bool union_segments_intersect(const double2& a1, const double2& a2, const double2& b1, const double2& b2)
+{
+    if (umax(a1.x, a2.x) < umin(b1.x, b2.x) || umax(b1.x, b2.x) < umin(a1.x, a2.x) || umax(a1.y, a2.y) < umin(b1.y, b2.y) ||
+        umax(b1.y, b2.y) < umin(a1.y, a2.y))
+        return false;
+    if ((a1.x == b1.x && a1.y == b1.y) || (a1.x == b2.x && a1.y == b2.y) || (a2.x == b1.x && a2.y == b1.y) || (a2.x == b2.x && a2.y == b2.y))
+        return false;
+    const double d1 = ucross2(b1, b2, a1), d2 = ucross2(b1, b2, a2), d3 = ucross2(a1, a2, b1), d4 = ucross2(a1, a2, b2);
+    if (((d1 > 0 && d2 < 0) || (d1 < 0 && d2 > 0)) && ((d3 > 0 && d4 < 0) || (d3 < 0 && d4 > 0)))
+        return true;
+    if (d1 == 0 && umin(b1.x, b2.x) <= a1.x && a1.x <= umax(b1.x, b2.x) && umin(b1.y, b2.y) <= a1.y && a1.y <= umax(b1.y, b2.y))
+        return true;
+    if (d2 == 0 && umin(b1.x, b2.x) <= a2.x && a2.x <= umax(b1.x, b2.x) && umin(b1.y, b2.y) <= a2.y && a2.y <= umax(b1.y, b2.y))
+        return true;
+    if (d3 == 0 && umin(a1.x, a2.x) <= b1.x && b1.x <= umax(a1.x, a2.x) && umin(a1.y, a2.y) <= b1.y && b1.y <= umax(a1.y, a2.y))
+        return true;
+    if (d4 == 0 && umin(a1.x, a2.x) <= b2.x && b2.x <= umax(a1.x, a2.x) && umin(a1.y, a2.y) <= b2.y && b2.y <= umax(a1.y, a2.y))
+        return true;
+    return false;
+}
+
+// segment_distance2: Boost's projected_point strategy in its comparable form, the measure of its Douglas-Peucker
+__device__ __forceinline__ double union_segment_distance2(const double2& p, const double2& a, const double2& b)
+{
+    const double vx = b.x - a.x, vy = b.y - a.y, wx = p.x - a.x, wy = p.y - a.y;
+    const double c1 = wx * vx + wy * vy;
+    if (c1 <= 0)
+        return wx * wx + wy * wy;
+    const double c2 = vx * vx + vy * vy;
+    if (c2 <= c1)
+    {
+        const double ux = p.x - b.x, uy = p.y - b.y;
+        return ux * ux + uy * uy;
+    }
+    const double t = c1 / c2;
+    const double qx = a.x + t * vx, qy = a.y + t * vy;
+    return (p.x - qx) * (p.x - qx) + (p.y - qy) * (p.y - qy);
+}
+
+// one edge (a = ring[i], b = ring[i - 1]) of point_in_ring: 2 = p lies on the edge, 1 = the ray towards +x crosses it, 0 = neither
+__device__ __forceinline__ int union_point_edge(const double2& p, const double2& a, const double2& b)
+{
+    if (ucross2(a, b, p) == 0 && umin(a.x, b.x) <= p.x && p.x <= umax(a.x, b.x) && umin(a.y, b.y) <= p.y && p.y <= umax(a.y, b.y))
+        return 2;
+    if (((a.y > p.y) != (b.y > p.y)) && (p.x < (b.x - a.x) * (p.y - a.y) / (b.y - a.y) + a.x))
+        return 1;
+    return 0;
+}
+
+} // namespace
+
+} // namespace cape
+
+#ifdef __HIPCC__
+#include "cape_layout.h"
+#include "cape_ring_area.h" // CAPE_MP_SYNC, ring_area_signed (the ordered sum)
+#include "cape_wave.h"
+
+namespace cape {
+
+namespace {
+
+// ---- the wave's carve: both operands, the segment and cut lists, the arrangement, two walked rings and simplify's arrays
+struct UnionLdsLayout
+{
+    size_t ringA, ringB, segs, cutT, cutSeg, sortT, sortSeg, nodes, adj, deg, seen, outer, face, keep, stack, bytes;
+};
+constexpr int kUnionStack = kUnionOut + 8;
+__host__ __device__ constexpr UnionLdsLayout union_layout()
+{
+    Layout l;
+    UnionLdsLayout o{};
+    o.ringA = l.take<double2>(kUnionRing + 1, 16); // (+ 1: simplify closes a ring onto its vertex 0)
+    o.ringB = l.take<double2>(kUnionRing, 16);
+    o.segs = l.take<unsigned short>(2 * kUnionRing); // bit 8: ring B; low bits: the first vertex of the segment
+    o.cutT = l.take<double>(kUnionCuts);
+    o.cutSeg = l.take<unsigned short>(kUnionCuts);
+    o.nodes = l.take<double2>(kUnionNodes, 16);
+    o.adj = l.take<unsigned short>((size_t)kUnionNodes * kUnionDegree);
+    o.deg = l.take<unsigned char>(kUnionNodes);
+    o.seen = l.take<unsigned char>(kUnionNodes); // bit k: the directed edge to neighbour k has been walked
+    o.outer = l.take<double2>(kUnionOut + 1, 16);
+    const size_t outerEnd = l.off;
+    o.face = l.take<double2>(kUnionOut + 1, 16);
+    const size_t faceEnd = l.off;
+    // the sorted cuts live where the walked rings will: they are consumed by the node numbering, before the first walk
+    o.sortT = l.alias<double>(o.outer, kUnionCuts, outerEnd);
+    o.sortSeg = l.alias<unsigned short>(o.face, kUnionCuts, faceEnd);
+    o.keep = l.take<unsigned char>(kUnionOut + 1);
+    o.stack = l.take<unsigned>(kUnionStack);
+    o.bytes = l.end(16);
+    return o;
+}
+static_assert(kUnionCuts * sizeof(double) <= (kUnionOut + 1) * sizeof(double2), "the sorted cuts fit the outer ring's place");
+static_assert(union_layout().bytes <= 64 * 1024, "one wave's carve fits the default LDS limit of a workgroup");
+static_assert(kUnionRing <= 256 && kUnionNodes <= 65535 && kUnionDegree <= 8 && kUnionOut < 65536, "the packed indices");
+
+struct UnionLds
+{
+    double2 *ringA, *ringB, *nodes, *outer, *face;
+    unsigned short *segs, *cutSeg, *sortSeg, *adj;
+    double *cutT, *sortT;
+    unsigned char *deg, *seen, *keep;
+    unsigned* stack;
+};
+__device__ __forceinline__ UnionLds union_carve(unsigned char* smem)
+{
+    constexpr UnionLdsLayout o = union_layout();
+    UnionLds L;
+    L.ringA = carve_at<double2>(smem, o.ringA);
+    L.ringB = carve_at<double2>(smem, o.ringB);
+    L.segs = carve_at<unsigned short>(smem, o.segs);
+    L.cutT = carve_at<double>(smem, o.cutT);
+    L.cutSeg = carve_at<unsigned short>(smem, o.cutSeg);
+    L.sortT = carve_at<double>(smem, o.sortT);
+    L.sortSeg = carve_at<unsigned short>(smem, o.sortSeg);
+    L.nodes = carve_at<double2>(smem, o.nodes);
+    L.adj = carve_at<unsigned short>(smem, o.adj);
+    L.deg = carve_at<unsigned char>(smem, o.deg);
+    L.seen = carve_at<unsigned char>(smem, o.seen);
+    L.outer = carve_at<double2>(smem, o.outer);
+    L.face = carve_at<double2>(smem, o.face);
+    L.keep = carve_at<unsigned char>(smem, o.keep);
+    L.stack = carve_at<unsigned>(smem, o.stack);
+    return L;
+}
+
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the orientation the host class gives an outer ring: reversed when its signed area is positive (every lane reads the whole ring
+// before any lane rewrites it)
+__device__ __forceinline__ void union_orient(double2* ring, int n, int lane)
+{
+    const double s = ring_area_signed(ring, n);
+    CAPE_MP_SYNC();
+    if (s > 0)
+    {
+        for (int v = lane; v < n / 2; v += 64)
+        {
+            const double2 a = ring[v], b = ring[n - 1 - v];
+            ring[v] = b;
+            ring[n - 1 - v] = a;
+        }
+        CAPE_MP_SYNC();
+    }
+}
+
+// Polygon::area of a polygon without holes
+__device__ __forceinline__ double union_area(const double2* ring, int n)
+{
+    if (n < 3)
+        return 0.0;
+    const double a = fabs(ring_area_signed(ring, n));
+    return a < 0 ? 0.0 : a;
+}
+
+// point_in_ring: crossing number, points on the boundary count as inside when `closed`.  Lanes over the edges.
+__device__ __forceinline__ bool union_point_in_ring(const double2& p, const double2* ring, int n, bool closed, int lane)
+{
+    bool on = false, inside = false;
+    for (int i = lane; i < n; i += 64)
+    {
+        const int e = union_point_edge(p, ring[i], ring[i == 0 ? n - 1 : i - 1]);
+        on = on || e == 2;
+        inside = inside != (e == 1);
+    }
+    if (__any(on))
+        return closed;
+    return (__popcll(__ballot(inside)) & 1) != 0;
+}
+
+// is every vertex of q[0, nq) outside ring[0, n) (not inside, not on it)?  Lanes over the vertices, each walks the whole ring.
+__device__ __forceinline__ bool union_left_out(const double2* q, int nq, const double2* ring, int n, int lane)
+{
+    bool in = false;
+    for (int v = lane; v < nq; v += 64)
+    {
+        const double2 p = q[v];
+        bool on = false, inside = false;
+        for (int i = 0; i < n && !on; ++i)
+        {
+            const int e = union_point_edge(p, ring[i], ring[i == 0 ? n - 1 : i - 1]);
+            on = e == 2;
+            inside = inside != (e == 1);
+        }
+        in = in || on || inside;
+    }
+    return !__any(in);
+}
+
+// ring_is_simple: no two non-adjacent edges touch, and the area is not zero.  Lanes over the first edge of a pair.
+__device__ __forceinline__ bool union_ring_is_simple(const double2* r, int n, int lane)
+{
+    if (n < 3)
+        return false;
+    bool bad = false;
+    for (int base = 0, round = 0; base < n; base += 64, ++round)
+    {
+        const int i = base + ((round & 1) ? 63 - lane : lane);
+        if (i >= n)
+            continue;
+        const double2 a1 = r[i], a2 = r[i + 1 == n ? 0 : i + 1];
+        for (int j = i + 1; j < n && !bad; ++j)
+        {
+            if (j == i + 1 || (i == 0 && j == n - 1))
+                continue; // adjacent edges share a vertex
+            bad = union_segments_intersect(a1, a2, r[j], r[j + 1 == n ? 0 : j + 1]);
+        }
+    }
+    if (__any(bad))
+        return false;
+    return fabs(ring_area_signed(r, n)) > 0;
+}
+
+// drop_collinear: vertices on the segment joining their neighbours go, one at a time in ring order, until a pass changes nothing.
+// Uniform: every lane runs the test, the erase shifts the tail down 64 vertices at a time.  Returns the new length.
+__device__ __forceinline__ int union_drop_collinear(double2* r, int n, int lane)
+{
+    bool changed = true;
+    while (changed && n > 3)
+    {
+        changed = false;
+        for (int i = 0; i < n && n > 3; ++i)
+        {
+            const double2 a = r[i == 0 ? n - 1 : i - 1], b = r[i], c = r[i + 1 == n ? 0 : i + 1];
+            if (union_collinear(a, b, c))
+            {
+                for (int base = i; base + 1 < n; base += 64)
+                {
+                    const int k = base + lane;
+                    double2 v = make_double2(0.0, 0.0);
+                    if (k + 1 < n)
+                        v = r[k + 1];
+                    CAPE_MP_SYNC();
+                    if (k + 1 < n)
+                        r[k] = v;
+                    CAPE_MP_SYNC();
+                }
+                --n;
+                changed = true;
+                --i;
+            }
+        }
+    }
+    return n;
+}
+
+// Polygon::simplify of a polygon without holes: ring[0, n) (room for n + 1) becomes the Douglas-Peucker candidate if that is a
+// simple ring of more than 75 % of the area; `cand` takes the candidate (room for n).  Returns the new length; area in / out.
+__device__ __forceinline__ int union_simplify(const UnionLds& L, double2* ring, int n, double2* cand, double& area, int lane)
+{
+    area = union_area(ring, n);
+    if (n < 4 || n > kUnionOut)
+        return n;
+    const double eps = umax(area / 1e5, 10.0);
+    if (lane == 0)
+        ring[n] = ring[0]; // closed onto vertex 0
+    for (int i = lane; i <= n; i += 64)
+        L.keep[i] = (i == 0 || i == n) ? 1 : 0;
+    if (lane == 0)
+        L.stack[0] = (unsigned)n; // (a << 16) | b with a = 0
+    int sp = 1;
+    CAPE_MP_SYNC();
+    while (sp > 0)
+    {
+        const unsigned ab = L.stack[--sp];
+        const int a = uni((int)(ab >> 16)), b = uni((int)(ab & 0xFFFFu));
+        if (b <= a + 1 || b > n)
+            continue;
+        const double2 pa = ring[a], pb = ring[b];
+        unsigned long long best = 0ull; // squared distance bits (>= +0); the first index wins a tie, like the host's strict >
+        int bestI = 0x7FFFFFFF;
+        for (int i = a + 1 + lane; i < b; i += 64)
+        {
+            const double d = union_segment_distance2(ring[i], pa, pb);
+            const unsigned long long db = (unsigned long long)__double_as_longlong(d);
+            if (bestI == 0x7FFFFFFF || db > best)
+            {
+                best = db;
+                bestI = i;
+            }
+        }
+        const unsigned long long mx = ~wave_min_u64(~best);
+        const unsigned mineKey = (bestI != 0x7FFFFFFF && best == mx) ? (unsigned)(0x7FFFFFFF - bestI) : 0u;
+        const int idx = 0x7FFFFFFF - (int)wave_max_u32(mineKey);
+        const double dmax = __longlong_as_double((long long)mx);
+        if (dmax > eps * eps && idx > a && idx < b && sp + 2 <= kUnionStack)
+        {
+            if (lane == 0)
+            {
+                L.keep[idx] = 1;
+                L.stack[sp] = ((unsigned)a << 16) | (unsigned)idx;
+                L.stack[sp + 1] = ((unsigned)idx << 16) | (unsigned)b;
+            }
+            sp += 2;
+            CAPE_MP_SYNC();
+        }
+    }
+    int cn = 0;
+    for (int base = 0; base < n; base += 64)
+    {
+        const int i = base + lane;
+        const bool k = i < n && L.keep[i];
+        const unsigned long long kb = __ballot(k);
+        if (k)
+            cand[cn + __popcll(kb & ((1ull << lane) - 1ull))] = ring[i];
+        cn += __popcll(kb);
+    }
+    CAPE_MP_SYNC();
+    if (cn >= 3 && union_ring_is_simple(cand, cn, lane))
+    {
+        const double newArea = union_area(cand, cn);
+        if (newArea > area * 0.75)
+        {
+            CAPE_MP_SYNC();
+            for (int i = lane; i < cn; i += 64)
+                ring[i] = cand[i];
+            CAPE_MP_SYNC();
+            area = newArea;
+            return cn;
+        }
+    }
+    return n;
+}
+
+// ---- the arrangement of the two rings (rings_union_outer)
+struct UnionGraph
+{
+    int nNodes;
+    uint32_t fail; // CAPE_UNION_HOST_* bits met on the way
+    double eps;
+};
+
+// node_of: the first node within eps of p (lanes over the nodes, the lowest set lane of the first chunk with a hit), else a new one
+__device__ __forceinline__ int union_node_of(const UnionLds& L, UnionGraph& G, const double2& p, int lane)
+{
+    for (int base = 0; base < G.nNodes; base += 64)
+    {
+        const int k = base + lane;
+        const bool hit = k < G.nNodes && usame(L.nodes[k], p, G.eps);
+        const unsigned long long m = __ballot(hit);
+        if (m)
+            return base + __ffsll((long long)m) - 1;
+    }
+    if (G.nNodes >= kUnionNodes)
+    {
+        G.fail |= CAPE_UNION_HOST_CAPACITY;
+        return -1;
+    }
+    if (lane == 0)
+    {
+        L.nodes[G.nNodes] = p;
+        L.deg[G.nNodes] = 0;
+        L.seen[G.nNodes] = 0;
+    }
+    CAPE_MP_SYNC();
+    return G.nNodes++;
+}
+
+// link: an undirected edge, once
+__device__ __forceinline__ void union_link(const UnionLds& L, UnionGraph& G, int a, int b, int lane)
+{
+    if (a < 0 || b < 0 || a == b)
+        return;
+    const int da = uni(L.deg[a]), db = uni(L.deg[b]);
+    for (int k = 0; k < da && k < kUnionDegree; ++k)
+        if (L.adj[a * kUnionDegree + k] == (unsigned short)b)
+            return;
+    if (da >= kUnionDegree || db >= kUnionDegree)
+    {
+        G.fail |= CAPE_UNION_HOST_CAPACITY;
+        return;
+    }
+    if (lane == 0)
+    {
+        L.adj[a * kUnionDegree + da] = (unsigned short)b;
+        L.adj[b * kUnionDegree + db] = (unsigned short)a;
+        L.deg[a] = (unsigned char)(da + 1);
+        L.deg[b] = (unsigned char)(db + 1);
+    }
+    CAPE_MP_SYNC();
+}
+
+// next_of: the first neighbour of v met when rotating counter-clockwise from the direction `back`; `from` is the node the walk came
+// from (-1: none).  Lanes over the neighbours; the choice runs in adjacency order with the host's strict <.  Returns the neighbour's
+// slot in v's list, -1 for a node without neighbours.
+__device__ __forceinline__ int union_next_of(const UnionLds& L, UnionGraph& G, int v, const double2& back, int from, int lane)
+{
+    const int dv = uni(L.deg[v]);
+    const double ba = atan2(back.y, back.x);
+    bool amb = false;
+    double ang = 0.0;
+    if (lane < dv && lane < kUnionDegree)
+    {
+        const int w = L.adj[v * kUnionDegree + lane];
+        const double2 pv = L.nodes[v], pw = L.nodes[w < kUnionNodes ? w : 0];
+        const double dx = pw.x - pv.x, dy = pw.y - pv.y;
+        ang = union_angle(dy, dx, ba, w == from || union_axis_parallel(dx, dy, back.x, back.y), amb);
+    }
+    int best = -1;
+    double bestAngle = 1e300;
+    for (int k = 0; k < dv && k < kUnionDegree; ++k)
+    {
+        const double a = readlane_f64(ang, k);
+        if (a < bestAngle)
+        {
+            bestAngle = a;
+            best = k;
+        }
+    }
+    // two candidates closer than the band: the device's atan2 and the host's may order them differently
+    const bool close = lane < dv && lane < kUnionDegree && lane != best && fabs(ang - bestAngle) < kUnionAngleBand;
+    if (__any(amb || close))
+        G.fail |= CAPE_UNION_HOST_AMBIGUOUS;
+    return best;
+}
+
+// walk_face: the face the directed edge (from -> its neighbour in slot `slot`) has on its right, into ring[0, kUnionOut); every edge
+// walked is marked seen.  Returns the length, -1 if the walk does not close within the host's guard or outgrows the ring.
+__device__ __forceinline__ int union_walk_face(const UnionLds& L, UnionGraph& G, int from, int slot, double2* ring, int lane)
+{
+    const int to = uni(L.adj[from * kUnionDegree + slot]);
+    int cur = from, nxt = to, curSlot = slot, n = 0;
+    for (int guard = 0; guard < 4 * G.nNodes + 8; ++guard)
+    {
+        if (n >= kUnionOut || nxt < 0 || nxt >= G.nNodes)
+            return -1;
+        const double2 pc = L.nodes[cur], pn = L.nodes[nxt];
+        if (lane == 0)
+        {
+            ring[n] = pc;
+            L.seen[cur] = (unsigned char)(L.seen[cur] | (1u << curSlot));
+        }
+        ++n;
+        CAPE_MP_SYNC();
+        const int afterSlot = union_next_of(L, G, nxt, make_double2(pc.x - pn.x, pc.y - pn.y), cur, lane);
+        if (afterSlot < 0)
+            return -1;
+        cur = nxt;
+        nxt = uni(L.adj[cur * kUnionDegree + afterSlot]);
+        curSlot = afterSlot;
+        if (cur == from && nxt == to)
+            return n;
+    }
+    return -1;
+}
+
+struct UnionResult
+{
+    uint32_t flags;
+    int n;          // vertices of the result ring
+    int nNodes;
+    double area;
+    const double2* ring; // in LDS
+};
+
+// One pair on one wavefront.  L.ringA[0, nA) holds the map polygon's ring in its frame `fa` (oriented or not), L.ringB[0, nB) the
+// detection's world ring in its frame `fb`; `target` is the fusion frame.  3 <= nA, nB <= kUnionRing.  `frame` receives the frame of
+// the result (the target, or the map polygon's own where Polygon::project's shortcut holds).
+__device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, const UnionFrame& fa, const UnionFrame& fb, const UnionFrame& target,
+                                         UnionFrame& frame, int lane)
+{
+    UnionResult res{};
+    // ---- 1. the map ring: as the host class holds it, then Polygon::project into the target unless its frame already is the target
+    union_orient(L.ringA, nA, lane);
+    frame = fa;
+    if (!(union_is_approx3(fa.c, target.c) && union_is_approx3(fa.x, target.x) && union_is_approx3(fa.y, target.y)))
+    {
+        for (int v = lane; v < nA; v += 64)
+            L.ringA[v] = union_project(L.ringA[v], fa, target);
+        CAPE_MP_SYNC();
+        union_orient(L.ringA, nA, lane);
+        frame = target;
+    }
+    // ---- 2. the detection: merge_union always projects it into this polygon's frame
+    union_orient(L.ringB, nB, lane);
+    for (int v = lane; v < nB; v += 64)
+        L.ringB[v] = union_project(L.ringB[v], fb, frame);
+    CAPE_MP_SYNC();
+    union_orient(L.ringB, nB, lane);
+    const double2 *A = L.ringA, *B = L.ringB;
+    const double areaMap = union_area(A, nA); // Polygon::_area of the projected map polygon
+    res.flags = CAPE_UNION_SERVED | CAPE_UNION_UNCHANGED;
+    res.ring = A;
+    res.n = nA;
+    res.area = areaMap;
+    if (nA < 3 || nB < 3)
+        return res;
+    // ---- 3. rings_union_outer(A, B, &holes, 0)
+    UnionGraph G{};
+    double scale = 1.0;
+    for (int v = 0; v < nA; ++v)
+        scale = umax(scale, umax(fabs(A[v].x), fabs(A[v].y)));
+    for (int v = 0; v < nB; ++v)
+        scale = umax(scale, umax(fabs(B[v].x), fabs(B[v].y)));
+    const double eps = 1e-9 * scale;
+    G.eps = eps;
+    // the segment list without `same` endpoints, ring A's first (ballot compaction keeps ring order)
+    int nSegA = 0, nSeg = 0;
+    for (int r = 0; r < 2; ++r)
+    {
+        const double2* R = r ? B : A;
+        const int nR = r ? nB : nA;
+        for (int base = 0; base < nR; base += 64)
+        {
+            const int i = base + lane;
+            const bool keep = i < nR && !usame(R[i], R[i + 1 == nR ? 0 : i + 1], eps);
+            const unsigned long long kb = __ballot(keep);
+            if (keep)
+                L.segs[nSeg + __popcll(kb & ((1ull << lane) - 1ull))] = (unsigned short)((r << 8) | i);
+            nSeg += __popcll(kb);
+        }
+        if (r == 0)
+            nSegA = nSeg;
+    }
+    CAPE_MP_SYNC();
+    const int nSegB = nSeg - nSegA;
+    auto seg_a = [&](int s) {
+        const unsigned e = L.segs[s];
+        return (e >> 8) ? B[e & 0xFF] : A[e & 0xFF];
+    };
+    auto seg_b = [&](int s) {
+        const unsigned e = L.segs[s];
+        const int i = (int)(e & 0xFF);
+        return (e >> 8) ? B[i + 1 == nB ? 0 : i + 1] : A[i + 1 == nA ? 0 : i + 1];
+    };
+    // the cuts of every (A segment, B segment): lanes over the pairs, six possible cuts each, appended in ballot order (the per-segment
+    // sort below makes the order of arrival irrelevant)
+    int nCuts = 0;
+    bool cutOverflow = false;
+    for (int base = 0; base < nSegA * nSegB; base += 64)
+    {
+        const int q = base + lane;
+        const bool live = q < nSegA * nSegB;
+        double t[6] = {0, 0, 0, 0, 0, 0};
+        bool has[6] = {false, false, false, false, false, false};
+        int si = 0, ui = 0;
+        if (live)
+        {
+            si = q / nSegB;
+            ui = nSegA + q % nSegB;
+            const double2 sa = seg_a(si), sb = seg_b(si), ua = seg_a(ui), ub = seg_b(ui);
+            has[0] = union_param_on(sa, sb, ua, eps, t[0]);
+            has[1] = union_param_on(sa, sb, ub, eps, t[1]);
+            has[3] = union_param_on(ua, ub, sa, eps, t[3]);
+            has[4] = union_param_on(ua, ub, sb, eps, t[4]);
+            bool ks = false, ku = false;
+            if (union_crossing(sa, sb, ua, ub, eps, t[2], ks, t[5], ku))
+            {
+                has[2] = ks;
+                has[5] = ku;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+        {
+            const unsigned long long m = __ballot(has[c]);
+            const int at = nCuts + __popcll(m & ((1ull << lane) - 1ull));
+            if (has[c] && at < kUnionCuts)
+            {
+                L.cutT[at] = t[c];
+                L.cutSeg[at] = (unsigned short)(c < 3 ? si : ui);
+            }
+            nCuts += __popcll(m);
+        }
+        if (nCuts > kUnionCuts)
+        {
+            cutOverflow = true;
+            break;
+        }
+    }
+    CAPE_MP_SYNC();
+    if (cutOverflow)
+    {
+        res = UnionResult{};
+        res.flags = CAPE_UNION_HOST_CAPACITY;
+        return res;
+    }
+    // the cuts in (segment, parameter) order: a rank sort on the parameters' bit patterns (non-negative doubles: the numbers' order)
+    for (int base = 0; base < nCuts; base += 64)
+    {
+        const int c = base + lane;
+        if (c < nCuts)
+        {
+            const unsigned sc = L.cutSeg[c];
+            const unsigned long long tc = (unsigned long long)__double_as_longlong(L.cutT[c]);
+            int rank = 0;
+            for (int k = 0; k < nCuts; ++k)
+            {
+                const unsigned sk = L.cutSeg[k];
+                const unsigned long long tk = (unsigned long long)__double_as_longlong(L.cutT[k]);
+                rank += (sk < sc || (sk == sc && (tk < tc || (tk == tc && k < c)))) ? 1 : 0;
+            }
+            L.sortT[rank] = L.cutT[c];
+            L.sortSeg[rank] = (unsigned short)sc;
+        }
+    }
+    CAPE_MP_SYNC();
+    // nodes and undirected edges in the host's order: segments in order, cuts ascending, the first node within eps wins
+    int at = 0;
+    for (int s = 0; s < nSeg && !G.fail; ++s)
+    {
+        const double2 a = seg_a(s), b = seg_b(s);
+        int prev = union_node_of(L, G, a, lane);
+        while (at < nCuts && uni(L.sortSeg[at]) == s && !G.fail)
+        {
+            const int cur = union_node_of(L, G, union_cut_point(a, b, L.sortT[at]), lane);
+            union_link(L, G, prev, cur, lane);
+            prev = cur;
+            ++at;
+        }
+        if (!G.fail)
+            union_link(L, G, prev, union_node_of(L, G, b, lane), lane);
+    }
+    CAPE_MP_SYNC(); // (the sorted cuts are dead: the walked rings take their place)
+    res.nNodes = G.nNodes;
+    const auto hosted = [&](uint32_t bits) {
+        UnionResult r{};
+        r.flags = (bits & CAPE_UNION_HOST_CAPACITY) ? (uint32_t)CAPE_UNION_HOST_CAPACITY : bits;
+        r.nNodes = G.nNodes;
+        return r;
+    };
+    if (G.fail)
+        return hosted(G.fail);
+    int nOuter = 0;
+    bool newHole = false;
+    if (G.nNodes >= 3)
+    {
+        // the outer face from the lowest of the leftmost nodes, reached heading south
+        int start = 0;
+        for (int k = 1; k < G.nNodes; ++k)
+        {
+            const double2 pk = L.nodes[k], ps = L.nodes[start];
+            if (pk.x < ps.x - eps || (fabs(pk.x - ps.x) <= eps && pk.y < ps.y))
+                start = k;
+        }
+        const int firstSlot = union_next_of(L, G, start, make_double2(0.0, 1.0), -1, lane);
+        if (firstSlot >= 0)
+        {
+            nOuter = union_walk_face(L, G, start, firstSlot, L.outer, lane);
+            if (nOuter < 0)
+                return hosted(G.fail | CAPE_UNION_HOST_CAPACITY);
+            // every other face: bounded, walked clockwise; a hole of the union is one whose inside belongs to neither operand
+            for (int a = 0; a < G.nNodes && nOuter > 0; ++a)
+            {
+                const int da = uni(L.deg[a]);
+                for (int k = 0; k < da && k < kUnionDegree; ++k)
+                {
+                    if ((uni(L.seen[a]) >> k) & 1)
+                        continue;
+                    int nf = union_walk_face(L, G, a, k, L.face, lane);
+                    if (nf < 0)
+                        return hosted(G.fail | CAPE_UNION_HOST_CAPACITY);
+                    if (nf < 3 || ring_area_signed(L.face, nf) >= 0)
+                        continue; // not a bounded face (or a degenerate spur)
+                    // a point strictly inside the face: just right of the middle of one of its edges
+                    bool found = false;
+                    double2 probe = make_double2(0.0, 0.0);
+                    for (int i = 0; i < nf && !found; ++i)
+                    {
+                        const double2 p = L.face[i], q = L.face[i + 1 == nf ? 0 : i + 1];
+                        const double dx = q.x - p.x, dy = q.y - p.y, len = hypot(dx, dy);
+                        if (len <= eps)
+                            continue;
+                        int step = 0;
+                        for (double off = 1e-3; off >= 1e-7 && !found && step < 8; off *= 0.1, ++step)
+                        {
+                            probe = make_double2(0.5 * (p.x + q.x) + off * len * (dy / len), 0.5 * (p.y + q.y) - off * len * (dx / len));
+                            found = union_point_in_ring(probe, L.face, nf, false, lane);
+                        }
+                    }
+                    if (!found)
+                        continue;
+                    const bool inA = union_point_in_ring(probe, A, nA, true, lane), inB = union_point_in_ring(probe, B, nB, true, lane);
+                    if (inA || inB)
+                        continue;
+                    // merge_union's own test of a hole: drop_collinear, then at least 3 vertices and simple
+                    nf = union_drop_collinear(L.face, nf, lane);
+                    if (nf >= 3 && union_ring_is_simple(L.face, nf, lane))
+                        newHole = true;
+                }
+            }
+        }
+    }
+    if (G.fail)
+        return hosted(G.fail);
+    // ---- 4. the outer ring: drop_collinear, the disjoint rule, ring_is_simple
+    if (nOuter > 0)
+        nOuter = union_drop_collinear(L.outer, nOuter, lane);
+    const double outerArea = nOuter >= 3 ? fabs(ring_area_signed(L.outer, nOuter)) : 0.0;
+    const double areaA = fabs(ring_area_signed(A, nA)), areaB = fabs(ring_area_signed(B, nB));
+    // an operand none of whose vertices lies inside or on the outer face is a piece of its own (MergeInfo::disjoint); the rule below
+    // catches that when the piece walked is the smaller one
+    bool disjoint = nOuter >= 3 && (union_left_out(A, nA, L.outer, nOuter, lane) || union_left_out(B, nB, L.outer, nOuter, lane));
+    double2* out = L.outer;
+    bool rule = false; // merge_union's own `disjoint`
+    if (outerArea + 1e-9 * umax(areaA, areaB) < umax(areaA, areaB))
+    {
+        disjoint = rule = true;
+        if (areaA >= areaB) // area() >= o.area(): this polygon is the bigger piece, simplified as it is
+        {
+            res.flags = CAPE_UNION_SERVED | CAPE_UNION_DISJOINT;
+            res.n = union_simplify(L, L.ringA, nA, L.face, res.area, lane);
+            res.ring = L.ringA;
+            return res;
+        }
+        for (int v = lane; v < nB; v += 64)
+            out[v] = B[v];
+        nOuter = nB;
+        CAPE_MP_SYNC();
+    }
+    if (nOuter < 3 || !union_ring_is_simple(out, nOuter, lane))
+    {
+        res.flags |= disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u; // merge_union returned false: the projected map polygon stays
+        return res;
+    }
+    // ---- 5. a face merge_union would add as a hole
+    if (!rule && newHole)
+        return hosted(CAPE_UNION_HOST_NEW_HOLE);
+    // ---- 6. Polygon(ring, x, y, c): a repeated closing vertex goes, the ring is oriented; then simplify()
+    if (nOuter > 1 && out[0].x == out[nOuter - 1].x && out[0].y == out[nOuter - 1].y)
+        --nOuter;
+    union_orient(out, nOuter, lane);
+    res.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u);
+    res.n = union_simplify(L, out, nOuter, L.face, res.area, lane);
+    res.ring = out;
+    return res;
+}
+
+} // namespace
+
+} // namespace cape
+#endif // __HIPCC__

@@ -1,0 +1,199 @@
+// The polygon half of the map update (host twin cape_host_map_union in host/polygon_capi.cpp): for every pair cape_map_kalman reports
+// as UPDATED, the map plane's new boundary polygon -- Polygon::project, merge_union and simplify of host/boundary_polygon.cpp, restated
+// for one wavefront in cape_map_union.h -- for a map plane without holes whose union with the detection creates no hole.  Everything
+// else is reported as the host's, per pair.  It reads the uploaded map, the match of the last cape_match_map_wide, the rows and world
+// rings of the last cape_map_measure and the fusion rows of the last cape_map_kalman, and writes only its own result buffers: every
+// frame sees the same map, so every (frame, pair) is independent.
+//
+//   cape_map_union_kernel : one wavefront per frame, one per workgroup, no block barrier.
+//        Pass 1, lanes over the kept planes (i and i + 64): which kept planes have a pair; the rows of the others are written here
+//        (map_plane = -1 below n_cur, zeros beyond), so that every row has one writer.
+//        Pass 2, the wave walks the frame's pairs in kept-plane order: both rings into LDS, union_pair, the row, and a served ring
+//        appended to the frame's slab -- the offsets are deterministic and there is no allocator.  A ring that does not fit the rest
+//        of the slab is CAPE_UNION_HOST_CAPACITY.
+//   cape_ring_union_kernel : the same per-pair function on one pair given by its rings and frames (cape_debug_ring_union).
+//   A frame the wide match flagged CAPE_MATCH_EXACT_OVERFLOW reports nothing: its rows are zeros.
+//
+// Every count read from the map, a row or a table is checked against its buffer before it indexes anything; every loop of union_pair
+// is bounded by a capacity of the carve.
+#include <hip/hip_runtime.h>
+
+#include "cape_internal.h"
+#include "cape_map_union.h"
+
+namespace cape {
+
+namespace {
+
+constexpr int kUnionPlanes = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+static_assert(kUnionPlanes == 128, "a lane serves kept planes i and i + 64");
+
+__device__ __forceinline__ void load_frame(UnionFrame& f, const double* x, const double* y, const double* c)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        f.x[k] = x[k], f.y[k] = y[k], f.c[k] = c[k];
+}
+
+// the row of a pair from union_pair's result; a served ring goes to slab[used, used + n) if it fits `capacity`.  Returns the new `used`.
+__device__ __forceinline__ unsigned put_pair(const UnionResult& res, const UnionFrame& frame, int mapPlane, cape_plane_union* row, double2* slab,
+                                             unsigned used, unsigned capacity, int lane)
+{
+    cape_plane_union r{};
+    r.map_plane = mapPlane;
+    r.flags = res.flags;
+    const bool served = (res.flags & CAPE_UNION_SERVED) != 0;
+    const bool fits = served && res.n >= 0 && (unsigned)res.n <= capacity - used;
+    if (served && !fits)
+        r.flags = CAPE_UNION_HOST_CAPACITY;
+    if (fits)
+    {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            r.x_axis[k] = frame.x[k], r.y_axis[k] = frame.y[k], r.center[k] = frame.c[k];
+        r.area = res.area;
+        r.vertex_offset = used;
+        r.vertex_count = (uint32_t)res.n;
+        r.n_nodes = (uint32_t)res.nNodes;
+        for (int v = lane; v < res.n; v += 64)
+            slab[used + v] = res.ring[v];
+        used += (unsigned)res.n;
+    }
+    if (lane == 0)
+        *row = r;
+    return used;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(64) void cape_map_union_kernel(MapUnionParams p, int nFrames)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const UnionLds L = union_carve(smem);
+    const int lane = threadIdx.x & 63;
+    const int frame = (int)blockIdx.x;
+    if (frame >= nFrames)
+        return;
+    const cape_frame_map_match_wide hd = p.matchFrames[frame];
+    const int nMap = p.nMap;
+    const bool reports = !(hd.flags & CAPE_MATCH_EXACT_OVERFLOW);
+    const int nCur = !reports ? 0 : (hd.n_cur < 0 ? 0 : (hd.n_cur > kUnionPlanes ? kUnionPlanes : hd.n_cur));
+    cape_plane_union* rows = p.rows + (size_t)frame * kUnionPlanes;
+    const cape_plane_fusion* fusion = p.fusion + (size_t)frame * kUnionPlanes;
+    double2* slab = p.vertices + (size_t)frame * CAPE_MAP_UNION_FRAME_VERTICES;
+    // ---- pass 1: which kept planes have a pair
+    unsigned long long pairs[2];
+#pragma unroll 1
+    for (int s = 0; s < 2; ++s)
+    {
+        const int i = lane + 64 * s;
+        bool pair = false;
+        if (i < nCur)
+        {
+            const int j = fusion[i].map_plane;
+            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
+            if (j >= 0 && j < nMap && (fusion[i].flags & CAPE_FUSION_FRAME) && at.x < (unsigned)p.nRecords && at.y < (unsigned)CAPE_MAX_PLANES)
+            {
+                const uint32_t mflags = p.measurements[(size_t)at.x * CAPE_MAX_PLANES + at.y].flags;
+                pair = (mflags & CAPE_MEASURE_KEPT) && !(mflags & CAPE_MEASURE_FAIL_POLYGON) && p.match[(size_t)frame * nMap + j] == i;
+            }
+        }
+        if (!pair)
+        {
+            cape_plane_union row{};
+            row.map_plane = i < nCur ? -1 : 0;
+            rows[i] = row;
+        }
+        pairs[s] = __ballot(pair);
+    }
+    // ---- pass 2: the pairs in kept-plane order
+    unsigned used = 0;
+#pragma unroll 1
+    for (int s = 0; s < 2; ++s)
+    {
+        unsigned long long todo = pairs[s];
+        while (todo)
+        {
+            const int i = 64 * s + __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int j = uni(fusion[i].map_plane);
+            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
+            const int rec = uni((int)at.x);
+            const cape_plane_measurement& m = p.measurements[(size_t)rec * CAPE_MAX_PLANES + uni((int)at.y)];
+            const cape_map_plane& M = p.mapPlanes[j];
+            UnionResult res{};
+            UnionFrame frameOut{};
+            const unsigned ringFirst = (unsigned)uni((int)M.ring_first), ringCount = (unsigned)uni((int)M.ring_count);
+            if (ringCount > 1u)
+                res.flags = CAPE_UNION_HOST_MAP_HOLES; // (decided before any geometry)
+            else if (ringCount == 0u || ringFirst >= p.nMapRings)
+                res.flags = CAPE_UNION_HOST_CAPACITY;
+            else
+            {
+                const cape_map_ring R = p.mapRings[ringFirst];
+                const unsigned nA = (unsigned)uni((int)R.vertex_count), offA = (unsigned)uni((int)R.vertex_offset);
+                const unsigned nB = (unsigned)uni((int)m.vertex_count), offB = (unsigned)uni((int)m.vertex_offset);
+                const unsigned cap = (unsigned)p.boundaryCapacity;
+                if (nA > (unsigned)kUnionRing || nB > (unsigned)kUnionRing || nA < 3u || nB < 3u || (unsigned long long)offA + nA > p.nMapVertices ||
+                    offB > cap || nB > cap - offB)
+                    res.flags = CAPE_UNION_HOST_CAPACITY;
+                else
+                {
+                    const double2* srcA = p.mapVertices + offA;
+                    const double2* srcB = p.worldVertices + (size_t)rec * cap + offB;
+                    for (unsigned v = lane; v < nA; v += 64)
+                        L.ringA[v] = srcA[v];
+                    for (unsigned v = lane; v < nB; v += 64)
+                        L.ringB[v] = srcB[v];
+                    CAPE_MP_SYNC();
+                    UnionFrame fa, fb, target;
+                    load_frame(fa, M.x_axis, M.y_axis, M.center);
+                    load_frame(fb, m.x_axis, m.y_axis, m.center);
+                    load_frame(target, fusion[i].x_axis, fusion[i].y_axis, fusion[i].center);
+                    res = union_pair(L, (int)nA, (int)nB, fa, fb, target, frameOut, lane);
+                }
+            }
+            used = put_pair(res, frameOut, j, rows + i, slab, used, CAPE_MAP_UNION_FRAME_VERTICES, lane);
+            CAPE_MP_SYNC(); // (the next pair rewrites the carve)
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void cape_ring_union_kernel(RingUnionParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const UnionLds L = union_carve(smem);
+    const int lane = threadIdx.x & 63;
+    UnionResult res{};
+    UnionFrame frameOut{};
+    if (p.nA > kUnionRing || p.nB > kUnionRing || p.nA < 3 || p.nB < 3)
+        res.flags = CAPE_UNION_HOST_CAPACITY;
+    else
+    {
+        for (int v = lane; v < p.nA; v += 64)
+            L.ringA[v] = p.ringA[v];
+        for (int v = lane; v < p.nB; v += 64)
+            L.ringB[v] = p.ringB[v];
+        CAPE_MP_SYNC();
+        UnionFrame fa, fb, target;
+        load_frame(fa, p.frames27, p.frames27 + 3, p.frames27 + 6);
+        load_frame(fb, p.frames27 + 9, p.frames27 + 12, p.frames27 + 15);
+        load_frame(target, p.frames27 + 18, p.frames27 + 21, p.frames27 + 24);
+        res = union_pair(L, p.nA, p.nB, fa, fb, target, frameOut, lane);
+    }
+    (void)put_pair(res, frameOut, 0, p.row, p.vertices, 0u, CAPE_MAP_MAX_RING, lane);
+}
+
+hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cape_map_union_kernel, dim3(nFrames), dim3(64), union_layout().bytes, stream, p, nFrames);
+    return hipGetLastError();
+}
+
+hipError_t launch_ring_union(const RingUnionParams& p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cape_ring_union_kernel, dim3(1), dim3(64), union_layout().bytes, stream, p);
+    return hipGetLastError();
+}
+
+} // namespace cape

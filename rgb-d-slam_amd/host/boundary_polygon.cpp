@@ -1084,8 +1084,12 @@ void drop_collinear(std::vector<vector2>& r)
 
 } // namespace
 
-bool Polygon::merge_union(const Polygon& other)
+bool Polygon::merge_union(const Polygon& other) { return merge_union(other, nullptr); }
+
+bool Polygon::merge_union(const Polygon& other, MergeInfo* info)
 {
+    if (info)
+        *info = MergeInfo {};
     const Polygon o = other.project(_xAxis, _yAxis, _center);
     if (_ring.size() < 3 || o._ring.size() < 3)
         return false;
@@ -1095,10 +1099,24 @@ bool Polygon::merge_union(const Polygon& other)
     const double outerArea = outer.size() >= 3 ? std::abs(ring_area_signed(outer)) : 0.0;
     // two disjoint pieces: union_one keeps the biggest one of the multi-polygon (polygon.cpp:474-492)
     const double areaA = std::abs(ring_area_signed(_ring)), areaB = std::abs(ring_area_signed(o._ring));
+    // (for `info` only) an operand none of whose vertices lies inside or on the outer face is a piece of its own: the walk from the
+    // leftmost node went round the other piece alone.  The rule below catches that when the piece walked is the smaller one.
+    if (info && outer.size() >= 3)
+    {
+        const auto left_out = [&outer](const std::vector<vector2>& ring) {
+            for (const vector2& p : ring)
+                if (point_in_ring(p, outer, true))
+                    return false;
+            return true;
+        };
+        info->disjoint = left_out(_ring) || left_out(o._ring);
+    }
     bool disjoint = false;
     if (outerArea + 1e-9 * std::max(areaA, areaB) < std::max(areaA, areaB))
     {
         disjoint = true;
+        if (info)
+            info->disjoint = true;
         if (area() >= o.area())
         {
             // this polygon is the biggest piece of the multi-polygon: union_one returns it as is, and merge_union

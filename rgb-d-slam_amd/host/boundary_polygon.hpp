@@ -94,6 +94,14 @@ class Polygon
     // changes nothing) if the result is empty.  Dependency-free: face walks over the arrangement of the two outer rings,
     // touching vertices and collinear overlaps included.
     bool merge_union(const Polygon& other);
+    // the same, and the fact a caller cannot read off the result: the operands are two disjoint pieces, of which the bigger one was
+    // kept -- by the disjoint rule (the outlines enclose less than the bigger operand), or because the outer face walked from the
+    // leftmost node already is the bigger piece (no vertex of the other operand lies inside or on it).  `info` changes no result
+    struct MergeInfo
+    {
+        bool disjoint = false;
+    };
+    bool merge_union(const Polygon& other, MergeInfo* info);
     // polygon from an explicit ring in a given frame (polygon.cpp:236-266)
     Polygon(const std::vector<vector2>& ring, const vector3& xAxis, const vector3& yAxis, const vector3& center);
     // polygon from an open outer ring (no repeated closing vertex) and its interior rings in a given frame -- a map plane's

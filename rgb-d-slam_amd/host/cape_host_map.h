@@ -99,6 +99,28 @@ int cape_host_map_update(const cape_host_map* map, const int32_t* match, const c
 int cape_host_map_kalman(const cape_host_map* map, const int32_t* match, const cape_plane_measurement* measurements, int32_t n_cur,
                          cape_frame_map_kalman* frame_out, cape_plane_fusion* rows_out, cape_map_track_result* tracks_out);
 
+/* The twin of cape_map_union (include/cape_hip.h) for ONE frame, through the host class itself (Polygon::project, merge_union,
+ * simplify): the very polygon step of cape_host_map_update above, so a served pair's ring, area and frame are the update's new map
+ * polygon bit for bit.  map: planes, rings and vertices (tracks are not read); match[map->n_planes] (NULL: not checked): a pair needs
+ * match[j] == i; fusion: n_cur rows of cape_map_kalman / cape_host_map_kalman in kept-plane order; measurements: n_cur rows of
+ * cape_map_measure in kept-plane order (frame, vertex_count and flags are read); world_vertices: the world rings of kept planes
+ * 0 .. n_cur - 1 back to back, ring i of measurements[i].vertex_count (x, y) pairs (vertex_offset is not read).  A pair exists where
+ * the fusion row has map_plane = j >= 0 and CAPE_FUSION_FRAME and the measurement row has CAPE_MEASURE_KEPT and lacks
+ * CAPE_MEASURE_FAIL_POLYGON.  Sets
+ * CAPE_UNION_SERVED / UNCHANGED / DISJOINT / HOST_MAP_HOLES / HOST_NEW_HOLE; of CAPE_UNION_HOST_CAPACITY it knows the ring-length rule
+ * (an operand of more than CAPE_MAP_UNION_MAX_RING vertices), the frame's slab and a union beyond the map's own limits
+ * (CAPE_MAP_RESULT_OVERFLOW); it never sets HOST_AMBIGUOUS, and n_nodes stays 0.  Outputs: rows_out[128] (zero beyond n_cur) and
+ * vertices_out (room for CAPE_MAP_UNION_FRAME_VERTICES pairs; only the served rings are written).  Returns 0, or
+ * CAPE_ERR_INVALID_ARGUMENT for a NULL argument, negative counts, n_cur > 128 or a map ring outside its array. */
+int cape_host_map_union(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion, const cape_plane_measurement* measurements,
+                        const double* world_vertices, int32_t n_cur, cape_plane_union* rows_out, double* vertices_out);
+
+/* The twin of cape_debug_ring_union: one pair, ring_a the map plane's outer ring, ring_b the detection's, frames27 = (x, y, centre) of
+ * ring a's frame, ring b's frame and the target frame (NULL: the canonical frame for all three).  row_out: one row (map_plane 0);
+ * vertices_out: room for CAPE_MAP_MAX_RING pairs.  CAPE_ERR_INVALID_ARGUMENT: a NULL ring or output, n_a or n_b outside [3, 4096]. */
+int cape_host_ring_union(const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27, cape_plane_union* row_out,
+                         double* vertices_out);
+
 /* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
  * cape_gather_primitives[_root] or any other transport -- as the kept planes the two calls above take: no handle, no device.
  * `frame` counts from the shard's first frame.  Each plane goes through the host class's Polygon(ring, xAxis, yAxis, center)

@@ -3,8 +3,8 @@
 // end are test hooks: the tests compare the device (or a numpy restatement) with them through ctypes.  cape_host_match_map,
 // cape_host_match_planes, cape_host_map_visibility, cape_host_map_update and cape_host_shard_frame are host twins a caller may use,
 // declared and described in cape_host_map.h: the first answers the frames cape_match_map flags, the second those the matchers of
-// consecutive frames flag, the third decides which map planes cape_match_map visits, the fourth is the map update, which runs on the
-// host only, the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
+// consecutive frames flag, the third decides which map planes cape_match_map visits, the fourth is the map update (cape_host_map_kalman and cape_host_map_union are the
+// twins of its two device halves, cape_host_ring_union of the union's debug entry), the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -203,6 +203,73 @@ bool to_world_space(const Polygon& p, const double* T, Polygon& out)
         return false;
     out = p.to_camera_space(T);
     return true;
+}
+
+// The polygon step of Plane::update_boundary_polygon (plane_with_tracking.cpp:63-82) once the target frame is known, for
+// cape_host_map_update and the twins of cape_map_union alike.  `poly` becomes the map polygon in the target frame -- Polygon::project
+// returns the polygon itself if its frame is already the target (isApprox) -- and, if the step passes, its union with the detection
+// (WorldPolygon::merge: merge_union of the detection projected into this frame; merge_union projects it, the reference's second
+// projection onto the same frame returns it unchanged).  detection_world(out) yields the detection in world space, false where the
+// reference throws.  A union beyond CAPE_MAP_MAX_RING / CAPE_MAP_MAX_HOLES keeps the OLD polygon (and its frame): `overflow`.
+struct PolygonStep
+{
+    bool ok = false, overflow = false, merged = false; // merged: what merge_union returned
+    Polygon::MergeInfo info;
+};
+template <class Detection>
+PolygonStep polygon_step(const Polygon& mapPolygon, const vector3& xAxis, const vector3& yAxis, const vector3& center, Detection&& detection_world,
+                         Polygon& poly)
+{
+    PolygonStep step;
+    poly = mapPolygon;
+    if (!(is_approx3(poly.get_center(), center) && is_approx3(poly.get_x_axis(), xAxis) && is_approx3(poly.get_y_axis(), yAxis)))
+        poly = poly.project(xAxis, yAxis, center);
+    Polygon detWorld;
+    step.ok = is_approx3(poly.get_center(), center) && detection_world(detWorld);
+    if (!step.ok)
+        return step;
+    Polygon merged = poly;
+    step.merged = merged.merge_union(detWorld, &step.info);
+    bool fits = merged.boundary().size() <= CAPE_MAP_MAX_RING && merged.interior_rings().size() <= CAPE_MAP_MAX_HOLES;
+    for (const auto& h : merged.interior_rings())
+        fits = fits && h.size() <= CAPE_MAP_MAX_RING;
+    if (fits)
+        poly = merged;
+    else
+    {
+        poly = mapPolygon;
+        step.overflow = true;
+    }
+    return step;
+}
+
+// A pair's row of cape_map_union from the step's outcome (the map polygon had no hole; both operands within
+// CAPE_MAP_UNION_MAX_RING): a union with a hole, or one beyond the map's limits, is the host's; a served ring goes to `slab` at
+// `used` if it fits the `capacity` pairs.
+void put_union_row(cape_plane_union& row, const Polygon& poly, const PolygonStep& step, uint32_t& used, uint32_t capacity, double* slab)
+{
+    if (step.overflow)
+        row.flags = CAPE_UNION_HOST_CAPACITY;
+    else if (!poly.interior_rings().empty())
+        row.flags = CAPE_UNION_HOST_NEW_HOLE;
+    else if (poly.boundary().size() > capacity - used)
+        row.flags = CAPE_UNION_HOST_CAPACITY;
+    else
+    {
+        row.flags = CAPE_UNION_SERVED | (step.merged ? 0u : (uint32_t)CAPE_UNION_UNCHANGED) | (step.info.disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u);
+        put3(row.x_axis, poly.get_x_axis());
+        put3(row.y_axis, poly.get_y_axis());
+        put3(row.center, poly.get_center());
+        row.area = poly.get_area();
+        row.vertex_offset = used;
+        row.vertex_count = (uint32_t)poly.boundary().size();
+        for (const vector2& p : poly.boundary())
+        {
+            slab[2 * (size_t)used] = p[0];
+            slab[2 * (size_t)used + 1] = p[1];
+            ++used;
+        }
+    }
 }
 
 } // namespace
@@ -559,28 +626,13 @@ extern "C" int cape_host_map_update(const cape_host_map* map, const int32_t* mat
                         if (ok)
                         {
                             const auto axes = rgbd_slam::utils::get_plane_coordinate_system(normal);
-                            // Polygon::project returns the polygon itself if its frame is already the target (isApprox)
-                            if (!(is_approx3(poly.get_center(), center) && is_approx3(poly.get_x_axis(), axes.first) &&
-                                  is_approx3(poly.get_y_axis(), axes.second)))
-                                poly = poly.project(axes.first, axes.second, center);
-                            Polygon detWorld;
-                            ok = is_approx3(poly.get_center(), center) && to_world_space(det[i], T, detWorld);
+                            const PolygonStep step = polygon_step(e.polygon, axes.first, axes.second, center,
+                                                                  [&](Polygon& detWorld) { return to_world_space(det[i], T, detWorld); }, poly);
+                            ok = step.ok;
                             if (ok)
                             {
-                                // WorldPolygon::merge: merge_union of the detection projected into this frame (merge_union projects
-                                // it; the reference's second projection onto the same frame returns it unchanged)
-                                Polygon merged = poly;
-                                (void)merged.merge_union(detWorld);
-                                bool fits = merged.boundary().size() <= CAPE_MAP_MAX_RING && merged.interior_rings().size() <= CAPE_MAP_MAX_HOLES;
-                                for (const auto& h : merged.interior_rings())
-                                    fits = fits && h.size() <= CAPE_MAP_MAX_RING;
-                                if (fits)
-                                    poly = merged;
-                                else
-                                {
-                                    poly = e.polygon;
+                                if (step.overflow)
                                     result |= CAPE_MAP_RESULT_OVERFLOW;
-                                }
                                 result |= CAPE_MAP_RESULT_UPDATED;
                             }
                         }
@@ -754,6 +806,109 @@ extern "C" int cape_host_map_kalman(const cape_host_map* map, const int32_t* mat
     if (frame_out)
         *frame_out = cape_frame_map_kalman {n_planes, n_cur, badPose ? (uint32_t)CAPE_KALMAN_BAD_POSE_COV : 0u, nUpdated};
     return 0;
+}
+
+// The twin of cape_map_union (cape_host_map.h): the polygon step above, per pair of one frame, through the host class itself.
+extern "C" int cape_host_map_union(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion,
+                                   const cape_plane_measurement* measurements, const double* world_vertices, int32_t n_cur,
+                                   cape_plane_union* rows_out, double* vertices_out)
+{
+    if (!map || map->n_planes < 0 || n_cur < 0 || n_cur > CAPE_MATCH_MAP_WIDE_MAX_PLANES || !rows_out || !vertices_out ||
+        (n_cur > 0 && (!fusion || !measurements || !world_vertices)) || (map->n_planes > 0 && (!map->planes || !map->rings || !map->vertices)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const int32_t n_planes = map->n_planes;
+    try
+    {
+        std::vector<cape_plane_union> rows(CAPE_MATCH_MAP_WIDE_MAX_PLANES, cape_plane_union {});
+        std::vector<double> slab;
+        slab.resize(2 * (size_t)CAPE_MAP_UNION_FRAME_VERTICES);
+        uint32_t used = 0;
+        size_t ringAt = 0;
+        for (int32_t i = 0; i < n_cur; ++i)
+        {
+            const cape_plane_fusion& F = fusion[i];
+            const cape_plane_measurement& m = measurements[i];
+            const size_t ringFirst = ringAt;
+            ringAt += m.vertex_count;
+            cape_plane_union& row = rows[i];
+            row.map_plane = -1;
+            const int32_t j = F.map_plane;
+            if (j < 0 || j >= n_planes || !(F.flags & CAPE_FUSION_FRAME) || !(m.flags & CAPE_MEASURE_KEPT) || (m.flags & CAPE_MEASURE_FAIL_POLYGON) ||
+                (match && match[j] != i))
+                continue;
+            row.map_plane = j;
+            const cape_map_plane& M = map->planes[j];
+            if (!map_polygon(*map, M, nullptr))
+                return CAPE_ERR_INVALID_ARGUMENT;
+            if (M.ring_count > 1)
+            {
+                row.flags = CAPE_UNION_HOST_MAP_HOLES;
+                continue;
+            }
+            if (map->rings[M.ring_first].vertex_count > CAPE_MAP_UNION_MAX_RING || m.vertex_count > CAPE_MAP_UNION_MAX_RING)
+            {
+                row.flags = CAPE_UNION_HOST_CAPACITY;
+                continue;
+            }
+            Polygon mapPolygon, poly;
+            map_polygon(*map, M, &mapPolygon);
+            const PolygonStep step = polygon_step(
+                mapPolygon, vec3(F.x_axis), vec3(F.y_axis), vec3(F.center),
+                [&](Polygon& detWorld) {
+                    detWorld = Polygon(ring_from(world_vertices + 2 * ringFirst, m.vertex_count), {}, vec3(m.x_axis), vec3(m.y_axis), vec3(m.center));
+                    return true;
+                },
+                poly);
+            if (!step.ok) // (the centre check after a projection: not reached, the projected polygon's centre IS the target)
+                continue;
+            put_union_row(row, poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, slab.data());
+        }
+        std::copy(rows.begin(), rows.end(), rows_out);
+        std::copy(slab.begin(), slab.begin() + 2 * (size_t)used, vertices_out);
+        return 0;
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
+}
+
+// The twin of cape_debug_ring_union (cape_host_map.h): one pair given by its two rings and three frames.
+extern "C" int cape_host_ring_union(const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
+                                    cape_plane_union* row_out, double* vertices_out)
+{
+    static const double kCanonical[27] = {1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0};
+    if (!ring_a || !ring_b || !row_out || !vertices_out || n_a < 3 || n_b < 3 || n_a > 4096 || n_b > 4096)
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const double* F = frames27 ? frames27 : kCanonical;
+    try
+    {
+        cape_plane_union row {};
+        if (n_a > CAPE_MAP_UNION_MAX_RING || n_b > CAPE_MAP_UNION_MAX_RING)
+            row.flags = CAPE_UNION_HOST_CAPACITY;
+        else
+        {
+            const Polygon a(ring_from(ring_a, n_a), {}, vec3(F), vec3(F + 3), vec3(F + 6));
+            const Polygon b(ring_from(ring_b, n_b), {}, vec3(F + 9), vec3(F + 12), vec3(F + 15));
+            Polygon poly;
+            const PolygonStep step = polygon_step(
+                a, vec3(F + 18), vec3(F + 21), vec3(F + 24),
+                [&](Polygon& detWorld) {
+                    detWorld = b;
+                    return true;
+                },
+                poly);
+            uint32_t used = 0;
+            if (step.ok)
+                put_union_row(row, poly, step, used, CAPE_MAP_MAX_RING, vertices_out);
+        }
+        *row_out = row;
+        return 0;
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
 }
 
 // Test hooks of the covariance and Kalman algebra (tests/test_map_update_host.py restates them in numpy).  Each returns 1 on

@@ -233,6 +233,16 @@ assert FRAME_MAP_KALMAN_DTYPE.itemsize == 16 and PLANE_FUSION_DTYPE.itemsize == 
 KALMAN_BAD_POSE_COV = 1 << 8
 FUSION_USED, FUSION_STATE, FUSION_FRAME = 1, 2, 4
 
+# cape_map_union: the polygon half of the map update (cape_plane_union), a row per kept plane and a vertex slab per frame
+PLANE_UNION_DTYPE = np.dtype([
+    ("x_axis", "<f8", 3), ("y_axis", "<f8", 3), ("center", "<f8", 3), ("area", "<f8"), ("vertex_offset", "<u4"), ("vertex_count", "<u4"),
+    ("map_plane", "<i4"), ("flags", "<u4"), ("n_nodes", "<u4"), ("pad", "<u4")], align=True)
+assert PLANE_UNION_DTYPE.itemsize == 10 * 8 + 24 == 104
+MAP_UNION_MAX_RING, MAP_UNION_MAX_NODES, MAP_UNION_FRAME_VERTICES = 128, 512, 2048
+(UNION_SERVED, UNION_UNCHANGED, UNION_DISJOINT, UNION_HOST_MAP_HOLES, UNION_HOST_NEW_HOLE, UNION_HOST_CAPACITY,
+ UNION_HOST_AMBIGUOUS) = (1 << k for k in range(7))
+UNION_HOST = UNION_HOST_MAP_HOLES | UNION_HOST_NEW_HOLE | UNION_HOST_CAPACITY | UNION_HOST_AMBIGUOUS
+
 
 class cape_host_map(C.Structure):
     """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
@@ -269,6 +279,8 @@ def _host_library():
         L.cape_host_shard_frame.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(cape_gather_layout), C.POINTER(cape_gather_polygon_layout),
                                             C.c_int32, Planes]
         L.cape_host_map_kalman.argtypes = [Map, i32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_host_map_union.argtypes = [Map, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.cape_host_ring_union.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
         L.cape_host_plane_to_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
@@ -402,6 +414,64 @@ def host_map_kalman(map_arrays, tracks, match, measurements):
     if rc != 0:
         raise CapeError(f"cape_host_map_kalman failed ({rc})")
     return frame[0], rows[:n_cur], results[:n_map]
+
+
+def _union_rings(rows, slab):
+    """the ring of every served row of a frame (rows: PLANE_UNION_DTYPE, slab: (n, 2) vertices), None for the others"""
+    return [slab[r["vertex_offset"]: r["vertex_offset"] + r["vertex_count"]].copy() if r["flags"] & UNION_SERVED else None for r in rows]
+
+
+def host_map_union(map_arrays, match, fusion_rows, measurements, world_rings):
+    """cape_host_map_union of libcape_primitives.so: the twin of Extractor.map_union for ONE frame -- the polygon step of
+    host_map_update (Polygon::project, merge_union, simplify on the host class) for every pair the fusion rows report.
+
+    map_arrays: pack_map(...); match: n_map kept-plane indices or -1 (None: not checked); fusion_rows: PLANE_FUSION_DTYPE[n_cur]
+    (host_map_kalman's or the device's); measurements: PLANE_MEASUREMENT_DTYPE[n_cur] in kept-plane order; world_rings: the n_cur
+    world rings, (k, 2) arrays in kept-plane order (ring i must have measurements[i]["vertex_count"] vertices).
+    Returns (rows: PLANE_UNION_DTYPE[n_cur], rings: per kept plane the served ring or None)."""
+    L = _host_library()
+    src, src_view = _map_arrays(map_arrays)
+    F = np.ascontiguousarray(fusion_rows, PLANE_FUSION_DTYPE).reshape(-1)
+    Mr = np.ascontiguousarray(measurements, PLANE_MEASUREMENT_DTYPE).reshape(-1)
+    n_cur = len(F)
+    if len(Mr) != n_cur or len(world_rings) != n_cur:
+        raise CapeError("host_map_union: one measurement row and one world ring per fusion row")
+    rings = [np.ascontiguousarray(r, np.float64).reshape(-1, 2) for r in world_rings]
+    if any(len(r) != int(m["vertex_count"]) for r, m in zip(rings, Mr)):
+        raise CapeError("host_map_union: a world ring's length differs from its measurement row's vertex_count")
+    W = np.ascontiguousarray(np.concatenate(rings + [np.zeros((1, 2))]))
+    M = None
+    if match is not None:
+        M = np.ascontiguousarray(match, np.int32).reshape(-1)
+        if len(M) != len(src["planes"]):
+            raise CapeError("host_map_union: one match per map plane")
+    rows = np.zeros(MATCH_MAP_WIDE_MAX_PLANES, PLANE_UNION_DTYPE)
+    slab = np.zeros((MAP_UNION_FRAME_VERTICES, 2))
+    rc = L.cape_host_map_union(C.byref(src_view), _as(M, C.c_int32), F.ctypes.data, Mr.ctypes.data, W.ctypes.data, n_cur, rows.ctypes.data,
+                               slab.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_map_union failed ({rc})")
+    return rows[:n_cur], _union_rings(rows[:n_cur], slab)
+
+
+def _ring_union_args(ring_a, ring_b, frames):
+    a = np.ascontiguousarray(ring_a, np.float64).reshape(-1, 2)
+    b = np.ascontiguousarray(ring_b, np.float64).reshape(-1, 2)
+    F = None if frames is None else np.ascontiguousarray(frames, np.float64).reshape(27)
+    return a, b, F, np.zeros(1, PLANE_UNION_DTYPE), np.zeros((MAP_MAX_RING, 2))
+
+
+def host_ring_union(ring_a, ring_b, frames=None):
+    """cape_host_ring_union: the twin of Extractor.debug_ring_union -- ring_a the map plane's outer ring, ring_b the detection's,
+    frames: 27 doubles, (x_axis, y_axis, center) of ring a's frame, ring b's frame and the target frame (None: the canonical frame for
+    all three).  Returns (row: PLANE_UNION_DTYPE scalar, ring[count, 2])."""
+    L = _host_library()
+    a, b, F, row, ver = _ring_union_args(ring_a, ring_b, frames)
+    rc = L.cape_host_ring_union(a.ctypes.data, len(a), b.ctypes.data, len(b), None if F is None else F.ctypes.data, row.ctypes.data,
+                                ver.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_ring_union failed ({rc})")
+    return row[0], ver[: int(row[0]["vertex_count"])].copy()
 
 
 def host_shard_frame(buf, layout, k):
@@ -550,6 +620,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_visibility", "cape_copy_map_visibility",
     "cape_map_measure", "cape_device_map_measurements", "cape_copy_map_measurements", "cape_copy_spill_measurements",
     "cape_map_upload_tracks", "cape_map_kalman", "cape_copy_map_kalman", "cape_device_map_kalman",
+    "cape_map_union", "cape_copy_map_union", "cape_device_map_union", "cape_debug_ring_union",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
@@ -645,6 +716,10 @@ def load_library():
     L.cape_map_kalman.argtypes = [vp, C.c_int32, vp]
     L.cape_copy_map_kalman.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.cape_device_map_kalman.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.cape_map_union.argtypes = [vp, C.c_int32, vp]
+    L.cape_copy_map_union.argtypes = [vp, C.c_int32, vp, vp]
+    L.cape_device_map_union.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.cape_debug_ring_union.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1079,6 +1154,35 @@ class Extractor:
             n_cur = 0 if frames[f]["flags"] & MATCH_EXACT_OVERFLOW else min(int(frames[f]["n_cur"]), MATCH_MAP_WIDE_MAX_PLANES)
             out.append(({name: int(frames[f][name]) for name in frames.dtype.names}, _fusion_dicts(rows[f], n_cur), results[f].copy()))
         return out
+
+    # ---- the polygon half of the map update (needs map_kalman of the batch) ----
+    def map_union(self, n_frames, stream=0):
+        """cape_map_union: per frame of [0, n_frames) and per pair map_kalman reports as UPDATED the map plane's new boundary polygon
+        (project, merge_union, simplify), for a map plane without holes whose union creates no hole; every other pair is flagged
+        UNION_HOST_* and stays with host_map_update.  The results are map_unions'."""
+        _check(self.L, self.L.cape_map_union(self.h, n_frames, C.c_void_p(stream)), "cape_map_union")
+
+    def map_union_rows(self, n_frames):
+        """(rows: PLANE_UNION_DTYPE[n_frames, 128], vertices[n_frames, MAP_UNION_FRAME_VERTICES, 2]) of the last map_union"""
+        rows = np.zeros((n_frames, MATCH_MAP_WIDE_MAX_PLANES), PLANE_UNION_DTYPE)
+        ver = np.zeros((n_frames, MAP_UNION_FRAME_VERTICES, 2), np.float64)
+        _check(self.L, self.L.cape_copy_map_union(self.h, n_frames, rows.ctypes.data_as(C.c_void_p), ver.ctypes.data_as(C.c_void_p)),
+               "cape_copy_map_union")
+        return rows, ver
+
+    def map_unions(self, n_frames):
+        """Per frame of the last map_union: (rows: PLANE_UNION_DTYPE[128], rings: per row the served ring (count, 2) or None)."""
+        rows, ver = self.map_union_rows(n_frames)
+        return [(rows[f].copy(), _union_rings(rows[f], ver[f])) for f in range(n_frames)]
+
+    def debug_ring_union(self, ring_a, ring_b, frames=None):
+        """cape_debug_ring_union: map_union's per-pair device function on one pair given by its rings and frames (see
+        host_ring_union, its twin).  Returns (row: PLANE_UNION_DTYPE scalar, ring[count, 2])."""
+        a, b, F, row, ver = _ring_union_args(ring_a, ring_b, frames)
+        _check(self.L, self.L.cape_debug_ring_union(self.h, a.ctypes.data_as(C.c_void_p), len(a), b.ctypes.data_as(C.c_void_p), len(b),
+                                                    None if F is None else F.ctypes.data_as(C.c_void_p), row.ctypes.data_as(C.c_void_p),
+                                                    ver.ctypes.data_as(C.c_void_p)), "cape_debug_ring_union")
+        return row[0], ver[: int(row[0]["vertex_count"])].copy()
 
     def map_visibility(self, n_frames, world_to_camera=None, moving=None, stream=0):
         """cape_map_visibility: the skip words of match_map / match_map_shards decided on the device -- bit j of frame (or slot) f set
