@@ -946,9 +946,11 @@ enum
                                             merge_union's disjoint rule, or because the outer face walked from the leftmost node already
                                             is the bigger piece (no vertex of the other operand lies inside or on it) */
     CAPE_UNION_HOST_MAP_HOLES = 1u << 3, /* the map plane has interior rings */
-    CAPE_UNION_HOST_NEW_HOLE = 1u << 4,  /* the union encloses a face merge_union would add as a hole */
+    CAPE_UNION_HOST_NEW_HOLE = 1u << 4,  /* the union encloses a face merge_union would add as a hole: one or many -- more than
+                                            CAPE_MAP_MAX_HOLES of them too, which the update reports as CAPE_MAP_RESULT_OVERFLOW */
     CAPE_UNION_HOST_CAPACITY = 1u << 5,  /* an operand > MAX_RING, nodes > MAX_NODES, a node of more than 8 neighbours, a walk that
-                                            reaches its guard, or the frame's vertex slab is full */
+                                            reaches its guard or outgrows CAPE_MAP_MAX_RING, or the frame's vertex slab is full; never
+                                            the number of holes */
     CAPE_UNION_HOST_AMBIGUOUS = 1u << 6  /* an angle comparison of the face walk lies inside the guard band */
 };
 /* One row per kept plane i < 128 of a frame, like the fusion rows.  A pair with a CAPE_UNION_HOST_* bit carries no ring:

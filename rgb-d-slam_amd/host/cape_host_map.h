@@ -108,8 +108,10 @@ int cape_host_map_kalman(const cape_host_map* map, const int32_t* match, const c
  * the fusion row has map_plane = j >= 0 and CAPE_FUSION_FRAME and the measurement row has CAPE_MEASURE_KEPT and lacks
  * CAPE_MEASURE_FAIL_POLYGON.  Sets
  * CAPE_UNION_SERVED / UNCHANGED / DISJOINT / HOST_MAP_HOLES / HOST_NEW_HOLE; of CAPE_UNION_HOST_CAPACITY it knows the ring-length rule
- * (an operand of more than CAPE_MAP_UNION_MAX_RING vertices), the frame's slab and a union beyond the map's own limits
- * (CAPE_MAP_RESULT_OVERFLOW); it never sets HOST_AMBIGUOUS, and n_nodes stays 0.  Outputs: rows_out[128] (zero beyond n_cur) and
+ * (an operand of more than CAPE_MAP_UNION_MAX_RING vertices), the frame's slab and a union whose outer ring exceeds
+ * CAPE_MAP_MAX_RING.  A union with interior rings is HOST_NEW_HOLE however many or how long they are, like the device's, which meets
+ * holes but does not count them -- also where cape_host_map_update reports CAPE_MAP_RESULT_OVERFLOW for more than CAPE_MAP_MAX_HOLES
+ * of them.  It never sets HOST_AMBIGUOUS, and n_nodes stays 0.  Outputs: rows_out[128] (zero beyond n_cur) and
  * vertices_out (room for CAPE_MAP_UNION_FRAME_VERTICES pairs; only the served rings are written).  Returns 0, or
  * CAPE_ERR_INVALID_ARGUMENT for a NULL argument, negative counts, n_cur > 128 or a map ring outside its array. */
 int cape_host_map_union(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion, const cape_plane_measurement* measurements,

@@ -210,10 +210,13 @@ bool to_world_space(const Polygon& p, const double* T, Polygon& out)
 // returns the polygon itself if its frame is already the target (isApprox) -- and, if the step passes, its union with the detection
 // (WorldPolygon::merge: merge_union of the detection projected into this frame; merge_union projects it, the reference's second
 // projection onto the same frame returns it unchanged).  detection_world(out) yields the detection in world space, false where the
-// reference throws.  A union beyond CAPE_MAP_MAX_RING / CAPE_MAP_MAX_HOLES keeps the OLD polygon (and its frame): `overflow`.
+// reference throws.  A union beyond CAPE_MAP_MAX_RING / CAPE_MAP_MAX_HOLES keeps the OLD polygon (and its frame): `overflow`; `holed`
+// says that the union had interior rings within an outer ring of at most CAPE_MAP_MAX_RING vertices, which `poly` no longer shows
+// after an overflow.
 struct PolygonStep
 {
     bool ok = false, overflow = false, merged = false; // merged: what merge_union returned
+    bool holed = false;
     Polygon::MergeInfo info;
 };
 template <class Detection>
@@ -230,6 +233,7 @@ PolygonStep polygon_step(const Polygon& mapPolygon, const vector3& xAxis, const 
         return step;
     Polygon merged = poly;
     step.merged = merged.merge_union(detWorld, &step.info);
+    step.holed = merged.boundary().size() <= CAPE_MAP_MAX_RING && !merged.interior_rings().empty();
     bool fits = merged.boundary().size() <= CAPE_MAP_MAX_RING && merged.interior_rings().size() <= CAPE_MAP_MAX_HOLES;
     for (const auto& h : merged.interior_rings())
         fits = fits && h.size() <= CAPE_MAP_MAX_RING;
@@ -244,14 +248,14 @@ PolygonStep polygon_step(const Polygon& mapPolygon, const vector3& xAxis, const 
 }
 
 // A pair's row of cape_map_union from the step's outcome (the map polygon had no hole; both operands within
-// CAPE_MAP_UNION_MAX_RING): a union with a hole, or one beyond the map's limits, is the host's; a served ring goes to `slab` at
-// `used` if it fits the `capacity` pairs.
+// CAPE_MAP_UNION_MAX_RING): a union with a hole -- however many, and however long: the device does not count them -- or an
+// outer ring beyond the map's limit is the host's; a served ring goes to `slab` at `used` if it fits the `capacity` pairs.
 void put_union_row(cape_plane_union& row, const Polygon& poly, const PolygonStep& step, uint32_t& used, uint32_t capacity, double* slab)
 {
-    if (step.overflow)
-        row.flags = CAPE_UNION_HOST_CAPACITY;
-    else if (!poly.interior_rings().empty())
+    if (step.holed)
         row.flags = CAPE_UNION_HOST_NEW_HOLE;
+    else if (step.overflow)
+        row.flags = CAPE_UNION_HOST_CAPACITY;
     else if (poly.boundary().size() > capacity - used)
         row.flags = CAPE_UNION_HOST_CAPACITY;
     else

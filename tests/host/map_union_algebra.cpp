@@ -10,8 +10,10 @@
 //   g++ -O2 -std=c++17 -ffp-contract=off -fsanitize=address,undefined -I../../tests/host/hip_stub -I. -I../host -I../host/compat \
 //       -o ../lib/map_union_algebra.exe ../../tests/host/map_union_algebra.cpp && ../lib/map_union_algebra.exe
 //
-// What needs the wave and is therefore covered on the GPU only (tests/test_gpu_map_union.py): the cut list and its sort, node_of's
-// search, link, the face walks, the probe loop, ring_is_simple's lane loop, drop_collinear's erase, the Douglas-Peucker stack loop.
+// What needs the wave and is therefore covered on the GPU only (tests/test_gpu_map_union.py): the ballot-ordered cut list, node_of's
+// search, link, the face walks, the probe loop, every barrier and the LDS carve.  The rank sort, ring_is_simple's lane loop,
+// drop_collinear's erase and the Douglas-Peucker reduction are restated below in the wave's shape (seq::), and run on the named long
+// pairs of tests/test_map_union_host.py, whose flags, vertex counts and node counts the program prints and checks.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -31,10 +33,13 @@ using rgbd_slam::vector3;
 static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
 // ---- The per-pair order of statements of csrc/cape_map_union.h's union_pair, one lane at a time: the same per-lane functions in the
-// same order, every lane loop flattened (the cut list in pair order instead of ballot order, which the sort makes irrelevant).  It
-// checks that the restatement -- cuts sorted on their bit patterns, edges marked seen while they are walked, a hole judged as soon as
-// its face is known, the closing-vertex and orientation rules of the constructor, the disjoint fact -- is the host class's
-// merge_union and simplify; the wave's mechanics are the GPU tests'.
+// same order (the cut list in pair order instead of ballot order, which the sort makes irrelevant).  Four loops keep the wave's
+// shape, 64 lanes at a time, because their chunking decides the result: the rank sort of the cuts, ring_is_simple's rounds with
+// every other one reversed, drop_collinear's erase and the Douglas-Peucker reduction with its tie rule.  It checks that the
+// restatement -- cuts ranked on their bit patterns, edges marked seen while they are walked, a hole judged as soon as its face is
+// known, the closing-vertex and orientation rules of the constructor, the disjoint fact -- is the host class's merge_union and
+// simplify, on random pairs and on the named long pairs below, whose node counts it also yields; the wave's mechanics (ballots,
+// barriers, LDS) are the GPU tests'.
 namespace seq {
 using cape::usame;
 struct Out
@@ -42,6 +47,7 @@ struct Out
     uint32_t flags = 0;
     std::vector<double2> ring;
     double area = 0;
+    int nNodes = 0; // the arrangement's nodes: what the device reports as n_nodes (counted on, not capped, beyond its capacity)
 };
 static double signed_area(const std::vector<double2>& r)
 {
@@ -72,14 +78,23 @@ static bool simple(const std::vector<double2>& r)
     const size_t n = r.size();
     if (n < 3)
         return false;
-    for (size_t i = 0; i < n; ++i)
-        for (size_t j = i + 1; j < n; ++j)
+    // the device's lanes: 64 first edges at a time, every other round with the lanes reversed; a lane that met a pair stops looking
+    bool bad[64] = {};
+    for (size_t base = 0, round = 0; base < n; base += 64, ++round)
+        for (size_t lane = 0; lane < 64; ++lane)
         {
-            if (j == i + 1 || (i == 0 && j == n - 1))
+            const size_t i = base + ((round & 1) ? 63 - lane : lane);
+            if (i >= n)
                 continue;
-            if (cape::union_segments_intersect(r[i], r[(i + 1) % n], r[j], r[(j + 1) % n]))
-                return false;
+            for (size_t j = i + 1; j < n && !bad[lane]; ++j)
+            {
+                if (j == i + 1 || (i == 0 && j == n - 1))
+                    continue;
+                bad[lane] = cape::union_segments_intersect(r[i], r[(i + 1) % n], r[j], r[(j + 1) % n]);
+            }
         }
+    if (std::any_of(bad, bad + 64, [](bool b) { return b; }))
+        return false;
     return std::abs(signed_area(r)) > 0;
 }
 static void drop(std::vector<double2>& r)
@@ -91,7 +106,18 @@ static void drop(std::vector<double2>& r)
         for (size_t i = 0; i < r.size() && r.size() > 3; ++i)
             if (cape::union_collinear(r[(i + r.size() - 1) % r.size()], r[i], r[(i + 1) % r.size()]))
             {
-                r.erase(r.begin() + static_cast<long>(i));
+                // the device's erase: the tail moves down 64 vertices at a time, every lane reading before any lane writes
+                const size_t n = r.size();
+                for (size_t base = i; base + 1 < n; base += 64)
+                {
+                    double2 v[64];
+                    for (size_t lane = 0; lane < 64; ++lane)
+                        v[lane] = base + lane + 1 < n ? r[base + lane + 1] : make_double2(0.0, 0.0);
+                    for (size_t lane = 0; lane < 64; ++lane)
+                        if (base + lane + 1 < n)
+                            r[base + lane] = v[lane];
+                }
+                r.pop_back();
                 changed = true;
                 --i;
             }
@@ -115,19 +141,29 @@ static void simplify(std::vector<double2>& ring, double& area)
         stack.pop_back();
         if (b <= a + 1)
             continue;
-        uint64_t best = 0;
-        int idx = -1;
-        for (int i = a + 1; i < b; ++i)
+        // the device's lanes: lane l looks at a + 1 + l, a + 1 + l + 64, ... and keeps its first largest; the wave takes the largest
+        // of the lanes' and, among the lanes that hold it, the lowest index: the host's strict > over the whole span
+        uint64_t laneBest[64] = {}, best = 0;
+        int laneIdx[64], idx = 0x7FFFFFFF;
+        for (int lane = 0; lane < 64; ++lane)
         {
-            const double d = cape::union_segment_distance2(closed[i], closed[a], closed[b]);
-            uint64_t db;
-            std::memcpy(&db, &d, sizeof db);
-            if (idx < 0 || db > best)
-                best = db, idx = i;
+            laneIdx[lane] = 0x7FFFFFFF;
+            for (int i = a + 1 + lane; i < b; i += 64)
+            {
+                const double d = cape::union_segment_distance2(closed[i], closed[a], closed[b]);
+                uint64_t db;
+                std::memcpy(&db, &d, sizeof db);
+                if (laneIdx[lane] == 0x7FFFFFFF || db > laneBest[lane])
+                    laneBest[lane] = db, laneIdx[lane] = i;
+            }
+            best = std::max(best, laneBest[lane]);
         }
+        for (int lane = 0; lane < 64; ++lane)
+            if (laneIdx[lane] != 0x7FFFFFFF && laneBest[lane] == best)
+                idx = std::min(idx, laneIdx[lane]);
         double dmax;
         std::memcpy(&dmax, &best, sizeof dmax);
-        if (dmax > eps * eps)
+        if (dmax > eps * eps && idx > a && idx < b)
         {
             keep[idx] = 1;
             stack.push_back({a, idx});
@@ -198,7 +234,19 @@ static Out pair(std::vector<double2> A, std::vector<double2> B)
                 if (ku) push(j, tu);
             }
         }
-    std::stable_sort(cuts.begin(), cuts.end(), [](const Cut& a, const Cut& b) { return a.seg < b.seg || (a.seg == b.seg && a.t < b.t); });
+    // the device's rank sort, statement for statement: a cut's place is the number of cuts before it in (segment, parameter, arrival)
+    // order.  A slot no cut claims keeps a segment that does not exist, which ends the node numbering early.
+    {
+        std::vector<Cut> sorted(cuts.size(), Cut {0xFFFFu, ~0ull});
+        for (size_t c = 0; c < cuts.size(); ++c)
+        {
+            size_t rank = 0;
+            for (size_t k = 0; k < cuts.size(); ++k)
+                rank += (cuts[k].seg < cuts[c].seg || (cuts[k].seg == cuts[c].seg && (cuts[k].t < cuts[c].t || (cuts[k].t == cuts[c].t && k < c)))) ? 1 : 0;
+            sorted[rank] = cuts[c];
+        }
+        cuts = sorted;
+    }
     std::vector<double2> nodes;
     std::vector<std::vector<int>> adj;
     bool capacity = false;
@@ -234,9 +282,11 @@ static Out pair(std::vector<double2> A, std::vector<double2> B)
         }
         link(prev, node_of(segs[s].b));
     }
-    const auto hosted = [](uint32_t f) {
+    out.nNodes = (int)nodes.size();
+    const auto hosted = [&](uint32_t f) {
         Out o;
         o.flags = f;
+        o.nNodes = (int)nodes.size();
         return o;
     };
     if (capacity)
@@ -370,7 +420,7 @@ static Out pair(std::vector<double2> A, std::vector<double2> B)
 } // namespace seq
 
 // one pair through the host class (merge_union with its info) and through seq::pair: flags, ring and area bit for bit
-static long compare_pair(const std::vector<vector2>& a, const std::vector<vector2>& b, long counts[4])
+static long compare_pair(const std::vector<vector2>& a, const std::vector<vector2>& b, long counts[4], seq::Out* port = nullptr)
 {
     const vector3 X(1, 0, 0), Y(0, 1, 0), C0(0, 0, 0);
     ref::Polygon pa(a, {}, X, Y, C0);
@@ -383,6 +433,8 @@ static long compare_pair(const std::vector<vector2>& a, const std::vector<vector
     ref::Polygon::MergeInfo info;
     const bool merged = pa.merge_union(pb, &info);
     const seq::Out mine = seq::pair(A, B);
+    if (port)
+        *port = mine;
     if (mine.flags & (CAPE_UNION_HOST_CAPACITY | CAPE_UNION_HOST_AMBIGUOUS))
     {
         ++counts[3];
@@ -400,6 +452,142 @@ static long compare_pair(const std::vector<vector2>& a, const std::vector<vector
         eq = same_bits(mine.ring[i].x, pa.boundary()[i][0]) && same_bits(mine.ring[i].y, pa.boundary()[i][1]);
     return eq ? 0 : 1;
 }
+
+// ---- The long pairs of tests/test_map_union_host.py (LONG_PAIRS, with its generators restated), and the two 128-gons of HAND_BUILT:
+// operands of more than 64 vertices.  Each pair goes through the host class and through seq::pair like the pairs above; the port's
+// flags, vertex count and node count are printed and checked against the table.  The node counts are the reference for the device's
+// n_nodes (LONG_NODES in the Python table); where the arithmetic is plain it is given.
+namespace named {
+using Ring = std::vector<vector2>;
+static Ring rect(double x0, double x1, double y0, double y1) { return {{x0, y0}, {x0, y1}, {x1, y1}, {x1, y0}}; }
+static Ring ngon(int n, double r, double cx, double cy, double phase)
+{
+    Ring o;
+    for (int i = 0; i < n; ++i)
+    {
+        const double t = phase + 2 * M_PI * i / n;
+        o.emplace_back(cx + r * std::cos(t), cy + r * std::sin(t));
+    }
+    return o;
+}
+static Ring comb(int teeth = 30, double pitch = 100, double width = 50, double spine = 100, double length = 3000)
+{
+    Ring o {{0, 0}, {(teeth - 1) * pitch + width, 0}};
+    for (int k = teeth - 1; k >= 0; --k)
+    {
+        const double x = k * pitch;
+        o.insert(o.end(), {{x + width, spine}, {x + width, length}, {x, length}, {x, spine}});
+    }
+    return o;
+}
+static Ring cog(double even = 1000, double odd = 700, int n = 128)
+{
+    Ring o;
+    for (int i = 0; i < n; ++i)
+    {
+        const double t = 2 * M_PI * i / n, r = i % 2 == 0 ? even : odd;
+        o.emplace_back(r * std::cos(t), r * std::sin(t));
+    }
+    return o;
+}
+static Ring subdivided(const Ring& ring, int parts = 32)
+{
+    Ring o;
+    for (size_t i = 0; i < ring.size(); ++i)
+        for (int k = 0; k < parts; ++k)
+        {
+            const vector2 &a = ring[i], &b = ring[(i + 1) % ring.size()];
+            o.emplace_back(a[0] + (b[0] - a[0]) * k / parts, a[1] + (b[1] - a[1]) * k / parts);
+        }
+    return o;
+}
+static Ring saw(int teeth = 60)
+{
+    Ring o {{0, 0}, {100.0 * teeth, 0}};
+    for (int k = teeth; k >= 1; --k)
+        o.insert(o.end(), {{100.0 * k, 1000}, {100.0 * (k - 0.5), 2000}});
+    o.emplace_back(0, 1000);
+    return o;
+}
+// (p - c) M + c for row vectors
+static Ring about(const Ring& ring, double cx, double cy, double m00, double m01, double m10, double m11)
+{
+    Ring o;
+    for (const vector2& p : ring)
+        o.emplace_back((p[0] - cx) * m00 + (p[1] - cy) * m10 + cx, (p[0] - cx) * m01 + (p[1] - cy) * m11 + cy);
+    return o;
+}
+static Ring mirrored(const Ring& ring, double dx, double dy)
+{
+    Ring o;
+    for (const vector2& p : ring)
+        o.emplace_back(p[0] + dx, -p[1] + dy);
+    return o;
+}
+static Ring rake()
+{
+    Ring o;
+    for (const vector2& p : comb(3, 100, 50, 100, 3200))
+        o.emplace_back(p[1] - 150, p[0] + 1000);
+    Ring extra;
+    for (int k = 1; k < 18; ++k)
+        extra.emplace_back(-150.0, 1000 + 10.0 * k);
+    o.insert(o.begin() + 1, extra.begin(), extra.end());
+    return o;
+}
+static Ring snag(int teeth = 32)
+{
+    Ring o {{-100, -100}, {130, -100}, {130, 1000}, {30, 1000}, {30, 505}, {-8, 500}, {30, 495}, {30, 0},
+            {0, 0}, {0, 480}, {-9, 490}, {-9, 510}, {0, 520}, {0, 1000}, {-50, 1050}};
+    const double pitch = 600.0 / teeth;
+    for (int k = 0; k < teeth; ++k)
+    {
+        o.emplace_back(-200.0, 1000 - pitch * (k + 0.5));
+        if (k + 1 < teeth)
+            o.emplace_back(-100.0, 1000 - pitch * (k + 1));
+    }
+    return o;
+}
+static Ring snag_plate(int teeth = 32)
+{
+    Ring o {{-50, -80}, {-50, 380}, {-150, 380}};
+    const double pitch = 460.0 / teeth;
+    for (int k = 0; k < teeth; ++k)
+        o.insert(o.end(), {{-300.0, 380 - pitch * (k + 0.5)}, {-150.0, 380 - pitch * (k + 1)}});
+    return o;
+}
+struct Pair
+{
+    const char* name;
+    Ring a, b;
+    uint32_t flags; // the port's
+    int count;      // vertices of the served ring, -1: none
+    int nodes;
+};
+static std::vector<Pair> table()
+{
+    const Ring pinch8 {{0, 0}, {400, 400}, {800, 0}, {800, 800}, {400, 400}, {0, 800}};
+    const Ring pinch10 {{0, 0}, {400, 400}, {800, 0}, {900, 400}, {400, 400}, {800, 800}, {400, 900}, {400, 400}, {0, 800}};
+    const Ring turned = about(pinch8, 400, 400, .6, .8, -.8, .6);
+    const uint32_t S = CAPE_UNION_SERVED, H = CAPE_UNION_HOST_NEW_HOLE, C = CAPE_UNION_HOST_CAPACITY;
+    return {
+        {"two 128-gons", ngon(128, 1000, 0, 0, 0.01), ngon(128, 1000, 700, 100, 0.01), S, 18, 258},             // 256 vertices, 2 crossings
+        {"half-step 128-gons", ngon(128, 1000, 0, 0, 0), ngon(128, 1000, 0, 0, M_PI / 128), S, 16, 512},        // 256 vertices, every edge crossed twice
+        {"mirrored cogs", cog(), mirrored(cog(), 150, 40), S, 188, 386},
+        {"half-step cogs", cog(), cog(700, 1000), S, 256, 384},                                                  // 256 vertices, every edge crossed once
+        {"subdivided squares", subdivided(rect(0, 400, 0, 400)), subdivided(rect(200, 600, 200, 600)), S, 8, 254}, // 256 vertices, two shared
+        {"comb and foot", comb(), rect(-50, 100, -50, 50), S, 124, 122 + 4 + 2},
+        {"saw and bar", saw(), rect(100, 5900, 500, 1500), S, 122, 123 + 4 + 116},
+        {"comb of 9 and bar", comb(9), rect(-100, 1000, 1500, 1600), H, -1, 38 + 4 + 36},                      // each tooth crossed 4 times
+        {"comb of 10 and bar", comb(10), rect(-100, 1100, 1500, 1600), H, -1, 42 + 4 + 40},
+        {"comb of 30 and bar", comb(), rect(-100, 3100, 1500, 1600), H, -1, 122 + 4 + 120},
+        {"pinched rings, degree 8", pinch8, turned, S, 16, 15},   // 5 + 5 distinct vertices, the centre shared, 6 crossings
+        {"pinched rings, degree 10", pinch10, turned, C, -1, 15}, // 7 + 5 distinct vertices, the centre shared, 4 crossings
+        {"comb and rake, 513 nodes", comb(), rake(), C, -1, 122 + 31 + 360},
+        {"snag at candidate edge 127", snag(), snag_plate(), S, 159, 177}, // (the last tooth's lower edge runs down to the corner through the plate's teeth)
+    };
+}
+} // namespace named
 
 int main()
 {
@@ -645,6 +833,18 @@ int main()
     bad += compare_pair({{0, 0}, {3000, 0}, {3000, 1000}, {1000, 1000}, {1000, 2000}, {3000, 2000}, {3000, 3000}, {0, 3000}},
                         rect(2500, 4000, 0, 3000), pairCounts);
     ++nPairs;
+    // ---- the named long pairs
+    long namedCounts[4] = {0, 0, 0, 0};
+    for (const named::Pair& c : named::table())
+    {
+        seq::Out port;
+        const long differs = compare_pair(c.a, c.b, namedCounts, &port);
+        const int count = (port.flags & CAPE_UNION_SERVED) ? (int)port.ring.size() : -1;
+        const bool asTable = port.flags == c.flags && count == c.count && port.nNodes == c.nodes;
+        std::printf("%-27s flags 0x%02x  vertices %3d  nodes %3d%s%s\n", c.name, port.flags, count, port.nNodes,
+                    differs ? "  DIFFERS from the host class" : "", asTable ? "" : "  NOT the table's");
+        bad += differs + !asTable;
+    }
     std::printf("pairs: %ld (served %ld, disjoint %ld, new hole %ld, capacity or ambiguous %ld)\n", nPairs, pairCounts[0], pairCounts[1],
                 pairCounts[2], pairCounts[3]);
     bad += pairCounts[3] != 0 || pairCounts[0] < 1000 || pairCounts[1] < 10 || pairCounts[2] < 10;

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from test_gpu_map_kalman import _tracks, room  # noqa: F401  (the eight room frames after the four calls)
-from test_map_union_host import CAPACITY, HAND_BUILT, classify, star_pairs
+from test_map_union_host import ALL_PAIRS, CAPACITY, DEVICE_CAPACITY, HAND_BUILT, LONG_NODES, LONG_PAIRS, SERVED, classify, star_pairs
 
 pytestmark = pytest.mark.gpu
 
@@ -102,15 +102,69 @@ def test_debug_entry_equals_the_twin_on_hand_built_pairs(ex1, host_binaries):
     counts = [0] * 7
     for name, a, b, cls, count in HAND_BUILT:
         row = _one_pair(ca, ex1, name, a, b, None, counts, allow_device_only=(name == "crossed combs"))
-        assert classify(ca, int(row["flags"])) == cls, name
+        assert classify(ca, int(row["flags"])) == (CAPACITY if name in DEVICE_CAPACITY else cls), name
         if count is not None:
             assert row["vertex_count"] == count, name
-        if cls == CAPACITY:
+        if cls == CAPACITY or name in DEVICE_CAPACITY:
             assert row["flags"] == ca.UNION_HOST_CAPACITY, name
     rng = np.random.default_rng(5)
     for name, a, b, cls, _ in HAND_BUILT:
         _one_pair(ca, ex1, name + " (tilted)", a, b, _tilted_frames(rng), counts, allow_device_only=(name == "crossed combs"))
     print(f"\nhand-built pairs, canonical and tilted frames: pairs per flag bit {counts}")
+
+
+def test_debug_entry_equals_the_twin_on_long_pairs(ex1, host_binaries):
+    """Operands of more than 64 vertices (LONG_PAIRS of tests/test_map_union_host.py, and the two 128-gons): every lane loop of the wave
+    runs more than one 64-wide chunk.  Rows and rings are the twin's bit for bit in canonical and in tilted frames; in canonical frames
+    the class and the vertex count are the table's and n_nodes of a served pair is the one-lane port's
+    (tests/host/map_union_algebra.cpp).  Only the pairs of DEVICE_CAPACITY may be the device's alone, as CAPE_UNION_HOST_CAPACITY and
+    nothing else -- in canonical frames they must be; HOST_AMBIGUOUS nowhere."""
+    import cape_amd as ca
+
+    pairs = [c for c in HAND_BUILT if c[0] == "two 128-gons"] + LONG_PAIRS
+    counts = [0] * 7
+    rng = np.random.default_rng(9)
+    print()
+    for name, a, b, cls, count in pairs:
+        alone = name in DEVICE_CAPACITY
+        for where, frames in (("canonical", None), ("tilted", _tilted_frames(rng))):
+            row, _ = ex1.debug_ring_union(a, b, frames)
+            trow, _ = ca.host_ring_union(a, b, frames)
+            device_only = _device_only(ca, int(row["flags"])) and not _device_only(ca, int(trow["flags"]))
+            print(f"{name:26s} {where:9s} flags {int(row['flags']):#04x} (twin {int(trow['flags']):#04x})  vertices {int(row['vertex_count']):3d}  "
+                  f"n_nodes {int(row['n_nodes']):3d}" + (f" (port {LONG_NODES[name]:3d})" if frames is None else "")
+                  + ("  the device's alone" if device_only else ""))
+            row = _one_pair(ca, ex1, f"{name} ({where})", a, b, frames, counts, allow_device_only=alone)
+            assert not row["flags"] & ca.UNION_HOST_AMBIGUOUS, f"{name} ({where})"
+            if device_only:
+                assert row["flags"] == ca.UNION_HOST_CAPACITY and row["vertex_count"] == 0 and row["area"] == 0, f"{name} ({where})"
+            if row["flags"] & ca.UNION_SERVED:
+                assert row["n_nodes"] > 64 or name.startswith("pinched"), f"{name} ({where}): node_of never left its first chunk"
+            if frames is not None:  # (each operand has a frame of its own: the rings shift against each other, the table does not hold)
+                continue
+            assert device_only == alone, name
+            if alone:
+                assert classify(ca, int(trow["flags"])) == cls, f"{name}: the twin"
+                continue
+            assert classify(ca, int(row["flags"])) == cls, name
+            if count is not None:
+                assert row["vertex_count"] == count, name
+            if cls == SERVED:
+                assert row["n_nodes"] == LONG_NODES[name], name
+    print(f"long pairs, canonical and tilted frames: pairs per flag bit {counts}")
+
+
+def test_a_pair_does_not_depend_on_the_pairs_before_it(ex1):
+    """Every pair of the tables through the one handle in table order and again in reverse: a row or ring that differs read something
+    an earlier pair left in the carve (the sorted cuts alias the walked rings; keep, seen and deg are written on demand)."""
+    rng = np.random.default_rng(10)
+    cases = [(name, a, b, frames) for name, a, b, _, _ in ALL_PAIRS for frames in (None, _tilted_frames(rng))]
+    forward = [ex1.debug_ring_union(a, b, frames) for _, a, b, frames in cases]
+    backward = [ex1.debug_ring_union(a, b, frames) for _, a, b, frames in reversed(cases)][::-1]
+    differ = [name + (" (tilted)" if frames is not None else "") for (name, _, _, frames), (r0, v0), (r1, v1) in zip(cases, forward, backward)
+              if r0.tobytes() != r1.tobytes() or not np.array_equal(_bits(v0), _bits(v1))]
+    print(f"\n{len(cases)} pairs in table order and in reverse: {len(differ)} differ {differ}")
+    assert not differ
 
 
 @pytest.mark.parametrize("n", [8, 24])
@@ -254,6 +308,70 @@ def test_map_holes_and_long_rings_are_the_hosts_pair_by_pair(room):  # noqa: F81
                 assert (rings[i] is None and brings[i] is None) or np.array_equal(_bits(rings[i]), _bits(brings[i]))
     print(f"\nmap plane {j_hole} given a hole, map plane {j_long} a ring of 129 vertices: {touched} frames hold a pair of theirs")
     assert touched >= 1
+    room.restore()
+
+
+def test_a_map_ring_of_128_vertices_is_served_by_the_frames_kernel(room):  # noqa: F811
+    """CAPE_MAP_UNION_MAX_RING exactly: one matched map plane whose pairs are all served gets the same outline with 128 vertices.  Its
+    pairs stay served with the vertex counts they had (simplify drops the added points), every frame is the twin's on the edited map,
+    and the other pairs do not move but for their place in the slab.
+
+    The added points lie on a shallow arc, not on the edge itself as in the 129-vertex test above: points interpolated on an edge are
+    collinear only up to rounding, and against the plane's own detection, whose edge is that very line, they give an arrangement
+    whose neighbours lie some 1e-14 rad apart.  The host class walks its faces by those angles (some of its walks do not close: it
+    skips those faces) and still returns the outline; the device hands such a pair to the host, as its guard band of 1e-10 rad demands
+    (CAPE_UNION_HOST_CAPACITY for the walk that does not close; measured on the device with this very map plane).  On the arc the
+    closest directions are 1e-5 rad apart."""
+    import cape_amd as ca
+
+    base = _union(room)
+    P, R, V = room.arrays
+    _, match, _ = room.matches
+
+    def pairs_of(j, got):
+        return [(f, i) for f in range(room.n) for i in range(len(room.meas[f])) if got[f][0][i]["map_plane"] == j]
+
+    j_long = next(j for j in range(len(P)) if pairs_of(j, base) and all(base[f][0][i]["flags"] & ca.UNION_SERVED for f, i in pairs_of(j, base)))
+    planes = []
+    for j in range(len(P)):
+        r = R[P[j]["ring_first"]]
+        outer = V[r["vertex_offset"]: r["vertex_offset"] + r["vertex_count"]].copy()
+        if j == j_long:  # the same outline with 128 vertices: points along its first edge, on an arc that bulges outwards by 0.01 mm
+            t = np.linspace(0, 1, W - len(outer) + 2)[1:-1, None]
+            x, y = outer[:, 0], outer[:, 1]
+            turn = np.sign(np.dot(x, np.roll(y, -1)) - np.dot(y, np.roll(x, -1)))
+            d = outer[1] - outer[0]
+            out = turn * np.array([d[1], -d[0]]) / np.hypot(*d)
+            outer = np.concatenate([outer[:1], outer[0] + t * d + 0.04 * t * (1 - t) * out, outer[1:]])
+            assert len(outer) == W == ca.MAP_UNION_MAX_RING
+        planes.append((P[j]["normal"], float(P[j]["d"]), P[j]["x_axis"], P[j]["y_axis"], P[j]["center"], outer, []))
+    arrays = ca.pack_map(planes)
+    ex, n, st = room.ex, room.n, room.st
+    ex.upload_map(arrays)
+    ex.upload_tracks(room.tracks)
+    ex.match_map_wide(n, room.W2C, None, room.flags, st)
+    ex.map_kalman(n, st)
+    assert np.array_equal(ex.map_matches_wide(n)[1], match), "the edit changed a match"
+    _, fusion, _ = ex.map_kalman_rows(n)
+    ex.map_union(n, st)
+    got = _compare_frames_with_twin(ca, ex, n, arrays, match, fusion, room.meas)
+    long_pairs = pairs_of(j_long, got)
+    print(f"\nmap plane {j_long} given a ring of {W} vertices: its pairs (frame, kept plane, flags, vertices, n_nodes; vertices before) "
+          f"{[(f, i, int(got[f][0][i]['flags']), int(got[f][0][i]['vertex_count']), int(got[f][0][i]['n_nodes']), int(base[f][0][i]['vertex_count'])) for f, i in long_pairs]}")
+    assert long_pairs == pairs_of(j_long, base) and len(long_pairs) >= 1
+    for f in range(n):
+        rows, rings = got[f]
+        brows, brings = base[f]
+        for i in range(W):
+            if (f, i) in long_pairs:
+                assert rows[i]["flags"] & ca.UNION_SERVED and rows[i]["flags"] == brows[i]["flags"], f"frame {f}, kept plane {i}"
+                assert rows[i]["vertex_count"] == brows[i]["vertex_count"], f"frame {f}, kept plane {i}"
+                assert rows[i]["n_nodes"] >= W, f"frame {f}, kept plane {i}: every vertex of the long ring is a node"
+            else:  # the other pairs: the same row and ring, wherever the slab has them
+                a, b = np.atleast_1d(rows[i]).copy(), np.atleast_1d(brows[i]).copy()
+                a["vertex_offset"] = b["vertex_offset"] = 0
+                assert a.tobytes() == b.tobytes(), f"frame {f}, kept plane {i}"
+                assert (rings[i] is None and brings[i] is None) or np.array_equal(_bits(rings[i]), _bits(brings[i]))
     room.restore()
 
 

@@ -71,8 +71,97 @@ HAND_BUILT = [
     ("two 128-gons", ngon(128, 1000, 0, 0, 0.01), ngon(128, 1000, 700, 100, 0.01), SERVED, 18),
     ("two 129-gons", ngon(129, 1000, 0, 0, 0.01), ngon(129, 1000, 700, 100, 0.01), CAPACITY, None),
     ("C shape and bar", C_SHAPE, rect(2500, 4000, 0, 3000), NEW_HOLE, None),
-    ("crossed combs", COMB, COMB[:, ::-1] + [1450.0, 1525.0], CAPACITY, None),
+    ("crossed combs", COMB, COMB[:, ::-1] + [1450.0, 1525.0], NEW_HOLE, None),  # (841 holes; the device: DEVICE_CAPACITY below)
 ]
+
+
+def cog(n=128, even=1000.0, odd=700.0):
+    """a cog of n vertices whose radii alternate: simplify keeps every vertex"""
+    t = 2 * np.pi * np.arange(n) / n
+    r = np.where(np.arange(n) % 2 == 0, even, odd)
+    return np.stack([r * np.cos(t), r * np.sin(t)], 1)
+
+
+def subdivided(ring, parts=32):
+    """every edge a -> b of the ring cut into `parts` equal parts: a + (b - a) * k / parts"""
+    k = np.arange(parts)[:, None]
+    return np.concatenate([a + (b - a) * k / parts for a, b in zip(ring, np.roll(ring, -1, axis=0))])
+
+
+def saw(teeth=60):
+    """a saw on a base along x: the valleys at y = 1000, the tips at y = 2000, 2 * teeth + 3 vertices"""
+    pts = [(0.0, 0.0), (100.0 * teeth, 0.0)]
+    for k in range(teeth, 0, -1):
+        pts += [(100.0 * k, 1000.0), (100.0 * (k - 0.5), 2000.0)]
+    return np.array(pts + [(0.0, 1000.0)], np.float64)
+
+
+def about(ring, centre, M):
+    """the ring's vertices about `centre` times the matrix M (row vectors)"""
+    return (np.asarray(ring, np.float64) - centre) @ np.asarray(M, np.float64) + centre
+
+
+def snag(teeth=32):
+    """A U whose arms stand 30 apart.  The left arm's inner wall has a dent 9 deep, below simplify's tolerance of 10; the right arm's
+    inner wall has a spike 38 long whose tip lies inside the dent.  Douglas-Peucker drops the dent and keeps the spike, so its
+    candidate crosses itself and simplify keeps the ring as it is.  Saw teeth on the upper left wall (and those of snag_plate below it)
+    bring the straightened wall to edge 127 of the candidate, the spike to edges 130 and 131: the only pairs of edges that meet."""
+    pts = [(-100.0, -100.0), (130.0, -100.0), (130.0, 1000.0), (30.0, 1000.0), (30.0, 505.0), (-8.0, 500.0), (30.0, 495.0), (30.0, 0.0),
+           (0.0, 0.0), (0.0, 480.0), (-9.0, 490.0), (-9.0, 510.0), (0.0, 520.0), (0.0, 1000.0), (-50.0, 1050.0)]
+    pitch = 600.0 / teeth
+    for k in range(teeth):
+        pts += [(-200.0, 1000.0 - pitch * (k + 0.5))] + ([(-100.0, 1000.0 - pitch * (k + 1))] if k + 1 < teeth else [])
+    return np.array(pts, np.float64)
+
+
+def snag_plate(teeth=32):
+    """a plate on the lower left wall of snag() with saw teeth of its own, further out"""
+    pts = [(-50.0, -80.0), (-50.0, 380.0), (-150.0, 380.0)]
+    pitch = 460.0 / teeth
+    for k in range(teeth):
+        pts += [(-300.0, 380.0 - pitch * (k + 0.5)), (-150.0, 380.0 - pitch * (k + 1))]
+    return np.array(pts, np.float64)
+
+
+COG = cog()
+PINCH_8 = np.array([[0, 0], [400, 400], [800, 0], [800, 800], [400, 400], [0, 800]], np.float64)
+PINCH_10 = np.array([[0, 0], [400, 400], [800, 0], [900, 400], [400, 400], [800, 800], [400, 900], [400, 400], [0, 800]], np.float64)
+PINCH_TURNED = about(PINCH_8, [400.0, 400.0], [[.6, .8], [-.8, .6]])
+# One node more than the device holds.  Two rings of at most 128 vertices whose union has no hole weave around each other like the
+# half-step 128-gons, which use every vertex and reach CAPE_MAP_UNION_MAX_NODES exactly; more nodes need edges that cross many
+# edges, which encloses cells: three horizontal teeth across the 30 vertical ones cross 360 times, 122 + 14 + 360 = 496 nodes, and 17
+# more vertices on the spine of ring b make 513.
+RAKE = comb(3, length=3200.0)[:, ::-1] + [-150.0, 1000.0]
+RAKE = np.concatenate([RAKE[:1], [[-150.0, 1000.0 + 10.0 * k] for k in range(1, 18)], RAKE[1:]])
+assert len(COG) == 128 and len(subdivided(rect(0, 400, 0, 400))) == 128 and len(saw()) == 123 and len(RAKE) == 31
+# The long pairs: operands of more than 64 vertices, whose cut lists, arrangements, walked faces, erased tails, Douglas-Peucker spans
+# and candidates all span more than one 64-wide chunk of the device's lane loops.  (name, ring a, ring b, expected class, expected
+# vertex count or None) like HAND_BUILT; LONG_NODES holds the arrangement's node count per pair from the one-lane port
+# (tests/host/map_union_algebra.cpp prints them), the reference for the device's n_nodes.
+LONG_PAIRS = [
+    ("half-step 128-gons", ngon(128, 1000, 0, 0, 0), ngon(128, 1000, 0, 0, np.pi / 128), SERVED, 16),
+    ("mirrored cogs", COG, COG * [1.0, -1.0] + [150.0, 40.0], SERVED, 188),
+    ("half-step cogs", COG, cog(even=700.0, odd=1000.0), SERVED, 256),
+    ("subdivided squares", subdivided(rect(0, 400, 0, 400)), subdivided(rect(200, 600, 200, 600)), SERVED, 8),
+    ("comb and foot", COMB, rect(-50, 100, -50, 50), SERVED, 124),
+    ("saw and bar", saw(), rect(100, 5900, 500, 1500), SERVED, 122),
+    ("comb of 9 and bar", comb(9), rect(-100, 1000, 1500, 1600), NEW_HOLE, None),
+    ("comb of 10 and bar", comb(10), rect(-100, 1100, 1500, 1600), NEW_HOLE, None),
+    ("comb of 30 and bar", COMB, rect(-100, 3100, 1500, 1600), NEW_HOLE, None),
+    ("pinched rings, degree 8", PINCH_8, PINCH_TURNED, SERVED, 16),
+    ("pinched rings, degree 10", PINCH_10, PINCH_TURNED, SERVED, 17),
+    ("comb and rake, 513 nodes", COMB, RAKE, NEW_HOLE, None),
+    ("snag at candidate edge 127", snag(), snag_plate(), SERVED, 159),
+]
+# what the device alone hands to the host (CAPE_UNION_HOST_CAPACITY) where the twin has an answer, the class of the table: more cuts
+# than its list holds (3 600), a node of 10 neighbours, and an arrangement of more than CAPE_MAP_UNION_MAX_NODES nodes
+DEVICE_CAPACITY = ("crossed combs", "pinched rings, degree 10", "comb and rake, 513 nodes")
+LONG_NODES = {
+    "two 128-gons": 258, "half-step 128-gons": 512, "mirrored cogs": 386, "half-step cogs": 384, "subdivided squares": 254,
+    "comb and foot": 128, "saw and bar": 243, "comb of 9 and bar": 78, "comb of 10 and bar": 86, "comb of 30 and bar": 246,
+    "pinched rings, degree 8": 15, "pinched rings, degree 10": 15, "comb and rake, 513 nodes": 513, "snag at candidate edge 127": 177,
+}
+ALL_PAIRS = HAND_BUILT + LONG_PAIRS
 
 
 def star(rng, n, cx, cy):
@@ -140,12 +229,13 @@ def _pair_against_the_update(ca, L, a, b, d=1010.0, holes=()):
         assert abs(row["area"] - 0.5 * abs(np.dot(x, np.roll(y, -1)) - np.dot(y, np.roll(x, -1)))) <= 1e-9 * row["area"]
     else:
         assert rings[0] is None and row["vertex_count"] == 0 and row["area"] == 0 and not row["x_axis"].any()
-        if row["flags"] & ca.UNION_HOST_NEW_HOLE:
-            assert P[0]["ring_count"] > 1
+        if row["flags"] & ca.UNION_HOST_NEW_HOLE:  # the update adds the holes, or -- more than CAPE_MAP_MAX_HOLES -- keeps the old polygon
+            assert row["flags"] == ca.UNION_HOST_NEW_HOLE
+            assert P[0]["ring_count"] > 1 or (Tr[0]["result"] & ca.MAP_RESULT_OVERFLOW and P[0]["ring_count"] == 1 and len(outer) == len(a))
     return row, rings[0], P[0], outer
 
 
-@pytest.mark.parametrize("case", HAND_BUILT, ids=[c[0] for c in HAND_BUILT])
+@pytest.mark.parametrize("case", ALL_PAIRS, ids=[c[0] for c in ALL_PAIRS])
 @pytest.mark.parametrize("d", [D, 1010.0], ids=["same plane", "fused plane"])
 def test_hand_built_pairs_equal_the_update(ca, L, case, d):
     _, a, b, cls, count = case
@@ -172,7 +262,7 @@ def test_star_sets_equal_the_update(ca, L, n):
 
 
 def test_ring_union_twin_classes(ca):
-    for name, a, b, cls, count in HAND_BUILT:
+    for name, a, b, cls, count in ALL_PAIRS:
         row, ring = ca.host_ring_union(a, b)
         assert classify(ca, int(row["flags"])) == cls, name
         assert row["map_plane"] == 0 and row["n_nodes"] == 0
