@@ -161,7 +161,9 @@ static inline void make_givens(double p, double q, double& c, double& s)
     }
 }
 
-static void tridiagonal_qr_step(double* diag, double* subdiag, int start, int end, double Q[3][3])
+// `trace` (optional, here and in self_adjoint_eigen3_iterative) collects the kEigTrace* bits of cape_oracle.hpp: which
+// branches the solve took.  It is written only; no result depends on it.
+static void tridiagonal_qr_step(double* diag, double* subdiag, int start, int end, double Q[3][3], unsigned* trace = nullptr)
 {
     // Wilkinson shift
     const double td = (diag[end - 1] - diag[end]) * 0.5;
@@ -169,12 +171,16 @@ static void tridiagonal_qr_step(double* diag, double* subdiag, int start, int en
     double mu = diag[end];
     if (td == 0.0)
     {
+        if (trace)
+            *trace |= kEigTraceShiftTdZero;
         mu -= std::abs(e);
     }
     else if (e != 0.0)
     {
         const double e2 = e * e;
         const double h = eigen_hypot(td, e);
+        if (trace && e2 == 0.0)
+            *trace |= kEigTraceShiftE2Zero;
         if (e2 == 0.0)
             mu -= e / ((td + (td > 0.0 ? h : -h)) / e);
         else
@@ -218,7 +224,8 @@ static void tridiagonal_qr_step(double* diag, double* subdiag, int start, int en
     }
 }
 
-static void self_adjoint_eigen3_iterative(const double lower[3][3], double evals[3], double evecs[3][3], int* iterations)
+static void self_adjoint_eigen3_iterative(const double lower[3][3], double evals[3], double evecs[3][3], int* iterations,
+                                          unsigned* trace = nullptr)
 {
     double m00 = lower[0][0], m10 = lower[1][0], m11 = lower[1][1];
     double m20 = lower[2][0], m21 = lower[2][1], m22 = lower[2][2];
@@ -245,6 +252,8 @@ static void self_adjoint_eigen3_iterative(const double lower[3][3], double evals
     const double tol = std::numeric_limits<double>::min();
     diag[0] = m00;
     const double v1norm2 = m20 * m20;
+    if (trace)
+        *trace |= (v1norm2 <= tol) ? kEigTraceTridiagSkipped : kEigTraceTridiagReflected;
     if (v1norm2 <= tol)
     {
         diag[1] = m11;
@@ -300,11 +309,17 @@ static void self_adjoint_eigen3_iterative(const double lower[3][3], double evals
             break;
         iter++;
         if (iter > maxIterations * n)
+        {
+            if (trace)
+                *trace |= kEigTraceIterationCap;
             break;
+        }
         start = end - 1;
         while (start > 0 && sub[start - 1] != 0.0)
             start--;
-        tridiagonal_qr_step(diag, sub, start, end, Q);
+        if (trace)
+            *trace |= (start == 1) ? kEigTraceBlock12 : (end == 2) ? kEigTraceBlock02 : kEigTraceBlock01;
+        tridiagonal_qr_step(diag, sub, start, end, Q, trace);
     }
     if (iterations)
         *iterations = iter;
@@ -485,6 +500,17 @@ void self_adjoint_eigen3(const double lower[3][3], double evals[3], double evecs
     self_adjoint_eigen3_variant(lower, evals, evecs);
 #else
     self_adjoint_eigen3_iterative(lower, evals, evecs, iterations);
+#endif
+}
+
+void self_adjoint_eigen3_trace(const double lower[3][3], double evals[3], double evecs[3][3], int* iterations, unsigned* trace)
+{
+    if (trace)
+        *trace = 0;
+#if CAPE_VAR_EIGEN
+    self_adjoint_eigen3(lower, evals, evecs, iterations); // the variants have no loop to trace
+#else
+    self_adjoint_eigen3_iterative(lower, evals, evecs, iterations, trace);
 #endif
 }
 
@@ -1866,6 +1892,34 @@ void cape_oracle_eigen3(const double* lower9 /* row-major 3x3 */, double* evals,
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c)
             evecs9[3 * r + c] = ev[r][c];
+}
+void cape_oracle_eigen3_trace(const double* lower9 /* row-major 3x3 */, double* evals, double* evecs9, int* iters, unsigned* trace)
+{
+    double m[3][3], ev[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+            m[r][c] = lower9[3 * r + c];
+    self_adjoint_eigen3_trace(m, evals, ev, iters, trace);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c)
+            evecs9[3 * r + c] = ev[r][c];
+}
+// fit_plane on caller-supplied sums (the device's order: Sx Sy Sz Sxs Sys Szs Sxy Syz Szx) ; out10 in CAPE_DEBUG_FIT_PLANE's order
+void cape_oracle_fit_plane(const double* sums9, unsigned n, double* out10 /* nx ny nz d cx cy cz mse score planar */)
+{
+    PlaneSeg s;
+    clear_segment(s);
+    s.n = n;
+    s.Sx = sums9[0]; s.Sy = sums9[1]; s.Sz = sums9[2];
+    s.Sxs = sums9[3]; s.Sys = sums9[4]; s.Szs = sums9[5];
+    s.Sxy = sums9[6]; s.Syz = sums9[7]; s.Szx = sums9[8];
+    fit_plane(s);
+    out10[0] = s.normal[0]; out10[1] = s.normal[1]; out10[2] = s.normal[2];
+    out10[3] = s.d;
+    out10[4] = s.centroid[0]; out10[5] = s.centroid[1]; out10[6] = s.centroid[2];
+    out10[7] = s.mse;
+    out10[8] = s.score;
+    out10[9] = s.planar ? 1.0 : 0.0;
 }
 double cape_oracle_mt19937_double(unsigned seed, int index) { return mt19937_first_double(seed, index); }
 void cape_oracle_back_project(void* h, double col, double row, double z, double* out)

@@ -139,6 +139,16 @@ class Oracle
 // ---- free functions exposed for known-answer tests ----
 double depth_quantization(double depth);                       // covariances.cpp:12-19
 void self_adjoint_eigen3(const double lower[3][3], double evals[3], double evecs[3][3], int* iterations);
+// the same solve, plus which of its branches ran (kEigTrace* bits; 0 in a CAPE_VAR_EIGEN build, whose variants have no such loop)
+constexpr unsigned kEigTraceBlock01 = 1u << 0;          // a QR step on block (start,end) = [0,1]
+constexpr unsigned kEigTraceBlock02 = 1u << 1;          // ... [0,2]
+constexpr unsigned kEigTraceBlock12 = 1u << 2;          // ... [1,2]
+constexpr unsigned kEigTraceTridiagSkipped = 1u << 3;   // tridiagonalisation: v1norm2 <= DBL_MIN, the matrix is taken as it is
+constexpr unsigned kEigTraceTridiagReflected = 1u << 4; // ... the Householder reflection ran
+constexpr unsigned kEigTraceShiftE2Zero = 1u << 5;      // Wilkinson shift: e != 0 with e * e == 0
+constexpr unsigned kEigTraceShiftTdZero = 1u << 6;      // Wilkinson shift: td == 0
+constexpr unsigned kEigTraceIterationCap = 1u << 7;     // the loop ended at maxIterations * n
+void self_adjoint_eigen3_trace(const double lower[3][3], double evals[3], double evecs[3][3], int* iterations, unsigned* trace);
 void fit_plane(PlaneSeg& s);                                   // plane_segment.cpp:232-284
 bool can_be_merged(const PlaneSeg& a, const PlaneSeg& p, double maxMatchDistance); // plane_segment.cpp:322-326
 void normalize3(double v[3]);                                  // Eigen normalize(), Appendix A.2

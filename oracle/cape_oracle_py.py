@@ -58,6 +58,8 @@ def lib(path=None):
         L.cape_oracle_depth_quantization.restype = C.c_double
         L.cape_oracle_depth_quantization.argtypes = [C.c_double]
         L.cape_oracle_eigen3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_oracle_eigen3_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_oracle_fit_plane.argtypes = [C.c_void_p, C.c_uint, C.c_void_p]
         L.cape_oracle_mt19937_double.restype = C.c_double
         L.cape_oracle_mt19937_double.argtypes = [C.c_uint, C.c_int]
         L.cape_oracle_back_project.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
@@ -185,6 +187,31 @@ def eigen3(m):
     it = C.c_int(0)
     lib().cape_oracle_eigen3(_p(m), _p(ev), _p(vec), C.byref(it))
     return ev, vec, it.value
+
+
+# bits of eigen3_trace()'s mask (kEigTrace* of cape_oracle.hpp)
+TRACE_BLOCK01, TRACE_BLOCK02, TRACE_BLOCK12 = 1, 2, 4
+TRACE_TRIDIAG_SKIPPED, TRACE_TRIDIAG_REFLECTED = 8, 16
+TRACE_SHIFT_E2_ZERO, TRACE_SHIFT_TD_ZERO, TRACE_ITERATION_CAP = 32, 64, 128
+
+
+def eigen3_trace(m):
+    """eigen3() plus the mask of the branches the solve took."""
+    m = np.ascontiguousarray(m, np.float64)
+    ev = np.zeros(3, np.float64)
+    vec = np.zeros((3, 3), np.float64)
+    it, tr = C.c_int(0), C.c_uint(0)
+    lib().cape_oracle_eigen3_trace(_p(m), _p(ev), _p(vec), C.byref(it), C.byref(tr))
+    return ev, vec, it.value, tr.value
+
+
+def fit_plane(S, n):
+    """Plane_Segment::fit_plane on the sums Sx Sy Sz Sxs Sys Szs Sxy Syz Szx of n points: nx ny nz d cx cy cz mse score planar."""
+    S = np.ascontiguousarray(S, np.float64)
+    assert S.shape == (9,)
+    out = np.zeros(10, np.float64)
+    lib().cape_oracle_fit_plane(_p(S), int(n), _p(out))
+    return out
 
 
 def mt19937_double(seed, index):
