@@ -951,7 +951,9 @@ enum
     CAPE_UNION_HOST_CAPACITY = 1u << 5,  /* an operand > MAX_RING, nodes > MAX_NODES, a node of more than 8 neighbours, a walk that
                                             reaches its guard or outgrows CAPE_MAP_MAX_RING, or the frame's vertex slab is full; never
                                             the number of holes */
-    CAPE_UNION_HOST_AMBIGUOUS = 1u << 6  /* an angle comparison of the face walk lies inside the guard band */
+    CAPE_UNION_HOST_AMBIGUOUS = 1u << 6, /* an angle comparison of the face walk lies inside the guard band */
+    CAPE_UNION_HOLES = 1u << 7,          /* with SERVED: the polygon has interior rings, see cape_plane_union_rings */
+    CAPE_UNION_HOST_HOLE_CUT = 1u << 8   /* a hole of the map plane is partly covered by the detection */
 };
 /* One row per kept plane i < 128 of a frame, like the fusion rows.  A pair with a CAPE_UNION_HOST_* bit carries no ring:
  * vertex_count = 0 and area = 0.  The frame is the new map polygon's: the fusion row's, except where the isApprox shortcut kept the
@@ -981,6 +983,37 @@ int cape_copy_map_union(cape_handle h, int32_t n_frames, cape_plane_union* rows 
 /* Device pointers of the same arrays.  Either may be NULL.  CAPE_ERR_CAPACITY when no cape_map_union has run on the current batch,
  * map, match, measurements and Kalman results. */
 int cape_device_map_union(cape_handle h, cape_plane_union** rows, double** vertices);
+
+/* The same half for a pair whose map plane HAS interior rings and / or whose union creates some: cape_map_union with the hole
+ * statements of the host class restated as well (cape_map_union itself and its results are unchanged; bits 3 and 4 are never set
+ * here).  Polygon::project re-projects every interior ring and add_hole orients it; every bounded face of the arrangement that lies
+ * inside neither operand becomes a hole after drop_collinear if it has >= 3 vertices and is simple, in face-walk order; the disjoint
+ * rule simplifies the projected map polygon WITH its holes where it is the bigger piece, and drops them where the detection is; a
+ * hole of the map plane is then kept (the detection covers at most 1e-12 of the bigger operand's area of it), dropped (the detection
+ * covers all of it) or -- partly covered -- hands the pair to the host as CAPE_UNION_HOST_HOLE_CUT, which wins over every capacity
+ * below; simplify() takes its tolerance and its 75 % rule from the area without the holes and replaces all rings or none.  A served
+ * polygon's rings lie back to back in the frame's slab from row.vertex_offset: the outer ring (row.vertex_count vertices), then the
+ * interior rings in the host's order (the new ones, then the kept ones in the map's order); row.area is Polygon::_area, the outer
+ * ring minus the holes; a polygon that does not fit the rest of the slab as a whole is CAPE_UNION_HOST_CAPACITY.  So is: a map plane
+ * of more than 1 + CAPE_MAP_MAX_HOLES rings, an interior ring of the map plane of more than CAPE_MAP_UNION_MAX_RING vertices, more
+ * than CAPE_MAP_UNION_HOLE_VERTICES vertices in the interior rings of the polygon before simplify(), more than CAPE_MAP_MAX_HOLES
+ * interior rings (the update reports CAPE_MAP_RESULT_OVERFLOW and keeps the old polygon) and a hole against a detection beyond the
+ * intersection's slab capacities (1024 slab boundaries, 16 edges of a ring over one slab). */
+#define CAPE_MAP_UNION_HOLE_VERTICES 512 /* vertices of all interior rings of a merged polygon before simplify() */
+typedef struct cape_plane_union_rings            /* 56 bytes, one per kept plane i < 128, parallel to cape_plane_union */
+{
+    uint32_t ring_count;                           /* 0 unless SERVED; 1 + interior rings */
+    uint32_t vertex_count[1 + CAPE_MAP_MAX_HOLES]; /* ring k's vertices; the rings lie back to back from row.vertex_offset */
+    uint32_t holes_new, holes_kept, holes_covered; /* what merge_union did (0 on the disjoint / unchanged paths) */
+    uint32_t pad;
+} cape_plane_union_rings;
+/* Preconditions and error codes of cape_map_union.  Writes the same row and slab buffers -- cape_copy_map_union and
+ * cape_device_map_union return them -- plus the rings table below.  A later cape_map_union overwrites the rows; the rings table is
+ * then no longer current, and the two calls below return CAPE_ERR_CAPACITY, as after anything that invalidates the union results. */
+int cape_map_union_holes(cape_handle h, int32_t n_frames, void* stream);
+/* Synchronous copy / device pointer of the rings table of the last cape_map_union_holes (n_frames x 128). */
+int cape_copy_map_union_rings(cape_handle h, int32_t n_frames, cape_plane_union_rings* rings /* n_frames x 128 */);
+int cape_device_map_union_rings(cape_handle h, cape_plane_union_rings** rings);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
@@ -1157,6 +1190,12 @@ int cape_debug_match_lists(cape_handle h, uint32_t* words32);
  * room for CAPE_MAP_MAX_RING (x, y) pairs.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, ring or output, n_a or n_b outside [3, 4096]. */
 int cape_debug_ring_union(cape_handle h, const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
                           cape_plane_union* row_out, double* vertices_out);
+/* The same for cape_map_union_holes' per-pair function.  rings_a: ring a's outer ring and its interior rings back to back, counts_a
+ * their n_rings_a lengths; rings_out: one cape_plane_union_rings; vertices_out: room for CAPE_MAP_UNION_FRAME_VERTICES (x, y) pairs,
+ * the served polygon's rings back to back.  CAPE_ERR_INVALID_ARGUMENT: a NULL argument (frames27 may be NULL), n_rings_a outside
+ * [1, 1 + CAPE_MAP_MAX_HOLES], a count or n_b outside [3, 4096].  Twin: cape_host_polygon_union. */
+int cape_debug_polygon_union(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                             const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out);
 
 /* The seed of the reference's random engine (src/utils/random.hpp:59-64): 0 under MAKE_DETERMINISTIC -- the default here, and the
  * mode BASELINE.json's bit-exactness is stated for --, `std::time(0)` taken once at process start otherwise.  The engine is

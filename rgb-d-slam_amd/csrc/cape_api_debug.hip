@@ -214,4 +214,57 @@ int cape_debug_ring_union(cape_handle h, const double* ring_a, int32_t n_a, cons
     return CAPE_OK;
 }
 
+int cape_debug_polygon_union(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                             const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
+{
+    static const double kCanonical[27] = {1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0};
+    if (!h || !rings_a || !counts_a || !ring_b || !row_out || !rings_out || !vertices_out || n_rings_a < 1 || n_rings_a > 1 + CAPE_MAP_MAX_HOLES ||
+        n_b < 3 || n_b > 4096)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null argument, n_rings_a outside [1, 1 + CAPE_MAP_MAX_HOLES] or a ring of fewer than 3 / more than 4096 vertices");
+    size_t n_a = 0;
+    for (int32_t k = 0; k < n_rings_a; ++k)
+    {
+        if (counts_a[k] < 3 || counts_a[k] > 4096)
+            return fail(CAPE_ERR_INVALID_ARGUMENT, "a ring of fewer than 3 / more than 4096 vertices");
+        n_a += (size_t)counts_a[k];
+    }
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    // a one-pair launch over buffers of its own (freed on the way out): the results of the last union call are not touched
+    Buffer<double> a, b, frames, verts;
+    Buffer<int32_t> counts;
+    Buffer<cape_plane_union> row;
+    Buffer<cape_plane_union_rings> ringRow;
+    CAPE_HIP_TRY(a.alloc(n_a * 2));
+    CAPE_HIP_TRY(counts.alloc((size_t)n_rings_a));
+    CAPE_HIP_TRY(b.alloc((size_t)n_b * 2));
+    CAPE_HIP_TRY(frames.alloc(27));
+    CAPE_HIP_TRY(verts.alloc((size_t)CAPE_MAP_UNION_FRAME_VERTICES * 2));
+    CAPE_HIP_TRY(row.alloc(1));
+    CAPE_HIP_TRY(ringRow.alloc(1));
+    CAPE_HIP_TRY(hipMemcpy(a, rings_a, n_a * 2 * sizeof(double), hipMemcpyHostToDevice));
+    CAPE_HIP_TRY(hipMemcpy(counts, counts_a, (size_t)n_rings_a * sizeof(int32_t), hipMemcpyHostToDevice));
+    CAPE_HIP_TRY(hipMemcpy(b, ring_b, (size_t)n_b * 2 * sizeof(double), hipMemcpyHostToDevice));
+    CAPE_HIP_TRY(hipMemcpy(frames, frames27 ? frames27 : kCanonical, 27 * sizeof(double), hipMemcpyHostToDevice));
+    cape::PolygonUnionParams p{};
+    p.ringsA = reinterpret_cast<const double2*>(a.get());
+    p.countsA = counts;
+    p.nRingsA = n_rings_a;
+    p.ringB = reinterpret_cast<const double2*>(b.get());
+    p.nB = n_b;
+    p.frames27 = frames;
+    p.row = row;
+    p.ringRow = ringRow;
+    p.vertices = reinterpret_cast<double2*>(verts.get());
+    CAPE_HIP_TRY(cape::launch_polygon_union(p, nullptr));
+    CAPE_HIP_TRY(hipDeviceSynchronize());
+    CAPE_HIP_TRY(copy_out(row_out, row, 0, 1));
+    CAPE_HIP_TRY(copy_out(rings_out, ringRow, 0, 1));
+    size_t n = 0;
+    for (uint32_t k = 0; k < rings_out->ring_count && k < 1 + CAPE_MAP_MAX_HOLES; ++k)
+        n += rings_out->vertex_count[k];
+    CAPE_HIP_TRY(copy_out(vertices_out, verts, 0, (n <= CAPE_MAP_UNION_FRAME_VERTICES ? n : 0) * 2));
+    return CAPE_OK;
+}
+
 } // extern "C"

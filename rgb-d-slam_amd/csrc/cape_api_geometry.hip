@@ -1252,7 +1252,8 @@ int cape_copy_map_kalman(cape_handle h, int32_t n_frames, cape_frame_map_kalman*
     return CAPE_OK;
 }
 
-int cape_map_union(cape_handle h, int32_t n_frames, void* stream_)
+// cape_map_union and cape_map_union_holes: the same preconditions, rows and slab; the second one's kernel and its rings table
+static int map_union(cape_handle h, int32_t n_frames, void* stream_, bool holes)
 {
     constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
     if (!h || n_frames < 0)
@@ -1262,6 +1263,7 @@ int cape_map_union(cape_handle h, int32_t n_frames, void* stream_)
     const auto& W = h->mapWide;
     const auto& M = h->measure;
     U.unionFrames = 0;
+    h->mapUnionRings.current = false;
     if (!kalman_results_live(h) || n_frames > K.kalmanFrames || K.kalmanN != h->map.n)
         return fail(CAPE_ERR_CAPACITY, "no cape_map_kalman on the current batch, map, tracks and measurements covers n_frames");
     if (n_frames == 0)
@@ -1271,6 +1273,8 @@ int cape_map_union(cape_handle h, int32_t n_frames, void* stream_)
     const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be writing them
     CAPE_HIP_TRY(U.rows.grow((size_t)n_frames * WP, drain));
     CAPE_HIP_TRY(U.vertices.grow((size_t)n_frames * SLAB * 2, drain));
+    if (holes)
+        CAPE_HIP_TRY(h->mapUnionRings.rows.grow((size_t)n_frames * WP, drain));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     StreamScope streamScope(h, stream);
     if (streamScope.rc() != CAPE_OK)
@@ -1292,9 +1296,40 @@ int cape_map_union(cape_handle h, int32_t n_frames, void* stream_)
     p.fusion = K.rows;
     p.rows = U.rows;
     p.vertices = reinterpret_cast<double2*>(U.vertices.get());
-    CAPE_HIP_TRY(cape::launch_map_union(p, n_frames, stream));
+    CAPE_HIP_TRY(holes ? cape::launch_map_union_holes(p, h->mapUnionRings.rows, n_frames, stream) : cape::launch_map_union(p, n_frames, stream));
     U.unionFrames = n_frames;
     U.kalmanRun = K.runs;
+    h->mapUnionRings.current = holes;
+    return CAPE_OK;
+}
+
+int cape_map_union(cape_handle h, int32_t n_frames, void* stream) { return map_union(h, n_frames, stream, false); }
+int cape_map_union_holes(cape_handle h, int32_t n_frames, void* stream) { return map_union(h, n_frames, stream, true); }
+
+int cape_device_map_union_rings(cape_handle h, cape_plane_union_rings** rings)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    if (!union_results_live(h) || !h->mapUnionRings.current)
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_union_holes has run on the current batch, map, match, measurements and Kalman results, or a cape_map_union has replaced its rows");
+    if (rings)
+        *rings = h->mapUnionRings.rows;
+    return CAPE_OK;
+}
+
+int cape_copy_map_union_rings(cape_handle h, int32_t n_frames, cape_plane_union_rings* rings)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+    if (!h || n_frames < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    const auto& U = h->mapUnion;
+    if (n_frames > (union_results_live(h) && h->mapUnionRings.current ? U.unionFrames : 0))
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_union_holes on the current batch, map, match, measurements and Kalman results (a cape_map_union replaces its rows)");
+    if (n_frames == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(copy_out(rings, h->mapUnionRings.rows, 0, (size_t)n_frames * WP));
     return CAPE_OK;
 }
 

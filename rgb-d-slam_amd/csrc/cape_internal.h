@@ -414,6 +414,20 @@ struct RingUnionParams
     double2* vertices; // CAPE_MAP_MAX_RING
 };
 
+// cape_debug_polygon_union: one pair of the holes mode, everything in device memory (ring a's rings back to back)
+struct PolygonUnionParams
+{
+    const double2* ringsA;
+    const int32_t* countsA; // nRingsA lengths: the outer ring, then the interior rings
+    int nRingsA;
+    const double2* ringB;
+    int nB;
+    const double* frames27;
+    cape_plane_union* row;
+    cape_plane_union_rings* ringRow;
+    double2* vertices; // CAPE_MAP_UNION_FRAME_VERTICES
+};
+
 // multi-GPU gather: device-side packing of the ragged primitive lists (cape_gather.hip)
 struct PackParams
 {

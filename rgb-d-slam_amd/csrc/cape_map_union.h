@@ -1,10 +1,15 @@
 // The polygon half of the map update for one matched pair (cape_map_union.hip, cape_debug_ring_union): the statements of
 // Polygon::project, merge_union, rings_union_outer, drop_collinear, ring_is_simple, simplify, douglas_peucker and segment_distance2 of
-// host/boundary_polygon.cpp in the host's order and with its early exits, for a map polygon without holes, on ONE wavefront.
+// host/boundary_polygon.cpp in the host's order and with its early exits, on ONE wavefront: union_pair for a map polygon without holes
+// whose union creates none, and beside it union_pair_holes (cape_map_union_holes, cape_debug_polygon_union) with add_hole,
+// carry_hole's kept and covered cases, Polygon::area and simplify over interior rings as well; a hole the detection covers in part
+// stays the host's.  The two share every per-lane and per-wave function; union_pair, union_simplify and the kernels that call them
+// are kept as they were, statement for statement, so that they compile to what they were.
 //
 // Two parts.  The first holds the plain per-lane functions (projection, cut parameters, crossing points, the angle of the face walk
-// with its guard band, the collinear test, the Douglas-Peucker distance): they need nothing of the wave and compile for the host too
-// (tests/host/map_union_algebra.cpp compares them with the host class under the sanitizers).  The second, under __HIPCC__, is the
+// with its guard band, the collinear test, the Douglas-Peucker distance, the bounding-box test in front of a hole's intersection): they
+// need nothing of the wave and compile for the host too (tests/host/map_union_algebra.cpp and map_union_holes_algebra.cpp compare them
+// and one-lane ports of both modes with the host class under the sanitizers).  The second, under __HIPCC__, is the
 // wave's part: the LDS carve, node_of's search (ballot, lowest set lane), the walks, the point tests, ring_is_simple and the
 // Douglas-Peucker loop.  What the host orders is uniform control flow: node numbering, the walks, drop_collinear's erase loop.
 //
@@ -178,6 +183,32 @@ __device__ __forceinline__ int union_point_edge(const double2& p, const double2&
     return 0;
 }
 
+// is p inside or on ring[0, n)?  One lane walks the whole ring: simplify's check of an interior ring's candidate against the
+// candidate outer ring (point_in_ring, closed)
+__device__ __forceinline__ bool union_point_in_or_on(const double2& p, const double2* ring, int n)
+{
+    bool on = false, inside = false;
+    for (int i = 0; i < n && !on; ++i)
+    {
+        const int e = union_point_edge(p, ring[i], ring[i == 0 ? n - 1 : i - 1]);
+        on = e == 2;
+        inside = inside != (e == 1);
+    }
+    return on || inside;
+}
+
+// are the bounding boxes of a[0, na) and b[0, nb) apart?  Then no slab of rings_inter_area holds an overlap and its sum is an empty
+// one: + 0.0 on the host too.
+__device__ __forceinline__ bool union_boxes_apart(const double2* a, int na, const double2* b, int nb)
+{
+    double ax0 = a[0].x, ax1 = a[0].x, ay0 = a[0].y, ay1 = a[0].y, bx0 = b[0].x, bx1 = b[0].x, by0 = b[0].y, by1 = b[0].y;
+    for (int v = 1; v < na; ++v)
+        ax0 = umin(ax0, a[v].x), ax1 = umax(ax1, a[v].x), ay0 = umin(ay0, a[v].y), ay1 = umax(ay1, a[v].y);
+    for (int v = 1; v < nb; ++v)
+        bx0 = umin(bx0, b[v].x), bx1 = umax(bx1, b[v].x), by0 = umin(by0, b[v].y), by1 = umax(by1, b[v].y);
+    return ax1 < bx0 || bx1 < ax0 || ay1 < by0 || by1 < ay0;
+}
+
 } // namespace
 
 } // namespace cape
@@ -254,6 +285,104 @@ __device__ __forceinline__ UnionLds union_carve(unsigned char* smem)
     L.keep = carve_at<unsigned char>(smem, o.keep);
     L.stack = carve_at<unsigned>(smem, o.stack);
     return L;
+}
+
+// ---- the carve of the holes mode (cape_map_union_holes, cape_debug_polygon_union): the carve above, the interior rings of the merged
+// polygon behind it, and the arrays of rings_inter_area (MpLds of cape_ring_area.h) for a hole against the detection.  The
+// intersection runs after the face walks, so most of its arrays borrow what is dead by then: the cut lists, the nodes and the
+// adjacency (`low`: cutT up to the outer ring) and the walked face (`face`).  Its tier: rings of kUnionRing vertices, 1024 slab
+// boundaries, 16 edges of a ring over one slab (Tier<1>'s figures) -- what the borrowed regions and an LDS share of half a CU hold.
+// simplify's candidates of the interior rings borrow the intersection's heights (`by`), dead once the last hole has been judged, and
+// the ring it closes the nodes and the adjacency.
+constexpr int kUnionHoleVertices = CAPE_MAP_UNION_HOLE_VERTICES; // interior rings of the merged polygon before simplify, in sum
+constexpr int kUnionHoles = CAPE_MAP_MAX_HOLES;
+constexpr int kUnionMpXs = 1024, kUnionMpStack = 16;
+struct UnionHolesLdsLayout
+{
+    size_t holes, holeLen, candLen, srcOff, srcLen, ea, eb, xs, terms, elo, ehi, bk, inc, by, pre, cnt, sidx, sh, cand, closed, bytes;
+};
+__host__ __device__ constexpr UnionHolesLdsLayout union_holes_layout()
+{
+    constexpr UnionLdsLayout u = union_layout();
+    UnionHolesLdsLayout o{};
+    Layout low; // [cutT, outer)
+    low.off = u.cutT;
+    o.ea = low.take<Edge>(kUnionRing, 16);
+    o.eb = low.take<Edge>(kUnionRing, 16);
+    o.xs = low.take<double>(kUnionMpXs);
+    o.terms = low.take<double>(64 * kUnionMpStack);
+    o.elo = low.take<int>(2 * kUnionRing);
+    o.ehi = low.take<int>(2 * kUnionRing);
+    CAPE_LAYOUT_CHECK(low.off <= u.outer);
+    // simplify closes an interior ring onto its vertex 0 in the place of the nodes and the adjacency (a face of kUnionOut vertices)
+    o.closed = low.alias<double2>(u.nodes, kUnionOut + 1, u.deg);
+    Layout face; // [face, keep)
+    face.off = u.face;
+    o.bk = face.take<unsigned short>(128 * kUnionMpStack);
+    o.inc = face.take<unsigned short>(128 * kUnionMpStack);
+    CAPE_LAYOUT_CHECK(face.off <= u.keep);
+    Layout l;
+    l.off = u.bytes;
+    o.holes = l.take<double2>(kUnionHoleVertices, 16);
+    o.by = l.take<double>(128 * kUnionMpStack, 16);
+    const size_t byEnd = l.off;
+    o.cand = l.alias<double2>(o.by, kUnionHoleVertices, byEnd);
+    o.pre = l.take<int>(2 * kUnionRing + 2);
+    o.cnt = l.take<int>(128);
+    o.sh = l.take<int>(8, 16);
+    o.srcOff = l.take<unsigned>(kUnionHoles);
+    o.sidx = l.take<unsigned char>(128 * kUnionMpStack);
+    o.holeLen = l.take<unsigned short>(kUnionHoles);
+    o.candLen = l.take<unsigned short>(kUnionHoles);
+    o.srcLen = l.take<unsigned short>(kUnionHoles);
+    o.bytes = l.end(16);
+    return o;
+}
+static_assert(union_layout().cutT % 16 == 0, "the borrowed edges are 16-byte aligned");
+static_assert(2 * union_holes_layout().bytes <= 160 * 1024, "two waves' carves fit the LDS of a CU");
+static_assert(kUnionHoleVertices * sizeof(double2) <= 128 * kUnionMpStack * sizeof(double), "the candidates fit the heights' place");
+
+struct UnionHolesLds
+{
+    double2 *holes, *cand;                // the interior rings back to back; simplify's candidates of them, at the same offsets
+    double2* closed;                      // kUnionOut + 1: the interior ring simplify is closing
+    unsigned short *holeLen, *candLen;    // kUnionHoles lengths each
+    unsigned* srcOff;                     // the map plane's interior rings: offsets into `src`, lengths (3 .. kUnionRing, checked)
+    unsigned short* srcLen;
+    const double2* src;
+    int nSrc;
+    MpLds mp;
+};
+__device__ __forceinline__ UnionHolesLds union_holes_carve(unsigned char* smem, const UnionLds& L)
+{
+    constexpr UnionHolesLdsLayout o = union_holes_layout();
+    UnionHolesLds H;
+    H.holes = carve_at<double2>(smem, o.holes);
+    H.cand = carve_at<double2>(smem, o.cand);
+    H.closed = carve_at<double2>(smem, o.closed);
+    H.holeLen = carve_at<unsigned short>(smem, o.holeLen);
+    H.candLen = carve_at<unsigned short>(smem, o.candLen);
+    H.srcOff = carve_at<unsigned>(smem, o.srcOff);
+    H.srcLen = carve_at<unsigned short>(smem, o.srcLen);
+    H.src = nullptr;
+    H.nSrc = 0;
+    H.mp.ringCap = kUnionRing;
+    H.mp.ringA = L.ringA; // a hole of the map plane
+    H.mp.ringB = L.ringB; // the detection's ring
+    H.mp.ea = carve_at<Edge>(smem, o.ea);
+    H.mp.eb = carve_at<Edge>(smem, o.eb);
+    H.mp.xs = carve_at<double>(smem, o.xs);
+    H.mp.terms = carve_at<double>(smem, o.terms);
+    H.mp.by = carve_at<double>(smem, o.by);
+    H.mp.elo = carve_at<int>(smem, o.elo);
+    H.mp.ehi = carve_at<int>(smem, o.ehi);
+    H.mp.pre = carve_at<int>(smem, o.pre);
+    H.mp.cnt = carve_at<int>(smem, o.cnt);
+    H.mp.bk = carve_at<unsigned short>(smem, o.bk);
+    H.mp.inc = carve_at<unsigned short>(smem, o.inc);
+    H.mp.sidx = carve_at<unsigned char>(smem, o.sidx);
+    H.mp.sh = carve_at<int>(smem, o.sh);
+    return H;
 }
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -452,6 +581,183 @@ __device__ __forceinline__ int union_simplify(const UnionLds& L, double2* ring, 
         }
     }
     return n;
+}
+
+// ---- interior rings (the holes mode)
+// The Douglas-Peucker candidate (the loop of union_simplify above, for any ring) of the closed ring ring[0, n) (room for n + 1: the ring is closed onto its vertex 0) for the
+// tolerance eps, into cand (room for n).  4 <= n <= kUnionOut.  Returns its length.
+__device__ __forceinline__ int union_dp_candidate(const UnionLds& L, double2* ring, int n, double2* cand, double eps, int lane)
+{
+    if (lane == 0)
+        ring[n] = ring[0]; // closed onto vertex 0
+    for (int i = lane; i <= n; i += 64)
+        L.keep[i] = (i == 0 || i == n) ? 1 : 0;
+    if (lane == 0)
+        L.stack[0] = (unsigned)n; // (a << 16) | b with a = 0
+    int sp = 1;
+    CAPE_MP_SYNC();
+    while (sp > 0)
+    {
+        const unsigned ab = L.stack[--sp];
+        const int a = uni((int)(ab >> 16)), b = uni((int)(ab & 0xFFFFu));
+        if (b <= a + 1 || b > n)
+            continue;
+        const double2 pa = ring[a], pb = ring[b];
+        unsigned long long best = 0ull; // squared distance bits (>= +0); the first index wins a tie, like the host's strict >
+        int bestI = 0x7FFFFFFF;
+        for (int i = a + 1 + lane; i < b; i += 64)
+        {
+            const double d = union_segment_distance2(ring[i], pa, pb);
+            const unsigned long long db = (unsigned long long)__double_as_longlong(d);
+            if (bestI == 0x7FFFFFFF || db > best)
+            {
+                best = db;
+                bestI = i;
+            }
+        }
+        const unsigned long long mx = ~wave_min_u64(~best);
+        const unsigned mineKey = (bestI != 0x7FFFFFFF && best == mx) ? (unsigned)(0x7FFFFFFF - bestI) : 0u;
+        const int idx = 0x7FFFFFFF - (int)wave_max_u32(mineKey);
+        const double dmax = __longlong_as_double((long long)mx);
+        if (dmax > eps * eps && idx > a && idx < b && sp + 2 <= kUnionStack)
+        {
+            if (lane == 0)
+            {
+                L.keep[idx] = 1;
+                L.stack[sp] = ((unsigned)a << 16) | (unsigned)idx;
+                L.stack[sp + 1] = ((unsigned)idx << 16) | (unsigned)b;
+            }
+            sp += 2;
+            CAPE_MP_SYNC();
+        }
+    }
+    int cn = 0;
+    for (int base = 0; base < n; base += 64)
+    {
+        const int i = base + lane;
+        const bool k = i < n && L.keep[i];
+        const unsigned long long kb = __ballot(k);
+        if (k)
+            cand[cn + __popcll(kb & ((1ull << lane) - 1ull))] = ring[i];
+        cn += __popcll(kb);
+    }
+    CAPE_MP_SYNC();
+    return cn;
+}
+
+// add_hole's orientation: reversed when the signed area is negative
+__device__ __forceinline__ void union_orient_hole(double2* ring, int n, int lane)
+{
+    const double s = ring_area_signed(ring, n);
+    CAPE_MP_SYNC();
+    if (s < 0)
+    {
+        for (int v = lane; v < n / 2; v += 64)
+        {
+            const double2 a = ring[v], b = ring[n - 1 - v];
+            ring[v] = b;
+            ring[n - 1 - v] = a;
+        }
+        CAPE_MP_SYNC();
+    }
+}
+
+// Polygon::area: the outer ring minus the interior rings in order, clamped at 0
+__device__ __forceinline__ double union_area_holed(const double2* ring, int n, const double2* holes, const unsigned short* len, int nHoles)
+{
+    if (n < 3)
+        return 0.0;
+    double a = fabs(ring_area_signed(ring, n));
+    for (int k = 0, at = 0; k < nHoles; ++k)
+    {
+        const int nk = uni(len[k]);
+        a -= fabs(ring_area_signed(holes + at, nk));
+        at += nk;
+    }
+    return a < 0 ? 0.0 : a;
+}
+
+// does every vertex of q[0, nq) lie inside or on ring[0, n)?  Lanes over the vertices, each walks the whole ring.
+__device__ __forceinline__ bool union_all_inside(const double2* q, int nq, const double2* ring, int n, int lane)
+{
+    bool out = false;
+    for (int v = lane; v < nq; v += 64)
+        out = out || !union_point_in_or_on(q[v], ring, n);
+    return !__any(out);
+}
+
+// Polygon::simplify of a polygon with nHoles interior rings in H.holes: the Douglas-Peucker candidates of the outer ring (into
+// `cand`, room for n) and of every interior ring of at least 4 vertices (into H.cand; H.closed takes the ring being closed); all
+// rings are replaced or none.  Returns the outer ring's new length; H.holeLen follows; area in / out.
+__device__ __forceinline__ int union_simplify_holed(const UnionLds& L, const UnionHolesLds& H, double2* ring, int n, int nHoles, double2* cand,
+                                                    double& area, int lane)
+{
+    double2* closed = H.closed;
+    area = union_area_holed(ring, n, H.holes, H.holeLen, nHoles); // the total area: eps and the 75 % rule are taken from it
+    if (n < 4 || n > kUnionOut)
+        return n;
+    const double eps = umax(area / 1e5, 10.0);
+    const int cn = union_dp_candidate(L, ring, n, cand, eps, lane);
+    bool valid = cn >= 3 && union_ring_is_simple(cand, cn, lane);
+    for (int k = 0, at = 0; valid && k < nHoles; ++k)
+    {
+        const int nk = uni(H.holeLen[k]);
+        int ck = nk;
+        if (nk < 4) // a triangle has nothing to drop: the candidate keeps it, and nothing is checked
+        {
+            for (int v = lane; v < nk; v += 64)
+                H.cand[at + v] = H.holes[at + v];
+            CAPE_MP_SYNC();
+        }
+        else
+        {
+            for (int v = lane; v < nk; v += 64)
+                closed[v] = H.holes[at + v];
+            CAPE_MP_SYNC();
+            ck = union_dp_candidate(L, closed, nk, H.cand + at, eps, lane);
+            valid = ck >= 3 && union_ring_is_simple(H.cand + at, ck, lane) && union_all_inside(H.cand + at, ck, cand, cn, lane);
+        }
+        if (lane == 0)
+            H.candLen[k] = (unsigned short)ck;
+        CAPE_MP_SYNC();
+        at += nk;
+    }
+    if (!valid)
+        return n;
+    // the candidates lie at their rings' old offsets: the area walks them one by one
+    double newArea = cn < 3 ? 0.0 : fabs(ring_area_signed(cand, cn));
+    for (int k = 0, at = 0; k < nHoles; ++k)
+    {
+        newArea -= fabs(ring_area_signed(H.cand + at, uni(H.candLen[k])));
+        at += uni(H.holeLen[k]);
+    }
+    newArea = newArea < 0 ? 0.0 : newArea;
+    if (!(newArea > area * 0.75))
+        return n;
+    CAPE_MP_SYNC();
+    for (int i = lane; i < cn; i += 64)
+        ring[i] = cand[i];
+    for (int k = 0, from = 0, to = 0; k < nHoles; ++k) // packed down: a ring never moves up, and ring k moves before ring k + 1 is read
+    {
+        const int nk = uni(H.holeLen[k]), ck = uni(H.candLen[k]);
+        for (int base = 0; base < ck; base += 64)
+        {
+            const int v = base + lane;
+            double2 q = make_double2(0.0, 0.0);
+            if (v < ck)
+                q = H.cand[from + v];
+            if (v < ck)
+                H.holes[to + v] = q;
+        }
+        CAPE_MP_SYNC();
+        if (lane == 0)
+            H.holeLen[k] = (unsigned short)ck;
+        from += nk;
+        to += ck;
+    }
+    CAPE_MP_SYNC();
+    area = newArea;
+    return cn;
 }
 
 // ---- the arrangement of the two rings (rings_union_outer)
@@ -855,6 +1161,412 @@ __device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, cons
     res.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u);
     res.n = union_simplify(L, out, nOuter, L.face, res.area, lane);
     res.ring = out;
+    return res;
+}
+
+// ... and of the holes mode: the interior rings lie back to back in UnionHolesLds::holes, their lengths in holeLen
+struct UnionHoleResult
+{
+    int nHoles;
+    uint32_t holesNew, holesKept, holesCovered;
+};
+
+// The map plane's interior rings as the projected polygon holds them (the holes mode): H.src / srcOff / srcLen describe them.
+struct UnionHoleFetch
+{
+    const UnionHolesLds& H;
+    const UnionFrame& fa;
+    const UnionFrame& target;
+    bool projected; // Polygon::project ran: the isApprox shortcut did not keep the map polygon's frame
+    int lane;
+    // ring k into dst: the Polygon constructor's add_hole, then -- if projected -- project's vertices and its add_hole.  Returns its length.
+    __device__ __forceinline__ int hole(int k, double2* dst) const
+    {
+        const unsigned off = (unsigned)uni((int)H.srcOff[k]);
+        const int n = uni(H.srcLen[k]);
+        for (int v = lane; v < n; v += 64)
+            dst[v] = H.src[off + v];
+        CAPE_MP_SYNC();
+        union_orient_hole(dst, n, lane);
+        if (projected)
+        {
+            for (int v = lane; v < n; v += 64)
+                dst[v] = union_project(dst[v], fa, target);
+            CAPE_MP_SYNC();
+            union_orient_hole(dst, n, lane);
+        }
+        return n;
+    }
+    // all of them into H.holes, back to back; false if they outgrow it
+    __device__ __forceinline__ bool all() const
+    {
+        int at = 0;
+        for (int k = 0; k < H.nSrc; ++k)
+        {
+            const int n = uni(H.srcLen[k]);
+            if (at + n > kUnionHoleVertices)
+                return false;
+            hole(k, H.holes + at);
+            if (lane == 0)
+                H.holeLen[k] = (unsigned short)n;
+            at += n;
+        }
+        CAPE_MP_SYNC();
+        return true;
+    }
+    // Polygon::area() of the projected map polygon with the outer ring A: its holes pass through `scratch` one by one
+    __device__ __forceinline__ double map_area(const double2* A, int nA, double2* scratch) const
+    {
+        double a = fabs(ring_area_signed(A, nA));
+        for (int k = 0; k < H.nSrc; ++k)
+        {
+            const int n = hole(k, scratch);
+            a -= fabs(ring_area_signed(scratch, n));
+            CAPE_MP_SYNC();
+        }
+        return a < 0 ? 0.0 : a;
+    }
+};
+
+// The same pair in the holes mode (cape_map_union_holes, cape_debug_polygon_union): union_pair's statements, restated here so that
+// union_pair itself stays as it was, with the host's hole statements between them.  H.src / srcOff / srcLen describe the map plane's
+// interior rings (H.nSrc <= kUnionHoles of 3 .. kUnionRing vertices each, inside their buffer: the caller has checked), which are
+// fetched, oriented and projected where the host's statements read them; faces the union encloses and holes the detection leaves alone
+// become the result's interior rings (`holes`; the rings in H.holes / H.holeLen).  Never HOST_MAP_HOLES or HOST_NEW_HOLE.
+__device__ inline UnionResult union_pair_holes(const UnionLds& L, const UnionHolesLds& H, int nA, int nB, const UnionFrame& fa, const UnionFrame& fb,
+                                               const UnionFrame& target, UnionFrame& frame, UnionHoleResult& holes, int lane)
+{
+    UnionResult res{};
+    bool projected = false;
+    // ---- 1. the map ring: as the host class holds it, then Polygon::project into the target unless its frame already is the target
+    union_orient(L.ringA, nA, lane);
+    frame = fa;
+    if (!(union_is_approx3(fa.c, target.c) && union_is_approx3(fa.x, target.x) && union_is_approx3(fa.y, target.y)))
+    {
+        for (int v = lane; v < nA; v += 64)
+            L.ringA[v] = union_project(L.ringA[v], fa, target);
+        CAPE_MP_SYNC();
+        union_orient(L.ringA, nA, lane);
+        frame = target;
+        projected = true;
+    }
+    // ---- 2. the detection: merge_union always projects it into this polygon's frame
+    union_orient(L.ringB, nB, lane);
+    for (int v = lane; v < nB; v += 64)
+        L.ringB[v] = union_project(L.ringB[v], fb, frame);
+    CAPE_MP_SYNC();
+    union_orient(L.ringB, nB, lane);
+    const double2 *A = L.ringA, *B = L.ringB;
+    const UnionHoleFetch fetch{H, fa, target, projected, lane};
+    const double areaMap = union_area(A, nA); // Polygon::_area of the projected map polygon (without holes)
+    res.flags = CAPE_UNION_SERVED | CAPE_UNION_UNCHANGED;
+    res.ring = A;
+    res.n = nA;
+    res.area = areaMap;
+    if (nA < 3 || nB < 3)
+        return res;
+    // ---- 3. rings_union_outer(A, B, &holes, 0)
+    UnionGraph G{};
+    double scale = 1.0;
+    for (int v = 0; v < nA; ++v)
+        scale = umax(scale, umax(fabs(A[v].x), fabs(A[v].y)));
+    for (int v = 0; v < nB; ++v)
+        scale = umax(scale, umax(fabs(B[v].x), fabs(B[v].y)));
+    const double eps = 1e-9 * scale;
+    G.eps = eps;
+    // the segment list without `same` endpoints, ring A's first (ballot compaction keeps ring order)
+    int nSegA = 0, nSeg = 0;
+    for (int r = 0; r < 2; ++r)
+    {
+        const double2* R = r ? B : A;
+        const int nR = r ? nB : nA;
+        for (int base = 0; base < nR; base += 64)
+        {
+            const int i = base + lane;
+            const bool keep = i < nR && !usame(R[i], R[i + 1 == nR ? 0 : i + 1], eps);
+            const unsigned long long kb = __ballot(keep);
+            if (keep)
+                L.segs[nSeg + __popcll(kb & ((1ull << lane) - 1ull))] = (unsigned short)((r << 8) | i);
+            nSeg += __popcll(kb);
+        }
+        if (r == 0)
+            nSegA = nSeg;
+    }
+    CAPE_MP_SYNC();
+    const int nSegB = nSeg - nSegA;
+    auto seg_a = [&](int s) {
+        const unsigned e = L.segs[s];
+        return (e >> 8) ? B[e & 0xFF] : A[e & 0xFF];
+    };
+    auto seg_b = [&](int s) {
+        const unsigned e = L.segs[s];
+        const int i = (int)(e & 0xFF);
+        return (e >> 8) ? B[i + 1 == nB ? 0 : i + 1] : A[i + 1 == nA ? 0 : i + 1];
+    };
+    // the cuts of every (A segment, B segment): lanes over the pairs, six possible cuts each, appended in ballot order (the per-segment
+    // sort below makes the order of arrival irrelevant)
+    int nCuts = 0;
+    bool cutOverflow = false;
+    for (int base = 0; base < nSegA * nSegB; base += 64)
+    {
+        const int q = base + lane;
+        const bool live = q < nSegA * nSegB;
+        double t[6] = {0, 0, 0, 0, 0, 0};
+        bool has[6] = {false, false, false, false, false, false};
+        int si = 0, ui = 0;
+        if (live)
+        {
+            si = q / nSegB;
+            ui = nSegA + q % nSegB;
+            const double2 sa = seg_a(si), sb = seg_b(si), ua = seg_a(ui), ub = seg_b(ui);
+            has[0] = union_param_on(sa, sb, ua, eps, t[0]);
+            has[1] = union_param_on(sa, sb, ub, eps, t[1]);
+            has[3] = union_param_on(ua, ub, sa, eps, t[3]);
+            has[4] = union_param_on(ua, ub, sb, eps, t[4]);
+            bool ks = false, ku = false;
+            if (union_crossing(sa, sb, ua, ub, eps, t[2], ks, t[5], ku))
+            {
+                has[2] = ks;
+                has[5] = ku;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+        {
+            const unsigned long long m = __ballot(has[c]);
+            const int at = nCuts + __popcll(m & ((1ull << lane) - 1ull));
+            if (has[c] && at < kUnionCuts)
+            {
+                L.cutT[at] = t[c];
+                L.cutSeg[at] = (unsigned short)(c < 3 ? si : ui);
+            }
+            nCuts += __popcll(m);
+        }
+        if (nCuts > kUnionCuts)
+        {
+            cutOverflow = true;
+            break;
+        }
+    }
+    CAPE_MP_SYNC();
+    if (cutOverflow)
+    {
+        res = UnionResult{};
+        res.flags = CAPE_UNION_HOST_CAPACITY;
+        return res;
+    }
+    // the cuts in (segment, parameter) order: a rank sort on the parameters' bit patterns (non-negative doubles: the numbers' order)
+    for (int base = 0; base < nCuts; base += 64)
+    {
+        const int c = base + lane;
+        if (c < nCuts)
+        {
+            const unsigned sc = L.cutSeg[c];
+            const unsigned long long tc = (unsigned long long)__double_as_longlong(L.cutT[c]);
+            int rank = 0;
+            for (int k = 0; k < nCuts; ++k)
+            {
+                const unsigned sk = L.cutSeg[k];
+                const unsigned long long tk = (unsigned long long)__double_as_longlong(L.cutT[k]);
+                rank += (sk < sc || (sk == sc && (tk < tc || (tk == tc && k < c)))) ? 1 : 0;
+            }
+            L.sortT[rank] = L.cutT[c];
+            L.sortSeg[rank] = (unsigned short)sc;
+        }
+    }
+    CAPE_MP_SYNC();
+    // nodes and undirected edges in the host's order: segments in order, cuts ascending, the first node within eps wins
+    int at = 0;
+    for (int s = 0; s < nSeg && !G.fail; ++s)
+    {
+        const double2 a = seg_a(s), b = seg_b(s);
+        int prev = union_node_of(L, G, a, lane);
+        while (at < nCuts && uni(L.sortSeg[at]) == s && !G.fail)
+        {
+            const int cur = union_node_of(L, G, union_cut_point(a, b, L.sortT[at]), lane);
+            union_link(L, G, prev, cur, lane);
+            prev = cur;
+            ++at;
+        }
+        if (!G.fail)
+            union_link(L, G, prev, union_node_of(L, G, b, lane), lane);
+    }
+    CAPE_MP_SYNC(); // (the sorted cuts are dead: the walked rings take their place)
+    res.nNodes = G.nNodes;
+    const auto hosted = [&](uint32_t bits) {
+        UnionResult r{};
+        r.flags = (bits & CAPE_UNION_HOST_CAPACITY) ? (uint32_t)CAPE_UNION_HOST_CAPACITY : bits;
+        r.nNodes = G.nNodes;
+        return r;
+    };
+    if (G.fail)
+        return hosted(G.fail);
+    int nOuter = 0;
+    int nNew = 0, newVertices = 0; // faces added as holes: all of them counted, stored while they fit
+    if (G.nNodes >= 3)
+    {
+        // the outer face from the lowest of the leftmost nodes, reached heading south
+        int start = 0;
+        for (int k = 1; k < G.nNodes; ++k)
+        {
+            const double2 pk = L.nodes[k], ps = L.nodes[start];
+            if (pk.x < ps.x - eps || (fabs(pk.x - ps.x) <= eps && pk.y < ps.y))
+                start = k;
+        }
+        const int firstSlot = union_next_of(L, G, start, make_double2(0.0, 1.0), -1, lane);
+        if (firstSlot >= 0)
+        {
+            nOuter = union_walk_face(L, G, start, firstSlot, L.outer, lane);
+            if (nOuter < 0)
+                return hosted(G.fail | CAPE_UNION_HOST_CAPACITY);
+            // every other face: bounded, walked clockwise; a hole of the union is one whose inside belongs to neither operand
+            for (int a = 0; a < G.nNodes && nOuter > 0; ++a)
+            {
+                const int da = uni(L.deg[a]);
+                for (int k = 0; k < da && k < kUnionDegree; ++k)
+                {
+                    if ((uni(L.seen[a]) >> k) & 1)
+                        continue;
+                    int nf = union_walk_face(L, G, a, k, L.face, lane);
+                    if (nf < 0)
+                        return hosted(G.fail | CAPE_UNION_HOST_CAPACITY);
+                    if (nf < 3 || ring_area_signed(L.face, nf) >= 0)
+                        continue; // not a bounded face (or a degenerate spur)
+                    // a point strictly inside the face: just right of the middle of one of its edges
+                    bool found = false;
+                    double2 probe = make_double2(0.0, 0.0);
+                    for (int i = 0; i < nf && !found; ++i)
+                    {
+                        const double2 p = L.face[i], q = L.face[i + 1 == nf ? 0 : i + 1];
+                        const double dx = q.x - p.x, dy = q.y - p.y, len = hypot(dx, dy);
+                        if (len <= eps)
+                            continue;
+                        int step = 0;
+                        for (double off = 1e-3; off >= 1e-7 && !found && step < 8; off *= 0.1, ++step)
+                        {
+                            probe = make_double2(0.5 * (p.x + q.x) + off * len * (dy / len), 0.5 * (p.y + q.y) - off * len * (dx / len));
+                            found = union_point_in_ring(probe, L.face, nf, false, lane);
+                        }
+                    }
+                    if (!found)
+                        continue;
+                    const bool inA = union_point_in_ring(probe, A, nA, true, lane), inB = union_point_in_ring(probe, B, nB, true, lane);
+                    if (inA || inB)
+                        continue;
+                    // merge_union's own test of a hole: drop_collinear, then at least 3 vertices and simple
+                    nf = union_drop_collinear(L.face, nf, lane);
+                    if (nf >= 3 && union_ring_is_simple(L.face, nf, lane))
+                    {
+                        if (nNew < kUnionHoles && newVertices + nf <= kUnionHoleVertices)
+                        {
+                            union_orient_hole(L.face, nf, lane); // add_hole
+                            for (int v = lane; v < nf; v += 64)
+                                H.holes[newVertices + v] = L.face[v];
+                            if (lane == 0)
+                                H.holeLen[nNew] = (unsigned short)nf;
+                            CAPE_MP_SYNC();
+                        }
+                        ++nNew;
+                        newVertices += nf;
+                    }
+                }
+            }
+        }
+    }
+    if (G.fail)
+        return hosted(G.fail);
+    // ---- 4. the outer ring: drop_collinear, the disjoint rule, ring_is_simple
+    if (nOuter > 0)
+        nOuter = union_drop_collinear(L.outer, nOuter, lane);
+    const double outerArea = nOuter >= 3 ? fabs(ring_area_signed(L.outer, nOuter)) : 0.0;
+    const double areaA = fabs(ring_area_signed(A, nA)), areaB = fabs(ring_area_signed(B, nB));
+    // an operand none of whose vertices lies inside or on the outer face is a piece of its own (MergeInfo::disjoint); the rule below
+    // catches that when the piece walked is the smaller one
+    bool disjoint = nOuter >= 3 && (union_left_out(A, nA, L.outer, nOuter, lane) || union_left_out(B, nB, L.outer, nOuter, lane));
+    double2* out = L.outer;
+    bool rule = false; // merge_union's own `disjoint`
+    if (outerArea + 1e-9 * umax(areaA, areaB) < umax(areaA, areaB))
+    {
+        disjoint = rule = true;
+        // area() >= o.area(), where area() counts the holes out: this polygon is the bigger piece, simplified as it is, holes and all
+        if (fetch.map_area(A, nA, L.face) >= areaB)
+        {
+            res.flags = CAPE_UNION_SERVED | CAPE_UNION_DISJOINT;
+            if (!fetch.all()) // (the faces stored there are no holes of this result)
+                return hosted(CAPE_UNION_HOST_CAPACITY);
+            holes.nHoles = H.nSrc;
+            res.flags |= H.nSrc > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u;
+            res.n = union_simplify_holed(L, H, L.ringA, nA, H.nSrc, L.face, res.area, lane);
+            res.ring = L.ringA;
+            return res;
+        }
+        for (int v = lane; v < nB; v += 64)
+            out[v] = B[v];
+        nOuter = nB;
+        CAPE_MP_SYNC();
+    }
+    if (nOuter < 3 || !union_ring_is_simple(out, nOuter, lane))
+    {
+        res.flags |= disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u; // merge_union returned false: the projected map polygon stays
+        if (!fetch.all()) // ... with its projected holes
+            return hosted(CAPE_UNION_HOST_CAPACITY);
+        holes.nHoles = H.nSrc;
+        res.flags |= H.nSrc > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u;
+        res.area = union_area_holed(A, nA, H.holes, H.holeLen, H.nSrc);
+        return res;
+    }
+    // ---- 5. Polygon(ring, x, y, c): a repeated closing vertex goes, the ring is oriented; then simplify()
+    if (nOuter > 1 && out[0].x == out[nOuter - 1].x && out[0].y == out[nOuter - 1].y)
+        --nOuter;
+    union_orient(out, nOuter, lane);
+    res.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u);
+    res.ring = out;
+    // ---- 6. the interior rings.  The detection is the bigger piece of two: none (it has none).  Otherwise the faces stored
+    // above, then the map plane's holes in their order (carry_hole): kept where the detection covers at most `tiny` of them,
+    // gone where it covers them, the host's where it covers a part.  Everything is counted, stored while it fits, and judged at
+    // the end: a partly covered hole first, then the capacities.
+    int nHoles = 0, holeVertices = 0;
+    bool cut = false;
+    if (!rule)
+    {
+        nHoles = nNew;
+        holeVertices = newVertices;
+        holes.holesNew = (uint32_t)nNew;
+        const double tiny = 1e-12 * umax(areaA, areaB);
+        for (int k = 0; k < H.nSrc; ++k)
+        {
+            const int nh = fetch.hole(k, L.ringA); // (ring A is dead: the outer ring stands in L.outer)
+            const double inter = union_boxes_apart(L.ringA, nh, B, nB) ? 0.0 : rings_inter_area<kUnionMpStack, kUnionMpXs>(H.mp, nh, nB, lane);
+            if (inter != inter) // one of its capacities
+                return hosted(CAPE_UNION_HOST_CAPACITY);
+            const double covered = inter < 0 ? 0.0 : inter;
+            if (covered <= tiny)
+            {
+                if (nHoles < kUnionHoles && holeVertices + nh <= kUnionHoleVertices)
+                {
+                    for (int v = lane; v < nh; v += 64)
+                        H.holes[holeVertices + v] = L.ringA[v];
+                    if (lane == 0)
+                        H.holeLen[nHoles] = (unsigned short)nh;
+                }
+                ++nHoles;
+                holeVertices += nh;
+                ++holes.holesKept;
+            }
+            else if (inter < fabs(ring_area_signed(L.ringA, nh)) - tiny)
+                cut = true;
+            else
+                ++holes.holesCovered;
+            CAPE_MP_SYNC();
+        }
+    }
+    if (cut)
+        return hosted(CAPE_UNION_HOST_HOLE_CUT);
+    if (nHoles > kUnionHoles || holeVertices > kUnionHoleVertices)
+        return hosted(CAPE_UNION_HOST_CAPACITY);
+    holes.nHoles = nHoles;
+    res.flags |= nHoles > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u;
+    res.n = union_simplify_holed(L, H, out, nOuter, nHoles, L.face, res.area, lane);
     return res;
 }
 

@@ -13,6 +13,10 @@
 //        of the slab is CAPE_UNION_HOST_CAPACITY.
 //   cape_ring_union_kernel : the same per-pair function on one pair given by its rings and frames (cape_debug_ring_union).
 //   A frame the wide match flagged CAPE_MATCH_EXACT_OVERFLOW reports nothing: its rows are zeros.
+//   cape_map_union_holes_kernel, cape_polygon_union_kernel : the same two for the holes mode (union_pair_holes: a map plane with
+//        interior rings, a union that encloses faces).  The same rows and slab, where a served polygon's rings lie back to back, plus
+//        a row of ring lengths per kept plane; a larger carve (union_holes_layout).  The kernels above stand as they were: the holes mode shares their
+//        per-lane functions and restates the rest beside them.
 //
 // Every count read from the map, a row or a table is checked against its buffer before it indexes anything; every loop of union_pair
 // is bounded by a capacity of the carve.
@@ -182,6 +186,237 @@ __global__ __launch_bounds__(64) void cape_ring_union_kernel(RingUnionParams p)
         res = union_pair(L, p.nA, p.nB, fa, fb, target, frameOut, lane);
     }
     (void)put_pair(res, frameOut, 0, p.row, p.vertices, 0u, CAPE_MAP_MAX_RING, lane);
+}
+
+namespace {
+
+// pass 1 of cape_map_union_kernel for the holes kernel, lanes over the kept planes (i and i + 64): which kept planes have a pair; the rows of the others are
+// written here
+__device__ __forceinline__ void union_find_pairs(const MapUnionParams& p, int frame, int nCur, cape_plane_union* rows, const cape_plane_fusion* fusion,
+                                                 int lane, unsigned long long (&pairs)[2])
+{
+    const int nMap = p.nMap;
+#pragma unroll 1
+    for (int s = 0; s < 2; ++s)
+    {
+        const int i = lane + 64 * s;
+        bool pair = false;
+        if (i < nCur)
+        {
+            const int j = fusion[i].map_plane;
+            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
+            if (j >= 0 && j < nMap && (fusion[i].flags & CAPE_FUSION_FRAME) && at.x < (unsigned)p.nRecords && at.y < (unsigned)CAPE_MAX_PLANES)
+            {
+                const uint32_t mflags = p.measurements[(size_t)at.x * CAPE_MAX_PLANES + at.y].flags;
+                pair = (mflags & CAPE_MEASURE_KEPT) && !(mflags & CAPE_MEASURE_FAIL_POLYGON) && p.match[(size_t)frame * nMap + j] == i;
+            }
+        }
+        if (!pair)
+        {
+            cape_plane_union row{};
+            row.map_plane = i < nCur ? -1 : 0;
+            rows[i] = row;
+        }
+        pairs[s] = __ballot(pair);
+    }
+}
+
+// the rows of a pair of the holes mode: the outer ring and the interior rings go to slab[used, ...) back to back if the whole polygon
+// fits `capacity`.  Returns the new `used`.
+__device__ __forceinline__ unsigned put_pair_holes(const UnionResult& res, const UnionHoleResult& hr, const UnionHolesLds& H, const UnionFrame& frame, int mapPlane,
+                                                   cape_plane_union* row, cape_plane_union_rings* ringRow, double2* slab, unsigned used,
+                                                   unsigned capacity, int lane)
+{
+    cape_plane_union r{};
+    cape_plane_union_rings q{};
+    r.map_plane = mapPlane;
+    r.flags = res.flags;
+    const bool served = (res.flags & CAPE_UNION_SERVED) != 0;
+    const int nHoles = served && hr.nHoles > 0 && hr.nHoles <= kUnionHoles ? hr.nHoles : 0;
+    unsigned total = served && res.n >= 0 ? (unsigned)res.n : 0u;
+    for (int k = 0; k < nHoles; ++k)
+        total += (unsigned)uni(H.holeLen[k]);
+    const bool fits = served && res.n >= 0 && total <= capacity - used;
+    if (served && !fits)
+        r.flags = CAPE_UNION_HOST_CAPACITY;
+    if (fits)
+    {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            r.x_axis[k] = frame.x[k], r.y_axis[k] = frame.y[k], r.center[k] = frame.c[k];
+        r.area = res.area;
+        r.vertex_offset = used;
+        r.vertex_count = (uint32_t)res.n;
+        r.n_nodes = (uint32_t)res.nNodes;
+        q.ring_count = 1u + (uint32_t)nHoles;
+        q.vertex_count[0] = (uint32_t)res.n;
+        q.holes_new = hr.holesNew;
+        q.holes_kept = hr.holesKept;
+        q.holes_covered = hr.holesCovered;
+        for (int v = lane; v < res.n; v += 64)
+            slab[used + v] = res.ring[v];
+        const unsigned holesAt = used + (unsigned)res.n;
+#pragma unroll
+        for (int k = 0; k < kUnionHoles; ++k)
+            q.vertex_count[1 + k] = k < nHoles ? (uint32_t)uni(H.holeLen[k]) : 0u;
+        for (unsigned v = lane; v < total - (unsigned)res.n; v += 64)
+            slab[holesAt + v] = H.holes[v];
+        used += total;
+    }
+    if (lane == 0)
+    {
+        *row = r;
+        *ringRow = q;
+    }
+    return used;
+}
+
+} // namespace
+
+// The holes mode of the frame kernel: the walk above, with the map plane's interior rings described to union_pair_holes (every
+// count and offset checked here) and the rings rows written beside the rows.
+__global__ __launch_bounds__(64) void cape_map_union_holes_kernel(MapUnionParams p, cape_plane_union_rings* ringRowsAll, int nFrames)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const UnionLds L = union_carve(smem);
+    UnionHolesLds H = union_holes_carve(smem, L);
+    const int lane = threadIdx.x & 63;
+    const int frame = (int)blockIdx.x;
+    if (frame >= nFrames)
+        return;
+    const cape_frame_map_match_wide hd = p.matchFrames[frame];
+    const bool reports = !(hd.flags & CAPE_MATCH_EXACT_OVERFLOW);
+    const int nCur = !reports ? 0 : (hd.n_cur < 0 ? 0 : (hd.n_cur > kUnionPlanes ? kUnionPlanes : hd.n_cur));
+    cape_plane_union* rows = p.rows + (size_t)frame * kUnionPlanes;
+    cape_plane_union_rings* ringRows = ringRowsAll + (size_t)frame * kUnionPlanes;
+    const cape_plane_fusion* fusion = p.fusion + (size_t)frame * kUnionPlanes;
+    double2* slab = p.vertices + (size_t)frame * CAPE_MAP_UNION_FRAME_VERTICES;
+    // ---- pass 1: which kept planes have a pair (the rings rows of the others: zeros)
+    unsigned long long pairs[2];
+    union_find_pairs(p, frame, nCur, rows, fusion, lane, pairs);
+#pragma unroll 1
+    for (int s = 0; s < 2; ++s)
+        if (!((pairs[s] >> lane) & 1ull))
+            ringRows[lane + 64 * s] = cape_plane_union_rings{};
+    H.src = p.mapVertices;
+    // ---- pass 2: the pairs in kept-plane order
+    unsigned used = 0;
+#pragma unroll 1
+    for (int s = 0; s < 2; ++s)
+    {
+        unsigned long long todo = pairs[s];
+        while (todo)
+        {
+            const int i = 64 * s + __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int j = uni(fusion[i].map_plane);
+            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
+            const int rec = uni((int)at.x);
+            const cape_plane_measurement& m = p.measurements[(size_t)rec * CAPE_MAX_PLANES + uni((int)at.y)];
+            const cape_map_plane& M = p.mapPlanes[j];
+            UnionResult res{};
+            UnionHoleResult holes{};
+            UnionFrame frameOut{};
+            const unsigned ringFirst = (unsigned)uni((int)M.ring_first), ringCount = (unsigned)uni((int)M.ring_count);
+            const unsigned nB = (unsigned)uni((int)m.vertex_count), offB = (unsigned)uni((int)m.vertex_offset);
+            const unsigned cap = (unsigned)p.boundaryCapacity;
+            // every ring of the map plane: in its table, inside the vertex buffer, of 3 .. kUnionRing vertices
+            bool fits = ringCount >= 1u && ringCount <= 1u + (unsigned)kUnionHoles && ringFirst < p.nMapRings && ringCount <= p.nMapRings - ringFirst &&
+                        nB >= 3u && nB <= (unsigned)kUnionRing && offB <= cap && nB <= cap - offB;
+            for (unsigned k = 0; fits && k < ringCount; ++k)
+            {
+                const cape_map_ring R = p.mapRings[ringFirst + k];
+                const unsigned n = (unsigned)uni((int)R.vertex_count), off = (unsigned)uni((int)R.vertex_offset);
+                fits = n >= 3u && n <= (unsigned)kUnionRing && (unsigned long long)off + n <= p.nMapVertices;
+                if (fits && k > 0u && lane == 0)
+                {
+                    H.srcOff[k - 1u] = off;
+                    H.srcLen[k - 1u] = (unsigned short)n;
+                }
+            }
+            CAPE_MP_SYNC();
+            if (!fits)
+                res.flags = CAPE_UNION_HOST_CAPACITY;
+            else
+            {
+                const cape_map_ring R = p.mapRings[ringFirst];
+                const unsigned nA = (unsigned)uni((int)R.vertex_count), offA = (unsigned)uni((int)R.vertex_offset);
+                const double2* srcA = p.mapVertices + offA;
+                const double2* srcB = p.worldVertices + (size_t)rec * cap + offB;
+                for (unsigned v = lane; v < nA; v += 64)
+                    L.ringA[v] = srcA[v];
+                for (unsigned v = lane; v < nB; v += 64)
+                    L.ringB[v] = srcB[v];
+                CAPE_MP_SYNC();
+                H.nSrc = (int)ringCount - 1;
+                UnionFrame fa, fb, target;
+                load_frame(fa, M.x_axis, M.y_axis, M.center);
+                load_frame(fb, m.x_axis, m.y_axis, m.center);
+                load_frame(target, fusion[i].x_axis, fusion[i].y_axis, fusion[i].center);
+                res = union_pair_holes(L, H, (int)nA, (int)nB, fa, fb, target, frameOut, holes, lane);
+            }
+            used = put_pair_holes(res, holes, H, frameOut, j, rows + i, ringRows + i, slab, used, CAPE_MAP_UNION_FRAME_VERTICES, lane);
+            CAPE_MP_SYNC(); // (the next pair rewrites the carve)
+        }
+    }
+}
+
+// The same per-pair function on one pair given by ring a's rings (back to back, counts[nRingsA]), ring b and the frames
+// (cape_debug_polygon_union).  1 <= nRingsA <= 1 + kUnionHoles: the entry point has checked it.
+__global__ __launch_bounds__(64) void cape_polygon_union_kernel(PolygonUnionParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const UnionLds L = union_carve(smem);
+    UnionHolesLds H = union_holes_carve(smem, L);
+    const int lane = threadIdx.x & 63;
+    UnionResult res{};
+    UnionHoleResult holes{};
+    UnionFrame frameOut{};
+    bool fits = p.nRingsA >= 1 && p.nRingsA <= 1 + kUnionHoles && p.nB >= 3 && p.nB <= kUnionRing;
+    unsigned at = 0;
+    for (int k = 0; fits && k < p.nRingsA; ++k)
+    {
+        const int n = uni(p.countsA[k]);
+        fits = n >= 3 && n <= kUnionRing;
+        if (fits && k > 0 && lane == 0)
+        {
+            H.srcOff[k - 1] = at;
+            H.srcLen[k - 1] = (unsigned short)n;
+        }
+        at += fits ? (unsigned)n : 0u;
+    }
+    CAPE_MP_SYNC();
+    if (!fits)
+        res.flags = CAPE_UNION_HOST_CAPACITY;
+    else
+    {
+        const int nA = uni(p.countsA[0]);
+        for (int v = lane; v < nA; v += 64)
+            L.ringA[v] = p.ringsA[v];
+        for (int v = lane; v < p.nB; v += 64)
+            L.ringB[v] = p.ringB[v];
+        CAPE_MP_SYNC();
+        H.src = p.ringsA;
+        H.nSrc = p.nRingsA - 1;
+        UnionFrame fa, fb, target;
+        load_frame(fa, p.frames27, p.frames27 + 3, p.frames27 + 6);
+        load_frame(fb, p.frames27 + 9, p.frames27 + 12, p.frames27 + 15);
+        load_frame(target, p.frames27 + 18, p.frames27 + 21, p.frames27 + 24);
+        res = union_pair_holes(L, H, nA, p.nB, fa, fb, target, frameOut, holes, lane);
+    }
+    (void)put_pair_holes(res, holes, H, frameOut, 0, p.row, p.ringRow, p.vertices, 0u, CAPE_MAP_UNION_FRAME_VERTICES, lane);
+}
+
+hipError_t launch_map_union_holes(const MapUnionParams& p, cape_plane_union_rings* ringRows, int nFrames, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cape_map_union_holes_kernel, dim3(nFrames), dim3(64), union_holes_layout().bytes, stream, p, ringRows, nFrames);
+    return hipGetLastError();
+}
+
+hipError_t launch_polygon_union(const PolygonUnionParams& p, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cape_polygon_union_kernel, dim3(1), dim3(64), union_holes_layout().bytes, stream, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t stream)

@@ -1121,6 +1121,9 @@ bool Polygon::merge_union(const Polygon& other, MergeInfo* info)
         {
             // this polygon is the biggest piece of the multi-polygon: union_one returns it as is, and merge_union
             // still simplifies what it assigned (polygon.cpp:325-336)
+            if (info)
+                for (const auto& h : _inners)
+                    info->holeVertices += h.size();
             simplify();
             return true;
         }
@@ -1140,7 +1143,11 @@ bool Polygon::merge_union(const Polygon& other, MergeInfo* info)
         {
             drop_collinear(h);
             if (h.size() >= 3 && ring_is_simple(h))
+            {
                 merged.add_hole(h);
+                if (info)
+                    ++info->holesNew;
+            }
         }
         // A hole an operand already had (boost::geometry::union_ of polygons with interior rings, polygon.cpp:463-470): what the
         // other operand leaves uncovered of it stays a hole -- the whole of it if the other stays clear, nothing if the other
@@ -1155,10 +1162,18 @@ bool Polygon::merge_union(const Polygon& other, MergeInfo* info)
             if (covered <= tiny)
             {
                 merged.add_hole(h);
+                if (info)
+                    ++info->holesKept;
                 return;
             }
             std::vector<std::vector<vector2>> pieces;
-            if (rings_inter_area(h, otherRing) < std::abs(ring_area_signed(h)) - tiny)
+            const bool cut = rings_inter_area(h, otherRing) < std::abs(ring_area_signed(h)) - tiny;
+            if (info)
+            {
+                info->holeCut = info->holeCut || cut;
+                info->holesCovered += cut ? 0u : 1u;
+            }
+            if (cut)
                 (void)rings_union_outer(h, otherRing, &pieces, 1); // hole \ other
             for (const auto& oh : otherHoles)
                 if (withOverlaps && rings_inter_area(h, oh) > tiny)
@@ -1175,6 +1190,9 @@ bool Polygon::merge_union(const Polygon& other, MergeInfo* info)
         for (const auto& h : o._inners)
             carry_hole(h, _ring, _inners, false);
     }
+    if (info)
+        for (const auto& h : merged._inners)
+            info->holeVertices += h.size();
     *this = merged;
     simplify();
     return true;

@@ -97,9 +97,15 @@ class Polygon
     // the same, and the fact a caller cannot read off the result: the operands are two disjoint pieces, of which the bigger one was
     // kept -- by the disjoint rule (the outlines enclose less than the bigger operand), or because the outer face walked from the
     // leftmost node already is the bigger piece (no vertex of the other operand lies inside or on it).  `info` changes no result
+    // ... and what became of the interior rings (the twins of cape_map_union_holes report it): faces of the union added as holes,
+    // holes of this polygon kept as they were, holes the other polygon covers, whether one of them was only partly covered (its
+    // pieces were added), and the vertices of all interior rings before simplify() -- set on every path that returns true
     struct MergeInfo
     {
         bool disjoint = false;
+        unsigned holesNew = 0, holesKept = 0, holesCovered = 0;
+        bool holeCut = false;
+        size_t holeVertices = 0;
     };
     bool merge_union(const Polygon& other, MergeInfo* info);
     // polygon from an explicit ring in a given frame (polygon.cpp:236-266)

@@ -123,6 +123,23 @@ int cape_host_map_union(const cape_host_map* map, const int32_t* match, const ca
 int cape_host_ring_union(const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27, cape_plane_union* row_out,
                          double* vertices_out);
 
+/* The twins of cape_map_union_holes and cape_debug_polygon_union (include/cape_hip.h): the arguments of the two calls above plus the
+ * rings output (rings_out[128], zero beyond n_cur; one row for a pair), through the same polygon step, for a map plane with interior
+ * rings and / or a union that creates some.  rings_a: ring a's outer ring and its interior rings back to back, counts_a[n_rings_a]
+ * their lengths, n_rings_a in [1, 1 + CAPE_MAP_MAX_HOLES], every count and n_b in [3, 4096].  A served polygon's rings go to
+ * vertices_out back to back, the outer ring first (room for CAPE_MAP_UNION_FRAME_VERTICES pairs in both calls); row.area is
+ * Polygon::_area.  They never set HOST_MAP_HOLES or HOST_NEW_HOLE.  CAPE_UNION_HOST_HOLE_CUT where merge_union met a partly covered
+ * hole, before every capacity.  Of CAPE_UNION_HOST_CAPACITY they know the rules that follow from inputs and results: a map plane of
+ * more than 1 + CAPE_MAP_MAX_HOLES rings, a ring of the map plane or a detection of more than CAPE_MAP_UNION_MAX_RING vertices, more
+ * than CAPE_MAP_UNION_HOLE_VERTICES vertices in the interior rings before simplify(), the update's own overflow (CAPE_MAP_MAX_RING,
+ * CAPE_MAP_MAX_HOLES) and a polygon that does not fit the rest of the slab as a whole.  They never set HOST_AMBIGUOUS, and n_nodes
+ * stays 0.  CAPE_ERR_INVALID_ARGUMENT as above, and for a NULL rings_out. */
+int cape_host_map_union_holes(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion,
+                              const cape_plane_measurement* measurements, const double* world_vertices, int32_t n_cur, cape_plane_union* rows_out,
+                              cape_plane_union_rings* rings_out, double* vertices_out);
+int cape_host_polygon_union(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                            const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out);
+
 /* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
  * cape_gather_primitives[_root] or any other transport -- as the kept planes the two calls above take: no handle, no device.
  * `frame` counts from the shard's first frame.  Each plane goes through the host class's Polygon(ring, xAxis, yAxis, center)

@@ -4,7 +4,7 @@
 // cape_host_match_planes, cape_host_map_visibility, cape_host_map_update and cape_host_shard_frame are host twins a caller may use,
 // declared and described in cape_host_map.h: the first answers the frames cape_match_map flags, the second those the matchers of
 // consecutive frames flag, the third decides which map planes cape_match_map visits, the fourth is the map update (cape_host_map_kalman and cape_host_map_union are the
-// twins of its two device halves, cape_host_ring_union of the union's debug entry), the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
+// twins of its two device halves, cape_host_map_union_holes of the polygon half's holes mode, cape_host_ring_union and cape_host_polygon_union of the union's debug entries), the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -274,6 +274,62 @@ void put_union_row(cape_plane_union& row, const Polygon& poly, const PolygonStep
             ++used;
         }
     }
+}
+
+// A pair's rows of cape_map_union_holes from the step's outcome (every ring of the map plane within CAPE_MAP_UNION_MAX_RING, at most
+// CAPE_MAP_MAX_HOLES of them): a partly covered hole first, then the capacities the device has -- the interior rings before simplify,
+// polygon_step's overflow, the slab, which takes the whole polygon or nothing.
+void put_union_holes_rows(cape_plane_union& row, cape_plane_union_rings& rings, const Polygon& poly, const PolygonStep& step, uint32_t& used,
+                          uint32_t capacity, double* slab)
+{
+    size_t holeVertices = 0, total = poly.boundary().size();
+    for (const auto& h : poly.interior_rings())
+        holeVertices += h.size();
+    total += holeVertices;
+    if (step.merged)
+        holeVertices = step.info.holeVertices; // (before simplify)
+    if (step.info.holeCut)
+        row.flags = CAPE_UNION_HOST_HOLE_CUT;
+    else if (step.overflow || holeVertices > CAPE_MAP_UNION_HOLE_VERTICES || total > capacity - used)
+        row.flags = CAPE_UNION_HOST_CAPACITY;
+    else
+    {
+        const auto& holes = poly.interior_rings();
+        row.flags = CAPE_UNION_SERVED | (step.merged ? 0u : (uint32_t)CAPE_UNION_UNCHANGED) | (step.info.disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u) |
+                    (holes.empty() ? 0u : (uint32_t)CAPE_UNION_HOLES);
+        put3(row.x_axis, poly.get_x_axis());
+        put3(row.y_axis, poly.get_y_axis());
+        put3(row.center, poly.get_center());
+        row.area = poly.get_area();
+        row.vertex_offset = used;
+        row.vertex_count = (uint32_t)poly.boundary().size();
+        rings.ring_count = 1 + (uint32_t)holes.size();
+        rings.holes_new = step.info.holesNew;
+        rings.holes_kept = step.info.holesKept;
+        rings.holes_covered = step.info.holesCovered;
+        for (size_t k = 0; k <= holes.size(); ++k)
+        {
+            const std::vector<vector2>& ring = k == 0 ? poly.boundary() : holes[k - 1];
+            rings.vertex_count[k] = (uint32_t)ring.size();
+            for (const vector2& p : ring)
+            {
+                slab[2 * (size_t)used] = p[0];
+                slab[2 * (size_t)used + 1] = p[1];
+                ++used;
+            }
+        }
+    }
+}
+
+// what the device refuses before any geometry: a map plane of too many rings or with a ring it cannot hold, a detection too long
+bool union_holes_operands_fit(const cape_host_map& map, const cape_map_plane& M, uint32_t detectionCount)
+{
+    if (M.ring_count > 1 + CAPE_MAP_MAX_HOLES || detectionCount > CAPE_MAP_UNION_MAX_RING)
+        return false;
+    for (uint32_t k = 0; k < M.ring_count; ++k)
+        if (map.rings[M.ring_first + k].vertex_count > CAPE_MAP_UNION_MAX_RING)
+            return false;
+    return true;
 }
 
 } // namespace
@@ -812,11 +868,13 @@ extern "C" int cape_host_map_kalman(const cape_host_map* map, const int32_t* mat
     return 0;
 }
 
-// The twin of cape_map_union (cape_host_map.h): the polygon step above, per pair of one frame, through the host class itself.
-extern "C" int cape_host_map_union(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion,
-                                   const cape_plane_measurement* measurements, const double* world_vertices, int32_t n_cur,
-                                   cape_plane_union* rows_out, double* vertices_out)
+// The twins of cape_map_union and cape_map_union_holes (cape_host_map.h): the polygon step above, per pair of one frame, through the
+// host class itself.  rings_out NULL: the first one's rules, otherwise the second one's.
+namespace {
+int host_map_union(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion, const cape_plane_measurement* measurements,
+                   const double* world_vertices, int32_t n_cur, cape_plane_union* rows_out, cape_plane_union_rings* rings_out, double* vertices_out)
 {
+    const bool holesMode = rings_out != nullptr;
     if (!map || map->n_planes < 0 || n_cur < 0 || n_cur > CAPE_MATCH_MAP_WIDE_MAX_PLANES || !rows_out || !vertices_out ||
         (n_cur > 0 && (!fusion || !measurements || !world_vertices)) || (map->n_planes > 0 && (!map->planes || !map->rings || !map->vertices)))
         return CAPE_ERR_INVALID_ARGUMENT;
@@ -824,6 +882,7 @@ extern "C" int cape_host_map_union(const cape_host_map* map, const int32_t* matc
     try
     {
         std::vector<cape_plane_union> rows(CAPE_MATCH_MAP_WIDE_MAX_PLANES, cape_plane_union {});
+        std::vector<cape_plane_union_rings> ringRows(CAPE_MATCH_MAP_WIDE_MAX_PLANES, cape_plane_union_rings {});
         std::vector<double> slab;
         slab.resize(2 * (size_t)CAPE_MAP_UNION_FRAME_VERTICES);
         uint32_t used = 0;
@@ -844,12 +903,12 @@ extern "C" int cape_host_map_union(const cape_host_map* map, const int32_t* matc
             const cape_map_plane& M = map->planes[j];
             if (!map_polygon(*map, M, nullptr))
                 return CAPE_ERR_INVALID_ARGUMENT;
-            if (M.ring_count > 1)
+            if (!holesMode && M.ring_count > 1)
             {
                 row.flags = CAPE_UNION_HOST_MAP_HOLES;
                 continue;
             }
-            if (map->rings[M.ring_first].vertex_count > CAPE_MAP_UNION_MAX_RING || m.vertex_count > CAPE_MAP_UNION_MAX_RING)
+            if (!union_holes_operands_fit(*map, M, m.vertex_count))
             {
                 row.flags = CAPE_UNION_HOST_CAPACITY;
                 continue;
@@ -865,9 +924,14 @@ extern "C" int cape_host_map_union(const cape_host_map* map, const int32_t* matc
                 poly);
             if (!step.ok) // (the centre check after a projection: not reached, the projected polygon's centre IS the target)
                 continue;
-            put_union_row(row, poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, slab.data());
+            if (holesMode)
+                put_union_holes_rows(row, ringRows[i], poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, slab.data());
+            else
+                put_union_row(row, poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, slab.data());
         }
         std::copy(rows.begin(), rows.end(), rows_out);
+        if (holesMode)
+            std::copy(ringRows.begin(), ringRows.end(), rings_out);
         std::copy(slab.begin(), slab.begin() + 2 * (size_t)used, vertices_out);
         return 0;
     }
@@ -877,22 +941,32 @@ extern "C" int cape_host_map_union(const cape_host_map* map, const int32_t* matc
     }
 }
 
-// The twin of cape_debug_ring_union (cape_host_map.h): one pair given by its two rings and three frames.
-extern "C" int cape_host_ring_union(const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
-                                    cape_plane_union* row_out, double* vertices_out)
+// one pair given by its rings and frames: ring a with its interior rings (holesMode) against ring b
+int host_pair_union(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b, const double* frames27,
+                    cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
 {
     static const double kCanonical[27] = {1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0};
-    if (!ring_a || !ring_b || !row_out || !vertices_out || n_a < 3 || n_b < 3 || n_a > 4096 || n_b > 4096)
-        return CAPE_ERR_INVALID_ARGUMENT;
+    const bool holesMode = rings_out != nullptr;
     const double* F = frames27 ? frames27 : kCanonical;
     try
     {
         cape_plane_union row {};
-        if (n_a > CAPE_MAP_UNION_MAX_RING || n_b > CAPE_MAP_UNION_MAX_RING)
+        cape_plane_union_rings ringRow {};
+        bool fits = n_b <= CAPE_MAP_UNION_MAX_RING;
+        for (int32_t k = 0; k < n_rings_a; ++k)
+            fits = fits && counts_a[k] <= CAPE_MAP_UNION_MAX_RING;
+        if (!fits)
             row.flags = CAPE_UNION_HOST_CAPACITY;
         else
         {
-            const Polygon a(ring_from(ring_a, n_a), {}, vec3(F), vec3(F + 3), vec3(F + 6));
+            std::vector<std::vector<vector2>> holes;
+            size_t at = (size_t)counts_a[0];
+            for (int32_t k = 1; k < n_rings_a; ++k)
+            {
+                holes.push_back(ring_from(rings_a + 2 * at, (size_t)counts_a[k]));
+                at += (size_t)counts_a[k];
+            }
+            const Polygon a(ring_from(rings_a, (size_t)counts_a[0]), holes, vec3(F), vec3(F + 3), vec3(F + 6));
             const Polygon b(ring_from(ring_b, n_b), {}, vec3(F + 9), vec3(F + 12), vec3(F + 15));
             Polygon poly;
             const PolygonStep step = polygon_step(
@@ -903,16 +977,58 @@ extern "C" int cape_host_ring_union(const double* ring_a, int32_t n_a, const dou
                 },
                 poly);
             uint32_t used = 0;
-            if (step.ok)
+            if (step.ok && holesMode)
+                put_union_holes_rows(row, ringRow, poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, vertices_out);
+            else if (step.ok)
                 put_union_row(row, poly, step, used, CAPE_MAP_MAX_RING, vertices_out);
         }
         *row_out = row;
+        if (holesMode)
+            *rings_out = ringRow;
         return 0;
     }
     catch (const std::exception&)
     {
         return CAPE_ERR_INVALID_ARGUMENT;
     }
+}
+} // namespace
+
+extern "C" int cape_host_map_union(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion,
+                                   const cape_plane_measurement* measurements, const double* world_vertices, int32_t n_cur,
+                                   cape_plane_union* rows_out, double* vertices_out)
+{
+    return host_map_union(map, match, fusion, measurements, world_vertices, n_cur, rows_out, nullptr, vertices_out);
+}
+
+extern "C" int cape_host_map_union_holes(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion,
+                                         const cape_plane_measurement* measurements, const double* world_vertices, int32_t n_cur,
+                                         cape_plane_union* rows_out, cape_plane_union_rings* rings_out, double* vertices_out)
+{
+    if (!rings_out)
+        return CAPE_ERR_INVALID_ARGUMENT;
+    return host_map_union(map, match, fusion, measurements, world_vertices, n_cur, rows_out, rings_out, vertices_out);
+}
+
+// The twins of cape_debug_ring_union and cape_debug_polygon_union (cape_host_map.h): one pair given by its rings and three frames.
+extern "C" int cape_host_ring_union(const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
+                                    cape_plane_union* row_out, double* vertices_out)
+{
+    if (!ring_a || !ring_b || !row_out || !vertices_out || n_a < 3 || n_b < 3 || n_a > 4096 || n_b > 4096)
+        return CAPE_ERR_INVALID_ARGUMENT;
+    return host_pair_union(ring_a, &n_a, 1, ring_b, n_b, frames27, row_out, nullptr, vertices_out);
+}
+
+extern "C" int cape_host_polygon_union(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                                       const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
+{
+    if (!rings_a || !counts_a || !ring_b || !row_out || !rings_out || !vertices_out || n_rings_a < 1 || n_rings_a > 1 + CAPE_MAP_MAX_HOLES || n_b < 3 ||
+        n_b > 4096)
+        return CAPE_ERR_INVALID_ARGUMENT;
+    for (int32_t k = 0; k < n_rings_a; ++k)
+        if (counts_a[k] < 3 || counts_a[k] > 4096)
+            return CAPE_ERR_INVALID_ARGUMENT;
+    return host_pair_union(rings_a, counts_a, n_rings_a, ring_b, n_b, frames27, row_out, rings_out, vertices_out);
 }
 
 // Test hooks of the covariance and Kalman algebra (tests/test_map_update_host.py restates them in numpy).  Each returns 1 on

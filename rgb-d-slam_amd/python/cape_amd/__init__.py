@@ -242,6 +242,13 @@ MAP_UNION_MAX_RING, MAP_UNION_MAX_NODES, MAP_UNION_FRAME_VERTICES = 128, 512, 20
 (UNION_SERVED, UNION_UNCHANGED, UNION_DISJOINT, UNION_HOST_MAP_HOLES, UNION_HOST_NEW_HOLE, UNION_HOST_CAPACITY,
  UNION_HOST_AMBIGUOUS) = (1 << k for k in range(7))
 UNION_HOST = UNION_HOST_MAP_HOLES | UNION_HOST_NEW_HOLE | UNION_HOST_CAPACITY | UNION_HOST_AMBIGUOUS
+# cape_map_union_holes: the same rows and slab plus a row of ring lengths per kept plane (cape_plane_union_rings)
+UNION_HOLES, UNION_HOST_HOLE_CUT = 1 << 7, 1 << 8
+MAP_UNION_HOLE_VERTICES = 512
+PLANE_UNION_RINGS_DTYPE = np.dtype([
+    ("ring_count", "<u4"), ("vertex_count", "<u4", 1 + MAP_MAX_HOLES), ("holes_new", "<u4"), ("holes_kept", "<u4"), ("holes_covered", "<u4"),
+    ("pad", "<u4")], align=True)
+assert PLANE_UNION_RINGS_DTYPE.itemsize == 56
 
 
 class cape_host_map(C.Structure):
@@ -281,6 +288,9 @@ def _host_library():
         L.cape_host_map_kalman.argtypes = [Map, i32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cape_host_map_union.argtypes = [Map, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.cape_host_ring_union.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_host_map_union_holes.argtypes = [Map, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_host_polygon_union.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
         L.cape_host_plane_to_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
@@ -421,14 +431,20 @@ def _union_rings(rows, slab):
     return [slab[r["vertex_offset"]: r["vertex_offset"] + r["vertex_count"]].copy() if r["flags"] & UNION_SERVED else None for r in rows]
 
 
-def host_map_union(map_arrays, match, fusion_rows, measurements, world_rings):
-    """cape_host_map_union of libcape_primitives.so: the twin of Extractor.map_union for ONE frame -- the polygon step of
-    host_map_update (Polygon::project, merge_union, simplify on the host class) for every pair the fusion rows report.
+def _union_polygons(rows, ring_rows, slab):
+    """the rings [outer, hole, ...] of every served row of a frame of map_union_holes, None for the others"""
+    out = []
+    for r, q in zip(rows, ring_rows):
+        if not r["flags"] & UNION_SERVED:
+            out.append(None)
+            continue
+        ends = int(r["vertex_offset"]) + np.concatenate([[0], np.cumsum(q["vertex_count"][: int(q["ring_count"])], dtype=np.int64)])
+        out.append([slab[a:b].copy() for a, b in zip(ends[:-1], ends[1:])])
+    return out
 
-    map_arrays: pack_map(...); match: n_map kept-plane indices or -1 (None: not checked); fusion_rows: PLANE_FUSION_DTYPE[n_cur]
-    (host_map_kalman's or the device's); measurements: PLANE_MEASUREMENT_DTYPE[n_cur] in kept-plane order; world_rings: the n_cur
-    world rings, (k, 2) arrays in kept-plane order (ring i must have measurements[i]["vertex_count"] vertices).
-    Returns (rows: PLANE_UNION_DTYPE[n_cur], rings: per kept plane the served ring or None)."""
+
+def _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, holes):
+    """host_map_union (holes=False) and host_map_union_holes (holes=True): the arguments packed once, the twin called"""
     L = _host_library()
     src, src_view = _map_arrays(map_arrays)
     F = np.ascontiguousarray(fusion_rows, PLANE_FUSION_DTYPE).reshape(-1)
@@ -447,11 +463,56 @@ def host_map_union(map_arrays, match, fusion_rows, measurements, world_rings):
             raise CapeError("host_map_union: one match per map plane")
     rows = np.zeros(MATCH_MAP_WIDE_MAX_PLANES, PLANE_UNION_DTYPE)
     slab = np.zeros((MAP_UNION_FRAME_VERTICES, 2))
+    if holes:
+        ring_rows = np.zeros(MATCH_MAP_WIDE_MAX_PLANES, PLANE_UNION_RINGS_DTYPE)
+        rc = L.cape_host_map_union_holes(C.byref(src_view), _as(M, C.c_int32), F.ctypes.data, Mr.ctypes.data, W.ctypes.data, n_cur,
+                                         rows.ctypes.data, ring_rows.ctypes.data, slab.ctypes.data)
+        if rc != 0:
+            raise CapeError(f"cape_host_map_union_holes failed ({rc})")
+        return rows[:n_cur], ring_rows[:n_cur], _union_polygons(rows[:n_cur], ring_rows[:n_cur], slab)
     rc = L.cape_host_map_union(C.byref(src_view), _as(M, C.c_int32), F.ctypes.data, Mr.ctypes.data, W.ctypes.data, n_cur, rows.ctypes.data,
                                slab.ctypes.data)
     if rc != 0:
         raise CapeError(f"cape_host_map_union failed ({rc})")
     return rows[:n_cur], _union_rings(rows[:n_cur], slab)
+
+
+def host_map_union(map_arrays, match, fusion_rows, measurements, world_rings):
+    """cape_host_map_union of libcape_primitives.so: the twin of Extractor.map_union for ONE frame -- the polygon step of
+    host_map_update (Polygon::project, merge_union, simplify on the host class) for every pair the fusion rows report.
+
+    map_arrays: pack_map(...); match: n_map kept-plane indices or -1 (None: not checked); fusion_rows: PLANE_FUSION_DTYPE[n_cur]
+    (host_map_kalman's or the device's); measurements: PLANE_MEASUREMENT_DTYPE[n_cur] in kept-plane order; world_rings: the n_cur
+    world rings, (k, 2) arrays in kept-plane order (ring i must have measurements[i]["vertex_count"] vertices).
+    Returns (rows: PLANE_UNION_DTYPE[n_cur], rings: per kept plane the served ring or None)."""
+    return _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, False)
+
+
+def host_map_union_holes(map_arrays, match, fusion_rows, measurements, world_rings):
+    """cape_host_map_union_holes: the twin of Extractor.map_union_holes for ONE frame, the arguments of host_map_union.  Returns
+    (rows: PLANE_UNION_DTYPE[n_cur], ring_rows: PLANE_UNION_RINGS_DTYPE[n_cur], polygons: per kept plane None or [outer, hole, ...])."""
+    return _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, True)
+
+
+def _polygon_union_args(rings_a, ring_b, frames):
+    rings = [np.ascontiguousarray(r, np.float64).reshape(-1, 2) for r in rings_a]
+    a = np.ascontiguousarray(np.concatenate(rings))
+    counts = np.array([len(r) for r in rings], np.int32)
+    b = np.ascontiguousarray(ring_b, np.float64).reshape(-1, 2)
+    F = None if frames is None else np.ascontiguousarray(frames, np.float64).reshape(27)
+    return a, counts, b, F, np.zeros(1, PLANE_UNION_DTYPE), np.zeros(1, PLANE_UNION_RINGS_DTYPE), np.zeros((MAP_UNION_FRAME_VERTICES, 2))
+
+
+def host_polygon_union(rings_a, ring_b, frames=None):
+    """cape_host_polygon_union: the twin of Extractor.debug_polygon_union -- rings_a = [outer, hole, ...] of the map plane, ring_b the
+    detection's ring, frames as in host_ring_union.  Returns (row, ring_row, polygon: None or [outer, hole, ...])."""
+    L = _host_library()
+    a, counts, b, F, row, rrow, ver = _polygon_union_args(rings_a, ring_b, frames)
+    rc = L.cape_host_polygon_union(a.ctypes.data, counts.ctypes.data, len(counts), b.ctypes.data, len(b), None if F is None else F.ctypes.data,
+                                   row.ctypes.data, rrow.ctypes.data, ver.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_polygon_union failed ({rc})")
+    return row[0], rrow[0], _union_polygons(row, rrow, ver)[0]
 
 
 def _ring_union_args(ring_a, ring_b, frames):
@@ -621,6 +682,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_measure", "cape_device_map_measurements", "cape_copy_map_measurements", "cape_copy_spill_measurements",
     "cape_map_upload_tracks", "cape_map_kalman", "cape_copy_map_kalman", "cape_device_map_kalman",
     "cape_map_union", "cape_copy_map_union", "cape_device_map_union", "cape_debug_ring_union",
+    "cape_map_union_holes", "cape_copy_map_union_rings", "cape_device_map_union_rings", "cape_debug_polygon_union",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
@@ -720,6 +782,10 @@ def load_library():
     L.cape_copy_map_union.argtypes = [vp, C.c_int32, vp, vp]
     L.cape_device_map_union.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_debug_ring_union.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    L.cape_map_union_holes.argtypes = [vp, C.c_int32, vp]
+    L.cape_copy_map_union_rings.argtypes = [vp, C.c_int32, vp]
+    L.cape_device_map_union_rings.argtypes = [vp, C.POINTER(vp)]
+    L.cape_debug_polygon_union.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1174,6 +1240,35 @@ class Extractor:
         """Per frame of the last map_union: (rows: PLANE_UNION_DTYPE[128], rings: per row the served ring (count, 2) or None)."""
         rows, ver = self.map_union_rows(n_frames)
         return [(rows[f].copy(), _union_rings(rows[f], ver[f])) for f in range(n_frames)]
+
+    def map_union_holes(self, n_frames, stream=0):
+        """cape_map_union_holes: map_union for map planes that have interior rings and unions that create some.  It writes the rows
+        and slabs map_union_rows returns -- a served polygon's rings back to back -- and the table of map_union_ring_rows; a pair
+        whose hole the detection covers in part is UNION_HOST_HOLE_CUT.  The results are map_union_polygons'."""
+        _check(self.L, self.L.cape_map_union_holes(self.h, n_frames, C.c_void_p(stream)), "cape_map_union_holes")
+
+    def map_union_ring_rows(self, n_frames):
+        """PLANE_UNION_RINGS_DTYPE[n_frames, 128] of the last map_union_holes (CapeError once a map_union has replaced its rows)"""
+        rings = np.zeros((n_frames, MATCH_MAP_WIDE_MAX_PLANES), PLANE_UNION_RINGS_DTYPE)
+        _check(self.L, self.L.cape_copy_map_union_rings(self.h, n_frames, rings.ctypes.data_as(C.c_void_p)), "cape_copy_map_union_rings")
+        return rings
+
+    def map_union_polygons(self, n_frames):
+        """Per frame of the last map_union_holes: (rows: PLANE_UNION_DTYPE[128], ring_rows: PLANE_UNION_RINGS_DTYPE[128], polygons: per
+        row None or [outer, hole, ...])."""
+        rows, ver = self.map_union_rows(n_frames)
+        rings = self.map_union_ring_rows(n_frames)
+        return [(rows[f].copy(), rings[f].copy(), _union_polygons(rows[f], rings[f], ver[f])) for f in range(n_frames)]
+
+    def debug_polygon_union(self, rings_a, ring_b, frames=None):
+        """cape_debug_polygon_union: map_union_holes' per-pair device function on one pair -- rings_a = [outer, hole, ...] of the map
+        plane, ring_b the detection's ring (see host_polygon_union, its twin).  Returns (row, ring_row, polygon: None or [outer, hole, ...])."""
+        a, counts, b, F, row, rrow, ver = _polygon_union_args(rings_a, ring_b, frames)
+        _check(self.L, self.L.cape_debug_polygon_union(self.h, a.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), len(counts),
+                                                       b.ctypes.data_as(C.c_void_p), len(b), None if F is None else F.ctypes.data_as(C.c_void_p),
+                                                       row.ctypes.data_as(C.c_void_p), rrow.ctypes.data_as(C.c_void_p),
+                                                       ver.ctypes.data_as(C.c_void_p)), "cape_debug_polygon_union")
+        return row[0], rrow[0], _union_polygons(row, rrow, ver)[0]
 
     def debug_ring_union(self, ring_a, ring_b, frames=None):
         """cape_debug_ring_union: map_union's per-pair device function on one pair given by its rings and frames (see
