@@ -1182,6 +1182,11 @@ int cape_debug_polygon_queue(cape_handle h, uint32_t* reserved, uint32_t* ticket
  * intersection kernel was handed, [8 + 4 * tier + reason] pairs that left tier `tier` for a larger one because of reason 1 = ring
  * vertices, 2 = slab boundaries, 3 = edges over one slab */
 int cape_debug_match_lists(cape_handle h, uint32_t* words32);
+/* the same for the last map-matcher call -- cape_match_map, cape_match_map_wide or cape_match_map_shards, whichever came last
+ * (tests; synchronises): 8 words -- [0..1] the (frame, map plane, detected plane) triples the gate kernel reserved (64-bit), [2..4]
+ * the pairs handed to capacity tiers 1, 2 and 3 of the intersection kernel, [5..7] the tickets the waves of those tiers drew.  All
+ * zero before the first such call. */
+int cape_debug_map_match_lists(cape_handle h, uint32_t* words8);
 /* cape_map_union's per-pair device function on a one-pair launch (tests; synchronous; the results of the last cape_map_union are not
  * disturbed): how disjoint operands, containment, T-junctions and capacity overflows -- pairs the matcher would never make -- reach
  * the kernel.  All pointers are HOST pointers.  ring_a plays the map plane's outer ring (n_a vertices, (x, y) pairs), ring_b the

@@ -179,6 +179,23 @@ int cape_debug_match_lists(cape_handle h, uint32_t* words32)
     return CAPE_OK;
 }
 
+int cape_debug_map_match_lists(cape_handle h, uint32_t* words8)
+{
+    if (!h || !words8)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad argument");
+    std::memset(words8, 0, 8 * sizeof(uint32_t));
+    const unsigned char* work = h->lastMapMatcher == cape_handle_s::kMapMatchRecords ? h->map.work.get()
+                                : h->lastMapMatcher == cape_handle_s::kMapMatchWide  ? h->mapWide.work.get()
+                                : h->lastMapMatcher == cape_handle_s::kMapMatchShards ? h->shardMatch.work.get()
+                                                                                      : nullptr;
+    if (!work)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(hipDeviceSynchronize());
+    CAPE_HIP_TRY(hipMemcpy(words8, work, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost)); // (the counters start the buffer: map_work_layout)
+    return CAPE_OK;
+}
+
 int cape_debug_ring_union(cape_handle h, const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
                           cape_plane_union* row_out, double* vertices_out)
 {

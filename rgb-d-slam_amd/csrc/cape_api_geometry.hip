@@ -711,6 +711,7 @@ int cape_match_map(cape_handle h, int32_t n_frames, const double* world_to_camer
     set_match_thresholds(p, flags);
     CAPE_HIP_TRY(cape::launch_match_map(p, n_frames, stream));
     map.matchFrames = n_frames;
+    h->lastMapMatcher = cape_handle_s::kMapMatchRecords;
     map.matchN = map.n;
     map.matchAreas = keepAreas;
     return CAPE_OK;
@@ -806,6 +807,7 @@ int cape_match_map_wide(cape_handle h, int32_t n_frames, const double* world_to_
     set_match_thresholds(p, flags);
     CAPE_HIP_TRY(cape::launch_match_map_wide(p, n_frames, stream));
     W.matchFrames = n_frames;
+    h->lastMapMatcher = cape_handle_s::kMapMatchWide;
     W.matchN = map.n;
     W.matchAreas = keepAreas;
     h->kalman.matchedThisMap = true;
@@ -928,6 +930,7 @@ int cape_match_map_shards(cape_handle h, const void* shards_dev, int32_t n_shard
     set_match_thresholds(p, flags);
     CAPE_HIP_TRY(cape::launch_match_map(p, nSlots, stream));
     S.slots = nSlots;
+    h->lastMapMatcher = cape_handle_s::kMapMatchShards;
     S.matchN = nMap;
     S.matchAreas = keepAreas;
     return CAPE_OK;

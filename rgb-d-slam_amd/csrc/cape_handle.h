@@ -416,6 +416,10 @@ struct cape_handle_s
         bool matchAreas = false;             // ... and whether it kept the dense table
     } shardMatch;
 
+    // cape_debug_map_match_lists: whose work buffer holds the counters of the last map-matcher call (they start the buffer:
+    // map_work_layout) -- none yet, cape_match_map's, cape_match_map_wide's or cape_match_map_shards'
+    enum LastMapMatcher { kNoMapMatch, kMapMatchRecords, kMapMatchWide, kMapMatchShards } lastMapMatcher = kNoMapMatch;
+
     // cape_map_visibility: the skip words of the uploaded map seen from the poses of the last call, for cape_match_map[_shards] with
     // CAPE_MATCH_MAP_DEVICE_SKIP.  Buffers of its own, sized by the call's frames (or slots) and grown on demand behind drain_handle:
     // no other call writes them

@@ -59,6 +59,12 @@ template <> struct Tier<3> // outlines of more than 128 vertices: the 64 x 48 ce
     static constexpr int kRing = 512, kXs = 2048, kStack = 32, kWavesPerGroup = kCoop ? 4 : 1, kGroupsPerCu = 1;
 };
 constexpr int kTiers = 4;
+// The boundary array of a tier: rings_inter_area writes the na + nb <= 2 * kRing vertex abscissae before it checks any capacity, and
+// sort_xs pads the boundaries to a power of two -- a kXs below 2 * kRing, or one that is no power of two (-DCAPE_MP_T0_XS=192),
+// would overrun the array without a word.
+template <int TIER> constexpr bool tier_xs_holds_its_rings() { return (Tier<TIER>::kXs & (Tier<TIER>::kXs - 1)) == 0 && Tier<TIER>::kXs >= 64 && Tier<TIER>::kXs >= 2 * Tier<TIER>::kRing; }
+static_assert(tier_xs_holds_its_rings<0>() && tier_xs_holds_its_rings<1>() && tier_xs_holds_its_rings<2>() && tier_xs_holds_its_rings<3>(),
+              "every tier's kXs must be a power of two (sort_xs pads to one, from 64 up) and at least 2 * kRing (the vertex abscissae are written before any capacity check)");
 // the largest capacity any LATER tier offers (a pair beyond a tier's capacity moves on while one of them can hold it)
 template <int TIER> constexpr int later_ring() { return TIER + 1 < kTiers ? (Tier<(TIER + 1 < kTiers ? TIER + 1 : TIER)>::kRing > later_ring<TIER + 1>() ? Tier<(TIER + 1 < kTiers ? TIER + 1 : TIER)>::kRing : later_ring<TIER + 1>()) : 0; }
 template <> constexpr int later_ring<kTiers>() { return 0; }

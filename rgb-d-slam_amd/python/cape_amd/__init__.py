@@ -685,7 +685,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_union_holes", "cape_copy_map_union_rings", "cape_device_map_union_rings", "cape_debug_polygon_union",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
-    "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_set_rng_seed",
+    "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
     "cape_comm_info", "cape_abi_version", "cape_spill_info", "cape_copy_spill", "cape_copy_spill_polygons", "cape_get_timings_sized",
 ]
 DEBUG_OPS = dict(sqrt=0, div=1, acos=2, atan2=3, quant=4, sqrtf=5, eigen3=6, fit_plane=7, cov_valid=8, plane_cov=9, world_plane_cov=10,
@@ -792,6 +792,7 @@ def load_library():
     L.cape_debug_polygon.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp]
     L.cape_debug_eval.argtypes = [C.c_int, vp, vp, vp, C.c_int]
     L.cape_debug_cycles.argtypes = [vp, C.c_int32, vp]
+    L.cape_debug_map_match_lists.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.cape_copy_seed_sequence.argtypes = [vp, C.c_int32, vp, C.c_int32, C.POINTER(C.c_int32)]
     L.cape_last_error.restype = C.c_char_p
     L.cape_version.restype = C.c_char_p
@@ -1416,6 +1417,13 @@ class Extractor:
         w = (C.c_uint32 * 32)()
         _check(self.L, self.L.cape_debug_match_lists(self.h, w), "cape_debug_match_lists")
         return list(w[:4]), {(t, r): int(w[8 + 4 * t + r]) for t in range(4) for r in (1, 2, 3) if w[8 + 4 * t + r]}
+
+    def map_match_lists(self):
+        """cape_debug_map_match_lists: the counters of the last match_map / match_map_wide / match_map_shards as a dict -- `reserved`
+        triples, `tiers`: the pairs handed to tiers 1, 2 and 3, `tickets`: the tickets their waves drew"""
+        w = (C.c_uint32 * 8)()
+        _check(self.L, self.L.cape_debug_map_match_lists(self.h, w), "cape_debug_map_match_lists")
+        return dict(reserved=int(w[0]) | (int(w[1]) << 32), tiers=[int(v) for v in w[2:5]], tickets=[int(v) for v in w[5:8]])
 
     def polygon_queue(self):
         """(slots reserved, tickets taken, slots usable) of the task queue of the last build_polygons (tests)."""
