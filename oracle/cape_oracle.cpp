@@ -829,8 +829,9 @@ static size_t run_ransac_loop(unsigned maximumIterations, const std::vector<unsi
                               const std::vector<double>& N, // 3 x n, column-major
                               const std::vector<double>& C, // projected centroids 3 x n
                               const std::vector<uint8_t>& idsLeftMask, std::vector<uint8_t>& isInlierFinal,
-                              unsigned cellActivatedCount, Rng& rng)
+                              unsigned cellActivatedCount, Rng& rng, CylLoopTrace& trace)
 {
+    trace.m = static_cast<uint32_t>(idsLeft.size());
     if (idsLeft.size() < 3)
         return 0;
 
@@ -843,6 +844,7 @@ static size_t run_ransac_loop(unsigned maximumIterations, const std::vector<unsi
 
     for (unsigned iteration = 0; iteration < maximumIterations; ++iteration)
     {
+        trace.iterations = iteration + 1;
         const unsigned id1 = idsLeft[rng.next_uint(planeIdsLeft)];
         const unsigned id2 = idsLeft[rng.next_uint(planeIdsLeft)];
         const unsigned id3 = idsLeft[rng.next_uint(planeIdsLeft)];
@@ -896,22 +898,29 @@ static size_t run_ransac_loop(unsigned maximumIterations, const std::vector<unsi
         {
             minHypothesisDist = dist;
             finalInlierIndexes.swap(inlierIndexes);
+            trace.winIterations.push_back(static_cast<uint8_t>(iteration + 1));
             // early stop (quirk: tests the swapped-out previous best, :308-312)
             if (inlierIndexes.size() > inliersAcceptedCount)
+            {
+                trace.earlyStop = true;
                 break;
+            }
         }
     }
 
     std::fill(isInlierFinal.begin(), isInlierFinal.end(), 0);
     for (const unsigned idx : finalInlierIndexes)
         isInlierFinal[idx] = 1;
+    trace.best = static_cast<uint32_t>(finalInlierIndexes.size());
     return finalInlierIndexes.size();
 }
 
 // cylinder_segment.cpp:35-225
 static CylinderSeg make_cylinder_segment(const std::vector<PlaneSeg>& planeGrid, const std::vector<uint8_t>& isActivated,
-                                         unsigned cellActivatedCount, Rng& rng)
+                                         unsigned cellActivatedCount, Rng& rng, CylCandidateTrace& trace,
+                                         std::vector<CylLoopTrace>& loops, int candidateIndex)
 {
+    trace.n = cellActivatedCount;
     CylinderSeg cs;
     cs.cellActivatedCount = cellActivatedCount;
     const size_t samplesCount = isActivated.size();
@@ -987,6 +996,7 @@ static CylinderSeg make_cylinder_segment(const std::vector<PlaneSeg>& planeGrid,
     const double score = evals[2] / evals[0];
     if (score < kCylMinScore)
         return cs;
+    trace.scorePassed = true;
 
     const double axis[3] = {evecs[0][0], evecs[1][0], evecs[2][0]};
     cs.axis[0] = axis[0];
@@ -1019,12 +1029,30 @@ static CylinderSeg make_cylinder_segment(const std::vector<PlaneSeg>& planeGrid,
 
     const size_t minimumCellActivated =
             static_cast<unsigned>(kMinActivatedProportion * static_cast<double>(samplesCount));
-    while (planeSegmentsLeft > minimumCellActivated && planeSegmentsLeft > 0.1 * n)
+    for (;;)
     {
-        std::vector<uint8_t> isInlierFinal(n, 0);
-        const size_t maxInliersCount = run_ransac_loop(maximumIterations, idsLeft, N, PC, idsLeftMask, isInlierFinal, n, rng);
-        if (maxInliersCount < 6)
+        // the while condition of :146, taken apart for the trace
+        if (!(planeSegmentsLeft > minimumCellActivated))
+        {
+            trace.endReason = kCylEndMinimumCells;
             break;
+        }
+        if (!(planeSegmentsLeft > 0.1 * n))
+        {
+            trace.endReason = kCylEndTenPercent;
+            break;
+        }
+        std::vector<uint8_t> isInlierFinal(n, 0);
+        loops.emplace_back();
+        loops.back().candidate = candidateIndex;
+        const size_t maxInliersCount =
+                run_ransac_loop(maximumIterations, idsLeft, N, PC, idsLeftMask, isInlierFinal, n, rng, loops.back());
+        if (maxInliersCount < 6)
+        {
+            trace.endReason = kCylEndBestUnderSix;
+            break;
+        }
+        trace.inliers.push_back(static_cast<uint32_t>(maxInliersCount));
 
         double b = 0;
         double sumN[3] = {0, 0, 0}, sumC[3] = {0, 0, 0};
@@ -1472,7 +1500,11 @@ void Oracle::find_primitives(const float* cloud, const float* depth, FrameResult
             }
             out.seedOutcome.back() = 2;
             // cylinder_fitting, :478-501
-            CylinderSeg cyl = make_cylinder_segment(planeGrid, isActivated, cellActivatedCount, rng);
+            out.cylCandidates.emplace_back();
+            CylCandidateTrace& candidateTrace = out.cylCandidates.back();
+            CylinderSeg cyl = make_cylinder_segment(planeGrid, isActivated, cellActivatedCount, rng, candidateTrace, out.cylLoops,
+                                                    static_cast<int>(out.cylCandidates.size()) - 1);
+            candidateTrace.planeWon.assign(cyl.segmentCount, 0);
             cylinderSegments.push_back(cyl);
             for (unsigned segId = 0; segId < cyl.segmentCount; ++segId)
             {
@@ -1499,6 +1531,7 @@ void Oracle::find_primitives(const float* cloud, const float* depth, FrameResult
                 // add_cylinder_to_features, :437-476
                 if (merged.mse < cyl.mse[segId])
                 {
+                    candidateTrace.planeWon[segId] = 1;
                     planeSegments.push_back(copy_segment(merged));
                     const int currentPlaneCount = static_cast<int>(planeSegments.size());
                     for (unsigned col = 0; col < cellActivatedCount; ++col)
@@ -1877,6 +1910,50 @@ void cape_oracle_get_cylinders(void* h, double* rec /* C x 4: axis[3], radius */
         rec[4 * i + 1] = c.axis[1];
         rec[4 * i + 2] = c.axis[2];
         rec[4 * i + 3] = c.radius;
+    }
+}
+
+// trace of the cylinder branch of the last run (cape_oracle.hpp: CylCandidateTrace, CylLoopTrace)
+int cape_oracle_num_cyl_candidates(void* h) { return static_cast<int>(static_cast<Handle*>(h)->res.cylCandidates.size()); }
+// rec: K x 4 = n, scorePassed, sub-segment count, endReason
+void cape_oracle_get_cyl_candidates(void* h, int32_t* rec)
+{
+    Handle* H = static_cast<Handle*>(h);
+    for (size_t i = 0; i < H->res.cylCandidates.size(); ++i)
+    {
+        const CylCandidateTrace& c = H->res.cylCandidates[i];
+        rec[4 * i + 0] = static_cast<int32_t>(c.n);
+        rec[4 * i + 1] = c.scorePassed ? 1 : 0;
+        rec[4 * i + 2] = static_cast<int32_t>(c.inliers.size());
+        rec[4 * i + 3] = c.endReason;
+    }
+}
+void cape_oracle_get_cyl_segments(void* h, int candidate, uint32_t* inliers, uint8_t* planeWon)
+{
+    const CylCandidateTrace& c = static_cast<Handle*>(h)->res.cylCandidates[candidate];
+    for (size_t s = 0; s < c.inliers.size(); ++s)
+    {
+        inliers[s] = c.inliers[s];
+        planeWon[s] = c.planeWon[s];
+    }
+}
+int cape_oracle_num_cyl_loops(void* h) { return static_cast<int>(static_cast<Handle*>(h)->res.cylLoops.size()); }
+// rec: L x 6 = candidate, m, iterations, wins, earlyStop, best ; winIterations: L x maxIterations, zero padded
+void cape_oracle_get_cyl_loops(void* h, int32_t* rec, uint8_t* winIterations, int maxIterations)
+{
+    Handle* H = static_cast<Handle*>(h);
+    for (size_t i = 0; i < H->res.cylLoops.size(); ++i)
+    {
+        const CylLoopTrace& l = H->res.cylLoops[i];
+        rec[6 * i + 0] = l.candidate;
+        rec[6 * i + 1] = static_cast<int32_t>(l.m);
+        rec[6 * i + 2] = static_cast<int32_t>(l.iterations);
+        rec[6 * i + 3] = static_cast<int32_t>(l.winIterations.size());
+        rec[6 * i + 4] = l.earlyStop ? 1 : 0;
+        rec[6 * i + 5] = static_cast<int32_t>(l.best);
+        for (int k = 0; k < maxIterations; ++k)
+            winIterations[static_cast<size_t>(maxIterations) * i + k] =
+                    k < static_cast<int>(l.winIterations.size()) ? l.winIterations[k] : 0;
     }
 }
 

@@ -78,8 +78,38 @@ struct CylinderOut
     double radius; // NaN by quirk (shape_primitives.cpp:17-24 with cylinder_segment.cpp:23-29)
 };
 
+// ---- trace of the cylinder branch: an observer, no result depends on it ----
+// why the `while` of Cylinder_Segment's constructor ended (cylinder_segment.cpp:146-155)
+constexpr int kCylEndScoreGate = 0;    // never entered: score < 75 returned first
+constexpr int kCylEndMinimumCells = 1; // cells left <= minimumCellActivated
+constexpr int kCylEndTenPercent = 2;   // cells left <= 10 % of N (with more than minimumCellActivated left)
+constexpr int kCylEndBestUnderSix = 3; // the RANSAC loop's best hypothesis held fewer than 6 cells
+
+// one per Cylinder_Segment construction, in the order of the seeds
+struct CylCandidateTrace
+{
+    uint32_t n = 0;           // cellActivatedCount
+    bool scorePassed = false; // the eigenvalue-ratio gate
+    int endReason = kCylEndScoreGate;
+    std::vector<uint32_t> inliers; // per sub-segment: its inlier count
+    std::vector<uint8_t> planeWon; // per sub-segment: the plane won add_cylinder_to_features' model selection
+};
+
+// one per run_ransac_loop call, in call order
+struct CylLoopTrace
+{
+    int candidate = 0;       // index in FrameResult::cylCandidates
+    uint32_t m = 0;          // cells left on entry
+    uint32_t iterations = 0; // iterations run; 0 for the m < 3 return
+    std::vector<uint8_t> winIterations; // 1-based iteration of every hypothesis that lowered the distance
+    bool earlyStop = false;  // the swapped-vector early stop fired
+    uint32_t best = 0;       // the returned inlier count
+};
+
 struct FrameResult
 {
+    std::vector<CylCandidateTrace> cylCandidates; // trace: every cylinder_fitting call of the frame
+    std::vector<CylLoopTrace> cylLoops;           // trace: every run_ransac_loop call of the frame
     std::vector<int32_t> planeLabels; // _gridPlaneSegmentMap, row-major cells
     std::vector<int32_t> cylLabels;   // _gridCylinderSegMap
     std::vector<PlaneSeg> planeSegments; // _planeSegments after merge_planes() (merged roots refitted in place)

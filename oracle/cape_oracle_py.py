@@ -4,6 +4,7 @@ TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and be
 The product package never imports this module.  Parity status of the oracle itself: **parity unpinned**
 (see oracle/cape_oracle.hpp).
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -55,6 +56,11 @@ def lib(path=None):
         L.cape_oracle_get_boundary.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.cape_oracle_num_cylinders.argtypes = [C.c_void_p]
         L.cape_oracle_get_cylinders.argtypes = [C.c_void_p, C.c_void_p]
+        L.cape_oracle_num_cyl_candidates.argtypes = [C.c_void_p]
+        L.cape_oracle_get_cyl_candidates.argtypes = [C.c_void_p, C.c_void_p]
+        L.cape_oracle_get_cyl_segments.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.cape_oracle_num_cyl_loops.argtypes = [C.c_void_p]
+        L.cape_oracle_get_cyl_loops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.cape_oracle_depth_quantization.restype = C.c_double
         L.cape_oracle_depth_quantization.argtypes = [C.c_double]
         L.cape_oracle_eigen3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -72,6 +78,16 @@ def lib(path=None):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# why a candidate's `while` ended (kCylEnd* of cape_oracle.hpp)
+CYL_END_SCORE_GATE, CYL_END_MINIMUM_CELLS, CYL_END_TEN_PERCENT, CYL_END_BEST_UNDER_SIX = 0, 1, 2, 3
+RANSAC_MAX_ITERATIONS = 43  # cape_oracle_ransac_max_iterations(), pinned in tests/test_oracle_kat.py
+
+# n: activated cells; end: a CYL_END_* value; inliers / plane_won: one entry per sub-segment
+CylCandidate = collections.namedtuple("CylCandidate", "n score_passed segments end inliers plane_won")
+# candidate: index in cyl_candidates; m: cells left on entry; win_iterations: 1-based, one per winning hypothesis
+CylLoop = collections.namedtuple("CylLoop", "candidate m iterations wins win_iterations early_stop best")
 
 
 class OracleResult:
@@ -156,7 +172,31 @@ class Oracle:
         r.cylinders = np.zeros((K, 4), np.float64)
         if K:
             self.L.cape_oracle_get_cylinders(self.h, _p(r.cylinders))
+        r.cyl_candidates, r.cyl_loops = self._cyl_trace()
         return r
+
+    def _cyl_trace(self):
+        """The cylinder branch of the last run: one CylCandidate per Cylinder_Segment built, one CylLoop per run_ransac_loop."""
+        K = self.L.cape_oracle_num_cyl_candidates(self.h)
+        rec = np.zeros((K, 4), np.int32)
+        if K:
+            self.L.cape_oracle_get_cyl_candidates(self.h, _p(rec))
+        candidates = []
+        for i in range(K):
+            inl = np.zeros(rec[i, 2], np.uint32)
+            won = np.zeros(rec[i, 2], np.uint8)
+            if rec[i, 2]:
+                self.L.cape_oracle_get_cyl_segments(self.h, i, _p(inl), _p(won))
+            candidates.append(CylCandidate(int(rec[i, 0]), bool(rec[i, 1]), int(rec[i, 2]), int(rec[i, 3]),
+                                           [int(v) for v in inl], [bool(v) for v in won]))
+        n = self.L.cape_oracle_num_cyl_loops(self.h)
+        rec = np.zeros((n, 6), np.int32)
+        wins = np.zeros((n, RANSAC_MAX_ITERATIONS), np.uint8)
+        if n:
+            self.L.cape_oracle_get_cyl_loops(self.h, _p(rec), _p(wins), RANSAC_MAX_ITERATIONS)
+        loops = [CylLoop(int(r[0]), int(r[1]), int(r[2]), int(r[3]), [int(v) for v in w[:r[3]]], bool(r[4]), int(r[5]))
+                 for r, w in zip(rec, wins)]
+        return candidates, loops
 
     def rectify(self, depth, T):
         d = np.ascontiguousarray(depth, np.float32)

@@ -138,14 +138,28 @@ constexpr int kCylCacheRounds = 12;
     if (j0 + lane + 64 * (k) < m)                                                                            \
         c.s_cur[cqi##k] = (unsigned char)((inlBits >> (k)) & 1u);
 
-// relative distance between the tree-order sum and the ordered sum of m <= 4096 non-negative doubles: each is within
-// (m - 1) * 2^-53 <= 2^-41 of the exact sum.  A test build widens it (-DCAPE_CYL_EPS=0.25) to drive the exact path.
+// Relative distance between the tree-order sum T and the ordered sum O of the same m non-negative doubles, exact sum S.  With
+// u = 2^-53 and g = (m - 1) u / (1 - (m - 1) u), ANY order of the m - 1 additions ends within g * S of S (every addend goes through at
+// most m - 1 roundings, and no addend cancels another), so T (1 - g) / (1 + g) <= O <= T (1 + g) / (1 - g): O lies within
+// 2 g + 2 g^2 + ... of T, and the products T * (1 -+ eps) round once more (u).  eps = 2 m u = m * 2^-52 covers all of it:
+// 2 m u - 2 g = 2 u - 2 (m - 1)^2 u^2 - ..., and 2 u exceeds the u of the product's rounding plus every second-order term while
+// m < 2^25.  The constant 2^-40 this replaced is that bound at m = 4096 exactly: at m = 4097 the worst case is outside it, and a
+// 96 x 54 grid (5184 cells) or the general instance (up to 65535 cells) can hand over more.  So the bracket grows with the number of
+// addends -- cyl_eps(m), never narrower than 2^-40 -- one uniform multiply per RANSAC loop and per model selection.  Both MSE paths
+// sum over the N cells of the region (zero addends for the cells outside the sub-segment): they take cyl_eps(N).
+// A test build replaces it (-DCAPE_CYL_EPS=0.25) to drive the exact path.
 #ifndef CAPE_CYL_PROJ_ROUNDS
 #define CAPE_CYL_PROJ_ROUNDS 4
 #endif
-#ifndef CAPE_CYL_EPS
-#define CAPE_CYL_EPS 0x1p-40
+__device__ __forceinline__ double cyl_eps(int m)
+{
+#ifdef CAPE_CYL_EPS
+    (void)m;
+    return CAPE_CYL_EPS;
+#else
+    return fmax(0x1p-40, (double)m * 0x1p-52);
 #endif
+}
 
 __device__ __forceinline__ int cyl_wave_sum(int v) { return wave_sum_i32(v); }
 
@@ -314,9 +328,10 @@ __device__ inline void cylinder_fitting(const CylCtxT<LabT>& c, int& nSeg, int& 
             // ever compares against it (dist < minHypothesisDist, :296); nothing else of it is observable.  An ordered sum is
             // a serial chain over m cells, so the wave keeps an INTERVAL [minLo, minHi] that contains the best's ordered sum
             // (exact, lo == hi, until a hypothesis wins) and decides with the tree-order sum psum, whose distance to the
-            // ordered sum is bounded (CAPE_CYL_EPS).  Only when the intervals overlap are the ordered sums computed -- of the
+            // ordered sum is bounded (cyl_eps).  Only when the intervals overlap are the ordered sums computed -- of the
             // new hypothesis and, if it is still an interval, of the best (its parameters are kept for that).
             double minLo = (double)(maxSqrtDistF * (float)m), minHi = minLo;
+            const double eps = cyl_eps(m);
             double bR = 0.0, bInvR2 = 0.0, bCx = 0.0, bCy = 0.0, bCz = 0.0; // the best hypothesis, for a late exact sum
             int prevBestCount = 0; // size of the vector swapped out of finalInlierIndexes
             for (int j = lane; j < N; j += 64)
@@ -434,7 +449,7 @@ __device__ inline void cylinder_fitting(const CylCtxT<LabT>& c, int& nSeg, int& 
                 }
                 const int curCount = cyl_wave_sum(curLocal);
                 psum = wave_sum_f64_tree(psum);
-                double lo = psum * (1.0 - CAPE_CYL_EPS), hi = psum * (1.0 + CAPE_CYL_EPS);
+                double lo = psum * (1.0 - eps), hi = psum * (1.0 + eps);
                 bool wins;
                 if (lo >= minHi)
                     wins = false; // ordered sum >= lo >= the best's
@@ -616,7 +631,8 @@ __device__ inline void cylinder_fitting(const CylCtxT<LabT>& c, int& nSeg, int& 
         bool planeWins;
         {
             const double kInl = (double)maxInliers;
-            const double mseLo = (mseTree * (1.0 - CAPE_CYL_EPS)) / kInl, mseHi = (mseTree * (1.0 + CAPE_CYL_EPS)) / kInl;
+            const double eps = cyl_eps(N);
+            const double mseLo = (mseTree * (1.0 - eps)) / kInl, mseHi = (mseTree * (1.0 + eps)) / kInl;
             if (f.mse < mseLo)
                 planeWins = true;
             else if (!(f.mse < mseHi))

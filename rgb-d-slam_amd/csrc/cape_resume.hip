@@ -346,8 +346,9 @@ __device__ inline void cylinder_fitting_group(const GroupCtx& g, int& nSeg, int&
             const int m = idsLeftCount;
             const unsigned inliersAccepted = (unsigned)floor(0.9 * (double)m);
             // [minLo, minHi] brackets the ORDERED sum of the best hypothesis' MSAC costs (see cape_cylinder.h: the reference
-            // only ever compares against it, and the tree-order sum of the same addends is within CAPE_CYL_EPS of it)
+            // only ever compares against it, and the tree-order sum of the same addends is within cyl_eps(m) of it)
             double minLo = (double)(maxSqrtDistF * (float)m), minHi = minLo;
+            const double eps = cyl_eps(m);
             int prevBestCount = 0;
             for (int j = tid; j < N; j += kGroupThreads)
                 g.s_best[j] = 0;
@@ -549,7 +550,7 @@ __device__ inline void cylinder_fitting_group(const GroupCtx& g, int& nSeg, int&
                     rngPos = rngBase + 3 * (it + 1);
                     const double psAll = psH[h];
                     const int curCount = cntH[h];
-                    double lo = psAll * (1.0 - CAPE_CYL_EPS), hi = psAll * (1.0 + CAPE_CYL_EPS);
+                    double lo = psAll * (1.0 - eps), hi = psAll * (1.0 + eps);
                     bool wins;
                     if (lo >= minHi)
                         wins = false; // ordered sum >= lo >= the best's
@@ -762,7 +763,8 @@ __device__ inline void cylinder_fitting_group(const GroupCtx& g, int& nSeg, int&
         bool planeWins;
         {
             const double kInl = (double)maxInliers;
-            const double mseLo = (mseTree * (1.0 - CAPE_CYL_EPS)) / kInl, mseHi = (mseTree * (1.0 + CAPE_CYL_EPS)) / kInl;
+            const double eps = cyl_eps(N);
+            const double mseLo = (mseTree * (1.0 - eps)) / kInl, mseHi = (mseTree * (1.0 + eps)) / kInl;
             if (f.mse < mseLo)
                 planeWins = true;
             else if (!(f.mse < mseHi))
