@@ -3,8 +3,13 @@
 // host/boundary_polygon.cpp in the host's order and with its early exits, on ONE wavefront: union_pair for a map polygon without holes
 // whose union creates none, and beside it union_pair_holes (cape_map_union_holes, cape_debug_polygon_union) with add_hole,
 // carry_hole's kept and covered cases, Polygon::area and simplify over interior rings as well; a hole the detection covers in part
-// stays the host's.  The two share every per-lane and per-wave function; union_pair, union_simplify and the kernels that call them
-// are kept as they were, statement for statement, so that they compile to what they were.
+// stays the host's.  The two modes call one copy of every per-lane and per-wave function and of the steps that cost nothing to share:
+// the placement of the operands (union_place_operands), the Douglas-Peucker loop (union_dp_candidate), union_orient with its sense,
+// union_area on union_area_holed, union_hosted.  The arrangement (step 3 up to the last link), the start of the outer walk, the test
+// of a walked face and union_left_out's loop stand in both modes, for a measured reason: shared as plain __forceinline__ functions
+// they compute the same rows, but the optimiser simplifies a callee before it inlines it, the register allocation moves, and on an
+// MI355X a call's median then left the spread of the restated build by 0.05 to 0.3 % (profiles/map_union_shared_steps.txt).  An
+// edit to one of those copies is made in union_pair and in union_pair_holes.
 //
 // Two parts.  The first holds the plain per-lane functions (projection, cut parameters, crossing points, the angle of the face walk
 // with its guard band, the collinear test, the Douglas-Peucker distance, the bounding-box test in front of a hole's intersection): they
@@ -389,11 +394,11 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 
 // the orientation the host class gives an outer ring: reversed when its signed area is positive (every lane reads the whole ring
 // before any lane rewrites it)
-__device__ __forceinline__ void union_orient(double2* ring, int n, int lane)
+__device__ __forceinline__ void union_orient(double2* ring, int n, int lane, bool hole = false)
 {
     const double s = ring_area_signed(ring, n);
     CAPE_MP_SYNC();
-    if (s > 0)
+    if (hole ? s < 0 : s > 0)
     {
         for (int v = lane; v < n / 2; v += 64)
         {
@@ -405,14 +410,22 @@ __device__ __forceinline__ void union_orient(double2* ring, int n, int lane)
     }
 }
 
-// Polygon::area of a polygon without holes
-__device__ __forceinline__ double union_area(const double2* ring, int n)
+// Polygon::area: the outer ring minus the interior rings in order, clamped at 0
+__device__ __forceinline__ double union_area_holed(const double2* ring, int n, const double2* holes, const unsigned short* len, int nHoles)
 {
     if (n < 3)
         return 0.0;
-    const double a = fabs(ring_area_signed(ring, n));
+    double a = fabs(ring_area_signed(ring, n));
+    for (int k = 0, at = 0; k < nHoles; ++k)
+    {
+        const int nk = uni(len[k]);
+        a -= fabs(ring_area_signed(holes + at, nk));
+        at += nk;
+    }
     return a < 0 ? 0.0 : a;
 }
+
+__device__ __forceinline__ double union_area(const double2* ring, int n) { return union_area_holed(ring, n, nullptr, nullptr, 0); }
 
 // point_in_ring: crossing number, points on the boundary count as inside when `closed`.  Lanes over the edges.
 __device__ __forceinline__ bool union_point_in_ring(const double2& p, const double2* ring, int n, bool closed, int lane)
@@ -505,87 +518,6 @@ __device__ __forceinline__ int union_drop_collinear(double2* r, int n, int lane)
     return n;
 }
 
-// Polygon::simplify of a polygon without holes: ring[0, n) (room for n + 1) becomes the Douglas-Peucker candidate if that is a
-// simple ring of more than 75 % of the area; `cand` takes the candidate (room for n).  Returns the new length; area in / out.
-__device__ __forceinline__ int union_simplify(const UnionLds& L, double2* ring, int n, double2* cand, double& area, int lane)
-{
-    area = union_area(ring, n);
-    if (n < 4 || n > kUnionOut)
-        return n;
-    const double eps = umax(area / 1e5, 10.0);
-    if (lane == 0)
-        ring[n] = ring[0]; // closed onto vertex 0
-    for (int i = lane; i <= n; i += 64)
-        L.keep[i] = (i == 0 || i == n) ? 1 : 0;
-    if (lane == 0)
-        L.stack[0] = (unsigned)n; // (a << 16) | b with a = 0
-    int sp = 1;
-    CAPE_MP_SYNC();
-    while (sp > 0)
-    {
-        const unsigned ab = L.stack[--sp];
-        const int a = uni((int)(ab >> 16)), b = uni((int)(ab & 0xFFFFu));
-        if (b <= a + 1 || b > n)
-            continue;
-        const double2 pa = ring[a], pb = ring[b];
-        unsigned long long best = 0ull; // squared distance bits (>= +0); the first index wins a tie, like the host's strict >
-        int bestI = 0x7FFFFFFF;
-        for (int i = a + 1 + lane; i < b; i += 64)
-        {
-            const double d = union_segment_distance2(ring[i], pa, pb);
-            const unsigned long long db = (unsigned long long)__double_as_longlong(d);
-            if (bestI == 0x7FFFFFFF || db > best)
-            {
-                best = db;
-                bestI = i;
-            }
-        }
-        const unsigned long long mx = ~wave_min_u64(~best);
-        const unsigned mineKey = (bestI != 0x7FFFFFFF && best == mx) ? (unsigned)(0x7FFFFFFF - bestI) : 0u;
-        const int idx = 0x7FFFFFFF - (int)wave_max_u32(mineKey);
-        const double dmax = __longlong_as_double((long long)mx);
-        if (dmax > eps * eps && idx > a && idx < b && sp + 2 <= kUnionStack)
-        {
-            if (lane == 0)
-            {
-                L.keep[idx] = 1;
-                L.stack[sp] = ((unsigned)a << 16) | (unsigned)idx;
-                L.stack[sp + 1] = ((unsigned)idx << 16) | (unsigned)b;
-            }
-            sp += 2;
-            CAPE_MP_SYNC();
-        }
-    }
-    int cn = 0;
-    for (int base = 0; base < n; base += 64)
-    {
-        const int i = base + lane;
-        const bool k = i < n && L.keep[i];
-        const unsigned long long kb = __ballot(k);
-        if (k)
-            cand[cn + __popcll(kb & ((1ull << lane) - 1ull))] = ring[i];
-        cn += __popcll(kb);
-    }
-    CAPE_MP_SYNC();
-    if (cn >= 3 && union_ring_is_simple(cand, cn, lane))
-    {
-        const double newArea = union_area(cand, cn);
-        if (newArea > area * 0.75)
-        {
-            CAPE_MP_SYNC();
-            for (int i = lane; i < cn; i += 64)
-                ring[i] = cand[i];
-            CAPE_MP_SYNC();
-            area = newArea;
-            return cn;
-        }
-    }
-    return n;
-}
-
-// ---- interior rings (the holes mode)
-// The Douglas-Peucker candidate (the loop of union_simplify above, for any ring) of the closed ring ring[0, n) (room for n + 1: the ring is closed onto its vertex 0) for the
-// tolerance eps, into cand (room for n).  4 <= n <= kUnionOut.  Returns its length.
 __device__ __forceinline__ int union_dp_candidate(const UnionLds& L, double2* ring, int n, double2* cand, double eps, int lane)
 {
     if (lane == 0)
@@ -645,38 +577,34 @@ __device__ __forceinline__ int union_dp_candidate(const UnionLds& L, double2* ri
     return cn;
 }
 
-// add_hole's orientation: reversed when the signed area is negative
-__device__ __forceinline__ void union_orient_hole(double2* ring, int n, int lane)
+// Polygon::simplify of a polygon without holes: ring[0, n) (room for n + 1) becomes the Douglas-Peucker candidate if that is a
+// simple ring of more than 75 % of the area; `cand` takes the candidate (room for n).  Returns the new length; area in / out.
+__device__ __forceinline__ int union_simplify(const UnionLds& L, double2* ring, int n, double2* cand, double& area, int lane)
 {
-    const double s = ring_area_signed(ring, n);
-    CAPE_MP_SYNC();
-    if (s < 0)
+    area = union_area(ring, n);
+    if (n < 4 || n > kUnionOut)
+        return n;
+    const double eps = umax(area / 1e5, 10.0);
+    const int cn = union_dp_candidate(L, ring, n, cand, eps, lane);
+    if (cn >= 3 && union_ring_is_simple(cand, cn, lane))
     {
-        for (int v = lane; v < n / 2; v += 64)
+        const double newArea = union_area(cand, cn);
+        if (newArea > area * 0.75)
         {
-            const double2 a = ring[v], b = ring[n - 1 - v];
-            ring[v] = b;
-            ring[n - 1 - v] = a;
+            CAPE_MP_SYNC();
+            for (int i = lane; i < cn; i += 64)
+                ring[i] = cand[i];
+            CAPE_MP_SYNC();
+            area = newArea;
+            return cn;
         }
-        CAPE_MP_SYNC();
     }
+    return n;
 }
 
-// Polygon::area: the outer ring minus the interior rings in order, clamped at 0
-__device__ __forceinline__ double union_area_holed(const double2* ring, int n, const double2* holes, const unsigned short* len, int nHoles)
-{
-    if (n < 3)
-        return 0.0;
-    double a = fabs(ring_area_signed(ring, n));
-    for (int k = 0, at = 0; k < nHoles; ++k)
-    {
-        const int nk = uni(len[k]);
-        a -= fabs(ring_area_signed(holes + at, nk));
-        at += nk;
-    }
-    return a < 0 ? 0.0 : a;
-}
-
+// ---- interior rings (the holes mode)
+// The Douglas-Peucker candidate (the loop of union_simplify above, for any ring) of the closed ring ring[0, n) (room for n + 1: the ring is closed onto its vertex 0) for the
+// tolerance eps, into cand (room for n).  4 <= n <= kUnionOut.  Returns its length.
 // does every vertex of q[0, nq) lie inside or on ring[0, n)?  Lanes over the vertices, each walks the whole ring.
 __device__ __forceinline__ bool union_all_inside(const double2* q, int nq, const double2* ring, int n, int lane)
 {
@@ -882,22 +810,14 @@ __device__ __forceinline__ int union_walk_face(const UnionLds& L, UnionGraph& G,
     return -1;
 }
 
-struct UnionResult
+// ---- the steps of a pair that both modes run (union_pair, union_pair_holes)
+// Steps 1 and 2.  L.ringA[0, nA) holds the map polygon's ring in its frame `fa` (oriented or not), L.ringB[0, nB) the detection's
+// world ring in its frame `fb`; both end up oriented in `frame`: the target, or the map polygon's own where Polygon::project's
+// isApprox shortcut holds.  Returns whether Polygon::project ran.
+__device__ __forceinline__ bool union_place_operands(const UnionLds& L, int nA, int nB, const UnionFrame& fa, const UnionFrame& fb,
+                                                     const UnionFrame& target, UnionFrame& frame, int lane)
 {
-    uint32_t flags;
-    int n;          // vertices of the result ring
-    int nNodes;
-    double area;
-    const double2* ring; // in LDS
-};
-
-// One pair on one wavefront.  L.ringA[0, nA) holds the map polygon's ring in its frame `fa` (oriented or not), L.ringB[0, nB) the
-// detection's world ring in its frame `fb`; `target` is the fusion frame.  3 <= nA, nB <= kUnionRing.  `frame` receives the frame of
-// the result (the target, or the map polygon's own where Polygon::project's shortcut holds).
-__device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, const UnionFrame& fa, const UnionFrame& fb, const UnionFrame& target,
-                                         UnionFrame& frame, int lane)
-{
-    UnionResult res{};
+    bool projected = false;
     // ---- 1. the map ring: as the host class holds it, then Polygon::project into the target unless its frame already is the target
     union_orient(L.ringA, nA, lane);
     frame = fa;
@@ -908,6 +828,7 @@ __device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, cons
         CAPE_MP_SYNC();
         union_orient(L.ringA, nA, lane);
         frame = target;
+        projected = true;
     }
     // ---- 2. the detection: merge_union always projects it into this polygon's frame
     union_orient(L.ringB, nB, lane);
@@ -915,6 +836,35 @@ __device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, cons
         L.ringB[v] = union_project(L.ringB[v], fb, frame);
     CAPE_MP_SYNC();
     union_orient(L.ringB, nB, lane);
+    return projected;
+}
+
+struct UnionResult
+{
+    uint32_t flags;
+    int n;          // vertices of the result ring
+    int nNodes;
+    double area;
+    const double2* ring; // in LDS
+};
+
+// a pair that is the host's: its reason alone (a capacity outranks every other), and the nodes met
+__device__ __forceinline__ UnionResult union_hosted(uint32_t bits, int nNodes)
+{
+    UnionResult r{};
+    r.flags = (bits & CAPE_UNION_HOST_CAPACITY) ? (uint32_t)CAPE_UNION_HOST_CAPACITY : bits;
+    r.nNodes = nNodes;
+    return r;
+}
+
+// One pair on one wavefront.  L.ringA[0, nA) holds the map polygon's ring in its frame `fa` (oriented or not), L.ringB[0, nB) the
+// detection's world ring in its frame `fb`; `target` is the fusion frame.  3 <= nA, nB <= kUnionRing.  `frame` receives the frame of
+// the result (the target, or the map polygon's own where Polygon::project's shortcut holds).
+__device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, const UnionFrame& fa, const UnionFrame& fb, const UnionFrame& target,
+                                         UnionFrame& frame, int lane)
+{
+    UnionResult res{};
+    (void)union_place_operands(L, nA, nB, fa, fb, target, frame, lane);
     const double2 *A = L.ringA, *B = L.ringB;
     const double areaMap = union_area(A, nA); // Polygon::_area of the projected map polygon
     res.flags = CAPE_UNION_SERVED | CAPE_UNION_UNCHANGED;
@@ -1008,11 +958,7 @@ __device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, cons
     }
     CAPE_MP_SYNC();
     if (cutOverflow)
-    {
-        res = UnionResult{};
-        res.flags = CAPE_UNION_HOST_CAPACITY;
-        return res;
-    }
+        return union_hosted(CAPE_UNION_HOST_CAPACITY, 0);
     // the cuts in (segment, parameter) order: a rank sort on the parameters' bit patterns (non-negative doubles: the numbers' order)
     for (int base = 0; base < nCuts; base += 64)
     {
@@ -1051,12 +997,7 @@ __device__ inline UnionResult union_pair(const UnionLds& L, int nA, int nB, cons
     }
     CAPE_MP_SYNC(); // (the sorted cuts are dead: the walked rings take their place)
     res.nNodes = G.nNodes;
-    const auto hosted = [&](uint32_t bits) {
-        UnionResult r{};
-        r.flags = (bits & CAPE_UNION_HOST_CAPACITY) ? (uint32_t)CAPE_UNION_HOST_CAPACITY : bits;
-        r.nNodes = G.nNodes;
-        return r;
-    };
+    const auto hosted = [&](uint32_t bits) { return union_hosted(bits, G.nNodes); };
     if (G.fail)
         return hosted(G.fail);
     int nOuter = 0;
@@ -1187,13 +1128,13 @@ struct UnionHoleFetch
         for (int v = lane; v < n; v += 64)
             dst[v] = H.src[off + v];
         CAPE_MP_SYNC();
-        union_orient_hole(dst, n, lane);
+        union_orient(dst, n, lane, true);
         if (projected)
         {
             for (int v = lane; v < n; v += 64)
                 dst[v] = union_project(dst[v], fa, target);
             CAPE_MP_SYNC();
-            union_orient_hole(dst, n, lane);
+            union_orient(dst, n, lane, true);
         }
         return n;
     }
@@ -1228,8 +1169,8 @@ struct UnionHoleFetch
     }
 };
 
-// The same pair in the holes mode (cape_map_union_holes, cape_debug_polygon_union): union_pair's statements, restated here so that
-// union_pair itself stays as it was, with the host's hole statements between them.  H.src / srcOff / srcLen describe the map plane's
+// The same pair in the holes mode (cape_map_union_holes, cape_debug_polygon_union): union_pair's steps -- the shared ones through the
+// same functions, step 3 and the face test restated (see the head of this file) -- with the host's hole statements between them.  H.src / srcOff / srcLen describe the map plane's
 // interior rings (H.nSrc <= kUnionHoles of 3 .. kUnionRing vertices each, inside their buffer: the caller has checked), which are
 // fetched, oriented and projected where the host's statements read them; faces the union encloses and holes the detection leaves alone
 // become the result's interior rings (`holes`; the rings in H.holes / H.holeLen).  Never HOST_MAP_HOLES or HOST_NEW_HOLE.
@@ -1237,25 +1178,7 @@ __device__ inline UnionResult union_pair_holes(const UnionLds& L, const UnionHol
                                                const UnionFrame& target, UnionFrame& frame, UnionHoleResult& holes, int lane)
 {
     UnionResult res{};
-    bool projected = false;
-    // ---- 1. the map ring: as the host class holds it, then Polygon::project into the target unless its frame already is the target
-    union_orient(L.ringA, nA, lane);
-    frame = fa;
-    if (!(union_is_approx3(fa.c, target.c) && union_is_approx3(fa.x, target.x) && union_is_approx3(fa.y, target.y)))
-    {
-        for (int v = lane; v < nA; v += 64)
-            L.ringA[v] = union_project(L.ringA[v], fa, target);
-        CAPE_MP_SYNC();
-        union_orient(L.ringA, nA, lane);
-        frame = target;
-        projected = true;
-    }
-    // ---- 2. the detection: merge_union always projects it into this polygon's frame
-    union_orient(L.ringB, nB, lane);
-    for (int v = lane; v < nB; v += 64)
-        L.ringB[v] = union_project(L.ringB[v], fb, frame);
-    CAPE_MP_SYNC();
-    union_orient(L.ringB, nB, lane);
+    const bool projected = union_place_operands(L, nA, nB, fa, fb, target, frame, lane);
     const double2 *A = L.ringA, *B = L.ringB;
     const UnionHoleFetch fetch{H, fa, target, projected, lane};
     const double areaMap = union_area(A, nA); // Polygon::_area of the projected map polygon (without holes)
@@ -1350,11 +1273,7 @@ __device__ inline UnionResult union_pair_holes(const UnionLds& L, const UnionHol
     }
     CAPE_MP_SYNC();
     if (cutOverflow)
-    {
-        res = UnionResult{};
-        res.flags = CAPE_UNION_HOST_CAPACITY;
-        return res;
-    }
+        return union_hosted(CAPE_UNION_HOST_CAPACITY, 0);
     // the cuts in (segment, parameter) order: a rank sort on the parameters' bit patterns (non-negative doubles: the numbers' order)
     for (int base = 0; base < nCuts; base += 64)
     {
@@ -1393,12 +1312,7 @@ __device__ inline UnionResult union_pair_holes(const UnionLds& L, const UnionHol
     }
     CAPE_MP_SYNC(); // (the sorted cuts are dead: the walked rings take their place)
     res.nNodes = G.nNodes;
-    const auto hosted = [&](uint32_t bits) {
-        UnionResult r{};
-        r.flags = (bits & CAPE_UNION_HOST_CAPACITY) ? (uint32_t)CAPE_UNION_HOST_CAPACITY : bits;
-        r.nNodes = G.nNodes;
-        return r;
-    };
+    const auto hosted = [&](uint32_t bits) { return union_hosted(bits, G.nNodes); };
     if (G.fail)
         return hosted(G.fail);
     int nOuter = 0;
@@ -1459,7 +1373,7 @@ __device__ inline UnionResult union_pair_holes(const UnionLds& L, const UnionHol
                     {
                         if (nNew < kUnionHoles && newVertices + nf <= kUnionHoleVertices)
                         {
-                            union_orient_hole(L.face, nf, lane); // add_hole
+                            union_orient(L.face, nf, lane, true); // add_hole
                             for (int v = lane; v < nf; v += 64)
                                 H.holes[newVertices + v] = L.face[v];
                             if (lane == 0)

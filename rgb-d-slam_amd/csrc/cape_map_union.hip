@@ -15,8 +15,10 @@
 //   A frame the wide match flagged CAPE_MATCH_EXACT_OVERFLOW reports nothing: its rows are zeros.
 //   cape_map_union_holes_kernel, cape_polygon_union_kernel : the same two for the holes mode (union_pair_holes: a map plane with
 //        interior rings, a union that encloses faces).  The same rows and slab, where a served polygon's rings lie back to back, plus
-//        a row of ring lengths per kept plane; a larger carve (union_holes_layout).  The kernels above stand as they were: the holes mode shares their
-//        per-lane functions and restates the rest beside them.
+//        a row of ring lengths per kept plane; a larger carve (union_holes_layout).  The two modes share the loading of a pair
+//        (load_map_pair, load_debug_pair).  Pass 1 stands twice, in cape_map_union_kernel and in union_find_pairs for the holes
+//        kernel: called from both, it moved the plain kernel's register allocation, and a call's median left the spread of the
+//        restated build (profiles/map_union_shared_steps.txt).
 //
 // Every count read from the map, a row or a table is checked against its buffer before it indexes anything; every loop of union_pair
 // is bounded by a capacity of the carve.
@@ -37,6 +39,36 @@ __device__ __forceinline__ void load_frame(UnionFrame& f, const double* x, const
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         f.x[k] = x[k], f.y[k] = y[k], f.c[k] = c[k];
+}
+
+// a frame's pair into the carve (both frame kernels): the map plane's outer ring, the detection's world ring, and the frames of the
+// map plane, the measurement and the fusion row.  The caller has checked the counts against the carve and the buffers.
+__device__ __forceinline__ void load_map_pair(const UnionLds& L, const double2* srcA, unsigned nA, const double2* srcB, unsigned nB, const cape_map_plane& M,
+                                              const cape_plane_measurement& m, const cape_plane_fusion& fu, UnionFrame& fa, UnionFrame& fb,
+                                              UnionFrame& target, int lane)
+{
+    for (unsigned v = lane; v < nA; v += 64)
+        L.ringA[v] = srcA[v];
+    for (unsigned v = lane; v < nB; v += 64)
+        L.ringB[v] = srcB[v];
+    CAPE_MP_SYNC();
+    load_frame(fa, M.x_axis, M.y_axis, M.center);
+    load_frame(fb, m.x_axis, m.y_axis, m.center);
+    load_frame(target, fu.x_axis, fu.y_axis, fu.center);
+}
+
+// ... and the pair of a debug kernel: two rings and 27 doubles, the frames of ring a, ring b and the target (x, y, centre each)
+__device__ __forceinline__ void load_debug_pair(const UnionLds& L, const double2* ringA, int nA, const double2* ringB, int nB, const double* frames27,
+                                                UnionFrame& fa, UnionFrame& fb, UnionFrame& target, int lane)
+{
+    for (int v = lane; v < nA; v += 64)
+        L.ringA[v] = ringA[v];
+    for (int v = lane; v < nB; v += 64)
+        L.ringB[v] = ringB[v];
+    CAPE_MP_SYNC();
+    load_frame(fa, frames27, frames27 + 3, frames27 + 6);
+    load_frame(fb, frames27 + 9, frames27 + 12, frames27 + 15);
+    load_frame(target, frames27 + 18, frames27 + 21, frames27 + 24);
 }
 
 // the row of a pair from union_pair's result; a served ring goes to slab[used, used + n) if it fits `capacity`.  Returns the new `used`.
@@ -68,130 +100,8 @@ __device__ __forceinline__ unsigned put_pair(const UnionResult& res, const Union
     return used;
 }
 
-} // namespace
-
-__global__ __launch_bounds__(64) void cape_map_union_kernel(MapUnionParams p, int nFrames)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const UnionLds L = union_carve(smem);
-    const int lane = threadIdx.x & 63;
-    const int frame = (int)blockIdx.x;
-    if (frame >= nFrames)
-        return;
-    const cape_frame_map_match_wide hd = p.matchFrames[frame];
-    const int nMap = p.nMap;
-    const bool reports = !(hd.flags & CAPE_MATCH_EXACT_OVERFLOW);
-    const int nCur = !reports ? 0 : (hd.n_cur < 0 ? 0 : (hd.n_cur > kUnionPlanes ? kUnionPlanes : hd.n_cur));
-    cape_plane_union* rows = p.rows + (size_t)frame * kUnionPlanes;
-    const cape_plane_fusion* fusion = p.fusion + (size_t)frame * kUnionPlanes;
-    double2* slab = p.vertices + (size_t)frame * CAPE_MAP_UNION_FRAME_VERTICES;
-    // ---- pass 1: which kept planes have a pair
-    unsigned long long pairs[2];
-#pragma unroll 1
-    for (int s = 0; s < 2; ++s)
-    {
-        const int i = lane + 64 * s;
-        bool pair = false;
-        if (i < nCur)
-        {
-            const int j = fusion[i].map_plane;
-            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
-            if (j >= 0 && j < nMap && (fusion[i].flags & CAPE_FUSION_FRAME) && at.x < (unsigned)p.nRecords && at.y < (unsigned)CAPE_MAX_PLANES)
-            {
-                const uint32_t mflags = p.measurements[(size_t)at.x * CAPE_MAX_PLANES + at.y].flags;
-                pair = (mflags & CAPE_MEASURE_KEPT) && !(mflags & CAPE_MEASURE_FAIL_POLYGON) && p.match[(size_t)frame * nMap + j] == i;
-            }
-        }
-        if (!pair)
-        {
-            cape_plane_union row{};
-            row.map_plane = i < nCur ? -1 : 0;
-            rows[i] = row;
-        }
-        pairs[s] = __ballot(pair);
-    }
-    // ---- pass 2: the pairs in kept-plane order
-    unsigned used = 0;
-#pragma unroll 1
-    for (int s = 0; s < 2; ++s)
-    {
-        unsigned long long todo = pairs[s];
-        while (todo)
-        {
-            const int i = 64 * s + __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int j = uni(fusion[i].map_plane);
-            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
-            const int rec = uni((int)at.x);
-            const cape_plane_measurement& m = p.measurements[(size_t)rec * CAPE_MAX_PLANES + uni((int)at.y)];
-            const cape_map_plane& M = p.mapPlanes[j];
-            UnionResult res{};
-            UnionFrame frameOut{};
-            const unsigned ringFirst = (unsigned)uni((int)M.ring_first), ringCount = (unsigned)uni((int)M.ring_count);
-            if (ringCount > 1u)
-                res.flags = CAPE_UNION_HOST_MAP_HOLES; // (decided before any geometry)
-            else if (ringCount == 0u || ringFirst >= p.nMapRings)
-                res.flags = CAPE_UNION_HOST_CAPACITY;
-            else
-            {
-                const cape_map_ring R = p.mapRings[ringFirst];
-                const unsigned nA = (unsigned)uni((int)R.vertex_count), offA = (unsigned)uni((int)R.vertex_offset);
-                const unsigned nB = (unsigned)uni((int)m.vertex_count), offB = (unsigned)uni((int)m.vertex_offset);
-                const unsigned cap = (unsigned)p.boundaryCapacity;
-                if (nA > (unsigned)kUnionRing || nB > (unsigned)kUnionRing || nA < 3u || nB < 3u || (unsigned long long)offA + nA > p.nMapVertices ||
-                    offB > cap || nB > cap - offB)
-                    res.flags = CAPE_UNION_HOST_CAPACITY;
-                else
-                {
-                    const double2* srcA = p.mapVertices + offA;
-                    const double2* srcB = p.worldVertices + (size_t)rec * cap + offB;
-                    for (unsigned v = lane; v < nA; v += 64)
-                        L.ringA[v] = srcA[v];
-                    for (unsigned v = lane; v < nB; v += 64)
-                        L.ringB[v] = srcB[v];
-                    CAPE_MP_SYNC();
-                    UnionFrame fa, fb, target;
-                    load_frame(fa, M.x_axis, M.y_axis, M.center);
-                    load_frame(fb, m.x_axis, m.y_axis, m.center);
-                    load_frame(target, fusion[i].x_axis, fusion[i].y_axis, fusion[i].center);
-                    res = union_pair(L, (int)nA, (int)nB, fa, fb, target, frameOut, lane);
-                }
-            }
-            used = put_pair(res, frameOut, j, rows + i, slab, used, CAPE_MAP_UNION_FRAME_VERTICES, lane);
-            CAPE_MP_SYNC(); // (the next pair rewrites the carve)
-        }
-    }
-}
-
-__global__ __launch_bounds__(64) void cape_ring_union_kernel(RingUnionParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const UnionLds L = union_carve(smem);
-    const int lane = threadIdx.x & 63;
-    UnionResult res{};
-    UnionFrame frameOut{};
-    if (p.nA > kUnionRing || p.nB > kUnionRing || p.nA < 3 || p.nB < 3)
-        res.flags = CAPE_UNION_HOST_CAPACITY;
-    else
-    {
-        for (int v = lane; v < p.nA; v += 64)
-            L.ringA[v] = p.ringA[v];
-        for (int v = lane; v < p.nB; v += 64)
-            L.ringB[v] = p.ringB[v];
-        CAPE_MP_SYNC();
-        UnionFrame fa, fb, target;
-        load_frame(fa, p.frames27, p.frames27 + 3, p.frames27 + 6);
-        load_frame(fb, p.frames27 + 9, p.frames27 + 12, p.frames27 + 15);
-        load_frame(target, p.frames27 + 18, p.frames27 + 21, p.frames27 + 24);
-        res = union_pair(L, p.nA, p.nB, fa, fb, target, frameOut, lane);
-    }
-    (void)put_pair(res, frameOut, 0, p.row, p.vertices, 0u, CAPE_MAP_MAX_RING, lane);
-}
-
-namespace {
-
-// pass 1 of cape_map_union_kernel for the holes kernel, lanes over the kept planes (i and i + 64): which kept planes have a pair; the rows of the others are
-// written here
+// pass 1 of cape_map_union_kernel for the holes kernel (a copy, kept for the measured reason at the head of this file), lanes over the kept planes (i and i + 64): which kept planes have a pair; the rows of the others
+// are written here
 __device__ __forceinline__ void union_find_pairs(const MapUnionParams& p, int frame, int nCur, cape_plane_union* rows, const cape_plane_fusion* fusion,
                                                  int lane, unsigned long long (&pairs)[2])
 {
@@ -273,6 +183,110 @@ __device__ __forceinline__ unsigned put_pair_holes(const UnionResult& res, const
 
 } // namespace
 
+__global__ __launch_bounds__(64) void cape_map_union_kernel(MapUnionParams p, int nFrames)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const UnionLds L = union_carve(smem);
+    const int lane = threadIdx.x & 63;
+    const int frame = (int)blockIdx.x;
+    if (frame >= nFrames)
+        return;
+    const cape_frame_map_match_wide hd = p.matchFrames[frame];
+    const int nMap = p.nMap;
+    const bool reports = !(hd.flags & CAPE_MATCH_EXACT_OVERFLOW);
+    const int nCur = !reports ? 0 : (hd.n_cur < 0 ? 0 : (hd.n_cur > kUnionPlanes ? kUnionPlanes : hd.n_cur));
+    cape_plane_union* rows = p.rows + (size_t)frame * kUnionPlanes;
+    const cape_plane_fusion* fusion = p.fusion + (size_t)frame * kUnionPlanes;
+    double2* slab = p.vertices + (size_t)frame * CAPE_MAP_UNION_FRAME_VERTICES;
+    // ---- pass 1: which kept planes have a pair
+    unsigned long long pairs[2];
+#pragma unroll 1
+    for (int s = 0; s < 2; ++s)
+    {
+        const int i = lane + 64 * s;
+        bool pair = false;
+        if (i < nCur)
+        {
+            const int j = fusion[i].map_plane;
+            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
+            if (j >= 0 && j < nMap && (fusion[i].flags & CAPE_FUSION_FRAME) && at.x < (unsigned)p.nRecords && at.y < (unsigned)CAPE_MAX_PLANES)
+            {
+                const uint32_t mflags = p.measurements[(size_t)at.x * CAPE_MAX_PLANES + at.y].flags;
+                pair = (mflags & CAPE_MEASURE_KEPT) && !(mflags & CAPE_MEASURE_FAIL_POLYGON) && p.match[(size_t)frame * nMap + j] == i;
+            }
+        }
+        if (!pair)
+        {
+            cape_plane_union row{};
+            row.map_plane = i < nCur ? -1 : 0;
+            rows[i] = row;
+        }
+        pairs[s] = __ballot(pair);
+    }
+    // ---- pass 2: the pairs in kept-plane order
+    unsigned used = 0;
+#pragma unroll 1
+    for (int s = 0; s < 2; ++s)
+    {
+        unsigned long long todo = pairs[s];
+        while (todo)
+        {
+            const int i = 64 * s + __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int j = uni(fusion[i].map_plane);
+            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
+            const int rec = uni((int)at.x);
+            const cape_plane_measurement& m = p.measurements[(size_t)rec * CAPE_MAX_PLANES + uni((int)at.y)];
+            const cape_map_plane& M = p.mapPlanes[j];
+            UnionResult res{};
+            UnionFrame frameOut{};
+            const unsigned ringFirst = (unsigned)uni((int)M.ring_first), ringCount = (unsigned)uni((int)M.ring_count);
+            if (ringCount > 1u)
+                res.flags = CAPE_UNION_HOST_MAP_HOLES; // (decided before any geometry)
+            else if (ringCount == 0u || ringFirst >= p.nMapRings)
+                res.flags = CAPE_UNION_HOST_CAPACITY;
+            else
+            {
+                const cape_map_ring R = p.mapRings[ringFirst];
+                const unsigned nA = (unsigned)uni((int)R.vertex_count), offA = (unsigned)uni((int)R.vertex_offset);
+                const unsigned nB = (unsigned)uni((int)m.vertex_count), offB = (unsigned)uni((int)m.vertex_offset);
+                const unsigned cap = (unsigned)p.boundaryCapacity;
+                if (nA > (unsigned)kUnionRing || nB > (unsigned)kUnionRing || nA < 3u || nB < 3u || (unsigned long long)offA + nA > p.nMapVertices ||
+                    offB > cap || nB > cap - offB)
+                    res.flags = CAPE_UNION_HOST_CAPACITY;
+                else
+                {
+                    const double2* srcA = p.mapVertices + offA;
+                    const double2* srcB = p.worldVertices + (size_t)rec * cap + offB;
+                    UnionFrame fa, fb, target;
+                    load_map_pair(L, srcA, nA, srcB, nB, M, m, fusion[i], fa, fb, target, lane);
+                    res = union_pair(L, (int)nA, (int)nB, fa, fb, target, frameOut, lane);
+                }
+            }
+            used = put_pair(res, frameOut, j, rows + i, slab, used, CAPE_MAP_UNION_FRAME_VERTICES, lane);
+            CAPE_MP_SYNC(); // (the next pair rewrites the carve)
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void cape_ring_union_kernel(RingUnionParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const UnionLds L = union_carve(smem);
+    const int lane = threadIdx.x & 63;
+    UnionResult res{};
+    UnionFrame frameOut{};
+    if (p.nA > kUnionRing || p.nB > kUnionRing || p.nA < 3 || p.nB < 3)
+        res.flags = CAPE_UNION_HOST_CAPACITY;
+    else
+    {
+        UnionFrame fa, fb, target;
+        load_debug_pair(L, p.ringA, p.nA, p.ringB, p.nB, p.frames27, fa, fb, target, lane);
+        res = union_pair(L, p.nA, p.nB, fa, fb, target, frameOut, lane);
+    }
+    (void)put_pair(res, frameOut, 0, p.row, p.vertices, 0u, CAPE_MAP_MAX_RING, lane);
+}
+
 // The holes mode of the frame kernel: the walk above, with the map plane's interior rings described to union_pair_holes (every
 // count and offset checked here) and the rings rows written beside the rows.
 __global__ __launch_bounds__(64) void cape_map_union_holes_kernel(MapUnionParams p, cape_plane_union_rings* ringRowsAll, int nFrames)
@@ -343,16 +357,9 @@ __global__ __launch_bounds__(64) void cape_map_union_holes_kernel(MapUnionParams
                 const unsigned nA = (unsigned)uni((int)R.vertex_count), offA = (unsigned)uni((int)R.vertex_offset);
                 const double2* srcA = p.mapVertices + offA;
                 const double2* srcB = p.worldVertices + (size_t)rec * cap + offB;
-                for (unsigned v = lane; v < nA; v += 64)
-                    L.ringA[v] = srcA[v];
-                for (unsigned v = lane; v < nB; v += 64)
-                    L.ringB[v] = srcB[v];
-                CAPE_MP_SYNC();
                 H.nSrc = (int)ringCount - 1;
                 UnionFrame fa, fb, target;
-                load_frame(fa, M.x_axis, M.y_axis, M.center);
-                load_frame(fb, m.x_axis, m.y_axis, m.center);
-                load_frame(target, fusion[i].x_axis, fusion[i].y_axis, fusion[i].center);
+                load_map_pair(L, srcA, nA, srcB, nB, M, m, fusion[i], fa, fb, target, lane);
                 res = union_pair_holes(L, H, (int)nA, (int)nB, fa, fb, target, frameOut, holes, lane);
             }
             used = put_pair_holes(res, holes, H, frameOut, j, rows + i, ringRows + i, slab, used, CAPE_MAP_UNION_FRAME_VERTICES, lane);
@@ -391,17 +398,10 @@ __global__ __launch_bounds__(64) void cape_polygon_union_kernel(PolygonUnionPara
     else
     {
         const int nA = uni(p.countsA[0]);
-        for (int v = lane; v < nA; v += 64)
-            L.ringA[v] = p.ringsA[v];
-        for (int v = lane; v < p.nB; v += 64)
-            L.ringB[v] = p.ringB[v];
-        CAPE_MP_SYNC();
         H.src = p.ringsA;
         H.nSrc = p.nRingsA - 1;
         UnionFrame fa, fb, target;
-        load_frame(fa, p.frames27, p.frames27 + 3, p.frames27 + 6);
-        load_frame(fb, p.frames27 + 9, p.frames27 + 12, p.frames27 + 15);
-        load_frame(target, p.frames27 + 18, p.frames27 + 21, p.frames27 + 24);
+        load_debug_pair(L, p.ringsA, nA, p.ringB, p.nB, p.frames27, fa, fb, target, lane);
         res = union_pair_holes(L, H, nA, p.nB, fa, fb, target, frameOut, holes, lane);
     }
     (void)put_pair_holes(res, holes, H, frameOut, 0, p.row, p.ringRow, p.vertices, 0u, CAPE_MAP_UNION_FRAME_VERTICES, lane);

@@ -33,7 +33,9 @@ using rgbd_slam::vector3;
 static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
 // ---- The per-pair order of statements of csrc/cape_map_union.h's union_pair, one lane at a time: the same per-lane functions in the
-// same order (the cut list in pair order instead of ballot order, which the sort makes irrelevant).  Four loops keep the wave's
+// same order (the cut list in pair order instead of ballot order, which the sort makes irrelevant).  What the device's two modes have in common
+// stands once here: seq::Arrangement and seq::dp_candidate also serve holes::pair of map_union_holes_algebra.cpp, which includes
+// this file.  Four loops keep the wave's
 // shape, 64 lanes at a time, because their chunking decides the result: the rank sort of the cuts, ring_is_simple's rounds with
 // every other one reversed, drop_collinear's erase and the Douglas-Peucker reduction with its tie rule.  It checks that the
 // restatement -- cuts ranked on their bit patterns, edges marked seen while they are walked, a hole judged as soon as its face is
@@ -42,6 +44,7 @@ static bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof a)
 // barriers, LDS) are the GPU tests'.
 namespace seq {
 using cape::usame;
+typedef std::vector<double2> Ring2;
 struct Out
 {
     uint32_t flags = 0;
@@ -123,14 +126,11 @@ static void drop(std::vector<double2>& r)
             }
     }
 }
-static void simplify(std::vector<double2>& ring, double& area)
+// union_dp_candidate: the closed ring, the lanes' first largest, the lowest index among the lanes that hold the wave's largest
+static Ring2 dp_candidate(const Ring2& ring, double eps)
 {
-    area = area_of(ring);
     const int n = (int)ring.size();
-    if (n < 4)
-        return;
-    const double eps = cape::umax(area / 1e5, 10.0);
-    std::vector<double2> closed = ring;
+    Ring2 closed = ring;
     closed.push_back(ring[0]);
     std::vector<char> keep(n + 1, 0);
     keep[0] = keep[n] = 1;
@@ -170,10 +170,18 @@ static void simplify(std::vector<double2>& ring, double& area)
             stack.push_back({idx, b});
         }
     }
-    std::vector<double2> cand;
+    Ring2 cand;
     for (int i = 0; i < n; ++i)
         if (keep[i])
             cand.push_back(closed[i]);
+    return cand;
+}
+static void simplify(Ring2& ring, double& area)
+{
+    area = area_of(ring);
+    if (ring.size() < 4)
+        return;
+    const Ring2 cand = dp_candidate(ring, cape::umax(area / 1e5, 10.0));
     if (cand.size() >= 3 && simple(cand))
     {
         const double newArea = area_of(cand);
@@ -184,115 +192,124 @@ static void simplify(std::vector<double2>& ring, double& area)
         }
     }
 }
-// A, B: both operands in one frame, oriented
-static Out pair(std::vector<double2> A, std::vector<double2> B)
+// is every vertex of q outside `outer` (not inside, not on it)?  union_left_out
+static bool left_out(const Ring2& q, const Ring2& outer)
 {
-    const int kDeg = 8, kNodes = 512, kOut = 512;
-    Out out;
-    out.flags = CAPE_UNION_SERVED | CAPE_UNION_UNCHANGED;
-    out.ring = A;
-    out.area = area_of(A);
-    const int nA = (int)A.size(), nB = (int)B.size();
-    double scale = 1.0;
-    for (const auto* r : {&A, &B})
-        for (const double2& p : *r)
-            scale = cape::umax(scale, cape::umax(std::fabs(p.x), std::fabs(p.y)));
-    const double eps = 1e-9 * scale;
-    struct Seg { double2 a, b; };
-    std::vector<Seg> segs;
-    int nSegA = 0;
-    for (int r = 0; r < 2; ++r)
-    {
-        const auto& R = r ? B : A;
-        for (size_t i = 0; i < R.size(); ++i)
-            if (!usame(R[i], R[(i + 1) % R.size()], eps))
-                segs.push_back({R[i], R[(i + 1) % R.size()]});
-        if (r == 0)
-            nSegA = (int)segs.size();
-    }
-    struct Cut { unsigned seg; uint64_t t; };
-    std::vector<Cut> cuts;
-    auto push = [&](unsigned seg, double t) {
-        uint64_t b;
-        std::memcpy(&b, &t, sizeof b);
-        cuts.push_back({seg, b});
-    };
-    for (int i = 0; i < nSegA; ++i)
-        for (int j = nSegA; j < (int)segs.size(); ++j)
-        {
-            const Seg &s = segs[i], &u = segs[j];
-            double t;
-            if (cape::union_param_on(s.a, s.b, u.a, eps, t)) push(i, t);
-            if (cape::union_param_on(s.a, s.b, u.b, eps, t)) push(i, t);
-            if (cape::union_param_on(u.a, u.b, s.a, eps, t)) push(j, t);
-            if (cape::union_param_on(u.a, u.b, s.b, eps, t)) push(j, t);
-            double ts, tu;
-            bool ks, ku;
-            if (cape::union_crossing(s.a, s.b, u.a, u.b, eps, ts, ks, tu, ku))
-            {
-                if (ks) push(i, ts);
-                if (ku) push(j, tu);
-            }
-        }
-    // the device's rank sort, statement for statement: a cut's place is the number of cuts before it in (segment, parameter, arrival)
-    // order.  A slot no cut claims keeps a segment that does not exist, which ends the node numbering early.
-    {
-        std::vector<Cut> sorted(cuts.size(), Cut {0xFFFFu, ~0ull});
-        for (size_t c = 0; c < cuts.size(); ++c)
-        {
-            size_t rank = 0;
-            for (size_t k = 0; k < cuts.size(); ++k)
-                rank += (cuts[k].seg < cuts[c].seg || (cuts[k].seg == cuts[c].seg && (cuts[k].t < cuts[c].t || (cuts[k].t == cuts[c].t && k < c)))) ? 1 : 0;
-            sorted[rank] = cuts[c];
-        }
-        cuts = sorted;
-    }
-    std::vector<double2> nodes;
+    for (const double2& p : q)
+        if (in_ring(p, outer, true))
+            return false;
+    return true;
+}
+
+// The arrangement of both modes (step 3 of union_pair and union_pair_holes with union_node_of, union_link, union_next_of and
+// union_walk_face, the start of the outer walk and the test of a walked face): seq::pair and holes::pair both run it, so an edit to
+// the order of the device's statements is mirrored here once.
+struct Arrangement
+{
+    static constexpr int kDeg = 8, kNodes = 512, kOut = 512, kCuts = 1024;
+    double eps = 0;
+    std::vector<double2> nodes; // counted on, not capped, beyond kNodes
     std::vector<std::vector<int>> adj;
-    bool capacity = false;
-    auto node_of = [&](const double2& p) {
+    std::vector<unsigned> seen; // bit k: the directed edge to neighbour k has been walked
+    bool capacity = false, ambiguous = false;
+
+    int node_of(const double2& p)
+    {
         for (size_t k = 0; k < nodes.size(); ++k)
             if (usame(nodes[k], p, eps))
                 return (int)k;
+        capacity = capacity || (int)nodes.size() >= kNodes;
         nodes.push_back(p);
         adj.emplace_back();
-        capacity = capacity || (int)nodes.size() > kNodes;
         return (int)nodes.size() - 1;
-    };
-    auto link = [&](int a, int b) {
-        if (a == b)
-            return;
-        if (std::find(adj[a].begin(), adj[a].end(), b) != adj[a].end())
+    }
+    void link(int a, int b)
+    {
+        if (a == b || std::find(adj[a].begin(), adj[a].end(), b) != adj[a].end())
             return;
         adj[a].push_back(b);
         adj[b].push_back(a);
         capacity = capacity || (int)adj[a].size() > kDeg || (int)adj[b].size() > kDeg;
-    };
-    size_t at = 0;
-    for (size_t s = 0; s < segs.size(); ++s)
-    {
-        int prev = node_of(segs[s].a);
-        for (; at < cuts.size() && cuts[at].seg == s; ++at)
-        {
-            double t;
-            std::memcpy(&t, &cuts[at].t, sizeof t);
-            const int cur = node_of(cape::union_cut_point(segs[s].a, segs[s].b, t));
-            link(prev, cur);
-            prev = cur;
-        }
-        link(prev, node_of(segs[s].b));
     }
-    out.nNodes = (int)nodes.size();
-    const auto hosted = [&](uint32_t f) {
-        Out o;
-        o.flags = f;
-        o.nNodes = (int)nodes.size();
-        return o;
-    };
-    if (capacity)
-        return hosted(CAPE_UNION_HOST_CAPACITY);
-    bool ambiguous = false;
-    auto next_of = [&](int v, const double2& back, int from) {
+    // A, B: both operands in one frame, oriented.  False when the cuts outgrow their list (nothing is numbered then).
+    bool build(const Ring2& A, const Ring2& B)
+    {
+        double scale = 1.0;
+        for (const auto* r : {&A, &B})
+            for (const double2& p : *r)
+                scale = cape::umax(scale, cape::umax(std::fabs(p.x), std::fabs(p.y)));
+        eps = 1e-9 * scale;
+        struct Seg { double2 a, b; };
+        std::vector<Seg> segs;
+        int nSegA = 0;
+        for (int r = 0; r < 2; ++r)
+        {
+            const auto& R = r ? B : A;
+            for (size_t i = 0; i < R.size(); ++i)
+                if (!usame(R[i], R[(i + 1) % R.size()], eps))
+                    segs.push_back({R[i], R[(i + 1) % R.size()]});
+            if (r == 0)
+                nSegA = (int)segs.size();
+        }
+        // the cuts in pair order instead of ballot order, which the sort makes irrelevant
+        struct Cut { unsigned seg; uint64_t t; };
+        std::vector<Cut> cuts;
+        auto push = [&](unsigned seg, double t) {
+            uint64_t b;
+            std::memcpy(&b, &t, sizeof b);
+            cuts.push_back({seg, b});
+        };
+        for (int i = 0; i < nSegA; ++i)
+            for (int j = nSegA; j < (int)segs.size(); ++j)
+            {
+                const Seg &s = segs[i], &u = segs[j];
+                double t;
+                if (cape::union_param_on(s.a, s.b, u.a, eps, t)) push(i, t);
+                if (cape::union_param_on(s.a, s.b, u.b, eps, t)) push(i, t);
+                if (cape::union_param_on(u.a, u.b, s.a, eps, t)) push(j, t);
+                if (cape::union_param_on(u.a, u.b, s.b, eps, t)) push(j, t);
+                double ts, tu;
+                bool ks, ku;
+                if (cape::union_crossing(s.a, s.b, u.a, u.b, eps, ts, ks, tu, ku))
+                {
+                    if (ks) push(i, ts);
+                    if (ku) push(j, tu);
+                }
+            }
+        if ((int)cuts.size() > kCuts)
+            return false;
+        // the device's rank sort, statement for statement: a cut's place is the number of cuts before it in (segment, parameter,
+        // arrival) order.  A slot no cut claims keeps a segment that does not exist, which ends the node numbering early.
+        {
+            std::vector<Cut> sorted(cuts.size(), Cut {0xFFFFu, ~0ull});
+            for (size_t c = 0; c < cuts.size(); ++c)
+            {
+                size_t rank = 0;
+                for (size_t k = 0; k < cuts.size(); ++k)
+                    rank += (cuts[k].seg < cuts[c].seg || (cuts[k].seg == cuts[c].seg && (cuts[k].t < cuts[c].t || (cuts[k].t == cuts[c].t && k < c)))) ? 1 : 0;
+                sorted[rank] = cuts[c];
+            }
+            cuts = sorted;
+        }
+        size_t at = 0;
+        for (size_t s = 0; s < segs.size(); ++s)
+        {
+            int prev = node_of(segs[s].a);
+            for (; at < cuts.size() && cuts[at].seg == s; ++at)
+            {
+                double t;
+                std::memcpy(&t, &cuts[at].t, sizeof t);
+                const int cur = node_of(cape::union_cut_point(segs[s].a, segs[s].b, t));
+                link(prev, cur);
+                prev = cur;
+            }
+            link(prev, node_of(segs[s].b));
+        }
+        seen.assign(nodes.size(), 0);
+        return true;
+    }
+    int next_of(int v, const double2& back, int from)
+    {
         const double ba = std::atan2(back.y, back.x);
         int best = -1;
         double bestAngle = 1e300;
@@ -309,9 +326,10 @@ static Out pair(std::vector<double2> A, std::vector<double2> B)
         for (size_t k = 0; k < angs.size(); ++k)
             ambiguous = ambiguous || ((int)k != best && std::fabs(angs[k] - bestAngle) < cape::kUnionAngleBand);
         return best;
-    };
-    std::vector<unsigned> seen(nodes.size(), 0);
-    auto walk = [&](int from, int slot, std::vector<double2>& ring) {
+    }
+    // the face the directed edge (from -> its neighbour in slot `slot`) has on its right; edges are marked seen while they are walked
+    bool walk(int from, int slot, Ring2& ring)
+    {
         ring.clear();
         const int to = adj[from][slot];
         int cur = from, nxt = to, curSlot = slot;
@@ -331,64 +349,91 @@ static Out pair(std::vector<double2> A, std::vector<double2> B)
                 return true;
         }
         return false;
-    };
-    std::vector<double2> outer;
-    bool newHole = false;
-    if (nodes.size() >= 3)
+    }
+    // the lowest of the leftmost nodes, left heading south: the slot of the outer walk's first neighbour
+    int start_slot(int& start)
     {
-        int start = 0;
+        start = 0;
         for (size_t k = 1; k < nodes.size(); ++k)
             if (nodes[k].x < nodes[start].x - eps || (std::fabs(nodes[k].x - nodes[start].x) <= eps && nodes[k].y < nodes[start].y))
                 start = (int)k;
-        const int first = next_of(start, make_double2(0.0, 1.0), -1);
+        return next_of(start, make_double2(0.0, 1.0), -1);
+    }
+    // a hole judged as soon as its face is known: bounded, its inside in neither operand, then merge_union's own test after `drop`
+    bool face_is_hole(Ring2& face, const Ring2& A, const Ring2& B) const
+    {
+        if (face.size() < 3 || signed_area(face) >= 0)
+            return false;
+        bool found = false;
+        double2 probe = make_double2(0, 0);
+        for (size_t i = 0; i < face.size() && !found; ++i)
+        {
+            const double2 p = face[i], q = face[(i + 1) % face.size()];
+            const double dx = q.x - p.x, dy = q.y - p.y, len = std::hypot(dx, dy);
+            if (len <= eps)
+                continue;
+            for (double off = 1e-3; off >= 1e-7 && !found; off *= 0.1)
+            {
+                probe = make_double2(0.5 * (p.x + q.x) + off * len * (dy / len), 0.5 * (p.y + q.y) - off * len * (dx / len));
+                found = in_ring(probe, face, false);
+            }
+        }
+        if (!found || in_ring(probe, A, true) || in_ring(probe, B, true))
+            return false;
+        drop(face);
+        return face.size() >= 3 && simple(face);
+    }
+};
+
+// union_pair.  A, B: both operands in one frame, oriented
+static Out pair(Ring2 A, Ring2 B)
+{
+    Out out;
+    out.flags = CAPE_UNION_SERVED | CAPE_UNION_UNCHANGED;
+    out.ring = A;
+    out.area = area_of(A);
+    Arrangement G;
+    const auto hosted = [&](uint32_t f) {
+        Out o;
+        o.flags = f;
+        o.nNodes = (int)G.nodes.size();
+        return o;
+    };
+    if (!G.build(A, B))
+        return hosted(CAPE_UNION_HOST_CAPACITY);
+    out.nNodes = (int)G.nodes.size();
+    if (G.capacity)
+        return hosted(CAPE_UNION_HOST_CAPACITY);
+    Ring2 outer;
+    bool newHole = false;
+    if (G.nodes.size() >= 3)
+    {
+        int start = 0;
+        const int first = G.start_slot(start);
         if (first >= 0)
         {
-            if (!walk(start, first, outer))
+            if (!G.walk(start, first, outer))
                 return hosted(CAPE_UNION_HOST_CAPACITY);
-            std::vector<double2> face;
-            for (size_t a = 0; a < nodes.size() && !outer.empty(); ++a)
-                for (size_t k = 0; k < adj[a].size(); ++k)
+            Ring2 face;
+            for (size_t a = 0; a < G.nodes.size() && !outer.empty(); ++a)
+                for (size_t k = 0; k < G.adj[a].size(); ++k)
                 {
-                    if ((seen[a] >> k) & 1u)
+                    if ((G.seen[a] >> k) & 1u)
                         continue;
-                    if (!walk((int)a, (int)k, face))
+                    if (!G.walk((int)a, (int)k, face))
                         return hosted(CAPE_UNION_HOST_CAPACITY);
-                    if (face.size() < 3 || signed_area(face) >= 0)
-                        continue;
-                    bool found = false;
-                    double2 probe = make_double2(0, 0);
-                    for (size_t i = 0; i < face.size() && !found; ++i)
-                    {
-                        const double2 p = face[i], q = face[(i + 1) % face.size()];
-                        const double dx = q.x - p.x, dy = q.y - p.y, len = std::hypot(dx, dy);
-                        if (len <= eps)
-                            continue;
-                        for (double off = 1e-3; off >= 1e-7 && !found; off *= 0.1)
-                        {
-                            probe = make_double2(0.5 * (p.x + q.x) + off * len * (dy / len), 0.5 * (p.y + q.y) - off * len * (dx / len));
-                            found = in_ring(probe, face, false);
-                        }
-                    }
-                    if (!found || in_ring(probe, A, true) || in_ring(probe, B, true))
-                        continue;
-                    drop(face);
-                    newHole = newHole || (face.size() >= 3 && simple(face));
+                    if (G.face_is_hole(face, A, B))
+                        newHole = true;
                 }
         }
     }
-    if (ambiguous)
+    if (G.ambiguous)
         return hosted(CAPE_UNION_HOST_AMBIGUOUS);
     if (!outer.empty())
         drop(outer);
     const double outerArea = outer.size() >= 3 ? std::abs(signed_area(outer)) : 0.0;
     const double areaA = std::abs(signed_area(A)), areaB = std::abs(signed_area(B));
-    auto left_out = [&](const std::vector<double2>& q) {
-        for (const double2& p : q)
-            if (in_ring(p, outer, true))
-                return false;
-        return true;
-    };
-    bool disjoint = outer.size() >= 3 && (left_out(A) || left_out(B)), rule = false;
+    bool disjoint = outer.size() >= 3 && (left_out(A, outer) || left_out(B, outer)), rule = false;
     if (outerArea + 1e-9 * cape::umax(areaA, areaB) < cape::umax(areaA, areaB))
     {
         disjoint = rule = true;
@@ -413,8 +458,6 @@ static Out pair(std::vector<double2> A, std::vector<double2> B)
     out.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u);
     out.ring = outer;
     simplify(out.ring, out.area);
-    (void)nA;
-    (void)nB;
     return out;
 }
 } // namespace seq

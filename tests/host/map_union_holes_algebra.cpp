@@ -2,7 +2,8 @@
 // host/boundary_polygon.cpp's merge_union and simplify on map polygons that have interior rings and unions that create some, under the
 // address and undefined-behaviour sanitizers.  A stand-alone program.  tests/host/map_union_algebra.cpp is included as text with its
 // main renamed: it brings the host class (boundary_polygon.cpp as text), the plain per-lane functions of the device header over
-// tests/host/hip_stub, the lane-shaped loops of the port of the mode without holes (seq::simple, seq::drop, seq::in_ring) and the ring
+// tests/host/hip_stub, what the port of the mode without holes shares with this one, as the device header shares it (seq::Arrangement
+// with the rank sort, the walks and the face test, seq::dp_candidate, seq::simple, seq::drop, seq::in_ring) and the ring
 // generators of the Python tables (named::).  New here, in the device's order of statements: the faces that become holes, stored in
 // face-walk order and oriented like add_hole; Polygon::area() in the disjoint rule; the carried holes with the bounding-box test of the
 // device header (union_boxes_apart, compiled here, like union_point_in_or_on of simplify's in-ring check) in front of the host's rings_inter_area, which the device restates elsewhere
@@ -20,11 +21,12 @@
 
 namespace holes {
 using seq::area_of;
+using seq::dp_candidate;
 using seq::drop;
 using seq::in_ring;
 using seq::signed_area;
 using seq::simple;
-typedef std::vector<double2> Ring2;
+using seq::Ring2;
 const int kHoles = CAPE_MAP_MAX_HOLES, kHoleVertices = CAPE_MAP_UNION_HOLE_VERTICES;
 
 struct Out
@@ -56,54 +58,6 @@ static size_t vertices_of(const std::vector<Ring2>& hs)
         n += h.size();
     return n;
 }
-// union_dp_candidate: the closed ring, the lanes' first largest, the lowest index among the lanes that hold the wave's largest
-static Ring2 dp_candidate(const Ring2& ring, double eps)
-{
-    const int n = (int)ring.size();
-    Ring2 closed = ring;
-    closed.push_back(ring[0]);
-    std::vector<char> keep(n + 1, 0);
-    keep[0] = keep[n] = 1;
-    std::vector<std::pair<int, int>> stack {{0, n}};
-    while (!stack.empty())
-    {
-        const auto [a, b] = stack.back();
-        stack.pop_back();
-        if (b <= a + 1)
-            continue;
-        uint64_t laneBest[64] = {}, best = 0;
-        int laneIdx[64], idx = 0x7FFFFFFF;
-        for (int lane = 0; lane < 64; ++lane)
-        {
-            laneIdx[lane] = 0x7FFFFFFF;
-            for (int i = a + 1 + lane; i < b; i += 64)
-            {
-                const double d = cape::union_segment_distance2(closed[i], closed[a], closed[b]);
-                uint64_t db;
-                std::memcpy(&db, &d, sizeof db);
-                if (laneIdx[lane] == 0x7FFFFFFF || db > laneBest[lane])
-                    laneBest[lane] = db, laneIdx[lane] = i;
-            }
-            best = std::max(best, laneBest[lane]);
-        }
-        for (int lane = 0; lane < 64; ++lane)
-            if (laneIdx[lane] != 0x7FFFFFFF && laneBest[lane] == best)
-                idx = std::min(idx, laneIdx[lane]);
-        double dmax;
-        std::memcpy(&dmax, &best, sizeof dmax);
-        if (dmax > eps * eps && idx > a && idx < b)
-        {
-            keep[idx] = 1;
-            stack.push_back({a, idx});
-            stack.push_back({idx, b});
-        }
-    }
-    Ring2 cand;
-    for (int i = 0; i < n; ++i)
-        if (keep[i])
-            cand.push_back(closed[i]);
-    return cand;
-}
 // union_simplify_holed
 static void simplify_holed(Ring2& ring, std::vector<Ring2>& hs, double& area)
 {
@@ -134,178 +88,39 @@ static void simplify_holed(Ring2& ring, std::vector<Ring2>& hs, double& area)
     }
 }
 
-// union_pair_holes: A, B oriented in one frame, mapHoles as the (projected) map polygon holds them
+// union_pair_holes: A, B oriented in one frame, mapHoles as the (projected) map polygon holds them.  The arrangement, the walks and
+// the face test are seq::Arrangement's, as on the device; what is the mode's own stands here.
 static Out pair(Ring2 A, Ring2 B, const std::vector<Ring2>& mapHoles)
 {
-    const int kDeg = 8, kNodes = 512, kOut = 512;
     Out out;
     const auto hosted = [](uint32_t f) {
         Out o;
         o.flags = f;
         return o;
     };
-    double scale = 1.0;
-    for (const auto* r : {&A, &B})
-        for (const double2& p : *r)
-            scale = cape::umax(scale, cape::umax(std::fabs(p.x), std::fabs(p.y)));
-    const double eps = 1e-9 * scale;
-    struct Seg { double2 a, b; };
-    std::vector<Seg> segs;
-    int nSegA = 0;
-    for (int r = 0; r < 2; ++r)
-    {
-        const auto& R = r ? B : A;
-        for (size_t i = 0; i < R.size(); ++i)
-            if (!cape::usame(R[i], R[(i + 1) % R.size()], eps))
-                segs.push_back({R[i], R[(i + 1) % R.size()]});
-        if (r == 0)
-            nSegA = (int)segs.size();
-    }
-    struct Cut { unsigned seg; uint64_t t; };
-    std::vector<Cut> cuts;
-    auto push = [&](unsigned seg, double t) {
-        uint64_t b;
-        std::memcpy(&b, &t, sizeof b);
-        cuts.push_back({seg, b});
-    };
-    for (int i = 0; i < nSegA; ++i)
-        for (int j = nSegA; j < (int)segs.size(); ++j)
-        {
-            const Seg &s = segs[i], &u = segs[j];
-            double t;
-            if (cape::union_param_on(s.a, s.b, u.a, eps, t)) push(i, t);
-            if (cape::union_param_on(s.a, s.b, u.b, eps, t)) push(i, t);
-            if (cape::union_param_on(u.a, u.b, s.a, eps, t)) push(j, t);
-            if (cape::union_param_on(u.a, u.b, s.b, eps, t)) push(j, t);
-            double ts, tu;
-            bool ks, ku;
-            if (cape::union_crossing(s.a, s.b, u.a, u.b, eps, ts, ks, tu, ku))
-            {
-                if (ks) push(i, ts);
-                if (ku) push(j, tu);
-            }
-        }
-    if (cuts.size() > 1024)
+    seq::Arrangement G;
+    if (!G.build(A, B) || G.capacity)
         return hosted(CAPE_UNION_HOST_CAPACITY);
-    std::stable_sort(cuts.begin(), cuts.end(), [](const Cut& l, const Cut& r) { return l.seg < r.seg || (l.seg == r.seg && l.t < r.t); });
-    std::vector<double2> nodes;
-    std::vector<std::vector<int>> adj;
-    bool capacity = false;
-    auto node_of = [&](const double2& p) {
-        for (size_t k = 0; k < nodes.size(); ++k)
-            if (cape::usame(nodes[k], p, eps))
-                return (int)k;
-        nodes.push_back(p);
-        adj.emplace_back();
-        capacity = capacity || (int)nodes.size() > kNodes;
-        return (int)nodes.size() - 1;
-    };
-    auto link = [&](int a, int b) {
-        if (a == b || std::find(adj[a].begin(), adj[a].end(), b) != adj[a].end())
-            return;
-        adj[a].push_back(b);
-        adj[b].push_back(a);
-        capacity = capacity || (int)adj[a].size() > kDeg || (int)adj[b].size() > kDeg;
-    };
-    size_t at = 0;
-    for (size_t s = 0; s < segs.size(); ++s)
-    {
-        int prev = node_of(segs[s].a);
-        for (; at < cuts.size() && cuts[at].seg == s; ++at)
-        {
-            double t;
-            std::memcpy(&t, &cuts[at].t, sizeof t);
-            const int cur = node_of(cape::union_cut_point(segs[s].a, segs[s].b, t));
-            link(prev, cur);
-            prev = cur;
-        }
-        link(prev, node_of(segs[s].b));
-    }
-    if (capacity)
-        return hosted(CAPE_UNION_HOST_CAPACITY);
-    bool ambiguous = false;
-    auto next_of = [&](int v, const double2& back, int from) {
-        const double ba = std::atan2(back.y, back.x);
-        int best = -1;
-        double bestAngle = 1e300;
-        std::vector<double> angs;
-        for (size_t k = 0; k < adj[v].size(); ++k)
-        {
-            const int w = adj[v][k];
-            const double dx = nodes[w].x - nodes[v].x, dy = nodes[w].y - nodes[v].y;
-            const double ang = cape::union_angle(dy, dx, ba, w == from || cape::union_axis_parallel(dx, dy, back.x, back.y), ambiguous);
-            angs.push_back(ang);
-            if (ang < bestAngle)
-                bestAngle = ang, best = (int)k;
-        }
-        for (size_t k = 0; k < angs.size(); ++k)
-            ambiguous = ambiguous || ((int)k != best && std::fabs(angs[k] - bestAngle) < cape::kUnionAngleBand);
-        return best;
-    };
-    std::vector<unsigned> seen(nodes.size(), 0);
-    auto walk = [&](int from, int slot, Ring2& ring) {
-        ring.clear();
-        const int to = adj[from][slot];
-        int cur = from, nxt = to, curSlot = slot;
-        for (size_t guard = 0; guard < 4 * nodes.size() + 8; ++guard)
-        {
-            if ((int)ring.size() >= kOut)
-                return false;
-            ring.push_back(nodes[cur]);
-            seen[cur] |= 1u << curSlot;
-            const int after = next_of(nxt, make_double2(nodes[cur].x - nodes[nxt].x, nodes[cur].y - nodes[nxt].y), cur);
-            if (after < 0)
-                return false;
-            cur = nxt;
-            nxt = adj[cur][after];
-            curSlot = after;
-            if (cur == from && nxt == to)
-                return true;
-        }
-        return false;
-    };
     Ring2 outer;
     std::vector<Ring2> stored; // the faces that are holes, while they fit; all of them counted
     int nNew = 0, newVertices = 0;
-    if (nodes.size() >= 3)
+    if (G.nodes.size() >= 3)
     {
         int start = 0;
-        for (size_t k = 1; k < nodes.size(); ++k)
-            if (nodes[k].x < nodes[start].x - eps || (std::fabs(nodes[k].x - nodes[start].x) <= eps && nodes[k].y < nodes[start].y))
-                start = (int)k;
-        const int first = next_of(start, make_double2(0.0, 1.0), -1);
+        const int first = G.start_slot(start);
         if (first >= 0)
         {
-            if (!walk(start, first, outer))
+            if (!G.walk(start, first, outer))
                 return hosted(CAPE_UNION_HOST_CAPACITY);
             Ring2 face;
-            for (size_t a = 0; a < nodes.size() && !outer.empty(); ++a)
-                for (size_t k = 0; k < adj[a].size(); ++k)
+            for (size_t a = 0; a < G.nodes.size() && !outer.empty(); ++a)
+                for (size_t k = 0; k < G.adj[a].size(); ++k)
                 {
-                    if ((seen[a] >> k) & 1u)
+                    if ((G.seen[a] >> k) & 1u)
                         continue;
-                    if (!walk((int)a, (int)k, face))
+                    if (!G.walk((int)a, (int)k, face))
                         return hosted(CAPE_UNION_HOST_CAPACITY);
-                    if (face.size() < 3 || signed_area(face) >= 0)
-                        continue;
-                    bool found = false;
-                    double2 probe = make_double2(0, 0);
-                    for (size_t i = 0; i < face.size() && !found; ++i)
-                    {
-                        const double2 p = face[i], q = face[(i + 1) % face.size()];
-                        const double dx = q.x - p.x, dy = q.y - p.y, len = std::hypot(dx, dy);
-                        if (len <= eps)
-                            continue;
-                        for (double off = 1e-3; off >= 1e-7 && !found; off *= 0.1)
-                        {
-                            probe = make_double2(0.5 * (p.x + q.x) + off * len * (dy / len), 0.5 * (p.y + q.y) - off * len * (dx / len));
-                            found = in_ring(probe, face, false);
-                        }
-                    }
-                    if (!found || in_ring(probe, A, true) || in_ring(probe, B, true))
-                        continue;
-                    drop(face);
-                    if (face.size() >= 3 && simple(face))
+                    if (G.face_is_hole(face, A, B))
                     {
                         if (nNew < kHoles && newVertices + (int)face.size() <= kHoleVertices)
                         {
@@ -318,19 +133,13 @@ static Out pair(Ring2 A, Ring2 B, const std::vector<Ring2>& mapHoles)
                 }
         }
     }
-    if (ambiguous)
+    if (G.ambiguous)
         return hosted(CAPE_UNION_HOST_AMBIGUOUS);
     if (!outer.empty())
         drop(outer);
     const double outerArea = outer.size() >= 3 ? std::abs(signed_area(outer)) : 0.0;
     const double areaA = std::abs(signed_area(A)), areaB = std::abs(signed_area(B));
-    auto left_out = [&](const Ring2& q) {
-        for (const double2& p : q)
-            if (in_ring(p, outer, true))
-                return false;
-        return true;
-    };
-    bool disjoint = outer.size() >= 3 && (left_out(A) || left_out(B)), rule = false;
+    bool disjoint = outer.size() >= 3 && (seq::left_out(A, outer) || seq::left_out(B, outer)), rule = false;
     if (outerArea + 1e-9 * cape::umax(areaA, areaB) < cape::umax(areaA, areaB))
     {
         disjoint = rule = true;
