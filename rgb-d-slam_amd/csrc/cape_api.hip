@@ -67,6 +67,7 @@ struct Knobs
     bool noResume = false;    // CAPE_RESUME=off or CAPE_NO_RESUME: every handed-over frame is grown again from scratch
     int schedule = 0;         // CAPE_SCHEDULE=two|single: 1 = always two-pass, 2 = always single (cape_handle_s::Chain::forcedSchedule)
     std::string stageA;       // CAPE_STAGE_A=strips|bands (see cape_handle_s::Chain::stripCounters)
+    std::string a1;           // CAPE_A1=cells|bands: the instance of the streaming kernel A1 (StageAParams::a1Bands)
     bool growGeneral = false; // CAPE_GROW=general|fast: general sends every frame through the general instance
     bool pinnedByDma = false; // CAPE_PINNED_INPUT=dma (cape_handle_s::Chain::pinnedByDma)
     int a2WideBatch = 0;      // CAPE_A2_WIDE_BATCH=n: the one-tile stage-A2 instance for batches <= n (cell_plane_threads)
@@ -90,6 +91,8 @@ int read_knobs(Knobs& k)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_SCHEDULE must be two or single");
     if (!one_of("CAPE_STAGE_A", {"strips", "bands"}, k.stageA))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_STAGE_A must be strips or bands");
+    if (!one_of("CAPE_A1", {"cells", "bands"}, k.a1))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_A1 must be cells or bands");
     if (!one_of("CAPE_GROW", {"general", "fast"}, grow))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_GROW must be general or fast");
     k.noResume = k.resume == "off" || std::getenv("CAPE_NO_RESUME");
@@ -431,6 +434,7 @@ int cape_create(const cape_config* cfg, cape_handle* out)
     a.sinMerge = sinf(static_cast<float>(18.0f * M_PI / 180.0));
     a.cosMergeA = std::cos(static_cast<double>(18.0f) * M_PI / 180.0); // plane_segment.cpp:324
     a.smallBatchFrames = knobs.a2WideBatch; // see cell_plane_threads()
+    a.a1Bands = knobs.a1 == "bands" ? 1 : 0;
     // plane_segment.hpp:33-34 ; parameters.hpp:72 minimumZeroDepthProportion = 0.7f
     a.minZeroPointCount = static_cast<int>(std::floor(static_cast<float>(400) * 0.7f));
 

@@ -1,4 +1,4 @@
-// Stage A, shared by the streaming kernel (cape_cell_moments.hip) and the per-cell / strip kernels (cape_cell_fit.hip):
+// Stage A, shared by the two instances of the streaming kernel (cape_cell_moments.hip) and the per-cell / strip kernels (cape_cell_fit.hip):
 // the pixel accumulators of plane_segment.cpp:131-152 on top of depth_map_transformation.cpp:123-138 and the continuity
 // step of plane_segment.cpp:44-60.
 #pragma once
@@ -10,15 +10,30 @@
 namespace cape {
 
 
-// tuning knobs (overridable for A/B builds, see profiles/sweep.py).  Four measured-and-rejected variants of this kernel
-// (LDS-DMA ring prefetch, ds_add_f64 partials, v_pk_mul_f32 pixel pairs, a three-buffer prefetch) lived here behind
-// macros through round 2; their numbers are kept in DESIGN.md 4.1, their code in the history (commit 4d9050d).
+// tuning knobs of the BAND instance of the streaming kernel (CAPE_A1=bands; overridable for A/B builds, see profiles/sweep.py).
+// Four measured-and-rejected variants of it (LDS-DMA ring prefetch, ds_add_f64 partials, v_pk_mul_f32 pixel pairs, a
+// three-buffer prefetch) lived here behind macros through round 2; their numbers are kept in DESIGN.md 4.1, their code in the
+// history (commit 4d9050d).
 #ifndef CAPE_A_GROUP
 #define CAPE_A_GROUP 2   // image rows per prefetch group
 #endif
 #ifndef CAPE_A_WAVES
 #define CAPE_A_WAVES 4   // __launch_bounds__ waves per SIMD of the streaming kernel (measured: 4 -> 1.46 ms, 5 -> 1.49 ms, 3 -> 2.6 ms)
 #endif
+
+// ... and of the shipped lane-per-cell instance: independent waves of 64 cells, no LDS, no barrier (measured, 4 096 frames of
+// 640x480, profiles/a1_lane_per_cell.txt)
+#ifndef CAPE_A1_CELL_WAVES
+#define CAPE_A1_CELL_WAVES 4   // __launch_bounds__ waves per SIMD: 4 (128 VGPRs, no scratch) -> 1.158 ms, 3 (155 VGPRs) -> 1.132 ms
+#endif
+#ifndef CAPE_A1_CELL_THREADS
+#define CAPE_A1_CELL_THREADS 256 // waves x 64 per workgroup; the waves do not talk to each other: 64 -> 1.173 ms, 256 -> 1.158, 512 -> 1.161
+#endif
+#ifndef CAPE_A1_CELL_LOAD_POLICY
+#define CAPE_A1_CELL_LOAD_POLICY 0 // cache policy bits of the image loads: 0 = plain (served by L1) -> 1.158 ms, 2 = nt (bypasses L1) -> 2.05 ms
+#endif
+constexpr int kThreadsCells = CAPE_A1_CELL_THREADS;
+static_assert(kThreadsCells % 64 == 0 && kThreadsCells >= 64 && kThreadsCells <= 1024, "whole waves");
 
 constexpr int kThreadsA = 320;
 constexpr int kBandThreads = 160;
@@ -126,7 +141,9 @@ __device__ __forceinline__ bool is_continuous_flat(float pixelDepth, float& last
 }
 
 // The same step decided in f32 wherever f32 can decide it: eleven instructions against the sixteen of the f64 form.  Returns
-// the verdict and raises `unsure` when it might differ from is_continuous_flat's; the caller then runs the f64 scan.
+// the verdict and raises `unsure` when it might differ from is_continuous_flat's; the caller then runs the f64 form -- of the whole
+// scan (band instance, strip kernel) or of that step from the same `last` (lane-per-cell instance: a sure lane's f32 verdict
+// and `last` ARE the f64 ones, by the margin below, so redoing a step for the whole wave changes nothing for it).
 //   The f64 verdict is d <= R with d = |z - last| (an f32 difference in both forms: the same bits) and
 // R = 4 max(P(z), 0.5), P = c0 + c1 z + c2 z^2 evaluated in f64 (relative error ~2^-50, nothing at the scale below).
 //   r below is max(4 P, 2) by two f32 fma on the constants rounded to f32 (u = 2^-24 each): its distance from the exact value

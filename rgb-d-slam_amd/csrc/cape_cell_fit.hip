@@ -9,12 +9,11 @@
 //      (plane_segment.cpp:155-168, 205-284), the merge tolerance of init_planar_cell_fitting
 //      (primitive_detection.cpp:201-220) and the histogram bin of init_histogram (primitive_detection.cpp:253-254 +
 //      histogram.hpp:48-54).  Splitting it off keeps the long dependent f64 chains (eigen-solver, div, sqrt) out of
-//      the streaming workgroups, whose LDS and wave slots are then released as soon as the band is summed.
+//      the streaming waves, whose registers are then released as soon as their cells are summed.
 //
-// A1 mapping: one 320-thread workgroup = two "bands" (band = 20 image rows x 640 pixels = 32 cells).  Thread t owns
-// float4 column q = t % 160 of band t / 160 and walks the band's 20 rows, so every wave-level load is a contiguous
-// 16 B/lane segment of the row-major image; a float4 never straddles a cell (20 = 5 float4).  Rows are loaded two
-// at a time (CAPE_A_GROUP), ping-pong buffered, one group ahead of the arithmetic (non-temporal: the image is read once).  Per-thread partial sums (f64) meet in LDS; 5 partials = one cell.
+// A1 mapping: one lane per cell -- a wave is 64 consecutive cells of a frame, a lane sums its cell's 400 pixels, runs both
+// continuity scans on the way and stores the cell's sums and aux record itself (the band instance, one lane per float4
+// column of a 20-row band with the partials meeting in LDS, stays selectable: CAPE_A1=bands; both in cape_cell_moments.hip).
 // The sums are exact in f64 for ANY summation order when the addends' exponent span is < 21 bits;
 // a per-cell z-range guard decides whether that holds, otherwise A2 redoes the cell in the reference's pixel order.
 // (A1 itself: cape_cell_moments.hip, compiled without the SLP vectoriser; the shared accumulators: cape_cell_acc.h.)

@@ -9,14 +9,24 @@
 //      (plane_segment.cpp:155-168, 205-284), the merge tolerance of init_planar_cell_fitting
 //      (primitive_detection.cpp:201-220) and the histogram bin of init_histogram (primitive_detection.cpp:253-254 +
 //      histogram.hpp:48-54).  Splitting it off keeps the long dependent f64 chains (eigen-solver, div, sqrt) out of
-//      the streaming workgroups, whose LDS and wave slots are then released as soon as the band is summed.
+//      the streaming waves, whose registers are then released as soon as their cells are summed.
 //
-// A1 mapping: one 320-thread workgroup = two "bands" (band = 20 image rows x 640 pixels = 32 cells).  Thread t owns
+// A1 mapping, the shipped instance (cape_cell_moments_kernel, "cells"): one LANE per cell.  A wave is 64 consecutive cells of a
+// frame in cell-row-major order, lane l of wave w owns cell 64 w + l and walks its 20 rows of 20 pixels (80 contiguous, 16-B
+// aligned bytes per row: five 16-B loads through L1, where the lanes' pieces meet in their 128-B lines).  The lane keeps the
+// cell's 20 column factors, its nine sums, count and z range in registers, takes one step of the vertical continuity scan per
+// row and the horizontal scan's 19 steps at row 10, and stores its 80 B of sums and its aux record itself: no LDS, no
+// barrier, no second pass; a wave leaves as soon as its last pixel is summed.  Any grid goes through the same code (waves
+// may start and end inside a cell row; the last wave of a frame may be partial).  128 VGPRs, 4 waves per SIMD.
+// The band instance (cape_cell_moments_bands_kernel, CAPE_A1=bands: the bit-for-bit twin of the tests and the in-build A/B
+// partner): one 320-thread workgroup = two "bands" (band = 20 image rows x 640 pixels = 32 cells).  Thread t owns
 // float4 column q = t % 160 of band t / 160 and walks the band's 20 rows, so every wave-level load is a contiguous
 // 16 B/lane segment of the row-major image; a float4 never straddles a cell (20 = 5 float4).  Rows are loaded two
 // at a time (CAPE_A_GROUP), ping-pong buffered, one group ahead of the arithmetic (non-temporal: the image is read once).  Per-thread partial sums (f64) meet in LDS; 5 partials = one cell.
+// Numbers of both: profiles/a1_lane_per_cell.txt.
 // The sums are exact in f64 for ANY summation order when the addends' exponent span is < 21 bits;
 // a per-cell z-range guard decides whether that holds, otherwise A2 redoes the cell in the reference's pixel order.
+// That is also why the two instances leave the same bits.
 //
 // This file holds A1 only and is compiled with -fno-slp-vectorize (Makefile): left to itself the SLP vectoriser pairs the six
 // f32 products of a pixel into v_pk_mul_f32, which costs as much as the two v_mul_f32_e32 it replaces on gfx950
@@ -31,7 +41,7 @@
 
 namespace cape {
 
-template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void cape_cell_moments_kernel(StageAParams p)
+template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void cape_cell_moments_bands_kernel(StageAParams p)
 {
     // LDS: per-thread partials (written behind the row loop) and the 64 cells' centre row / centre column samples (written in it)
     __shared__ double s_part[kThreadsA * kPartStride]; // [thread][9 sums, count, (zmin,zmax) packed in the pad slot]
@@ -332,15 +342,256 @@ template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void c
     p.cell_aux[gcell] = aux;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The lane-per-cell instance (see the header; the band instance above is kept selectable until the wide grids are measured).
+// A wave is 64 consecutive cells of one frame, lane l of wave w owns cell 64 w + l: its nine sums, count, z range, both
+// continuity scans and the corner / centre samples never leave its registers.  nWaves: frames x waves per frame.
+template <bool U16> __global__ __launch_bounds__(kThreadsCells, CAPE_A1_CELL_WAVES) void cape_cell_moments_kernel(StageAParams p, int nWaves)
+{
+    // the wave: uniform, so the frame and its base address live in scalar registers
+    const int gw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kThreadsCells / 64) + (threadIdx.x >> 6)));
+    if (gw >= nWaves)
+        return; // the last workgroup's waves beyond the batch's last frame
+    const int wavesPerFrame = (p.cells + 63) >> 6;
+    const int frame = gw / wavesPerFrame;
+    const int w = gw - frame * wavesPerFrame;
+    const int cell = w * 64 + (int)(threadIdx.x & 63);
+    if (cell >= p.cells)
+        return; // (no barrier anywhere: a lane without a cell just leaves)
+    const int cellRow = cell / p.hCells;
+    const int cellCol = cell - cellRow * p.hCells;
+    const size_t frameOff = (size_t)frame * p.W * p.H;
+
+    PxAcc A;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+        A.S[k] = 0.0;
+    A.n = 0;
+    A.zminBits1 = 0xFFFFFFFFu;
+    A.zmaxBits = 0u;
+
+    // the cell's 20 column factors: 40 VGPRs, loaded once
+    double a[kCell];
+    {
+        const double2* ap = reinterpret_cast<const double2*>(p.acol + cellCol * kCell);
+#pragma unroll
+        for (int k = 0; k < kCell / 2; ++k)
+        {
+            const double2 v = ap[k];
+            a[2 * k] = v.x;
+            a[2 * k + 1] = v.y;
+        }
+    }
+    // piece j of a row: four pixels and their column factors
+    auto acc_piece = [&](const float4& v, int j, double b) { acc_f4(v, a[4 * j], a[4 * j + 1], a[4 * j + 2], a[4 * j + 3], b, A); };
+
+    // Addresses: one buffer descriptor per FRAME (scalar registers; built from uniform values only), the row as the scalar
+    // offset of the load, and ONE 32-bit byte offset per lane -- no 64-bit pointer per lane and per stream, which is what
+    // loop strength reduction makes of plain pointers here.  A frame is far below the descriptor's 4 GB, and a load beyond the
+    // frame would return zeros instead of faulting.
+    constexpr uint32_t kPixBytes = U16 ? 2 : 4;
+    const uint32_t pixByteOff = ((uint32_t)(cellRow * kCell) * (uint32_t)p.W + (uint32_t)(cellCol * kCell)) * kPixBytes;
+    const uint32_t browByteOff = (uint32_t)(cellRow * kCell) * 8u;
+    const uint32_t rowBytes = (uint32_t)p.W * kPixBytes;
+    const float scale16 = p.u16_scale;
+    auto uniform_ptr = [](const void* q) {
+        const uint64_t u = reinterpret_cast<uint64_t>(q);
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+        return reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
+    };
+    const void* frameBase = U16 ? (const void*)(p.depth_u16 + frameOff) : (const void*)(p.depth + frameOff);
+    const __amdgpu_buffer_rsrc_t frameRsrc =
+        __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(frameBase), 0, (int)((uint32_t)p.H * rowBytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t browRsrc = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(p.brow), 0, p.H * 8, 0x00020000);
+    auto brow_at = [&](int r) {
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(browRsrc, browByteOff, r * 8, 0);
+        return __hiloint2double((int)v.y, (int)v.x);
+    };
+
+    // a row of the cell as it was LOADED: five 16-B (8-B in the U16 variant) pieces of the lane's 80 (40) contiguous bytes.
+    // Plain loads, not non-temporal ones: the five pieces share their 128-B lines with each other and with the neighbour lanes'.
+    using Raw = typename std::conditional<U16, ushort4, float4>::type;
+    constexpr int kQuads = kCell / 4;
+    static_assert(kCell == 20, "five float4 per row, pixel column 10 = .z of piece 2");
+    auto load_piece = [&](int r, int j) -> Raw {
+        const int rowOff = r * (int)rowBytes; // uniform, and so is the piece: both travel in the load's scalar offset
+        if constexpr (U16)
+        {
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(frameRsrc, pixByteOff, rowOff + 8 * j, CAPE_A1_CELL_LOAD_POLICY);
+            return make_ushort4((unsigned short)(v.x & 0xFFFFu), (unsigned short)(v.x >> 16), (unsigned short)(v.y & 0xFFFFu), (unsigned short)(v.y >> 16));
+        }
+        else
+        {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(frameRsrc, pixByteOff, rowOff + 16 * j, CAPE_A1_CELL_LOAD_POLICY);
+            return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        }
+    };
+    auto to_f4 = [&](const Raw& rw) {
+        if constexpr (U16)
+            return make_float4((float)rw.x * scale16, (float)rw.y * scale16, (float)rw.z * scale16, (float)rw.w * scale16); // see the band kernel
+        else
+            return rw;
+    };
+
+    // Continuity cross scans (plane_segment.cpp:62-100), one step at a time as the pixels stream by:
+    //   vertical: local column 10, seeded with max(z[row 0], z[row 1]), one step per row 1..18 (the loop stops before row 19)
+    //   horizontal: local row 10, seeded with max(z[0], z[1]), steps 1..19
+    // A step runs in f32 (is_continuous_flat_f32); where some lane of the wave cannot call it, the wave redoes THAT step in f64
+    // from the same `last`: a sure lane's f32 verdict and `last` are the f64 ones (margin proof in cape_cell_acc.h).
+    // `counts`: uniform; a step that does not count neither fails the scan nor asks for the f64 form.
+    auto scan_step = [](float z, float& last, bool& continuous, bool counts) {
+        const float before = last;
+        bool unsure = false;
+        bool pass = is_continuous_flat_f32(z, last, unsure);
+        if (__any(unsure & counts))
+        {
+            last = before;
+            pass = is_continuous_flat(z, last);
+        }
+        continuous &= pass | !counts;
+    };
+    bool continuous = true;
+    // The lane's cell in the per-cell arrays, worked out afresh where the results are stored: the lane id from mbcnt of an
+    // all-ones mask, opaque to the compiler so that no index or address of the prologue is carried through the loops, where
+    // every register counts.
+    auto my_cell = [&]() {
+        uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lane));
+        return ((size_t)frame * p.cells + (size_t)(w * 64)) + lane;
+    };
+
+    // One row buffer in the source, refilled piece by piece: a piece of row r + 1 is requested as soon as the same piece of row r
+    // has been taken out.  (The compiler gathers the five requests at the top of the row and so holds two rows after all; spelled
+    // as two buffers with the scans inside the loop the same kernel spilled at 128 VGPRs.)
+    Raw buf[kQuads];
+#pragma unroll
+    for (int j = 0; j < kQuads; ++j)
+        buf[j] = load_piece(0, j);
+    double b = brow_at(0);
+    const float z0 = to_f4(buf[0]).x;
+    float zc = 0.0f;
+    float vLast = 0.0f;
+    // A row's arithmetic is ONE straight-line block -- nothing in it depends on r but addresses -- and the vertical scan's step
+    // comes behind it: its row-dependent parts are selects on the uniform r, its f64 form the row's only branch.
+    //   row 0: last = z, and the step (z against itself) does not count;  row 1: last = max(last, z), which seeds the scan
+    auto stream_row = [&](int r) {
+        const double bn = brow_at(r + 1);
+        float zv = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kQuads; ++j)
+        {
+            const float4 v = to_f4(buf[j]);
+            buf[j] = load_piece(r + 1, j);
+            acc_piece(v, j, b);
+            if (j == 2)
+                zv = v.z; // pixel column 10
+        }
+        b = bn;
+        const float seed = std_maxf(vLast, zv);
+        vLast = r == 0 ? zv : (r == 1 ? seed : vLast);
+        continuous &= (r != 1) | !(vLast <= 0);
+        scan_step(zv, vLast, continuous, r != 0);
+    };
+#pragma unroll 1
+    for (int r = 0; r < kCell / 2; ++r)
+        stream_row(r);
+    // row 10: the horizontal scan takes each piece's four steps right behind its arithmetic, then the piece is refilled
+    {
+        const int r = kCell / 2;
+        float hLast = 0.0f;
+#pragma unroll
+        for (int j = 0; j < kQuads; ++j)
+        {
+            const float4 v = to_f4(buf[j]);
+            buf[j] = load_piece(r + 1, j);
+            acc_piece(v, j, b);
+            if (j == 0)
+            {
+                hLast = std_maxf(v.x, v.y);
+                continuous &= !(hLast <= 0);
+            }
+            else
+            {
+                scan_step(v.x, hLast, continuous, true);
+            }
+            scan_step(v.y, hLast, continuous, true);
+            scan_step(v.z, hLast, continuous, true);
+            scan_step(v.w, hLast, continuous, true);
+            if (j == 2)
+            {
+                zc = v.z;
+                scan_step(v.z, vLast, continuous, true);
+            }
+        }
+        b = brow_at(r + 1); // (behind the scans, which leave no register pair for it)
+    }
+#pragma unroll 1
+    for (int r = kCell / 2 + 1; r < kCell - 1; ++r)
+        stream_row(r);
+    // row 19: nothing left to load, no scan step (the vertical scan stops before it)
+    float z399;
+#pragma unroll
+    for (int j = 0; j < kQuads; ++j)
+    {
+        const float4 v = to_f4(buf[j]);
+        acc_piece(v, j, b);
+        z399 = v.w;
+    }
+
+    // ------------------------------------------------------------------ the lane's cell leaves
+    // exactness guard: all addends of every sum within 2^20 of each other (see header)
+    const uint32_t n = A.n;
+    // back to depths: with n > 0 at least one pixel was valid, so the minimum is a real pattern - 1
+    const float zmin = __uint_as_float(A.zminBits1 + 1u), zmax = __uint_as_float(A.zmaxBits);
+    // (the cell's row and column once more, from the fresh index: a division per cell is cheaper than a register per loop)
+    const size_t gcell = my_cell();
+    const int ecell = (int)(gcell - (size_t)frame * p.cells);
+    int hCells = p.hCells;
+    asm volatile("" : "+s"(hCells)); // (opaque, or the prologue's reciprocal of it is what gets carried through the loops)
+    const int eRow = ecell / hCells;
+    const float rab = fmaxf(p.ratio_col[ecell - eRow * hCells], p.ratio_row[eRow]);
+    // all pixels +0 or positive and finite (acc_px_fast's precondition), and their range within the exactness bound
+    const bool exact_ok = A.zmaxBits <= 0x7F7FFFFFu && ((n == 0) || (zmax * rab <= 512.0f * zmin));
+
+    CellAux aux;
+    aux.z0 = z0;
+    aux.z399 = z399;
+    aux.flags = (n & kCountMask) | (continuous ? kAuxContinuous : 0u) | (exact_ok ? kAuxExact : 0u);
+    aux.zc = zc;
+    p.cell_aux[gcell] = aux;
+    double2* dst = reinterpret_cast<double2*>(p.cell_sums + gcell * kSumStride);
+    static_assert(kSumStride == 10, "nine sums and the count: five 16-B stores");
+    dst[0] = make_double2(A.S[0], A.S[1]);
+    dst[1] = make_double2(A.S[2], A.S[3]);
+    dst[2] = make_double2(A.S[4], A.S[5]);
+    dst[3] = make_double2(A.S[6], A.S[7]);
+    dst[4] = make_double2(A.S[8], (double)n);
+}
+
 // every launch helper reports its own failure: hipGetLastError() right behind the launch (a later runtime call would
 // overwrite the sticky-free error state on ROCm < 7)
 hipError_t launch_cell_moments(const StageAParams& p, int nFrames, hipStream_t stream)
 {
-    const int grid = nFrames * p.pairsPerFrame;
+    if (p.a1Bands)
+    {
+        const int grid = nFrames * p.pairsPerFrame;
+        if (p.depth)
+            hipLaunchKernelGGL(cape_cell_moments_bands_kernel<false>, dim3(grid), dim3(kThreadsA), 0, stream, p);
+        else
+            hipLaunchKernelGGL(cape_cell_moments_bands_kernel<true>, dim3(grid), dim3(kThreadsA), 0, stream, p);
+        return hipGetLastError();
+    }
+    // one wave per 64 cells of a frame, kThreadsCells / 64 independent waves per workgroup
+    constexpr int kWaves = kThreadsCells / 64;
+    const int waves = nFrames * ((p.cells + 63) / 64); // (cells <= 65535 per frame: far from 2^31 for any batch that fits the device)
+    const int grid = (waves + kWaves - 1) / kWaves;
     if (p.depth)
-        hipLaunchKernelGGL(cape_cell_moments_kernel<false>, dim3(grid), dim3(kThreadsA), 0, stream, p);
+        hipLaunchKernelGGL(cape_cell_moments_kernel<false>, dim3(grid), dim3(kThreadsCells), 0, stream, p, waves);
     else
-        hipLaunchKernelGGL(cape_cell_moments_kernel<true>, dim3(grid), dim3(kThreadsA), 0, stream, p);
+        hipLaunchKernelGGL(cape_cell_moments_kernel<true>, dim3(grid), dim3(kThreadsCells), 0, stream, p, waves);
     return hipGetLastError();
 }
 

@@ -517,7 +517,11 @@ __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFram
                 key = wave_max_u32(key);
                 if (key == 0)
                 {
-                    moreSeeds = false; // mostFrequentBin = -1 -> empty candidate list -> size < planeSeedCount
+                    // mostFrequentBin = -1 -> empty candidate list -> size < planeSeedCount; on a grid of fewer than 125 cells
+                    // planeSeedCount is 0, the reference goes on with the empty list and ends on "invalid seed" (:299-304)
+                    moreSeeds = false;
+                    if (p.planeSeedCount == 0)
+                        status |= CAPE_FRAME_INVALID_SEED;
                     break;
                 }
                 const int bin = 0xFFFF - (int)(key & 0xFFFFu);
@@ -579,6 +583,8 @@ __device__ __forceinline__ void grow_frame_wave(const StageBParams& p, int nFram
                 if (cand < p.planeSeedCount || cand == 0)
                 {
                     moreSeeds = false;
+                    if (cand >= p.planeSeedCount)
+                        status |= CAPE_FRAME_INVALID_SEED; // (no candidate, planeSeedCount 0: the reference's empty list, as above)
                     break;
                 }
                 const unsigned long long bestAll = wave_min_u64(bestLocal);

@@ -315,7 +315,9 @@ __device__ void general_frame(const StageBParams& p, const GenParams& g, const G
                 key = wave_max_u32(key);
                 if (key == 0)
                 {
-                    moreSeeds = false;
+                    moreSeeds = false; // (an empty candidate list: "invalid seed" where planeSeedCount is 0, see cape_grow.hip)
+                    if (p.planeSeedCount == 0)
+                        status |= CAPE_FRAME_INVALID_SEED;
                     break;
                 }
                 const int bin = 0xFFFF - (int)(key & 0xFFFFu);
@@ -356,6 +358,8 @@ __device__ void general_frame(const StageBParams& p, const GenParams& g, const G
                 if (cand < p.planeSeedCount || cand == 0)
                 {
                     moreSeeds = false;
+                    if (cand >= p.planeSeedCount)
+                        status |= CAPE_FRAME_INVALID_SEED; // (no candidate, planeSeedCount 0: the reference's empty list, as above)
                     break;
                 }
                 const u64 bestAll = wave_min_u64(bestLocal);

@@ -72,6 +72,7 @@ struct StageAParams
     uint32_t* clear4; // ... and the allocation counter of the spill record pool (nullptr on a sub-batch: cleared once per call)
     double cosMergeA; // cos(18 * pi / 180), plane_segment.cpp:324 (the edge predicates of stage A2)
     int smallBatchFrames; // host side: batches up to this many frames run the latency-oriented kernel instances
+    int a1Bands;          // host side: 1 = launch_cell_moments runs the band instance of A1 (CAPE_A1=bands), 0 = lane per cell
     int minZeroPointCount; // floor(400 * 0.7f) = 280, plane_segment.hpp:33-34
 };
 
