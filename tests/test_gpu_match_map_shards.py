@@ -335,7 +335,8 @@ def test_chained_frames():
     tiles 100..150, 1280x720 tiles 90..150, 960x720 tiles 90..150, and the same with a crease of 0.05..0.3 through every facet) has
     exactly as many output planes and kept planes as segments (e.g. 70 / 70 / 70 at 1280x960 tile 130, 63 / 63 / 63 at tile 135),
     synth.facets with 150..600 planes gives 3..6 segments, and coplanar half-facets with a depth step between them (cell-aligned,
-    tile 160, steps 25..85 mm) either grow through, or split without merging (95 / 95), or give 16..36 segments that are all planes.  The path itself is the one this test and
+    tile 160, steps 25..85 mm) either grow through, or split without merging (95 / 95), or give 16..36 segments that are all planes.  A wall behind a lattice
+    with stepped half-panes meant to merge (tests/capacity_cases.py's lattice, depth steps of 20 to 60 mm) was tried too: 47, 0 or 111 segments, with as many planes.  The path itself is the one this test and
     test_more_than_16_kept_planes_are_served_from_a_shard run: the gate kernel never looks at the segment count."""
     import torch
     import cape_amd
