@@ -953,7 +953,9 @@ enum
                                             the number of holes */
     CAPE_UNION_HOST_AMBIGUOUS = 1u << 6, /* an angle comparison of the face walk lies inside the guard band */
     CAPE_UNION_HOLES = 1u << 7,          /* with SERVED: the polygon has interior rings, see cape_plane_union_rings */
-    CAPE_UNION_HOST_HOLE_CUT = 1u << 8   /* a hole of the map plane is partly covered by the detection */
+    CAPE_UNION_HOST_HOLE_CUT = 1u << 8,  /* a hole of the map plane is partly covered by the detection */
+    CAPE_UNION_HOLE_PIECES = 1u << 9     /* with SERVED, cape_map_union_cut only: a hole of the map plane was partly covered and
+                                            merge_union's `cut` branch ran -- also where every piece was then dropped */
 };
 /* One row per kept plane i < 128 of a frame, like the fusion rows.  A pair with a CAPE_UNION_HOST_* bit carries no ring:
  * vertex_count = 0 and area = 0.  The frame is the new map polygon's: the fusion row's, except where the isApprox shortcut kept the
@@ -1014,6 +1016,24 @@ int cape_map_union_holes(cape_handle h, int32_t n_frames, void* stream);
 /* Synchronous copy / device pointer of the rings table of the last cape_map_union_holes (n_frames x 128). */
 int cape_copy_map_union_rings(cape_handle h, int32_t n_frames, cape_plane_union_rings* rings /* n_frames x 128 */);
 int cape_device_map_union_rings(cape_handle h, cape_plane_union_rings** rings);
+
+/* cape_map_union_holes for a map plane whose hole the detection covers in part as well: instead of CAPE_UNION_HOST_HOLE_CUT the
+ * pieces of (hole minus detection) become interior rings, as carry_hole's rings_union_outer(hole, detection, &pieces, 1) computes
+ * them.  The arrangement of the hole (as the projected map polygon holds it) and the detection's ring is built a second time inside
+ * the pair, with its own eps, cuts, nodes and start node; its outer face is walked only to mark its edges; every other bounded face
+ * whose probe point lies in or on the hole and not in or on the detection is a piece after drop_collinear if it has >= 3 vertices,
+ * is simple and its area exceeds 1e-12 of the bigger operand's (of the FIRST pair of operands).  The interior rings of a served
+ * polygon stand in the host's order: the new ones, then per hole of the map plane, in the map's order, the kept hole itself, nothing
+ * for a covered one, or the cut hole's pieces in face-walk order.  Such a pair is served with CAPE_UNION_HOLE_PIECES; holes_covered
+ * counts the wholly covered holes only.  Never sets CAPE_UNION_HOST_HOLE_CUT, HOST_MAP_HOLES or HOST_NEW_HOLE.
+ * CAPE_UNION_HOST_CAPACITY as for cape_map_union_holes -- the limits on interior rings and their vertices count the pieces -- and
+ * for the second arrangement's own limits: more than 1024 cuts, more than CAPE_MAP_UNION_MAX_NODES nodes, a node of more than 8
+ * neighbours, a walk that reaches its guard or outgrows CAPE_MAP_MAX_RING.  CAPE_UNION_HOST_AMBIGUOUS also for an angle comparison of
+ * the second walk.  A pair without a partly covered hole has the rows, rings and vertices of cape_map_union_holes bit for bit.
+ * Preconditions and error codes of cape_map_union_holes.  Writes the same row buffer, slab and rings table: the copy and device-pointer
+ * calls of both return its results; a later cape_map_union makes the rings table stale, a later cape_map_union_holes overwrites
+ * everything with its own rows (and the other way round). */
+int cape_map_union_cut(cape_handle h, int32_t n_frames, void* stream);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
@@ -1201,6 +1221,11 @@ int cape_debug_ring_union(cape_handle h, const double* ring_a, int32_t n_a, cons
  * [1, 1 + CAPE_MAP_MAX_HOLES], a count or n_b outside [3, 4096].  Twin: cape_host_polygon_union. */
 int cape_debug_polygon_union(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
                              const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out);
+/* The same for cape_map_union_cut's per-pair function: the arguments, outputs and error codes of cape_debug_polygon_union.  Twin:
+ * cape_host_polygon_union_cut. */
+int cape_debug_polygon_union_cut(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b,
+                                 int32_t n_b, const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out,
+                                 double* vertices_out);
 
 /* The seed of the reference's random engine (src/utils/random.hpp:59-64): 0 under MAKE_DETERMINISTIC -- the default here, and the
  * mode BASELINE.json's bit-exactness is stated for --, `std::time(0)` taken once at process start otherwise.  The engine is

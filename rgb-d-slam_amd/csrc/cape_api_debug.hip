@@ -231,8 +231,9 @@ int cape_debug_ring_union(cape_handle h, const double* ring_a, int32_t n_a, cons
     return CAPE_OK;
 }
 
-int cape_debug_polygon_union(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
-                             const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
+// cape_debug_polygon_union and cape_debug_polygon_union_cut: the same arguments and buffers, the kernel of the mode
+static int debug_polygon_union(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                               const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out, bool cut)
 {
     static const double kCanonical[27] = {1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0};
     if (!h || !rings_a || !counts_a || !ring_b || !row_out || !rings_out || !vertices_out || n_rings_a < 1 || n_rings_a > 1 + CAPE_MAP_MAX_HOLES ||
@@ -273,7 +274,7 @@ int cape_debug_polygon_union(cape_handle h, const double* rings_a, const int32_t
     p.row = row;
     p.ringRow = ringRow;
     p.vertices = reinterpret_cast<double2*>(verts.get());
-    CAPE_HIP_TRY(cape::launch_polygon_union(p, nullptr));
+    CAPE_HIP_TRY(cut ? cape::launch_polygon_union_cut(p, nullptr) : cape::launch_polygon_union(p, nullptr));
     CAPE_HIP_TRY(hipDeviceSynchronize());
     CAPE_HIP_TRY(copy_out(row_out, row, 0, 1));
     CAPE_HIP_TRY(copy_out(rings_out, ringRow, 0, 1));
@@ -282,6 +283,19 @@ int cape_debug_polygon_union(cape_handle h, const double* rings_a, const int32_t
         n += rings_out->vertex_count[k];
     CAPE_HIP_TRY(copy_out(vertices_out, verts, 0, (n <= CAPE_MAP_UNION_FRAME_VERTICES ? n : 0) * 2));
     return CAPE_OK;
+}
+
+int cape_debug_polygon_union(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                             const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
+{
+    return debug_polygon_union(h, rings_a, counts_a, n_rings_a, ring_b, n_b, frames27, row_out, rings_out, vertices_out, false);
+}
+
+int cape_debug_polygon_union_cut(cape_handle h, const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b,
+                                 int32_t n_b, const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out,
+                                 double* vertices_out)
+{
+    return debug_polygon_union(h, rings_a, counts_a, n_rings_a, ring_b, n_b, frames27, row_out, rings_out, vertices_out, true);
 }
 
 } // extern "C"

@@ -1255,9 +1255,12 @@ int cape_copy_map_kalman(cape_handle h, int32_t n_frames, cape_frame_map_kalman*
     return CAPE_OK;
 }
 
-// cape_map_union and cape_map_union_holes: the same preconditions, rows and slab; the second one's kernel and its rings table
-static int map_union(cape_handle h, int32_t n_frames, void* stream_, bool holes)
+// cape_map_union, cape_map_union_holes and cape_map_union_cut: the same preconditions, rows and slab; the kernels of the last two
+// and their rings table
+enum MapUnionMode { kUnionPlain, kUnionWithHoles, kUnionWithCuts };
+static int map_union(cape_handle h, int32_t n_frames, void* stream_, MapUnionMode mode)
 {
+    const bool holes = mode != kUnionPlain;
     constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
     if (!h || n_frames < 0)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
@@ -1299,22 +1302,25 @@ static int map_union(cape_handle h, int32_t n_frames, void* stream_, bool holes)
     p.fusion = K.rows;
     p.rows = U.rows;
     p.vertices = reinterpret_cast<double2*>(U.vertices.get());
-    CAPE_HIP_TRY(holes ? cape::launch_map_union_holes(p, h->mapUnionRings.rows, n_frames, stream) : cape::launch_map_union(p, n_frames, stream));
+    CAPE_HIP_TRY(mode == kUnionWithCuts    ? cape::launch_map_union_cut(p, h->mapUnionRings.rows, n_frames, stream)
+                 : mode == kUnionWithHoles ? cape::launch_map_union_holes(p, h->mapUnionRings.rows, n_frames, stream)
+                                           : cape::launch_map_union(p, n_frames, stream));
     U.unionFrames = n_frames;
     U.kalmanRun = K.runs;
     h->mapUnionRings.current = holes;
     return CAPE_OK;
 }
 
-int cape_map_union(cape_handle h, int32_t n_frames, void* stream) { return map_union(h, n_frames, stream, false); }
-int cape_map_union_holes(cape_handle h, int32_t n_frames, void* stream) { return map_union(h, n_frames, stream, true); }
+int cape_map_union(cape_handle h, int32_t n_frames, void* stream) { return map_union(h, n_frames, stream, kUnionPlain); }
+int cape_map_union_holes(cape_handle h, int32_t n_frames, void* stream) { return map_union(h, n_frames, stream, kUnionWithHoles); }
+int cape_map_union_cut(cape_handle h, int32_t n_frames, void* stream) { return map_union(h, n_frames, stream, kUnionWithCuts); }
 
 int cape_device_map_union_rings(cape_handle h, cape_plane_union_rings** rings)
 {
     if (!h)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
     if (!union_results_live(h) || !h->mapUnionRings.current)
-        return fail(CAPE_ERR_CAPACITY, "no cape_map_union_holes has run on the current batch, map, match, measurements and Kalman results, or a cape_map_union has replaced its rows");
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_union_holes or cape_map_union_cut has run on the current batch, map, match, measurements and Kalman results, or a cape_map_union has replaced its rows");
     if (rings)
         *rings = h->mapUnionRings.rows;
     return CAPE_OK;
@@ -1327,7 +1333,7 @@ int cape_copy_map_union_rings(cape_handle h, int32_t n_frames, cape_plane_union_
         return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
     const auto& U = h->mapUnion;
     if (n_frames > (union_results_live(h) && h->mapUnionRings.current ? U.unionFrames : 0))
-        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_union_holes on the current batch, map, match, measurements and Kalman results (a cape_map_union replaces its rows)");
+        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_union_holes or cape_map_union_cut on the current batch, map, match, measurements and Kalman results (a cape_map_union replaces its rows)");
     if (n_frames == 0)
         return CAPE_OK;
     CAPE_ON_DEVICE(h);

@@ -39,6 +39,8 @@ hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t st
 hipError_t launch_ring_union(const RingUnionParams& p, hipStream_t stream);
 hipError_t launch_map_union_holes(const MapUnionParams& p, cape_plane_union_rings* ringRows /* frames x 128 */, int nFrames, hipStream_t stream);
 hipError_t launch_polygon_union(const PolygonUnionParams& p, hipStream_t stream);
+hipError_t launch_map_union_cut(const MapUnionParams& p, cape_plane_union_rings* ringRows /* frames x 128 */, int nFrames, hipStream_t stream);
+hipError_t launch_polygon_union_cut(const PolygonUnionParams& p, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -487,12 +489,12 @@ struct cape_handle_s
         unsigned kalmanRun = 0;        // Kalman::runs when it ran: a later cape_map_kalman invalidates the results
     } mapUnion;
 
-    // cape_map_union_holes: the rings table beside mapUnion's rows and slab, which the call writes too.  (Declared last, like the
-    // structs above.)
+    // cape_map_union_holes and cape_map_union_cut: the rings table beside mapUnion's rows and slab, which either call writes too.
+    // (Declared last, like the structs above.)
     struct UnionRings
     {
         Buffer<cape_plane_union_rings> rows; // frames x 128
-        bool current = false;                // mapUnion's rows are those of a cape_map_union_holes: the table belongs to them
+        bool current = false;                // mapUnion's rows are those of one of these two calls: the table belongs to them
     } mapUnionRings;
 };
 

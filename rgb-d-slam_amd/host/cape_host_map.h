@@ -140,6 +140,19 @@ int cape_host_map_union_holes(const cape_host_map* map, const int32_t* match, co
 int cape_host_polygon_union(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
                             const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out);
 
+/* The twins of cape_map_union_cut and cape_debug_polygon_union_cut: the signatures, outputs and capacity rules of the two above, for
+ * a map plane whose hole the detection covers in part as well.  The host class computes the pieces of such a hole itself
+ * (merge_union's carry_hole), so these never set CAPE_UNION_HOST_HOLE_CUT: the pair is served like any other, with
+ * CAPE_UNION_HOLE_PIECES beside CAPE_UNION_SERVED where merge_union's `cut` branch ran (MergeInfo::holeCut), whatever became of the
+ * pieces; rings.holes_covered counts the wholly covered holes only.  A pair without a partly covered hole has the rows of the twins
+ * above.  Of the device's CAPE_UNION_HOST_CAPACITY they do not know the second arrangement's own limits (its cuts, nodes, degrees and
+ * walks): such a pair is served here. */
+int cape_host_map_union_cut(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion,
+                            const cape_plane_measurement* measurements, const double* world_vertices, int32_t n_cur, cape_plane_union* rows_out,
+                            cape_plane_union_rings* rings_out, double* vertices_out);
+int cape_host_polygon_union_cut(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                                const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out);
+
 /* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
  * cape_gather_primitives[_root] or any other transport -- as the kept planes the two calls above take: no handle, no device.
  * `frame` counts from the shard's first frame.  Each plane goes through the host class's Polygon(ring, xAxis, yAxis, center)

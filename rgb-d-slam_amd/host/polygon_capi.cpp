@@ -279,8 +279,10 @@ void put_union_row(cape_plane_union& row, const Polygon& poly, const PolygonStep
 // A pair's rows of cape_map_union_holes from the step's outcome (every ring of the map plane within CAPE_MAP_UNION_MAX_RING, at most
 // CAPE_MAP_MAX_HOLES of them): a partly covered hole first, then the capacities the device has -- the interior rings before simplify,
 // polygon_step's overflow, the slab, which takes the whole polygon or nothing.
+// `cutMode` (cape_map_union_cut): a partly covered hole is no refusal -- the host class has computed its pieces -- and a served row
+// says that merge_union's `cut` branch ran (CAPE_UNION_HOLE_PIECES).
 void put_union_holes_rows(cape_plane_union& row, cape_plane_union_rings& rings, const Polygon& poly, const PolygonStep& step, uint32_t& used,
-                          uint32_t capacity, double* slab)
+                          uint32_t capacity, double* slab, bool cutMode = false)
 {
     size_t holeVertices = 0, total = poly.boundary().size();
     for (const auto& h : poly.interior_rings())
@@ -288,7 +290,7 @@ void put_union_holes_rows(cape_plane_union& row, cape_plane_union_rings& rings, 
     total += holeVertices;
     if (step.merged)
         holeVertices = step.info.holeVertices; // (before simplify)
-    if (step.info.holeCut)
+    if (step.info.holeCut && !cutMode)
         row.flags = CAPE_UNION_HOST_HOLE_CUT;
     else if (step.overflow || holeVertices > CAPE_MAP_UNION_HOLE_VERTICES || total > capacity - used)
         row.flags = CAPE_UNION_HOST_CAPACITY;
@@ -296,7 +298,7 @@ void put_union_holes_rows(cape_plane_union& row, cape_plane_union_rings& rings, 
     {
         const auto& holes = poly.interior_rings();
         row.flags = CAPE_UNION_SERVED | (step.merged ? 0u : (uint32_t)CAPE_UNION_UNCHANGED) | (step.info.disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u) |
-                    (holes.empty() ? 0u : (uint32_t)CAPE_UNION_HOLES);
+                    (holes.empty() ? 0u : (uint32_t)CAPE_UNION_HOLES) | (step.info.holeCut ? (uint32_t)CAPE_UNION_HOLE_PIECES : 0u);
         put3(row.x_axis, poly.get_x_axis());
         put3(row.y_axis, poly.get_y_axis());
         put3(row.center, poly.get_center());
@@ -872,7 +874,8 @@ extern "C" int cape_host_map_kalman(const cape_host_map* map, const int32_t* mat
 // host class itself.  rings_out NULL: the first one's rules, otherwise the second one's.
 namespace {
 int host_map_union(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion, const cape_plane_measurement* measurements,
-                   const double* world_vertices, int32_t n_cur, cape_plane_union* rows_out, cape_plane_union_rings* rings_out, double* vertices_out)
+                   const double* world_vertices, int32_t n_cur, cape_plane_union* rows_out, cape_plane_union_rings* rings_out, double* vertices_out,
+                   bool cutMode = false)
 {
     const bool holesMode = rings_out != nullptr;
     if (!map || map->n_planes < 0 || n_cur < 0 || n_cur > CAPE_MATCH_MAP_WIDE_MAX_PLANES || !rows_out || !vertices_out ||
@@ -925,7 +928,7 @@ int host_map_union(const cape_host_map* map, const int32_t* match, const cape_pl
             if (!step.ok) // (the centre check after a projection: not reached, the projected polygon's centre IS the target)
                 continue;
             if (holesMode)
-                put_union_holes_rows(row, ringRows[i], poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, slab.data());
+                put_union_holes_rows(row, ringRows[i], poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, slab.data(), cutMode);
             else
                 put_union_row(row, poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, slab.data());
         }
@@ -943,7 +946,7 @@ int host_map_union(const cape_host_map* map, const int32_t* match, const cape_pl
 
 // one pair given by its rings and frames: ring a with its interior rings (holesMode) against ring b
 int host_pair_union(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b, const double* frames27,
-                    cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
+                    cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out, bool cutMode = false)
 {
     static const double kCanonical[27] = {1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 0};
     const bool holesMode = rings_out != nullptr;
@@ -978,7 +981,7 @@ int host_pair_union(const double* rings_a, const int32_t* counts_a, int32_t n_ri
                 poly);
             uint32_t used = 0;
             if (step.ok && holesMode)
-                put_union_holes_rows(row, ringRow, poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, vertices_out);
+                put_union_holes_rows(row, ringRow, poly, step, used, CAPE_MAP_UNION_FRAME_VERTICES, vertices_out, cutMode);
             else if (step.ok)
                 put_union_row(row, poly, step, used, CAPE_MAP_MAX_RING, vertices_out);
         }
@@ -1010,7 +1013,17 @@ extern "C" int cape_host_map_union_holes(const cape_host_map* map, const int32_t
     return host_map_union(map, match, fusion, measurements, world_vertices, n_cur, rows_out, rings_out, vertices_out);
 }
 
-// The twins of cape_debug_ring_union and cape_debug_polygon_union (cape_host_map.h): one pair given by its rings and three frames.
+extern "C" int cape_host_map_union_cut(const cape_host_map* map, const int32_t* match, const cape_plane_fusion* fusion,
+                                       const cape_plane_measurement* measurements, const double* world_vertices, int32_t n_cur,
+                                       cape_plane_union* rows_out, cape_plane_union_rings* rings_out, double* vertices_out)
+{
+    if (!rings_out)
+        return CAPE_ERR_INVALID_ARGUMENT;
+    return host_map_union(map, match, fusion, measurements, world_vertices, n_cur, rows_out, rings_out, vertices_out, true);
+}
+
+// The twins of cape_debug_ring_union, cape_debug_polygon_union and cape_debug_polygon_union_cut (cape_host_map.h): one pair given by
+// its rings and three frames.
 extern "C" int cape_host_ring_union(const double* ring_a, int32_t n_a, const double* ring_b, int32_t n_b, const double* frames27,
                                     cape_plane_union* row_out, double* vertices_out)
 {
@@ -1019,16 +1032,34 @@ extern "C" int cape_host_ring_union(const double* ring_a, int32_t n_a, const dou
     return host_pair_union(ring_a, &n_a, 1, ring_b, n_b, frames27, row_out, nullptr, vertices_out);
 }
 
-extern "C" int cape_host_polygon_union(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
-                                       const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
+// the argument checks of cape_host_polygon_union and cape_host_polygon_union_cut
+static bool polygon_union_arguments_fit(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                                        const cape_plane_union* row_out, const cape_plane_union_rings* rings_out, const double* vertices_out)
 {
     if (!rings_a || !counts_a || !ring_b || !row_out || !rings_out || !vertices_out || n_rings_a < 1 || n_rings_a > 1 + CAPE_MAP_MAX_HOLES || n_b < 3 ||
         n_b > 4096)
-        return CAPE_ERR_INVALID_ARGUMENT;
+        return false;
     for (int32_t k = 0; k < n_rings_a; ++k)
         if (counts_a[k] < 3 || counts_a[k] > 4096)
-            return CAPE_ERR_INVALID_ARGUMENT;
+            return false;
+    return true;
+}
+
+extern "C" int cape_host_polygon_union(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                                       const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out)
+{
+    if (!polygon_union_arguments_fit(rings_a, counts_a, n_rings_a, ring_b, n_b, row_out, rings_out, vertices_out))
+        return CAPE_ERR_INVALID_ARGUMENT;
     return host_pair_union(rings_a, counts_a, n_rings_a, ring_b, n_b, frames27, row_out, rings_out, vertices_out);
+}
+
+extern "C" int cape_host_polygon_union_cut(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
+                                           const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out,
+                                           double* vertices_out)
+{
+    if (!polygon_union_arguments_fit(rings_a, counts_a, n_rings_a, ring_b, n_b, row_out, rings_out, vertices_out))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    return host_pair_union(rings_a, counts_a, n_rings_a, ring_b, n_b, frames27, row_out, rings_out, vertices_out, true);
 }
 
 // Test hooks of the covariance and Kalman algebra (tests/test_map_update_host.py restates them in numpy).  Each returns 1 on

@@ -244,6 +244,8 @@ MAP_UNION_MAX_RING, MAP_UNION_MAX_NODES, MAP_UNION_FRAME_VERTICES = 128, 512, 20
 UNION_HOST = UNION_HOST_MAP_HOLES | UNION_HOST_NEW_HOLE | UNION_HOST_CAPACITY | UNION_HOST_AMBIGUOUS
 # cape_map_union_holes: the same rows and slab plus a row of ring lengths per kept plane (cape_plane_union_rings)
 UNION_HOLES, UNION_HOST_HOLE_CUT = 1 << 7, 1 << 8
+# cape_map_union_cut: with SERVED, a hole of the map plane was partly covered and cut into its pieces
+UNION_HOLE_PIECES = 1 << 9
 MAP_UNION_HOLE_VERTICES = 512
 PLANE_UNION_RINGS_DTYPE = np.dtype([
     ("ring_count", "<u4"), ("vertex_count", "<u4", 1 + MAP_MAX_HOLES), ("holes_new", "<u4"), ("holes_kept", "<u4"), ("holes_covered", "<u4"),
@@ -291,6 +293,8 @@ def _host_library():
         L.cape_host_map_union_holes.argtypes = [Map, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cape_host_polygon_union.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
+        L.cape_host_map_union_cut.argtypes = L.cape_host_map_union_holes.argtypes
+        L.cape_host_polygon_union_cut.argtypes = L.cape_host_polygon_union.argtypes
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
         L.cape_host_plane_to_world.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
@@ -443,8 +447,9 @@ def _union_polygons(rows, ring_rows, slab):
     return out
 
 
-def _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, holes):
-    """host_map_union (holes=False) and host_map_union_holes (holes=True): the arguments packed once, the twin called"""
+def _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, holes, cut=False):
+    """host_map_union (holes=False), host_map_union_holes (holes=True) and host_map_union_cut (cut=True too): the arguments packed
+    once, the twin called"""
     L = _host_library()
     src, src_view = _map_arrays(map_arrays)
     F = np.ascontiguousarray(fusion_rows, PLANE_FUSION_DTYPE).reshape(-1)
@@ -465,10 +470,11 @@ def _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, h
     slab = np.zeros((MAP_UNION_FRAME_VERTICES, 2))
     if holes:
         ring_rows = np.zeros(MATCH_MAP_WIDE_MAX_PLANES, PLANE_UNION_RINGS_DTYPE)
-        rc = L.cape_host_map_union_holes(C.byref(src_view), _as(M, C.c_int32), F.ctypes.data, Mr.ctypes.data, W.ctypes.data, n_cur,
-                                         rows.ctypes.data, ring_rows.ctypes.data, slab.ctypes.data)
+        name = "cape_host_map_union_cut" if cut else "cape_host_map_union_holes"
+        rc = getattr(L, name)(C.byref(src_view), _as(M, C.c_int32), F.ctypes.data, Mr.ctypes.data, W.ctypes.data, n_cur,
+                              rows.ctypes.data, ring_rows.ctypes.data, slab.ctypes.data)
         if rc != 0:
-            raise CapeError(f"cape_host_map_union_holes failed ({rc})")
+            raise CapeError(f"{name} failed ({rc})")
         return rows[:n_cur], ring_rows[:n_cur], _union_polygons(rows[:n_cur], ring_rows[:n_cur], slab)
     rc = L.cape_host_map_union(C.byref(src_view), _as(M, C.c_int32), F.ctypes.data, Mr.ctypes.data, W.ctypes.data, n_cur, rows.ctypes.data,
                                slab.ctypes.data)
@@ -494,6 +500,12 @@ def host_map_union_holes(map_arrays, match, fusion_rows, measurements, world_rin
     return _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, True)
 
 
+def host_map_union_cut(map_arrays, match, fusion_rows, measurements, world_rings):
+    """cape_host_map_union_cut: the twin of Extractor.map_union_cut for ONE frame, the arguments and results of host_map_union_holes.
+    A pair whose hole the detection covers in part is served with UNION_HOLE_PIECES instead of UNION_HOST_HOLE_CUT."""
+    return _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, True, True)
+
+
 def _polygon_union_args(rings_a, ring_b, frames):
     rings = [np.ascontiguousarray(r, np.float64).reshape(-1, 2) for r in rings_a]
     a = np.ascontiguousarray(np.concatenate(rings))
@@ -512,6 +524,17 @@ def host_polygon_union(rings_a, ring_b, frames=None):
                                    row.ctypes.data, rrow.ctypes.data, ver.ctypes.data)
     if rc != 0:
         raise CapeError(f"cape_host_polygon_union failed ({rc})")
+    return row[0], rrow[0], _union_polygons(row, rrow, ver)[0]
+
+
+def host_polygon_union_cut(rings_a, ring_b, frames=None):
+    """cape_host_polygon_union_cut: the twin of Extractor.debug_polygon_union_cut, the arguments and results of host_polygon_union"""
+    L = _host_library()
+    a, counts, b, F, row, rrow, ver = _polygon_union_args(rings_a, ring_b, frames)
+    rc = L.cape_host_polygon_union_cut(a.ctypes.data, counts.ctypes.data, len(counts), b.ctypes.data, len(b),
+                                       None if F is None else F.ctypes.data, row.ctypes.data, rrow.ctypes.data, ver.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_polygon_union_cut failed ({rc})")
     return row[0], rrow[0], _union_polygons(row, rrow, ver)[0]
 
 
@@ -683,6 +706,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_upload_tracks", "cape_map_kalman", "cape_copy_map_kalman", "cape_device_map_kalman",
     "cape_map_union", "cape_copy_map_union", "cape_device_map_union", "cape_debug_ring_union",
     "cape_map_union_holes", "cape_copy_map_union_rings", "cape_device_map_union_rings", "cape_debug_polygon_union",
+    "cape_map_union_cut", "cape_debug_polygon_union_cut",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -786,6 +810,8 @@ def load_library():
     L.cape_copy_map_union_rings.argtypes = [vp, C.c_int32, vp]
     L.cape_device_map_union_rings.argtypes = [vp, C.POINTER(vp)]
     L.cape_debug_polygon_union.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
+    L.cape_map_union_cut.argtypes = [vp, C.c_int32, vp]
+    L.cape_debug_polygon_union_cut.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1248,8 +1274,15 @@ class Extractor:
         whose hole the detection covers in part is UNION_HOST_HOLE_CUT.  The results are map_union_polygons'."""
         _check(self.L, self.L.cape_map_union_holes(self.h, n_frames, C.c_void_p(stream)), "cape_map_union_holes")
 
+    def map_union_cut(self, n_frames, stream=0):
+        """cape_map_union_cut: map_union_holes, and a hole of the map plane the detection covers in part is cut into its pieces on
+        the device: the pair is served with UNION_HOLE_PIECES where map_union_holes reports UNION_HOST_HOLE_CUT.  It writes the same
+        rows, slabs and ring rows; map_union_polygons returns its results."""
+        _check(self.L, self.L.cape_map_union_cut(self.h, n_frames, C.c_void_p(stream)), "cape_map_union_cut")
+
     def map_union_ring_rows(self, n_frames):
-        """PLANE_UNION_RINGS_DTYPE[n_frames, 128] of the last map_union_holes (CapeError once a map_union has replaced its rows)"""
+        """PLANE_UNION_RINGS_DTYPE[n_frames, 128] of the last map_union_holes or map_union_cut (CapeError once a map_union has
+        replaced its rows)"""
         rings = np.zeros((n_frames, MATCH_MAP_WIDE_MAX_PLANES), PLANE_UNION_RINGS_DTYPE)
         _check(self.L, self.L.cape_copy_map_union_rings(self.h, n_frames, rings.ctypes.data_as(C.c_void_p)), "cape_copy_map_union_rings")
         return rings
@@ -1269,6 +1302,16 @@ class Extractor:
                                                        b.ctypes.data_as(C.c_void_p), len(b), None if F is None else F.ctypes.data_as(C.c_void_p),
                                                        row.ctypes.data_as(C.c_void_p), rrow.ctypes.data_as(C.c_void_p),
                                                        ver.ctypes.data_as(C.c_void_p)), "cape_debug_polygon_union")
+        return row[0], rrow[0], _union_polygons(row, rrow, ver)[0]
+
+    def debug_polygon_union_cut(self, rings_a, ring_b, frames=None):
+        """cape_debug_polygon_union_cut: map_union_cut's per-pair device function on one pair, the arguments and results of
+        debug_polygon_union (twin: host_polygon_union_cut)."""
+        a, counts, b, F, row, rrow, ver = _polygon_union_args(rings_a, ring_b, frames)
+        _check(self.L, self.L.cape_debug_polygon_union_cut(self.h, a.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), len(counts),
+                                                           b.ctypes.data_as(C.c_void_p), len(b), None if F is None else F.ctypes.data_as(C.c_void_p),
+                                                           row.ctypes.data_as(C.c_void_p), rrow.ctypes.data_as(C.c_void_p),
+                                                           ver.ctypes.data_as(C.c_void_p)), "cape_debug_polygon_union_cut")
         return row[0], rrow[0], _union_polygons(row, rrow, ver)[0]
 
     def debug_ring_union(self, ring_a, ring_b, frames=None):
