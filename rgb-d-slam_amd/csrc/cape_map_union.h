@@ -1,27 +1,35 @@
 // The polygon half of the map update for one matched pair (cape_map_union.hip, cape_debug_ring_union): the statements of
 // Polygon::project, merge_union, rings_union_outer, drop_collinear, ring_is_simple, simplify, douglas_peucker and segment_distance2 of
-// host/boundary_polygon.cpp in the host's order and with its early exits, on ONE wavefront: union_pair for a map polygon without holes
-// whose union creates none, and beside it union_pair_holes (cape_map_union_holes, cape_debug_polygon_union) with add_hole,
-// carry_hole's kept and covered cases, Polygon::area and simplify over interior rings as well; a hole the detection covers in part
-// stays the host's.  The two modes call one copy of every per-lane and per-wave function and of the steps that cost nothing to share:
-// the placement of the operands (union_place_operands), the Douglas-Peucker loop (union_dp_candidate), union_orient with its sense,
-// union_area on union_area_holed, union_hosted.  The arrangement (step 3 up to the last link), the start of the outer walk, the test
-// of a walked face and union_left_out's loop stand in both modes, for a measured reason: shared as plain __forceinline__ functions
-// they compute the same rows, but the optimiser simplifies a callee before it inlines it, the register allocation moves, and on an
-// MI355X a call's median then left the spread of the restated build by 0.05 to 0.3 % (profiles/map_union_shared_steps.txt).  An
-// edit to one of those copies is made in union_pair and in union_pair_holes.
-// A third mode, union_pair_cut (cape_map_union_cut, cape_debug_polygon_union_cut), also serves the hole the detection covers in part:
-// it runs the arrangement twice inside a pair -- rule 0 on (map ring, detection) for the union and its new holes, rule 1 on (hole,
-// detection) for the pieces of hole minus detection -- and so has ONE function for it, union_arrange, with the walked-face test
-// and the storing of a face inside.  union_pair and union_pair_holes are NOT routed through union_arrange and keep their restated
-// copies: that is the sharing the measurement above decided against, and it has not been measured again for this function; an edit
-// to the arrangement is therefore made in three places on the device (union_pair, union_pair_holes, union_arrange) and once in the
-// ports (seq::Arrangement).
+// host/boundary_polygon.cpp in the host's order and with its early exits, on ONE wavefront.  Two pair functions:
+//   union_pair               for a map polygon without holes whose union creates none (cape_map_union, cape_debug_ring_union);
+//   union_pair_rings<Cuts>   for the modes with rings, one text: with add_hole, carry_hole's kept and covered cases, Polygon::area and
+//       simplify over interior rings as well.  Cuts = false is the holes mode (cape_map_union_holes, cape_debug_polygon_union), where
+//       a hole the detection covers in part stays the host's; Cuts = true the cut mode (cape_map_union_cut,
+//       cape_debug_polygon_union_cut), which cuts such a hole into its pieces by a second arrangement inside the pair -- rule 1 of
+//       union_arrange on (hole, detection).  `if constexpr (Cuts)` stands at the three places the two differ: that branch of the
+//       carried-holes loop, the HOST_HOLE_CUT return, the HOLE_PIECES flag.
+// Every per-lane and per-wave function stands once, and so do the steps that cost nothing to share: the placement of the operands
+// (union_place_operands), the Douglas-Peucker loop (union_dp_candidate), union_orient with its sense, union_area on
+// union_area_holed, union_hosted.  Everything of the modes with rings from the placement of the operands through step 6 stands once,
+// in union_pair_rings.
+// What still stands more than once, and why.  The arrangement (step 3 up to the last link), the start of the outer walk, the test of
+// a walked face and union_left_out's loop stand in union_pair and in union_pair_rings, for a measured reason: shared as plain
+// __forceinline__ functions they compute the same rows, but the optimiser simplifies a callee before it inlines it, the register
+// allocation moves, and on an MI355X a call's median then left the spread of the restated build by 0.05 to 0.3 %
+// (profiles/map_union_shared_steps.txt).  union_pair folded into the template as a third mode was tried and measured too
+// (profiles/map_union_one_pair.txt): the plain frame kernel grows from 6 952 to 7 138 instructions, and cape_map_union's median
+// leaves the parent's spread by 0.9 to 1.4 % in three of its four timed settings, so union_pair stays.  The arrangement with the face
+// test also stands in union_arrange, which union_pair_rings<true> calls for the second arrangement only (rule 1; its rule 0 is the
+// first arrangement and is kept for the one-lane port, which runs both): the first arrangement of union_pair_rings is the inline
+// one in both modes, which is what keeps the holes kernels the parent's instructions.  So the arrangement stands in three places
+// on the device (union_pair, union_pair_rings, union_arrange) and once in the ports (seq::Arrangement); the evidence for the one pair function of the modes with rings -- the holes kernels are the
+// parent's instructions, the cut call's median lies inside the parent's spread -- is in profiles/map_union_one_pair.txt.
 //
 // Two parts.  The first holds the plain per-lane functions (projection, cut parameters, crossing points, the angle of the face walk
 // with its guard band, the collinear test, the Douglas-Peucker distance, the bounding-box test in front of a hole's intersection): they
 // need nothing of the wave and compile for the host too (tests/host/map_union_algebra.cpp and map_union_holes_algebra.cpp compare them
-// and one-lane ports of both modes with the host class under the sanitizers).  The second, under __HIPCC__, is the
+// and one-lane ports of the modes, map_union_cut_algebra.cpp the cut mode's, with the host class under the sanitizers).  The second,
+// under __HIPCC__, is the
 // wave's part: the LDS carve, node_of's search (ballot, lowest set lane), the walks, the point tests, ring_is_simple and the
 // Douglas-Peucker loop.  What the host orders is uniform control flow: node numbering, the walks, drop_collinear's erase loop.
 //
@@ -817,7 +825,7 @@ __device__ __forceinline__ int union_walk_face(const UnionLds& L, UnionGraph& G,
     return -1;
 }
 
-// ---- the steps of a pair that both modes run (union_pair, union_pair_holes)
+// ---- the steps of a pair that every mode runs (union_pair, union_pair_rings)
 // Steps 1 and 2.  L.ringA[0, nA) holds the map polygon's ring in its frame `fa` (oriented or not), L.ringB[0, nB) the detection's
 // world ring in its frame `fb`; both end up oriented in `frame`: the target, or the map polygon's own where Polygon::project's
 // isApprox shortcut holds.  Returns whether Polygon::project ran.
@@ -1176,13 +1184,281 @@ struct UnionHoleFetch
     }
 };
 
-// The same pair in the holes mode (cape_map_union_holes, cape_debug_polygon_union): union_pair's steps -- the shared ones through the
-// same functions, step 3 and the face test restated (see the head of this file) -- with the host's hole statements between them.  H.src / srcOff / srcLen describe the map plane's
-// interior rings (H.nSrc <= kUnionHoles of 3 .. kUnionRing vertices each, inside their buffer: the caller has checked), which are
-// fetched, oriented and projected where the host's statements read them; faces the union encloses and holes the detection leaves alone
-// become the result's interior rings (`holes`; the rings in H.holes / H.holeLen).  Never HOST_MAP_HOLES or HOST_NEW_HOLE.
-__device__ inline UnionResult union_pair_holes(const UnionLds& L, const UnionHolesLds& H, int nA, int nB, const UnionFrame& fa, const UnionFrame& fb,
-                                               const UnionFrame& target, UnionFrame& frame, UnionHoleResult& holes, int lane)
+// ---- the cut mode (cape_map_union_cut, cape_debug_polygon_union_cut): the holes mode, and a hole of the map plane the detection
+// covers in part is cut into its pieces by a second arrangement inside the pair.
+// The carve is the holes mode's, byte for byte.  The one thing the second arrangement cannot keep where the first has it is the
+// sorted cut list: L.sortT aliases L.outer, which holds the union's outer ring by then.  It goes, with its segment numbers, to the
+// intersection's heights (`by`), dead between two rings_inter_area calls.  Everything else of an arrangement -- the segment list,
+// the cuts, the nodes, the adjacency, the degrees, the seen bits -- lies in [segs, outer), which only the intersection borrows and
+// which is dead once that has returned for the hole; the walked faces, the second outer face among them, go to L.face (the
+// intersection's bk / inc, as dead).  Live throughout: L.ringB, L.outer, H.holes, H.holeLen, H.srcOff, H.srcLen.
+struct UnionCutLdsLayout
+{
+    size_t sortT, sortSeg, bytes;
+};
+__host__ __device__ constexpr UnionCutLdsLayout union_cut_layout()
+{
+    constexpr UnionHolesLdsLayout h = union_holes_layout();
+    UnionCutLdsLayout o{};
+    Layout by; // [by, by + the heights)
+    by.off = h.by;
+    o.sortT = by.take<double>(kUnionCuts);
+    o.sortSeg = by.take<unsigned short>(kUnionCuts);
+    CAPE_LAYOUT_CHECK(by.off <= h.by + 128 * kUnionMpStack * sizeof(double));
+    o.bytes = h.bytes;
+    return o;
+}
+static_assert(kUnionCuts * (sizeof(double) + sizeof(unsigned short)) <= 128 * kUnionMpStack * sizeof(double), "the second arrangement's sorted cuts fit the heights' place");
+static_assert(union_cut_layout().sortT >= union_layout().bytes, "the second arrangement's sorted cuts lie behind the first carve: clear of L.outer and L.face");
+static_assert(union_cut_layout().bytes == union_holes_layout().bytes && 2 * union_cut_layout().bytes <= 160 * 1024, "two waves' carves fit the LDS of a CU");
+
+struct UnionCutLds
+{
+    double* sortT; // the second arrangement's sorted cuts
+    unsigned short* sortSeg;
+};
+__device__ __forceinline__ UnionCutLds union_cut_carve(unsigned char* smem)
+{
+    constexpr UnionCutLdsLayout o = union_cut_layout();
+    UnionCutLds C;
+    C.sortT = carve_at<double>(smem, o.sortT);
+    C.sortSeg = carve_at<unsigned short>(smem, o.sortSeg);
+    return C;
+}
+
+// One arrangement of two rings and its faces: rings_union_outer(A, B, &holes, rule) followed by what merge_union does with every
+// face it returns.  Rule 0 on (map ring, detection) gives the union and its new holes, rule 1 on (hole, detection) the pieces of a
+// partly covered hole; the cut mode calls it with rule 1 only, its first arrangement being union_pair_rings' own.  Everything rings_union_outer derives from its operands is derived here from
+// S.A and S.B: scale and eps, the segment list, the cuts and their order, the nodes and links, the start node and its first slot.
+struct UnionArrangeSpec
+{
+    const double2 *A, *B; // both operands in one frame
+    int nA, nB;
+    int rule;             // 0: a face inside neither operand (a hole of the union); 1: inside or on A and not inside or on B (a piece of A \ B)
+    double tiny;          // rule 1: a piece's |signed area| exceeds it (carry_hole)
+    double* sortT;        // the sorted cuts: kUnionCuts each, dead once the nodes are numbered
+    unsigned short* sortSeg;
+    double2* outer;       // where the outer face is walked (kUnionOut + 1)
+};
+// The faces that pass are oriented by add_hole and appended to H.holes / H.holeLen at (count, vertices): all of them counted, stored
+// while they fit.  nOuter: the outer face's length.  Returns 0, or the CAPE_UNION_HOST_* bits that end the pair.
+__device__ __forceinline__ uint32_t union_arrange(const UnionLds& L, const UnionHolesLds& H, const UnionArrangeSpec& S, UnionGraph& G, int& nOuter,
+                                                  int& count, int& vertices, int lane)
+{
+    const double2 *A = S.A, *B = S.B;
+    const int nA = S.nA, nB = S.nB;
+    double scale = 1.0;
+    for (int v = 0; v < nA; ++v)
+        scale = umax(scale, umax(fabs(A[v].x), fabs(A[v].y)));
+    for (int v = 0; v < nB; ++v)
+        scale = umax(scale, umax(fabs(B[v].x), fabs(B[v].y)));
+    const double eps = 1e-9 * scale;
+    G.eps = eps;
+    // the segment list without `same` endpoints, ring A's first (ballot compaction keeps ring order)
+    int nSegA = 0, nSeg = 0;
+    for (int r = 0; r < 2; ++r)
+    {
+        const double2* R = r ? B : A;
+        const int nR = r ? nB : nA;
+        for (int base = 0; base < nR; base += 64)
+        {
+            const int i = base + lane;
+            const bool keep = i < nR && !usame(R[i], R[i + 1 == nR ? 0 : i + 1], eps);
+            const unsigned long long kb = __ballot(keep);
+            if (keep)
+                L.segs[nSeg + __popcll(kb & ((1ull << lane) - 1ull))] = (unsigned short)((r << 8) | i);
+            nSeg += __popcll(kb);
+        }
+        if (r == 0)
+            nSegA = nSeg;
+    }
+    CAPE_MP_SYNC();
+    const int nSegB = nSeg - nSegA;
+    auto seg_a = [&](int s) {
+        const unsigned e = L.segs[s];
+        return (e >> 8) ? B[e & 0xFF] : A[e & 0xFF];
+    };
+    auto seg_b = [&](int s) {
+        const unsigned e = L.segs[s];
+        const int i = (int)(e & 0xFF);
+        return (e >> 8) ? B[i + 1 == nB ? 0 : i + 1] : A[i + 1 == nA ? 0 : i + 1];
+    };
+    // the cuts of every (A segment, B segment): lanes over the pairs, six possible cuts each, appended in ballot order (the per-segment
+    // sort below makes the order of arrival irrelevant)
+    int nCuts = 0;
+    bool cutOverflow = false;
+    for (int base = 0; base < nSegA * nSegB; base += 64)
+    {
+        const int q = base + lane;
+        const bool live = q < nSegA * nSegB;
+        double t[6] = {0, 0, 0, 0, 0, 0};
+        bool has[6] = {false, false, false, false, false, false};
+        int si = 0, ui = 0;
+        if (live)
+        {
+            si = q / nSegB;
+            ui = nSegA + q % nSegB;
+            const double2 sa = seg_a(si), sb = seg_b(si), ua = seg_a(ui), ub = seg_b(ui);
+            has[0] = union_param_on(sa, sb, ua, eps, t[0]);
+            has[1] = union_param_on(sa, sb, ub, eps, t[1]);
+            has[3] = union_param_on(ua, ub, sa, eps, t[3]);
+            has[4] = union_param_on(ua, ub, sb, eps, t[4]);
+            bool ks = false, ku = false;
+            if (union_crossing(sa, sb, ua, ub, eps, t[2], ks, t[5], ku))
+            {
+                has[2] = ks;
+                has[5] = ku;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c)
+        {
+            const unsigned long long m = __ballot(has[c]);
+            const int at = nCuts + __popcll(m & ((1ull << lane) - 1ull));
+            if (has[c] && at < kUnionCuts)
+            {
+                L.cutT[at] = t[c];
+                L.cutSeg[at] = (unsigned short)(c < 3 ? si : ui);
+            }
+            nCuts += __popcll(m);
+        }
+        if (nCuts > kUnionCuts)
+        {
+            cutOverflow = true;
+            break;
+        }
+    }
+    CAPE_MP_SYNC();
+    if (cutOverflow)
+        return CAPE_UNION_HOST_CAPACITY;
+    // the cuts in (segment, parameter) order: a rank sort on the parameters' bit patterns (non-negative doubles: the numbers' order)
+    for (int base = 0; base < nCuts; base += 64)
+    {
+        const int c = base + lane;
+        if (c < nCuts)
+        {
+            const unsigned sc = L.cutSeg[c];
+            const unsigned long long tc = (unsigned long long)__double_as_longlong(L.cutT[c]);
+            int rank = 0;
+            for (int k = 0; k < nCuts; ++k)
+            {
+                const unsigned sk = L.cutSeg[k];
+                const unsigned long long tk = (unsigned long long)__double_as_longlong(L.cutT[k]);
+                rank += (sk < sc || (sk == sc && (tk < tc || (tk == tc && k < c)))) ? 1 : 0;
+            }
+            S.sortT[rank] = L.cutT[c];
+            S.sortSeg[rank] = (unsigned short)sc;
+        }
+    }
+    CAPE_MP_SYNC();
+    // nodes and undirected edges in the host's order: segments in order, cuts ascending, the first node within eps wins
+    int at = 0;
+    for (int s = 0; s < nSeg && !G.fail; ++s)
+    {
+        const double2 a = seg_a(s), b = seg_b(s);
+        int prev = union_node_of(L, G, a, lane);
+        while (at < nCuts && uni(S.sortSeg[at]) == s && !G.fail)
+        {
+            const int cur = union_node_of(L, G, union_cut_point(a, b, S.sortT[at]), lane);
+            union_link(L, G, prev, cur, lane);
+            prev = cur;
+            ++at;
+        }
+        if (!G.fail)
+            union_link(L, G, prev, union_node_of(L, G, b, lane), lane);
+    }
+    CAPE_MP_SYNC(); // (the sorted cuts are dead)
+    if (G.fail)
+        return G.fail;
+    nOuter = 0;
+    if (G.nNodes >= 3)
+    {
+        // the outer face from the lowest of the leftmost nodes, reached heading south
+        int start = 0;
+        for (int k = 1; k < G.nNodes; ++k)
+        {
+            const double2 pk = L.nodes[k], ps = L.nodes[start];
+            if (pk.x < ps.x - eps || (fabs(pk.x - ps.x) <= eps && pk.y < ps.y))
+                start = k;
+        }
+        const int firstSlot = union_next_of(L, G, start, make_double2(0.0, 1.0), -1, lane);
+        if (firstSlot >= 0)
+        {
+            nOuter = union_walk_face(L, G, start, firstSlot, S.outer, lane);
+            if (nOuter < 0)
+                return G.fail | CAPE_UNION_HOST_CAPACITY;
+            // every other face: bounded, walked clockwise, judged by the rule on a point strictly inside it
+            for (int a = 0; a < G.nNodes && nOuter > 0; ++a)
+            {
+                const int da = uni(L.deg[a]);
+                for (int k = 0; k < da && k < kUnionDegree; ++k)
+                {
+                    if ((uni(L.seen[a]) >> k) & 1)
+                        continue;
+                    int nf = union_walk_face(L, G, a, k, L.face, lane);
+                    if (nf < 0)
+                        return G.fail | CAPE_UNION_HOST_CAPACITY;
+                    if (nf < 3 || ring_area_signed(L.face, nf) >= 0)
+                        continue; // not a bounded face (or a degenerate spur)
+                    // a point strictly inside the face: just right of the middle of one of its edges
+                    bool found = false;
+                    double2 probe = make_double2(0.0, 0.0);
+                    for (int i = 0; i < nf && !found; ++i)
+                    {
+                        const double2 p = L.face[i], q = L.face[i + 1 == nf ? 0 : i + 1];
+                        const double dx = q.x - p.x, dy = q.y - p.y, len = hypot(dx, dy);
+                        if (len <= eps)
+                            continue;
+                        int step = 0;
+                        for (double off = 1e-3; off >= 1e-7 && !found && step < 8; off *= 0.1, ++step)
+                        {
+                            probe = make_double2(0.5 * (p.x + q.x) + off * len * (dy / len), 0.5 * (p.y + q.y) - off * len * (dx / len));
+                            found = union_point_in_ring(probe, L.face, nf, false, lane);
+                        }
+                    }
+                    if (!found)
+                        continue;
+                    const bool inA = union_point_in_ring(probe, A, nA, true, lane), inB = union_point_in_ring(probe, B, nB, true, lane);
+                    if (S.rule == 0 ? (inA || inB) : (!inA || inB))
+                        continue;
+                    // merge_union's own test of a hole, carry_hole's of a piece: drop_collinear, then at least 3 vertices, simple
+                    // and -- a piece -- more than `tiny`
+                    nf = union_drop_collinear(L.face, nf, lane);
+                    if (nf >= 3 && union_ring_is_simple(L.face, nf, lane) && (S.rule == 0 || fabs(ring_area_signed(L.face, nf)) > S.tiny))
+                    {
+                        if (count < kUnionHoles && vertices + nf <= kUnionHoleVertices)
+                        {
+                            union_orient(L.face, nf, lane, true); // add_hole
+                            for (int v = lane; v < nf; v += 64)
+                                H.holes[vertices + v] = L.face[v];
+                            if (lane == 0)
+                                H.holeLen[count] = (unsigned short)nf;
+                            CAPE_MP_SYNC();
+                        }
+                        ++count;
+                        vertices += nf;
+                    }
+                }
+            }
+        }
+    }
+    return G.fail;
+}
+
+// The same pair in the modes with rings: the holes mode (Cuts = false: cape_map_union_holes, cape_debug_polygon_union) and the cut
+// mode (Cuts = true: cape_map_union_cut, cape_debug_polygon_union_cut), one text with `if constexpr (Cuts)` at the three places they
+// differ.  union_pair's steps -- the shared ones through the same functions, step 3 and the face test restated (see the head of this
+// file) -- with the host's hole statements between them.  H.src / srcOff / srcLen describe the map plane's interior rings (H.nSrc <=
+// kUnionHoles of 3 .. kUnionRing vertices each, inside their buffer: the caller has checked), which are fetched, oriented and
+// projected where the host's statements read them; faces the union encloses and holes the detection leaves alone become the result's
+// interior rings (`holes`; the rings in H.holes / H.holeLen).  A hole the detection covers in part is the host's in the holes mode
+// (HOST_HOLE_CUT); in the cut mode union_arrange runs on (the hole as fetch.hole put it into L.ringA, the detection) with rule 1 and
+// the sorted cuts in C, and its pieces follow the interior rings stored so far, so that the rings stand as merge_union appends them.
+// A pair without such a hole computes the same result in both modes, bit for bit.  C is read in the cut mode only.  Never
+// HOST_MAP_HOLES or HOST_NEW_HOLE; never HOST_HOLE_CUT in the cut mode.
+template <bool Cuts>
+__device__ inline UnionResult union_pair_rings(const UnionLds& L, const UnionHolesLds& H, const UnionCutLds& C, int nA, int nB, const UnionFrame& fa,
+                                               const UnionFrame& fb, const UnionFrame& target, UnionFrame& frame, UnionHoleResult& holes, int lane)
 {
     UnionResult res{};
     const bool projected = union_place_operands(L, nA, nB, fa, fb, target, frame, lane);
@@ -1444,394 +1720,9 @@ __device__ inline UnionResult union_pair_holes(const UnionLds& L, const UnionHol
     res.ring = out;
     // ---- 6. the interior rings.  The detection is the bigger piece of two: none (it has none).  Otherwise the faces stored
     // above, then the map plane's holes in their order (carry_hole): kept where the detection covers at most `tiny` of them,
-    // gone where it covers them, the host's where it covers a part.  Everything is counted, stored while it fits, and judged at
-    // the end: a partly covered hole first, then the capacities.
-    int nHoles = 0, holeVertices = 0;
-    bool cut = false;
-    if (!rule)
-    {
-        nHoles = nNew;
-        holeVertices = newVertices;
-        holes.holesNew = (uint32_t)nNew;
-        const double tiny = 1e-12 * umax(areaA, areaB);
-        for (int k = 0; k < H.nSrc; ++k)
-        {
-            const int nh = fetch.hole(k, L.ringA); // (ring A is dead: the outer ring stands in L.outer)
-            const double inter = union_boxes_apart(L.ringA, nh, B, nB) ? 0.0 : rings_inter_area<kUnionMpStack, kUnionMpXs>(H.mp, nh, nB, lane);
-            if (inter != inter) // one of its capacities
-                return hosted(CAPE_UNION_HOST_CAPACITY);
-            const double covered = inter < 0 ? 0.0 : inter;
-            if (covered <= tiny)
-            {
-                if (nHoles < kUnionHoles && holeVertices + nh <= kUnionHoleVertices)
-                {
-                    for (int v = lane; v < nh; v += 64)
-                        H.holes[holeVertices + v] = L.ringA[v];
-                    if (lane == 0)
-                        H.holeLen[nHoles] = (unsigned short)nh;
-                }
-                ++nHoles;
-                holeVertices += nh;
-                ++holes.holesKept;
-            }
-            else if (inter < fabs(ring_area_signed(L.ringA, nh)) - tiny)
-                cut = true;
-            else
-                ++holes.holesCovered;
-            CAPE_MP_SYNC();
-        }
-    }
-    if (cut)
-        return hosted(CAPE_UNION_HOST_HOLE_CUT);
-    if (nHoles > kUnionHoles || holeVertices > kUnionHoleVertices)
-        return hosted(CAPE_UNION_HOST_CAPACITY);
-    holes.nHoles = nHoles;
-    res.flags |= nHoles > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u;
-    res.n = union_simplify_holed(L, H, out, nOuter, nHoles, L.face, res.area, lane);
-    return res;
-}
-
-// ---- the cut mode (cape_map_union_cut, cape_debug_polygon_union_cut): the holes mode, and a hole of the map plane the detection
-// covers in part is cut into its pieces by a second arrangement inside the pair.
-// The carve is the holes mode's, byte for byte.  The one thing the second arrangement cannot keep where the first has it is the
-// sorted cut list: L.sortT aliases L.outer, which holds the union's outer ring by then.  It goes, with its segment numbers, to the
-// intersection's heights (`by`), dead between two rings_inter_area calls.  Everything else of an arrangement -- the segment list,
-// the cuts, the nodes, the adjacency, the degrees, the seen bits -- lies in [segs, outer), which only the intersection borrows and
-// which is dead once that has returned for the hole; the walked faces, the second outer face among them, go to L.face (the
-// intersection's bk / inc, as dead).  Live throughout: L.ringB, L.outer, H.holes, H.holeLen, H.srcOff, H.srcLen.
-struct UnionCutLdsLayout
-{
-    size_t sortT, sortSeg, bytes;
-};
-__host__ __device__ constexpr UnionCutLdsLayout union_cut_layout()
-{
-    constexpr UnionHolesLdsLayout h = union_holes_layout();
-    UnionCutLdsLayout o{};
-    Layout by; // [by, by + the heights)
-    by.off = h.by;
-    o.sortT = by.take<double>(kUnionCuts);
-    o.sortSeg = by.take<unsigned short>(kUnionCuts);
-    CAPE_LAYOUT_CHECK(by.off <= h.by + 128 * kUnionMpStack * sizeof(double));
-    o.bytes = h.bytes;
-    return o;
-}
-static_assert(kUnionCuts * (sizeof(double) + sizeof(unsigned short)) <= 128 * kUnionMpStack * sizeof(double), "the second arrangement's sorted cuts fit the heights' place");
-static_assert(union_cut_layout().sortT >= union_layout().bytes, "the second arrangement's sorted cuts lie behind the first carve: clear of L.outer and L.face");
-static_assert(union_cut_layout().bytes == union_holes_layout().bytes && 2 * union_cut_layout().bytes <= 160 * 1024, "two waves' carves fit the LDS of a CU");
-
-struct UnionCutLds
-{
-    double* sortT; // the second arrangement's sorted cuts
-    unsigned short* sortSeg;
-};
-__device__ __forceinline__ UnionCutLds union_cut_carve(unsigned char* smem)
-{
-    constexpr UnionCutLdsLayout o = union_cut_layout();
-    UnionCutLds C;
-    C.sortT = carve_at<double>(smem, o.sortT);
-    C.sortSeg = carve_at<unsigned short>(smem, o.sortSeg);
-    return C;
-}
-
-// One arrangement of two rings and its faces: rings_union_outer(A, B, &holes, rule) followed by what merge_union does with every
-// face it returns.  The cut mode calls it twice: rule 0 on (map ring, detection) for the union and its new holes, rule 1 on (hole,
-// detection) for the pieces of a partly covered hole.  Everything rings_union_outer derives from its operands is derived here from
-// S.A and S.B: scale and eps, the segment list, the cuts and their order, the nodes and links, the start node and its first slot.
-struct UnionArrangeSpec
-{
-    const double2 *A, *B; // both operands in one frame
-    int nA, nB;
-    int rule;             // 0: a face inside neither operand (a hole of the union); 1: inside or on A and not inside or on B (a piece of A \ B)
-    double tiny;          // rule 1: a piece's |signed area| exceeds it (carry_hole)
-    double* sortT;        // the sorted cuts: kUnionCuts each, dead once the nodes are numbered
-    unsigned short* sortSeg;
-    double2* outer;       // where the outer face is walked (kUnionOut + 1)
-};
-// The faces that pass are oriented by add_hole and appended to H.holes / H.holeLen at (count, vertices): all of them counted, stored
-// while they fit.  nOuter: the outer face's length.  Returns 0, or the CAPE_UNION_HOST_* bits that end the pair.
-__device__ __forceinline__ uint32_t union_arrange(const UnionLds& L, const UnionHolesLds& H, const UnionArrangeSpec& S, UnionGraph& G, int& nOuter,
-                                                  int& count, int& vertices, int lane)
-{
-    const double2 *A = S.A, *B = S.B;
-    const int nA = S.nA, nB = S.nB;
-    double scale = 1.0;
-    for (int v = 0; v < nA; ++v)
-        scale = umax(scale, umax(fabs(A[v].x), fabs(A[v].y)));
-    for (int v = 0; v < nB; ++v)
-        scale = umax(scale, umax(fabs(B[v].x), fabs(B[v].y)));
-    const double eps = 1e-9 * scale;
-    G.eps = eps;
-    // the segment list without `same` endpoints, ring A's first (ballot compaction keeps ring order)
-    int nSegA = 0, nSeg = 0;
-    for (int r = 0; r < 2; ++r)
-    {
-        const double2* R = r ? B : A;
-        const int nR = r ? nB : nA;
-        for (int base = 0; base < nR; base += 64)
-        {
-            const int i = base + lane;
-            const bool keep = i < nR && !usame(R[i], R[i + 1 == nR ? 0 : i + 1], eps);
-            const unsigned long long kb = __ballot(keep);
-            if (keep)
-                L.segs[nSeg + __popcll(kb & ((1ull << lane) - 1ull))] = (unsigned short)((r << 8) | i);
-            nSeg += __popcll(kb);
-        }
-        if (r == 0)
-            nSegA = nSeg;
-    }
-    CAPE_MP_SYNC();
-    const int nSegB = nSeg - nSegA;
-    auto seg_a = [&](int s) {
-        const unsigned e = L.segs[s];
-        return (e >> 8) ? B[e & 0xFF] : A[e & 0xFF];
-    };
-    auto seg_b = [&](int s) {
-        const unsigned e = L.segs[s];
-        const int i = (int)(e & 0xFF);
-        return (e >> 8) ? B[i + 1 == nB ? 0 : i + 1] : A[i + 1 == nA ? 0 : i + 1];
-    };
-    // the cuts of every (A segment, B segment): lanes over the pairs, six possible cuts each, appended in ballot order (the per-segment
-    // sort below makes the order of arrival irrelevant)
-    int nCuts = 0;
-    bool cutOverflow = false;
-    for (int base = 0; base < nSegA * nSegB; base += 64)
-    {
-        const int q = base + lane;
-        const bool live = q < nSegA * nSegB;
-        double t[6] = {0, 0, 0, 0, 0, 0};
-        bool has[6] = {false, false, false, false, false, false};
-        int si = 0, ui = 0;
-        if (live)
-        {
-            si = q / nSegB;
-            ui = nSegA + q % nSegB;
-            const double2 sa = seg_a(si), sb = seg_b(si), ua = seg_a(ui), ub = seg_b(ui);
-            has[0] = union_param_on(sa, sb, ua, eps, t[0]);
-            has[1] = union_param_on(sa, sb, ub, eps, t[1]);
-            has[3] = union_param_on(ua, ub, sa, eps, t[3]);
-            has[4] = union_param_on(ua, ub, sb, eps, t[4]);
-            bool ks = false, ku = false;
-            if (union_crossing(sa, sb, ua, ub, eps, t[2], ks, t[5], ku))
-            {
-                has[2] = ks;
-                has[5] = ku;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-        {
-            const unsigned long long m = __ballot(has[c]);
-            const int at = nCuts + __popcll(m & ((1ull << lane) - 1ull));
-            if (has[c] && at < kUnionCuts)
-            {
-                L.cutT[at] = t[c];
-                L.cutSeg[at] = (unsigned short)(c < 3 ? si : ui);
-            }
-            nCuts += __popcll(m);
-        }
-        if (nCuts > kUnionCuts)
-        {
-            cutOverflow = true;
-            break;
-        }
-    }
-    CAPE_MP_SYNC();
-    if (cutOverflow)
-        return CAPE_UNION_HOST_CAPACITY;
-    // the cuts in (segment, parameter) order: a rank sort on the parameters' bit patterns (non-negative doubles: the numbers' order)
-    for (int base = 0; base < nCuts; base += 64)
-    {
-        const int c = base + lane;
-        if (c < nCuts)
-        {
-            const unsigned sc = L.cutSeg[c];
-            const unsigned long long tc = (unsigned long long)__double_as_longlong(L.cutT[c]);
-            int rank = 0;
-            for (int k = 0; k < nCuts; ++k)
-            {
-                const unsigned sk = L.cutSeg[k];
-                const unsigned long long tk = (unsigned long long)__double_as_longlong(L.cutT[k]);
-                rank += (sk < sc || (sk == sc && (tk < tc || (tk == tc && k < c)))) ? 1 : 0;
-            }
-            S.sortT[rank] = L.cutT[c];
-            S.sortSeg[rank] = (unsigned short)sc;
-        }
-    }
-    CAPE_MP_SYNC();
-    // nodes and undirected edges in the host's order: segments in order, cuts ascending, the first node within eps wins
-    int at = 0;
-    for (int s = 0; s < nSeg && !G.fail; ++s)
-    {
-        const double2 a = seg_a(s), b = seg_b(s);
-        int prev = union_node_of(L, G, a, lane);
-        while (at < nCuts && uni(S.sortSeg[at]) == s && !G.fail)
-        {
-            const int cur = union_node_of(L, G, union_cut_point(a, b, S.sortT[at]), lane);
-            union_link(L, G, prev, cur, lane);
-            prev = cur;
-            ++at;
-        }
-        if (!G.fail)
-            union_link(L, G, prev, union_node_of(L, G, b, lane), lane);
-    }
-    CAPE_MP_SYNC(); // (the sorted cuts are dead)
-    if (G.fail)
-        return G.fail;
-    nOuter = 0;
-    if (G.nNodes >= 3)
-    {
-        // the outer face from the lowest of the leftmost nodes, reached heading south
-        int start = 0;
-        for (int k = 1; k < G.nNodes; ++k)
-        {
-            const double2 pk = L.nodes[k], ps = L.nodes[start];
-            if (pk.x < ps.x - eps || (fabs(pk.x - ps.x) <= eps && pk.y < ps.y))
-                start = k;
-        }
-        const int firstSlot = union_next_of(L, G, start, make_double2(0.0, 1.0), -1, lane);
-        if (firstSlot >= 0)
-        {
-            nOuter = union_walk_face(L, G, start, firstSlot, S.outer, lane);
-            if (nOuter < 0)
-                return G.fail | CAPE_UNION_HOST_CAPACITY;
-            // every other face: bounded, walked clockwise, judged by the rule on a point strictly inside it
-            for (int a = 0; a < G.nNodes && nOuter > 0; ++a)
-            {
-                const int da = uni(L.deg[a]);
-                for (int k = 0; k < da && k < kUnionDegree; ++k)
-                {
-                    if ((uni(L.seen[a]) >> k) & 1)
-                        continue;
-                    int nf = union_walk_face(L, G, a, k, L.face, lane);
-                    if (nf < 0)
-                        return G.fail | CAPE_UNION_HOST_CAPACITY;
-                    if (nf < 3 || ring_area_signed(L.face, nf) >= 0)
-                        continue; // not a bounded face (or a degenerate spur)
-                    // a point strictly inside the face: just right of the middle of one of its edges
-                    bool found = false;
-                    double2 probe = make_double2(0.0, 0.0);
-                    for (int i = 0; i < nf && !found; ++i)
-                    {
-                        const double2 p = L.face[i], q = L.face[i + 1 == nf ? 0 : i + 1];
-                        const double dx = q.x - p.x, dy = q.y - p.y, len = hypot(dx, dy);
-                        if (len <= eps)
-                            continue;
-                        int step = 0;
-                        for (double off = 1e-3; off >= 1e-7 && !found && step < 8; off *= 0.1, ++step)
-                        {
-                            probe = make_double2(0.5 * (p.x + q.x) + off * len * (dy / len), 0.5 * (p.y + q.y) - off * len * (dx / len));
-                            found = union_point_in_ring(probe, L.face, nf, false, lane);
-                        }
-                    }
-                    if (!found)
-                        continue;
-                    const bool inA = union_point_in_ring(probe, A, nA, true, lane), inB = union_point_in_ring(probe, B, nB, true, lane);
-                    if (S.rule == 0 ? (inA || inB) : (!inA || inB))
-                        continue;
-                    // merge_union's own test of a hole, carry_hole's of a piece: drop_collinear, then at least 3 vertices, simple
-                    // and -- a piece -- more than `tiny`
-                    nf = union_drop_collinear(L.face, nf, lane);
-                    if (nf >= 3 && union_ring_is_simple(L.face, nf, lane) && (S.rule == 0 || fabs(ring_area_signed(L.face, nf)) > S.tiny))
-                    {
-                        if (count < kUnionHoles && vertices + nf <= kUnionHoleVertices)
-                        {
-                            union_orient(L.face, nf, lane, true); // add_hole
-                            for (int v = lane; v < nf; v += 64)
-                                H.holes[vertices + v] = L.face[v];
-                            if (lane == 0)
-                                H.holeLen[count] = (unsigned short)nf;
-                            CAPE_MP_SYNC();
-                        }
-                        ++count;
-                        vertices += nf;
-                    }
-                }
-            }
-        }
-    }
-    return G.fail;
-}
-
-// The same pair in the cut mode: union_pair_holes' statements in its order, the arrangement through union_arrange, and in step 6 a
-// partly covered hole is no longer the host's: union_arrange runs again on (the hole as fetch.hole put it into L.ringA, the
-// detection) with rule 1, and its pieces follow the interior rings stored so far, so that the rings stand as merge_union appends
-// them.  A pair without such a hole computes union_pair_holes' result bit for bit.  Never HOST_MAP_HOLES, HOST_NEW_HOLE or
-// HOST_HOLE_CUT.
-__device__ inline UnionResult union_pair_cut(const UnionLds& L, const UnionHolesLds& H, const UnionCutLds& C, int nA, int nB, const UnionFrame& fa, const UnionFrame& fb,
-                                             const UnionFrame& target, UnionFrame& frame, UnionHoleResult& holes, int lane)
-{
-    UnionResult res{};
-    const bool projected = union_place_operands(L, nA, nB, fa, fb, target, frame, lane);
-    const double2 *A = L.ringA, *B = L.ringB;
-    const UnionHoleFetch fetch{H, fa, target, projected, lane};
-    const double areaMap = union_area(A, nA); // Polygon::_area of the projected map polygon (without holes)
-    res.flags = CAPE_UNION_SERVED | CAPE_UNION_UNCHANGED;
-    res.ring = A;
-    res.n = nA;
-    res.area = areaMap;
-    if (nA < 3 || nB < 3)
-        return res;
-    // ---- 3. rings_union_outer(A, B, &holes, 0), and the faces added as holes: all of them counted, stored while they fit
-    UnionGraph G{};
-    int nOuter = 0, nNew = 0, newVertices = 0;
-    {
-        const UnionArrangeSpec first{A, B, nA, nB, 0, 0.0, L.sortT, L.sortSeg, L.outer};
-        const uint32_t bits = union_arrange(L, H, first, G, nOuter, nNew, newVertices, lane);
-        if (bits)
-            return union_hosted(bits, G.nNodes);
-    }
-    res.nNodes = G.nNodes;
-    const auto hosted = [&](uint32_t bits) { return union_hosted(bits, G.nNodes); };
-    // ---- 4. the outer ring: drop_collinear, the disjoint rule, ring_is_simple
-    if (nOuter > 0)
-        nOuter = union_drop_collinear(L.outer, nOuter, lane);
-    const double outerArea = nOuter >= 3 ? fabs(ring_area_signed(L.outer, nOuter)) : 0.0;
-    const double areaA = fabs(ring_area_signed(A, nA)), areaB = fabs(ring_area_signed(B, nB));
-    // an operand none of whose vertices lies inside or on the outer face is a piece of its own (MergeInfo::disjoint); the rule below
-    // catches that when the piece walked is the smaller one
-    bool disjoint = nOuter >= 3 && (union_left_out(A, nA, L.outer, nOuter, lane) || union_left_out(B, nB, L.outer, nOuter, lane));
-    double2* out = L.outer;
-    bool rule = false; // merge_union's own `disjoint`
-    if (outerArea + 1e-9 * umax(areaA, areaB) < umax(areaA, areaB))
-    {
-        disjoint = rule = true;
-        // area() >= o.area(), where area() counts the holes out: this polygon is the bigger piece, simplified as it is, holes and all
-        if (fetch.map_area(A, nA, L.face) >= areaB)
-        {
-            res.flags = CAPE_UNION_SERVED | CAPE_UNION_DISJOINT;
-            if (!fetch.all()) // (the faces stored there are no holes of this result)
-                return hosted(CAPE_UNION_HOST_CAPACITY);
-            holes.nHoles = H.nSrc;
-            res.flags |= H.nSrc > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u;
-            res.n = union_simplify_holed(L, H, L.ringA, nA, H.nSrc, L.face, res.area, lane);
-            res.ring = L.ringA;
-            return res;
-        }
-        for (int v = lane; v < nB; v += 64)
-            out[v] = B[v];
-        nOuter = nB;
-        CAPE_MP_SYNC();
-    }
-    if (nOuter < 3 || !union_ring_is_simple(out, nOuter, lane))
-    {
-        res.flags |= disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u; // merge_union returned false: the projected map polygon stays
-        if (!fetch.all()) // ... with its projected holes
-            return hosted(CAPE_UNION_HOST_CAPACITY);
-        holes.nHoles = H.nSrc;
-        res.flags |= H.nSrc > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u;
-        res.area = union_area_holed(A, nA, H.holes, H.holeLen, H.nSrc);
-        return res;
-    }
-    // ---- 5. Polygon(ring, x, y, c): a repeated closing vertex goes, the ring is oriented; then simplify()
-    if (nOuter > 1 && out[0].x == out[nOuter - 1].x && out[0].y == out[nOuter - 1].y)
-        --nOuter;
-    union_orient(out, nOuter, lane);
-    res.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u);
-    res.ring = out;
-    // ---- 6. the interior rings.  The detection is the bigger piece of two: none (it has none).  Otherwise the faces stored
-    // above, then the map plane's holes in their order (carry_hole): kept where the detection covers at most `tiny` of them,
-    // gone where it covers them, and where it covers a part the pieces of rings_union_outer(hole, detection, &pieces, 1) in
-    // face-walk order.  Everything is counted, stored while it fits, and judged at the end.
+    // gone where it covers them; where it covers a part, the host's in the holes mode, and in the cut mode the pieces of
+    // rings_union_outer(hole, detection, &pieces, 1) in face-walk order.  Everything is counted, stored while it fits, and judged
+    // at the end: a partly covered hole of the holes mode first, then the capacities.
     int nHoles = 0, holeVertices = 0;
     bool cut = false;
     if (!rule)
@@ -1863,26 +1754,35 @@ __device__ inline UnionResult union_pair_cut(const UnionLds& L, const UnionHoles
             else if (inter < fabs(ring_area_signed(L.ringA, nh)) - tiny)
             {
                 cut = true;
-                CAPE_MP_SYNC(); // (the intersection's arrays are dead: the second arrangement takes their place)
-                UnionGraph G2{};
-                int nOuter2 = 0;
-                const UnionArrangeSpec second{L.ringA, B, nh, nB, 1, tiny, C.sortT, C.sortSeg, L.face};
-                const uint32_t bits = union_arrange(L, H, second, G2, nOuter2, nHoles, holeVertices, lane);
-                if (bits)
-                    return hosted(bits);
+                if constexpr (Cuts)
+                {
+                    CAPE_MP_SYNC(); // (the intersection's arrays are dead: the second arrangement takes their place)
+                    UnionGraph G2{};
+                    int nOuter2 = 0;
+                    const UnionArrangeSpec second{L.ringA, B, nh, nB, 1, tiny, C.sortT, C.sortSeg, L.face};
+                    const uint32_t bits = union_arrange(L, H, second, G2, nOuter2, nHoles, holeVertices, lane);
+                    if (bits)
+                        return hosted(bits);
+                }
             }
             else
                 ++holes.holesCovered;
             CAPE_MP_SYNC();
         }
     }
+    if constexpr (!Cuts)
+        if (cut)
+            return hosted(CAPE_UNION_HOST_HOLE_CUT);
     if (nHoles > kUnionHoles || holeVertices > kUnionHoleVertices)
         return hosted(CAPE_UNION_HOST_CAPACITY);
     holes.nHoles = nHoles;
-    res.flags |= (nHoles > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u) | (cut ? (uint32_t)CAPE_UNION_HOLE_PIECES : 0u);
+    res.flags |= nHoles > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u;
+    if constexpr (Cuts)
+        res.flags |= cut ? (uint32_t)CAPE_UNION_HOLE_PIECES : 0u;
     res.n = union_simplify_holed(L, H, out, nOuter, nHoles, L.face, res.area, lane);
     return res;
 }
+
 
 } // namespace
 

@@ -13,15 +13,17 @@
 //        of the slab is CAPE_UNION_HOST_CAPACITY.
 //   cape_ring_union_kernel : the same per-pair function on one pair given by its rings and frames (cape_debug_ring_union).
 //   A frame the wide match flagged CAPE_MATCH_EXACT_OVERFLOW reports nothing: its rows are zeros.
-//   cape_map_union_holes_kernel, cape_polygon_union_kernel : the same two for the holes mode (union_pair_holes: a map plane with
-//        interior rings, a union that encloses faces).  The same rows and slab, where a served polygon's rings lie back to back, plus
-//        a row of ring lengths per kept plane; a larger carve (union_holes_layout).  The two modes share the loading of a pair
-//        (load_map_pair, load_debug_pair).  Pass 1 stands twice, in cape_map_union_kernel and in union_find_pairs for the holes
-//        kernel: called from both, it moved the plain kernel's register allocation, and a call's median left the spread of the
-//        restated build (profiles/map_union_shared_steps.txt).
-//   cape_map_union_cut_kernel, cape_polygon_union_cut_kernel : the same two for the cut mode (union_pair_cut: a hole of the map plane
-//        that the detection covers in part is cut into its pieces by a second arrangement inside the pair).  The rows, slab, rings
-//        rows and carve size of the holes mode; kernels of their own, so that the holes kernels stay the code they were.
+//   cape_map_union_rings_kernel<Cuts>, cape_polygon_union_kernel<Cuts> : the same two for the modes with rings, one template each
+//        over union_pair_rings<Cuts>.  <false> is the holes mode (a map plane with interior rings, a union that encloses faces):
+//        the same rows and slab, where a served polygon's rings lie back to back, plus a row of ring lengths per kept plane; a
+//        larger carve (union_holes_layout).  <true> is the cut mode (a hole of the map plane that the detection covers in part is
+//        cut into its pieces by a second arrangement inside the pair): the rows, slab, rings rows and carve size of the holes
+//        mode, and the second arrangement's sorted cuts (union_cut_carve).  The <false> instantiations are the instructions the
+//        holes kernels were before they were templates, and the cut call's median lies inside its former spread
+//        (profiles/map_union_one_pair.txt).  All modes share the loading of a pair (load_map_pair, load_debug_pair).  Pass 1
+//        stands twice, in cape_map_union_kernel and in union_find_pairs for the kernels with rings: called from both, it moved the
+//        plain kernel's register allocation, and a call's median left the spread of the restated build
+//        (profiles/map_union_shared_steps.txt).
 //
 // Every count read from the map, a row or a table is checked against its buffer before it indexes anything; every loop of union_pair
 // is bounded by a capacity of the carve.
@@ -103,7 +105,7 @@ __device__ __forceinline__ unsigned put_pair(const UnionResult& res, const Union
     return used;
 }
 
-// pass 1 of cape_map_union_kernel for the holes kernel (a copy, kept for the measured reason at the head of this file), lanes over the kept planes (i and i + 64): which kept planes have a pair; the rows of the others
+// pass 1 of cape_map_union_kernel for the kernels with rings (a copy, kept for the measured reason at the head of this file), lanes over the kept planes (i and i + 64): which kept planes have a pair; the rows of the others
 // are written here
 __device__ __forceinline__ void union_find_pairs(const MapUnionParams& p, int frame, int nCur, cape_plane_union* rows, const cape_plane_fusion* fusion,
                                                  int lane, unsigned long long (&pairs)[2])
@@ -134,7 +136,7 @@ __device__ __forceinline__ void union_find_pairs(const MapUnionParams& p, int fr
     }
 }
 
-// the rows of a pair of the holes mode: the outer ring and the interior rings go to slab[used, ...) back to back if the whole polygon
+// the rows of a pair of the modes with rings: the outer ring and the interior rings go to slab[used, ...) back to back if the whole polygon
 // fits `capacity`.  Returns the new `used`.
 __device__ __forceinline__ unsigned put_pair_holes(const UnionResult& res, const UnionHoleResult& hr, const UnionHolesLds& H, const UnionFrame& frame, int mapPlane,
                                                    cape_plane_union* row, cape_plane_union_rings* ringRow, double2* slab, unsigned used,
@@ -290,13 +292,17 @@ __global__ __launch_bounds__(64) void cape_ring_union_kernel(RingUnionParams p)
     (void)put_pair(res, frameOut, 0, p.row, p.vertices, 0u, CAPE_MAP_MAX_RING, lane);
 }
 
-// The holes mode of the frame kernel: the walk above, with the map plane's interior rings described to union_pair_holes (every
-// count and offset checked here) and the rings rows written beside the rows.
-__global__ __launch_bounds__(64) void cape_map_union_holes_kernel(MapUnionParams p, cape_plane_union_rings* ringRowsAll, int nFrames)
+// The frame kernel of the modes with rings (Cuts = false: the holes mode, true: the cut mode): the walk above, with the map plane's
+// interior rings described to union_pair_rings (every count and offset checked here) and the rings rows written beside the rows.
+template <bool Cuts>
+__global__ __launch_bounds__(64) void cape_map_union_rings_kernel(MapUnionParams p, cape_plane_union_rings* ringRowsAll, int nFrames)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const UnionLds L = union_carve(smem);
     UnionHolesLds H = union_holes_carve(smem, L);
+    UnionCutLds C{}; // (the second arrangement's sorted cuts: the cut mode's alone)
+    if constexpr (Cuts)
+        C = union_cut_carve(smem);
     const int lane = threadIdx.x & 63;
     const int frame = (int)blockIdx.x;
     if (frame >= nFrames)
@@ -363,7 +369,7 @@ __global__ __launch_bounds__(64) void cape_map_union_holes_kernel(MapUnionParams
                 H.nSrc = (int)ringCount - 1;
                 UnionFrame fa, fb, target;
                 load_map_pair(L, srcA, nA, srcB, nB, M, m, fusion[i], fa, fb, target, lane);
-                res = union_pair_holes(L, H, (int)nA, (int)nB, fa, fb, target, frameOut, holes, lane);
+                res = union_pair_rings<Cuts>(L, H, C, (int)nA, (int)nB, fa, fb, target, frameOut, holes, lane);
             }
             used = put_pair_holes(res, holes, H, frameOut, j, rows + i, ringRows + i, slab, used, CAPE_MAP_UNION_FRAME_VERTICES, lane);
             CAPE_MP_SYNC(); // (the next pair rewrites the carve)
@@ -372,12 +378,17 @@ __global__ __launch_bounds__(64) void cape_map_union_holes_kernel(MapUnionParams
 }
 
 // The same per-pair function on one pair given by ring a's rings (back to back, counts[nRingsA]), ring b and the frames
-// (cape_debug_polygon_union).  1 <= nRingsA <= 1 + kUnionHoles: the entry point has checked it.
+// (cape_debug_polygon_union, and cape_debug_polygon_union_cut with Cuts).  1 <= nRingsA <= 1 + kUnionHoles: the entry point has
+// checked it.
+template <bool Cuts>
 __global__ __launch_bounds__(64) void cape_polygon_union_kernel(PolygonUnionParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const UnionLds L = union_carve(smem);
     UnionHolesLds H = union_holes_carve(smem, L);
+    UnionCutLds C{};
+    if constexpr (Cuts)
+        C = union_cut_carve(smem);
     const int lane = threadIdx.x & 63;
     UnionResult res{};
     UnionHoleResult holes{};
@@ -405,153 +416,32 @@ __global__ __launch_bounds__(64) void cape_polygon_union_kernel(PolygonUnionPara
         H.nSrc = p.nRingsA - 1;
         UnionFrame fa, fb, target;
         load_debug_pair(L, p.ringsA, nA, p.ringB, p.nB, p.frames27, fa, fb, target, lane);
-        res = union_pair_holes(L, H, nA, p.nB, fa, fb, target, frameOut, holes, lane);
-    }
-    (void)put_pair_holes(res, holes, H, frameOut, 0, p.row, p.ringRow, p.vertices, 0u, CAPE_MAP_UNION_FRAME_VERTICES, lane);
-}
-
-// The cut mode of the frame kernel: cape_map_union_holes_kernel's walk, statement for statement, with union_pair_cut for the pair
-// (a copy, not a parameter of that kernel, which stays the code it was: see the head of this file).
-__global__ __launch_bounds__(64) void cape_map_union_cut_kernel(MapUnionParams p, cape_plane_union_rings* ringRowsAll, int nFrames)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const UnionLds L = union_carve(smem);
-    UnionHolesLds H = union_holes_carve(smem, L);
-    const UnionCutLds C = union_cut_carve(smem);
-    const int lane = threadIdx.x & 63;
-    const int frame = (int)blockIdx.x;
-    if (frame >= nFrames)
-        return;
-    const cape_frame_map_match_wide hd = p.matchFrames[frame];
-    const bool reports = !(hd.flags & CAPE_MATCH_EXACT_OVERFLOW);
-    const int nCur = !reports ? 0 : (hd.n_cur < 0 ? 0 : (hd.n_cur > kUnionPlanes ? kUnionPlanes : hd.n_cur));
-    cape_plane_union* rows = p.rows + (size_t)frame * kUnionPlanes;
-    cape_plane_union_rings* ringRows = ringRowsAll + (size_t)frame * kUnionPlanes;
-    const cape_plane_fusion* fusion = p.fusion + (size_t)frame * kUnionPlanes;
-    double2* slab = p.vertices + (size_t)frame * CAPE_MAP_UNION_FRAME_VERTICES;
-    // ---- pass 1: which kept planes have a pair (the rings rows of the others: zeros)
-    unsigned long long pairs[2];
-    union_find_pairs(p, frame, nCur, rows, fusion, lane, pairs);
-#pragma unroll 1
-    for (int s = 0; s < 2; ++s)
-        if (!((pairs[s] >> lane) & 1ull))
-            ringRows[lane + 64 * s] = cape_plane_union_rings{};
-    H.src = p.mapVertices;
-    // ---- pass 2: the pairs in kept-plane order
-    unsigned used = 0;
-#pragma unroll 1
-    for (int s = 0; s < 2; ++s)
-    {
-        unsigned long long todo = pairs[s];
-        while (todo)
-        {
-            const int i = 64 * s + __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int j = uni(fusion[i].map_plane);
-            const uint2 at = p.kept[(size_t)frame * kUnionPlanes + i];
-            const int rec = uni((int)at.x);
-            const cape_plane_measurement& m = p.measurements[(size_t)rec * CAPE_MAX_PLANES + uni((int)at.y)];
-            const cape_map_plane& M = p.mapPlanes[j];
-            UnionResult res{};
-            UnionHoleResult holes{};
-            UnionFrame frameOut{};
-            const unsigned ringFirst = (unsigned)uni((int)M.ring_first), ringCount = (unsigned)uni((int)M.ring_count);
-            const unsigned nB = (unsigned)uni((int)m.vertex_count), offB = (unsigned)uni((int)m.vertex_offset);
-            const unsigned cap = (unsigned)p.boundaryCapacity;
-            // every ring of the map plane: in its table, inside the vertex buffer, of 3 .. kUnionRing vertices
-            bool fits = ringCount >= 1u && ringCount <= 1u + (unsigned)kUnionHoles && ringFirst < p.nMapRings && ringCount <= p.nMapRings - ringFirst &&
-                        nB >= 3u && nB <= (unsigned)kUnionRing && offB <= cap && nB <= cap - offB;
-            for (unsigned k = 0; fits && k < ringCount; ++k)
-            {
-                const cape_map_ring R = p.mapRings[ringFirst + k];
-                const unsigned n = (unsigned)uni((int)R.vertex_count), off = (unsigned)uni((int)R.vertex_offset);
-                fits = n >= 3u && n <= (unsigned)kUnionRing && (unsigned long long)off + n <= p.nMapVertices;
-                if (fits && k > 0u && lane == 0)
-                {
-                    H.srcOff[k - 1u] = off;
-                    H.srcLen[k - 1u] = (unsigned short)n;
-                }
-            }
-            CAPE_MP_SYNC();
-            if (!fits)
-                res.flags = CAPE_UNION_HOST_CAPACITY;
-            else
-            {
-                const cape_map_ring R = p.mapRings[ringFirst];
-                const unsigned nA = (unsigned)uni((int)R.vertex_count), offA = (unsigned)uni((int)R.vertex_offset);
-                const double2* srcA = p.mapVertices + offA;
-                const double2* srcB = p.worldVertices + (size_t)rec * cap + offB;
-                H.nSrc = (int)ringCount - 1;
-                UnionFrame fa, fb, target;
-                load_map_pair(L, srcA, nA, srcB, nB, M, m, fusion[i], fa, fb, target, lane);
-                res = union_pair_cut(L, H, C, (int)nA, (int)nB, fa, fb, target, frameOut, holes, lane);
-            }
-            used = put_pair_holes(res, holes, H, frameOut, j, rows + i, ringRows + i, slab, used, CAPE_MAP_UNION_FRAME_VERTICES, lane);
-            CAPE_MP_SYNC(); // (the next pair rewrites the carve)
-        }
-    }
-}
-
-// ... and of the one-pair debug kernel (cape_debug_polygon_union_cut): cape_polygon_union_kernel's statements.
-__global__ __launch_bounds__(64) void cape_polygon_union_cut_kernel(PolygonUnionParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const UnionLds L = union_carve(smem);
-    UnionHolesLds H = union_holes_carve(smem, L);
-    const UnionCutLds C = union_cut_carve(smem);
-    const int lane = threadIdx.x & 63;
-    UnionResult res{};
-    UnionHoleResult holes{};
-    UnionFrame frameOut{};
-    bool fits = p.nRingsA >= 1 && p.nRingsA <= 1 + kUnionHoles && p.nB >= 3 && p.nB <= kUnionRing;
-    unsigned at = 0;
-    for (int k = 0; fits && k < p.nRingsA; ++k)
-    {
-        const int n = uni(p.countsA[k]);
-        fits = n >= 3 && n <= kUnionRing;
-        if (fits && k > 0 && lane == 0)
-        {
-            H.srcOff[k - 1] = at;
-            H.srcLen[k - 1] = (unsigned short)n;
-        }
-        at += fits ? (unsigned)n : 0u;
-    }
-    CAPE_MP_SYNC();
-    if (!fits)
-        res.flags = CAPE_UNION_HOST_CAPACITY;
-    else
-    {
-        const int nA = uni(p.countsA[0]);
-        H.src = p.ringsA;
-        H.nSrc = p.nRingsA - 1;
-        UnionFrame fa, fb, target;
-        load_debug_pair(L, p.ringsA, nA, p.ringB, p.nB, p.frames27, fa, fb, target, lane);
-        res = union_pair_cut(L, H, C, nA, p.nB, fa, fb, target, frameOut, holes, lane);
+        res = union_pair_rings<Cuts>(L, H, C, nA, p.nB, fa, fb, target, frameOut, holes, lane);
     }
     (void)put_pair_holes(res, holes, H, frameOut, 0, p.row, p.ringRow, p.vertices, 0u, CAPE_MAP_UNION_FRAME_VERTICES, lane);
 }
 
 hipError_t launch_map_union_cut(const MapUnionParams& p, cape_plane_union_rings* ringRows, int nFrames, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cape_map_union_cut_kernel, dim3(nFrames), dim3(64), union_cut_layout().bytes, stream, p, ringRows, nFrames);
+    hipLaunchKernelGGL(cape_map_union_rings_kernel<true>, dim3(nFrames), dim3(64), union_cut_layout().bytes, stream, p, ringRows, nFrames);
     return hipGetLastError();
 }
 
 hipError_t launch_polygon_union_cut(const PolygonUnionParams& p, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cape_polygon_union_cut_kernel, dim3(1), dim3(64), union_cut_layout().bytes, stream, p);
+    hipLaunchKernelGGL(cape_polygon_union_kernel<true>, dim3(1), dim3(64), union_cut_layout().bytes, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_map_union_holes(const MapUnionParams& p, cape_plane_union_rings* ringRows, int nFrames, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cape_map_union_holes_kernel, dim3(nFrames), dim3(64), union_holes_layout().bytes, stream, p, ringRows, nFrames);
+    hipLaunchKernelGGL(cape_map_union_rings_kernel<false>, dim3(nFrames), dim3(64), union_holes_layout().bytes, stream, p, ringRows, nFrames);
     return hipGetLastError();
 }
 
 hipError_t launch_polygon_union(const PolygonUnionParams& p, hipStream_t stream)
 {
-    hipLaunchKernelGGL(cape_polygon_union_kernel, dim3(1), dim3(64), union_holes_layout().bytes, stream, p);
+    hipLaunchKernelGGL(cape_polygon_union_kernel<false>, dim3(1), dim3(64), union_holes_layout().bytes, stream, p);
     return hipGetLastError();
 }
 

@@ -1,95 +1,36 @@
-// The cut mode of csrc/cape_map_union.h (union_arrange, union_pair_cut) one lane at a time, compared bit for bit with
+// The cut mode of csrc/cape_map_union.h (union_arrange, union_pair_rings<true>) one lane at a time, compared bit for bit with
 // host/boundary_polygon.cpp's merge_union and simplify on map polygons whose holes the detection covers in part, under the address and
-// undefined-behaviour sanitizers.  A stand-alone program.  tests/host/map_union_algebra.cpp is included as text with its main renamed,
-// as tests/host/map_union_holes_algebra.cpp includes it: it brings the host class, the per-lane functions of the device header, the
-// arrangement of both older modes (seq::Arrangement: the rank sort, node_of, link, next_of with its guard band, the walks), the
-// wave-shaped loops (seq::simple, seq::drop, seq::dp_candidate) and the ring generators.  The holes port itself cannot be included a
-// second time -- it ends in its own main and undefines the macro that would rename it -- so the four helpers of its namespace that
-// this mode needs stand here again, unchanged (cut::orient_hole, area_holed, vertices_of, simplify_holed).  New here, in the device's
-// order of statements: cut::arrange, which is union_arrange -- one arrangement per call, built from ITS operands (its own scale and
-// eps, segment list, cuts, nodes, start node and first slot), the outer face walked and dropped, every other face tested by the rule
-// (0: in neither operand, 1: in or on the first and not in or on the second) on the probe point, then drop_collinear, >= 3 vertices,
-// simple and -- rule 1 -- more than `tiny`, oriented like add_hole and appended while it fits, counted either way -- and cut::pair,
-// which is union_pair_cut: the holes mode's statements, and in the carried-holes loop a partly covered hole runs cut::arrange(hole,
-// detection, rule 1) with the tiny of the FIRST pair of operands, its pieces following the rings stored so far; the capacities are
-// judged at the end.  What needs the wave -- the second sorted cut list in the intersection's heights, the second outer face in
-// L.face, the barriers -- is tests/test_gpu_map_union_cut.py's.  Build and run from the repository root:
+// undefined-behaviour sanitizers.  A stand-alone program.  tests/host/map_union_holes_algebra.cpp is included as text with its main
+// renamed, as that file includes tests/host/map_union_algebra.cpp: together they bring the host class, the per-lane functions of the
+// device header, the arrangement of every mode (seq::Arrangement: the rank sort, node_of, link, next_of with its guard band, the
+// walks), the wave-shaped loops (seq::simple, seq::drop, seq::dp_candidate), the ring generators, and holes::pair -- the one pair
+// function of the modes with rings, as union_pair_rings is on the device -- with its helpers (orient_hole, area_holed, vertices_of,
+// simplify_holed).  New here, in the device's order of statements: cut::arrange, which is union_arrange -- one arrangement per
+// call, built from ITS operands (its own scale and eps, segment list, cuts, nodes, start node and first slot), the outer face walked
+// and dropped, every other face tested by the rule (0: in neither operand, 1: in or on the first and not in or on the second) on the
+// probe point, then drop_collinear, >= 3 vertices, simple and -- rule 1 -- more than `tiny`, oriented like add_hole and appended
+// while it fits, counted either way.  holes::pair runs it through cut::pieces with rule 1 on (a partly covered hole, the detection)
+// and the tiny of the FIRST pair of operands, the pieces following the rings stored so far; the capacities are judged at the end.
+// Rule 0 is the pair function's own first arrangement restated: cut::compare runs cut::arrange(A, B, rule 0) beside every pair and
+// holds its count of faces against the pair's new holes.  What needs the wave -- the second sorted cut list in the intersection's
+// heights, the second outer face in L.face, the barriers -- is tests/test_gpu_map_union_cut.py's.  Build and run from the repository
+// root:
 //
 //   g++ -O2 -std=c++17 -ffp-contract=off -fsanitize=address,undefined -Itests/host/hip_stub -Irgb-d-slam_amd/csrc -Irgb-d-slam_amd/host \
 //       -Irgb-d-slam_amd/host/compat -o map_union_cut_algebra.exe tests/host/map_union_cut_algebra.cpp && ./map_union_cut_algebra.exe
-#define main map_union_algebra_main
-#include "map_union_algebra.cpp"
-#undef main
+#define MAP_UNION_HOLES_ALGEBRA_MAIN map_union_holes_algebra_main
+#include "map_union_holes_algebra.cpp"
 
 namespace cut {
-using seq::dp_candidate;
+using holes::kHoleVertices;
+using holes::kHoles;
+using holes::orient_hole;
+using holes::Out;
 using seq::drop;
 using seq::in_ring;
 using seq::Ring2;
 using seq::signed_area;
 using seq::simple;
-
-const int kHoles = CAPE_MAP_MAX_HOLES, kHoleVertices = CAPE_MAP_UNION_HOLE_VERTICES;
-
-struct Out
-{
-    uint32_t flags = 0;
-    std::vector<Ring2> rings; // outer, holes
-    double area = 0;
-    unsigned holesNew = 0, holesKept = 0, holesCovered = 0;
-};
-
-// ---- as in map_union_holes_algebra.cpp
-static void orient_hole(Ring2& r) // add_hole
-{
-    if (signed_area(r) < 0)
-        std::reverse(r.begin(), r.end());
-}
-static double area_holed(const Ring2& ring, const std::vector<Ring2>& hs) // Polygon::area
-{
-    if (ring.size() < 3)
-        return 0.0;
-    double a = std::abs(signed_area(ring));
-    for (const Ring2& h : hs)
-        a -= std::abs(signed_area(h));
-    return a < 0 ? 0.0 : a;
-}
-static size_t vertices_of(const std::vector<Ring2>& hs)
-{
-    size_t n = 0;
-    for (const Ring2& h : hs)
-        n += h.size();
-    return n;
-}
-// union_simplify_holed
-static void simplify_holed(Ring2& ring, std::vector<Ring2>& hs, double& area)
-{
-    area = area_holed(ring, hs);
-    if (ring.size() < 4)
-        return;
-    const double eps = cape::umax(area / 1e5, 10.0);
-    const Ring2 cand = dp_candidate(ring, eps);
-    bool valid = cand.size() >= 3 && simple(cand);
-    std::vector<Ring2> chs = hs;
-    for (size_t k = 0; valid && k < hs.size(); ++k)
-    {
-        if (hs[k].size() < 4)
-            continue;
-        chs[k] = dp_candidate(hs[k], eps);
-        valid = chs[k].size() >= 3 && simple(chs[k]);
-        for (size_t i = 0; valid && i < chs[k].size(); ++i)
-            valid = cape::union_point_in_or_on(chs[k][i], cand.data(), (int)cand.size());
-    }
-    if (!valid)
-        return;
-    const double newArea = area_holed(cand, chs);
-    if (newArea > area * 0.75)
-    {
-        ring = cand;
-        hs = chs;
-        area = newArea;
-    }
-}
 
 // ---- the cut mode's own
 static int largestSecond = 0; // nodes of the largest second arrangement met
@@ -165,105 +106,14 @@ static uint32_t arrange(const Ring2& A, const Ring2& B, int rule, double tiny, R
     return G.ambiguous ? (uint32_t)CAPE_UNION_HOST_AMBIGUOUS : 0u;
 }
 
-// union_pair_cut: A, B oriented in one frame, mapHoles as the (projected) map polygon holds them
-static Out pair(Ring2 A, Ring2 B, const std::vector<Ring2>& mapHoles)
+// the second arrangement of holes::pair's cut mode: union_arrange(hole, detection, rule 1)
+static uint32_t pieces(const Ring2& hole, const Ring2& B, double tiny, std::vector<Ring2>& hs, int& nHoles, int& holeVertices)
 {
-    Out out;
-    const auto hosted = [](uint32_t f) {
-        Out o;
-        o.flags = (f & CAPE_UNION_HOST_CAPACITY) ? (uint32_t)CAPE_UNION_HOST_CAPACITY : f;
-        return o;
-    };
-    Ring2 outer;
-    std::vector<Ring2> stored;
-    int nNew = 0, newVertices = 0, nNodes = 0;
-    if (const uint32_t bits = arrange(A, B, 0, 0.0, outer, stored, nNew, newVertices, nNodes))
-        return hosted(bits);
-    if (!outer.empty())
-        drop(outer);
-    const double outerArea = outer.size() >= 3 ? std::abs(signed_area(outer)) : 0.0;
-    const double areaA = std::abs(signed_area(A)), areaB = std::abs(signed_area(B));
-    bool disjoint = outer.size() >= 3 && (seq::left_out(A, outer) || seq::left_out(B, outer)), rule = false;
-    if (outerArea + 1e-9 * cape::umax(areaA, areaB) < cape::umax(areaA, areaB))
-    {
-        disjoint = rule = true;
-        if (area_holed(A, mapHoles) >= areaB)
-        {
-            if (vertices_of(mapHoles) > (size_t)kHoleVertices)
-                return hosted(CAPE_UNION_HOST_CAPACITY);
-            out.flags = CAPE_UNION_SERVED | CAPE_UNION_DISJOINT | (mapHoles.empty() ? 0u : (uint32_t)CAPE_UNION_HOLES);
-            std::vector<Ring2> hs = mapHoles;
-            simplify_holed(A, hs, out.area);
-            out.rings.push_back(A);
-            out.rings.insert(out.rings.end(), hs.begin(), hs.end());
-            return out;
-        }
-        outer = B;
-    }
-    if (outer.size() < 3 || !simple(outer))
-    {
-        if (vertices_of(mapHoles) > (size_t)kHoleVertices)
-            return hosted(CAPE_UNION_HOST_CAPACITY);
-        out.flags = CAPE_UNION_SERVED | CAPE_UNION_UNCHANGED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u) |
-                    (mapHoles.empty() ? 0u : (uint32_t)CAPE_UNION_HOLES);
-        out.rings.push_back(A);
-        out.rings.insert(out.rings.end(), mapHoles.begin(), mapHoles.end());
-        out.area = area_holed(A, mapHoles);
-        return out;
-    }
-    if (outer.size() > 1 && outer.front().x == outer.back().x && outer.front().y == outer.back().y)
-        outer.pop_back();
-    seq::orient(outer);
-    std::vector<Ring2> hs;
-    int nHoles = 0, holeVertices = 0;
-    bool cutAny = false;
-    if (!rule)
-    {
-        hs = stored;
-        nHoles = nNew;
-        holeVertices = newVertices;
-        out.holesNew = (unsigned)nNew;
-        const double tiny = 1e-12 * cape::umax(areaA, areaB); // of the first pair of operands, for every hole
-        std::vector<vector2> rb;
-        for (const double2& p : B)
-            rb.emplace_back(p.x, p.y);
-        for (const Ring2& h : mapHoles)
-        {
-            std::vector<vector2> rh;
-            for (const double2& p : h)
-                rh.emplace_back(p.x, p.y);
-            const double inter = cape::union_boxes_apart(h.data(), (int)h.size(), B.data(), (int)B.size()) ? 0.0 : ref::rings_inter_area(rh, rb);
-            const double covered = inter < 0 ? 0.0 : inter;
-            if (covered <= tiny)
-            {
-                if (nHoles < kHoles && holeVertices + (int)h.size() <= kHoleVertices)
-                    hs.push_back(h);
-                ++nHoles;
-                holeVertices += (int)h.size();
-                ++out.holesKept;
-            }
-            else if (inter < std::abs(signed_area(h)) - tiny)
-            {
-                cutAny = true;
-                Ring2 outer2; // walked for its edges' marks only
-                int nodes2 = 0;
-                const uint32_t bits = arrange(h, B, 1, tiny, outer2, hs, nHoles, holeVertices, nodes2);
-                largestSecond = std::max(largestSecond, nodes2);
-                if (bits)
-                    return hosted(bits);
-            }
-            else
-                ++out.holesCovered;
-        }
-    }
-    if (nHoles > kHoles || holeVertices > kHoleVertices)
-        return hosted(CAPE_UNION_HOST_CAPACITY);
-    out.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u) | (nHoles > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u) |
-                (cutAny ? (uint32_t)CAPE_UNION_HOLE_PIECES : 0u);
-    simplify_holed(outer, hs, out.area);
-    out.rings.push_back(outer);
-    out.rings.insert(out.rings.end(), hs.begin(), hs.end());
-    return out;
+    Ring2 outer2; // walked for its edges' marks only
+    int nodes2 = 0;
+    const uint32_t bits = arrange(hole, B, 1, tiny, outer2, hs, nHoles, holeVertices, nodes2);
+    largestSecond = std::max(largestSecond, nodes2);
+    return bits;
 }
 
 // counts: served without a cut hole, served with HOLE_PIECES, capacity on both sides, handed away by the port alone, differing
@@ -293,7 +143,19 @@ static long compare(const char* name, const named::Ring& a, const std::vector<na
     }
     ref::Polygon::MergeInfo info;
     const bool merged = pa.merge_union(pb, &info);
-    const Out mine = pair(A, B, H);
+    const Out mine = holes::pair(A, B, H, pieces);
+    // rule 0: where the pair got as far as its interior rings with every face of the first arrangement a new hole, union_arrange finds them
+    {
+        Ring2 outer0;
+        std::vector<Ring2> faces0;
+        int n0 = 0, vertices0 = 0, nodes0 = 0;
+        const uint32_t bits0 = arrange(A, B, 0, 0.0, outer0, faces0, n0, vertices0, nodes0);
+        if ((mine.flags & CAPE_UNION_SERVED) && !(mine.flags & (CAPE_UNION_UNCHANGED | CAPE_UNION_DISJOINT)) && (bits0 != 0 || (unsigned)n0 != mine.holesNew))
+        {
+            std::printf("DIFFERS: %s: rule 0 finds %d faces (bits %#x), the pair %u new holes\n", name, n0, bits0, mine.holesNew);
+            return 1;
+        }
+    }
     const bool fits = pa.boundary().size() <= CAPE_MAP_MAX_RING && pa.interior_rings().size() <= CAPE_MAP_MAX_HOLES;
     uint32_t want;
     if (!fits || (merged ? info.holeVertices : before) > CAPE_MAP_UNION_HOLE_VERTICES)

@@ -1,4 +1,4 @@
-// The holes mode of csrc/cape_map_union.h (union_pair_holes, union_simplify_holed) one lane at a time, compared bit for bit with
+// The holes mode of csrc/cape_map_union.h (union_pair_rings<false>, union_simplify_holed) one lane at a time, compared bit for bit with
 // host/boundary_polygon.cpp's merge_union and simplify on map polygons that have interior rings and unions that create some, under the
 // address and undefined-behaviour sanitizers.  A stand-alone program.  tests/host/map_union_algebra.cpp is included as text with its
 // main renamed: it brings the host class (boundary_polygon.cpp as text), the plain per-lane functions of the device header over
@@ -10,14 +10,19 @@
 // (cape_ring_area.h, the matchers' tests); a partly covered hole before every capacity; simplify() over all rings or none with the
 // 3-vertex skip, the in-ring check and the tolerance from the area without the holes.  The frames are canonical: the projection of an
 // interior ring is union_project, covered by map_union_algebra.cpp, and its order on the wave by tests/test_gpu_map_union_holes.py,
-// which also covers what needs the wave: the LDS carve and its borrowed regions, the barriers, the ballots.  Build and run from the
-// repository root:
+// which also covers what needs the wave: the LDS carve and its borrowed regions, the barriers, the ballots.  holes::pair also holds
+// the cut mode, as union_pair_rings does: given the second arrangement (`pieces`), a partly covered hole is cut into its pieces instead
+// of handed to the host.  tests/host/map_union_cut_algebra.cpp includes this file as text for it, as this file includes
+// map_union_algebra.cpp, with MAP_UNION_HOLES_ALGEBRA_MAIN naming this program's main.  Build and run from the repository root:
 //
 //   g++ -O2 -std=c++17 -ffp-contract=off -fsanitize=address,undefined -Itests/host/hip_stub -Irgb-d-slam_amd/csrc -Irgb-d-slam_amd/host \
 //       -Irgb-d-slam_amd/host/compat -o map_union_holes_algebra.exe tests/host/map_union_holes_algebra.cpp && ./map_union_holes_algebra.exe
 #define main map_union_algebra_main
 #include "map_union_algebra.cpp"
 #undef main
+#ifndef MAP_UNION_HOLES_ALGEBRA_MAIN
+#define MAP_UNION_HOLES_ALGEBRA_MAIN main
+#endif
 
 namespace holes {
 using seq::area_of;
@@ -88,14 +93,19 @@ static void simplify_holed(Ring2& ring, std::vector<Ring2>& hs, double& area)
     }
 }
 
-// union_pair_holes: A, B oriented in one frame, mapHoles as the (projected) map polygon holds them.  The arrangement, the walks and
-// the face test are seq::Arrangement's, as on the device; what is the mode's own stands here.
-static Out pair(Ring2 A, Ring2 B, const std::vector<Ring2>& mapHoles)
+// The cut mode's second arrangement (union_arrange with rule 1 on a partly covered hole and the detection): the pieces of hole minus
+// B follow the rings in `hs` while they fit, counted either way.  Returns 0 or the bits that end the pair.
+typedef uint32_t (*Pieces)(const Ring2& hole, const Ring2& B, double tiny, std::vector<Ring2>& hs, int& nHoles, int& holeVertices);
+
+// union_pair_rings: A, B oriented in one frame, mapHoles as the (projected) map polygon holds them.  The arrangement, the walks and
+// the face test are seq::Arrangement's, as on the device; what is the modes' own stands here.  Without `pieces` the holes mode (a
+// partly covered hole is the host's), with it the cut mode.
+static Out pair(Ring2 A, Ring2 B, const std::vector<Ring2>& mapHoles, Pieces pieces = nullptr)
 {
     Out out;
-    const auto hosted = [](uint32_t f) {
+    const auto hosted = [](uint32_t f) { // union_hosted
         Out o;
-        o.flags = f;
+        o.flags = (f & CAPE_UNION_HOST_CAPACITY) ? (uint32_t)CAPE_UNION_HOST_CAPACITY : f;
         return o;
     };
     seq::Arrangement G;
@@ -179,7 +189,7 @@ static Out pair(Ring2 A, Ring2 B, const std::vector<Ring2>& mapHoles)
         nHoles = nNew;
         holeVertices = newVertices;
         out.holesNew = (unsigned)nNew;
-        const double tiny = 1e-12 * cape::umax(areaA, areaB);
+        const double tiny = 1e-12 * cape::umax(areaA, areaB); // of the first pair of operands, for every hole
         std::vector<vector2> rb;
         for (const double2& p : B)
             rb.emplace_back(p.x, p.y);
@@ -199,16 +209,22 @@ static Out pair(Ring2 A, Ring2 B, const std::vector<Ring2>& mapHoles)
                 ++out.holesKept;
             }
             else if (inter < std::abs(signed_area(h)) - tiny)
+            {
                 cut = true;
+                if (pieces)
+                    if (const uint32_t bits = pieces(h, B, tiny, hs, nHoles, holeVertices))
+                        return hosted(bits);
+            }
             else
                 ++out.holesCovered;
         }
     }
-    if (cut)
+    if (!pieces && cut)
         return hosted(CAPE_UNION_HOST_HOLE_CUT);
     if (nHoles > kHoles || holeVertices > kHoleVertices)
         return hosted(CAPE_UNION_HOST_CAPACITY);
-    out.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u) | (nHoles > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u);
+    out.flags = CAPE_UNION_SERVED | (disjoint ? (uint32_t)CAPE_UNION_DISJOINT : 0u) | (nHoles > 0 ? (uint32_t)CAPE_UNION_HOLES : 0u) |
+                (pieces && cut ? (uint32_t)CAPE_UNION_HOLE_PIECES : 0u);
     simplify_holed(outer, hs, out.area);
     out.rings.push_back(outer);
     out.rings.insert(out.rings.end(), hs.begin(), hs.end());
@@ -274,7 +290,7 @@ static long compare(const char* name, const named::Ring& a, const std::vector<na
 }
 } // namespace holes
 
-int main()
+int MAP_UNION_HOLES_ALGEBRA_MAIN()
 {
     using named::Ring;
     using named::rect;
