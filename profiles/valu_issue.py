@@ -5,14 +5,17 @@ A1 moves 1.0001 x its algorithmic bytes at ~0.49 of the HBM peak: it is bound by
 This script makes that number reproducible instead of prose:
 
   1. compiles csrc/cape_cell_moments.hip to gfx950 assembly with the Makefile's flags (hipcc -S, no GPU needed);
-  2. cuts the kernel (the lane-per-cell instance) into its regions -- prologue, a trip of each of the two row loops, row 10 with
-     the horizontal scan, the tail -- and classifies every vector instruction by the issue cost MEASURED on gfx950
+  2. cuts the kernel (the FUSED lane-per-cell instance, the one a 640x480 batch runs) into its regions -- prologue, a trip of each
+     of the two row loops, row 10 with the horizontal scan, the tail up to the aux record's store, and "fit + edges + stores":
+     the cell's plane fit, the barrier, the edge predicates and the stores behind it -- and classifies every vector instruction by the issue cost MEASURED on gfx950
      (csrc/microbench/valu_rates.hip, profiles/r02_valu_rates.txt): f64-rate (v_*_f64, conversions from / to f64),
      double-rate (v_mul/add/sub_f32, v_add/sub_u32, v_and_b32, v_mov_b32: ~2.3 cycles), every other vector op (~4.3 cycles);
   3. prices one launch: instructions per wave x waves per SIMD x ns per wave-instruction;
   4. cross-checks the static count against the dynamic one of a rocprofv3 --pmc SQ_INSTS_VALU pass on the same binary
      (profiles/pmc_sq.sh), when its csv is given, and prices the dynamic count (every wave runs every region once, so the two
-     differ only by the f64 form of the scan steps, which is listed apart and not run on the benchmark's frames).
+     differ only by the f64 form of the scan steps, which is listed apart and not run on the benchmark's frames -- and by the
+     fit region, whose branches depend on the cells: it is LISTED once, every loop body and both sides of every branch, the in-order
+     redo included, so only the counter pass says what a launch runs of it).
 
 usage: valu_issue.py [--pmc profiles/r05_pmc_sq_insts.csv] [--frames 4096] [--out profiles/valu_issue.json]
 bench.py reads the json (like profiles/traffic.json) and puts `roofline.valu_issue` in its line, with
@@ -44,7 +47,11 @@ def classify(op):
 
 def kernel_regions(asm_lines, symbol):
     """[(region name, [opcodes])] of the lane-per-cell kernel: prologue, one trip of the first row loop (rows 0..9), row 10 with the
-    horizontal scan, one trip of the second row loop (rows 11..18), tail (row 19, guard, stores).  A loop is a backward branch.
+    horizontal scan, one trip of the second row loop (rows 11..18), tail (row 19, guard, the aux record's 16-B store) and what
+    follows it: the fit, the barrier, the edge predicates and the stores of the fused instance (the five stores of the sums in the
+    split one).  A loop is a backward branch; the row loops are the first two, every later one belongs to the fit.  (The aux
+    record needs the count and the z range but none of the sums, so the compiler sinks row 19's f64 adds behind its store: they are
+    listed with the fit.)
     The f64 form of a scan step sits behind an `s_cbranch_vccz` that skips it unless a lane of the wave is unsure of its f32
     verdict (which the benchmark's frames never are: the counter pass agrees with the count without it), so the instructions
     between such a branch and its target are left out and listed on their own as `redo_listed`."""
@@ -57,7 +64,8 @@ def kernel_regions(asm_lines, symbol):
         m = re.match(r"\s+s_c?branch\w*\s+(\.LBB\d+_\d+)", ln)
         if m and label_at.get(m.group(1), len(body)) < i:
             loops.append((label_at[m.group(1)], i))
-    assert len(loops) == 2, "two row loops"
+    loops.sort()
+    assert len(loops) >= 2, "two row loops"
     redo = []
 
     def ops(lo, hi):
@@ -79,9 +87,10 @@ def kernel_regions(asm_lines, symbol):
                     skip_to = v.group(1)
         return out
 
-    (h1, e1), (h2, e2) = loops
+    (h1, e1), (h2, e2) = loops[:2]
+    aux = next(i for i in range(e2 + 1, len(body)) if "global_store_dwordx4" in body[i])
     regions = [("prologue", ops(0, h1)), ("loop_rows_0_9", ops(h1, e1 + 1)), ("row_10", ops(e1 + 1, h2)), ("loop_rows_11_18", ops(h2, e2 + 1)),
-               ("tail", ops(e2 + 1, len(body)))]
+               ("tail", ops(e2 + 1, aux + 1)), ("fit_edges_writes", ops(aux + 1, len(body)))]
     return regions + [("redo_listed", redo)]
 
 
@@ -122,11 +131,11 @@ def main():
     out = {"kernel": "cape_cell_moments_kernel", "frames_per_launch": args.frames, "width": args.width, "height": args.height,
            "waves_per_launch": waves_per_launch, "simds": args.simds, "rate_ns_per_wave_instruction": RATE_NS,
            "rates_from": "profiles/r02_valu_rates.txt (csrc/microbench/valu_rates.hip on MI355X)", "variants": {}}
-    for variant, symbol in (("f32", "_ZN4cape24cape_cell_moments_kernelILb0EEEvNS_12StageAParamsEi"),
-                            ("u16", "_ZN4cape24cape_cell_moments_kernelILb1EEEvNS_12StageAParamsEi")):
+    for variant, symbol in (("f32", "_ZN4cape24cape_cell_moments_kernelILb0ELb1EEEvNS_12StageAParamsEi"),
+                            ("u16", "_ZN4cape24cape_cell_moments_kernelILb1ELb1EEEvNS_12StageAParamsEi")):
         regs = dict(kernel_regions(asm, symbol))
         c = {k: count(v) for k, v in regs.items()}
-        weights = {"prologue": 1, "loop_rows_0_9": cell // 2, "row_10": 1, "loop_rows_11_18": cell // 2 - 2, "tail": 1}
+        weights = {"prologue": 1, "loop_rows_0_9": cell // 2, "row_10": 1, "loop_rows_11_18": cell // 2 - 2, "tail": 1, "fit_edges_writes": 1}
         per_wave = {k: sum(c[r][k] * w for r, w in weights.items()) for k in ("f64", "double_rate", "other", "salu", "lds", "vmem")}
         static_valu = per_wave["f64"] + per_wave["double_rate"] + per_wave["other"]
         v = {"static_per_wave": {"all_rows": per_wave, "per_region": {r: c[r] for r in weights}, "redo_listed_not_run": c["redo_listed"],
@@ -134,7 +143,7 @@ def main():
         valu = static_valu
         if args.pmc:
             for row in csv.DictReader(open(args.pmc)):
-                if ("cell_moments_kernel<false>" if variant == "f32" else "cell_moments_kernel<true>") in row["kernel"] and row["counter"] == "SQ_INSTS_VALU":
+                if ("cell_moments_kernel<false, true>" if variant == "f32" else "cell_moments_kernel<true, true>") in row["kernel"] and row["counter"] == "SQ_INSTS_VALU":
                     dyn = float(row["avg_value"])
                     v["pmc"] = {"SQ_INSTS_VALU_per_launch": dyn, "per_wave": dyn / waves_per_launch, "static_per_wave": static_valu,
                                 "source": os.path.relpath(args.pmc, ROOT)}

@@ -68,6 +68,7 @@ struct Knobs
     int schedule = 0;         // CAPE_SCHEDULE=two|single: 1 = always two-pass, 2 = always single (cape_handle_s::Chain::forcedSchedule)
     std::string stageA;       // CAPE_STAGE_A=strips|bands (see cape_handle_s::Chain::stripCounters)
     std::string a1;           // CAPE_A1=cells|bands: the instance of the streaming kernel A1 (StageAParams::a1Bands)
+    std::string a2;           // CAPE_A2=split|fused: A2 as a launch of its own, or in A1's lanes (StageAParams::a2Fused); unset: fused where eligible
     bool growGeneral = false; // CAPE_GROW=general|fast: general sends every frame through the general instance
     bool pinnedByDma = false; // CAPE_PINNED_INPUT=dma (cape_handle_s::Chain::pinnedByDma)
     int a2WideBatch = 0;      // CAPE_A2_WIDE_BATCH=n: the one-tile stage-A2 instance for batches <= n (cell_plane_threads)
@@ -93,6 +94,8 @@ int read_knobs(Knobs& k)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_STAGE_A must be strips or bands");
     if (!one_of("CAPE_A1", {"cells", "bands"}, k.a1))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_A1 must be cells or bands");
+    if (!one_of("CAPE_A2", {"split", "fused"}, k.a2))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_A2 must be split or fused");
     if (!one_of("CAPE_GROW", {"general", "fast"}, grow))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "CAPE_GROW must be general or fast");
     k.noResume = k.resume == "off" || std::getenv("CAPE_NO_RESUME");
@@ -435,6 +438,14 @@ int cape_create(const cape_config* cfg, cape_handle* out)
     a.cosMergeA = std::cos(static_cast<double>(18.0f) * M_PI / 180.0); // plane_segment.cpp:324
     a.smallBatchFrames = knobs.a2WideBatch; // see cell_plane_threads()
     a.a1Bands = knobs.a1 == "bands" ? 1 : 0;
+    // Stage A in one launch where the lane-per-cell workgroups are A2's tiles; CAPE_A1=bands implies split.  CAPE_A2=fused is a
+    // promise about which kernel runs, so whatever would send a call of this handle down the split path is an error here.
+    a.a2Fused = (knobs.a2 != "split" && !a.a1Bands && cape::cell_fused_eligible(a)) ? 1 : 0;
+    if (knobs.a2 == "fused" && (!a.a2Fused || knobs.a2WideBatch > 0 || cfg->sub_batches > 1))
+        return fail(CAPE_ERR_INVALID_ARGUMENT,
+                    "CAPE_A2=fused: this handle's grid of " + std::to_string(h->hCells) + " x " + std::to_string(h->vCells) +
+                        " cells is not eligible (256 cells per workgroup must be whole cell rows and divide the frame), or CAPE_A1=bands, "
+                        "CAPE_A2_WIDE_BATCH or sub_batches > 1 select the split kernels");
     // plane_segment.hpp:33-34 ; parameters.hpp:72 minimumZeroDepthProportion = 0.7f
     a.minZeroPointCount = static_cast<int>(std::floor(static_cast<float>(400) * 0.7f));
 

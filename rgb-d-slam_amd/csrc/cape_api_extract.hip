@@ -64,7 +64,7 @@ void offset_params(const cape_handle_s* h, int f0, cape::StageAParams& a, cape::
     b.debugCycles += F * cape::kProfileSlots;
 }
 
-// the per-launch fields of one chain of `frames` frames: stage A2 clears the chain's lists (and the spill pool's counters,
+// the per-launch fields of one chain of `frames` frames: the kernel that ends stage A (A2, the fused A1 or the strip kernel) clears the chain's lists (and the spill pool's counters,
 // `clear4`, unless they are shared with other sub-batches), stage B learns A2's tiling and whether this chain is timed
 void prepare_launch(const cape_handle_s* h, cape::StageAParams& a2, cape::StageBParams& b, uint32_t* clear4, bool strips, int frames,
                     bool timed)
@@ -133,6 +133,17 @@ int launch_chain(cape_handle_s* h, const cape::StageAParams& a, const cape::Stag
     {
         // the latency instance: all of stage A in one launch (timing: booked as the moments kernel, the plane kernel reads 0)
         CAPE_HIP_TRY(cape::launch_cell_strips(a2, frames, c.stripCounters, st));
+        if (t)
+        {
+            CAPE_HIP_TRY(hipEventRecord(t->e[1], st));
+            CAPE_HIP_TRY(hipEventRecord(t->e[2], st));
+        }
+    }
+    else if (a.a2Fused && cape::cell_plane_threads(a2, frames) == 256)
+    {
+        // the lanes of A1 fit their cells: one launch, whose tiles are those of the 256-thread A2 that the split path would run for
+        // this call -- so a2RowsPerTile is what stage B was told anyway (timing: booked as the moments kernel, the plane kernel reads 0)
+        CAPE_HIP_TRY(cape::launch_cell_fused(a2, frames, st));
         if (t)
         {
             CAPE_HIP_TRY(hipEventRecord(t->e[1], st));

@@ -26,6 +26,9 @@ namespace cape {
 #ifndef CAPE_A1_CELL_WAVES
 #define CAPE_A1_CELL_WAVES 4   // __launch_bounds__ waves per SIMD: 4 (128 VGPRs, no scratch) -> 1.158 ms, 3 (155 VGPRs) -> 1.132 ms
 #endif
+#ifndef CAPE_A1_FUSED_WAVES
+#define CAPE_A1_FUSED_WAVES 4  // the same bound for the fused instance (the lane fits its cell's plane too): profiles/a_fused.txt
+#endif
 #ifndef CAPE_A1_CELL_THREADS
 #define CAPE_A1_CELL_THREADS 256 // waves x 64 per workgroup; the waves do not talk to each other: 64 -> 1.173 ms, 256 -> 1.158, 512 -> 1.161
 #endif

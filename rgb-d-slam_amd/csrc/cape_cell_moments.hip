@@ -1,15 +1,16 @@
-// Stage A -- fused back-projection + per-cell PCA for gfx950, as two kernels:
+// Stage A -- fused back-projection + per-cell PCA for gfx950.  Two parts, one launch where the grid allows it:
 //
 //   A1 cape_cell_moments_kernel : the HBM/FP64-issue bound streaming pass.  Reads the row-major depth image once,
 //      back-projects on the fly and leaves, per cell, the nine moment sums + count, the result of the continuity
 //      cross scan and the exactness verdict.  Replaces Depth_Map_Transformation::get_organized_cloud_array
 //      (reference src/features/primitives/depth_map_transformation.cpp:89-142) and the scan + accumulation part of
 //      Plane_Segment::init_plane_segment (plane_segment.cpp:44-152).  The 3.7 MB organised cloud is never built.
-//   A2 cape_cell_plane_kernel   : one lane per cell, every lane busy: validity gates, Plane_Segment::fit_plane
+//   A2 the per-cell fit (cape_cell_plane.h) : one lane per cell: validity gates, Plane_Segment::fit_plane
 //      (plane_segment.cpp:155-168, 205-284), the merge tolerance of init_planar_cell_fitting
-//      (primitive_detection.cpp:201-220) and the histogram bin of init_histogram (primitive_detection.cpp:253-254 +
-//      histogram.hpp:48-54).  Splitting it off keeps the long dependent f64 chains (eigen-solver, div, sqrt) out of
-//      the streaming waves, whose registers are then released as soon as their cells are summed.
+//      (primitive_detection.cpp:201-220), the histogram bin of init_histogram (primitive_detection.cpp:253-254 +
+//      histogram.hpp:48-54) and the merge predicates of the cell's left and upper edges.  The lane that summed a cell
+//      holds everything the fit reads, so in the FUSED instance it carries on with it (below); elsewhere A2 is
+//      cape_cell_plane_kernel (cape_cell_fit.hip), which loads what A1 stored.
 //
 // A1 mapping, the shipped instance (cape_cell_moments_kernel, "cells"): one LANE per cell.  A wave is 64 consecutive cells of a
 // frame in cell-row-major order, lane l of wave w owns cell 64 w + l and walks its 20 rows of 20 pixels (80 contiguous, 16-B
@@ -18,6 +19,13 @@
 // row and the horizontal scan's 19 steps at row 10, and stores its 80 B of sums and its aux record itself: no LDS, no
 // barrier, no second pass; a wave leaves as soon as its last pixel is summed.  Any grid goes through the same code (waves
 // may start and end inside a cell row; the last wave of a frame may be partial).  128 VGPRs, 4 waves per SIMD.
+// FUSED = true is the same kernel with A2 behind the last pixel, for the grids on which a 256-lane workgroup -- four waves of 64
+// consecutive cells -- is exactly a tile of A2's 256-thread instance (cell_fused_eligible: 640x480 is 3 tiles of 8 cell rows per
+// frame): the lane runs cell_fit_and_bin on the sums in its registers (the column factors' 40 registers are dead by then), stores
+// the sums once, and the workgroup publishes its planes in LDS (16 KB), meets at ONE barrier and evaluates the left and up edge
+// predicates as an A2 tile does (tile_publish_and_finish).  No lane leaves ahead of that barrier: every lane of every workgroup
+// holds a cell, which launch_cell_fused checks.  A2's launch, its 96 B per cell of loads and the cache contents that A1's image
+// loads cost it are gone: 1.565 against 1.615 ms per 4 096 frames (profiles/a_fused.txt); same 128 VGPRs, no scratch.
 // The band instance (cape_cell_moments_bands_kernel, CAPE_A1=bands: the bit-for-bit twin of the tests and the in-build A/B
 // partner): one 320-thread workgroup = two "bands" (band = 20 image rows x 640 pixels = 32 cells).  Thread t owns
 // float4 column q = t % 160 of band t / 160 and walks the band's 20 rows, so every wave-level load is a contiguous
@@ -28,16 +36,17 @@
 // a per-cell z-range guard decides whether that holds, otherwise A2 redoes the cell in the reference's pixel order.
 // That is also why the two instances leave the same bits.
 //
-// This file holds A1 only and is compiled with -fno-slp-vectorize (Makefile): left to itself the SLP vectoriser pairs the six
+// This file is compiled with -fno-slp-vectorize (Makefile): left to itself the SLP vectoriser pairs the six
 // f32 products of a pixel into v_pk_mul_f32, which costs as much as the two v_mul_f32_e32 it replaces on gfx950
 // (profiles/r02_valu_rates.txt: 4.5 against 2 x 2.3 cycles) PLUS the v_mov_b32 / v_pk_mov_b32 that build its register pairs
 // (36 moves per 16 pixels; 94 -> 84 VGPRs without them).  A2 and the strip kernel (cape_cell_fit.hip) keep the vectoriser:
-// A2 measured 2 % slower without it.
+// A2 measured 2 % slower without it.  The fit of the fused instance is compiled without it like the rest of this file (the row
+// loop loses 6 % with it); what that costs the fit on its own was not measured apart.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "cape_cell_acc.h"
+#include "cape_cell_plane.h"
 
 namespace cape {
 
@@ -346,18 +355,22 @@ template <bool U16> __global__ __launch_bounds__(kThreadsA, CAPE_A_WAVES) void c
 // The lane-per-cell instance (see the header; the band instance above is kept selectable until the wide grids are measured).
 // A wave is 64 consecutive cells of one frame, lane l of wave w owns cell 64 w + l: its nine sums, count, z range, both
 // continuity scans and the corner / centre samples never leave its registers.  nWaves: frames x waves per frame.
-template <bool U16> __global__ __launch_bounds__(kThreadsCells, CAPE_A1_CELL_WAVES) void cape_cell_moments_kernel(StageAParams p, int nWaves)
+template <bool U16, bool FUSED>
+__global__ __launch_bounds__(kThreadsCells, FUSED ? CAPE_A1_FUSED_WAVES : CAPE_A1_CELL_WAVES) void cape_cell_moments_kernel(StageAParams p, int nWaves)
 {
     // the wave: uniform, so the frame and its base address live in scalar registers
     const int gw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kThreadsCells / 64) + (threadIdx.x >> 6)));
-    if (gw >= nWaves)
-        return; // the last workgroup's waves beyond the batch's last frame
+    // FUSED: every lane of every workgroup holds a cell (launch_cell_fused checks the grid), so nobody leaves ahead of the barrier
+    if constexpr (!FUSED)
+        if (gw >= nWaves)
+            return; // the last workgroup's waves beyond the batch's last frame
     const int wavesPerFrame = (p.cells + 63) >> 6;
     const int frame = gw / wavesPerFrame;
     const int w = gw - frame * wavesPerFrame;
     const int cell = w * 64 + (int)(threadIdx.x & 63);
-    if (cell >= p.cells)
-        return; // (no barrier anywhere: a lane without a cell just leaves)
+    if constexpr (!FUSED)
+        if (cell >= p.cells)
+            return; // (no barrier in this instance: a lane without a cell just leaves)
     const int cellRow = cell / p.hCells;
     const int cellCol = cell - cellRow * p.hCells;
     const size_t frameOff = (size_t)frame * p.W * p.H;
@@ -552,7 +565,8 @@ template <bool U16> __global__ __launch_bounds__(kThreadsCells, CAPE_A1_CELL_WAV
     int hCells = p.hCells;
     asm volatile("" : "+s"(hCells)); // (opaque, or the prologue's reciprocal of it is what gets carried through the loops)
     const int eRow = ecell / hCells;
-    const float rab = fmaxf(p.ratio_col[ecell - eRow * hCells], p.ratio_row[eRow]);
+    const int eCol = ecell - eRow * hCells;
+    const float rab = fmaxf(p.ratio_col[eCol], p.ratio_row[eRow]);
     // all pixels +0 or positive and finite (acc_px_fast's precondition), and their range within the exactness bound
     const bool exact_ok = A.zmaxBits <= 0x7F7FFFFFu && ((n == 0) || (zmax * rab <= 512.0f * zmin));
 
@@ -564,11 +578,55 @@ template <bool U16> __global__ __launch_bounds__(kThreadsCells, CAPE_A1_CELL_WAV
     p.cell_aux[gcell] = aux;
     double2* dst = reinterpret_cast<double2*>(p.cell_sums + gcell * kSumStride);
     static_assert(kSumStride == 10, "nine sums and the count: five 16-B stores");
-    dst[0] = make_double2(A.S[0], A.S[1]);
-    dst[1] = make_double2(A.S[2], A.S[3]);
-    dst[2] = make_double2(A.S[4], A.S[5]);
-    dst[3] = make_double2(A.S[6], A.S[7]);
-    dst[4] = make_double2(A.S[8], (double)n);
+    if constexpr (!FUSED)
+    {
+        dst[0] = make_double2(A.S[0], A.S[1]);
+        dst[1] = make_double2(A.S[2], A.S[3]);
+        dst[2] = make_double2(A.S[4], A.S[5]);
+        dst[3] = make_double2(A.S[6], A.S[7]);
+        dst[4] = make_double2(A.S[8], (double)n);
+    }
+    else
+    {
+        // The lane carries on with its cell: the fit on the sums it holds (the column factors' 40 registers are free by now),
+        // the sums stored ONCE -- cleared or redone in pixel order where the fit says so --, and the workgroup, which is one
+        // tile of stage A2 (256 consecutive cells = whole cell rows of one frame), does what such a tile does behind the fit.
+        __shared__ CellPub s_pub[kThreadsCells];
+        // (the lane's place in the workgroup from the fresh cell index, like everything else down here: a frame is whole workgroups)
+        const int tid = (int)((uint32_t)ecell % (uint32_t)kThreadsCells);
+        if (frame == 0 && ecell == 0)
+            clear_grow_counters(p);
+        CellFit cf;
+        cell_fit_and_bin(p, frame, eRow, eCol, aux, A.S, cf);
+        dst[0] = make_double2(A.S[0], A.S[1]);
+        dst[1] = make_double2(A.S[2], A.S[3]);
+        dst[2] = make_double2(A.S[4], A.S[5]);
+        dst[3] = make_double2(A.S[6], A.S[7]);
+        dst[4] = make_double2(A.S[8], (double)cf.n);
+        tile_publish_and_finish(p, s_pub, tid, hCells, tid / hCells, eCol, true, gcell, cf);
+    }
+}
+
+// The fused instance runs where its workgroups ARE the tiles of stage A2's 256-thread instance: 256 lanes, whole cell rows per
+// workgroup, whole workgroups per frame -- no workgroup straddles a frame, no wave is partial, no lane is without a cell.
+bool cell_fused_eligible(const StageAParams& p)
+{
+    return kThreadsCells == 256 && p.hCells > 0 && p.hCells <= 256 && 256 % p.hCells == 0 && p.cells % 256 == 0;
+}
+
+// stage A in one launch: A1's lanes fit their cells (the caller has checked that the split path would run the 256-thread A2)
+hipError_t launch_cell_fused(const StageAParams& p, int nFrames, hipStream_t stream)
+{
+    // the kernel has no way out ahead of its barrier: it must never see a grid with a lane to spare
+    if (!cell_fused_eligible(p) || p.a1Bands)
+        return hipErrorInvalidConfiguration;
+    constexpr int kWaves = kThreadsCells / 64;
+    const int grid = nFrames * (p.cells / kThreadsCells);
+    if (p.depth)
+        hipLaunchKernelGGL((cape_cell_moments_kernel<false, true>), dim3(grid), dim3(kThreadsCells), 0, stream, p, grid * kWaves);
+    else
+        hipLaunchKernelGGL((cape_cell_moments_kernel<true, true>), dim3(grid), dim3(kThreadsCells), 0, stream, p, grid * kWaves);
+    return hipGetLastError();
 }
 
 // every launch helper reports its own failure: hipGetLastError() right behind the launch (a later runtime call would
@@ -589,9 +647,9 @@ hipError_t launch_cell_moments(const StageAParams& p, int nFrames, hipStream_t s
     const int waves = nFrames * ((p.cells + 63) / 64); // (cells <= 65535 per frame: far from 2^31 for any batch that fits the device)
     const int grid = (waves + kWaves - 1) / kWaves;
     if (p.depth)
-        hipLaunchKernelGGL(cape_cell_moments_kernel<false>, dim3(grid), dim3(kThreadsCells), 0, stream, p, waves);
+        hipLaunchKernelGGL((cape_cell_moments_kernel<false, false>), dim3(grid), dim3(kThreadsCells), 0, stream, p, waves);
     else
-        hipLaunchKernelGGL(cape_cell_moments_kernel<true>, dim3(grid), dim3(kThreadsCells), 0, stream, p, waves);
+        hipLaunchKernelGGL((cape_cell_moments_kernel<true, false>), dim3(grid), dim3(kThreadsCells), 0, stream, p, waves);
     return hipGetLastError();
 }
 

@@ -16,7 +16,10 @@ namespace cape {
 hipError_t launch_cell_moments(const StageAParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_cell_plane(const StageAParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_cell_strips(const StageAParams& p, int nFrames, uint32_t* frameCounters, hipStream_t stream);
+int cell_plane_threads(const StageAParams& p, int nFrames);
 int cell_plane_rows_per_tile(const StageAParams& p, int nFrames);
+bool cell_fused_eligible(const StageAParams& p);
+hipError_t launch_cell_fused(const StageAParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_grow(const StageBParams& p, int nFrames, hipStream_t stream, hipStream_t side, hipEvent_t fork, hipEvent_t done,
                        const GenParams* gen);
 hipError_t launch_grow_general(const StageBParams& p, const GenParams& g, int nFrames, hipStream_t stream);

@@ -73,6 +73,7 @@ struct StageAParams
     double cosMergeA; // cos(18 * pi / 180), plane_segment.cpp:324 (the edge predicates of stage A2)
     int smallBatchFrames; // host side: batches up to this many frames run the latency-oriented kernel instances
     int a1Bands;          // host side: 1 = launch_cell_moments runs the band instance of A1 (CAPE_A1=bands), 0 = lane per cell
+    int a2Fused;          // host side: 1 = the lanes of A1 fit their cells on this grid (cell_fused_eligible and CAPE_A2 allows it), 0 = A2 is a launch of its own
     int minZeroPointCount; // floor(400 * 0.7f) = 280, plane_segment.hpp:33-34
 };
 
