@@ -905,7 +905,7 @@ typedef struct cape_map_track_result
     int32_t kept_plane;         /* match[f][j]: the kept plane map plane j took, or -1 */
 } cape_map_track_result;
 /* What cape_map_kalman reads of the tracks, parallel to the planes of the last cape_map_upload: covariance, successive_matched,
- * failed_tracking, flags.  Host pointer, synchronous.  n must equal the uploaded map's plane count.  A cape_map_upload discards the
+ * failed_tracking, flags; `result` and `id` are kept beside them for cape_map_commit and cape_map_download.  Host pointer, synchronous.  n must equal the uploaded map's plane count.  A cape_map_upload discards the
  * tracks (and waits for a call in flight).  CAPE_ERR_INVALID_ARGUMENT: NULL handle, no map uploaded, n other than the map's plane
  * count, NULL tracks with n > 0. */
 int cape_map_upload_tracks(cape_handle h, const cape_map_track* tracks, int32_t n);
@@ -1034,6 +1034,70 @@ int cape_device_map_union_rings(cape_handle h, cape_plane_union_rings** rings);
  * calls of both return its results; a later cape_map_union makes the rings table stale, a later cape_map_union_holes overwrites
  * everything with its own rows (and the other way round). */
 int cape_map_union_cut(cape_handle h, int32_t n_frames, void* stream);
+
+/* The COMMIT of the map update on the device: the uploaded map M and frame `frame` of the last cape_map_union, cape_map_union_holes or
+ * cape_map_union_cut -- which must be current on the batch, map, match, measurements and Kalman results -- become the map_out of
+ * cape_host_map_update for that frame, in the device's map and track buffers.  Pure data movement (no floating-point statement):
+ * the new map is the host twin's cape_host_map_commit (host/cape_host_map.h) on the same rows byte for byte.  The list order is
+ * unchanged; PROMOTE, DROP and LOST are reported in the track's `result` and left to the caller, as the host update leaves them.
+ * Per map plane j in order:
+ *   no pair (cape_map_track_result.kept_plane < 0), or a pair whose fusion row lacks CAPE_FUSION_STATE: plane, frame, rings and
+ *     covariance are M's;
+ *   CAPE_FUSION_STATE and a union row of this pair with CAPE_UNION_SERVED: normal, d and covariance of the fusion row; x_axis, y_axis
+ *     and center of the union row; the rings from the frame's slab at vertex_offset, split by the rings table (ring_count,
+ *     vertex_count[]) -- one ring of row.vertex_count vertices after a plain cape_map_union -- copied as they lie (they are in the
+ *     host class's orientation);
+ *   CAPE_FUSION_STATE otherwise: the frame is refused, CAPE_COMMIT_HOST_PAIR where the union row carries a CAPE_UNION_HOST_* bit,
+ *     CAPE_COMMIT_FAIL_POLYGON where there is no union pair (or one that neither served nor handed over);
+ *   every plane: successive_matched, failed_tracking and result of cape_map_track_result; flags and id are kept.
+ * Then, with CAPE_COMMIT_ADD_STAGED, every kept plane of the frame's whole record chain whose fusion row lacks CAPE_FUSION_USED and
+ * whose measurement row has CAPE_MEASURE_STAGEABLE is appended in kept-plane order: the plane (staged_normal, d), covariance and frame
+ * of the measurement row, one ring, its world ring; flags CAPE_MAP_TRACK_STAGED, counters 0, result CAPE_MAP_RESULT_APPENDED, id
+ * (*next_id)++.  Kept plane i is resolved through the kept-plane table of the wide match, as cape_map_kalman does, and every index is
+ * checked against its buffer.  Rings and vertices are laid out plane after plane, back to back, as cape_map_upload lays them out.
+ * A refused frame (any flag but CAPE_COMMIT_DONE) changes nothing: map, tracks, every result buffer and *next_id stay as they were, and
+ * the caller downloads the map, runs cape_host_map_update and uploads.  n_updated, n_appended, n_host_pairs and n_fail_polygon are
+ * what the plan counted either way.
+ * The work is enqueued on `stream` behind the union; the call RETURNS once the result header has come back through pinned memory --
+ * one small read that tells the host the new plane count for the next launch: the sequential step of a tracking loop.
+ * A DONE commit invalidates what cape_map_upload invalidates (visibility words, map matches, Kalman and union results) but not the
+ * tracks, which are now the committed ones: a following cape_match_map_wide + cape_map_kalman needs no cape_map_upload_tracks, and
+ * cape_map_measure's rows stay valid.  CAPE_ERR_CAPACITY: no union result is current, or `frame` is outside what it covered;
+ * CAPE_ERR_INVALID_ARGUMENT: NULL handle, out or next_id, unknown flags, a negative frame. */
+enum
+{
+    CAPE_COMMIT_ADD_STAGED = 1u << 0 /* flags of the call */
+};
+enum /* cape_map_commit_result.flags */
+{
+    CAPE_COMMIT_DONE = 1u << 0,           /* the map and the tracks are the new ones */
+    CAPE_COMMIT_FRAME_OVERFLOW = 1u << 1, /* the wide match flagged the frame CAPE_MATCH_EXACT_OVERFLOW */
+    CAPE_COMMIT_BAD_POSE_COV = 1u << 2,   /* CAPE_KALMAN_BAD_POSE_COV: the host refuses the whole frame */
+    CAPE_COMMIT_HOST_PAIR = 1u << 3,      /* a pair with CAPE_FUSION_STATE whose union row carries a CAPE_UNION_HOST_* bit */
+    CAPE_COMMIT_FAIL_POLYGON = 1u << 4,   /* a pair with CAPE_FUSION_STATE and no union pair (FAIL_POLYGON on the host: the polygon
+                                             would be the projected or the old one, which the device does not hold) */
+    CAPE_COMMIT_CAPACITY = 1u << 5        /* the new map exceeds CAPE_MAP_MAX_PLANES or a uint32 offset */
+};
+typedef struct cape_map_commit_result
+{
+    uint32_t flags;
+    int32_t frame;
+    int32_t n_planes, n_rings; /* of the map after the call (the old map's if not DONE) */
+    int64_t n_vertices;
+    int32_t n_updated, n_appended, n_host_pairs, n_fail_polygon;
+    uint64_t next_id; /* after the call */
+} cape_map_commit_result;
+int cape_map_commit(cape_handle h, int32_t frame, uint32_t flags, uint64_t* next_id, cape_map_commit_result* out, void* stream);
+/* The sizes of the device map as it stands, after a cape_map_upload or a commit.  Any pointer may be NULL.  Synchronous.
+ * CAPE_ERR_INVALID_ARGUMENT: NULL handle, no map. */
+int cape_map_info(cape_handle h, int32_t* n_planes, int32_t* n_rings, int64_t* n_vertices);
+/* Synchronous copy of the device map and tracks as they stand: after cape_map_upload the upload with the rings re-oriented and laid
+ * out plane after plane, after a DONE commit the committed map.  tracks (planes_capacity entries, may be NULL): what
+ * cape_map_upload_tracks or the commit left, `result` and `id` included; the zero track per plane if none were uploaded for this map.
+ * CAPE_ERR_INVALID_ARGUMENT: NULL handle, no map, a negative capacity, a NULL array the map needs; CAPE_ERR_CAPACITY: an array is too
+ * small (cape_map_info tells the sizes). */
+int cape_map_download(cape_handle h, cape_map_plane* planes, int32_t planes_capacity, cape_map_ring* rings, int32_t rings_capacity,
+                      double* vertices, int64_t vertices_capacity, cape_map_track* tracks /* planes_capacity, may be NULL */);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as

@@ -649,6 +649,8 @@ int cape_map_upload(cape_handle h, const cape_map_plane* planes, int32_t n_plane
         CAPE_HIP_TRY(hipMemcpy(map.vertices, V.data(), V.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     map.n = n_planes;
+    h->mapCommit.nRings = (int)R.size(); // (cape_map_info / cape_map_download / cape_map_commit: what the ring and vertex buffers hold)
+    h->mapCommit.nVertices = (long long)(V.size() / 2);
     return CAPE_OK;
 }
 
@@ -1153,6 +1155,7 @@ int cape_map_upload_tracks(cape_handle h, const cape_map_track* tracks, int32_t 
     if (n > 0 && !tracks)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null array");
     std::vector<cape::MapTrackState> T((size_t)n);
+    std::vector<cape::MapTrackTag> G((size_t)n); // (id and result: cape_map_commit keeps them, cape_map_download returns them)
     for (int32_t j = 0; j < n; ++j)
     {
         std::memcpy(T[j].covariance, tracks[j].covariance, sizeof(T[j].covariance));
@@ -1160,6 +1163,7 @@ int cape_map_upload_tracks(cape_handle h, const cape_map_track* tracks, int32_t 
         T[j].failedTracking = tracks[j].failed_tracking;
         T[j].flags = tracks[j].flags;
         T[j].pad = 0;
+        G[j] = cape::MapTrackTag {tracks[j].id, tracks[j].result, 0u};
     }
     CAPE_ON_DEVICE(h);
     CAPE_HIP_TRY(drain_handle(h)); // a cape_map_kalman in flight still reads the old tracks
@@ -1167,8 +1171,12 @@ int cape_map_upload_tracks(cape_handle h, const cape_map_track* tracks, int32_t 
     K.tracksN = -1;
     K.kalmanFrames = 0;
     CAPE_HIP_TRY(K.tracks.grow(T.size(), [] { return hipSuccess; }));
+    CAPE_HIP_TRY(h->mapCommit.tags.grow(G.size(), [] { return hipSuccess; }));
     if (n > 0)
+    {
         CAPE_HIP_TRY(hipMemcpy(K.tracks, T.data(), T.size() * sizeof(cape::MapTrackState), hipMemcpyHostToDevice));
+        CAPE_HIP_TRY(hipMemcpy(h->mapCommit.tags, G.data(), G.size() * sizeof(cape::MapTrackTag), hipMemcpyHostToDevice));
+    }
     K.tracksN = n;
     return CAPE_OK;
 }
@@ -1369,6 +1377,162 @@ int cape_copy_map_union(cape_handle h, int32_t n_frames, cape_plane_union* rows,
     CAPE_HIP_TRY(drain_handle(h));
     CAPE_HIP_TRY(copy_out(rows, U.rows, 0, (size_t)n_frames * WP));
     CAPE_HIP_TRY(copy_out(vertices, U.vertices, 0, (size_t)n_frames * SLAB * 2));
+    return CAPE_OK;
+}
+
+// cape_map_commit: the sequential step of a tracking loop.  Two launches behind the union, then the one small read that tells the host
+// the new map's sizes: front and back buffers are swapped here, on the host, only if the header says DONE.
+int cape_map_commit(cape_handle h, int32_t frame, uint32_t flags, uint64_t* next_id, cape_map_commit_result* out, void* stream_)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
+    if (!h || !out || !next_id || frame < 0 || (flags & ~(uint32_t)CAPE_COMMIT_ADD_STAGED))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, result or next_id, a negative frame or an unknown flag");
+    auto& map = h->map;
+    auto& K = h->kalman;
+    auto& U = h->mapUnion;
+    auto& X = h->mapCommit;
+    const auto& W = h->mapWide;
+    const auto& M = h->measure;
+    if (!union_results_live(h) || frame >= U.unionFrames || K.kalmanN != map.n || K.tracksN != map.n)
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_union, cape_map_union_holes or cape_map_union_cut on the current batch, map, match, measurements and Kalman results covers `frame`");
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    // the back buffers, to bounds the host knows: at most 128 appended planes of one ring each, a frame's slab of served rings, the
+    // world rings of the frame's chain
+    const size_t n = (size_t)map.n, cap = (size_t)h->boundaryCap;
+    const size_t planesCap = std::min<size_t>(CAPE_MAP_MAX_PLANES, n + WP), ringsCap = planesCap * (1 + CAPE_MAP_MAX_HOLES);
+    const size_t verticesCap = (size_t)X.nVertices + SLAB + std::min<size_t>(WP * CAPE_MAP_MAX_RING, (size_t)(1 + h->chain.spillRecords) * cap);
+    const auto drain = [h] { return drain_handle(h); }; // (a back buffer was the front one of an earlier map: a call in flight may read it)
+    CAPE_HIP_TRY(X.planes.grow(planesCap, drain));
+    CAPE_HIP_TRY(X.rings.grow(ringsCap, drain));
+    CAPE_HIP_TRY(X.vertices.grow(verticesCap * 2, drain));
+    CAPE_HIP_TRY(X.tracks.grow(planesCap, drain));
+    CAPE_HIP_TRY(X.tagsBack.grow(planesCap, drain));
+    CAPE_HIP_TRY(X.plan.ensure(CAPE_MAP_MAX_PLANES));
+    CAPE_HIP_TRY(X.header.ensure(1));
+    if (!X.headerHost)
+        CAPE_HIP_TRY(X.headerHost.alloc_host(1, hipHostMallocDefault));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    cape_map_commit_result result{};
+    {
+        StreamScope streamScope(h, stream);
+        if (streamScope.rc() != CAPE_OK)
+            return streamScope.rc();
+        cape::MapCommitParams p{};
+        p.mapPlanes = map.planes;
+        p.mapRings = map.rings;
+        p.mapVertices = map.vertices;
+        p.tracks = K.tracks;
+        p.tags = X.tags;
+        p.nMap = map.n;
+        p.nMapRings = X.nRings;
+        p.nMapVertices = X.nVertices;
+        p.frame = frame;
+        p.kalmanFrame = K.frames + frame;
+        p.trackResults = K.trackResults + (size_t)frame * n;
+        p.fusion = K.rows + (size_t)frame * WP;
+        p.kept = W.kept + (size_t)frame * WP;
+        p.measurements = M.rows;
+        p.worldVertices = M.vertices;
+        p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows and slabs cape_map_measure allocated: one per record)
+        p.boundaryCapacity = h->boundaryCap;
+        p.unionRows = U.rows + (size_t)frame * WP;
+        p.ringRows = h->mapUnionRings.current ? h->mapUnionRings.rows + (size_t)frame * WP : nullptr;
+        p.slab = U.vertices + (size_t)frame * SLAB * 2;
+        p.flags = flags;
+        p.nextId = *next_id;
+        p.outPlanes = X.planes;
+        p.outRings = X.rings;
+        p.outVertices = X.vertices;
+        p.outTracks = X.tracks;
+        p.outTags = X.tagsBack;
+        p.planesCapacity = planesCap;
+        p.ringsCapacity = ringsCap;
+        p.verticesCapacity = verticesCap;
+        p.plan = X.plan;
+        p.header = X.header;
+        CAPE_HIP_TRY(cape::launch_map_commit(p, (int)std::min<size_t>(planesCap, n + ((flags & CAPE_COMMIT_ADD_STAGED) ? WP : 0)), stream));
+        CAPE_HIP_TRY(hipMemcpyAsync(X.headerHost, X.header, sizeof(cape_map_commit_result), hipMemcpyDeviceToHost, stream));
+        CAPE_HIP_TRY(hipStreamSynchronize(stream)); // the one wait of the call: the header, and with it both kernels
+        result = *X.headerHost.get();
+    }
+    if (result.flags & CAPE_COMMIT_DONE)
+    {
+        map.planes.swap(X.planes);
+        map.rings.swap(X.rings);
+        map.vertices.swap(X.vertices);
+        K.tracks.swap(X.tracks);
+        X.tags.swap(X.tagsBack);
+        map.n = result.n_planes;
+        X.nRings = result.n_rings;
+        X.nVertices = result.n_vertices;
+        K.tracksN = result.n_planes; // the committed tracks are those of the new map
+        // what cape_map_upload invalidates: the words of the old map, the wide match against it and what was made of them
+        h->visibility.frames = 0;
+        K.matchedThisMap = false;
+        K.kalmanFrames = 0;
+        *next_id = result.next_id;
+    }
+    *out = result;
+    return CAPE_OK;
+}
+
+int cape_map_info(cape_handle h, int32_t* n_planes, int32_t* n_rings, int64_t* n_vertices)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (n_planes)
+        *n_planes = h->map.n;
+    if (n_rings)
+        *n_rings = h->mapCommit.nRings;
+    if (n_vertices)
+        *n_vertices = h->mapCommit.nVertices;
+    return CAPE_OK;
+}
+
+int cape_map_download(cape_handle h, cape_map_plane* planes, int32_t planes_capacity, cape_map_ring* rings, int32_t rings_capacity,
+                      double* vertices, int64_t vertices_capacity, cape_map_track* tracks)
+{
+    if (!h || planes_capacity < 0 || rings_capacity < 0 || vertices_capacity < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative capacity");
+    const auto& map = h->map;
+    const auto& X = h->mapCommit;
+    if (map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (map.n > planes_capacity || X.nRings > rings_capacity || X.nVertices > vertices_capacity)
+        return fail(CAPE_ERR_CAPACITY, "an array is too small for the device map (cape_map_info tells its sizes)");
+    if ((map.n > 0 && !planes) || (X.nRings > 0 && !rings) || (X.nVertices > 0 && !vertices))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null array");
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    const size_t n = (size_t)map.n;
+    if (n == 0)
+        return CAPE_OK;
+    CAPE_HIP_TRY(hipMemcpy(planes, map.planes, n * sizeof(cape_map_plane), hipMemcpyDeviceToHost));
+    CAPE_HIP_TRY(hipMemcpy(rings, map.rings, (size_t)X.nRings * sizeof(cape_map_ring), hipMemcpyDeviceToHost));
+    CAPE_HIP_TRY(hipMemcpy(vertices, map.vertices, (size_t)X.nVertices * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (tracks)
+    {
+        std::memset(tracks, 0, n * sizeof(cape_map_track)); // (the zero track per plane if none were uploaded for this map)
+        if (h->kalman.tracksN == map.n)
+        {
+            std::vector<cape::MapTrackState> T(n);
+            std::vector<cape::MapTrackTag> G(n);
+            CAPE_HIP_TRY(hipMemcpy(T.data(), h->kalman.tracks, n * sizeof(cape::MapTrackState), hipMemcpyDeviceToHost));
+            CAPE_HIP_TRY(hipMemcpy(G.data(), X.tags, n * sizeof(cape::MapTrackTag), hipMemcpyDeviceToHost));
+            for (size_t j = 0; j < n; ++j)
+            {
+                std::memcpy(tracks[j].covariance, T[j].covariance, sizeof(T[j].covariance));
+                tracks[j].successive_matched = T[j].successiveMatched;
+                tracks[j].failed_tracking = T[j].failedTracking;
+                tracks[j].flags = T[j].flags;
+                tracks[j].result = G[j].result;
+                tracks[j].id = G[j].id;
+            }
+        }
+    }
     return CAPE_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "cape_internal.h"
+#include "cape_map_commit.h"
 
 namespace cape {
 // every launcher returns the error of its own launch(es) (hipGetLastError right behind hipLaunchKernelGGL)
@@ -44,6 +45,7 @@ hipError_t launch_map_union_holes(const MapUnionParams& p, cape_plane_union_ring
 hipError_t launch_polygon_union(const PolygonUnionParams& p, hipStream_t stream);
 hipError_t launch_map_union_cut(const MapUnionParams& p, cape_plane_union_rings* ringRows /* frames x 128 */, int nFrames, hipStream_t stream);
 hipError_t launch_polygon_union_cut(const PolygonUnionParams& p, hipStream_t stream);
+hipError_t launch_map_commit(const MapCommitParams& p, int outPlanesBound /* workgroups of the copy kernel */, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -499,6 +501,24 @@ struct cape_handle_s
         Buffer<cape_plane_union_rings> rows; // frames x 128
         bool current = false;                // mapUnion's rows are those of one of these two calls: the table belongs to them
     } mapUnionRings;
+
+    // cape_map_commit / cape_map_info / cape_map_download: the BACK buffers of Map's planes, rings and vertices and of Kalman's tracks,
+    // which the commit writes and swaps with the front ones once its header says DONE, and the id / result of every track (front and
+    // back), which cape::MapTrackState does not hold.  The back buffers are grown behind drain_handle before the launch.  (Declared
+    // last, like the structs above.)
+    struct MapCommit
+    {
+        Buffer<cape_map_plane> planes;
+        Buffer<cape_map_ring> rings;
+        Buffer<double> vertices;
+        Buffer<cape::MapTrackState> tracks;
+        Buffer<cape::MapTrackTag> tags, tagsBack; // tags: parallel to Kalman::tracks, written by cape_map_upload_tracks and the commit
+        Buffer<cape::CommitPlanRow> plan;         // CAPE_MAP_MAX_PLANES rows
+        Buffer<cape_map_commit_result> header;    // device memory: the plan kernel's, read by the copy kernel
+        Buffer<cape_map_commit_result> headerHost; // pinned: the header comes back through it before the call returns
+        int nRings = 0;                           // rings and vertices of the map on the device (Map::n says the planes)
+        long long nVertices = 0;
+    } mapCommit;
 };
 
 namespace cape::abi {

@@ -1,5 +1,5 @@
 /* cape_host_map.h -- the host twins of libcape_primitives.so (host/polygon_capi.cpp) that track planes without the device: the map
- * matcher, the matcher of two consecutive frames, the visibility test in front of it, the map update and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
+ * matcher, the matcher of two consecutive frames, the visibility test in front of it, the map update, its halves and its commit and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
  * frame's kept planes.  Not part of libcape_hip's C ABI: no function of libcape_hip takes these types. */
 #ifndef CAPE_HOST_MAP_H
 #define CAPE_HOST_MAP_H
@@ -152,6 +152,24 @@ int cape_host_map_union_cut(const cape_host_map* map, const int32_t* match, cons
                             cape_plane_union_rings* rings_out, double* vertices_out);
 int cape_host_polygon_union_cut(const double* rings_a, const int32_t* counts_a, int32_t n_rings_a, const double* ring_b, int32_t n_b,
                                 const double* frames27, cape_plane_union* row_out, cape_plane_union_rings* rings_out, double* vertices_out);
+
+/* The twin of cape_map_commit (include/cape_hip.h) for ONE frame, and its reference byte for byte: the map after the frame from the
+ * results of the calls before it, with no arithmetic of its own.  map: planes, rings, vertices and tracks; frame: goes into the result
+ * only; frame_header and track_results[map->n_planes]: cape_map_kalman's (or cape_host_map_kalman's) for the frame; fusion,
+ * measurements and world_vertices: n_cur rows in kept-plane order and the world rings back to back (ring i of
+ * measurements[i].vertex_count pairs; vertex_offset is not read), as cape_host_map_union takes them, n_cur being frame_header->n_cur
+ * (0 for a frame flagged CAPE_MATCH_EXACT_OVERFLOW, at most 128); union_rows[128], rings[128] (NULL: the rows are a plain
+ * cape_map_union's, one ring per pair) and slab (CAPE_MAP_UNION_FRAME_VERTICES pairs): the frame's union results; flags:
+ * CAPE_COMMIT_ADD_STAGED; next_id: the id of the first appended plane (advanced if DONE).  The rules are cape_map_commit's, written
+ * once in csrc/cape_map_commit.h; the planes go through the host class and put_map like those of cape_host_map_update, which this
+ * call equals where the rows come from the host algebra and every pair is served.  result_out is always written.  Returns 0 for a
+ * DONE and for a refused frame alike -- a refused one (result_out->flags lacks CAPE_COMMIT_DONE) leaves map_out and next_id
+ * untouched; CAPE_ERR_INVALID_ARGUMENT for a NULL argument the frame needs, a negative count or frame, an unknown flag;
+ * CAPE_ERR_CAPACITY if an array of map_out is too small or NULL -- nothing is written then but the three counts of map_out. */
+int cape_host_map_commit(const cape_host_map* map, int32_t frame, const cape_frame_map_kalman* frame_header,
+                         const cape_map_track_result* track_results, const cape_plane_fusion* fusion, const cape_plane_measurement* measurements,
+                         const double* world_vertices, const cape_plane_union* union_rows, const cape_plane_union_rings* rings, const double* slab,
+                         uint32_t flags, uint64_t* next_id, cape_host_map* map_out, cape_map_commit_result* result_out);
 
 /* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
  * cape_gather_primitives[_root] or any other transport -- as the kept planes the two calls above take: no handle, no device.

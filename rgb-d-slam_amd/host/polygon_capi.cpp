@@ -4,7 +4,7 @@
 // cape_host_match_planes, cape_host_map_visibility, cape_host_map_update and cape_host_shard_frame are host twins a caller may use,
 // declared and described in cape_host_map.h: the first answers the frames cape_match_map flags, the second those the matchers of
 // consecutive frames flag, the third decides which map planes cape_match_map visits, the fourth is the map update (cape_host_map_kalman and cape_host_map_union are the
-// twins of its two device halves, cape_host_map_union_holes of the polygon half's holes mode, cape_host_ring_union and cape_host_polygon_union of the union's debug entries), the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
+// twins of its two device halves, cape_host_map_union_holes of the polygon half's holes mode, cape_host_map_commit of the commit that follows them, cape_host_ring_union and cape_host_polygon_union of the union's debug entries), the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -17,6 +17,7 @@
 #include "map_tracking.hpp"
 #include "cape_hip.h"
 #include "cape_host_map.h"
+#include "../csrc/cape_map_commit.h" // the commit's per-plane rules, shared with the plan kernel
 
 namespace {
 
@@ -1020,6 +1021,89 @@ extern "C" int cape_host_map_union_cut(const cape_host_map* map, const int32_t* 
     if (!rings_out)
         return CAPE_ERR_INVALID_ARGUMENT;
     return host_map_union(map, match, fusion, measurements, world_vertices, n_cur, rows_out, rings_out, vertices_out, true);
+}
+
+// The twin of cape_map_commit (cape_host_map.h): the decisions are the plan of csrc/cape_map_commit.h, one plane after the other; the
+// planes it names are then built like cape_host_map_update builds them and laid out by put_map.
+extern "C" int cape_host_map_commit(const cape_host_map* map, int32_t frame, const cape_frame_map_kalman* frame_header,
+                                    const cape_map_track_result* track_results, const cape_plane_fusion* fusion,
+                                    const cape_plane_measurement* measurements, const double* world_vertices, const cape_plane_union* union_rows,
+                                    const cape_plane_union_rings* rings, const double* slab, uint32_t flags, uint64_t* next_id,
+                                    cape_host_map* map_out, cape_map_commit_result* result_out)
+{
+    if (!map || !frame_header || !next_id || !map_out || !result_out || frame < 0 || map->n_planes < 0 || map->n_rings < 0 || map->n_vertices < 0 ||
+        (flags & ~(uint32_t)CAPE_COMMIT_ADD_STAGED) ||
+        (map->n_planes > 0 && (!map->planes || !map->tracks || !map->rings || !map->vertices || !track_results)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    const int32_t n_planes = map->n_planes, n_cur = cape::commit_kept_planes(*frame_header);
+    if (n_cur > 0 && (!fusion || !measurements || !world_vertices || !union_rows || !slab))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    try
+    {
+        std::vector<cape::CommitPlanRow> plan((size_t)n_planes + cape::kCommitMaxAppended);
+        const uint64_t unbounded = ~(uint64_t)0; // (the twin writes the caller's arrays: put_map checks them)
+        const cape_map_commit_result result =
+            cape::commit_plan_serial(map->planes, n_planes, map->rings, map->n_rings, map->n_vertices, frame, *frame_header, track_results, fusion,
+                                     measurements, union_rows, rings, flags, *next_id, unbounded, unbounded, unbounded, plan.data());
+        *result_out = result;
+        if (!(result.flags & CAPE_COMMIT_DONE))
+            return 0; // refused: map_out and next_id stay as they were
+        std::vector<MapEntry> out;
+        out.reserve((size_t)result.n_planes);
+        for (int32_t b = 0; b < result.n_planes; ++b)
+        {
+            const cape::CommitPlanRow& row = plan[b];
+            MapEntry e {};
+            if (row.source == cape::kCommitFromMeasure)
+            {
+                const cape_plane_measurement& m = measurements[row.index];
+                std::memcpy(e.plane.normal, m.staged_normal, sizeof(m.staged_normal));
+                e.plane.d = m.d;
+                std::memcpy(e.track.covariance, m.covariance, sizeof(m.covariance));
+                e.polygon = Polygon(ring_from(world_vertices + 2 * (size_t)row.srcVertex, m.vertex_count), {}, vec3(m.x_axis), vec3(m.y_axis),
+                                    vec3(m.center));
+                e.track.flags = CAPE_MAP_TRACK_STAGED;
+                e.track.result = CAPE_MAP_RESULT_APPENDED;
+                e.track.id = *next_id + (uint64_t)(b - n_planes);
+                out.push_back(std::move(e));
+                continue;
+            }
+            const int32_t j = row.source == cape::kCommitFromUnion ? union_rows[row.index].map_plane : (int32_t)row.index;
+            e.plane = map->planes[j];
+            e.track = map->tracks[j];
+            if (row.source == cape::kCommitFromUnion)
+            {
+                const cape_plane_fusion& F = fusion[row.index];
+                const cape_plane_union& U = union_rows[row.index];
+                std::memcpy(e.plane.normal, F.normal, sizeof(F.normal));
+                e.plane.d = F.d;
+                std::memcpy(e.track.covariance, F.covariance, sizeof(F.covariance));
+                std::vector<std::vector<vector2>> polygonRings;
+                size_t at = (size_t)row.srcVertex;
+                for (uint32_t k = 0; k < row.ringCount; ++k)
+                {
+                    const uint32_t count = rings ? rings[row.index].vertex_count[k] : U.vertex_count;
+                    polygonRings.push_back(ring_from(slab + 2 * at, count));
+                    at += count;
+                }
+                e.polygon = Polygon(polygonRings[0], {polygonRings.begin() + 1, polygonRings.end()}, vec3(U.x_axis), vec3(U.y_axis), vec3(U.center));
+            }
+            else if (!map_polygon(*map, e.plane, &e.polygon))
+                return CAPE_ERR_INVALID_ARGUMENT;
+            e.track.successive_matched = track_results[j].successive_matched;
+            e.track.failed_tracking = track_results[j].failed_tracking;
+            e.track.result = track_results[j].result;
+            out.push_back(std::move(e));
+        }
+        if (!put_map(out, *map_out))
+            return CAPE_ERR_CAPACITY;
+        *next_id = result.next_id;
+        return 0;
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
 }
 
 // The twins of cape_debug_ring_union, cape_debug_polygon_union and cape_debug_polygon_union_cut (cape_host_map.h): one pair given by

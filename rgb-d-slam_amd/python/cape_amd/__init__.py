@@ -252,6 +252,14 @@ PLANE_UNION_RINGS_DTYPE = np.dtype([
     ("pad", "<u4")], align=True)
 assert PLANE_UNION_RINGS_DTYPE.itemsize == 56
 
+# cape_map_commit: a frame's update written into the device map (cape_map_commit_result)
+COMMIT_ADD_STAGED = 1
+(COMMIT_DONE, COMMIT_FRAME_OVERFLOW, COMMIT_BAD_POSE_COV, COMMIT_HOST_PAIR, COMMIT_FAIL_POLYGON, COMMIT_CAPACITY) = (1 << k for k in range(6))
+MAP_COMMIT_RESULT_DTYPE = np.dtype([
+    ("flags", "<u4"), ("frame", "<i4"), ("n_planes", "<i4"), ("n_rings", "<i4"), ("n_vertices", "<i8"), ("n_updated", "<i4"),
+    ("n_appended", "<i4"), ("n_host_pairs", "<i4"), ("n_fail_polygon", "<i4"), ("next_id", "<u8")], align=True)
+assert MAP_COMMIT_RESULT_DTYPE.itemsize == 48
+
 
 class cape_host_map(C.Structure):
     """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
@@ -294,6 +302,7 @@ def _host_library():
         L.cape_host_polygon_union.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
         L.cape_host_map_union_cut.argtypes = L.cape_host_map_union_holes.argtypes
+        L.cape_host_map_commit.argtypes = [Map, C.c_int32] + [C.c_void_p] * 8 + [C.c_uint32, C.POINTER(C.c_uint64), Map, C.c_void_p]
         L.cape_host_polygon_union_cut.argtypes = L.cape_host_polygon_union.argtypes
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
@@ -506,6 +515,71 @@ def host_map_union_cut(map_arrays, match, fusion_rows, measurements, world_rings
     return _host_map_union(map_arrays, match, fusion_rows, measurements, world_rings, True, True)
 
 
+def host_map_commit(map_arrays, tracks, frame_header, track_results, fusion_rows, measurements, world_rings, union_rows, ring_rows, slab,
+                    flags=0, next_id=0, frame=0):
+    """cape_host_map_commit of libcape_primitives.so: the twin of Extractor.map_commit for ONE frame -- the map after the frame from
+    the results of the calls before it, byte for byte what the device writes.
+
+    map_arrays: pack_map(...); tracks: MAP_TRACK_DTYPE array parallel to the planes; frame_header: the frame's FRAME_MAP_KALMAN_DTYPE
+    scalar and track_results its MAP_TRACK_RESULT_DTYPE[n_map] (map_kalman_rows / host_map_kalman); fusion_rows, measurements,
+    world_rings: n_cur rows and rings in kept-plane order, as host_map_union takes them; union_rows: PLANE_UNION_DTYPE[n_cur or 128],
+    ring_rows: PLANE_UNION_RINGS_DTYPE likewise, or None for the rows of a plain map_union; slab: the frame's vertices
+    (MAP_UNION_FRAME_VERTICES x 2); flags: COMMIT_ADD_STAGED.
+    Returns ((planes, rings, vertices), tracks, result: MAP_COMMIT_RESULT_DTYPE scalar, next_id): the new map in pack_map's layout, or
+    -- for a refused frame, result["flags"] without COMMIT_DONE -- (None, None, result, next_id unchanged)."""
+    L = _host_library()
+    src, src_view = _map_arrays(map_arrays, np.ascontiguousarray(tracks, MAP_TRACK_DTYPE))
+    n_map = len(src["planes"])
+    if len(src["tracks"]) != n_map:
+        raise CapeError("host_map_commit: one track per map plane")
+    H = np.zeros(1, FRAME_MAP_KALMAN_DTYPE)
+    H[0] = frame_header
+    R = np.ascontiguousarray(track_results, MAP_TRACK_RESULT_DTYPE).reshape(-1)
+    if len(R) != n_map:
+        raise CapeError("host_map_commit: one track result per map plane")
+    W = MATCH_MAP_WIDE_MAX_PLANES
+    n_cur = 0 if H[0]["flags"] & MATCH_EXACT_OVERFLOW else min(max(int(H[0]["n_cur"]), 0), W)
+
+    def rows_of(a, dtype, what):
+        out = np.zeros(W, dtype)
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype).reshape(-1)
+            if len(a) < n_cur:
+                raise CapeError(f"host_map_commit: fewer {what} than the frame's kept planes")
+            out[:min(len(a), W)] = a[:W]
+        return out
+
+    F, Mr, U = (rows_of(a, t, w) for a, t, w in ((fusion_rows, PLANE_FUSION_DTYPE, "fusion rows"), (measurements, PLANE_MEASUREMENT_DTYPE,
+                                                 "measurement rows"), (union_rows, PLANE_UNION_DTYPE, "union rows")))
+    Q = None if ring_rows is None else rows_of(ring_rows, PLANE_UNION_RINGS_DTYPE, "ring rows")
+    rings = [np.ascontiguousarray(r, np.float64).reshape(-1, 2) for r in world_rings[:n_cur]]
+    if len(rings) != n_cur or any(len(r) != int(m["vertex_count"]) for r, m in zip(rings, Mr)):
+        raise CapeError("host_map_commit: one world ring per kept plane, of its measurement row's vertex_count")
+    Wv = np.ascontiguousarray(np.concatenate(rings + [np.zeros((1, 2))]))
+    S = np.zeros((MAP_UNION_FRAME_VERTICES, 2))
+    if slab is not None:
+        slab = np.ascontiguousarray(slab, np.float64).reshape(-1, 2)
+        S[:len(slab)] = slab[:MAP_UNION_FRAME_VERTICES]
+    nid = C.c_uint64(next_id)
+    result = np.zeros(1, MAP_COMMIT_RESULT_DTYPE)
+
+    def call(cap_p, cap_r, cap_v):
+        out = dict(planes=np.zeros(max(cap_p, 1), MAP_PLANE_DTYPE), rings=np.zeros(max(cap_r, 1), MAP_RING_DTYPE),
+                   vertices=np.zeros((max(cap_v, 1), 2)), tracks=np.zeros(max(cap_p, 1), MAP_TRACK_DTYPE))
+        v = _view(cape_host_map, out, planes_capacity=len(out["planes"]), rings_capacity=len(out["rings"]), vertices_capacity=len(out["vertices"]))
+        rc = L.cape_host_map_commit(C.byref(src_view), frame, H.ctypes.data, R.ctypes.data, F.ctypes.data, Mr.ctypes.data, Wv.ctypes.data,
+                                    U.ctypes.data, None if Q is None else Q.ctypes.data, S.ctypes.data, flags, C.byref(nid), C.byref(v),
+                                    result.ctypes.data)
+        return rc, (out, v), (v.n_planes, v.n_rings, v.n_vertices)
+
+    out, v = _retry_on_capacity("cape_host_map_commit", call, (n_map + n_cur, len(src["rings"]) + MAP_MAX_HOLES * n_cur + n_cur + 8,
+                                                               len(src["vertices"]) + MAP_UNION_FRAME_VERTICES + len(Wv)))
+    if not result[0]["flags"] & COMMIT_DONE:
+        return None, None, result[0], nid.value
+    return ((out["planes"][:v.n_planes].copy(), out["rings"][:v.n_rings].copy(), out["vertices"][:v.n_vertices].copy()),
+            out["tracks"][:v.n_planes].copy(), result[0], nid.value)
+
+
 def _polygon_union_args(rings_a, ring_b, frames):
     rings = [np.ascontiguousarray(r, np.float64).reshape(-1, 2) for r in rings_a]
     a = np.ascontiguousarray(np.concatenate(rings))
@@ -707,6 +781,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_union", "cape_copy_map_union", "cape_device_map_union", "cape_debug_ring_union",
     "cape_map_union_holes", "cape_copy_map_union_rings", "cape_device_map_union_rings", "cape_debug_polygon_union",
     "cape_map_union_cut", "cape_debug_polygon_union_cut",
+    "cape_map_commit", "cape_map_info", "cape_map_download",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -812,6 +887,9 @@ def load_library():
     L.cape_debug_polygon_union.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
     L.cape_map_union_cut.argtypes = [vp, C.c_int32, vp]
     L.cape_debug_polygon_union_cut.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp]
+    L.cape_map_commit.argtypes = [vp, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64), vp, vp]
+    L.cape_map_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.cape_map_download.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1293,6 +1371,37 @@ class Extractor:
         rows, ver = self.map_union_rows(n_frames)
         rings = self.map_union_ring_rows(n_frames)
         return [(rows[f].copy(), rings[f].copy(), _union_polygons(rows[f], rings[f], ver[f])) for f in range(n_frames)]
+
+    # ---- the commit of the map update (needs map_union, map_union_holes or map_union_cut of the batch) ----
+    def map_commit(self, frame, flags=0, next_id=0, stream=0):
+        """cape_map_commit: frame `frame` of the last map_union / map_union_holes / map_union_cut written into the device map and
+        tracks -- the sequential step of a tracking loop; it returns once the result header is back.  flags: COMMIT_ADD_STAGED;
+        next_id: the id of the first appended plane.  Returns (result: MAP_COMMIT_RESULT_DTYPE scalar, next_id).  A refused frame
+        (result["flags"] without COMMIT_DONE) changes nothing; after a DONE one match_map_wide + map_kalman run on the new map without
+        another upload."""
+        nid = C.c_uint64(next_id)
+        result = np.zeros(1, MAP_COMMIT_RESULT_DTYPE)
+        _check(self.L, self.L.cape_map_commit(self.h, frame, flags, C.byref(nid), result.ctypes.data_as(C.c_void_p), C.c_void_p(stream)),
+               "cape_map_commit")
+        if result[0]["flags"] & COMMIT_DONE:
+            self.map_size = int(result[0]["n_planes"])
+        return result[0], nid.value
+
+    def map_info(self):
+        """cape_map_info: (n_planes, n_rings, n_vertices) of the device map as it stands"""
+        n, r, v = C.c_int32(), C.c_int32(), C.c_int64()
+        _check(self.L, self.L.cape_map_info(self.h, C.byref(n), C.byref(r), C.byref(v)), "cape_map_info")
+        return n.value, r.value, v.value
+
+    def download_map(self):
+        """cape_map_download: ((planes, rings, vertices), tracks) of the device map and tracks as they stand, in pack_map's layout --
+        after upload_map the upload with the rings re-oriented and laid out plane after plane, after a DONE map_commit the committed
+        map; the tracks are all zero if none were uploaded for this map."""
+        n, r, v = self.map_info()
+        P, R, V, T = np.zeros(n, MAP_PLANE_DTYPE), np.zeros(r, MAP_RING_DTYPE), np.zeros((v, 2)), np.zeros(n, MAP_TRACK_DTYPE)
+        _check(self.L, self.L.cape_map_download(self.h, P.ctypes.data_as(C.c_void_p), n, R.ctypes.data_as(C.c_void_p), r,
+                                                V.ctypes.data_as(C.c_void_p), v, T.ctypes.data_as(C.c_void_p)), "cape_map_download")
+        return (P, R, V), T
 
     def debug_polygon_union(self, rings_a, ring_b, frames=None):
         """cape_debug_polygon_union: map_union_holes' per-pair device function on one pair -- rings_a = [outer, hole, ...] of the map
