@@ -806,7 +806,7 @@ int cape_copy_spill_measurements(cape_handle h, int32_t first, int32_t count, ca
 /* Tracking state of one map plane, parallel to cape_map_plane: what Feature_Map::update_map (feature_map.hpp:367-384, :701-830)
  * reads and changes besides the plane and its polygon.  Promotion from staged to local, removal from staged and the loss of a local
  * plane reorder or delete entries of the ordered list: cape_host_map_update (host/cape_host_map.h) and cape_map_kalman report them
- * in `result` and leave them to the caller. */
+ * in `result` and leave them to the caller; cape_map_maintain (below) executes them on the device map. */
 typedef struct cape_map_track
 {
     double covariance[16];      /* 4 x 4 covariance of (normal, d), row-major */
@@ -1098,6 +1098,69 @@ int cape_map_info(cape_handle h, int32_t* n_planes, int32_t* n_rings, int64_t* n
  * small (cape_map_info tells the sizes). */
 int cape_map_download(cape_handle h, cape_map_plane* planes, int32_t planes_capacity, cape_map_ring* rings, int32_t rings_capacity,
                       double* vertices, int64_t vertices_capacity, cape_map_track* tracks /* planes_capacity, may be NULL */);
+
+/* The LIST MAINTENANCE of the map update on the device: PROMOTE, DROP and LOST executed on the device map and tracks as they stand --
+ * after a DONE cape_map_commit, or after cape_map_upload + cape_map_upload_tracks -- with a RETIRED LOG on the device that receives the
+ * lost planes.  It is what Feature_Map::update_local_map (feature_map.hpp:748-762) and update_staged_map (:805-830) do to their two
+ * containers, with the constructor LocalMapPlane(const StagedMapPlane&) (map_primitive.cpp:286-318), on this project's ONE ordered
+ * list.  The host twin cape_host_map_maintain (host/cape_host_map.h) gives the same bytes.  Per map plane j, decided from the
+ * track's counters and flags (not from `result`; after a commit the two agree):
+ *   staged (CAPE_MAP_TRACK_STAGED), in this order:
+ *     successive_matched >= 4: PROMOTE.  The constructor throws unless is_covariance_valid of the 4 x 4 covariance and
+ *       double_equal(|normal|, 1) (threshold DBL_EPSILON) hold.  Where both hold the plane stays in the list with
+ *       CAPE_MAP_TRACK_STAGED cleared and failed_tracking = 0; successive_matched, id, result, CAPE_MAP_TRACK_MOVING, covariance,
+ *       plane, frame and rings are kept.  Where one fails the plane stays staged and unchanged and is counted in n_promote_refused;
+ *       it is not dropped either (the reference's `else if` is not reached; there the iterator does not advance at all);
+ *     else failed_tracking >= 2: DROP.  The plane is removed and not logged;
+ *     else the plane is kept as it is;
+ *   local: failed_tracking >= 10: LOST.  The plane is removed and appended to the retired log -- the plane, all its rings and
+ *     vertices and the whole cape_map_track, id and CAPE_MAP_TRACK_MOVING included; the caller applies the reference's
+ *     `if (not is_moving()) write_to_file` (feature_map.hpp:750-754).  Else the plane is kept.
+ * The new list is a STABLE PARTITION of the survivors: first those that are not staged after the step, in list order, then those
+ * that are staged, in list order -- so a promoted plane goes behind the last local plane of a list that has its local planes first,
+ * everything else keeps its relative order, and the commit's later appends still land at the end.  Rings and vertices are laid out
+ * plane after plane, back to back, as cape_map_upload lays them out.  The call is idempotent.
+ * out->flags is exactly one of:
+ *   CAPE_MAINTAIN_DONE: map, tracks and log are the new ones.  It invalidates what a DONE commit invalidates (visibility words, map
+ *     matches, Kalman and union results), not the tracks and not cape_map_measure's rows;
+ *   CAPE_MAINTAIN_NOTHING: no plane is promoted, dropped or lost.  Nothing is written, swapped or invalidated;
+ *   a refusal, which changes nothing, log included: CAPE_MAINTAIN_CAPACITY, a map plane whose rings do not lie in the map's buffers;
+ *     CAPE_MAINTAIN_LOG_FULL, the lost planes of this call do not fit the log's CAPE_MAP_RETIRED_MAX_PLANES (both bits may be set).
+ * The class counts are what the plan counted either way; the sizes are the old ones unless DONE.
+ * Like the commit, the work (a plan kernel and a copy kernel) is enqueued on `stream` and the call RETURNS once the result header has
+ * come back through pinned memory.  CAPE_ERR_INVALID_ARGUMENT: NULL handle or out, non-zero flags, no map; CAPE_ERR_CAPACITY: no
+ * tracks are current for the map (cape_map_upload_tracks, or a DONE commit). */
+#define CAPE_MAP_RETIRED_MAX_PLANES 4096 /* planes the retired log holds until cape_map_retired_clear */
+enum /* cape_map_maintain_result.flags */
+{
+    CAPE_MAINTAIN_DONE = 1u << 0,     /* the map, the tracks and the log are the new ones */
+    CAPE_MAINTAIN_NOTHING = 1u << 1,  /* nothing was due: nothing written, swapped or invalidated */
+    CAPE_MAINTAIN_CAPACITY = 1u << 2, /* a map plane whose rings do not lie in the map's buffers */
+    CAPE_MAINTAIN_LOG_FULL = 1u << 3  /* the lost planes of this call do not fit the retired log */
+};
+typedef struct cape_map_maintain_result
+{
+    uint32_t flags;
+    int32_t n_planes, n_rings; /* of the map after the call */
+    int32_t n_local;           /* survivors that are not staged after the step: the first n_local planes of a DONE call's list */
+    int64_t n_vertices;
+    int32_t n_staged; /* survivors that are staged after the step */
+    int32_t n_promoted, n_promote_refused, n_dropped, n_lost;
+    int32_t n_retired, n_retired_rings; /* of the retired log after the call */
+    uint32_t pad;
+    int64_t n_retired_vertices;
+} cape_map_maintain_result;
+int cape_map_maintain(cape_handle h, uint32_t flags /* must be 0 */, cape_map_maintain_result* out, void* stream);
+/* The RETIRED LOG: the lost planes of every DONE cape_map_maintain since the handle was created or the log was cleared, in the order
+ * they were lost, in the layout of a map -- planes, rings, vertices, tracks -- whose ring_first and vertex_offset are relative to the
+ * log's own arrays.  It survives cape_map_upload, commits and further maintains.  cape_map_retired_info: its sizes (any pointer may be
+ * NULL).  cape_map_retired_download: a synchronous copy under the rules of cape_map_download (tracks may be NULL).
+ * cape_map_retired_clear: the log is empty afterwards (it waits for a call in flight).  CAPE_ERR_INVALID_ARGUMENT: NULL handle, a
+ * negative capacity, a NULL array the log needs; CAPE_ERR_CAPACITY: an array is too small. */
+int cape_map_retired_info(cape_handle h, int32_t* n_planes, int32_t* n_rings, int64_t* n_vertices);
+int cape_map_retired_download(cape_handle h, cape_map_plane* planes, int32_t planes_capacity, cape_map_ring* rings, int32_t rings_capacity,
+                              double* vertices, int64_t vertices_capacity, cape_map_track* tracks /* planes_capacity, may be NULL */);
+int cape_map_retired_clear(cape_handle h);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as

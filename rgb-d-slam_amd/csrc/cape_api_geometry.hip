@@ -1536,6 +1536,152 @@ int cape_map_download(cape_handle h, cape_map_plane* planes, int32_t planes_capa
     return CAPE_OK;
 }
 
+// cape_map_maintain: PROMOTE, DROP and LOST executed on the device map.  Like the commit: two launches, then the one small read that
+// tells the host the new sizes; front and back buffers are swapped here, on the host, only if the header says DONE.
+int cape_map_maintain(cape_handle h, uint32_t flags, cape_map_maintain_result* out, void* stream_)
+{
+    if (!h || !out || flags != 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or result, or a flag (none is defined)");
+    auto& map = h->map;
+    auto& K = h->kalman;
+    auto& X = h->mapCommit;
+    auto& R = h->mapMaintain;
+    if (map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (K.tracksN != map.n)
+        return fail(CAPE_ERR_CAPACITY, "no tracks are current for the map (cape_map_upload_tracks, or a DONE cape_map_commit)");
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    // the back buffers and the log, to bounds the host knows: the new map is no larger than the old one, and the log takes at most
+    // the whole map on top of what it holds
+    const size_t n = (size_t)map.n, nRings = (size_t)X.nRings, nVertices = (size_t)X.nVertices;
+    const auto drain = [h] { return drain_handle(h); }; // (a back buffer was the front one of an earlier map: a call in flight may read it)
+    CAPE_HIP_TRY(X.planes.grow(n, drain));
+    CAPE_HIP_TRY(X.rings.grow(nRings, drain));
+    CAPE_HIP_TRY(X.vertices.grow(nVertices * 2, drain));
+    CAPE_HIP_TRY(X.tracks.grow(n, drain));
+    CAPE_HIP_TRY(X.tagsBack.grow(n, drain));
+    const size_t logPlanes = std::min<size_t>(CAPE_MAP_RETIRED_MAX_PLANES, (size_t)R.nPlanes + n), logRings = (size_t)R.nRings + nRings,
+                 logVertices = (size_t)R.nVertices + nVertices;
+    CAPE_HIP_TRY(R.planes.grow_keeping(logPlanes, (size_t)R.nPlanes, drain));
+    CAPE_HIP_TRY(R.tracks.grow_keeping(logPlanes, (size_t)R.nPlanes, drain));
+    CAPE_HIP_TRY(R.rings.grow_keeping(logRings, (size_t)R.nRings, drain));
+    CAPE_HIP_TRY(R.vertices.grow_keeping(logVertices * 2, (size_t)R.nVertices * 2, drain));
+    CAPE_HIP_TRY(R.plan.ensure(CAPE_MAP_MAX_PLANES));
+    CAPE_HIP_TRY(R.header.ensure(1));
+    if (!R.headerHost)
+        CAPE_HIP_TRY(R.headerHost.alloc_host(1, hipHostMallocDefault));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    cape_map_maintain_result result{};
+    {
+        StreamScope streamScope(h, stream);
+        if (streamScope.rc() != CAPE_OK)
+            return streamScope.rc();
+        cape::MapMaintainParams p{};
+        p.mapPlanes = map.planes;
+        p.mapRings = map.rings;
+        p.mapVertices = map.vertices;
+        p.tracks = K.tracks;
+        p.tags = X.tags;
+        p.nMap = map.n;
+        p.nMapRings = X.nRings;
+        p.nMapVertices = X.nVertices;
+        p.outPlanes = X.planes;
+        p.outRings = X.rings;
+        p.outVertices = X.vertices;
+        p.outTracks = X.tracks;
+        p.outTags = X.tagsBack;
+        p.planesCapacity = n;
+        p.ringsCapacity = nRings;
+        p.verticesCapacity = nVertices;
+        p.logPlanes = R.planes;
+        p.logRings = R.rings;
+        p.logVertices = R.vertices;
+        p.logTracks = R.tracks;
+        p.log.held = cape::MaintainCursor {R.nPlanes, R.nRings, R.nVertices};
+        p.log.planesCapacity = logPlanes;
+        p.log.ringsCapacity = logRings;
+        p.log.verticesCapacity = logVertices;
+        p.plan = R.plan;
+        p.header = R.header;
+        CAPE_HIP_TRY(cape::launch_map_maintain(p, stream));
+        CAPE_HIP_TRY(hipMemcpyAsync(R.headerHost, R.header, sizeof(cape_map_maintain_result), hipMemcpyDeviceToHost, stream));
+        CAPE_HIP_TRY(hipStreamSynchronize(stream)); // the one wait of the call: the header, and with it both kernels
+        result = *R.headerHost.get();
+    }
+    if (result.flags & CAPE_MAINTAIN_DONE)
+    {
+        map.planes.swap(X.planes);
+        map.rings.swap(X.rings);
+        map.vertices.swap(X.vertices);
+        K.tracks.swap(X.tracks);
+        X.tags.swap(X.tagsBack);
+        map.n = result.n_planes;
+        X.nRings = result.n_rings;
+        X.nVertices = result.n_vertices;
+        K.tracksN = result.n_planes; // the tracks are those of the new map
+        R.nPlanes = result.n_retired;
+        R.nRings = result.n_retired_rings;
+        R.nVertices = result.n_retired_vertices;
+        // what a DONE commit invalidates: the words of the old map, the wide match against it and what was made of them
+        h->visibility.frames = 0;
+        K.matchedThisMap = false;
+        K.kalmanFrames = 0;
+    }
+    *out = result;
+    return CAPE_OK;
+}
+
+int cape_map_retired_info(cape_handle h, int32_t* n_planes, int32_t* n_rings, int64_t* n_vertices)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_planes)
+        *n_planes = h->mapMaintain.nPlanes;
+    if (n_rings)
+        *n_rings = h->mapMaintain.nRings;
+    if (n_vertices)
+        *n_vertices = h->mapMaintain.nVertices;
+    return CAPE_OK;
+}
+
+int cape_map_retired_download(cape_handle h, cape_map_plane* planes, int32_t planes_capacity, cape_map_ring* rings, int32_t rings_capacity,
+                              double* vertices, int64_t vertices_capacity, cape_map_track* tracks)
+{
+    if (!h || planes_capacity < 0 || rings_capacity < 0 || vertices_capacity < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative capacity");
+    const auto& R = h->mapMaintain;
+    if (R.nPlanes > planes_capacity || R.nRings > rings_capacity || R.nVertices > vertices_capacity)
+        return fail(CAPE_ERR_CAPACITY, "an array is too small for the retired log (cape_map_retired_info tells its sizes)");
+    if ((R.nPlanes > 0 && !planes) || (R.nRings > 0 && !rings) || (R.nVertices > 0 && !vertices))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null array");
+    if (R.nPlanes == 0)
+        return CAPE_OK;
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(hipMemcpy(planes, R.planes, (size_t)R.nPlanes * sizeof(cape_map_plane), hipMemcpyDeviceToHost));
+    CAPE_HIP_TRY(hipMemcpy(rings, R.rings, (size_t)R.nRings * sizeof(cape_map_ring), hipMemcpyDeviceToHost));
+    CAPE_HIP_TRY(hipMemcpy(vertices, R.vertices, (size_t)R.nVertices * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (tracks)
+        CAPE_HIP_TRY(hipMemcpy(tracks, R.tracks, (size_t)R.nPlanes * sizeof(cape_map_track), hipMemcpyDeviceToHost));
+    return CAPE_OK;
+}
+
+int cape_map_retired_clear(cape_handle h)
+{
+    if (!h)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle");
+    auto& R = h->mapMaintain;
+    if (R.nPlanes > 0)
+    {
+        CAPE_ON_DEVICE(h);
+        CAPE_HIP_TRY(drain_handle(h));
+    }
+    R.nPlanes = R.nRings = 0;
+    R.nVertices = 0;
+    return CAPE_OK;
+}
+
 int cape_device_polygons(cape_handle h, cape_polygon** polygons, double** vertices)
 {
     if (!h)

@@ -11,6 +11,7 @@
 
 #include "cape_internal.h"
 #include "cape_map_commit.h"
+#include "cape_map_maintain.h"
 
 namespace cape {
 // every launcher returns the error of its own launch(es) (hipGetLastError right behind hipLaunchKernelGGL)
@@ -46,6 +47,7 @@ hipError_t launch_polygon_union(const PolygonUnionParams& p, hipStream_t stream)
 hipError_t launch_map_union_cut(const MapUnionParams& p, cape_plane_union_rings* ringRows /* frames x 128 */, int nFrames, hipStream_t stream);
 hipError_t launch_polygon_union_cut(const PolygonUnionParams& p, hipStream_t stream);
 hipError_t launch_map_commit(const MapCommitParams& p, int outPlanesBound /* workgroups of the copy kernel */, hipStream_t stream);
+hipError_t launch_map_maintain(const MapMaintainParams& p, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -90,6 +92,23 @@ template <typename T> class Buffer
             return hipSuccess;
         const hipError_t e = sync();
         return e != hipSuccess ? e : alloc(n);
+    }
+    // the same for device memory whose first `held` elements are kept (the retired log): a new allocation of at least twice the old
+    // size, a device copy, a swap
+    template <typename Sync> hipError_t grow_keeping(size_t n, size_t held, Sync sync)
+    {
+        if (_n >= n)
+            return hipSuccess;
+        hipError_t e = sync();
+        if (e != hipSuccess)
+            return e;
+        Buffer wider;
+        e = wider.alloc(n > 2 * _n ? n : 2 * _n);
+        if (e == hipSuccess && held > 0)
+            e = hipMemcpy(wider._p, _p, held * sizeof(T), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess)
+            swap(wider);
+        return e;
     }
     void reset()
     {
@@ -519,6 +538,22 @@ struct cape_handle_s
         int nRings = 0;                           // rings and vertices of the map on the device (Map::n says the planes)
         long long nVertices = 0;
     } mapCommit;
+
+    // cape_map_maintain / cape_map_retired_*: the retired log -- the lost planes in a map's layout, offsets relative to these arrays --
+    // and the call's plan and header.  The map's back buffers are MapCommit's.  The log outlives every map: only
+    // cape_map_retired_clear empties it.  Its arrays are grown behind drain_handle before the launch, their contents kept.
+    struct MapMaintain
+    {
+        Buffer<cape_map_plane> planes;
+        Buffer<cape_map_ring> rings;
+        Buffer<double> vertices;
+        Buffer<cape_map_track> tracks;
+        int nPlanes = 0, nRings = 0; // what the log holds
+        long long nVertices = 0;
+        Buffer<cape::MaintainPlanRow> plan;           // CAPE_MAP_MAX_PLANES rows
+        Buffer<cape_map_maintain_result> header;     // device memory: the plan kernel's, read by the copy kernel
+        Buffer<cape_map_maintain_result> headerHost; // pinned: the header comes back through it before the call returns
+    } mapMaintain;
 };
 
 namespace cape::abi {

@@ -1,5 +1,5 @@
 /* cape_host_map.h -- the host twins of libcape_primitives.so (host/polygon_capi.cpp) that track planes without the device: the map
- * matcher, the matcher of two consecutive frames, the visibility test in front of it, the map update, its halves and its commit and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
+ * matcher, the matcher of two consecutive frames, the visibility test in front of it, the map update, its halves, its commit and its list maintenance and the reader of a gathered shard, over a map in the layout of cape_map_upload (include/cape_hip.h) and a
  * frame's kept planes.  Not part of libcape_hip's C ABI: no function of libcape_hip takes these types. */
 #ifndef CAPE_HOST_MAP_H
 #define CAPE_HOST_MAP_H
@@ -170,6 +170,19 @@ int cape_host_map_commit(const cape_host_map* map, int32_t frame, const cape_fra
                          const cape_map_track_result* track_results, const cape_plane_fusion* fusion, const cape_plane_measurement* measurements,
                          const double* world_vertices, const cape_plane_union* union_rows, const cape_plane_union_rings* rings, const double* slab,
                          uint32_t flags, uint64_t* next_id, cape_host_map* map_out, cape_map_commit_result* result_out);
+
+/* The twin of cape_map_maintain (include/cape_hip.h), and its reference byte for byte: PROMOTE, DROP and LOST executed on `map`
+ * (planes, rings, vertices and tracks) -- the decisions are cape_map_maintain's, written once in csrc/cape_map_maintain.h and taken
+ * one plane after the other (maintain_plan_serial); a promote candidate is promotable where mt::is_covariance_valid of its 4 x 4
+ * covariance and |normal| = 1 within DBL_EPSILON hold; the planes then go through the host class and put_map like those of
+ * cape_host_map_commit.  map_out: the new map, a stable partition of the survivors (not staged first, then staged).  retired_out: the
+ * retired log, an INPUT AND an output -- its counts say what it holds on entry (they, not the arrays, decide
+ * CAPE_MAINTAIN_LOG_FULL against CAPE_MAP_RETIRED_MAX_PLANES), the lost planes are appended behind that with ring_first and
+ * vertex_offset relative to the log's own arrays, and the counts are advanced.  result_out is always written.  Returns 0 for DONE,
+ * NOTHING and a refusal alike -- only DONE writes map_out and retired_out; CAPE_ERR_INVALID_ARGUMENT for a NULL argument, a negative
+ * count or a map plane without a polygon; CAPE_ERR_CAPACITY if an array of map_out or retired_out is too small or NULL (the old map's
+ * sizes, and the log's plus the old map's, always suffice) -- nothing is written then. */
+int cape_host_map_maintain(const cape_host_map* map, cape_host_map* map_out, cape_host_map* retired_out, cape_map_maintain_result* result_out);
 
 /* One frame of a packed shard -- the bytes cape_pack_primitives writes with CAPE_GATHER_POLYGONS, as they arrive from
  * cape_gather_primitives[_root] or any other transport -- as the kept planes the two calls above take: no handle, no device.

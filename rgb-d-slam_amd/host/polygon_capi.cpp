@@ -4,7 +4,7 @@
 // cape_host_match_planes, cape_host_map_visibility, cape_host_map_update and cape_host_shard_frame are host twins a caller may use,
 // declared and described in cape_host_map.h: the first answers the frames cape_match_map flags, the second those the matchers of
 // consecutive frames flag, the third decides which map planes cape_match_map visits, the fourth is the map update (cape_host_map_kalman and cape_host_map_union are the
-// twins of its two device halves, cape_host_map_union_holes of the polygon half's holes mode, cape_host_map_commit of the commit that follows them, cape_host_ring_union and cape_host_polygon_union of the union's debug entries), the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
+// twins of its two device halves, cape_host_map_union_holes of the polygon half's holes mode, cape_host_map_commit of the commit that follows them, cape_host_map_maintain of the list maintenance behind it, cape_host_ring_union and cape_host_polygon_union of the union's debug entries), the fifth reads a gathered shard.  They share the conversions of the anonymous namespace below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,6 +18,7 @@
 #include "cape_hip.h"
 #include "cape_host_map.h"
 #include "../csrc/cape_map_commit.h" // the commit's per-plane rules, shared with the plan kernel
+#include "../csrc/cape_map_maintain.h" // the list maintenance's, likewise
 
 namespace {
 
@@ -128,11 +129,14 @@ struct MapEntry
 };
 
 // The entries as a map in cape_map_upload's layout, each plane's frame and rings from its polygon.  The three counts are
-// written either way; false, and nothing else written, if an array of `out` is too small or NULL.
-bool put_map(std::vector<MapEntry>& entries, cape_host_map& out)
+// written either way; false, and nothing else written, if an array of `out` is too small or NULL.  `append` (the retired log): the
+// entries go behind what `out` holds by its counts, which are advanced -- or, with false, left as they were.
+bool put_map(std::vector<MapEntry>& entries, cape_host_map& out, bool append = false)
 {
-    int32_t nr = 0;
-    int64_t nv = 0;
+    const int32_t p0 = append ? out.n_planes : 0, r0 = append ? out.n_rings : 0;
+    const int64_t v0 = append ? out.n_vertices : 0;
+    int32_t nr = r0;
+    int64_t nv = v0;
     for (const MapEntry& e : entries)
     {
         nr += 1 + (int32_t)e.polygon.interior_rings().size();
@@ -140,14 +144,18 @@ bool put_map(std::vector<MapEntry>& entries, cape_host_map& out)
         for (const auto& h : e.polygon.interior_rings())
             nv += (int64_t)h.size();
     }
-    out.n_planes = (int32_t)entries.size();
-    out.n_rings = nr;
-    out.n_vertices = nv;
-    if ((int64_t)entries.size() > out.planes_capacity || nr > out.rings_capacity || nv > out.vertices_capacity || !out.planes || !out.tracks ||
-        !out.rings || !out.vertices)
+    const bool fits = (int64_t)p0 + (int64_t)entries.size() <= out.planes_capacity && nr <= out.rings_capacity && nv <= out.vertices_capacity &&
+                      out.planes && out.tracks && out.rings && out.vertices;
+    if (!append || fits)
+    {
+        out.n_planes = p0 + (int32_t)entries.size();
+        out.n_rings = nr;
+        out.n_vertices = nv;
+    }
+    if (!fits)
         return false;
-    int32_t r = 0;
-    int64_t v = 0;
+    int32_t r = r0;
+    int64_t v = v0;
     for (size_t j = 0; j < entries.size(); ++j)
     {
         MapEntry& e = entries[j];
@@ -170,8 +178,8 @@ bool put_map(std::vector<MapEntry>& entries, cape_host_map& out)
         put(e.polygon.boundary());
         for (const auto& h : e.polygon.interior_rings())
             put(h);
-        out.planes[j] = e.plane;
-        out.tracks[j] = e.track;
+        out.planes[(size_t)p0 + j] = e.plane;
+        out.tracks[(size_t)p0 + j] = e.track;
     }
     return true;
 }
@@ -1098,6 +1106,71 @@ extern "C" int cape_host_map_commit(const cape_host_map* map, int32_t frame, con
         if (!put_map(out, *map_out))
             return CAPE_ERR_CAPACITY;
         *next_id = result.next_id;
+        return 0;
+    }
+    catch (const std::exception&)
+    {
+        return CAPE_ERR_INVALID_ARGUMENT;
+    }
+}
+
+// The twin of cape_map_maintain (cape_host_map.h): the decisions are the plan of csrc/cape_map_maintain.h, one plane after the other,
+// with the promote candidates' check made here by the host algebra; the planes it keeps or retires go through the host class and
+// put_map.
+extern "C" int cape_host_map_maintain(const cape_host_map* map, cape_host_map* map_out, cape_host_map* retired_out, cape_map_maintain_result* result_out)
+{
+    if (!map || !map_out || !retired_out || !result_out || map->n_planes < 0 || map->n_rings < 0 || map->n_vertices < 0 ||
+        retired_out->n_planes < 0 || retired_out->n_rings < 0 || retired_out->n_vertices < 0 ||
+        (map->n_planes > 0 && (!map->planes || !map->tracks || !map->rings || !map->vertices)))
+        return CAPE_ERR_INVALID_ARGUMENT;
+    namespace mt = rgbd_slam::map_tracking;
+    const int32_t n_planes = map->n_planes;
+    try
+    {
+        std::vector<uint8_t> promotable((size_t)n_planes, 0);
+        for (int32_t j = 0; j < n_planes; ++j)
+        {
+            const cape_map_track& T = map->tracks[j];
+            if (cape::maintain_promote_candidate(T.flags, T.successive_matched))
+                promotable[j] = mt::is_covariance_valid(T.covariance, 4) &&
+                                std::abs(mt::norm3(map->planes[j].normal) - 1.0) <= std::numeric_limits<double>::epsilon();
+        }
+        std::vector<cape::MaintainPlanRow> plan((size_t)n_planes);
+        const uint64_t unbounded = ~(uint64_t)0; // (the twin writes the caller's arrays: put_map checks them)
+        const cape::MaintainLog log {cape::MaintainCursor {retired_out->n_planes, retired_out->n_rings, retired_out->n_vertices}, unbounded, unbounded,
+                                     unbounded};
+        const cape_map_maintain_result result = cape::maintain_plan_serial(map->planes, n_planes, map->rings, map->n_rings, map->n_vertices, map->tracks,
+                                                                           promotable.data(), unbounded, unbounded, unbounded, log, plan.data());
+        *result_out = result;
+        if (!(result.flags & CAPE_MAINTAIN_DONE))
+            return 0; // NOTHING or refused: map_out and retired_out stay as they were
+        std::vector<MapEntry> out((size_t)result.n_planes), lost;
+        for (int32_t j = 0; j < n_planes; ++j)
+        {
+            const cape::MaintainPlanRow& row = plan[j];
+            if (row.dest == cape::kMaintainToNone)
+                continue;
+            MapEntry e {};
+            e.plane = map->planes[j];
+            e.track = map->tracks[j];
+            if (!map_polygon(*map, e.plane, &e.polygon))
+                return CAPE_ERR_INVALID_ARGUMENT;
+            if (row.edit == cape::kMaintainEditPromote)
+            {
+                e.track.flags &= ~(uint32_t)CAPE_MAP_TRACK_STAGED;
+                e.track.failed_tracking = 0;
+            }
+            if (row.dest == cape::kMaintainToLog)
+                lost.push_back(std::move(e)); // (in list order: the log's planes count up with j)
+            else
+                out[row.plane] = std::move(e);
+        }
+        if (result.n_planes > map_out->planes_capacity || result.n_rings > map_out->rings_capacity || result.n_vertices > map_out->vertices_capacity ||
+            result.n_retired > retired_out->planes_capacity || result.n_retired_rings > retired_out->rings_capacity ||
+            result.n_retired_vertices > retired_out->vertices_capacity)
+            return CAPE_ERR_CAPACITY;
+        if (!put_map(out, *map_out) || (!lost.empty() && !put_map(lost, *retired_out, true)))
+            return CAPE_ERR_CAPACITY;
         return 0;
     }
     catch (const std::exception&)

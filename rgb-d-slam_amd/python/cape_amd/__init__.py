@@ -260,6 +260,15 @@ MAP_COMMIT_RESULT_DTYPE = np.dtype([
     ("n_appended", "<i4"), ("n_host_pairs", "<i4"), ("n_fail_polygon", "<i4"), ("next_id", "<u8")], align=True)
 assert MAP_COMMIT_RESULT_DTYPE.itemsize == 48
 
+# cape_map_maintain: PROMOTE, DROP and LOST executed on the device map, with the retired log (cape_map_maintain_result)
+(MAINTAIN_DONE, MAINTAIN_NOTHING, MAINTAIN_CAPACITY, MAINTAIN_LOG_FULL) = (1 << k for k in range(4))
+MAP_RETIRED_MAX_PLANES = 4096
+MAP_MAINTAIN_RESULT_DTYPE = np.dtype([
+    ("flags", "<u4"), ("n_planes", "<i4"), ("n_rings", "<i4"), ("n_local", "<i4"), ("n_vertices", "<i8"), ("n_staged", "<i4"),
+    ("n_promoted", "<i4"), ("n_promote_refused", "<i4"), ("n_dropped", "<i4"), ("n_lost", "<i4"), ("n_retired", "<i4"),
+    ("n_retired_rings", "<i4"), ("pad", "<u4"), ("n_retired_vertices", "<i8")], align=True)
+assert MAP_MAINTAIN_RESULT_DTYPE.itemsize == 64
+
 
 class cape_host_map(C.Structure):
     """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
@@ -303,6 +312,7 @@ def _host_library():
                                               C.c_void_p]
         L.cape_host_map_union_cut.argtypes = L.cape_host_map_union_holes.argtypes
         L.cape_host_map_commit.argtypes = [Map, C.c_int32] + [C.c_void_p] * 8 + [C.c_uint32, C.POINTER(C.c_uint64), Map, C.c_void_p]
+        L.cape_host_map_maintain.argtypes = [Map, Map, Map, C.c_void_p]
         L.cape_host_polygon_union_cut.argtypes = L.cape_host_polygon_union.argtypes
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
@@ -580,6 +590,50 @@ def host_map_commit(map_arrays, tracks, frame_header, track_results, fusion_rows
             out["tracks"][:v.n_planes].copy(), result[0], nid.value)
 
 
+def host_map_maintain(map_arrays, tracks, retired=None, retired_held=None):
+    """cape_host_map_maintain of libcape_primitives.so: the twin of Extractor.map_maintain -- PROMOTE, DROP and LOST executed on the
+    map from the tracks' counters and flags, byte for byte what the device writes.
+
+    map_arrays: pack_map(...); tracks: MAP_TRACK_DTYPE array parallel to the planes; retired: the retired log so far as
+    ((planes, rings, vertices), tracks) in a map's layout (Extractor.download_retired / this call's third result), None: empty;
+    retired_held: (n_planes, n_rings, n_vertices) the log is to be taken to hold instead of len(retired's arrays) -- entries beyond
+    `retired` are zero.
+    Returns ((planes, rings, vertices), tracks, retired, result: MAP_MAINTAIN_RESULT_DTYPE scalar): the new map in pack_map's layout
+    and the log with the lost planes appended -- or, unless result["flags"] is MAINTAIN_DONE, (None, None, the log as it was, result)."""
+    L = _host_library()
+    src, src_view = _map_arrays(map_arrays, np.ascontiguousarray(tracks, MAP_TRACK_DTYPE))
+    n_map = len(src["planes"])
+    if len(src["tracks"]) != n_map:
+        raise CapeError("host_map_maintain: one track per map plane")
+    if retired is None:
+        retired = ((np.zeros(0, MAP_PLANE_DTYPE), np.zeros(0, MAP_RING_DTYPE), np.zeros((0, 2))), np.zeros(0, MAP_TRACK_DTYPE))
+    (LP, LR, LV), LT = retired
+    LV = np.ascontiguousarray(LV, np.float64).reshape(-1, 2)
+    held = (len(LP), len(LR), len(LV)) if retired_held is None else tuple(int(x) for x in retired_held)
+    if len(LT) != len(LP) or any(h < k for h, k in zip(held, (len(LP), len(LR), len(LV)))):
+        raise CapeError("host_map_maintain: one track per retired plane, and retired_held no smaller than the log given")
+    caps = (held[0] + n_map, held[1] + len(src["rings"]), held[2] + len(src["vertices"]))
+    log = dict(planes=np.zeros(max(caps[0], 1), MAP_PLANE_DTYPE), rings=np.zeros(max(caps[1], 1), MAP_RING_DTYPE),
+               vertices=np.zeros((max(caps[2], 1), 2)), tracks=np.zeros(max(caps[0], 1), MAP_TRACK_DTYPE))
+    for name, a in (("planes", LP), ("rings", LR), ("vertices", LV), ("tracks", LT)):
+        log[name][:len(a)] = a
+    log_view = _view(cape_host_map, log, n_planes=held[0], n_rings=held[1], n_vertices=held[2], planes_capacity=len(log["planes"]),
+                     rings_capacity=len(log["rings"]), vertices_capacity=len(log["vertices"]))
+    out = dict(planes=np.zeros(max(n_map, 1), MAP_PLANE_DTYPE), rings=np.zeros(max(len(src["rings"]), 1), MAP_RING_DTYPE),
+               vertices=np.zeros((max(len(src["vertices"]), 1), 2)), tracks=np.zeros(max(n_map, 1), MAP_TRACK_DTYPE))
+    v = _view(cape_host_map, out, planes_capacity=len(out["planes"]), rings_capacity=len(out["rings"]), vertices_capacity=len(out["vertices"]))
+    result = np.zeros(1, MAP_MAINTAIN_RESULT_DTYPE)
+    rc = L.cape_host_map_maintain(C.byref(src_view), C.byref(v), C.byref(log_view), result.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_map_maintain failed ({rc})")
+    new_log = ((log["planes"][:log_view.n_planes].copy(), log["rings"][:log_view.n_rings].copy(), log["vertices"][:log_view.n_vertices].copy()),
+               log["tracks"][:log_view.n_planes].copy())
+    if result[0]["flags"] != MAINTAIN_DONE:
+        return None, None, new_log, result[0]
+    return ((out["planes"][:v.n_planes].copy(), out["rings"][:v.n_rings].copy(), out["vertices"][:v.n_vertices].copy()),
+            out["tracks"][:v.n_planes].copy(), new_log, result[0])
+
+
 def _polygon_union_args(rings_a, ring_b, frames):
     rings = [np.ascontiguousarray(r, np.float64).reshape(-1, 2) for r in rings_a]
     a = np.ascontiguousarray(np.concatenate(rings))
@@ -782,6 +836,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_union_holes", "cape_copy_map_union_rings", "cape_device_map_union_rings", "cape_debug_polygon_union",
     "cape_map_union_cut", "cape_debug_polygon_union_cut",
     "cape_map_commit", "cape_map_info", "cape_map_download",
+    "cape_map_maintain", "cape_map_retired_info", "cape_map_retired_download", "cape_map_retired_clear",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -890,6 +945,10 @@ def load_library():
     L.cape_map_commit.argtypes = [vp, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64), vp, vp]
     L.cape_map_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.cape_map_download.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]
+    L.cape_map_maintain.argtypes = [vp, C.c_uint32, vp, vp]
+    L.cape_map_retired_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.cape_map_retired_download.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]
+    L.cape_map_retired_clear.argtypes = [vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1402,6 +1461,37 @@ class Extractor:
         _check(self.L, self.L.cape_map_download(self.h, P.ctypes.data_as(C.c_void_p), n, R.ctypes.data_as(C.c_void_p), r,
                                                 V.ctypes.data_as(C.c_void_p), v, T.ctypes.data_as(C.c_void_p)), "cape_map_download")
         return (P, R, V), T
+
+    # ---- the list maintenance of the map update, and the retired log ----
+    def map_maintain(self, flags=0, stream=0):
+        """cape_map_maintain: PROMOTE, DROP and LOST executed on the device map and tracks as they stand (after a DONE map_commit, or
+        upload_map + upload_tracks); the lost planes go to the retired log.  Returns the MAP_MAINTAIN_RESULT_DTYPE scalar; its flags
+        are MAINTAIN_DONE, MAINTAIN_NOTHING (nothing was due, nothing changed) or a refusal (MAINTAIN_CAPACITY, MAINTAIN_LOG_FULL:
+        nothing changed)."""
+        result = np.zeros(1, MAP_MAINTAIN_RESULT_DTYPE)
+        _check(self.L, self.L.cape_map_maintain(self.h, flags, result.ctypes.data_as(C.c_void_p), C.c_void_p(stream)), "cape_map_maintain")
+        if result[0]["flags"] & MAINTAIN_DONE:
+            self.map_size = int(result[0]["n_planes"])
+        return result[0]
+
+    def retired_info(self):
+        """cape_map_retired_info: (n_planes, n_rings, n_vertices) of the retired log"""
+        n, r, v = C.c_int32(), C.c_int32(), C.c_int64()
+        _check(self.L, self.L.cape_map_retired_info(self.h, C.byref(n), C.byref(r), C.byref(v)), "cape_map_retired_info")
+        return n.value, r.value, v.value
+
+    def download_retired(self):
+        """cape_map_retired_download: ((planes, rings, vertices), tracks) of the retired log -- the lost planes in the order they were
+        lost, in pack_map's layout, ring_first and vertex_offset relative to the log's own arrays"""
+        n, r, v = self.retired_info()
+        P, R, V, T = np.zeros(n, MAP_PLANE_DTYPE), np.zeros(r, MAP_RING_DTYPE), np.zeros((v, 2)), np.zeros(n, MAP_TRACK_DTYPE)
+        _check(self.L, self.L.cape_map_retired_download(self.h, P.ctypes.data_as(C.c_void_p), n, R.ctypes.data_as(C.c_void_p), r,
+                                                        V.ctypes.data_as(C.c_void_p), v, T.ctypes.data_as(C.c_void_p)), "cape_map_retired_download")
+        return (P, R, V), T
+
+    def clear_retired(self):
+        """cape_map_retired_clear: the retired log is empty afterwards"""
+        _check(self.L, self.L.cape_map_retired_clear(self.h), "cape_map_retired_clear")
 
     def debug_polygon_union(self, rings_a, ring_b, frames=None):
         """cape_debug_polygon_union: map_union_holes' per-pair device function on one pair -- rings_a = [outer, hole, ...] of the map
