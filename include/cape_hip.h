@@ -1162,6 +1162,37 @@ int cape_map_retired_download(cape_handle h, cape_map_plane* planes, int32_t pla
                               double* vertices, int64_t vertices_capacity, cape_map_track* tracks /* planes_capacity, may be NULL */);
 int cape_map_retired_clear(cape_handle h);
 
+/* ONE FRAME THROUGH THE DEVICE MAP: the sequential step of a tracker, frame `frame` of the current batch against the map the frame
+ * before left.  The call enqueues on `stream`, for that frame alone: the wide match against the device map (cape_match_map_wide's
+ * kernels on one frame; world_to_camera: 16 doubles, this frame's; skip: (n_map + 31) / 32 words of this frame, may be NULL), the
+ * Kalman step, the union in cut mode, the commit and -- decided on the device from the commit's header, only if it says
+ * CAPE_COMMIT_DONE -- the maintenance of the committed map.  It waits ONCE, for both headers.  Afterwards the device map, tracks,
+ * ids, retired log and *next_id hold, byte for byte, what cape_match_map_wide(n), cape_map_kalman(n), cape_map_union_cut(n),
+ * cape_map_commit(frame, commit_flags) and, behind a DONE commit, cape_map_maintain(0) leave on the same map, tracks and log, for
+ * any n > frame; out->commit and out->maintain are what those two calls report (maintain all zero, flags 0, where the commit is
+ * not DONE: the maintenance has not run).
+ *   commit refused:                   nothing changes, *next_id included;
+ *   DONE, maintenance NOTHING:        the committed map;
+ *   DONE, maintenance DONE:           the maintained map, and the log;
+ *   DONE, maintenance refused:        the committed map, the log unchanged.
+ * It needs a map with current tracks (cape_map_upload + cape_map_upload_tracks, or a DONE commit, maintenance or step: the next
+ * step needs no upload) and the cape_build_polygons and cape_map_measure of the batch covering `frame`.  match_flags:
+ * CAPE_MATCH_ADVANCED and CAPE_MATCH_ALLOW_INDEX0 (CAPE_MATCH_MAP_AREAS and CAPE_MATCH_MAP_DEVICE_SKIP are refused: the
+ * visibility words do not survive a commit); commit_flags: cape_map_commit's.  The step works in the buffers of
+ * cape_match_map_wide, cape_map_kalman and cape_map_union*: whatever its outcome their batch-wide results are NOT current
+ * afterwards (their cape_copy_* / cape_device_* readers refuse as after a DONE commit); cape_map_measure's rows stay valid; the
+ * visibility words are invalidated when the commit is DONE.  cape_map_info, cape_map_download and cape_map_retired_* read what the
+ * step left.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, out, next_id or pose, a negative frame, an unknown or refused flag, no map;
+ * CAPE_ERR_CAPACITY: no tracks are current for the map, no cape_map_measure covers the frame, the frame lies beyond the polygons. */
+typedef struct cape_map_step_result
+{
+    cape_map_commit_result commit;     /* as cape_map_commit would report for this frame */
+    cape_map_maintain_result maintain; /* as cape_map_maintain behind a DONE commit; all zero (flags 0) where the commit is not DONE */
+} cape_map_step_result;
+int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera /* 16, this frame's */,
+                  const uint32_t* skip /* (n_map+31)/32 words of this frame, may be NULL */, uint32_t match_flags, uint32_t commit_flags,
+                  uint64_t* next_id, cape_map_step_result* out, void* stream);
+
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
  * the `stream` argument of the calls below; destroy it before the handle. */

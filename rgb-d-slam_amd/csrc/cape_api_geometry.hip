@@ -219,6 +219,139 @@ bool union_results_live(const cape_handle_s* h)
     return U.unionFrames > 0 && kalman_results_live(h) && h->kalman.kalmanFrames >= U.unionFrames && U.kalmanRun == h->kalman.runs;
 }
 
+// The kernel parameters of the map update's calls, bound to the handle's buffers: cape_map_kalman, cape_map_union* and cape_map_commit
+// run them on the first n frames of the batch-wide tables, cape_map_step on the one frame whose rows it has put at row 0 of them.
+cape::MapKalmanParams bind_map_kalman(const cape_handle_s* h)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
+    const auto& K = h->kalman;
+    const auto& W = h->mapWide;
+    cape::MapKalmanParams p{};
+    p.mapPlanes = h->map.planes;
+    p.tracks = K.tracks;
+    p.nMap = h->map.n;
+    p.matchFrames = W.frames;
+    p.match = W.match;
+    p.mapOf = W.planes + (size_t)h->cfg.max_batch * WP;
+    p.kept = W.kept;
+    p.measurements = h->measure.rows;
+    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows cape_map_measure allocated: a row of CAPE_MAX_PLANES per record)
+    p.frames = K.frames;
+    p.rows = K.rows;
+    p.trackResults = K.trackResults;
+    return p;
+}
+cape::MapUnionParams bind_map_union(const cape_handle_s* h)
+{
+    const auto& W = h->mapWide;
+    const auto& M = h->measure;
+    cape::MapUnionParams p{};
+    p.mapPlanes = h->map.planes;
+    p.mapRings = h->map.rings;
+    p.mapVertices = reinterpret_cast<const double2*>(h->map.vertices.get());
+    p.nMap = h->map.n;
+    p.nMapRings = (unsigned)h->map.rings.size();
+    p.nMapVertices = (unsigned long long)(h->map.vertices.size() / 2);
+    p.matchFrames = W.frames;
+    p.match = W.match;
+    p.kept = W.kept;
+    p.measurements = M.rows;
+    p.worldVertices = reinterpret_cast<const double2*>(M.vertices.get());
+    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows and slabs cape_map_measure allocated: one per record)
+    p.boundaryCapacity = h->boundaryCap;
+    p.fusion = h->kalman.rows;
+    p.rows = h->mapUnion.rows;
+    p.vertices = reinterpret_cast<double2*>(h->mapUnion.vertices.get());
+    return p;
+}
+// what a commit's destination set takes, to bounds the host knows: at most 128 appended planes of one ring each, a frame's slab of
+// served rings, the world rings of the frame's chain
+struct CommitBounds
+{
+    size_t planes, rings, vertices;
+};
+CommitBounds commit_bounds(const cape_handle_s* h)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
+    const size_t n = (size_t)h->map.n, cap = (size_t)h->boundaryCap;
+    CommitBounds b;
+    b.planes = std::min<size_t>(CAPE_MAP_MAX_PLANES, n + WP);
+    b.rings = b.planes * (1 + CAPE_MAP_MAX_HOLES);
+    b.vertices = (size_t)h->mapCommit.nVertices + SLAB + std::min<size_t>(WP * CAPE_MAP_MAX_RING, (size_t)(1 + h->chain.spillRecords) * cap);
+    return b;
+}
+// workgroups of the commit's copy kernel: the planes of the new map at most
+int commit_planes_bound(const cape_handle_s* h, const CommitBounds& b, uint32_t flags)
+{
+    return (int)std::min<size_t>(b.planes, (size_t)h->map.n + ((flags & CAPE_COMMIT_ADD_STAGED) ? (size_t)CAPE_MATCH_MAP_WIDE_MAX_PLANES : 0));
+}
+// frame `frame` of the batch, whose rows are row `row` of the per-frame tables; withRings: the union's rings table belongs to its rows
+cape::MapCommitParams bind_map_commit(const cape_handle_s* h, size_t row, int32_t frame, bool withRings, uint32_t flags, uint64_t nextId,
+                                      const CommitBounds& b, cape_map_commit_result* header)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
+    const auto& map = h->map;
+    const auto& K = h->kalman;
+    const auto& U = h->mapUnion;
+    const auto& X = h->mapCommit;
+    cape::MapCommitParams p{};
+    p.mapPlanes = map.planes;
+    p.mapRings = map.rings;
+    p.mapVertices = map.vertices;
+    p.tracks = K.tracks;
+    p.tags = X.tags;
+    p.nMap = map.n;
+    p.nMapRings = X.nRings;
+    p.nMapVertices = X.nVertices;
+    p.frame = frame;
+    p.kalmanFrame = K.frames + row;
+    p.trackResults = K.trackResults + row * (size_t)map.n;
+    p.fusion = K.rows + row * WP;
+    p.kept = h->mapWide.kept + row * WP;
+    p.measurements = h->measure.rows;
+    p.worldVertices = h->measure.vertices;
+    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows and slabs cape_map_measure allocated: one per record)
+    p.boundaryCapacity = h->boundaryCap;
+    p.unionRows = U.rows + row * WP;
+    p.ringRows = withRings ? h->mapUnionRings.rows + row * WP : nullptr;
+    p.slab = U.vertices + row * SLAB * 2;
+    p.flags = flags;
+    p.nextId = nextId;
+    p.outPlanes = X.planes;
+    p.outRings = X.rings;
+    p.outVertices = X.vertices;
+    p.outTracks = X.tracks;
+    p.outTags = X.tagsBack;
+    p.planesCapacity = b.planes;
+    p.ringsCapacity = b.rings;
+    p.verticesCapacity = b.vertices;
+    p.plan = X.plan;
+    p.header = header;
+    return p;
+}
+// the retired log's arrays take what `log` says, their contents kept (behind drain_handle: a call in flight may read them)
+int grow_retired_log(cape_handle_s* h, const cape::MaintainLog& log)
+{
+    auto& R = h->mapMaintain;
+    const auto drain = [h] { return drain_handle(h); };
+    CAPE_HIP_TRY(R.planes.grow_keeping((size_t)log.planesCapacity, (size_t)R.nPlanes, drain));
+    CAPE_HIP_TRY(R.tracks.grow_keeping((size_t)log.planesCapacity, (size_t)R.nPlanes, drain));
+    CAPE_HIP_TRY(R.rings.grow_keeping((size_t)log.ringsCapacity, (size_t)R.nRings, drain));
+    CAPE_HIP_TRY(R.vertices.grow_keeping((size_t)log.verticesCapacity * 2, (size_t)R.nVertices * 2, drain));
+    return CAPE_OK;
+}
+// the map, its tracks and their ids change places with another buffer set (the commit's back set, or the step's third one)
+void swap_map_set(cape_handle_s* h, cape_handle_s::Buffer<cape_map_plane>& planes, cape_handle_s::Buffer<cape_map_ring>& rings,
+                  cape_handle_s::Buffer<double>& vertices, cape_handle_s::Buffer<cape::MapTrackState>& tracks,
+                  cape_handle_s::Buffer<cape::MapTrackTag>& tags)
+{
+    h->map.planes.swap(planes);
+    h->map.rings.swap(rings);
+    h->map.vertices.swap(vertices);
+    h->kalman.tracks.swap(tracks);
+    h->mapCommit.tags.swap(tags);
+}
+
 } // namespace
 
 extern "C" {
@@ -1209,20 +1342,7 @@ int cape_map_kalman(cape_handle h, int32_t n_frames, void* stream_)
     StreamScope streamScope(h, stream);
     if (streamScope.rc() != CAPE_OK)
         return streamScope.rc();
-    cape::MapKalmanParams p{};
-    p.mapPlanes = h->map.planes;
-    p.tracks = K.tracks;
-    p.nMap = nMap;
-    p.matchFrames = W.frames;
-    p.match = W.match;
-    p.mapOf = W.planes + (size_t)h->cfg.max_batch * WP;
-    p.kept = W.kept;
-    p.measurements = M.rows;
-    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows cape_map_measure allocated: a row of CAPE_MAX_PLANES per record)
-    p.frames = K.frames;
-    p.rows = K.rows;
-    p.trackResults = K.trackResults;
-    CAPE_HIP_TRY(cape::launch_map_kalman(p, n_frames, stream));
+    CAPE_HIP_TRY(cape::launch_map_kalman(bind_map_kalman(h), n_frames, stream));
     K.kalmanFrames = n_frames;
     K.kalmanN = nMap;
     ++K.runs; // (cape_map_union's results belong to the rows this call replaced)
@@ -1274,8 +1394,6 @@ static int map_union(cape_handle h, int32_t n_frames, void* stream_, MapUnionMod
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative frame count");
     auto& U = h->mapUnion;
     const auto& K = h->kalman;
-    const auto& W = h->mapWide;
-    const auto& M = h->measure;
     U.unionFrames = 0;
     h->mapUnionRings.current = false;
     if (!kalman_results_live(h) || n_frames > K.kalmanFrames || K.kalmanN != h->map.n)
@@ -1293,23 +1411,7 @@ static int map_union(cape_handle h, int32_t n_frames, void* stream_, MapUnionMod
     StreamScope streamScope(h, stream);
     if (streamScope.rc() != CAPE_OK)
         return streamScope.rc();
-    cape::MapUnionParams p{};
-    p.mapPlanes = h->map.planes;
-    p.mapRings = h->map.rings;
-    p.mapVertices = reinterpret_cast<const double2*>(h->map.vertices.get());
-    p.nMap = h->map.n;
-    p.nMapRings = (unsigned)h->map.rings.size();
-    p.nMapVertices = (unsigned long long)(h->map.vertices.size() / 2);
-    p.matchFrames = W.frames;
-    p.match = W.match;
-    p.kept = W.kept;
-    p.measurements = M.rows;
-    p.worldVertices = reinterpret_cast<const double2*>(M.vertices.get());
-    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows and slabs cape_map_measure allocated: one per record)
-    p.boundaryCapacity = h->boundaryCap;
-    p.fusion = K.rows;
-    p.rows = U.rows;
-    p.vertices = reinterpret_cast<double2*>(U.vertices.get());
+    const cape::MapUnionParams p = bind_map_union(h);
     CAPE_HIP_TRY(mode == kUnionWithCuts    ? cape::launch_map_union_cut(p, h->mapUnionRings.rows, n_frames, stream)
                  : mode == kUnionWithHoles ? cape::launch_map_union_holes(p, h->mapUnionRings.rows, n_frames, stream)
                                            : cape::launch_map_union(p, n_frames, stream));
@@ -1384,30 +1486,24 @@ int cape_copy_map_union(cape_handle h, int32_t n_frames, cape_plane_union* rows,
 // the new map's sizes: front and back buffers are swapped here, on the host, only if the header says DONE.
 int cape_map_commit(cape_handle h, int32_t frame, uint32_t flags, uint64_t* next_id, cape_map_commit_result* out, void* stream_)
 {
-    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
     if (!h || !out || !next_id || frame < 0 || (flags & ~(uint32_t)CAPE_COMMIT_ADD_STAGED))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, result or next_id, a negative frame or an unknown flag");
     auto& map = h->map;
     auto& K = h->kalman;
     auto& U = h->mapUnion;
     auto& X = h->mapCommit;
-    const auto& W = h->mapWide;
-    const auto& M = h->measure;
     if (!union_results_live(h) || frame >= U.unionFrames || K.kalmanN != map.n || K.tracksN != map.n)
         return fail(CAPE_ERR_CAPACITY, "no cape_map_union, cape_map_union_holes or cape_map_union_cut on the current batch, map, match, measurements and Kalman results covers `frame`");
     CAPE_ON_DEVICE(h);
     CAPE_SETTLE_RESULTS(h);
-    // the back buffers, to bounds the host knows: at most 128 appended planes of one ring each, a frame's slab of served rings, the
-    // world rings of the frame's chain
-    const size_t n = (size_t)map.n, cap = (size_t)h->boundaryCap;
-    const size_t planesCap = std::min<size_t>(CAPE_MAP_MAX_PLANES, n + WP), ringsCap = planesCap * (1 + CAPE_MAP_MAX_HOLES);
-    const size_t verticesCap = (size_t)X.nVertices + SLAB + std::min<size_t>(WP * CAPE_MAP_MAX_RING, (size_t)(1 + h->chain.spillRecords) * cap);
+    // the back buffers, to bounds the host knows
+    const CommitBounds bounds = commit_bounds(h);
     const auto drain = [h] { return drain_handle(h); }; // (a back buffer was the front one of an earlier map: a call in flight may read it)
-    CAPE_HIP_TRY(X.planes.grow(planesCap, drain));
-    CAPE_HIP_TRY(X.rings.grow(ringsCap, drain));
-    CAPE_HIP_TRY(X.vertices.grow(verticesCap * 2, drain));
-    CAPE_HIP_TRY(X.tracks.grow(planesCap, drain));
-    CAPE_HIP_TRY(X.tagsBack.grow(planesCap, drain));
+    CAPE_HIP_TRY(X.planes.grow(bounds.planes, drain));
+    CAPE_HIP_TRY(X.rings.grow(bounds.rings, drain));
+    CAPE_HIP_TRY(X.vertices.grow(bounds.vertices * 2, drain));
+    CAPE_HIP_TRY(X.tracks.grow(bounds.planes, drain));
+    CAPE_HIP_TRY(X.tagsBack.grow(bounds.planes, drain));
     CAPE_HIP_TRY(X.plan.ensure(CAPE_MAP_MAX_PLANES));
     CAPE_HIP_TRY(X.header.ensure(1));
     if (!X.headerHost)
@@ -1418,51 +1514,15 @@ int cape_map_commit(cape_handle h, int32_t frame, uint32_t flags, uint64_t* next
         StreamScope streamScope(h, stream);
         if (streamScope.rc() != CAPE_OK)
             return streamScope.rc();
-        cape::MapCommitParams p{};
-        p.mapPlanes = map.planes;
-        p.mapRings = map.rings;
-        p.mapVertices = map.vertices;
-        p.tracks = K.tracks;
-        p.tags = X.tags;
-        p.nMap = map.n;
-        p.nMapRings = X.nRings;
-        p.nMapVertices = X.nVertices;
-        p.frame = frame;
-        p.kalmanFrame = K.frames + frame;
-        p.trackResults = K.trackResults + (size_t)frame * n;
-        p.fusion = K.rows + (size_t)frame * WP;
-        p.kept = W.kept + (size_t)frame * WP;
-        p.measurements = M.rows;
-        p.worldVertices = M.vertices;
-        p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the rows and slabs cape_map_measure allocated: one per record)
-        p.boundaryCapacity = h->boundaryCap;
-        p.unionRows = U.rows + (size_t)frame * WP;
-        p.ringRows = h->mapUnionRings.current ? h->mapUnionRings.rows + (size_t)frame * WP : nullptr;
-        p.slab = U.vertices + (size_t)frame * SLAB * 2;
-        p.flags = flags;
-        p.nextId = *next_id;
-        p.outPlanes = X.planes;
-        p.outRings = X.rings;
-        p.outVertices = X.vertices;
-        p.outTracks = X.tracks;
-        p.outTags = X.tagsBack;
-        p.planesCapacity = planesCap;
-        p.ringsCapacity = ringsCap;
-        p.verticesCapacity = verticesCap;
-        p.plan = X.plan;
-        p.header = X.header;
-        CAPE_HIP_TRY(cape::launch_map_commit(p, (int)std::min<size_t>(planesCap, n + ((flags & CAPE_COMMIT_ADD_STAGED) ? WP : 0)), stream));
+        const cape::MapCommitParams p = bind_map_commit(h, (size_t)frame, frame, h->mapUnionRings.current, flags, *next_id, bounds, X.header);
+        CAPE_HIP_TRY(cape::launch_map_commit(p, commit_planes_bound(h, bounds, flags), stream));
         CAPE_HIP_TRY(hipMemcpyAsync(X.headerHost, X.header, sizeof(cape_map_commit_result), hipMemcpyDeviceToHost, stream));
         CAPE_HIP_TRY(hipStreamSynchronize(stream)); // the one wait of the call: the header, and with it both kernels
         result = *X.headerHost.get();
     }
     if (result.flags & CAPE_COMMIT_DONE)
     {
-        map.planes.swap(X.planes);
-        map.rings.swap(X.rings);
-        map.vertices.swap(X.vertices);
-        K.tracks.swap(X.tracks);
-        X.tags.swap(X.tagsBack);
+        swap_map_set(h, X.planes, X.rings, X.vertices, X.tracks, X.tagsBack);
         map.n = result.n_planes;
         X.nRings = result.n_rings;
         X.nVertices = result.n_vertices;
@@ -1561,12 +1621,9 @@ int cape_map_maintain(cape_handle h, uint32_t flags, cape_map_maintain_result* o
     CAPE_HIP_TRY(X.vertices.grow(nVertices * 2, drain));
     CAPE_HIP_TRY(X.tracks.grow(n, drain));
     CAPE_HIP_TRY(X.tagsBack.grow(n, drain));
-    const size_t logPlanes = std::min<size_t>(CAPE_MAP_RETIRED_MAX_PLANES, (size_t)R.nPlanes + n), logRings = (size_t)R.nRings + nRings,
-                 logVertices = (size_t)R.nVertices + nVertices;
-    CAPE_HIP_TRY(R.planes.grow_keeping(logPlanes, (size_t)R.nPlanes, drain));
-    CAPE_HIP_TRY(R.tracks.grow_keeping(logPlanes, (size_t)R.nPlanes, drain));
-    CAPE_HIP_TRY(R.rings.grow_keeping(logRings, (size_t)R.nRings, drain));
-    CAPE_HIP_TRY(R.vertices.grow_keeping(logVertices * 2, (size_t)R.nVertices * 2, drain));
+    const cape::MaintainLog log = cape::maintain_log_bounds(cape::MaintainCursor {R.nPlanes, R.nRings, R.nVertices}, n, nRings, nVertices);
+    if (const int rc = grow_retired_log(h, log); rc != CAPE_OK)
+        return rc;
     CAPE_HIP_TRY(R.plan.ensure(CAPE_MAP_MAX_PLANES));
     CAPE_HIP_TRY(R.header.ensure(1));
     if (!R.headerHost)
@@ -1598,10 +1655,7 @@ int cape_map_maintain(cape_handle h, uint32_t flags, cape_map_maintain_result* o
         p.logRings = R.rings;
         p.logVertices = R.vertices;
         p.logTracks = R.tracks;
-        p.log.held = cape::MaintainCursor {R.nPlanes, R.nRings, R.nVertices};
-        p.log.planesCapacity = logPlanes;
-        p.log.ringsCapacity = logRings;
-        p.log.verticesCapacity = logVertices;
+        p.log = log;
         p.plan = R.plan;
         p.header = R.header;
         CAPE_HIP_TRY(cape::launch_map_maintain(p, stream));
@@ -1611,11 +1665,7 @@ int cape_map_maintain(cape_handle h, uint32_t flags, cape_map_maintain_result* o
     }
     if (result.flags & CAPE_MAINTAIN_DONE)
     {
-        map.planes.swap(X.planes);
-        map.rings.swap(X.rings);
-        map.vertices.swap(X.vertices);
-        K.tracks.swap(X.tracks);
-        X.tags.swap(X.tagsBack);
+        swap_map_set(h, X.planes, X.rings, X.vertices, X.tracks, X.tagsBack);
         map.n = result.n_planes;
         X.nRings = result.n_rings;
         X.nVertices = result.n_vertices;
@@ -1679,6 +1729,174 @@ int cape_map_retired_clear(cape_handle h)
     }
     R.nPlanes = R.nRings = 0;
     R.nVertices = 0;
+    return CAPE_OK;
+}
+
+// cape_map_step: one frame through match, Kalman step, union with cuts, commit and maintenance, the last decided on the device from
+// the commit's header.  Every buffer is grown before the first launch; one copy brings both headers back, one wait ends the call; the
+// host learns which buffer set holds the map from the same function the maintenance kernels took their source from.
+int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, const uint32_t* skip, uint32_t match_flags, uint32_t commit_flags,
+                  uint64_t* next_id, cape_map_step_result* out, void* stream_)
+{
+    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
+    constexpr uint32_t kStepMatchFlags = CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0;
+    if (!h || !out || !next_id || !world_to_camera || frame < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, result, next_id or pose, or a negative frame");
+    if (match_flags & (CAPE_MATCH_MAP_AREAS | CAPE_MATCH_MAP_DEVICE_SKIP))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "cape_map_step takes neither CAPE_MATCH_MAP_AREAS nor CAPE_MATCH_MAP_DEVICE_SKIP (the visibility words do not survive a commit)");
+    if ((match_flags & ~kStepMatchFlags) || (commit_flags & ~(uint32_t)CAPE_COMMIT_ADD_STAGED))
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match or commit flag");
+    auto& map = h->map;
+    auto& W = h->mapWide;
+    auto& K = h->kalman;
+    auto& U = h->mapUnion;
+    auto& X = h->mapCommit;
+    auto& R = h->mapMaintain;
+    auto& S = h->mapStep;
+    if (map.n < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
+    if (K.tracksN != map.n)
+        return fail(CAPE_ERR_CAPACITY, "no tracks are current for the map (cape_map_upload_tracks, or a DONE commit, maintenance or step)");
+    if (frame >= h->poly.frames)
+        return fail(CAPE_ERR_CAPACITY, "`frame` lies beyond the frames of the last cape_build_polygons (build the polygons of the batch first)");
+    if (frame >= h->measure.frames)
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_measure of the current batch covers `frame`");
+    CAPE_ON_DEVICE(h);
+    CAPE_SETTLE_RESULTS(h);
+    // the step works in row 0 of the batch-wide tables of the three calls it stands for: whatever they held is gone from here on
+    W.matchFrames = 0;
+    K.kalmanFrames = 0;
+    U.unionFrames = 0;
+    h->mapUnionRings.current = false;
+    // ---- every buffer of the five steps, before the first launch
+    const int B = h->cfg.max_batch, nMap = map.n, skipWords = (nMap + 31) / 32;
+    const size_t n = (size_t)nMap;
+    const size_t poseCapacity = (size_t)B * 16 * sizeof(double) + (size_t)B * (CAPE_MAP_MAX_PLANES / 32) * sizeof(uint32_t);
+    const size_t workCap = std::min((size_t)B * (size_t)std::max(nMap, 1) * WP, kMapWorkMax);
+    const MapWorkLayout lay = map_work_layout(B, workCap, 2);
+    const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them
+    CAPE_HIP_TRY(W.frames.ensure((size_t)B));
+    CAPE_HIP_TRY(W.match.ensure((size_t)B * CAPE_MAP_MAX_PLANES));
+    CAPE_HIP_TRY(W.planes.ensure(2 * (size_t)B * WP));
+    CAPE_HIP_TRY(W.kept.ensure((size_t)B * WP));
+    CAPE_HIP_TRY(W.poses.ensure(poseCapacity));
+    CAPE_HIP_TRY(W.work.grow(lay.total, drain));
+    CAPE_HIP_TRY(K.frames.grow(1, drain));
+    CAPE_HIP_TRY(K.rows.grow(WP, drain));
+    CAPE_HIP_TRY(K.trackResults.grow(std::max<size_t>(n, 1), drain));
+    CAPE_HIP_TRY(U.rows.grow(WP, drain));
+    CAPE_HIP_TRY(U.vertices.grow(SLAB * 2, drain));
+    CAPE_HIP_TRY(h->mapUnionRings.rows.grow(WP, drain));
+    // the commit's destination and the maintenance's, both to the commit's bounds: the committed map is the largest of the three
+    const CommitBounds bounds = commit_bounds(h);
+    CAPE_HIP_TRY(X.planes.grow(bounds.planes, drain));
+    CAPE_HIP_TRY(X.rings.grow(bounds.rings, drain));
+    CAPE_HIP_TRY(X.vertices.grow(bounds.vertices * 2, drain));
+    CAPE_HIP_TRY(X.tracks.grow(bounds.planes, drain));
+    CAPE_HIP_TRY(X.tagsBack.grow(bounds.planes, drain));
+    CAPE_HIP_TRY(X.plan.ensure(CAPE_MAP_MAX_PLANES));
+    CAPE_HIP_TRY(S.planes.grow(bounds.planes, drain));
+    CAPE_HIP_TRY(S.rings.grow(bounds.rings, drain));
+    CAPE_HIP_TRY(S.vertices.grow(bounds.vertices * 2, drain));
+    CAPE_HIP_TRY(S.tracks.grow(bounds.planes, drain));
+    CAPE_HIP_TRY(S.tags.grow(bounds.planes, drain));
+    // ... and the log, for the committed map's bounds in place of a map's sizes (the kernels derive the log's capacities from the
+    // committed sizes, which are no larger)
+    const cape::MaintainCursor held{R.nPlanes, R.nRings, R.nVertices};
+    if (const int rc = grow_retired_log(h, cape::maintain_log_bounds(held, bounds.planes, bounds.rings, bounds.vertices)); rc != CAPE_OK)
+        return rc;
+    CAPE_HIP_TRY(R.plan.ensure(CAPE_MAP_MAX_PLANES));
+    CAPE_HIP_TRY(S.header.ensure(1));
+    if (!S.headerHost)
+        CAPE_HIP_TRY(S.headerHost.alloc_host(1, hipHostMallocDefault));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    cape_map_step_result result{};
+    {
+        StreamScope streamScope(h, stream);
+        if (streamScope.rc() != CAPE_OK)
+            return streamScope.rc();
+        // ---- the wide match of frame `frame`: its pose and skip words at row 0, its chain found through the chain base
+        const size_t poseBytes = 16 * sizeof(double), skipBytes = skip ? (size_t)skipWords * sizeof(uint32_t) : 0;
+        CAPE_HIP_TRY(W.posesTwin.upload(W.poses, poseBytes + skipBytes, poseCapacity, stream,
+                                        [&](void* stage) { fill_poses(stage, 1, world_to_camera, poseBytes, skip, skipBytes); }));
+        cape::MatchMapParams pm;
+        pm.records = h->res.records;
+        pm.polygons = h->poly.polygons;
+        pm.vertices = reinterpret_cast<const double2*>(h->poly.vertices.get());
+        pm.boundaryCapacity = h->boundaryCap;
+        pm.maxBatch = B;
+        pm.nRecords = B + h->chain.spillRecords;
+        bind_map_call(pm, h, W.work, lay, workCap);
+        pm.poses = reinterpret_cast<const double*>(W.poses.get());
+        pm.skip = skipBytes ? reinterpret_cast<const uint32_t*>(W.poses + poseBytes) : nullptr;
+        pm.frames = nullptr;
+        pm.framesWide = W.frames;
+        pm.match = W.match;
+        pm.segCur = W.planes;
+        pm.mapOf = W.planes + (size_t)B * WP;
+        pm.keptIndex = W.kept;
+        pm.areas = nullptr;
+        pm.chainBase = frame;
+        set_match_thresholds(pm, match_flags);
+        CAPE_HIP_TRY(cape::launch_match_map_wide(pm, 1, stream));
+        h->lastMapMatcher = cape_handle_s::kMapMatchWide;
+        // ---- the Kalman step and the union with cuts on the same rows
+        CAPE_HIP_TRY(cape::launch_map_kalman(bind_map_kalman(h), 1, stream));
+        ++K.runs; // (cape_map_union's results belong to the rows this call replaced)
+        CAPE_HIP_TRY(cape::launch_map_union_cut(bind_map_union(h), h->mapUnionRings.rows, 1, stream));
+        // ---- the commit: front set -> back set
+        cape_map_step_result* header = S.header.get();
+        const cape::MapCommitParams pc = bind_map_commit(h, 0, frame, true, commit_flags, *next_id, bounds, &header->commit);
+        CAPE_HIP_TRY(cape::launch_map_commit(pc, commit_planes_bound(h, bounds, commit_flags), stream));
+        // ---- the maintenance behind it: back set -> third set, its sizes and whether it runs read from the commit's header
+        cape::MapStepParams ps{};
+        ps.commit = &header->commit;
+        cape::MapMaintainParams& p = ps.maintain;
+        p.mapPlanes = X.planes;
+        p.mapRings = X.rings;
+        p.mapVertices = X.vertices;
+        p.tracks = X.tracks;
+        p.tags = X.tagsBack;
+        p.outPlanes = S.planes;
+        p.outRings = S.rings;
+        p.outVertices = S.vertices;
+        p.outTracks = S.tracks;
+        p.outTags = S.tags;
+        p.logPlanes = R.planes;
+        p.logRings = R.rings;
+        p.logVertices = R.vertices;
+        p.logTracks = R.tracks;
+        p.log.held = held;
+        p.plan = R.plan;
+        p.header = &header->maintain;
+        CAPE_HIP_TRY(cape::launch_map_step_maintain(ps, commit_planes_bound(h, bounds, commit_flags), stream));
+        CAPE_HIP_TRY(hipMemcpyAsync(S.headerHost, S.header, sizeof(cape_map_step_result), hipMemcpyDeviceToHost, stream));
+        CAPE_HIP_TRY(hipStreamSynchronize(stream)); // the one wait of the call: both headers, and with them every kernel
+        result = *S.headerHost.get();
+    }
+    // ---- where the map lies now, and what it holds
+    const cape::StepMapState after = cape::step_map_after(result.commit, result.maintain);
+    if (after.set == cape::kStepSetBack)
+        swap_map_set(h, X.planes, X.rings, X.vertices, X.tracks, X.tagsBack);
+    else if (after.set == cape::kStepSetThird)
+        swap_map_set(h, S.planes, S.rings, S.vertices, S.tracks, S.tags);
+    if (after.set != cape::kStepSetFront)
+    {
+        map.n = after.planes;
+        X.nRings = after.rings;
+        X.nVertices = after.vertices;
+        K.tracksN = after.planes; // the tracks are those of the new map
+        h->visibility.frames = 0; // (the words of the old map)
+        *next_id = result.commit.next_id;
+    }
+    if (result.maintain.flags & CAPE_MAINTAIN_DONE)
+    {
+        R.nPlanes = result.maintain.n_retired;
+        R.nRings = result.maintain.n_retired_rings;
+        R.nVertices = result.maintain.n_retired_vertices;
+    }
+    K.matchedThisMap = false; // (the one-frame match is the step's own: a cape_map_kalman needs a cape_match_map_wide of its frames)
+    *out = result;
     return CAPE_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "cape_internal.h"
 #include "cape_map_commit.h"
 #include "cape_map_maintain.h"
+#include "cape_map_step.h"
 
 namespace cape {
 // every launcher returns the error of its own launch(es) (hipGetLastError right behind hipLaunchKernelGGL)
@@ -48,6 +49,7 @@ hipError_t launch_map_union_cut(const MapUnionParams& p, cape_plane_union_rings*
 hipError_t launch_polygon_union_cut(const PolygonUnionParams& p, hipStream_t stream);
 hipError_t launch_map_commit(const MapCommitParams& p, int outPlanesBound /* workgroups of the copy kernel */, hipStream_t stream);
 hipError_t launch_map_maintain(const MapMaintainParams& p, hipStream_t stream);
+hipError_t launch_map_step_maintain(const MapStepParams& s, int planesBound /* workgroups of the copy kernel */, hipStream_t stream);
 const char* rccl_load(); // nullptr on success, else the reason
 int rccl_unique_id(RcclUniqueId* id);
 int rccl_comm_init(void** comm, int world, const RcclUniqueId& id, int rank);
@@ -554,6 +556,22 @@ struct cape_handle_s
         Buffer<cape_map_maintain_result> header;     // device memory: the plan kernel's, read by the copy kernel
         Buffer<cape_map_maintain_result> headerHost; // pinned: the header comes back through it before the call returns
     } mapMaintain;
+
+    // cape_map_step: the THIRD buffer set of the map, its tracks and their ids -- what the maintenance behind the step's commit writes,
+    // since the commit's source (the front set) and destination (MapCommit's back set) are both live until the one wait of the call --
+    // and the two headers of the call side by side, so that one copy brings both back.  The sets rotate: after a step whose
+    // maintenance is DONE the third set is the front one and the old front one the third.  Grown behind drain_handle before the
+    // first launch, contents dropped.  (Declared last, like the structs above.)
+    struct MapStep
+    {
+        Buffer<cape_map_plane> planes;
+        Buffer<cape_map_ring> rings;
+        Buffer<double> vertices;
+        Buffer<cape::MapTrackState> tracks;
+        Buffer<cape::MapTrackTag> tags;
+        Buffer<cape_map_step_result> header;     // device memory: the commit's and the maintenance's plan kernels write their halves
+        Buffer<cape_map_step_result> headerHost; // pinned: both headers come back through it before the call returns
+    } mapStep;
 };
 
 namespace cape::abi {

@@ -262,6 +262,9 @@ struct MatchMapParams
     cape_frame_map_match_wide* framesWide = nullptr;
     int32_t* segCur = nullptr; // frames x 128: position of kept plane i in the frame's concatenated segment list
     int32_t* mapOf = nullptr;  // frames x 128: map plane that took kept plane i
+    // cape_map_step: the call's frames are frames chainBase .. of the batch.  Every table above is indexed by the call's own frame
+    // number; only the chain walk (whose head is the frame's record) takes the batch's.  0 for every other entry point
+    int chainBase = 0;
 };
 
 // The carried frame of a handle (cape_match_carry_save): what the wide matcher reads of one frame as a PREVIOUS frame, kept plane by

@@ -194,6 +194,19 @@ struct MaintainLog
     uint64_t planesCapacity, ringsCapacity, verticesCapacity;
 };
 
+// What the log may take in a maintenance of a map of these sizes: the whole map on top of what it holds, CAPE_MAP_RETIRED_MAX_PLANES
+// planes at the most.  The host grows the log's arrays to at least this before the launch.
+CAPE_MAINTAIN_FN MaintainLog maintain_log_bounds(const MaintainCursor& held, uint64_t planes, uint64_t rings, uint64_t vertices)
+{
+    const uint64_t all = (uint64_t)held.planes + planes;
+    MaintainLog log{};
+    log.held = held;
+    log.planesCapacity = all < (uint64_t)CAPE_MAP_RETIRED_MAX_PLANES ? all : (uint64_t)CAPE_MAP_RETIRED_MAX_PLANES;
+    log.ringsCapacity = (uint64_t)held.rings + rings;
+    log.verticesCapacity = (uint64_t)held.vertices + vertices;
+    return log;
+}
+
 // The result header.  Refused (nothing changes, log included): CAPE_MAINTAIN_CAPACITY for a plane whose rings do not lie in the
 // map's buffers or a new map beyond the buffers it is written to; CAPE_MAINTAIN_LOG_FULL where the lost planes do not fit
 // CAPE_MAP_RETIRED_MAX_PLANES, the log's arrays or a uint32 offset.  Otherwise NOTHING if no plane is promoted, dropped or lost, else

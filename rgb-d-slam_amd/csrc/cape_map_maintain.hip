@@ -13,12 +13,17 @@
 //        writes the plane record, the track, the id / result and the re-based ring records -- into the back set for a map
 //        destination, as a whole cape_map_track into the log for a log destination; all lanes copy the vertices, a 16-byte load and
 //        store per vertex.
+//   cape_map_step_plan_kernel, cape_map_step_copy_kernel : the same two behind a commit on the same stream (cape_map_step).  They read
+//        the commit's header in device memory: unless it says DONE they leave at once (the plan kernel writes the all-zero header);
+//        else the map's sizes, the capacities and the log's bounds are derived from it (step_map_after, cape_map_step.h) where
+//        cape_map_maintain's host side passes them as arguments, and the work is that of the two kernels above, one copy of it.
 #include <hip/hip_runtime.h>
 
 #include "cape_internal.h"
 #include "cape_layout.h"
 #include "cape_map_commit.h"
 #include "cape_map_maintain.h"
+#include "cape_map_step.h"
 #include "cape_map_tracking.h"
 #include "cape_wave.h"
 
@@ -53,11 +58,9 @@ __host__ __device__ constexpr MapMaintainLayout map_maintain_layout()
     return o;
 }
 
-} // namespace
-
-__global__ __launch_bounds__(kMaintainLanes) void cape_map_maintain_plan_kernel(MapMaintainParams p)
+// the plan kernel's work, for a map whose sizes the caller has put into p (cape_map_maintain: the host; cape_map_step: the kernel)
+__device__ __forceinline__ void map_maintain_plan(const MapMaintainParams& p, unsigned char* smem)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr MapMaintainLayout lay = map_maintain_layout();
     int* sums = carve_at<int>(smem, lay.sums);
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -180,7 +183,8 @@ __global__ __launch_bounds__(kMaintainLanes) void cape_map_maintain_plan_kernel(
     }
 }
 
-__global__ __launch_bounds__(kMaintainLanes) void cape_map_maintain_copy_kernel(MapMaintainParams p)
+// the copy kernel's work, likewise
+__device__ __forceinline__ void map_maintain_copy(const MapMaintainParams& p)
 {
     const cape_map_maintain_result hd = *p.header;
     const int j = (int)blockIdx.x, tid = (int)threadIdx.x;
@@ -237,6 +241,72 @@ __global__ __launch_bounds__(kMaintainLanes) void cape_map_maintain_copy_kernel(
         p.outTracks[row.plane] = T;
         p.outTags[row.plane] = G;
     }
+}
+
+// cape_map_step: whether the maintenance runs, and on which map.  The state after the commit alone (step_map_after with the maintain
+// header all zero) is the source: nothing to do unless that is the commit's BACK set, the set s.maintain's source pointers name.
+// Its counts are the map's sizes, the capacities and the log's bounds what cape_map_maintain's host side derives from those sizes.
+__device__ __forceinline__ bool map_step_source(MapMaintainParams& p, const cape_map_commit_result& commit)
+{
+    const StepMapState from = step_map_after(commit, cape_map_maintain_result{});
+    if (from.set != kStepSetBack)
+        return false;
+    p.nMap = from.planes;
+    p.nMapRings = from.rings;
+    p.nMapVertices = from.vertices;
+    p.planesCapacity = (unsigned long long)from.planes;
+    p.ringsCapacity = (unsigned long long)from.rings;
+    p.verticesCapacity = (unsigned long long)from.vertices;
+    p.log = maintain_log_bounds(p.log.held, (uint64_t)from.planes, (uint64_t)from.rings, (uint64_t)from.vertices);
+    return true;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(kMaintainLanes) void cape_map_maintain_plan_kernel(MapMaintainParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    map_maintain_plan(p, smem);
+}
+
+__global__ __launch_bounds__(kMaintainLanes) void cape_map_maintain_copy_kernel(MapMaintainParams p)
+{
+    map_maintain_copy(p);
+}
+
+// The step's plan kernel: ONE workgroup.  Behind a commit that is not DONE it writes the all-zero maintain header and leaves.
+__global__ __launch_bounds__(kMaintainLanes) void cape_map_step_plan_kernel(MapStepParams s)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    MapMaintainParams p = s.maintain;
+    if (!map_step_source(p, *s.commit)) // (uniform: one header)
+    {
+        if (threadIdx.x == 0)
+            *p.header = cape_map_maintain_result{};
+        return;
+    }
+    map_maintain_plan(p, smem);
+}
+
+// The step's copy kernel: launched to the bound the host knows of the committed map's planes; the workgroups beyond the committed
+// count leave (map_maintain_copy: j >= nMap), all of them behind a commit that is not DONE.
+__global__ __launch_bounds__(kMaintainLanes) void cape_map_step_copy_kernel(MapStepParams s)
+{
+    MapMaintainParams p = s.maintain;
+    if (!map_step_source(p, *s.commit))
+        return;
+    map_maintain_copy(p);
+}
+
+hipError_t launch_map_step_maintain(const MapStepParams& s, int planesBound, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cape_map_step_plan_kernel, dim3(1), dim3(kMaintainLanes), map_maintain_layout().bytes, stream, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    const int planes = planesBound < 1 ? 1 : (planesBound > CAPE_MAP_MAX_PLANES ? CAPE_MAP_MAX_PLANES : planesBound);
+    hipLaunchKernelGGL(cape_map_step_copy_kernel, dim3(planes), dim3(kMaintainLanes), 0, stream, s);
+    return hipGetLastError();
 }
 
 hipError_t launch_map_maintain(const MapMaintainParams& p, hipStream_t stream)

@@ -399,7 +399,8 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_wide_kernel
     const int frame = live ? frameRaw : nFrames - 1; // (idle waves of the last workgroup shadow a real frame and store nothing)
     bool hostOnly = false;
     const RecordChains chains{p.records, p.polygons, p.maxBatch, p.nRecords};
-    const int nCurAll = walk_chain(chains, frame, lane, kept, segs, hostOnly);
+    const int head = p.chainBase + frame; // the frame's own record, where its chain starts
+    const int nCurAll = walk_chain(chains, head, lane, kept, segs, hostOnly);
     CAPE_MP_SYNC(); // (the table is read by other lanes of the wave than wrote it)
     const bool fits = nCurAll <= WP && !hostOnly;
     const int nCur = nCurAll < WP ? nCurAll : WP;
@@ -412,7 +413,7 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_wide_kernel
         if (live)
         {
             const size_t at = (size_t)frame * WP + k;
-            p.keptIndex[at] = k < nCur ? kept[k] : make_uint2((unsigned)frame, 0u);
+            p.keptIndex[at] = k < nCur ? kept[k] : make_uint2((unsigned)head, 0u);
             p.segCur[at] = k < nCur ? segs[k] : -1;
             p.mapOf[at] = -1;
         }

@@ -269,6 +269,10 @@ MAP_MAINTAIN_RESULT_DTYPE = np.dtype([
     ("n_retired_rings", "<i4"), ("pad", "<u4"), ("n_retired_vertices", "<i8")], align=True)
 assert MAP_MAINTAIN_RESULT_DTYPE.itemsize == 64
 
+# cape_map_step: one frame through match, Kalman step, union with cuts, commit and maintenance (cape_map_step_result)
+MAP_STEP_RESULT_DTYPE = np.dtype([("commit", MAP_COMMIT_RESULT_DTYPE), ("maintain", MAP_MAINTAIN_RESULT_DTYPE)], align=True)
+assert MAP_STEP_RESULT_DTYPE.itemsize == 112 and MAP_STEP_RESULT_DTYPE.fields["maintain"][1] == 48
+
 
 class cape_host_map(C.Structure):
     """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
@@ -836,7 +840,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_union_holes", "cape_copy_map_union_rings", "cape_device_map_union_rings", "cape_debug_polygon_union",
     "cape_map_union_cut", "cape_debug_polygon_union_cut",
     "cape_map_commit", "cape_map_info", "cape_map_download",
-    "cape_map_maintain", "cape_map_retired_info", "cape_map_retired_download", "cape_map_retired_clear",
+    "cape_map_maintain", "cape_map_retired_info", "cape_map_retired_download", "cape_map_retired_clear", "cape_map_step",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -949,6 +953,7 @@ def load_library():
     L.cape_map_retired_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.cape_map_retired_download.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]
     L.cape_map_retired_clear.argtypes = [vp]
+    L.cape_map_step.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), vp, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1492,6 +1497,31 @@ class Extractor:
     def clear_retired(self):
         """cape_map_retired_clear: the retired log is empty afterwards"""
         _check(self.L, self.L.cape_map_retired_clear(self.h), "cape_map_retired_clear")
+
+    # ---- one frame through the device map: match, Kalman step, union with cuts, commit and maintenance in one call ----
+    def map_step(self, frame, world_to_camera, skip=None, match_flags=0, commit_flags=0, next_id=0, stream=0):
+        """cape_map_step: frame `frame` of the batch (build_polygons and map_measure must cover it) against the device map and tracks as
+        they stand -- the wide match, the Kalman step, the union in cut mode, the commit and, behind a DONE commit, the maintenance,
+        enqueued together and waited for once.  world_to_camera: this frame's 16 doubles; skip: this frame's words or None;
+        match_flags: MATCH_ADVANCED, MATCH_ALLOW_INDEX0; commit_flags: COMMIT_ADD_STAGED; next_id: the id of the first appended plane.
+        Returns (result: MAP_STEP_RESULT_DTYPE scalar, next_id): result["commit"] and result["maintain"] are what map_commit and
+        map_maintain report (maintain all zero where the commit is not DONE).  The map, tracks and retired log afterwards are those
+        of match_map_wide + map_kalman + map_union_cut + map_commit + map_maintain; the batch-wide results of the first three are
+        not current after the call."""
+        T = np.ascontiguousarray(world_to_camera, np.float64).reshape(16)
+        S = None if skip is None else np.ascontiguousarray(skip, np.uint32).reshape(-1)
+        if S is not None and S.size < (getattr(self, "map_size", 0) + 31) // 32:
+            raise CapeError("map_step: skip needs (n_map + 31) // 32 words")
+        nid = C.c_uint64(next_id)
+        result = np.zeros(1, MAP_STEP_RESULT_DTYPE)
+        _check(self.L, self.L.cape_map_step(self.h, frame, T.ctypes.data_as(C.c_void_p), None if S is None else S.ctypes.data_as(C.c_void_p),
+                                            match_flags, commit_flags, C.byref(nid), result.ctypes.data_as(C.c_void_p), C.c_void_p(stream)),
+               "cape_map_step")
+        if result[0]["maintain"]["flags"] & MAINTAIN_DONE:
+            self.map_size = int(result[0]["maintain"]["n_planes"])
+        elif result[0]["commit"]["flags"] & COMMIT_DONE:
+            self.map_size = int(result[0]["commit"]["n_planes"])
+        return result[0], nid.value
 
     def debug_polygon_union(self, rings_a, ring_b, frames=None):
         """cape_debug_polygon_union: map_union_holes' per-pair device function on one pair -- rings_a = [outer, hole, ...] of the map
