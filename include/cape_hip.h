@@ -819,7 +819,7 @@ typedef struct cape_map_track
 enum
 {
     CAPE_MAP_TRACK_STAGED = 1u << 0, /* a staged plane (StagedMapPlane): a match counts the detection as used even if the update fails */
-    CAPE_MAP_TRACK_MOVING = 1u << 1  /* is_moving(): informational here, the caller's skip bits of cape_match_map follow it */
+    CAPE_MAP_TRACK_MOVING = 1u << 1  /* is_moving(): cape_map_step_visible skips the plane; every other matcher takes the caller's skip bits */
 };
 enum
 {
@@ -1192,6 +1192,38 @@ typedef struct cape_map_step_result
 int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera /* 16, this frame's */,
                   const uint32_t* skip /* (n_map+31)/32 words of this frame, may be NULL */, uint32_t match_flags, uint32_t commit_flags,
                   uint64_t* next_id, cape_map_step_result* out, void* stream);
+
+/* THE SAME STEP WITH THE FRAME'S SKIP WORDS DECIDED ON THE DEVICE, in the same call and behind the same single wait: the first
+ * statement of the loop the step stands for, `if (mapFeature.is_moving() or not mapFeature.is_visible(worldToCamera)) continue;`.
+ * Ahead of the match the call decides, for the map as it finds it (n_map planes, BEFORE the step), bit j = the device track j has
+ * CAPE_MAP_TRACK_MOVING, or map plane j is not visible from world_to_camera -- a one-frame classify kernel that reads the moving
+ * bit from the device tracks, then cape_map_visibility's intersection kernels -- and the match reads those words on the device.
+ * Afterwards the device map, tracks, ids, retired log, *next_id and out->step are byte for byte what this route leaves on the same
+ * map, tracks and log:  moving = the tracks' CAPE_MAP_TRACK_MOVING bits;  cape_map_visibility(1, world_to_camera, moving);
+ * cape_copy_map_visibility(1, words, &und);  cape_map_step(frame, world_to_camera, words, match_flags, commit_flags, &id, &r).
+ * The words are those of that route (cape_host_map_visibility's bit for bit, the bits beyond n_map in the last word 0) and
+ * out->n_undecided == und.  An empty map runs no visibility kernel and has no words (n_map = 0); the step proceeds, so that it can
+ * append.  match_flags, commit_flags, the preconditions and the error list are cape_map_step's (CAPE_MATCH_MAP_AREAS and
+ * CAPE_MATCH_MAP_DEVICE_SKIP are refused), and so is what the call does to the results of other calls.  The words live in a buffer
+ * of the step's own: the words of cape_map_visibility are neither read nor written (cape_copy_map_visibility behaves as after a
+ * cape_map_step: it refuses once the commit is DONE).
+ * cape_map_step_skip_words: a synchronous copy of the words of the last cape_map_step_visible, (n_map + 31) / 32 of them for the
+ * map as it was BEFORE that step, whatever the step's outcome (a refused commit included); valid until the next
+ * cape_map_step_visible or cape_map_upload.  *n_map (may be NULL) is that map's plane count.  CAPE_ERR_CAPACITY: no such step since
+ * the last cape_map_upload, or words_capacity is too small (*n_map is still reported); CAPE_ERR_INVALID_ARGUMENT: NULL handle, a
+ * negative capacity, NULL words with n_map > 0. */
+typedef struct cape_map_step_visible_result
+{
+    cape_map_step_result step; /* exactly what cape_map_step reports */
+    int32_t n_map;             /* planes of the map the words were decided against (the map BEFORE the step) */
+    int32_t n_moving;          /* of them, CAPE_MAP_TRACK_MOVING in the device track */
+    int32_t n_listed;          /* not moving and not ruled out by the classify: handed to the ring intersection */
+    int32_t pad;
+    int64_t n_undecided;       /* pairs beyond the intersection capacities: they count as visible, as in cape_map_visibility */
+} cape_map_step_visible_result;
+int cape_map_step_visible(cape_handle h, int32_t frame, const double* world_to_camera /* 16, this frame's */, uint32_t match_flags,
+                          uint32_t commit_flags, uint64_t* next_id, cape_map_step_visible_result* out, void* stream);
+int cape_map_step_skip_words(cape_handle h, uint32_t* words, int32_t words_capacity, int32_t* n_map);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as

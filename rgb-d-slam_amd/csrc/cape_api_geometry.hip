@@ -141,6 +141,25 @@ VisibilityWorkLayout visibility_work_layout(size_t cap)
     return l;
 }
 constexpr size_t kVisibilityWorkBudget = (size_t)1 << 30; // bytes of the visibility work list at most
+// what the visibility kernels read of the handle, for cape_map_visibility and cape_map_step_visible: the front map, the camera, the device
+cape::MapVisibilityParams bind_map_visibility(const cape_handle_s* h)
+{
+    cape::MapVisibilityParams p{};
+    p.mapPlanes = h->map.planes;
+    p.mapRings = h->map.rings;
+    p.mapVertices = reinterpret_cast<const double2*>(h->map.vertices.get());
+    p.nMap = h->map.n;
+    p.skipWords = (h->map.n + 31) / 32;
+    p.computeUnits = h->computeUnits;
+    p.ldsLimitBytes = h->ldsLimit;
+    p.width = h->cfg.width;
+    p.height = h->cfg.height;
+    p.fx = h->cfg.fx;
+    p.fy = h->cfg.fy;
+    p.cx = h->cfg.cx;
+    p.cy = h->cfg.cy;
+    return p;
+}
 // CAPE_MATCH_MAP_DEVICE_SKIP: the skip words of the last cape_map_visibility for a match call over n frames (or slots), or the
 // reason there are none
 int device_skip_words(const cape_handle_s* h, int n, const uint32_t* skip, const uint32_t** words)
@@ -768,6 +787,7 @@ int cape_map_upload(cape_handle h, const cape_map_plane* planes, int32_t n_plane
     auto& map = h->map;
     map.n = -1; // (no map until the copies are through)
     h->visibility.frames = 0; // (the words of the old map)
+    h->mapStepVisible.n = -1;
     h->kalman.tracksN = -1;   // (its tracks, the wide match against it and what cape_map_kalman made of them)
     h->kalman.matchedThisMap = false;
     h->kalman.kalmanFrames = 0;
@@ -1131,12 +1151,7 @@ int cape_map_visibility(cape_handle h, int32_t n_frames, const double* world_to_
         return streamScope.rc();
     CAPE_HIP_TRY(V.posesTwin.upload(V.poses, poseBytes + movingBytes, V.poses.size(), stream,
                                     [&](void* stage) { fill_poses(stage, n_frames, world_to_camera, poseBytes, moving, movingBytes); }));
-    cape::MapVisibilityParams p{};
-    p.mapPlanes = h->map.planes;
-    p.mapRings = h->map.rings;
-    p.mapVertices = reinterpret_cast<const double2*>(h->map.vertices.get());
-    p.nMap = nMap;
-    p.skipWords = skipWords;
+    cape::MapVisibilityParams p = bind_map_visibility(h);
     p.poses = reinterpret_cast<const double*>(V.poses.get());
     p.moving = movingBytes ? reinterpret_cast<const uint32_t*>(V.poses + poseBytes) : nullptr;
     p.skip = V.skip;
@@ -1144,14 +1159,6 @@ int cape_map_visibility(cape_handle h, int32_t n_frames, const double* world_to_
     p.work = reinterpret_cast<unsigned long long*>(V.work + lay.work);
     p.tierLists = reinterpret_cast<unsigned*>(V.work + lay.tiers);
     p.workCapacity = cap;
-    p.computeUnits = h->computeUnits;
-    p.ldsLimitBytes = h->ldsLimit;
-    p.width = h->cfg.width;
-    p.height = h->cfg.height;
-    p.fx = h->cfg.fx;
-    p.fy = h->cfg.fy;
-    p.cx = h->cfg.cx;
-    p.cy = h->cfg.cy;
     CAPE_HIP_TRY(cape::launch_map_visibility(p, n_frames, stream));
     V.frames = n_frames;
     V.n = nMap;
@@ -1732,18 +1739,33 @@ int cape_map_retired_clear(cape_handle h)
     return CAPE_OK;
 }
 
-// cape_map_step: one frame through match, Kalman step, union with cuts, commit and maintenance, the last decided on the device from
-// the commit's header.  Every buffer is grown before the first launch; one copy brings both headers back, one wait ends the call; the
-// host learns which buffer set holds the map from the same function the maintenance kernels took their source from.
-int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, const uint32_t* skip, uint32_t match_flags, uint32_t commit_flags,
-                  uint64_t* next_id, cape_map_step_result* out, void* stream_)
+} // extern "C"
+
+namespace {
+
+// what cape_map_step_visible reports beside the step's result
+struct StepVisibleCounts
+{
+    int32_t nMap = 0, nMoving = 0, nListed = 0;
+    int64_t nUndecided = 0;
+};
+
+// cape_map_step and cape_map_step_visible: one frame through match, Kalman step, union with cuts, commit and maintenance, the last
+// decided on the device from the commit's header.  Every buffer is grown before the first launch; one copy brings both headers back,
+// one wait ends the call; the host learns which buffer set holds the map from the same function the maintenance kernels took their
+// source from.  visible == nullptr: the gate reads the caller's skip words (or none).  Else they are decided ahead of the gate, on
+// the same stream, from the pose row the gate reads and the front set's planes and tracks, into MapStepVisible::skip; their
+// counters come back in a second small copy before the one wait.
+int map_step_body(cape_handle h, int32_t frame, const double* world_to_camera, const uint32_t* skip, StepVisibleCounts* visible, uint32_t match_flags,
+                  uint32_t commit_flags, uint64_t* next_id, cape_map_step_result* out, void* stream_)
 {
     constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES, SLAB = CAPE_MAP_UNION_FRAME_VERTICES;
     constexpr uint32_t kStepMatchFlags = CAPE_MATCH_ADVANCED | CAPE_MATCH_ALLOW_INDEX0;
     if (!h || !out || !next_id || !world_to_camera || frame < 0)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, result, next_id or pose, or a negative frame");
     if (match_flags & (CAPE_MATCH_MAP_AREAS | CAPE_MATCH_MAP_DEVICE_SKIP))
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "cape_map_step takes neither CAPE_MATCH_MAP_AREAS nor CAPE_MATCH_MAP_DEVICE_SKIP (the visibility words do not survive a commit)");
+        return fail(CAPE_ERR_INVALID_ARGUMENT, visible ? "cape_map_step_visible takes neither CAPE_MATCH_MAP_AREAS nor CAPE_MATCH_MAP_DEVICE_SKIP (it decides the words itself)"
+                                                       : "cape_map_step takes neither CAPE_MATCH_MAP_AREAS nor CAPE_MATCH_MAP_DEVICE_SKIP (the visibility words do not survive a commit)");
     if ((match_flags & ~kStepMatchFlags) || (commit_flags & ~(uint32_t)CAPE_COMMIT_ADD_STAGED))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "unknown match or commit flag");
     auto& map = h->map;
@@ -1753,6 +1775,7 @@ int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, c
     auto& X = h->mapCommit;
     auto& R = h->mapMaintain;
     auto& S = h->mapStep;
+    auto& SV = h->mapStepVisible;
     if (map.n < 0)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "no map has been uploaded (cape_map_upload)");
     if (K.tracksN != map.n)
@@ -1809,8 +1832,20 @@ int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, c
     CAPE_HIP_TRY(S.header.ensure(1));
     if (!S.headerHost)
         CAPE_HIP_TRY(S.headerHost.alloc_host(1, hipHostMallocDefault));
+    // ... and what the visibility kernels take: one frame's words, work list and tier lists, the counters' pinned twin
+    const VisibilityWorkLayout visLay = visibility_work_layout(n);
+    const bool decide = visible && nMap > 0; // (an empty map has no words: no kernel runs for them)
+    if (visible)
+    {
+        SV.n = -1; // (whatever words it held: gone from here on)
+        CAPE_HIP_TRY(SV.skip.grow(CAPE_MAP_MAX_PLANES / 32, drain));
+        CAPE_HIP_TRY(SV.work.grow(visLay.total, drain));
+        if (!SV.countsHost)
+            CAPE_HIP_TRY(SV.countsHost.alloc_host(16, hipHostMallocDefault));
+    }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     cape_map_step_result result{};
+    unsigned counts[16] = {};
     {
         StreamScope streamScope(h, stream);
         if (streamScope.rc() != CAPE_OK)
@@ -1829,6 +1864,19 @@ int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, c
         bind_map_call(pm, h, W.work, lay, workCap);
         pm.poses = reinterpret_cast<const double*>(W.poses.get());
         pm.skip = skipBytes ? reinterpret_cast<const uint32_t*>(W.poses + poseBytes) : nullptr;
+        if (decide)
+        {
+            // ---- the frame's skip words, from the pose row the gate reads and the FRONT set's planes and tracks
+            cape::MapVisibilityParams pv = bind_map_visibility(h);
+            pv.poses = pm.poses;
+            pv.skip = SV.skip;
+            pv.counts = reinterpret_cast<unsigned*>(SV.work + visLay.counts);
+            pv.work = reinterpret_cast<unsigned long long*>(SV.work + visLay.work);
+            pv.tierLists = reinterpret_cast<unsigned*>(SV.work + visLay.tiers);
+            pv.workCapacity = n;
+            CAPE_HIP_TRY(cape::launch_map_step_visibility(pv, K.tracks, stream));
+            pm.skip = SV.skip;
+        }
         pm.frames = nullptr;
         pm.framesWide = W.frames;
         pm.match = W.match;
@@ -1871,8 +1919,23 @@ int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, c
         p.header = &header->maintain;
         CAPE_HIP_TRY(cape::launch_map_step_maintain(ps, commit_planes_bound(h, bounds, commit_flags), stream));
         CAPE_HIP_TRY(hipMemcpyAsync(S.headerHost, S.header, sizeof(cape_map_step_result), hipMemcpyDeviceToHost, stream));
+        if (decide)
+            CAPE_HIP_TRY(hipMemcpyAsync(SV.countsHost, SV.work + visLay.counts, sizeof(counts), hipMemcpyDeviceToHost, stream));
         CAPE_HIP_TRY(hipStreamSynchronize(stream)); // the one wait of the call: both headers, and with them every kernel
         result = *S.headerHost.get();
+        if (decide)
+            std::memcpy(counts, SV.countsHost.get(), sizeof(counts));
+    }
+    if (visible)
+    {
+        // the words stand for the map as the call found it, whatever becomes of it below
+        SV.n = nMap;
+        visible->nMap = nMap;
+        visible->nMoving = (int32_t)counts[10];
+        visible->nListed = (int32_t)counts[11];
+        unsigned long long undecided = 0;
+        std::memcpy(&undecided, counts + 8, sizeof(undecided));
+        visible->nUndecided = (int64_t)undecided;
     }
     // ---- where the map lies now, and what it holds
     const cape::StepMapState after = cape::step_map_after(result.commit, result.maintain);
@@ -1897,6 +1960,59 @@ int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, c
     }
     K.matchedThisMap = false; // (the one-frame match is the step's own: a cape_map_kalman needs a cape_match_map_wide of its frames)
     *out = result;
+    return CAPE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int cape_map_step(cape_handle h, int32_t frame, const double* world_to_camera, const uint32_t* skip, uint32_t match_flags, uint32_t commit_flags,
+                  uint64_t* next_id, cape_map_step_result* out, void* stream)
+{
+    return map_step_body(h, frame, world_to_camera, skip, nullptr, match_flags, commit_flags, next_id, out, stream);
+}
+
+// cape_map_step_visible: cape_map_step with the frame's skip words decided on the device, ahead of the gate, from the tracks' moving
+// bits and the map as the call finds it
+int cape_map_step_visible(cape_handle h, int32_t frame, const double* world_to_camera, uint32_t match_flags, uint32_t commit_flags,
+                          uint64_t* next_id, cape_map_step_visible_result* out, void* stream)
+{
+    if (!out)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle, result, next_id or pose, or a negative frame");
+    StepVisibleCounts counts;
+    cape_map_step_result step{};
+    if (const int rc = map_step_body(h, frame, world_to_camera, nullptr, &counts, match_flags, commit_flags, next_id, &step, stream); rc != CAPE_OK)
+        return rc;
+    cape_map_step_visible_result result{};
+    result.step = step;
+    result.n_map = counts.nMap;
+    result.n_moving = counts.nMoving;
+    result.n_listed = counts.nListed;
+    result.n_undecided = counts.nUndecided;
+    *out = result;
+    return CAPE_OK;
+}
+
+int cape_map_step_skip_words(cape_handle h, uint32_t* words, int32_t words_capacity, int32_t* n_map)
+{
+    if (!h || words_capacity < 0)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null handle or negative capacity");
+    const auto& SV = h->mapStepVisible;
+    if (SV.n < 0)
+        return fail(CAPE_ERR_CAPACITY, "no cape_map_step_visible has run since the last cape_map_upload");
+    if (n_map)
+        *n_map = SV.n;
+    const int nWords = (SV.n + 31) / 32;
+    if (nWords > words_capacity)
+        return fail(CAPE_ERR_CAPACITY, "words_capacity is too small for the words of the last cape_map_step_visible ((n_map + 31) / 32)");
+    if (nWords == 0)
+        return CAPE_OK;
+    if (!words)
+        return fail(CAPE_ERR_INVALID_ARGUMENT, "null words");
+    CAPE_ON_DEVICE(h);
+    CAPE_HIP_TRY(drain_handle(h));
+    CAPE_HIP_TRY(copy_out(words, SV.skip, 0, (size_t)nWords));
     return CAPE_OK;
 }
 

@@ -39,6 +39,7 @@ hipError_t launch_match_map_wide(const MatchMapParams& p, int nFrames, hipStream
 hipError_t launch_match_wide(const MatchWideParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_carry_save(const CarrySaveParams& p, hipStream_t stream);
 hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_step_visibility(const MapVisibilityParams& p, const MapTrackState* tracks, hipStream_t stream);
 hipError_t launch_map_measure(const MapMeasureParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_kalman(const MapKalmanParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t stream);
@@ -572,6 +573,17 @@ struct cape_handle_s
         Buffer<cape_map_step_result> header;     // device memory: the commit's and the maintenance's plan kernels write their halves
         Buffer<cape_map_step_result> headerHost; // pinned: both headers come back through it before the call returns
     } mapStep;
+
+    // cape_map_step_visible / cape_map_step_skip_words: the skip words the step decided for its frame against the map as it found
+    // it, the work buffers of its visibility kernels and their counters' way back.  Buffers of its own -- cape_map_visibility's words
+    // are not touched -- grown behind drain_handle before the first launch.  (Declared last, like the structs above.)
+    struct MapStepVisible
+    {
+        Buffer<uint32_t> skip;         // CAPE_MAP_MAX_PLANES / 32 words
+        Buffer<unsigned char> work;    // counters, work list, tier lists (visibility_work_layout) for one frame
+        Buffer<unsigned> countsHost;   // pinned: the 16 counters come back through it before the call returns
+        int n = -1;                    // map planes the words of the last cape_map_step_visible stand for (-1: none since cape_map_upload)
+    } mapStepVisible;
 };
 
 namespace cape::abi {

@@ -11,6 +11,9 @@
 //        visible, one whose box misses the rectangle neither (see box_misses_screen); every other plane that is not moving goes to
 //        the work list, per frame in j order.  Every bit j < n_map of the frame's words is set here; the next kernel clears the bits
 //        of the visible planes.
+//   cape_map_classify_one_kernel: the same decision for ONE frame (cape_map_step_visible), spread over the chip: a workgroup per 64
+//        map planes (two skip words), a wave per plane at a time, the lanes over the ring's vertices (cape_map_step_visible.h has the
+//        ownership rules).  The moving bit comes from the device tracks, not from host words.
 //   cape_map_visible_kernel<TIER>: persistent waves over the work list (tier 0) or a tier's list of indices into it (tiers 1..3),
 //        as cape_map_inter_kernel: the screen ring as ring A, the rectangle as ring B, each oriented like the host class orients an
 //        outer ring.  Area > 0: the bit of the pair is cleared.  A pair beyond every tier's capacities is not decided: it counts as
@@ -22,6 +25,7 @@
 
 #include "cape_internal.h"
 #include "cape_map_camera.h"
+#include "cape_map_step_visible.h"
 #include "cape_ring_area.h"
 #include "cape_wave.h"
 
@@ -87,6 +91,51 @@ __device__ inline bool may_be_visible(const double* Tm, const MapVisibilityParam
     return finite && !box_misses_screen(p, minU, maxU, minV, maxV);
 }
 
+// the minimum / maximum of the 64 lanes' doubles, uniform: comparisons only, so for finite values the order of the reduction does not
+// show (a -0 against a +0 may come out either way; box_misses_screen compares and takes magnitudes, where the two are one value)
+template <bool MAX> __device__ __forceinline__ double op_extreme_f64_bits(unsigned long long a, unsigned long long b)
+{
+    const double x = __longlong_as_double((long long)a), y = __longlong_as_double((long long)b);
+    return MAX ? (y > x ? y : x) : (y < x ? y : x);
+}
+template <bool MAX> __device__ __forceinline__ double wave_extreme_f64(double x)
+{
+    unsigned long long v = (unsigned long long)__double_as_longlong(x);
+#define CAPE_F64_STEP(CTRL) v = (unsigned long long)__double_as_longlong(op_extreme_f64_bits<MAX>(v, dpp_u64<CTRL>(v)));
+    CAPE_F64_STEP(kDppQuadXor1)
+    CAPE_F64_STEP(kDppQuadXor2)
+    CAPE_F64_STEP(kDppRowHalfMirror)
+    CAPE_F64_STEP(kDppRowMirror)
+#undef CAPE_F64_STEP
+    const double a = op_extreme_f64_bits<MAX>(readlane_u64(v, 0), readlane_u64(v, 16)), b = op_extreme_f64_bits<MAX>(readlane_u64(v, 32), readlane_u64(v, 48));
+    return MAX ? (b > a ? b : a) : (b < a ? b : a);
+}
+
+// may_be_visible by one wave, lane l on the vertices l, l + 64, ..: the same statements per vertex; a non-finite coordinate in any
+// lane decides before the box is looked at, and the box of finite coordinates does not depend on the order they were met in
+__device__ inline bool may_be_visible_wave(const double* Tm, const MapVisibilityParams& p, int j, int lane)
+{
+    const cape_map_plane& M = p.mapPlanes[j];
+    const CameraFrame F = camera_frame(Tm, M);
+    const cape_map_ring R = p.mapRings[M.ring_first];
+    const double2* src = p.mapVertices + R.vertex_offset;
+    const int n = (int)R.vertex_count;
+    bool finite = true;
+    double minU = __builtin_inf(), maxU = -__builtin_inf(), minV = __builtin_inf(), maxV = -__builtin_inf();
+    for (int i = lane; i < n; i += 64)
+    {
+        const double2 s = screen_vertex(p, F, to_camera_vertex(Tm, F, src[i]));
+        finite = finite && isfinite(s.x) && isfinite(s.y);
+        minU = s.x < minU ? s.x : minU;
+        maxU = s.x > maxU ? s.x : maxU;
+        minV = s.y < minV ? s.y : minV;
+        maxV = s.y > maxV ? s.y : maxV;
+    }
+    if (__ballot(!finite))
+        return false;
+    return !box_misses_screen(p, wave_extreme_f64<false>(minU), wave_extreme_f64<true>(maxU), wave_extreme_f64<false>(minV), wave_extreme_f64<true>(maxV));
+}
+
 } // namespace
 
 __global__ __launch_bounds__(64 * kVisFrames) void cape_map_classify_kernel(MapVisibilityParams p, int nFrames)
@@ -147,6 +196,60 @@ __global__ __launch_bounds__(64 * kVisFrames) void cape_map_classify_kernel(MapV
             p.work[at + (unsigned)__popcll(l & ((1ull << lane) - 1ull))] = ((unsigned long long)(unsigned)frame << 32) | (unsigned)(jb + lane);
         at += (unsigned)__popcll(l);
     }
+}
+
+// cape_map_step_visible: frame 0 of p (one pose, one row of words) against the map whose tracks are `tracks`.  Group, wave and round of
+// a plane and the words of a group: cape_map_step_visible.h.  The words and the content of the work list are the batch kernel's for
+// n_frames = 1 with the tracks' moving bits as its moving words; the ORDER of the list is not (groups reserve their entries as they
+// finish): no result depends on it -- the visible kernels decide every entry on its own and clear its own bit.  counts[10] and
+// counts[11]: the moving planes and the listed ones.
+__global__ __launch_bounds__(64 * kStepVisGroupWaves) void cape_map_classify_one_kernel(MapVisibilityParams p, const MapTrackState* tracks)
+{
+    __shared__ unsigned long long s_listed[kStepVisGroupWaves], s_moving[kStepVisGroupWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, group = blockIdx.x;
+    unsigned long long listed = 0ull, moving = 0ull; // (uniform in the wave)
+    for (int r = 0; r < kStepVisRounds; ++r)
+    {
+        const int j = step_vis_plane(group, wave, r);
+        if (j >= p.nMap)
+            break;
+        const unsigned long long bit = 1ull << step_vis_slot(wave, r);
+        if (tracks[j].flags & CAPE_MAP_TRACK_MOVING)
+            moving |= bit;
+        else if (may_be_visible_wave(p.poses, p, j, lane))
+            listed |= bit;
+    }
+    if (lane == 0)
+    {
+        s_listed[wave] = listed;
+        s_moving[wave] = moving;
+    }
+    __syncthreads();
+    if (wave != 0)
+        return;
+    listed = moving = 0ull;
+    for (int w = 0; w < kStepVisGroupWaves; ++w)
+    {
+        listed |= s_listed[w];
+        moving |= s_moving[w];
+    }
+    unsigned long long base = 0ull;
+    if (lane == 0)
+    {
+        // every bit of a plane starts set (moving, or not visible until a visible kernel says otherwise), the bits beyond n_map clear
+        step_vis_store_words(p.skip, p.skipWords, group, step_vis_present(group, p.nMap));
+        if (listed)
+        {
+            base = atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)__popcll(listed));
+            atomicAdd(&p.counts[11], (unsigned)__popcll(listed));
+        }
+        if (moving)
+            atomicAdd(&p.counts[10], (unsigned)__popcll(moving));
+    }
+    base = readlane_u64(base, 0);
+    // (the list holds n_map entries: every plane fits)
+    if ((listed >> lane) & 1ull)
+        p.work[base + (unsigned)__popcll(listed & ((1ull << lane) - 1ull))] = (unsigned long long)(unsigned)(group * kStepVisGroupPlanes + lane);
 }
 
 // A pair beyond this tier's capacities moves to the next tier's list when that one is larger in the resource that ran out (and
@@ -262,15 +365,11 @@ template <int TIER> __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup
     }
 }
 
-hipError_t launch_map_visibility(const MapVisibilityParams& params, int nFrames, hipStream_t stream)
+namespace {
+
+// the visible kernels behind either classify kernel
+hipError_t launch_visible_tiers(const MapVisibilityParams& p, hipStream_t stream)
 {
-    MapVisibilityParams p = params;
-    p.lastTier = tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes ? 3 : 2;
-    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
-        return e;
-    hipLaunchKernelGGL(cape_map_classify_kernel, dim3((nFrames + kVisFrames - 1) / kVisFrames), dim3(64 * kVisFrames), 0, stream, p, nFrames);
-    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
-        return e;
     // persistent grids: as many workgroups as the chip holds at once (the list's length is only known on the device)
     const int cus = p.computeUnits > 0 ? p.computeUnits : 256;
     auto launch = [&](auto kernel, int lds, int wavesPerGroup, bool coop, int groupsPerCu) {
@@ -287,6 +386,33 @@ hipError_t launch_map_visibility(const MapVisibilityParams& params, int nFrames,
     if (p.lastTier >= 3)
         return launch(cape_map_visible_kernel<3>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu);
     return hipSuccess;
+}
+
+} // namespace
+
+hipError_t launch_map_visibility(const MapVisibilityParams& params, int nFrames, hipStream_t stream)
+{
+    MapVisibilityParams p = params;
+    p.lastTier = tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes ? 3 : 2;
+    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(cape_map_classify_kernel, dim3((nFrames + kVisFrames - 1) / kVisFrames), dim3(64 * kVisFrames), 0, stream, p, nFrames);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    return launch_visible_tiers(p, stream);
+}
+
+// one frame (p.poses: its pose; p.skip: its words; p.moving is not read) of a map of p.nMap >= 1 planes with the tracks `tracks`
+hipError_t launch_map_step_visibility(const MapVisibilityParams& params, const MapTrackState* tracks, hipStream_t stream)
+{
+    MapVisibilityParams p = params;
+    p.lastTier = tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes ? 3 : 2;
+    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(cape_map_classify_one_kernel, dim3(step_vis_groups(p.nMap)), dim3(64 * kStepVisGroupWaves), 0, stream, p, tracks);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    return launch_visible_tiers(p, stream);
 }
 
 } // namespace cape

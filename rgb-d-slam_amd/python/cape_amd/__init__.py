@@ -273,6 +273,11 @@ assert MAP_MAINTAIN_RESULT_DTYPE.itemsize == 64
 MAP_STEP_RESULT_DTYPE = np.dtype([("commit", MAP_COMMIT_RESULT_DTYPE), ("maintain", MAP_MAINTAIN_RESULT_DTYPE)], align=True)
 assert MAP_STEP_RESULT_DTYPE.itemsize == 112 and MAP_STEP_RESULT_DTYPE.fields["maintain"][1] == 48
 
+# cape_map_step_visible: the step's result, then what the visibility ahead of it counted (cape_map_step_visible_result)
+MAP_STEP_VISIBLE_RESULT_DTYPE = np.dtype([("step", MAP_STEP_RESULT_DTYPE), ("n_map", "<i4"), ("n_moving", "<i4"), ("n_listed", "<i4"),
+                                          ("pad", "<i4"), ("n_undecided", "<i8")], align=True)
+assert MAP_STEP_VISIBLE_RESULT_DTYPE.itemsize == 136 and MAP_STEP_VISIBLE_RESULT_DTYPE.fields["n_undecided"][1] == 128
+
 
 class cape_host_map(C.Structure):
     """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
@@ -841,6 +846,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_union_cut", "cape_debug_polygon_union_cut",
     "cape_map_commit", "cape_map_info", "cape_map_download",
     "cape_map_maintain", "cape_map_retired_info", "cape_map_retired_download", "cape_map_retired_clear", "cape_map_step",
+    "cape_map_step_visible", "cape_map_step_skip_words",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -954,6 +960,8 @@ def load_library():
     L.cape_map_retired_download.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, vp]
     L.cape_map_retired_clear.argtypes = [vp]
     L.cape_map_step.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), vp, vp]
+    L.cape_map_step_visible.argtypes = [vp, C.c_int32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), vp, vp]
+    L.cape_map_step_skip_words.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1522,6 +1530,33 @@ class Extractor:
         elif result[0]["commit"]["flags"] & COMMIT_DONE:
             self.map_size = int(result[0]["commit"]["n_planes"])
         return result[0], nid.value
+
+    def map_step_visible(self, frame, world_to_camera, match_flags=0, commit_flags=0, next_id=0, stream=0):
+        """cape_map_step_visible: map_step with the frame's skip words decided on the device in the same call -- bit j = the device
+        track j is MAP_TRACK_MOVING, or map plane j is not visible from world_to_camera -- against the map as the call finds it.
+        Returns (result: MAP_STEP_VISIBLE_RESULT_DTYPE scalar, next_id): result["step"] is map_step's result for the words of
+        map_visibility(1, world_to_camera, the tracks' moving bits); n_map, n_moving, n_listed and n_undecided describe the words,
+        which map_step_skip_words copies."""
+        T = np.ascontiguousarray(world_to_camera, np.float64).reshape(16)
+        nid = C.c_uint64(next_id)
+        result = np.zeros(1, MAP_STEP_VISIBLE_RESULT_DTYPE)
+        _check(self.L, self.L.cape_map_step_visible(self.h, frame, T.ctypes.data_as(C.c_void_p), match_flags, commit_flags, C.byref(nid),
+                                                    result.ctypes.data_as(C.c_void_p), C.c_void_p(stream)), "cape_map_step_visible")
+        step = result[0]["step"]
+        if step["maintain"]["flags"] & MAINTAIN_DONE:
+            self.map_size = int(step["maintain"]["n_planes"])
+        elif step["commit"]["flags"] & COMMIT_DONE:
+            self.map_size = int(step["commit"]["n_planes"])
+        return result[0], nid.value
+
+    def map_step_skip_words(self):
+        """cape_map_step_skip_words: (words[ceil(n_map / 32)] uint32, n_map) of the last map_step_visible -- the map as it was before
+        that step, whatever the step's outcome; valid until the next map_step_visible or upload_map."""
+        words = np.zeros(MAP_MAX_PLANES // 32, np.uint32)
+        n_map = C.c_int32(0)
+        _check(self.L, self.L.cape_map_step_skip_words(self.h, words.ctypes.data_as(C.c_void_p), len(words), C.byref(n_map)),
+               "cape_map_step_skip_words")
+        return words[: (n_map.value + 31) // 32].copy(), int(n_map.value)
 
     def debug_polygon_union(self, rings_a, ring_b, frames=None):
         """cape_debug_polygon_union: map_union_holes' per-pair device function on one pair -- rings_a = [outer, hole, ...] of the map
