@@ -1,7 +1,9 @@
 // C ABI of libcape_hip (see include/cape_hip.h), host side only.  This file: handle creation / destruction, the debug knobs,
 // version and error reporting, the log callback, timings, host memory and streams.  The other entry points live in
 // cape_api_extract.hip (extraction and its results), cape_api_gather.hip (packing and RCCL), cape_api_geometry.hip (rectify,
-// matching, polygons, the map) and cape_api_debug.hip.  The handle itself is in cape_handle.h.
+// matching between frames, polygons), cape_api_map_match.hip (the device map and the calls that read it), cape_api_map_update.hip
+// (the calls that change it) and cape_api_debug.hip.  The handle itself is in cape_handle.h, what the map's files share in
+// cape_api_map.h.
 // There is no CPU fallback: without a HIP device cape_create fails with CAPE_ERR_NO_DEVICE.
 #include <algorithm>
 #include <cmath>

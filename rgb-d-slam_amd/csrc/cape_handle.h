@@ -205,6 +205,41 @@ struct PinnedTwin
     }
 };
 
+// One buffer set of the device map: its planes, rings and vertices, the tracks parallel to the planes and their ids.  The handle
+// has three (cape_handle_s::MapSets); they rotate by swapping buffers, so every buffer lives as long as its owner.
+struct MapSet
+{
+    Buffer<cape_map_plane> planes;
+    Buffer<cape_map_ring> rings;
+    Buffer<double> vertices;       // two doubles per vertex
+    Buffer<cape::MapTrackState> tracks; // parallel to the planes
+    Buffer<cape::MapTrackTag> tags;     // ... and their id / result, which cape::MapTrackState does not hold
+
+    void swap(MapSet& o) noexcept
+    {
+        planes.swap(o.planes);
+        rings.swap(o.rings);
+        vertices.swap(o.vertices);
+        tracks.swap(o.tracks);
+        tags.swap(o.tags);
+    }
+    // a destination set takes a map of these sizes (contents dropped where a buffer is replaced; `drain` runs first: a set was the front
+    // one of an earlier map, and a call in flight may read it)
+    template <typename Sync> hipError_t grow(size_t nPlanes, size_t nRings, size_t nVertices, Sync drain)
+    {
+        hipError_t e = planes.grow(nPlanes, drain);
+        if (e == hipSuccess)
+            e = rings.grow(nRings, drain);
+        if (e == hipSuccess)
+            e = vertices.grow(nVertices * 2, drain);
+        if (e == hipSuccess)
+            e = tracks.grow(nPlanes, drain);
+        if (e == hipSuccess)
+            e = tags.grow(nPlanes, drain);
+        return e;
+    }
+};
+
 constexpr int kHostResultFrames = 8; // see cape_handle_s::resultsOnHost
 
 } // namespace cape::abi
@@ -374,7 +409,7 @@ struct cape_handle_s
         Buffer<int32_t> match;                // max_batch x 128 match, then as many seg_prev, then seg_cur
         Buffer<uint2> kept;                   // max_batch x 128: MatchWideParams::kept
         Buffer<double> areas;                 // CAPE_MATCH_MAP_AREAS: frames x 128 x 128 of the call
-        Buffer<unsigned char> work;           // counters, frame ranges, work list, its areas, the tier lists (wide_work_layout)
+        Buffer<unsigned char> work;           // counters, frame ranges, work list, its areas, the tier lists (map_work_layout without mask words)
         int matchFrames = 0;                  // frames of the last cape_match_polygons_wide (0: none for the current batch)
         bool matchAreas = false;              // ... and whether it kept the dense table
     } wide;
@@ -392,13 +427,24 @@ struct cape_handle_s
         bool saved = false;                   // a frame is carried (cape_match_carry_clear: none)
     } carry;
 
-    // N2 against a persistent map (cape_map_upload / cape_match_map): the map sized at upload, the rest allocated on first use
+    // The device map (cape_map_upload, cape_map_upload_tracks) and what changes it (cape_map_commit, cape_map_maintain, cape_map_step):
+    // three buffer sets and the sizes of the FRONT one, the map every call reads.  `back` is the destination of a commit or a
+    // maintenance, swapped with the front set once the call's header says DONE; `third` is what the maintenance behind a step's commit
+    // writes, since the commit's source (front) and destination (back) are both live until the one wait of that call.  The sets
+    // rotate: after a step whose maintenance is DONE the third set is the front one and the old front one the third.  The front
+    // set is sized at upload; a destination is grown behind drain_handle before the first launch, contents dropped.
+    struct MapSets
+    {
+        cape::abi::MapSet front, back, third;
+        int n = -1;              // planes of the front set's map (-1: none uploaded yet)
+        int nRings = 0;          // ... its rings and vertices
+        long long nVertices = 0;
+        int tracksN = -1;        // tracks current for that map (-1: none since cape_map_upload)
+    } maps;
+
+    // N2 against the map (cape_match_map): results and work buffers, allocated on first use
     struct Map
     {
-        Buffer<cape_map_plane> planes;
-        Buffer<cape_map_ring> rings;
-        Buffer<double> vertices;
-        int n = -1;                  // planes of the uploaded map (-1: none yet)
         Buffer<unsigned char> poses; // the poses of the call (frames x 16 doubles), then its skip words
         cape::abi::PinnedTwin posesTwin;
         Buffer<cape_frame_map_match> frames; // max_batch
@@ -490,13 +536,10 @@ struct cape_handle_s
     Event sideFork, sideDone;
     bool sidePending = false;
 
-    // cape_map_upload_tracks / cape_map_kalman: the tracks parallel to the uploaded map's planes and the state half of the map update
-    // for the frames of the last call.  Result buffers of its own, grown on demand behind drain_handle: no other call writes them.
-    // (Declared last: the members above keep their places for the files that do not know this call.)
+    // cape_map_kalman: the state half of the map update for the frames of the last call, on the front set's tracks.  Result buffers
+    // of its own, grown on demand behind drain_handle: no other call writes them.
     struct Kalman
     {
-        Buffer<cape::MapTrackState> tracks;       // n planes of the uploaded map
-        int tracksN = -1;                         // tracks uploaded for the current map (-1: none since cape_map_upload)
         bool matchedThisMap = false;              // a cape_match_map_wide has run since the last cape_map_upload
         Buffer<cape_frame_map_kalman> frames;     // frames of the call
         Buffer<cape_plane_fusion> rows;           // frames x 128
@@ -507,7 +550,7 @@ struct cape_handle_s
     } kalman;
 
     // cape_map_union: the polygon half of the map update for the frames of the last call.  Result buffers of its own, grown on demand
-    // behind drain_handle: no other call writes them.  (Declared last, like the struct above.)
+    // behind drain_handle: no other call writes them.
     struct Union
     {
         Buffer<cape_plane_union> rows; // frames x 128
@@ -517,33 +560,22 @@ struct cape_handle_s
     } mapUnion;
 
     // cape_map_union_holes and cape_map_union_cut: the rings table beside mapUnion's rows and slab, which either call writes too.
-    // (Declared last, like the structs above.)
     struct UnionRings
     {
         Buffer<cape_plane_union_rings> rows; // frames x 128
         bool current = false;                // mapUnion's rows are those of one of these two calls: the table belongs to them
     } mapUnionRings;
 
-    // cape_map_commit / cape_map_info / cape_map_download: the BACK buffers of Map's planes, rings and vertices and of Kalman's tracks,
-    // which the commit writes and swaps with the front ones once its header says DONE, and the id / result of every track (front and
-    // back), which cape::MapTrackState does not hold.  The back buffers are grown behind drain_handle before the launch.  (Declared
-    // last, like the structs above.)
+    // cape_map_commit: the call's plan and header.  Its destination is MapSets::back.
     struct MapCommit
     {
-        Buffer<cape_map_plane> planes;
-        Buffer<cape_map_ring> rings;
-        Buffer<double> vertices;
-        Buffer<cape::MapTrackState> tracks;
-        Buffer<cape::MapTrackTag> tags, tagsBack; // tags: parallel to Kalman::tracks, written by cape_map_upload_tracks and the commit
-        Buffer<cape::CommitPlanRow> plan;         // CAPE_MAP_MAX_PLANES rows
-        Buffer<cape_map_commit_result> header;    // device memory: the plan kernel's, read by the copy kernel
+        Buffer<cape::CommitPlanRow> plan;          // CAPE_MAP_MAX_PLANES rows
+        Buffer<cape_map_commit_result> header;     // device memory: the plan kernel's, read by the copy kernel
         Buffer<cape_map_commit_result> headerHost; // pinned: the header comes back through it before the call returns
-        int nRings = 0;                           // rings and vertices of the map on the device (Map::n says the planes)
-        long long nVertices = 0;
     } mapCommit;
 
     // cape_map_maintain / cape_map_retired_*: the retired log -- the lost planes in a map's layout, offsets relative to these arrays --
-    // and the call's plan and header.  The map's back buffers are MapCommit's.  The log outlives every map: only
+    // and the call's plan and header.  Its destination is MapSets::back.  The log outlives every map: only
     // cape_map_retired_clear empties it.  Its arrays are grown behind drain_handle before the launch, their contents kept.
     struct MapMaintain
     {
@@ -558,25 +590,17 @@ struct cape_handle_s
         Buffer<cape_map_maintain_result> headerHost; // pinned: the header comes back through it before the call returns
     } mapMaintain;
 
-    // cape_map_step: the THIRD buffer set of the map, its tracks and their ids -- what the maintenance behind the step's commit writes,
-    // since the commit's source (the front set) and destination (MapCommit's back set) are both live until the one wait of the call --
-    // and the two headers of the call side by side, so that one copy brings both back.  The sets rotate: after a step whose
-    // maintenance is DONE the third set is the front one and the old front one the third.  Grown behind drain_handle before the
-    // first launch, contents dropped.  (Declared last, like the structs above.)
+    // cape_map_step: the two headers of the call side by side, so that one copy brings both back.  Its maintenance writes
+    // MapSets::third.
     struct MapStep
     {
-        Buffer<cape_map_plane> planes;
-        Buffer<cape_map_ring> rings;
-        Buffer<double> vertices;
-        Buffer<cape::MapTrackState> tracks;
-        Buffer<cape::MapTrackTag> tags;
         Buffer<cape_map_step_result> header;     // device memory: the commit's and the maintenance's plan kernels write their halves
         Buffer<cape_map_step_result> headerHost; // pinned: both headers come back through it before the call returns
     } mapStep;
 
     // cape_map_step_visible / cape_map_step_skip_words: the skip words the step decided for its frame against the map as it found
     // it, the work buffers of its visibility kernels and their counters' way back.  Buffers of its own -- cape_map_visibility's words
-    // are not touched -- grown behind drain_handle before the first launch.  (Declared last, like the structs above.)
+    // are not touched -- grown behind drain_handle before the first launch.
     struct MapStepVisible
     {
         Buffer<uint32_t> skip;         // CAPE_MAP_MAX_PLANES / 32 words

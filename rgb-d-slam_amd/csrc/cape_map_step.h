@@ -1,6 +1,6 @@
 // cape_map_step: the hand-off from a frame's commit to the maintenance behind it, without the host in between.  One plain function
 // says which buffer set holds the map after (commit header, maintain header) and with which counts; the step's two kernels
-// (cape_map_maintain.hip) take their source from it with the maintain header still all zero, the host (cape_api_geometry.hip) does
+// (cape_map_maintain.hip) take their source from it with the maintain header still all zero, the host (cape_api_map_update.hip) does
 // its bookkeeping with it after the one wait, and tests/host/map_step_plan.cpp compiles it between the two serial plans.
 //
 // Like cape_map_commit.h and cape_map_maintain.h: __host__ __device__ with hipcc, plain inline functions with any other compiler.

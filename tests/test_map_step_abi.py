@@ -67,7 +67,7 @@ def test_the_hand_off_rule_has_one_definition(hip_library):
     csrc = os.path.join(ROOT, "rgb-d-slam_amd", "csrc")
     rule = open(os.path.join(csrc, "cape_map_step.h")).read()
     assert len(re.findall(r"StepMapState step_map_after\(", rule)) == 1
-    for name in ("cape_map_maintain.hip", "cape_api_geometry.hip"):
+    for name in ("cape_map_maintain.hip", "cape_api_map_update.hip"):
         text = open(os.path.join(csrc, name)).read()
         assert "step_map_after(" in text and "StepMapState step_map_after(" not in text, name
 
