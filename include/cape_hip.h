@@ -1225,6 +1225,75 @@ int cape_map_step_visible(cape_handle h, int32_t frame, const double* world_to_c
                           uint32_t commit_flags, uint64_t* next_id, cape_map_step_visible_result* out, void* stream);
 int cape_map_step_skip_words(cape_handle h, uint32_t* words, int32_t words_capacity, int32_t* n_map);
 
+/* THE PLANE COST FUNCTION OF THE POSE SOLVER, for a batch of pose hypotheses per frame: the stage between the match and the update
+ * (find matches -> optimise the pose -> update -> maintain).  The solver itself (RANSAC over hypotheses, Levenberg-Marquardt) stays
+ * with the caller; what it evaluates thousands of times per frame -- PlaneOptimizationFeature::is_inlier / get_distance
+ * (map_primitive.cpp:15-85), called by Pose_Optimization::get_features_inliers_outliers (pose_optimization.cpp:40-75) and the LM
+ * functor (levenberg_marquardt_functors.cpp:154-166) -- runs here on data that is already on the device.
+ * Frame f's PAIRS are the map planes j = 0 .. n_map-1 in ascending order with i = match[f][j] >= 0 of the last cape_match_map_wide,
+ * at most 128.  The k-th pair's feature row: matched = (out_normal, d) of the segment the wide match's kept-plane table names for
+ * kept plane i (every index taken from that table is checked against the record buffer before use; one that fails gives NaN, i.e. an
+ * invalid feature and an outlier), map_plane = the map plane's (normal, d), stddev[c] = sqrt(covariance[5 c]) of the device track,
+ * map_id = the track's id.  For hypothesis T = world_to_camera[f][h], with (qn, qd) = plane_to_camera(T, map plane):
+ *   signed[c] = atan2(sin(cn[c] - qn[c]), cos(cn[c] - qn[c])) for c < 3 (get_signed_distance, plane_coordinates.cpp:26-37, through
+ *     angle_distance, distance_utils.cpp:6-9: the reference feeds normal components to an angle function), signed[3] = cd - qd;
+ *   inlier = |signed[c]| <= (double)0.2f for c < 3 and |signed[3]| <= (double)50.0f (parameters.hpp:27-30; a NaN is an outlier);
+ *   reduced[c] = cd cn[c] - qd qn[c] (get_reduced_signed_distance, plane_coordinates.cpp:49-56);
+ *   r[c] = reduced[c] * 1.0 / 3.0 and sum_sq += r[c] r[c], c ascending within k, k ascending;  score += 1.0 / 3 per inlier in pair
+ *     order (get_score, map_primitive.cpp:27-31).
+ * A pair is VALID (is_valid, map_primitive.cpp:79-83) when matched, map_plane and stddev hold no NaN and no stddev is negative.  An
+ * invalid pair is still scored; it is counted in n_invalid and every row of the frame carries CAPE_POSE_SCORE_INVALID_FEATURE (the
+ * reference abandons the optimisation there, pose_optimization.cpp:270-280: the caller decides).
+ * Everything but the three atan2(sin, cos) values is + - x / sqrt and equals the host twin cape_host_pose_score
+ * (host/cape_host_map.h) bit for bit; the three angle parts are the device math library's and may differ from the host's libm in
+ * the last places.  Every sum belongs to one (frame, hypothesis) and is taken in pair order: no result depends on the other
+ * hypotheses of the call. */
+enum /* flags of cape_map_pose_score */
+{
+    CAPE_POSE_SCORE_DEVICE_POSES = 1u << 0, /* world_to_camera is DEVICE memory, read in place when the kernel runs */
+    CAPE_POSE_SCORE_RESIDUALS = 1u << 1     /* also keep signed[4] and reduced[3] of every (frame, hypothesis, pair) */
+};
+enum /* cape_pose_score.flags, beside CAPE_MATCH_EXACT_OVERFLOW */
+{
+    CAPE_POSE_SCORE_INVALID_FEATURE = 1u << 8 /* a pair of the frame fails is_valid (n_invalid > 0) */
+};
+typedef struct cape_pose_score /* 48 bytes, one per (frame, hypothesis) */
+{
+    int32_t n_pairs, n_inliers, n_invalid;
+    uint32_t flags;            /* CAPE_MATCH_EXACT_OVERFLOW of the wide match (n_pairs = 0, everything else 0), CAPE_POSE_SCORE_INVALID_FEATURE */
+    double score, sum_sq;      /* n_inliers times 1.0 / 3 added in pair order; the sum of the squared LM residuals */
+    uint32_t inlier_words[4];  /* bit i set: kept plane i is matched and an inlier */
+} cape_pose_score;
+typedef struct cape_pose_feature /* 112 bytes, one per pair k < 128 of a frame, all zero beyond n_pairs: the constructor arguments of
+                                    PlaneOptimizationFeature */
+{
+    double matched[4];   /* the detected plane (cn, cd), camera coordinates */
+    double map_plane[4]; /* the map plane (normal, d), world coordinates */
+    double stddev[4];    /* sqrt of the track covariance's diagonal */
+    uint64_t map_id;     /* the track's id */
+    int32_t map_index, kept_plane; /* j and i of the pair */
+} cape_pose_feature;
+/* world_to_camera: n_frames x n_hypotheses x 16 doubles, row-major [R t; 0 0 0 1] -- HOST memory read before the call returns, or,
+ * with CAPE_POSE_SCORE_DEVICE_POSES, device memory that must stay unchanged until the call's work on `stream` is done.
+ * CAPE_POSE_SCORE_RESIDUALS keeps the table [f][h][k][7] (CAPE_ERR_CAPACITY if n_frames x n_hypotheses x 128 x 7 x 8 bytes would
+ * exceed 1 GiB).  Needs, on the current batch and covering n_frames, a cape_match_map_wide since the last cape_map_upload, and tracks
+ * current for the map -- otherwise CAPE_ERR_CAPACITY.  CAPE_ERR_INVALID_ARGUMENT: NULL handle or poses, n_frames < 0,
+ * n_hypotheses < 1, unknown flag.  A frame the wide match flagged CAPE_MATCH_EXACT_OVERFLOW reports that flag, n_pairs = 0 and zeros;
+ * an empty map succeeds with n_pairs = 0 everywhere.  Nothing is written into the map, the tracks, the matches or any other call's
+ * results: the buffers are the handle's own, grown on demand.  What invalidates cape_map_kalman's results -- a later cape_extract,
+ * cape_build_polygons, cape_map_upload, cape_map_upload_tracks, cape_match_map_wide, cape_map_measure, or a cape_map_commit,
+ * cape_map_maintain or cape_map_step[_visible] that changes the map -- invalidates these.  Asynchronous on `stream`. */
+int cape_map_pose_score(cape_handle h, int32_t n_frames, int32_t n_hypotheses, const double* world_to_camera, uint32_t flags, void* stream);
+/* Synchronous copy of the last cape_map_pose_score: scores (n_frames x n_hypotheses of that call), features (n_frames x 128),
+ * residuals (n_frames x n_hypotheses x 128 x 7: signed[4] then reduced[3], zeros beyond n_pairs; the call must have had
+ * CAPE_POSE_SCORE_RESIDUALS, else CAPE_ERR_INVALID_ARGUMENT).  Any pointer may be NULL.  CAPE_ERR_CAPACITY: more frames than that call
+ * covered, or its results are no longer current. */
+int cape_copy_pose_scores(cape_handle h, int32_t n_frames, cape_pose_score* scores, cape_pose_feature* features, double* residuals);
+/* Device pointers of the score rows (frames x n_hypotheses of the call) and the feature rows (frames x 128), for a caller that
+ * selects the best hypothesis with a kernel of its own on the stream of the scoring call.  Either may be NULL.  CAPE_ERR_CAPACITY
+ * when no cape_map_pose_score is current. */
+int cape_pose_score_device(cape_handle h, const cape_pose_score** scores, const cape_pose_feature** features);
+
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
  * the `stream` argument of the calls below; destroy it before the handle. */

@@ -267,7 +267,7 @@ int cape_build_polygons(cape_handle h, int32_t n_frames, void* stream_)
 #endif
     h->res.doneArmed = false; // the chain's completion word was written before this kernel: results are waited for the slow way
     h->measure.frames = 0; // (the measurements index the polygons this call replaces)
-    h->kalman.kalmanFrames = 0;
+    invalidate_frame_results(h);
     CAPE_HIP_TRY(cape::launch_polygons(p, n_frames, stream));
     P.frames = n_frames;
     return CAPE_OK;

@@ -352,14 +352,14 @@ inline void adopt_map(cape_handle_s* h, MapSet& from, const MapSizes& sizes)
 }
 
 // What a changed map invalidates, for every call that changes it: the words cape_map_visibility decided for the old map, the wide
-// match against it and what cape_map_kalman (and with it the unions) made of that.  An upload brings no tracks, and ends the words
+// match against it and what cape_map_kalman (and with it the unions) and cape_map_pose_score made of that.  An upload brings no tracks, and ends the words
 // of cape_map_step_visible too; behind a commit, a maintenance or a step those words stay readable -- they stand for the map that
 // step found -- and the new set's tracks are current (adopt_map).
 inline void invalidate_for_new_map(cape_handle_s* h, bool uploaded = false)
 {
     h->visibility.frames = 0;
     h->kalman.matchedThisMap = false;
-    h->kalman.kalmanFrames = 0;
+    invalidate_frame_results(h);
     if (uploaded)
     {
         h->mapStepVisible.n = -1;

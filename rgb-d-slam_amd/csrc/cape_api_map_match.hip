@@ -143,7 +143,7 @@ int cape_map_upload_tracks(cape_handle h, const cape_map_track* tracks, int32_t 
     CAPE_HIP_TRY(drain_handle(h)); // a cape_map_kalman in flight still reads the old tracks
     auto& M = h->maps;
     M.tracksN = -1;
-    h->kalman.kalmanFrames = 0;
+    invalidate_frame_results(h);
     CAPE_HIP_TRY(M.front.tracks.grow(T.size(), [] { return hipSuccess; }));
     CAPE_HIP_TRY(M.front.tags.grow(G.size(), [] { return hipSuccess; }));
     if (n > 0)
@@ -251,7 +251,7 @@ int cape_match_map_wide(cape_handle h, int32_t n_frames, const double* world_to_
     if (const int rc = check_map_match(h, c, kFewerFrames); rc != CAPE_OK)
         return rc;
     W.matchFrames = 0;
-    h->kalman.kalmanFrames = 0; // (cape_map_kalman's results belong to the match this call replaces)
+    invalidate_frame_results(h); // (cape_map_kalman's and cape_map_pose_score's results belong to the match this call replaces)
     if (const int rc = run_map_match(h, c, true, stream); rc != CAPE_OK || n_frames == 0)
         return rc;
     h->kalman.matchedThisMap = true;

@@ -10,7 +10,7 @@ using namespace cape::abi;
 namespace {
 
 // the results of the last cape_map_kalman still describe the current batch, match and measurements (a cape_extract clears the latter
-// two; every other call that replaces an input clears kalmanFrames itself)
+// two; every other call that replaces an input says so through invalidate_frame_results)
 bool kalman_results_live(const cape_handle_s* h)
 {
     const auto& K = h->kalman;
@@ -189,7 +189,7 @@ int map_step_body(cape_handle h, int32_t frame, const double* world_to_camera, c
     CAPE_SETTLE_RESULTS(h);
     // the step works in row 0 of the batch-wide tables of the three calls it stands for: whatever they held is gone from here on
     h->mapWide.matchFrames = 0;
-    K.kalmanFrames = 0;
+    invalidate_frame_results(h);
     U.unionFrames = 0;
     h->mapUnionRings.current = false;
     // ---- every buffer of the five steps, before the first launch.  The wide match of frame `frame`: its pose and skip words at
@@ -313,7 +313,7 @@ int cape_map_measure(cape_handle h, int32_t n_frames, const double* camera_to_wo
         return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_build_polygons (build the polygons of the batch first)");
     auto& M = h->measure;
     M.frames = 0;
-    h->kalman.kalmanFrames = 0; // (cape_map_kalman's results belong to the rows this call replaces)
+    invalidate_frame_results(h); // (cape_map_kalman's results belong to the rows this call replaces)
     if (n_frames == 0)
         return CAPE_OK;
     CAPE_ON_DEVICE(h);

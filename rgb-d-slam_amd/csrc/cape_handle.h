@@ -13,6 +13,7 @@
 #include "cape_map_commit.h"
 #include "cape_map_maintain.h"
 #include "cape_map_step.h"
+#include "cape_pose_score.h"
 
 namespace cape {
 // every launcher returns the error of its own launch(es) (hipGetLastError right behind hipLaunchKernelGGL)
@@ -42,6 +43,7 @@ hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipS
 hipError_t launch_map_step_visibility(const MapVisibilityParams& p, const MapTrackState* tracks, hipStream_t stream);
 hipError_t launch_map_measure(const MapMeasureParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_kalman(const MapKalmanParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_ring_union(const RingUnionParams& p, hipStream_t stream);
 hipError_t launch_map_union_holes(const MapUnionParams& p, cape_plane_union_rings* ringRows /* frames x 128 */, int nFrames, hipStream_t stream);
@@ -608,7 +610,33 @@ struct cape_handle_s
         Buffer<unsigned> countsHost;   // pinned: the 16 counters come back through it before the call returns
         int n = -1;                    // map planes the words of the last cape_map_step_visible stand for (-1: none since cape_map_upload)
     } mapStepVisible;
+
+    // cape_map_pose_score: the pose hypotheses of the last call and what it made of them.  Buffers of its own, grown on demand behind
+    // drain_handle: no other call writes them, and the call writes nothing else.
+    struct PoseScore
+    {
+        Buffer<double> poses; // the poses of the call (frames x hypotheses x 16), unless they are the caller's device memory
+        cape::abi::PinnedTwin posesTwin;
+        Buffer<int4> frameInfo;             // frames: n_pairs, n_invalid, flags, 0 (the pairs kernel's, read by the score kernel)
+        Buffer<cape_pose_feature> features; // frames x 128
+        Buffer<cape_pose_score> scores;     // frames x hypotheses
+        Buffer<double> residuals;           // CAPE_POSE_SCORE_RESIDUALS: frames x hypotheses x 128 x 7
+        int frames = 0;                     // frames of the last cape_map_pose_score (0: none for the current batch, map, tracks and match)
+        int hypotheses = 0;                 // hypotheses per frame of that call
+        bool keptResiduals = false;         // ... and whether it kept the per-pair table
+    } poseScore;
 };
+
+namespace cape::abi {
+// What a replaced input of the map update's per-frame results invalidates, for every call that replaces one (the batch's polygons,
+// the wide match, the measurements, the map, its tracks): the results of cape_map_kalman -- and with them the unions' -- and those of
+// cape_map_pose_score.  (A cape_extract ends the wide match and the measurements themselves: both results are checked against them.)
+inline void invalidate_frame_results(cape_handle_s* h)
+{
+    h->kalman.kalmanFrames = 0;
+    h->poseScore.frames = 0;
+}
+} // namespace cape::abi
 
 namespace cape::abi {
 

@@ -206,6 +206,21 @@ int cape_host_shard_frame(const void* shard, uint64_t shard_bytes, const cape_ga
 int cape_host_map_visibility(const cape_host_map* map, const double* world_to_camera, int32_t width, int32_t height, double fx, double fy,
                              double cx, double cy, const uint32_t* moving, uint32_t* skip_out);
 
+/* The twin of cape_map_pose_score (include/cape_hip.h) for ONE frame (host/pose_score.cpp), on the rules of csrc/cape_pose_score.h
+ * that the kernels compile too: the plane cost function of the pose solver -- PlaneOptimizationFeature's is_inlier, get_distance and
+ * get_score (map_primitive.cpp:15-85) -- for n_hypotheses poses.  map: planes and tracks (covariance and id; rings and vertices are not
+ * read); match[map->n_planes]: the kept plane matched to map plane j or -1 (cape_copy_map_matches_wide's row of the frame);
+ * detected: the frame's kept planes, of which `planes` (normal[3], d) is read; frame_flags: the frame's flags of the wide match
+ * (CAPE_MATCH_EXACT_OVERFLOW: the frame reports that flag, n_pairs = 0 and zeros); world_to_camera: n_hypotheses x 16 doubles
+ * row-major.  The map plane goes through utils::plane_to_camera.  Outputs, any may be NULL: scores_out[n_hypotheses],
+ * features_out[128] (zero beyond n_pairs), residuals_out[n_hypotheses x 128 x 7] (signed[4] then reduced[3], zero beyond n_pairs).
+ * Everything equals the device bit for bit except the three angle parts of `signed`, which are this host's libm's (and what follows
+ * from a part within a few ulp of its threshold).  Returns 0, or CAPE_ERR_INVALID_ARGUMENT for a NULL map, detected or poses, negative
+ * counts, more than 128 kept planes, n_hypotheses < 1, an unknown frame flag, a match out of range or a missing array. */
+int cape_host_pose_score(const cape_host_map* map, const int32_t* match, const cape_host_planes* detected, uint32_t frame_flags,
+                         int32_t n_hypotheses, const double* world_to_camera, cape_pose_score* scores_out, cape_pose_feature* features_out,
+                         double* residuals_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -278,6 +278,17 @@ MAP_STEP_VISIBLE_RESULT_DTYPE = np.dtype([("step", MAP_STEP_RESULT_DTYPE), ("n_m
                                           ("pad", "<i4"), ("n_undecided", "<i8")], align=True)
 assert MAP_STEP_VISIBLE_RESULT_DTYPE.itemsize == 136 and MAP_STEP_VISIBLE_RESULT_DTYPE.fields["n_undecided"][1] == 128
 
+# cape_map_pose_score: a batch of pose hypotheses per frame scored against the frame's map matches (cape_pose_score, one per
+# (frame, hypothesis); cape_pose_feature, one per pair k < 128 of a frame)
+POSE_SCORE_DTYPE = np.dtype([("n_pairs", "<i4"), ("n_inliers", "<i4"), ("n_invalid", "<i4"), ("flags", "<u4"), ("score", "<f8"),
+                             ("sum_sq", "<f8"), ("inlier_words", "<u4", 4)], align=True)
+POSE_FEATURE_DTYPE = np.dtype([("matched", "<f8", 4), ("map_plane", "<f8", 4), ("stddev", "<f8", 4), ("map_id", "<u8"), ("map_index", "<i4"),
+                               ("kept_plane", "<i4")], align=True)
+assert POSE_SCORE_DTYPE.itemsize == 48 and POSE_FEATURE_DTYPE.itemsize == 112
+POSE_SCORE_DEVICE_POSES, POSE_SCORE_RESIDUALS = 1, 2
+POSE_SCORE_INVALID_FEATURE = 1 << 8
+POSE_SCORE_MAX_PAIRS = 128
+
 
 class cape_host_map(C.Structure):
     """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
@@ -322,6 +333,7 @@ def _host_library():
         L.cape_host_map_union_cut.argtypes = L.cape_host_map_union_holes.argtypes
         L.cape_host_map_commit.argtypes = [Map, C.c_int32] + [C.c_void_p] * 8 + [C.c_uint32, C.POINTER(C.c_uint64), Map, C.c_void_p]
         L.cape_host_map_maintain.argtypes = [Map, Map, Map, C.c_void_p]
+        L.cape_host_pose_score.argtypes = [Map, i32, Planes, C.c_uint32, C.c_int32, f64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cape_host_polygon_union_cut.argtypes = L.cape_host_polygon_union.argtypes
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
@@ -456,6 +468,37 @@ def host_map_kalman(map_arrays, tracks, match, measurements):
     if rc != 0:
         raise CapeError(f"cape_host_map_kalman failed ({rc})")
     return frame[0], rows[:n_cur], results[:n_map]
+
+
+def host_pose_score(map_arrays, tracks, match, detected_planes, world_to_camera, frame_flags=0, residuals=True):
+    """cape_host_pose_score of libcape_primitives.so: the twin of Extractor.map_pose_score for ONE frame -- the plane cost function of
+    the pose solver (PlaneOptimizationFeature's is_inlier, get_distance and get_score) for every given pose, on the rules the kernels
+    compile too.
+
+    map_arrays: pack_map(...); tracks: MAP_TRACK_DTYPE array parallel to the planes (covariance and id are read); match: n_map
+    kept-plane indices or -1; detected_planes: (n_cur, 4) the kept planes' (normal, d) in camera coordinates; world_to_camera:
+    (n_hypotheses, 4, 4); frame_flags: the frame's flags of the wide match (MATCH_EXACT_OVERFLOW).
+    Returns (scores: POSE_SCORE_DTYPE[n_hypotheses], features: POSE_FEATURE_DTYPE[128], residuals: float64[n_hypotheses, 128, 7] --
+    signed[4] then reduced[3] -- or None)."""
+    L = _host_library()
+    src, src_view = _map_arrays(map_arrays, np.ascontiguousarray(tracks, MAP_TRACK_DTYPE))
+    n_map = len(src["planes"])
+    if len(src["tracks"]) != n_map:
+        raise CapeError("host_pose_score: one track per map plane")
+    M = np.ascontiguousarray(match, np.int32).reshape(-1)
+    if len(M) != n_map:
+        raise CapeError("host_pose_score: one match per map plane")
+    D = np.ascontiguousarray(detected_planes, np.float64).reshape(-1, 4)
+    det_view = _view(cape_host_planes, dict(planes=D), n=len(D))
+    T = np.ascontiguousarray(world_to_camera, np.float64).reshape(-1, 16)
+    scores = np.zeros(max(len(T), 1), POSE_SCORE_DTYPE)
+    features = np.zeros(POSE_SCORE_MAX_PAIRS, POSE_FEATURE_DTYPE)
+    res = np.zeros((max(len(T), 1), POSE_SCORE_MAX_PAIRS, 7), np.float64) if residuals else None
+    rc = L.cape_host_pose_score(C.byref(src_view), _as(M, C.c_int32), C.byref(det_view), frame_flags, len(T), _as(T, C.c_double),
+                                scores.ctypes.data, features.ctypes.data, None if res is None else res.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_pose_score failed ({rc})")
+    return scores[:len(T)], features, None if res is None else res[:len(T)]
 
 
 def _union_rings(rows, slab):
@@ -847,6 +890,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_commit", "cape_map_info", "cape_map_download",
     "cape_map_maintain", "cape_map_retired_info", "cape_map_retired_download", "cape_map_retired_clear", "cape_map_step",
     "cape_map_step_visible", "cape_map_step_skip_words",
+    "cape_map_pose_score", "cape_copy_pose_scores", "cape_pose_score_device",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -962,6 +1006,9 @@ def load_library():
     L.cape_map_step.argtypes = [vp, C.c_int32, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), vp, vp]
     L.cape_map_step_visible.argtypes = [vp, C.c_int32, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), vp, vp]
     L.cape_map_step_skip_words.argtypes = [vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+    L.cape_map_pose_score.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_uint32, vp]
+    L.cape_copy_pose_scores.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.cape_pose_score_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1397,6 +1444,43 @@ class Extractor:
             n_cur = 0 if frames[f]["flags"] & MATCH_EXACT_OVERFLOW else min(int(frames[f]["n_cur"]), MATCH_MAP_WIDE_MAX_PLANES)
             out.append(({name: int(frames[f][name]) for name in frames.dtype.names}, _fusion_dicts(rows[f], n_cur), results[f].copy()))
         return out
+
+    # ---- between the match and the update: pose hypotheses scored against the frame's map matches (needs upload_map +
+    # upload_tracks and match_map_wide of the batch) ----
+    def map_pose_score(self, n_frames, world_to_camera, flags=0, n_hypotheses=None, stream=0):
+        """cape_map_pose_score: per frame of [0, n_frames) and per pose hypothesis the plane cost function of the pose solver over the
+        frame's matched pairs of the last match_map_wide -- inliers, score, the LM residuals' sum of squares.  world_to_camera:
+        (n_frames, n_hypotheses, 4, 4) row-major [R t; 0 0 0 1]; with POSE_SCORE_DEVICE_POSES a device address (int) of that many
+        doubles and n_hypotheses given.  POSE_SCORE_RESIDUALS keeps the per-pair table.  The results are pose_scores' and
+        pose_features'."""
+        if flags & POSE_SCORE_DEVICE_POSES and not isinstance(world_to_camera, np.ndarray):
+            if n_hypotheses is None:
+                raise CapeError("map_pose_score: n_hypotheses is required with a device address")
+            ptr = C.c_void_p(int(world_to_camera))
+        else:
+            T = np.ascontiguousarray(world_to_camera, np.float64)
+            n_hypotheses = T.size // (16 * n_frames) if n_hypotheses is None and n_frames > 0 else (n_hypotheses or 0)
+            if T.size != n_frames * n_hypotheses * 16:
+                raise CapeError("map_pose_score: world_to_camera must hold n_frames x n_hypotheses x 16 doubles")
+            ptr = T.ctypes.data_as(C.c_void_p)
+        _check(self.L, self.L.cape_map_pose_score(self.h, n_frames, n_hypotheses, ptr, flags, C.c_void_p(stream)), "cape_map_pose_score")
+        self.pose_score_hypotheses = n_hypotheses
+
+    def pose_scores(self, n_frames, residuals=False):
+        """POSE_SCORE_DTYPE[n_frames, n_hypotheses] of the last map_pose_score; with residuals=True (the call must have had
+        POSE_SCORE_RESIDUALS) the pair (scores, float64[n_frames, n_hypotheses, 128, 7]: signed[4] then reduced[3])."""
+        n_hyp = getattr(self, "pose_score_hypotheses", 0)
+        scores = np.zeros((n_frames, max(n_hyp, 1)), POSE_SCORE_DTYPE)
+        res = np.zeros((n_frames, max(n_hyp, 1), POSE_SCORE_MAX_PAIRS, 7), np.float64) if residuals else None
+        _check(self.L, self.L.cape_copy_pose_scores(self.h, n_frames, scores.ctypes.data_as(C.c_void_p), None,
+                                                    None if res is None else res.ctypes.data_as(C.c_void_p)), "cape_copy_pose_scores")
+        return (scores[:, :n_hyp], res[:, :n_hyp]) if residuals else scores[:, :n_hyp]
+
+    def pose_features(self, n_frames):
+        """POSE_FEATURE_DTYPE[n_frames, 128] of the last map_pose_score: the frame's pairs in map order, zeros beyond n_pairs."""
+        features = np.zeros((n_frames, POSE_SCORE_MAX_PAIRS), POSE_FEATURE_DTYPE)
+        _check(self.L, self.L.cape_copy_pose_scores(self.h, n_frames, None, features.ctypes.data_as(C.c_void_p), None), "cape_copy_pose_scores")
+        return features
 
     # ---- the polygon half of the map update (needs map_kalman of the batch) ----
     def map_union(self, n_frames, stream=0):
