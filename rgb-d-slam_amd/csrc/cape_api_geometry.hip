@@ -347,12 +347,7 @@ int cape_match_polygons_wide(cape_handle h, int32_t n_frames, const double* prev
     p.segCur = W.match + 2 * B * WP;
     p.areas = keepAreas ? W.areas.get() : nullptr;
     p.kept = W.kept;
-    p.counts = reinterpret_cast<unsigned*>(W.work + lay.counts);
-    p.frameRange = reinterpret_cast<uint2*>(W.work + lay.ranges);
-    p.work = reinterpret_cast<unsigned long long*>(W.work + lay.work);
-    p.workArea = reinterpret_cast<double*>(W.work + lay.area);
-    p.tierLists = reinterpret_cast<unsigned*>(W.work + lay.tiers);
-    p.workCapacity = cap;
+    p.list = bind_pair_list(W.work, lay, cap);
     p.computeUnits = h->computeUnits;
     p.ldsLimitBytes = h->ldsLimit;
     if (carried)

@@ -106,15 +106,25 @@ inline int device_skip_words(const cape_handle_s* h, int n, const uint32_t* skip
     return CAPE_OK;
 }
 
+// the pair list (PairList, cape_internal.h) in a work buffer: the sections of a matcher's layout, or of the visibility kernels', whose
+// list has neither areas nor ranges
+inline cape::PairList bind_pair_list(unsigned char* work, const MapWorkLayout& lay, size_t cap)
+{
+    return {reinterpret_cast<unsigned long long*>(work + lay.work), reinterpret_cast<double*>(work + lay.area), reinterpret_cast<unsigned*>(work + lay.tiers),
+            reinterpret_cast<unsigned*>(work + lay.counts), reinterpret_cast<uint2*>(work + lay.ranges), cap};
+}
+inline cape::PairList bind_pair_list(unsigned char* work, const VisibilityWorkLayout& lay, size_t cap)
+{
+    return {reinterpret_cast<unsigned long long*>(work + lay.work), nullptr, reinterpret_cast<unsigned*>(work + lay.tiers), reinterpret_cast<unsigned*>(work + lay.counts),
+            nullptr, cap};
+}
+
 // what the visibility kernels read of the handle, for cape_map_visibility and cape_map_step_visible: the front map, the camera, the
 // device, and the sections of the call's work buffer
 inline cape::MapVisibilityParams bind_map_visibility(const cape_handle_s* h, unsigned char* work, const VisibilityWorkLayout& lay, size_t cap)
 {
     cape::MapVisibilityParams p{};
-    p.counts = reinterpret_cast<unsigned*>(work + lay.counts);
-    p.work = reinterpret_cast<unsigned long long*>(work + lay.work);
-    p.tierLists = reinterpret_cast<unsigned*>(work + lay.tiers);
-    p.workCapacity = cap;
+    p.list = bind_pair_list(work, lay, cap);
     p.mapPlanes = h->maps.front.planes;
     p.mapRings = h->maps.front.rings;
     p.mapVertices = reinterpret_cast<const double2*>(h->maps.front.vertices.get());
@@ -287,13 +297,8 @@ template <typename Between> int enqueue_map_match(cape_handle_s* h, const MapMat
     p.match = c.b.match->get();
     p.keptIndex = c.b.kept ? c.b.kept->get() : nullptr;
     p.areas = c.keep_areas() ? c.b.areas->get() : nullptr;
-    p.counts = reinterpret_cast<unsigned*>(work + c.lay.counts);
-    p.frameRange = reinterpret_cast<uint2*>(work + c.lay.ranges);
+    p.list = bind_pair_list(work, c.lay, c.cap);
     p.gateMasks = reinterpret_cast<unsigned long long*>(work + c.lay.masks);
-    p.work = reinterpret_cast<unsigned long long*>(work + c.lay.work);
-    p.workArea = reinterpret_cast<double*>(work + c.lay.area);
-    p.tierLists = reinterpret_cast<unsigned*>(work + c.lay.tiers);
-    p.workCapacity = c.cap;
     p.computeUnits = h->computeUnits;
     p.ldsLimitBytes = h->ldsLimit;
     set_match_thresholds(p, c.flags);

@@ -216,6 +216,22 @@ struct MatchPolygonParams
     const double* poses = nullptr; // cape_match_polygons_pose: frames x 16, row-major [R t; 0 0 0 1] from camera f-1 to camera f; null = identity
 };
 
+// The 64-bit work list of the pair-list kernels (cape_pair_list.h): a gate kernel reserves its entries, persistent waves walk it
+// through the capacity tiers of cape_ring_area.h, a select kernel reads each frame's run.
+// counts, 16 words cleared before the gate kernel: [0..1] entries reserved (64-bit; beyond `capacity` when a frame did not fit),
+// [2..4] entries on the lists of tiers 1..3, [5..7] tickets drawn by the waves of tiers 1..3, [8..9] the undecided pairs of the
+// visibility kernels (64-bit), [10] / [11] the moving and the listed planes of cape_map_step_visible; cape_debug_map_match_lists
+// reads [0..7].
+struct PairList
+{
+    unsigned long long* work; // capacity entries, per frame in (j, i) order: (frame << 32) | (j << 8) | i, or (frame << 32) | j (visibility)
+    double* workArea;         // the area of each entry (null: the visibility list)
+    unsigned* tierLists;      // 3 x capacity: indices into `work` handed to tiers 1..3
+    unsigned* counts;
+    uint2* frameRange;        // frames: (first entry, entries) of the frame's pairs (null: the visibility list)
+    size_t capacity;
+};
+
 // N2 against a persistent map (cape_match_map.hip)
 struct MatchMapParams
 {
@@ -233,14 +249,8 @@ struct MatchMapParams
     cape_frame_map_match* frames;
     int32_t* match;                // frames x nMap
     double* areas;                 // frames x nMap x CAPE_MAX_PLANES, or null (CAPE_MATCH_MAP_AREAS off)
-    unsigned long long* work;      // workCapacity entries (frame << 32) | (j << 8) | i, per frame in (j, i) order
-    double* workArea;              // the area of each entry
-    unsigned* tierLists;           // 3 x workCapacity: indices into `work` handed to tiers 1..3
-    unsigned* counts;              // 16 words: [0..1] entries reserved (64-bit), [2..4] entries on the lists of tiers 1..3,
-                                   // [5..7] tickets drawn by tiers 1..3
-    uint2* frameRange;             // frames: (first entry, entries) of the frame's pairs
+    PairList list;                 // the gated (frame, j, i) triples
     unsigned long long* gateMasks; // frames x nMap: the gated kept planes of each visited map plane with a positive projected area
-    size_t workCapacity;
     int computeUnits;
     int ldsLimitBytes;
     uint32_t flags;
@@ -295,12 +305,7 @@ struct MatchWideParams
     double* areas;                    // frames x CAPE_MATCH_WIDE_MAX_PLANES^2, or null (CAPE_MATCH_MAP_AREAS off)
     uint2* kept;                      // frames x CAPE_MATCH_WIDE_MAX_PLANES, written by the gate kernel: (record index, segment in that record) of
                                       // kept plane k of the frame -- where its polygon row and vertex slab lie
-    unsigned long long* work;         // workCapacity entries (frame << 32) | (j << 8) | i, per frame in (j, i) order
-    double* workArea;                 // the area of each entry
-    unsigned* tierLists;              // 3 x workCapacity: indices into `work` handed to tiers 1..3
-    unsigned* counts;                 // 16 words, as MatchMapParams::counts
-    uint2* frameRange;                // frames: (first entry, entries) of the frame's pairs
-    size_t workCapacity;
+    PairList list;                    // the gated (frame, j, i) triples
     int computeUnits;
     int ldsLimitBytes;
     uint32_t flags;
@@ -331,10 +336,7 @@ struct MapVisibilityParams
     const double* poses;      // frames x 16
     const uint32_t* moving;   // skipWords words, one bit per map plane (null = none)
     uint32_t* skip;           // frames x skipWords: the result
-    unsigned long long* work; // workCapacity = frames x nMap entries (frame << 32) | j, per frame in j order
-    unsigned* tierLists;      // 3 x workCapacity: indices into `work` handed to tiers 1..3
-    unsigned* counts;         // 16 words, [0..7] as MatchMapParams::counts, [8..9] the undecided pairs (64-bit)
-    size_t workCapacity;
+    PairList list;            // capacity = frames x nMap entries (frame << 32) | j, per frame in j order; no areas, no ranges
     int computeUnits;
     int ldsLimitBytes;
     int lastTier;             // the largest tier that runs on this device (set by the launcher)

@@ -1,5 +1,6 @@
-// The map polygon seen from a frame's camera, shared by the map matcher (cape_match_map.hip), the visibility kernels
-// (cape_map_visibility.hip) and -- with the camera-to-world matrix, a detected polygon carried to the world -- the measurement kernel
+// A polygon seen from a frame's camera, shared by the map matcher (cape_match_map.hip), the visibility kernels
+// (cape_map_visibility.hip), the pose path of the consecutive matchers (cape_match_polygon.hip, cape_match_wide.hip: the previous
+// frame's polygon) and -- with the camera-to-world matrix, a detected polygon carried to the world -- the measurement kernel
 // (cape_map_measure.hip): plane_to_camera of the plane, to_camera_space of the polygon's frame and of one ring vertex.  Every file
 // compiles its own copy (anonymous namespace; no device symbol crosses a file).
 #pragma once
@@ -27,11 +28,11 @@ __device__ __forceinline__ void plane_to_camera(const double* T, const double* n
         pn[0] = r0 / nn, pn[1] = r1 / nn, pn[2] = r2 / nn;
 }
 
-// to_camera_space of the map polygon's frame (polygon_coordinates.cpp:135-165): the centre through the transform, the axes through
-// its rotation, re-normalised -- the statements of the pose path of cape_match_polygon.hip
+// to_camera_space of a polygon's frame (polygon_coordinates.cpp:135-165): the centre through the transform, the axes through
+// its rotation, re-normalised
 struct CameraFrame
 {
-    double qc[3], qx[3], qy[3]; // the map polygon's own frame
+    double qc[3], qx[3], qy[3]; // the polygon's own frame
     double nc[3], nx[3], ny[3]; // ... seen from the camera
 };
 __device__ __forceinline__ CameraFrame camera_frame(const double* Tm, const double* center, const double* xAxis, const double* yAxis)

@@ -14,9 +14,9 @@
 //   cape_map_classify_one_kernel: the same decision for ONE frame (cape_map_step_visible), spread over the chip: a workgroup per 64
 //        map planes (two skip words), a wave per plane at a time, the lanes over the ring's vertices (cape_map_step_visible.h has the
 //        ownership rules).  The moving bit comes from the device tracks, not from host words.
-//   cape_map_visible_kernel<TIER>: persistent waves over the work list (tier 0) or a tier's list of indices into it (tiers 1..3),
-//        as cape_map_inter_kernel: the screen ring as ring A, the rectangle as ring B, each oriented like the host class orients an
-//        outer ring.  Area > 0: the bit of the pair is cleared.  A pair beyond every tier's capacities is not decided: it counts as
+//   cape_map_visible_kernel<TIER>: the walk of the list through the capacity tiers (walk_tier, cape_pair_list.h) around one pair's
+//        area: the screen ring as ring A, the rectangle as ring B, each oriented like the host class orients an outer ring
+//        (orient_ring).  Area > 0: the bit of the pair is cleared.  A pair beyond every tier's capacities is not decided: it counts as
 //        visible (a plane visited in vain costs work, a plane skipped in vain loses a match) and is counted.
 //
 // + - x / and comparisons only, in the order of the host twin cape_host_map_visibility (-ffp-contract=off): the words are compared
@@ -26,6 +26,7 @@
 #include "cape_internal.h"
 #include "cape_map_camera.h"
 #include "cape_map_step_visible.h"
+#include "cape_pair_list.h"
 #include "cape_ring_area.h"
 #include "cape_wave.h"
 
@@ -170,30 +171,15 @@ __global__ __launch_bounds__(64 * kVisFrames) void cape_map_classify_kernel(MapV
             myCount += (unsigned)__popcll(l);
         }
     }
-    if (lane == 0)
-        s_count[wave] = myCount;
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        unsigned total = 0;
-        for (int w = 0; w < kVisFrames; ++w)
-        {
-            const unsigned c = s_count[w];
-            s_count[w] = total;
-            total += c;
-        }
-        s_base = total ? atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)total) : 0ull;
-    }
-    __syncthreads();
+    // (the list holds frames x n_map entries: every pair fits)
+    unsigned long long at = reserve_pairs<kVisFrames>(p.list, s_count, s_base, myCount);
     if (!live)
         return;
-    // (the list holds frames x n_map entries: every pair fits)
-    unsigned long long at = s_base + s_count[wave];
     for (int jb = 0; jb < p.nMap; jb += 64)
     {
         const unsigned long long l = s_listed[wave][jb >> 6];
         if ((l >> lane) & 1ull)
-            p.work[at + (unsigned)__popcll(l & ((1ull << lane) - 1ull))] = ((unsigned long long)(unsigned)frame << 32) | (unsigned)(jb + lane);
+            p.list.work[at + (unsigned)__popcll(l & ((1ull << lane) - 1ull))] = ((unsigned long long)(unsigned)frame << 32) | (unsigned)(jb + lane);
         at += (unsigned)__popcll(l);
     }
 }
@@ -240,129 +226,60 @@ __global__ __launch_bounds__(64 * kStepVisGroupWaves) void cape_map_classify_one
         step_vis_store_words(p.skip, p.skipWords, group, step_vis_present(group, p.nMap));
         if (listed)
         {
-            base = atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)__popcll(listed));
-            atomicAdd(&p.counts[11], (unsigned)__popcll(listed));
+            base = atomicAdd(reinterpret_cast<unsigned long long*>(p.list.counts), (unsigned long long)__popcll(listed));
+            atomicAdd(&p.list.counts[11], (unsigned)__popcll(listed));
         }
         if (moving)
-            atomicAdd(&p.counts[10], (unsigned)__popcll(moving));
+            atomicAdd(&p.list.counts[10], (unsigned)__popcll(moving));
     }
     base = readlane_u64(base, 0);
     // (the list holds n_map entries: every plane fits)
     if ((listed >> lane) & 1ull)
-        p.work[base + (unsigned)__popcll(listed & ((1ull << lane) - 1ull))] = (unsigned long long)(unsigned)(group * kStepVisGroupPlanes + lane);
+        p.list.work[base + (unsigned)__popcll(listed & ((1ull << lane) - 1ull))] = (unsigned long long)(unsigned)(group * kStepVisGroupPlanes + lane);
 }
 
-// A pair beyond this tier's capacities moves to the next tier's list when that one is larger in the resource that ran out (and
-// runs on this device: lastTier); otherwise it is undecided.
+// One tier of the list's walk (walk_tier, cape_pair_list.h; p.lastTier: the largest tier that runs on this device).  A pair beyond
+// the capacities of every tier that runs is undecided.
 template <int TIER> __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_visible_kernel(MapVisibilityParams p, int ldsPerWave)
 {
     using T = Tier<TIER>;
-    constexpr bool kHasNext = TIER + 1 < kTiers;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr bool kCoop = T::kCoop;
-    const int tid = kCoop ? (int)threadIdx.x : lane;
-    constexpr int kStride = kCoop ? 256 : 64;
-    unsigned char* smem = smem_all + (kCoop ? (size_t)0 : (size_t)wave * ldsPerWave);
-    const MpLds L = mp_carve<TIER>(smem);
-    const size_t cap = p.workCapacity;
-    const unsigned long long reserved = *reinterpret_cast<const unsigned long long*>(p.counts);
-    const unsigned long long count = TIER == 0 ? (reserved < cap ? reserved : cap) : (unsigned long long)p.counts[1 + TIER];
-    const unsigned* list = TIER == 0 ? nullptr : p.tierLists + (size_t)(TIER - 1) * cap;
-    // tier 0: a fixed stride over the (many, short) pairs; the later tiers draw tickets (few pairs of very unequal cost)
-    auto next_index = [&](unsigned long long prev, bool first) -> unsigned long long {
-        if (kCoop)
-        {
-            if (threadIdx.x == 0)
-                L.sh[7] = (int)(TIER > 0 ? atomicAdd(&p.counts[4 + TIER], 1u) : (unsigned)(first ? blockIdx.x : prev + gridDim.x));
-            __syncthreads();
-            const unsigned t = (unsigned)L.sh[7];
-            __syncthreads();
-            return t;
-        }
-        if (TIER == 0)
-            return first ? (unsigned long long)blockIdx.x * T::kWavesPerGroup + wave : prev + (unsigned long long)gridDim.x * T::kWavesPerGroup;
-        unsigned t = 0;
-        if (lane == 0)
-            t = atomicAdd(&p.counts[4 + TIER], 1u);
-        return (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-    };
-    auto sync = [&]() {
-        if (kCoop)
-            __syncthreads();
-        else
-            CAPE_MP_SYNC();
-    };
-    // the orientation the host class gives an outer ring (OpenRing constructor): reversed when its signed area is positive
-    // (every lane reads the whole ring before any lane of the carve rewrites it)
-    auto orient = [&](double2* ring, int n) {
-        const double s = ring_area_signed(ring, n);
-        sync();
-        if (s > 0)
-        {
-            for (int v = tid; v < n / 2; v += kStride)
-            {
-                const double2 a = ring[v], b = ring[n - 1 - v];
-                ring[v] = b;
-                ring[n - 1 - v] = a;
-            }
-            sync();
-        }
-    };
-    for (unsigned long long t = next_index(0ull, true); t < count; t = next_index(t, false))
-    {
-        const size_t idx = TIER == 0 ? (size_t)t : (size_t)list[t];
-        const unsigned long long e = p.work[idx];
-        const int frame = (int)(e >> 32), j = (int)(e & 0xFFFFFFFFu);
-        const cape_map_plane& M = p.mapPlanes[j];
-        const cape_map_ring R = p.mapRings[M.ring_first];
-        const int na = (int)R.vertex_count;
-        double result;
-        if (na > T::kRing)
-            result = nan_code(kNanRing);
-        else
-        {
+    walk_tier<TIER>(
+        p.list, ldsPerWave, p.lastTier,
+        [&](const TierCtx<TIER>& ctx, unsigned long long e) -> double {
+            const MpLds& L = ctx.L;
+            const int frame = (int)(e >> 32), j = (int)(e & 0xFFFFFFFFu);
+            const cape_map_plane& M = p.mapPlanes[j];
+            const cape_map_ring R = p.mapRings[M.ring_first];
+            const int na = (int)R.vertex_count;
+            if (na > T::kRing)
+                return nan_code(kNanRing);
             const double* Tm = p.poses + (size_t)frame * 16;
             const CameraFrame F = camera_frame(Tm, M);
             // the outer ring seen from the camera (transform_boundary, polygon.cpp:430-451), oriented as the CameraPolygon holds it ...
             const double2* src = p.mapVertices + R.vertex_offset;
-            for (int v = tid; v < na; v += kStride)
+            for (int v = ctx.tid; v < na; v += ctx.kStride)
                 L.ringA[v] = to_camera_vertex(Tm, F, src[v]);
-            sync();
-            orient(L.ringA, na);
+            ctx.sync();
+            orient_ring(L.ringA, na, false, ctx);
             // ... on the screen, oriented again (boost::geometry::correct in to_screen_space)
-            for (int v = tid; v < na; v += kStride)
+            for (int v = ctx.tid; v < na; v += ctx.kStride)
                 L.ringA[v] = screen_vertex(p, F, L.ringA[v]);
             // the screen rectangle (utils/polygon.cpp:27-37)
-            if (tid < 4)
-                L.ringB[tid] = make_double2((tid == 1 || tid == 2) ? p.width - 1.0 : 1.0, tid >= 2 ? p.height - 1.0 : 1.0);
-            sync();
-            orient(L.ringA, na);
-            orient(L.ringB, 4);
-            if constexpr (kCoop)
-                result = rings_inter_area_coop<T::kStack, T::kXs>(L, na, 4, tid);
-            else
-                result = rings_inter_area<T::kStack, T::kXs>(L, na, 4, lane);
-            sync();
-        }
-        if (tid == 0)
-        {
-            const bool stack = is_nan_code(result, kNanStack), slabs = is_nan_code(result, kNanSlabs), ring = is_nan_code(result, kNanRing);
-            bool again = false;
-            if (kHasNext && TIER + 1 <= p.lastTier)
-                again = (stack && later_stack<TIER>() > T::kStack) || (slabs && later_xs<TIER>() > T::kXs) || (ring && later_ring<TIER>() > T::kRing);
-            if (again)
-                p.tierLists[(size_t)TIER * cap + atomicAdd(&p.counts[2 + TIER], 1u)] = (unsigned)idx; // (an entry visits each tier once)
-            else
-            {
-                const bool undecided = stack || slabs || ring;
-                if (result > 0 || undecided)
-                    atomicAnd(&p.skip[(size_t)frame * p.skipWords + (j >> 5)], ~(1u << (j & 31)));
-                if (undecided)
-                    atomicAdd(reinterpret_cast<unsigned long long*>(p.counts + 8), 1ull);
-            }
-        }
-    }
+            if (ctx.tid < 4)
+                L.ringB[ctx.tid] = make_double2((ctx.tid == 1 || ctx.tid == 2) ? p.width - 1.0 : 1.0, ctx.tid >= 2 ? p.height - 1.0 : 1.0);
+            ctx.sync();
+            orient_ring(L.ringA, na, false, ctx);
+            orient_ring(L.ringB, 4, false, ctx);
+            return ctx.inter_area(na, 4);
+        },
+        [&](size_t, unsigned long long e, double result) {
+            const int frame = (int)(e >> 32), j = (int)(e & 0xFFFFFFFFu);
+            const bool undecided = is_nan_code(result, kNanStack) || is_nan_code(result, kNanSlabs) || is_nan_code(result, kNanRing);
+            if (result > 0 || undecided)
+                atomicAnd(&p.skip[(size_t)frame * p.skipWords + (j >> 5)], ~(1u << (j & 31)));
+            if (undecided)
+                atomicAdd(reinterpret_cast<unsigned long long*>(p.list.counts + 8), 1ull);
+        });
 }
 
 namespace {
@@ -370,21 +287,15 @@ namespace {
 // the visible kernels behind either classify kernel
 hipError_t launch_visible_tiers(const MapVisibilityParams& p, hipStream_t stream)
 {
-    // persistent grids: as many workgroups as the chip holds at once (the list's length is only known on the device)
-    const int cus = p.computeUnits > 0 ? p.computeUnits : 256;
-    auto launch = [&](auto kernel, int lds, int wavesPerGroup, bool coop, int groupsPerCu) {
-        hipLaunchKernelGGL(kernel, dim3(cus * groupsPerCu), dim3(64 * wavesPerGroup), (size_t)lds * (coop ? 1 : wavesPerGroup), stream, p, lds);
-        return hipGetLastError();
-    };
-    if (const hipError_t e = launch(cape_map_visible_kernel<0>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch_tier<0>(cape_map_visible_kernel<0>, p, stream); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_visible_kernel<1>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch_tier<1>(cape_map_visible_kernel<1>, p, stream); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_visible_kernel<2>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch_tier<2>(cape_map_visible_kernel<2>, p, stream); e != hipSuccess)
         return e;
     // (a device without the LDS for the largest tier: lastTier = 2, the pairs it would take are undecided)
     if (p.lastTier >= 3)
-        return launch(cape_map_visible_kernel<3>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu);
+        return launch_tier<3>(cape_map_visible_kernel<3>, p, stream);
     return hipSuccess;
 }
 
@@ -394,7 +305,7 @@ hipError_t launch_map_visibility(const MapVisibilityParams& params, int nFrames,
 {
     MapVisibilityParams p = params;
     p.lastTier = tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes ? 3 : 2;
-    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
+    if (const hipError_t e = hipMemsetAsync(p.list.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(cape_map_classify_kernel, dim3((nFrames + kVisFrames - 1) / kVisFrames), dim3(64 * kVisFrames), 0, stream, p, nFrames);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)
@@ -407,7 +318,7 @@ hipError_t launch_map_step_visibility(const MapVisibilityParams& params, const M
 {
     MapVisibilityParams p = params;
     p.lastTier = tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes ? 3 : 2;
-    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
+    if (const hipError_t e = hipMemsetAsync(p.list.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
         return e;
     hipLaunchKernelGGL(cape_map_classify_one_kernel, dim3(step_vis_groups(p.nMap)), dim3(64 * kStepVisGroupWaves), 0, stream, p, tracks);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)

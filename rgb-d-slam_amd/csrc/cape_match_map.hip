@@ -9,9 +9,10 @@
 //        (plane_coordinates.cpp:20-24), the gates is_distance_similar / is_normal_similar (shape_primitives.cpp:66-86) against
 //        every kept plane i of the frame; for a map plane with a gated pair, the area of its polygon seen from the camera
 //        (to_camera_space, polygon_coordinates.cpp:135-165, holes included) -- <= 0: it matches nothing and lists no pair --
-//        and the work list of the gated (frame, j, i) triples, per frame in (j, i) order.
-//   cape_map_inter_kernel<TIER>  : persistent waves over the work list, one triple at a time: every ring of the map polygon goes
-//        through to_camera_space and is projected into the detected plane's frame (Polygon::project) and
+//        and the work list of the gated (frame, j, i) triples, per frame in (j, i) order (reserve_pairs, cape_pair_list.h).
+//   cape_map_inter_kernel<TIER>  : the walk of the list through the capacity tiers (walk_tier, cape_pair_list.h) around one triple's
+//        area: every ring of the map polygon goes through to_camera_space (cape_map_camera.h) and is projected into the detected
+//        plane's frame (project_ring_b) and oriented (orient_ring), and
 //        inter = I(detected, outer) - I(detected, hole_k) in order, clamped at 0 -- Polygon::inter_area of the host class
 //        (host/boundary_polygon.cpp: polygons_inter_area).  The capacity tiers and the intersection are cape_ring_area.h's.
 //   cape_map_select_kernel       : one wavefront per frame: map plane after map plane in order, lanes over the gated pairs of
@@ -30,8 +31,7 @@
 //        cape_chain_walk.h), a lane holds kept planes k and k + 64; lanes over the map planes, 64 at a time, both gates on all
 //        n_map x n_cur pairs as a 128-bit mask per map plane, the projected polygon measured once per map plane with a gated pair,
 //        the triples appended in (j, i) order with one atomic per workgroup.
-//   cape_map_select_wide_kernel  : cape_map_select_kernel with runs of up to 128 gated pairs (two candidates per lane) and a
-//        128-bit is-matched mask.
+//   cape_map_select_wide_kernel  : cape_map_select_kernel with runs of up to 128 gated pairs (select_wide, cape_pair_list.h).
 //
 // The intersection kernel is the same for the three: only the accessor differs.
 //
@@ -43,6 +43,7 @@
 #include "cape_internal.h"
 #include "cape_layout.h"
 #include "cape_map_camera.h"
+#include "cape_pair_list.h"
 #include "cape_ring_area.h"
 #include "cape_wave.h"
 
@@ -52,7 +53,6 @@ namespace {
 
 constexpr int kMapGateFrames = 4;   // frames (waves) of a gate workgroup
 constexpr int kMapSelectFrames = 4; // frames (waves) of a select workgroup
-constexpr unsigned long long kNoEntry = ~0ull; // a slot of the work list reserved by a frame that did not fit
 constexpr int WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
 static_assert(WP == 2 * 64, "a lane holds kept planes k and k + 64");
 // a triple is (frame << 32) | (j << 8) | i: i takes 8 bits, j the 24 above them
@@ -67,11 +67,6 @@ enum MapSource
 };
 // kept planes a frame of the source holds at most = entries per map plane of the dense area table
 template <MapSource kSource> constexpr int kSourcePlanes = kSource == kFromChain ? WP : CAPE_MAX_PLANES;
-
-__device__ __forceinline__ unsigned long long pack_map_pair(int frame, int j, int i)
-{
-    return ((unsigned long long)(unsigned)frame << 32) | ((unsigned long long)(unsigned)j << 8) | (unsigned long long)(unsigned)i;
-}
 
 // map plane j seen from the frame's camera (plane_to_camera of cape_map_camera.h)
 __device__ __forceinline__ void plane_to_camera(const double* T, const cape_map_plane& M, double pn[3], double& pd)
@@ -155,7 +150,7 @@ template <MapSource kSource> __device__ __forceinline__ DetectedPolygon detected
 __device__ __forceinline__ void gate_kept_planes(const MatchMapParams& p, int frame, bool live, int nCur, bool fits, uint32_t flagged, int seg,
                                                  double cn0, double cn1, double cn2, double cd, unsigned* s_count, unsigned long long& s_base)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     cape_frame_map_match& out = p.frames[frame];
     const double* T = p.poses + (size_t)frame * 16;
     const uint32_t* skip = p.skip ? p.skip + (size_t)frame * p.skipWords : nullptr;
@@ -189,41 +184,19 @@ __device__ __forceinline__ void gate_kept_planes(const MatchMapParams& p, int fr
             masks[j] = m;
         myCount += (unsigned)wave_sum_i32(__popcll(m));
     }
-    if (lane == 0)
-        s_count[wave] = live ? myCount : 0u;
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        unsigned total = 0;
-        for (int w = 0; w < kMapGateFrames; ++w)
-        {
-            const unsigned c = s_count[w];
-            s_count[w] = total;
-            total += c;
-        }
-        s_base = total ? atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)total) : 0ull;
-    }
-    __syncthreads();
+    const unsigned long long first = reserve_pairs<kMapGateFrames>(p.list, s_count, s_base, live ? myCount : 0u);
     if (!live)
         return;
-    const unsigned long long first = s_base + s_count[wave];
-    const bool listed = first + myCount <= p.workCapacity;
+    const bool listed = claim_frame(p.list, frame, first, myCount);
     if (lane == 0)
     {
         out.n_map = p.nMap;
         out.n_cur = nCur;
         out.flags = (fits && listed) ? 0u : flagged | (uint32_t)CAPE_MATCH_EXACT_OVERFLOW;
         out.n_matched = 0;
-        p.frameRange[frame] = make_uint2((unsigned)(listed ? first : 0ull), listed ? myCount : 0u);
     }
     out.seg_cur[lane] = lane < nCur ? seg : -1;
     out.map_of[lane] = -1;
-    if (!listed)
-    {
-        // the slots the frame reserved inside the list are marked empty: the intersection kernel skips them
-        for (unsigned long long k = first + lane; k < first + myCount && k < p.workCapacity; k += 64)
-            p.work[k] = kNoEntry;
-    }
     unsigned long long at = first;
     for (int jb = 0; jb < p.nMap; jb += 64)
     {
@@ -238,8 +211,8 @@ __device__ __forceinline__ void gate_kept_planes(const MatchMapParams& p, int fr
             unsigned long long w = at + (unsigned)(incl - c);
             for (unsigned long long mm = m; mm; mm &= mm - 1, ++w)
             {
-                p.work[w] = pack_map_pair(frame, j, __ffsll((long long)mm) - 1);
-                p.workArea[w] = nan_code(kNanPending);
+                p.list.work[w] = pack_pair64(frame, j, __ffsll((long long)mm) - 1);
+                p.list.workArea[w] = nan_code(kNanPending);
             }
         }
         at += (unsigned)__builtin_amdgcn_readlane(incl, 63);
@@ -466,25 +439,10 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_wide_kernel
         myCount += (unsigned)wave_sum_i32(__popcll(m0) + __popcll(m1));
     }
     // ONE atomic per workgroup on the list's counter reserves the slots of its frames
-    if (lane == 0)
-        s_count[wave] = live ? myCount : 0u;
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        unsigned total = 0;
-        for (int w = 0; w < kMapGateFrames; ++w)
-        {
-            const unsigned c = s_count[w];
-            s_count[w] = total;
-            total += c;
-        }
-        s_base = total ? atomicAdd(reinterpret_cast<unsigned long long*>(p.counts), (unsigned long long)total) : 0ull;
-    }
-    __syncthreads();
+    const unsigned long long first = reserve_pairs<kMapGateFrames>(p.list, s_count, s_base, live ? myCount : 0u);
     if (!live)
         return;
-    const unsigned long long first = s_base + s_count[wave];
-    const bool listed = first + myCount <= p.workCapacity;
+    const bool listed = claim_frame(p.list, frame, first, myCount);
     if (lane == 0)
     {
         cape_frame_map_match_wide& out = p.framesWide[frame];
@@ -492,13 +450,6 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_wide_kernel
         out.n_cur = nCurAll;
         out.flags = (fits && listed) ? 0u : (uint32_t)CAPE_MATCH_EXACT_OVERFLOW;
         out.n_matched = 0;
-        p.frameRange[frame] = make_uint2((unsigned)(listed ? first : 0ull), listed ? myCount : 0u);
-    }
-    if (!listed)
-    {
-        // the slots the frame reserved inside the list are marked empty: the intersection kernel skips them
-        for (unsigned long long k = first + lane; k < first + myCount && k < p.workCapacity; k += 64)
-            p.work[k] = kNoEntry;
     }
     unsigned long long at = first;
     for (int jb = 0; jb < p.nMap; jb += 64)
@@ -514,13 +465,13 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_wide_kernel
             unsigned long long w = at + (unsigned)(incl - c);
             for (unsigned long long mm = m0; mm; mm &= mm - 1, ++w)
             {
-                p.work[w] = pack_map_pair(frame, j, __ffsll((long long)mm) - 1);
-                p.workArea[w] = nan_code(kNanPending);
+                p.list.work[w] = pack_pair64(frame, j, __ffsll((long long)mm) - 1);
+                p.list.workArea[w] = nan_code(kNanPending);
             }
             for (unsigned long long mm = m1; mm; mm &= mm - 1, ++w)
             {
-                p.work[w] = pack_map_pair(frame, j, 64 + __ffsll((long long)mm) - 1);
-                p.workArea[w] = nan_code(kNanPending);
+                p.list.work[w] = pack_pair64(frame, j, 64 + __ffsll((long long)mm) - 1);
+                p.list.workArea[w] = nan_code(kNanPending);
             }
         }
         at += (unsigned)__builtin_amdgcn_readlane(incl, 63);
@@ -540,168 +491,65 @@ __global__ __launch_bounds__(64 * kMapGateFrames) void cape_map_gate_wide_kernel
     }
 }
 
-// Persistent waves over the work list (tier 0) or a tier's list of indices into it (tiers 1..3).  A triple beyond this tier's
-// capacities moves to the next tier's list when that one is larger in the resource that ran out; otherwise its area stays a NaN
-// that names the resource.
+// One tier of the list's walk (walk_tier, cape_pair_list.h).  A triple beyond every tier's capacities keeps a NaN that names the
+// resource: its frame is flagged by the select kernel.
 template <int TIER, MapSource kSource>
 __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_map_inter_kernel(MatchMapParams p, int ldsPerWave)
 {
     using T = Tier<TIER>;
-    constexpr bool kHasNext = TIER + 1 < kTiers;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr bool kCoop = T::kCoop;
-    const int tid = kCoop ? (int)threadIdx.x : lane;
-    constexpr int kStride = kCoop ? 256 : 64;
-    unsigned char* smem = smem_all + (kCoop ? (size_t)0 : (size_t)wave * ldsPerWave);
-    const MpLds L = mp_carve<TIER>(smem);
-    const size_t cap = p.workCapacity;
-    const unsigned long long reserved = *reinterpret_cast<const unsigned long long*>(p.counts);
-    const unsigned long long count = TIER == 0 ? (reserved < cap ? reserved : cap) : (unsigned long long)p.counts[1 + TIER];
-    const unsigned* list = TIER == 0 ? nullptr : p.tierLists + (size_t)(TIER - 1) * cap;
-    // tier 0: a fixed stride over the (many, short) triples; the later tiers draw tickets (few triples of very unequal cost)
-    auto next_index = [&](unsigned long long prev, bool first) -> unsigned long long {
-        if (kCoop)
-        {
-            if (threadIdx.x == 0)
-                L.sh[7] = (int)(TIER > 0 ? atomicAdd(&p.counts[4 + TIER], 1u) : (unsigned)(first ? blockIdx.x : prev + gridDim.x));
-            __syncthreads();
-            const unsigned t = (unsigned)L.sh[7];
-            __syncthreads();
-            return t;
-        }
-        if (TIER == 0)
-            return first ? (unsigned long long)blockIdx.x * T::kWavesPerGroup + wave : prev + (unsigned long long)gridDim.x * T::kWavesPerGroup;
-        unsigned t = 0;
-        if (lane == 0)
-            t = atomicAdd(&p.counts[4 + TIER], 1u);
-        return (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-    };
-    auto sync = [&]() {
-        if (kCoop)
-            __syncthreads();
-        else
-            CAPE_MP_SYNC();
-    };
-    for (unsigned long long t = next_index(0ull, true); t < count; t = next_index(t, false))
-    {
-        const size_t idx = TIER == 0 ? (size_t)t : (size_t)list[t];
-        const unsigned long long e = p.work[idx];
-        if (e == kNoEntry)
-            continue;
-        const int frame = (int)(e >> 32), j = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
-        const DetectedPolygon D = detected_polygon<kSource>(p, frame, i);
-        const cape_polygon& PS = *D.polygon; // detected polygon
-        const cape_map_plane& M = p.mapPlanes[j];
-        const int na = (int)PS.vertex_count, nRings = (int)M.ring_count;
-        int nbMax = 0;
-        for (int k = 0; k < nRings; ++k)
-        {
-            const int nb = (int)p.mapRings[M.ring_first + k].vertex_count;
-            nbMax = nb > nbMax ? nb : nbMax;
-        }
-        double result;
-        if (na > T::kRing || nbMax > T::kRing)
-            result = nan_code(kNanRing);
-        else
-        {
+    walk_tier<TIER>(
+        p.list, ldsPerWave, kTiers - 1,
+        [&](const TierCtx<TIER>& ctx, unsigned long long e) -> double {
+            const MpLds& L = ctx.L;
+            const int frame = (int)(e >> 32), j = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
+            const DetectedPolygon D = detected_polygon<kSource>(p, frame, i);
+            const cape_polygon& PS = *D.polygon; // detected polygon
+            const cape_map_plane& M = p.mapPlanes[j];
+            const int na = (int)PS.vertex_count, nRings = (int)M.ring_count;
+            int nbMax = 0;
+            for (int k = 0; k < nRings; ++k)
+            {
+                const int nb = (int)p.mapRings[M.ring_first + k].vertex_count;
+                nbMax = nb > nbMax ? nb : nbMax;
+            }
+            if (na > T::kRing || nbMax > T::kRing)
+                return nan_code(kNanRing);
             const double2* vertsC = D.ring();
-            for (int v = tid; v < na; v += kStride)
+            for (int v = ctx.tid; v < na; v += ctx.kStride)
                 L.ringA[v] = vertsC[v];
-            // to_camera_space (polygon_coordinates.cpp:135-165): the centre through the transform, the axes through its rotation,
-            // re-normalised -- the statements of the pose path of cape_match_polygon.hip
             const double* Tm = p.poses + (size_t)frame * 16;
-            const CameraFrame F = camera_frame(Tm, M);
-            const double* nc = F.nc;
-            const double* nx = F.nx;
-            const double* ny = F.ny;
-            // a ring in reverse order (lane v swaps v and n - 1 - v)
-            auto reverse_b = [&](int n) {
-                for (int v = tid; v < n / 2; v += kStride)
-                {
-                    const double2 a = L.ringB[v], b = L.ringB[n - 1 - v];
-                    L.ringB[v] = b;
-                    L.ringB[n - 1 - v] = a;
-                }
-                sync();
-            };
-            // the orientation the host class gives a ring: the outer one clockwise (OpenRing constructor), holes counter-clockwise
-            // (add_hole)
-            // (every lane reads the whole ring before any lane of the carve rewrites it)
-            auto orient_b = [&](int n, bool hole) {
-                const double s = ring_area_signed(L.ringB, n);
-                sync();
-                if (hole ? s < 0 : s > 0)
-                    reverse_b(n);
-            };
-            // ring k of the map polygon into L.ringB, seen from the camera (transform_boundary, polygon.cpp:430-451), oriented
-            auto to_camera = [&](int k) {
+            const CameraFrame F = camera_frame(Tm, M); // to_camera_space (polygon_coordinates.cpp:135-165)
+            // (the projected polygon's area was found positive by the gate kernel: only such map planes list pairs)
+            double acc = 0.0, result = 0.0;
+            for (int k = 0; k < nRings; ++k)
+            {
+                // ring k of the map polygon into ring B, seen from the camera (transform_boundary, polygon.cpp:430-451), in the
+                // orientation the host class gives it: the outer one clockwise (OpenRing constructor), holes counter-clockwise (add_hole)
                 const cape_map_ring R = p.mapRings[M.ring_first + k];
                 const double2* src = p.mapVertices + R.vertex_offset;
                 const int nb = (int)R.vertex_count;
-                for (int v = tid; v < nb; v += kStride)
+                for (int v = ctx.tid; v < nb; v += ctx.kStride)
                     L.ringB[v] = to_camera_vertex(Tm, F, src[v]);
-                sync();
-                orient_b(nb, k > 0);
-            };
-            // the camera-space ring in L.ringB projected into the detected plane's frame (Polygon::project, polygon.cpp:338-382), oriented
-            auto project = [&](int k) {
-                const int nb = (int)p.mapRings[M.ring_first + k].vertex_count;
-                for (int v = tid; v < nb; v += kStride)
-                {
-                    const double2 q = L.ringB[v];
-                    const double X = nc[0] + q.x * nx[0] + q.y * ny[0];
-                    const double Y = nc[1] + q.x * nx[1] + q.y * ny[1];
-                    const double Z = nc[2] + q.x * nx[2] + q.y * ny[2];
-                    const double dx = X - PS.center[0], dy = Y - PS.center[1], dz = Z - PS.center[2];
-                    L.ringB[v] = make_double2((PS.x_axis[0] * dx + PS.x_axis[1] * dy) + PS.x_axis[2] * dz,
-                                              (PS.y_axis[0] * dx + PS.y_axis[1] * dy) + PS.y_axis[2] * dz);
-                }
-                sync();
-                orient_b(nb, k > 0);
-                return nb;
-            };
-            auto inter = [&](int nb) -> double {
-                double r;
-                if constexpr (kCoop)
-                    r = rings_inter_area_coop<T::kStack, T::kXs>(L, na, nb, tid);
-                else
-                    r = rings_inter_area<T::kStack, T::kXs>(L, na, nb, lane);
-                sync();
-                return r;
-            };
-            // (the projected polygon's area was found positive by the gate kernel: only such map planes list pairs)
-            double acc = 0.0;
-            result = 0.0;
-            for (int k = 0; k < nRings; ++k)
-            {
-                to_camera(k);
-                const double r = inter(project(k));
+                ctx.sync();
+                orient_ring(L.ringB, nb, k > 0, ctx);
+                // ... projected into the detected plane's frame (Polygon::project, polygon.cpp:338-382), oriented again
+                project_ring_b(ctx, L.ringB, nb, F.nc, F.nx, F.ny, PS);
+                ctx.sync();
+                orient_ring(L.ringB, nb, k > 0, ctx);
+                const double r = ctx.inter_area(na, nb);
                 if (r != r)
-                {
-                    result = r;
-                    break;
-                }
+                    return r;
                 acc = k == 0 ? r : acc - r; // polygons_inter_area: I(A, B) - I(A, hole_k) in order
                 result = acc < 0 ? 0.0 : acc;
             }
-        }
-        if (tid == 0)
-        {
-            bool again = false;
-            if (kHasNext)
-                again = (is_nan_code(result, kNanStack) && later_stack<TIER>() > T::kStack) || (is_nan_code(result, kNanSlabs) && later_xs<TIER>() > T::kXs) ||
-                        (is_nan_code(result, kNanRing) && later_ring<TIER>() > T::kRing);
-            if (again)
-                p.tierLists[(size_t)TIER * cap + atomicAdd(&p.counts[2 + TIER], 1u)] = (unsigned)idx; // (an entry visits each tier once)
-            else
-            {
-                p.workArea[idx] = result;
-                if (p.areas)
-                    p.areas[((size_t)frame * p.nMap + j) * kSourcePlanes<kSource> + i] = result;
-            }
-        }
-    }
+            return result;
+        },
+        [&](size_t idx, unsigned long long e, double result) {
+            const int frame = (int)(e >> 32), j = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
+            p.list.workArea[idx] = result;
+            if (p.areas)
+                p.areas[((size_t)frame * p.nMap + j) * kSourcePlanes<kSource> + i] = result;
+        });
 }
 
 // One wavefront per frame: the map planes in order, each with the contiguous run of its gated pairs (one run fits the wave: at
@@ -717,12 +565,12 @@ template <MapSource kSource> __global__ __launch_bounds__(64 * kMapSelectFrames)
         return; // nothing was intersected
     const int nc = out.n_cur;
     const double myArea = lane < nc ? detected_polygon<kSource>(p, frame, lane).polygon->area : 0.0; // detectedPolygon.get_area()
-    const uint2 range = p.frameRange[frame];
+    const uint2 range = p.list.frameRange[frame];
     const unsigned begin = range.x, end = range.x + range.y;
     // a pair beyond the intersection kernel's capacities: no match is reported for the frame
     bool nan = false;
     for (unsigned k = begin + lane; k < end; k += 64)
-        nan |= p.workArea[k] != p.workArea[k];
+        nan |= p.list.workArea[k] != p.list.workArea[k];
     if (__any(nan))
     {
         if (lane == 0)
@@ -735,8 +583,8 @@ template <MapSource kSource> __global__ __launch_bounds__(64 * kMapSelectFrames)
     {
         const unsigned k = at + lane;
         const bool valid = k < end;
-        const unsigned long long e = valid ? p.work[k] : 0ull;
-        const double ia = valid ? p.workArea[k] : -1.0;
+        const unsigned long long e = valid ? p.list.work[k] : 0ull;
+        const double ia = valid ? p.list.workArea[k] : -1.0;
         const int jl = (int)((e >> 8) & 0xFFFFFFu), i = (int)(e & 255u);
         const int j = __builtin_amdgcn_readfirstlane(jl);
         const bool mine = valid && jl == j;
@@ -767,91 +615,23 @@ template <MapSource kSource> __global__ __launch_bounds__(64 * kMapSelectFrames)
     out.map_of[lane] = myMapOf;
 }
 
-// The select kernel of the chain source, one wavefront per frame: the map planes in order, each with the contiguous run of its gated
-// pairs (at most WP of them: two candidates per lane, at list positions at + lane and at + lane + 64).
+// The select kernel of the chain source, one wavefront per frame (select_wide, cape_pair_list.h): the map planes in order; which
+// map plane took a kept plane goes to the frame's row of mapOf.
 __global__ __launch_bounds__(64 * kMapSelectFrames) void cape_map_select_wide_kernel(MatchMapParams p, int nFrames)
 {
-    const int lane = threadIdx.x & 63;
     const int frame = blockIdx.x * kMapSelectFrames + (threadIdx.x >> 6);
     if (frame >= nFrames)
         return;
-    cape_frame_map_match_wide& out = p.framesWide[frame];
-    if (out.flags & CAPE_MATCH_EXACT_OVERFLOW)
-        return; // nothing was intersected
-    const int nc = out.n_cur; // (<= WP: the frame is not flagged)
-    // detectedPolygon.get_area() of my two planes
-    const double curArea0 = lane < nc ? detected_polygon<kFromChain>(p, frame, lane).polygon->area : 0.0;
-    const double curArea1 = lane + 64 < nc ? detected_polygon<kFromChain>(p, frame, lane + 64).polygon->area : 0.0;
-    const uint2 range = p.frameRange[frame];
-    const unsigned begin = range.x, end = range.x + range.y;
-    // a pair beyond the intersection kernel's capacities: no match is reported for the frame
-    bool nan = false;
-    for (unsigned k = begin + lane; k < end; k += 64)
-        nan |= p.workArea[k] != p.workArea[k];
-    if (__any(nan))
-    {
-        if (lane == 0)
-            out.flags |= CAPE_MATCH_EXACT_OVERFLOW;
-        return;
-    }
-    unsigned long long takenLo = 0ull, takenHi = 0ull; // is-matched flags of the detected planes
-    int myMapOf0 = -1, myMapOf1 = -1, nMatched = 0;
-    for (unsigned at = begin; at < end;)
-    {
-        const unsigned k0 = at + lane, k1 = k0 + 64;
-        const bool valid0 = k0 < end, valid1 = k1 < end;
-        const unsigned long long e0 = valid0 ? p.work[k0] : 0ull, e1 = valid1 ? p.work[k1] : 0ull;
-        const double ia0 = valid0 ? p.workArea[k0] : -1.0, ia1 = valid1 ? p.workArea[k1] : -1.0;
-        const int jl0 = (int)((e0 >> 8) & 0xFFFFFFu), jl1 = (int)((e1 >> 8) & 0xFFFFFFu), i0 = (int)(e0 & 255u), i1 = (int)(e1 & 255u);
-        const int j = __builtin_amdgcn_readfirstlane(jl0); // (lane 0's first candidate is the head of the run)
-        const bool mine0 = valid0 && jl0 == j, mine1 = valid1 && jl1 == j;
-        const double lo0 = __shfl(curArea0, i0 & 63), hi0 = __shfl(curArea1, i0 & 63), lo1 = __shfl(curArea0, i1 & 63), hi1 = __shfl(curArea1, i1 & 63);
-        const double detArea0 = i0 < 64 ? lo0 : hi0, detArea1 = i1 < 64 ? lo1 : hi1;
-        const bool taken0 = ((i0 < 64 ? takenLo >> i0 : takenHi >> (i0 - 64)) & 1ull) != 0ull;
-        const bool taken1 = ((i1 < 64 ? takenLo >> i1 : takenHi >> (i1 - 64)) & 1ull) != 0ull;
-        // interArea > greatestSimilarity (starting at 0) and interArea / newPlaneArea >= threshold (map_primitive.cpp:137-143); the
-        // run is in ascending i and the comparison strict: the lowest index among the largest areas
-        unsigned long long key0 = 0, key1 = 0;
-        if (mine0 && !taken0 && ia0 > 0.0 && ia0 / detArea0 >= p.minOverlap)
-            key0 = (unsigned long long)__double_as_longlong(ia0);
-        if (mine1 && !taken1 && ia1 > 0.0 && ia1 / detArea1 >= p.minOverlap)
-            key1 = (unsigned long long)__double_as_longlong(ia1);
-        const unsigned long long best = ~wave_min_u64(~(key0 > key1 ? key0 : key1)); // maximum of the bit patterns (positive doubles order like them)
-        // the winner's position in the run: my first candidate lies before every second one
-        const unsigned pos = (key0 != 0 && key0 == best) ? (unsigned)lane : ((key1 != 0 && key1 == best) ? (unsigned)lane + 64u : 0xFFFFFFFFu);
-        const unsigned win = wave_min_u32(pos);
-        int selected = -1;
-        if (best)
-            selected = win < 64u ? __builtin_amdgcn_readlane(i0, (int)win) : __builtin_amdgcn_readlane(i1, (int)win - 64);
-        if (!(p.flags & CAPE_MATCH_ALLOW_INDEX0) && selected <= 0) // map_primitive.cpp:146
-            selected = -1;
-        if (selected >= 0)
-        {
-            if (selected < 64)
-                takenLo |= 1ull << selected;
-            else
-                takenHi |= 1ull << (selected - 64);
-            ++nMatched;
-            if (lane == selected)
-                myMapOf0 = j;
-            if (lane + 64 == selected)
-                myMapOf1 = j;
-            if (lane == 0)
-                p.match[(size_t)frame * p.nMap + j] = selected;
-        }
-        at += (unsigned)(__popcll(__ballot(mine0)) + __popcll(__ballot(mine1)));
-    }
-    if (lane == 0)
-        out.n_matched = nMatched;
-    p.mapOf[(size_t)frame * WP + lane] = myMapOf0;
-    p.mapOf[(size_t)frame * WP + lane + 64] = myMapOf1;
+    select_wide<false, true>(
+        p.list, frame, p.framesWide[frame], p.flags, p.minOverlap, p.match + (size_t)frame * p.nMap, p.mapOf + (size_t)frame * WP,
+        [&](int k) { return detected_polygon<kFromChain>(p, frame, k).polygon->area; }, [](int) { return 0.0; });
 }
 
 namespace {
 
 template <MapSource kSource> hipError_t launch_match_map_from(const MatchMapParams& p, int nFrames, hipStream_t stream)
 {
-    if (const hipError_t e = hipMemsetAsync(p.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
+    if (const hipError_t e = hipMemsetAsync(p.list.counts, 0, 16 * sizeof(unsigned), stream); e != hipSuccess)
         return e;
     const dim3 gateGrid((nFrames + kMapGateFrames - 1) / kMapGateFrames), gateGroup(64 * kMapGateFrames);
     if constexpr (kSource == kFromChain)
@@ -860,21 +640,15 @@ template <MapSource kSource> hipError_t launch_match_map_from(const MatchMapPara
         hipLaunchKernelGGL(kSource == kFromShards ? cape_map_gate_shards_kernel : cape_map_gate_kernel, gateGrid, gateGroup, 0, stream, p, nFrames);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
-    // persistent grids: as many workgroups as the chip holds at once (the list's length is only known on the device)
-    const int cus = p.computeUnits > 0 ? p.computeUnits : 256;
-    auto launch = [&](auto kernel, int lds, int wavesPerGroup, bool coop, int groupsPerCu) {
-        hipLaunchKernelGGL(kernel, dim3(cus * groupsPerCu), dim3(64 * wavesPerGroup), (size_t)lds * (coop ? 1 : wavesPerGroup), stream, p, lds);
-        return hipGetLastError();
-    };
-    if (const hipError_t e = launch(cape_map_inter_kernel<0, kSource>, (int)tier_lds_bytes<0>(), Tier<0>::kWavesPerGroup, Tier<0>::kCoop, Tier<0>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch_tier<0>(cape_map_inter_kernel<0, kSource>, p, stream); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_inter_kernel<1, kSource>, (int)tier_lds_bytes<1>(), Tier<1>::kWavesPerGroup, Tier<1>::kCoop, Tier<1>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch_tier<1>(cape_map_inter_kernel<1, kSource>, p, stream); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch(cape_map_inter_kernel<2, kSource>, (int)tier_lds_bytes<2>(), Tier<2>::kWavesPerGroup, Tier<2>::kCoop, Tier<2>::kGroupsPerCu); e != hipSuccess)
+    if (const hipError_t e = launch_tier<2>(cape_map_inter_kernel<2, kSource>, p, stream); e != hipSuccess)
         return e;
     // (a device without the LDS for the largest tier leaves its triples NaN: their frames are flagged)
     if (tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes)
-        if (const hipError_t e = launch(cape_map_inter_kernel<3, kSource>, (int)tier_lds_bytes<3>(), Tier<3>::kWavesPerGroup, Tier<3>::kCoop, Tier<3>::kGroupsPerCu); e != hipSuccess)
+        if (const hipError_t e = launch_tier<3>(cape_map_inter_kernel<3, kSource>, p, stream); e != hipSuccess)
             return e;
     const dim3 selectGrid((nFrames + kMapSelectFrames - 1) / kMapSelectFrames), selectGroup(64 * kMapSelectFrames);
     if constexpr (kSource == kFromChain)

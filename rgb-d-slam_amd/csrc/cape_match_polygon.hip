@@ -7,9 +7,11 @@
 //   cape_polygon_gate_kernel   : one wavefront per frame: the kept planes of the frame and of its predecessor, the gates
 //        is_distance_similar / is_normal_similar (shape_primitives.cpp:66-86) of every (previous plane j, plane i) pair, and
 //        the work list of the pairs to intersect.
-//   cape_polygon_inter_kernel  : persistent wavefronts, one pair at a time: the polygon of j is projected into the frame of i
-//        (Polygon::project, polygon.cpp:338-382) and the area of the intersection of the two rings is computed.  Two
-//        instances by capacity (LDS carve); a pair beyond the small one's moves to the large one's list.
+//   cape_polygon_inter_kernel  : persistent wavefronts, one pair at a time: the polygon of j -- with a pose, through to_camera_space
+//        (camera_frame / to_camera_vertex, cape_map_camera.h) -- is projected into the frame of i (Polygon::project: project_ring_b,
+//        cape_pair_list.h) and oriented (orient_ring), and the area of the intersection of the two rings is computed.  Four
+//        instances by capacity (LDS carve); a pair beyond one's capacities moves to the next one's list.  The walk over the 32-bit
+//        lists, their front/back fill and the A/B knobs are this file's own (the 64-bit lists' walk: cape_pair_list.h).
 //   cape_polygon_select_kernel : one wavefront per frame: the selection loop (greatest intersection above the overlap
 //        threshold, is-matched flags updated between previous planes, the `selectedIndex <= 0` quirk).
 //
@@ -23,6 +25,8 @@
 #include <hip/hip_runtime.h>
 
 #include "cape_internal.h"
+#include "cape_map_camera.h"
+#include "cape_pair_list.h"
 #include "cape_ring_area.h"
 #include "cape_wave.h"
 
@@ -161,13 +165,12 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_polygon_
     using T = Tier<TIER>;
     constexpr bool kHasNext = TIER + 1 < kTiers;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr bool kCoop = T::kCoop;
     // cooperative tiers: ONE carve for the workgroup's four waves, `tid` strides of 256; else a carve per (independent) wave
-    const int tid = kCoop ? (int)threadIdx.x : lane;
-    constexpr int kStride = kCoop ? 256 : 64;
-    unsigned char* smem = smem_all + (kCoop ? (size_t)0 : (size_t)wave * ldsPerWave);
-    const MpLds L = mp_carve<TIER>(smem);
+    const TierCtx<TIER> ctx = tier_ctx<TIER>(smem_all, ldsPerWave);
+    const MpLds& L = ctx.L;
+    const int lane = ctx.lane, wave = ctx.wave, tid = ctx.tid;
+    constexpr int kStride = TierCtx<TIER>::kStride;
     const unsigned* list = p.pairLists + (size_t)TIER * p.pairCapacity;
     const unsigned count = p.listCounts[TIER];
     // The tiers behind the first hold few pairs of very unequal cost (an outline of 70 vertices over 145 slabs keeps a lone wave busy
@@ -200,13 +203,6 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_polygon_
             t = atomicAdd(&p.listCounts[4 + TIER], 1u);
         return (unsigned)__builtin_amdgcn_readfirstlane((int)t);
     };
-    // ordering point between the lanes that share a carve: the wave (fence + wait) or the workgroup (barrier)
-    auto sync = [&]() {
-        if (kCoop)
-            __syncthreads();
-        else
-            CAPE_MP_SYNC();
-    };
     for (unsigned t = next_index(0u, true); t < count; t = next_index(t, false))
     {
         // (tier 0's list is the gate kernel's, front only; the later tiers': front entries, then the back entries)
@@ -228,80 +224,24 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_polygon_
             const double2* vertsP = p.vertices + (size_t)(frame - 1) * p.boundaryCapacity + PQ.vertex_offset;
             for (int v = tid; v < na; v += kStride)
                 L.ringA[v] = vertsC[v];
-            // Polygon::project (polygon.cpp:338-382): every vertex of the previous plane's ring lifted to 3-D and expressed in
-            // the frame of plane i; the projected ring is re-oriented clockwise like every polygon (OpenRing constructor)
             // the frame the previous plane's polygon lives in: its own, or -- with a pose -- the one to_camera_space gives it
-            // (polygon_coordinates.cpp:135-165: centre through the transform, axes through its rotation and re-normalised)
-            double qc[3] = {PQ.center[0], PQ.center[1], PQ.center[2]}, qx[3] = {PQ.x_axis[0], PQ.x_axis[1], PQ.x_axis[2]},
-                   qy[3] = {PQ.y_axis[0], PQ.y_axis[1], PQ.y_axis[2]};
+            // (polygon_coordinates.cpp:135-165), its ring moved by transform_boundary (polygon.cpp:430-451) and oriented by the
+            // explicit-ring constructor (polygon.cpp:236-266); then Polygon::project (polygon.cpp:338-382) into the frame of plane i,
+            // the projected ring re-oriented clockwise like every polygon (OpenRing constructor)
             if (p.poses)
             {
-                const double* T = p.poses + (size_t)frame * 16;
-                double nc[3], nx[3], ny[3];
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-                {
-                    nc[r] = ((T[4 * r] * qc[0] + T[4 * r + 1] * qc[1]) + T[4 * r + 2] * qc[2]) + T[4 * r + 3];
-                    nx[r] = (T[4 * r] * qx[0] + T[4 * r + 1] * qx[1]) + T[4 * r + 2] * qx[2];
-                    ny[r] = (T[4 * r] * qy[0] + T[4 * r + 1] * qy[1]) + T[4 * r + 2] * qy[2];
-                }
-                const double lx = sqrt((nx[0] * nx[0] + nx[1] * nx[1]) + nx[2] * nx[2]), ly = sqrt((ny[0] * ny[0] + ny[1] * ny[1]) + ny[2] * ny[2]);
-                if (lx > 0)
-                    nx[0] /= lx, nx[1] /= lx, nx[2] /= lx;
-                if (ly > 0)
-                    ny[0] /= ly, ny[1] /= ly, ny[2] /= ly;
-                // transform_boundary (polygon.cpp:430-451): every vertex lifted to 3-D, moved, re-expressed in the new frame; then the
-                // explicit-ring constructor's orientation fix (polygon.cpp:236-266)
+                const double* Tm = p.poses + (size_t)frame * 16;
+                const CameraFrame F = camera_frame(Tm, PQ.center, PQ.x_axis, PQ.y_axis);
                 for (int v = tid; v < nb; v += kStride)
-                {
-                    const double2 q = vertsP[v];
-                    const double X = qc[0] + q.x * qx[0] + q.y * qy[0], Y = qc[1] + q.x * qx[1] + q.y * qy[1], Z = qc[2] + q.x * qx[2] + q.y * qy[2];
-                    const double mx = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[3], my = ((T[4] * X + T[5] * Y) + T[6] * Z) + T[7],
-                                 mz = ((T[8] * X + T[9] * Y) + T[10] * Z) + T[11];
-                    const double dx = mx - nc[0], dy = my - nc[1], dz = mz - nc[2];
-                    L.ringB[v] = make_double2((nx[0] * dx + nx[1] * dy) + nx[2] * dz, (ny[0] * dx + ny[1] * dy) + ny[2] * dz);
-                }
-                sync();
-                const bool flip = ring_area_signed(L.ringB, nb) > 0;
-                sync(); // (every lane has read the ring before any lane of the carve rewrites it)
-                if (flip)
-                {
-                    for (int v = tid; v < nb / 2; v += kStride)
-                    {
-                        const double2 a = L.ringB[v], b = L.ringB[nb - 1 - v];
-                        L.ringB[v] = b;
-                        L.ringB[nb - 1 - v] = a;
-                    }
-                    sync();
-                }
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-                    qc[r] = nc[r], qx[r] = nx[r], qy[r] = ny[r];
+                    L.ringB[v] = to_camera_vertex(Tm, F, vertsP[v]);
+                ctx.sync();
+                orient_ring(L.ringB, nb, false, ctx);
+                project_ring_b(ctx, L.ringB, nb, F.nc, F.nx, F.ny, PS);
             }
-            for (int v = tid; v < nb; v += kStride)
-            {
-                const double2 q = p.poses ? L.ringB[v] : vertsP[v];
-                const double X = qc[0] + q.x * qx[0] + q.y * qy[0];
-                const double Y = qc[1] + q.x * qx[1] + q.y * qy[1];
-                const double Z = qc[2] + q.x * qx[2] + q.y * qy[2];
-                const double dx = X - PS.center[0], dy = Y - PS.center[1], dz = Z - PS.center[2];
-                L.ringB[v] = make_double2((PS.x_axis[0] * dx + PS.x_axis[1] * dy) + PS.x_axis[2] * dz,
-                                          (PS.y_axis[0] * dx + PS.y_axis[1] * dy) + PS.y_axis[2] * dz);
-            }
-            sync();
-            const bool flip = ring_area_signed(L.ringB, nb) > 0;
-            sync(); // (every lane has read the ring before any lane of the carve rewrites it)
-            if (flip)
-            {
-                // reverse in place: lane v swaps v and nb - 1 - v
-                for (int v = tid; v < nb / 2; v += kStride)
-                {
-                    const double2 a = L.ringB[v], b = L.ringB[nb - 1 - v];
-                    L.ringB[v] = b;
-                    L.ringB[nb - 1 - v] = a;
-                }
-                sync();
-            }
+            else
+                project_ring_b(ctx, vertsP, nb, PQ.center, PQ.x_axis, PQ.y_axis, PS);
+            ctx.sync();
+            orient_ring(L.ringB, nb, false, ctx);
 #ifdef CAPE_MP_PROFILE
             unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             const unsigned long long tStart = __builtin_amdgcn_s_memtime();
@@ -322,7 +262,7 @@ __global__ __launch_bounds__(64 * Tier<TIER>::kWavesPerGroup) void cape_polygon_
             else
                 result = rings_inter_area<T::kStack, T::kXs>(L, na, nb, lane);
 #endif
-            sync();
+            ctx.sync();
         }
         if (tid == 0)
         {
@@ -402,7 +342,7 @@ __global__ __launch_bounds__(64 * kWaves) void cape_polygon_select_kernel(MatchP
 }
 
 
-template <int TIER> static hipError_t launch_tier(const MatchPolygonParams& p, int blocks, hipStream_t stream)
+template <int TIER> static hipError_t launch_polygon_tier(const MatchPolygonParams& p, int blocks, hipStream_t stream)
 {
     const int lds = (int)tier_lds_bytes<TIER>();
     // (a cooperative tier's four waves share ONE carve)
@@ -425,14 +365,14 @@ hipError_t launch_match_polygons(const MatchPolygonParams& p, int nFrames, hipSt
         const int need = (maxPairs + pairsPerGroup - 1) / pairsPerGroup;
         return need < cus * perCu ? need : cus * perCu;
     };
-    if (const hipError_t e = launch_tier<0>(p, blocks_for(Tier<0>::kGroupsPerCu, Tier<0>::kCoop ? 1 : Tier<0>::kWavesPerGroup), stream); e != hipSuccess)
+    if (const hipError_t e = launch_polygon_tier<0>(p, blocks_for(Tier<0>::kGroupsPerCu, Tier<0>::kCoop ? 1 : Tier<0>::kWavesPerGroup), stream); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch_tier<1>(p, blocks_for(Tier<1>::kGroupsPerCu, Tier<1>::kCoop ? 1 : Tier<1>::kWavesPerGroup), stream); e != hipSuccess)
+    if (const hipError_t e = launch_polygon_tier<1>(p, blocks_for(Tier<1>::kGroupsPerCu, Tier<1>::kCoop ? 1 : Tier<1>::kWavesPerGroup), stream); e != hipSuccess)
         return e;
-    if (const hipError_t e = launch_tier<2>(p, blocks_for(Tier<2>::kGroupsPerCu, Tier<2>::kCoop ? 1 : Tier<2>::kWavesPerGroup), stream); e != hipSuccess)
+    if (const hipError_t e = launch_polygon_tier<2>(p, blocks_for(Tier<2>::kGroupsPerCu, Tier<2>::kCoop ? 1 : Tier<2>::kWavesPerGroup), stream); e != hipSuccess)
         return e;
     if (p.boundaryCapacity > Tier<2>::kRing && tier_lds_bytes<3>() <= (size_t)p.ldsLimitBytes) // (a ring is a subset of its plane's candidates)
-        if (const hipError_t e = launch_tier<3>(p, blocks_for(Tier<3>::kGroupsPerCu, Tier<3>::kCoop ? 1 : Tier<3>::kWavesPerGroup), stream); e != hipSuccess)
+        if (const hipError_t e = launch_polygon_tier<3>(p, blocks_for(Tier<3>::kGroupsPerCu, Tier<3>::kCoop ? 1 : Tier<3>::kWavesPerGroup), stream); e != hipSuccess)
             return e;
     hipLaunchKernelGGL(cape_polygon_select_kernel, dim3((nFrames + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, stream, p, nFrames);
     return hipGetLastError();

@@ -1,7 +1,8 @@
-// Shared by the intersection kernels of the polygon matchers (cape_match_polygon.hip: consecutive frames; cape_match_map.hip:
-// a persistent map): the capacity tiers, the LDS carve and rings_inter_area / rings_inter_area_coop -- this repo's host
+// Shared by the intersection kernels of the polygon matchers and of the visibility kernels (cape_match_polygon.hip,
+// cape_match_wide.hip: consecutive frames; cape_match_map.hip: a persistent map; cape_map_visibility.hip; what stands around the
+// intersection in them: cape_pair_list.h): the capacity tiers, the LDS carve and rings_inter_area / rings_inter_area_coop -- this repo's host
 // algorithm (host/boundary_polygon.cpp: rings_inter_area) statement for statement, see the header of cape_match_polygon.hip.
-// Both files compile their own copy (anonymous namespace; no device symbol crosses a file).
+// Every file compiles its own copy (anonymous namespace; no device symbol crosses a file).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -285,3 +285,46 @@ def test_determinism():
     assert len(runs) == 3 and int(runs[0][0]["n_matched"].sum()) > 64 and np.all(runs[0][0]["flags"] == 0)
     for other in runs[1:]:
         assert all(a.tobytes() == b.tobytes() for a, b in zip(runs[0], other))
+
+
+def test_outlines_beyond_128_vertices_equal_match_map():
+    """The stream of test_polygon_matches_1280x960_outlines_beyond_128_vertices (64 tumlike frames of 1280 x 960, cylinders on) against
+    a map lifted from the kept planes of the frame with the longest outline (more than 128 vertices): both intersection kernels hand
+    pairs on up to the last tier, and the wide call serves what cape_match_map serves -- counts, segment lists, matches, and every
+    entry of the area table bit for bit; no frame flagged."""
+    import torch
+    import cape_amd
+    from cape_amd import Extractor, synth, synth_gpu
+    from test_gpu_map_match import _lift
+    from test_gpu_match_wide import _small_pose
+
+    n, M = 64, 64
+    intr = {k: v * 2.0 for k, v in synth.TUM_FR1_INTRINSICS.items()}
+    dev = synth_gpu.stream("tumlike", 17, n, width=1280, height=960, start=256, device="cuda", chunk=4)
+    ex = Extractor(1280, 960, cylinders=True, max_batch=n, **intr)
+    st = torch.cuda.current_stream().cuda_stream
+    ex.extract_device(dev.data_ptr(), n, st)
+    ex.build_polygons(n, st)
+    kept = ex.kept_planes(n)
+    longest = [max((len(k[5]) for k in det), default=0) for det, _ in kept]
+    source = int(np.argmax(longest))
+    assert longest[source] > 128, "the stream must show an outline the 128-vertex tiers cannot hold"
+    planes = [_lift(k, *EYE) for k in kept[source][0]]
+    ex.upload_map(planes)
+    T = _small_pose(n)
+    ex.match_map(n, T, None, cape_amd.MATCH_MAP_AREAS, st)
+    assert ex.map_match_lists()["tiers"][2] > 0, "no pair reached the last tier"
+    ex.match_map_wide(n, T, None, cape_amd.MATCH_MAP_AREAS, st)
+    assert ex.map_match_lists()["tiers"][2] > 0, "no pair reached the last tier"
+    narrow, nmatch, ninter = ex.map_matches(n, areas=True)
+    frames, match, seg_cur, map_of, inter = ex.map_matches_wide(n, areas=True)
+    assert not narrow["flags"].any() and not frames["flags"].any(), "a frame is flagged"
+    assert int((nmatch >= 0).sum()) > 0 and np.count_nonzero(ninter > 0) > n, "the comparison would pass on empty results"
+    for name in ("n_map", "n_cur", "n_matched"):
+        assert np.array_equal(frames[name], narrow[name]), name
+    assert np.array_equal(match, nmatch)
+    assert np.array_equal(seg_cur[:, :M], narrow["seg_cur"]) and np.array_equal(map_of[:, :M], narrow["map_of"])
+    assert np.all(seg_cur[:, M:] == -1) and np.all(map_of[:, M:] == -1)
+    assert np.array_equal(_bits(inter[:, :, :M]), _bits(ninter)), "the area tables differ"
+    assert np.all(inter[:, :, M:] == -1.0)
+    ex.close()

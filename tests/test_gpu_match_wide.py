@@ -225,3 +225,42 @@ def test_more_than_128_kept_planes_are_flagged_and_the_twin_answers():
     m = cape_amd.host_match_planes(kept[0][0], kept[1][0], None, 0)
     assert list(m) == [-1] + list(range(1, n_big))
     ex.close()
+
+
+def test_outlines_beyond_128_vertices_equal_the_16_plane_path():
+    """The stream of test_polygon_matches_1280x960_outlines_beyond_128_vertices (64 tumlike frames of 1280 x 960, cylinders on): a
+    gated pair with an outline of more than 128 vertices is handed from tier to tier up to the last one by the wide intersection
+    kernel as by the 16-plane one -- counts, matches, segment lists, and every entry of the area table bit for bit; no frame flagged."""
+    import torch
+    import cape_amd
+    from cape_amd import Extractor, synth, synth_gpu
+
+    n, M = 64, cape_amd.MATCH_MAX_PLANES
+    intr = {k: v * 2.0 for k, v in synth.TUM_FR1_INTRINSICS.items()}
+    dev = synth_gpu.stream("tumlike", 17, n, width=1280, height=960, start=256, device="cuda", chunk=4)
+    ex = Extractor(1280, 960, cylinders=True, max_batch=n, **intr)
+    st = torch.cuda.current_stream().cuda_stream
+    ex.extract_device(dev.data_ptr(), n, st)
+    ex.build_polygons(n, st)
+    ex.match_polygons(n, 0, st)
+    ex.match_polygons_wide(n, None, cape_amd.MATCH_MAP_AREAS, st)
+    narrow = ex.polygon_matches(n)
+    frames, match, seg_prev, seg_cur, inter = ex.polygon_matches_wide(n, areas=True)
+    assert not narrow["flags"].any() and not frames["flags"].any(), "a frame is flagged"
+    # a pair of the last tier: a kept outline of more than 128 vertices that passes the gates against a plane of the next frame
+    pol, _ = ex.polygons(n)
+    long_pairs = 0
+    for f in range(1, n):
+        for j in range(int(frames[f]["n_prev"])):
+            if pol[f - 1, seg_prev[f, j]]["vertex_count"] > 128:
+                long_pairs += int(np.count_nonzero(inter[f, j] != -1.0))
+    assert long_pairs > 0, "the stream must show a gated pair the 128-vertex tiers cannot hold"
+    assert np.array_equal(frames["n_prev"], narrow["n_prev"]) and np.array_equal(frames["n_cur"], narrow["n_cur"])
+    assert int((narrow["match"] >= 0).sum()) > 0 and np.count_nonzero(narrow["inter_area"] > 0) > n
+    for name, wide in (("match", match), ("seg_prev", seg_prev), ("seg_cur", seg_cur)):
+        assert np.array_equal(wide[:, :M], narrow[name]), name
+        assert np.all(wide[:, M:] == -1), name
+    assert np.array_equal(frames["n_matched"], (narrow["match"] >= 0).sum(1))
+    assert np.array_equal(_bits(inter[:, :M, :M]), _bits(narrow["inter_area"])), "the area tables differ"
+    assert np.all(inter[:, M:] == -1.0) and np.all(inter[:, :, M:] == -1.0)
+    ex.close()
