@@ -1226,8 +1226,8 @@ int cape_map_step_visible(cape_handle h, int32_t frame, const double* world_to_c
 int cape_map_step_skip_words(cape_handle h, uint32_t* words, int32_t words_capacity, int32_t* n_map);
 
 /* THE PLANE COST FUNCTION OF THE POSE SOLVER, for a batch of pose hypotheses per frame: the stage between the match and the update
- * (find matches -> optimise the pose -> update -> maintain).  The solver itself (RANSAC over hypotheses, Levenberg-Marquardt) stays
- * with the caller; what it evaluates thousands of times per frame -- PlaneOptimizationFeature::is_inlier / get_distance
+ * (find matches -> optimise the pose -> update -> maintain).  The solver itself (RANSAC over hypotheses, Levenberg-Marquardt) is
+ * cape_map_pose_solve / cape_map_pose_select below; what it evaluates thousands of times per frame -- PlaneOptimizationFeature::is_inlier / get_distance
  * (map_primitive.cpp:15-85), called by Pose_Optimization::get_features_inliers_outliers (pose_optimization.cpp:40-75) and the LM
  * functor (levenberg_marquardt_functors.cpp:154-166) -- runs here on data that is already on the device.
  * Frame f's PAIRS are the map planes j = 0 .. n_map-1 in ascending order with i = match[f][j] >= 0 of the last cape_match_map_wide,
@@ -1293,6 +1293,100 @@ int cape_copy_pose_scores(cape_handle h, int32_t n_frames, cape_pose_score* scor
  * selects the best hypothesis with a kernel of its own on the stream of the scoring call.  Either may be NULL.  CAPE_ERR_CAPACITY
  * when no cape_map_pose_score is current. */
 int cape_pose_score_device(cape_handle h, const cape_pose_score** scores, const cape_pose_feature** features);
+
+/* THE POSE SOLVER ITSELF on the same pairs: Levenberg-Marquardt per (frame, hypothesis), the RANSAC bookkeeping over a frame's scored
+ * hypotheses and the final re-optimisation on the chosen inliers (Pose_Optimization::compute_pose_with_ransac and
+ * compute_optimized_global_pose, pose_optimization.cpp:90-350).  The chain, on one stream without a host wait in between:
+ *   cape_match_map_wide -> cape_map_pose_solve(subsets) -> cape_map_pose_score(CAPE_POSE_SCORE_DEVICE_POSES = the solve's poses) ->
+ *   cape_map_pose_select -> cape_map_pose_solve(CAPE_POSE_SOLVE_FROM_SELECTION);  the host only draws the random subsets.
+ * A PROBLEM (f, h) minimises the sum of r^2 over the pairs of frame f (those of cape_map_pose_score, in its order) that the subset
+ * names: r = reduced[c] * 1.0 / 3.0 for c < 3, pair after pair (the LM functor, levenberg_marquardt_functors.cpp:154-166), the map
+ * plane seen through the pose of x.  x[6] = the position, then the three coefficients of get_optimization_coefficients_from_quaternion;
+ * the pose of x: the quaternion of the coefficients (levenberg_marquardt_functors.cpp:29-38), normalised (pose.cpp:20), its rotation
+ * matrix R, camera-to-world [C R | C p] with the camera basis C of the parameters, world-to-camera its rigid inverse.  The minimiser is
+ * MINPACK's lmstr driver with a forward-difference Jacobian (rules and departures from the reference: csrc/cape_pose_solve.h).
+ * Everything is + - x / sqrt in one order and equals the host twin cape_host_pose_solve (host/cape_host_map.h) bit for bit; no
+ * result of a problem depends on the other problems of the call. */
+enum /* flags of cape_map_pose_solve */
+{
+    CAPE_POSE_SOLVE_DEVICE_INPUT = 1u << 0,  /* x0 and subsets are DEVICE memory, read in place when the kernel runs */
+    CAPE_POSE_SOLVE_FROM_SELECTION = 1u << 1 /* one problem per frame from x and inlier_words of the last cape_map_pose_select */
+};
+enum /* cape_pose_solution.status: MINPACK's info 1..8 when the minimiser ran, or why the problem was refused (x = x0 then) */
+{
+    CAPE_POSE_SOLVE_TOO_FEW_PAIRS = -1,   /* 3 x pairs <= 6 (pose_optimization.cpp:322-331) */
+    CAPE_POSE_SOLVE_LOW_SCORE = -2,       /* the subset's score, 1.0 / 3 added per pair in order, is below 1.0 (same lines) */
+    CAPE_POSE_SOLVE_INVALID_FEATURE = -3, /* the frame has n_invalid > 0 (pose_optimization.cpp:270-282) */
+    CAPE_POSE_SOLVE_OVERFLOW = -4,        /* the wide match flagged the frame CAPE_MATCH_EXACT_OVERFLOW */
+    CAPE_POSE_SOLVE_BAD_START = -5,       /* a NaN or an infinity in x0 */
+    CAPE_POSE_SOLVE_NOT_FINITE = -6,      /* a NaN or an infinity in x or in a residual during the run: x is the last accepted point */
+    CAPE_POSE_SOLVE_NO_SELECTION = -7     /* CAPE_POSE_SOLVE_FROM_SELECTION on a frame whose selection has no best hypothesis */
+};
+enum /* cape_pose_solution.flags, beside CAPE_MATCH_EXACT_OVERFLOW and CAPE_POSE_SCORE_INVALID_FEATURE of the frame */
+{
+    CAPE_POSE_SOLVE_RANK_DEFICIENT = 1u << 9 /* a diagonal entry of R was 0 at least once: the pivoted qrfac ran */
+};
+enum /* cape_pose_selection.flags */
+{
+    CAPE_POSE_SELECT_NO_CONSENSUS = 1u << 0, /* no hypothesis was taken: best = -1 */
+    CAPE_POSE_SELECT_EARLY_STOP = 1u << 1    /* the scan ended before the last hypothesis (pose_optimization.cpp:225-229) */
+};
+typedef struct cape_pose_solve_params /* NULL = the defaults of Eigen::LevenbergMarquardt and the identity basis */
+{
+    double ftol, xtol;       /* sqrt(DBL_EPSILON) */
+    double gtol;             /* 0 */
+    double factor;           /* 100 */
+    double epsfcn;           /* 0: the difference step is sqrt(max(epsfcn, DBL_EPSILON)) |x_j|, or that factor alone where x_j = 0 */
+    int32_t maxfev;          /* 400; a Jacobian counts 6 */
+    int32_t mode;            /* 1: the columns' norms scale the variables (internal scaling); 2: no scaling */
+    double camera_basis[9];  /* C, row-major: the reference's constant CameraToWorld rotation (camera_transformation.cpp:11-18) */
+} cape_pose_solve_params;
+typedef struct cape_pose_solution /* 96 bytes, one per problem */
+{
+    double x[6];           /* where the minimiser ended (the start for a refused problem) */
+    double fnorm0, fnorm;  /* the residuals' norm at the start and at x (0 for a refused problem) */
+    int32_t status;        /* > 0: MINPACK's info; < 0: CAPE_POSE_SOLVE_* */
+    int32_t nfev;          /* evaluations of the residual vector, the Jacobians' included */
+    int32_t iterations;    /* accepted steps */
+    int32_t n_pairs_used;  /* pairs of the frame that the subset names */
+    uint32_t flags;
+    uint32_t reserved[3];
+} cape_pose_solution;
+typedef struct cape_pose_selection /* 96 bytes, one per frame */
+{
+    int32_t best;             /* the chosen hypothesis, -1: none (CAPE_POSE_SELECT_NO_CONSENSUS) */
+    int32_t n_scanned;        /* hypotheses the scan looked at before it stopped */
+    int32_t n_inliers;        /* of the chosen hypothesis */
+    uint32_t flags;           /* CAPE_POSE_SELECT_* */
+    double score;             /* of the chosen hypothesis (1.0 when none) */
+    double reserved;
+    uint32_t inlier_words[4]; /* its cape_pose_score.inlier_words: a subset for CAPE_POSE_SOLVE_FROM_SELECTION */
+    double x[6];              /* its cape_pose_solution.x */
+} cape_pose_selection;
+/* n_frames x n_hypotheses problems.  x0: 6 doubles per problem; subsets: 4 uint32 per problem, bit i = the pair of kept plane i takes
+ * part (the indexing of cape_pose_score.inlier_words; bits of unmatched kept planes are ignored) -- HOST memory read before the call
+ * returns, or with CAPE_POSE_SOLVE_DEVICE_INPUT device memory that must stay unchanged until the call's work on `stream` is done.  With
+ * CAPE_POSE_SOLVE_FROM_SELECTION n_hypotheses must be 1, x0 and subsets are not read, and a current cape_map_pose_select covering
+ * n_frames is needed (CAPE_ERR_CAPACITY otherwise).  Per problem a cape_pose_solution and the pose of its x as 16 doubles row-major
+ * [R t; 0 0 0 1]: the layout cape_map_pose_score takes with CAPE_POSE_SCORE_DEVICE_POSES.  Needs what cape_map_pose_score needs and is
+ * invalidated by what invalidates it; a later cape_map_pose_solve replaces the rows.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, NULL x0
+ * or subsets without CAPE_POSE_SOLVE_FROM_SELECTION, n_frames < 0, n_hypotheses < 1, unknown flag, a parameter that is NaN or negative,
+ * maxfev < 1, a mode other than 1 and 2.  Nothing but the call's own buffers is written.  Asynchronous on `stream`. */
+int cape_map_pose_solve(cape_handle h, int32_t n_frames, int32_t n_hypotheses, const double* x0, const uint32_t* subsets,
+                        const cape_pose_solve_params* params, uint32_t flags, void* stream);
+/* Synchronous copy of the last cape_map_pose_solve: solutions (n_frames x n_hypotheses of that call) and poses (x 16 doubles).  Either
+ * may be NULL.  CAPE_ERR_CAPACITY: more frames than that call covered, or its results are no longer current. */
+int cape_copy_pose_solutions(cape_handle h, int32_t n_frames, cape_pose_solution* solutions, double* world_to_camera);
+/* Device pointers of the solution rows and of the pose buffer.  Either may be NULL.  CAPE_ERR_CAPACITY when no solve is current. */
+int cape_pose_solve_device(cape_handle h, const cape_pose_solution** solutions, const double** world_to_camera);
+/* The RANSAC bookkeeping of pose_optimization.cpp:190-235 per frame over the current score rows and solution rows, hypotheses in
+ * ascending order: maxScore = 1.0, bestInliers = 0; h is SKIPPED when its solve status is <= 0 or its score < 1.0; it is TAKEN when
+ * score > maxScore, or |score - maxScore| <= 0.1 and bestInliers < n_inliers; after a hypothesis that was not skipped the scan stops
+ * when h >= 3 and bestInliers > ceil(n_pairs x (double)0.80f).  Needs a current cape_map_pose_solve (not FROM_SELECTION) and a current
+ * cape_map_pose_score with the same n_hypotheses, both covering n_frames: CAPE_ERR_CAPACITY otherwise.  Asynchronous on `stream`. */
+int cape_map_pose_select(cape_handle h, int32_t n_frames, void* stream);
+/* Synchronous copy of the last cape_map_pose_select (n_frames rows).  CAPE_ERR_CAPACITY: more frames than it covered, or not current. */
+int cape_copy_pose_selection(cape_handle h, int32_t n_frames, cape_pose_selection* selection);
 
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as

@@ -14,6 +14,7 @@
 #include "cape_map_maintain.h"
 #include "cape_map_step.h"
 #include "cape_pose_score.h"
+#include "cape_pose_solve.h"
 
 namespace cape {
 // every launcher returns the error of its own launch(es) (hipGetLastError right behind hipLaunchKernelGGL)
@@ -44,6 +45,9 @@ hipError_t launch_map_step_visibility(const MapVisibilityParams& p, const MapTra
 hipError_t launch_map_measure(const MapMeasureParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_kalman(const MapKalmanParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_pose_pairs(const PoseScoreParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_pose_solve(const PoseSolveParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_pose_select(const PoseSelectParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_ring_union(const RingUnionParams& p, hipStream_t stream);
 hipError_t launch_map_union_holes(const MapUnionParams& p, cape_plane_union_rings* ringRows /* frames x 128 */, int nFrames, hipStream_t stream);
@@ -625,16 +629,34 @@ struct cape_handle_s
         int hypotheses = 0;                 // hypotheses per frame of that call
         bool keptResiduals = false;         // ... and whether it kept the per-pair table
     } poseScore;
+
+    // cape_map_pose_solve / cape_map_pose_select: the problems of the last solve, what it made of them and the last selection over
+    // them.  Buffers of its own, like PoseScore's: the pairs kernel in front of the solve writes frameInfo and features HERE.
+    struct PoseSolve
+    {
+        Buffer<unsigned char> input; // the call's x0 (frames x problems x 6 doubles), then its subsets (x 4 words), unless device memory
+        cape::abi::PinnedTwin inputTwin;
+        Buffer<int4> frameInfo;             // frames: n_pairs, n_invalid, flags, 0
+        Buffer<cape_pose_feature> features; // frames x 128
+        Buffer<cape_pose_solution> solutions; // frames x problems
+        Buffer<double> poses;                 // frames x problems x 16
+        Buffer<cape_pose_selection> selection; // frames
+        int frames = 0;          // frames of the last cape_map_pose_solve (0: none for the current batch, map, tracks and match)
+        int problems = 0;        // problems per frame of that call
+        bool fromSelection = false; // ... and whether they came from the selection
+        int selectFrames = 0;    // frames of the last cape_map_pose_select (0: none current)
+    } poseSolve;
 };
 
 namespace cape::abi {
 // What a replaced input of the map update's per-frame results invalidates, for every call that replaces one (the batch's polygons,
 // the wide match, the measurements, the map, its tracks): the results of cape_map_kalman -- and with them the unions' -- and those of
-// cape_map_pose_score.  (A cape_extract ends the wide match and the measurements themselves: both results are checked against them.)
+// cape_map_pose_score, cape_map_pose_solve and cape_map_pose_select.  (A cape_extract ends the wide match and the measurements themselves: both results are checked against them.)
 inline void invalidate_frame_results(cape_handle_s* h)
 {
     h->kalman.kalmanFrames = 0;
     h->poseScore.frames = 0;
+    h->poseSolve.frames = h->poseSolve.selectFrames = 0;
 }
 } // namespace cape::abi
 

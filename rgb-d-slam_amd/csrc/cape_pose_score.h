@@ -90,13 +90,18 @@ CAPE_POSE_FN double pose_angle_distance(double a, double b)
     const double diff = a - b;
     return atan2(sin(diff), cos(diff));
 }
+// get_reduced_signed_distance alone: what the LM functor reads of a pair (cape_pose_solve.h evaluates nothing else)
+CAPE_POSE_FN void pose_pair_reduced(const double* cn, double cd, const double* qn, double qd, double reduced[3])
+{
+    for (int c = 0; c < 3; ++c)
+        reduced[c] = cd * cn[c] - qd * qn[c];
+}
 CAPE_POSE_FN void pose_pair_distances(const double* cn, double cd, const double* qn, double qd, double signedDistance[4], double reduced[3])
 {
     for (int c = 0; c < 3; ++c)
         signedDistance[c] = pose_angle_distance(cn[c], qn[c]);
     signedDistance[3] = cd - qd;
-    for (int c = 0; c < 3; ++c)
-        reduced[c] = cd * cn[c] - qd * qn[c];
+    pose_pair_reduced(cn, cd, qn, qd, reduced);
 }
 CAPE_POSE_FN bool pose_pair_inlier(const double signedDistance[4])
 {

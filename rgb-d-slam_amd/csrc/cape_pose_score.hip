@@ -170,10 +170,16 @@ __global__ __launch_bounds__(kPoseScoreGroupHypotheses) void cape_pose_score_ker
     out[2] = make_uint4(r.inlier_words[0], r.inlier_words[1], r.inlier_words[2], r.inlier_words[3]);
 }
 
-hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStream_t stream)
+// the pairs kernel alone: frameInfo and features of p (cape_map_pose_solve runs it in front of its own kernel, into its own rows)
+hipError_t launch_map_pose_pairs(const PoseScoreParams& p, int nFrames, hipStream_t stream)
 {
     hipLaunchKernelGGL(cape_pose_pairs_kernel, dim3((nFrames + kPairsFrames - 1) / kPairsFrames), dim3(64 * kPairsFrames), 0, stream, p, nFrames);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStream_t stream)
+{
+    hipError_t e = launch_map_pose_pairs(p, nFrames, stream);
     if (e != hipSuccess)
         return e;
     const int groups = (p.nHypotheses + kPoseScoreGroupHypotheses - 1) / kPoseScoreGroupHypotheses;

@@ -221,6 +221,23 @@ int cape_host_pose_score(const cape_host_map* map, const int32_t* match, const c
                          int32_t n_hypotheses, const double* world_to_camera, cape_pose_score* scores_out, cape_pose_feature* features_out,
                          double* residuals_out);
 
+/* The twin of cape_map_pose_solve (include/cape_hip.h) for ONE frame (host/pose_solve.cpp), on the rules of csrc/cape_pose_solve.h that
+ * the kernel compiles too: MINPACK's lmstr driver over forward differences on the frame's pairs, problem after problem.  map, match,
+ * detected, frame_flags: as cape_host_pose_score takes them (its pairs and feature rows are used).  x0: n_problems x 6 doubles;
+ * subsets: n_problems x 4 words (bit i: the pair of kept plane i takes part); or, with `selection` given, n_problems = 1 and the
+ * problem comes from its x and inlier_words (CAPE_POSE_SOLVE_FROM_SELECTION; a selection without a best gives
+ * CAPE_POSE_SOLVE_NO_SELECTION).  params: NULL = the defaults.  Outputs, any may be NULL: solutions_out[n_problems],
+ * world_to_camera_out[n_problems x 16], n_rank_deficient_out: the problems in which the pivoted qrfac ran
+ * (CAPE_POSE_SOLVE_RANK_DEFICIENT), for the tests.  Everything equals the device bit for bit.  Returns 0, or
+ * CAPE_ERR_INVALID_ARGUMENT for what cape_host_pose_score refuses, a missing input or a parameter out of range. */
+int cape_host_pose_solve(const cape_host_map* map, const int32_t* match, const cape_host_planes* detected, uint32_t frame_flags,
+                         int32_t n_problems, const double* x0, const uint32_t* subsets, const cape_pose_selection* selection,
+                         const cape_pose_solve_params* params, cape_pose_solution* solutions_out, double* world_to_camera_out,
+                         int32_t* n_rank_deficient_out);
+/* The twin of cape_map_pose_select for ONE frame: pose_select_frame over the frame's n_hypotheses score rows and solution rows. */
+int cape_host_pose_select(int32_t n_hypotheses, const cape_pose_score* scores, const cape_pose_solution* solutions,
+                          cape_pose_selection* selection_out);
+
 #ifdef __cplusplus
 }
 #endif

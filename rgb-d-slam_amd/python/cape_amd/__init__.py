@@ -289,6 +289,31 @@ POSE_SCORE_DEVICE_POSES, POSE_SCORE_RESIDUALS = 1, 2
 POSE_SCORE_INVALID_FEATURE = 1 << 8
 POSE_SCORE_MAX_PAIRS = 128
 
+# cape_map_pose_solve / cape_map_pose_select: Levenberg-Marquardt per (frame, hypothesis) on the same pairs and the RANSAC bookkeeping
+# over the scored hypotheses (cape_pose_solution, one per problem; cape_pose_selection, one per frame; cape_pose_solve_params)
+POSE_SOLUTION_DTYPE = np.dtype([("x", "<f8", 6), ("fnorm0", "<f8"), ("fnorm", "<f8"), ("status", "<i4"), ("nfev", "<i4"),
+                                ("iterations", "<i4"), ("n_pairs_used", "<i4"), ("flags", "<u4"), ("reserved", "<u4", 3)], align=True)
+POSE_SELECTION_DTYPE = np.dtype([("best", "<i4"), ("n_scanned", "<i4"), ("n_inliers", "<i4"), ("flags", "<u4"), ("score", "<f8"),
+                                 ("reserved", "<f8"), ("inlier_words", "<u4", 4), ("x", "<f8", 6)], align=True)
+POSE_SOLVE_PARAMS_DTYPE = np.dtype([("ftol", "<f8"), ("xtol", "<f8"), ("gtol", "<f8"), ("factor", "<f8"), ("epsfcn", "<f8"),
+                                    ("maxfev", "<i4"), ("mode", "<i4"), ("camera_basis", "<f8", 9)], align=True)
+assert POSE_SOLUTION_DTYPE.itemsize == 96 and POSE_SELECTION_DTYPE.itemsize == 96 and POSE_SOLVE_PARAMS_DTYPE.itemsize == 120
+POSE_SOLVE_DEVICE_INPUT, POSE_SOLVE_FROM_SELECTION = 1, 2
+POSE_SOLVE_TOO_FEW_PAIRS, POSE_SOLVE_LOW_SCORE, POSE_SOLVE_INVALID_FEATURE, POSE_SOLVE_OVERFLOW = -1, -2, -3, -4
+POSE_SOLVE_BAD_START, POSE_SOLVE_NOT_FINITE, POSE_SOLVE_NO_SELECTION = -5, -6, -7
+POSE_SOLVE_RANK_DEFICIENT = 1 << 9
+POSE_SELECT_NO_CONSENSUS, POSE_SELECT_EARLY_STOP = 1, 2
+
+
+def pose_solve_params(ftol=None, xtol=None, gtol=0.0, factor=100.0, epsfcn=0.0, maxfev=400, mode=1, camera_basis=None):
+    """a cape_pose_solve_params row: the defaults of Eigen::LevenbergMarquardt and the identity camera basis unless given"""
+    p = np.zeros(1, POSE_SOLVE_PARAMS_DTYPE)
+    eps = float(np.sqrt(np.finfo(np.float64).eps))
+    p["ftol"], p["xtol"] = eps if ftol is None else ftol, eps if xtol is None else xtol
+    p["gtol"], p["factor"], p["epsfcn"], p["maxfev"], p["mode"] = gtol, factor, epsfcn, maxfev, mode
+    p["camera_basis"] = np.eye(3).reshape(9) if camera_basis is None else np.asarray(camera_basis, np.float64).reshape(9)
+    return p
+
 
 class cape_host_map(C.Structure):
     """a map in cape_map_upload's layout with its tracks (cape_host_map.h): the counts describe an input, the capacities an output"""
@@ -334,6 +359,8 @@ def _host_library():
         L.cape_host_map_commit.argtypes = [Map, C.c_int32] + [C.c_void_p] * 8 + [C.c_uint32, C.POINTER(C.c_uint64), Map, C.c_void_p]
         L.cape_host_map_maintain.argtypes = [Map, Map, Map, C.c_void_p]
         L.cape_host_pose_score.argtypes = [Map, i32, Planes, C.c_uint32, C.c_int32, f64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_host_pose_solve.argtypes = [Map, i32, Planes, C.c_uint32, C.c_int32, f64, C.POINTER(C.c_uint32)] + [C.c_void_p] * 5
+        L.cape_host_pose_select.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cape_host_polygon_union_cut.argtypes = L.cape_host_polygon_union.argtypes
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
@@ -499,6 +526,64 @@ def host_pose_score(map_arrays, tracks, match, detected_planes, world_to_camera,
     if rc != 0:
         raise CapeError(f"cape_host_pose_score failed ({rc})")
     return scores[:len(T)], features, None if res is None else res[:len(T)]
+
+
+def host_pose_solve(map_arrays, tracks, match, detected_planes, x0=None, subsets=None, params=None, frame_flags=0, selection=None):
+    """cape_host_pose_solve of libcape_primitives.so: the twin of Extractor.map_pose_solve for ONE frame -- MINPACK's lmstr driver over
+    forward differences on the frame's pairs, one problem per row of x0 / subsets, on the rules the kernel compiles too.
+
+    map_arrays, tracks, match, detected_planes, frame_flags: as host_pose_score takes them; x0: (n_problems, 6) position then the three
+    quaternion coefficients; subsets: (n_problems, 4) uint32 words, bit i = the pair of kept plane i takes part; params: a
+    pose_solve_params(...) row or None for the defaults; selection: a POSE_SELECTION_DTYPE row instead of x0 and subsets (the refit of
+    POSE_SOLVE_FROM_SELECTION).
+    Returns (solutions: POSE_SOLUTION_DTYPE[n_problems], world_to_camera: float64[n_problems, 4, 4], n_rank_deficient: the problems in
+    which the pivoted qrfac ran)."""
+    L = _host_library()
+    src, src_view = _map_arrays(map_arrays, np.ascontiguousarray(tracks, MAP_TRACK_DTYPE))
+    n_map = len(src["planes"])
+    if len(src["tracks"]) != n_map:
+        raise CapeError("host_pose_solve: one track per map plane")
+    M = np.ascontiguousarray(match, np.int32).reshape(-1)
+    if len(M) != n_map:
+        raise CapeError("host_pose_solve: one match per map plane")
+    D = np.ascontiguousarray(detected_planes, np.float64).reshape(-1, 4)
+    det_view = _view(cape_host_planes, dict(planes=D), n=len(D))
+    if selection is not None:
+        sel = np.ascontiguousarray(selection, POSE_SELECTION_DTYPE).reshape(1)
+        X, S, n = None, None, 1
+    else:
+        sel = None
+        X = np.ascontiguousarray(x0, np.float64).reshape(-1, 6)
+        S = np.ascontiguousarray(subsets, np.uint32).reshape(-1, 4)
+        n = len(X)
+        if len(S) != n:
+            raise CapeError("host_pose_solve: one subset per start")
+    P = None if params is None else np.ascontiguousarray(params, POSE_SOLVE_PARAMS_DTYPE).reshape(1)
+    solutions = np.zeros(max(n, 1), POSE_SOLUTION_DTYPE)
+    poses = np.zeros((max(n, 1), 4, 4), np.float64)
+    count = C.c_int32(0)
+    rc = L.cape_host_pose_solve(C.byref(src_view), _as(M, C.c_int32), C.byref(det_view), frame_flags, n,
+                                None if X is None else _as(X, C.c_double), None if S is None else _as(S, C.c_uint32),
+                                None if sel is None else sel.ctypes.data, None if P is None else P.ctypes.data, solutions.ctypes.data,
+                                poses.ctypes.data, C.addressof(count))
+    if rc != 0:
+        raise CapeError(f"cape_host_pose_solve failed ({rc})")
+    return solutions[:n], poses[:n], int(count.value)
+
+
+def host_pose_select(scores, solutions):
+    """cape_host_pose_select: the twin of Extractor.map_pose_select for ONE frame -- the RANSAC bookkeeping over the frame's score rows
+    (POSE_SCORE_DTYPE[n_hypotheses]) and solution rows (POSE_SOLUTION_DTYPE[n_hypotheses]).  Returns a POSE_SELECTION_DTYPE scalar."""
+    L = _host_library()
+    sc = np.ascontiguousarray(scores, POSE_SCORE_DTYPE).reshape(-1)
+    so = np.ascontiguousarray(solutions, POSE_SOLUTION_DTYPE).reshape(-1)
+    if len(sc) != len(so):
+        raise CapeError("host_pose_select: one solution row per score row")
+    out = np.zeros(1, POSE_SELECTION_DTYPE)
+    rc = L.cape_host_pose_select(len(sc), sc.ctypes.data, so.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_pose_select failed ({rc})")
+    return out[0]
 
 
 def _union_rings(rows, slab):
@@ -891,6 +976,7 @@ EXPORTED_SYMBOLS = [
     "cape_map_maintain", "cape_map_retired_info", "cape_map_retired_download", "cape_map_retired_clear", "cape_map_step",
     "cape_map_step_visible", "cape_map_step_skip_words",
     "cape_map_pose_score", "cape_copy_pose_scores", "cape_pose_score_device",
+    "cape_map_pose_solve", "cape_copy_pose_solutions", "cape_pose_solve_device", "cape_map_pose_select", "cape_copy_pose_selection",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -1009,6 +1095,11 @@ def load_library():
     L.cape_map_pose_score.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_uint32, vp]
     L.cape_copy_pose_scores.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.cape_pose_score_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.cape_map_pose_solve.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_uint32, vp]
+    L.cape_copy_pose_solutions.argtypes = [vp, C.c_int32, vp, vp]
+    L.cape_pose_solve_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.cape_map_pose_select.argtypes = [vp, C.c_int32, vp]
+    L.cape_copy_pose_selection.argtypes = [vp, C.c_int32, vp]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1481,6 +1572,58 @@ class Extractor:
         features = np.zeros((n_frames, POSE_SCORE_MAX_PAIRS), POSE_FEATURE_DTYPE)
         _check(self.L, self.L.cape_copy_pose_scores(self.h, n_frames, None, features.ctypes.data_as(C.c_void_p), None), "cape_copy_pose_scores")
         return features
+
+    # ---- the pose solver on the same pairs: LM per (frame, hypothesis), the RANSAC selection, the refit from it ----
+    def map_pose_solve(self, n_frames, x0=None, subsets=None, params=None, flags=0, n_hypotheses=None, stream=0):
+        """cape_map_pose_solve: per frame of [0, n_frames) and per hypothesis one Levenberg-Marquardt minimisation over the pairs of the
+        last match_map_wide that the subset names.  x0: (n_frames, n_hypotheses, 6) position then the three quaternion coefficients;
+        subsets: (n_frames, n_hypotheses, 4) uint32 words, bit i = the pair of kept plane i; with POSE_SOLVE_DEVICE_INPUT both are device
+        addresses (int) and n_hypotheses is given; with POSE_SOLVE_FROM_SELECTION neither is read and one problem per frame comes from
+        the last map_pose_select.  params: a pose_solve_params(...) row or None.  The results are pose_solutions'."""
+        P = None if params is None else np.ascontiguousarray(params, POSE_SOLVE_PARAMS_DTYPE).reshape(1)
+        pp = None if P is None else P.ctypes.data_as(C.c_void_p)
+        if flags & POSE_SOLVE_FROM_SELECTION:
+            n_hypotheses, xp, sp = 1, None, None
+        elif flags & POSE_SOLVE_DEVICE_INPUT and not isinstance(x0, np.ndarray):
+            if n_hypotheses is None:
+                raise CapeError("map_pose_solve: n_hypotheses is required with device addresses")
+            xp, sp = C.c_void_p(int(x0)), C.c_void_p(int(subsets))
+        else:
+            X = np.ascontiguousarray(x0, np.float64)
+            S = np.ascontiguousarray(subsets, np.uint32)
+            n_hypotheses = X.size // (6 * n_frames) if n_hypotheses is None and n_frames > 0 else (n_hypotheses or 0)
+            if X.size != n_frames * n_hypotheses * 6 or S.size != n_frames * n_hypotheses * 4:
+                raise CapeError("map_pose_solve: x0 must hold n_frames x n_hypotheses x 6 doubles and subsets x 4 words")
+            xp, sp = X.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p)
+        _check(self.L, self.L.cape_map_pose_solve(self.h, n_frames, n_hypotheses, xp, sp, pp, flags, C.c_void_p(stream)), "cape_map_pose_solve")
+        self.pose_solve_hypotheses = n_hypotheses
+
+    def pose_solutions(self, n_frames):
+        """(POSE_SOLUTION_DTYPE[n_frames, n_hypotheses], world_to_camera float64[n_frames, n_hypotheses, 4, 4]) of the last map_pose_solve"""
+        n_hyp = getattr(self, "pose_solve_hypotheses", 0)
+        rows = np.zeros((n_frames, max(n_hyp, 1)), POSE_SOLUTION_DTYPE)
+        poses = np.zeros((n_frames, max(n_hyp, 1), 4, 4), np.float64)
+        _check(self.L, self.L.cape_copy_pose_solutions(self.h, n_frames, rows.ctypes.data_as(C.c_void_p), poses.ctypes.data_as(C.c_void_p)),
+               "cape_copy_pose_solutions")
+        return rows[:, :n_hyp], poses[:, :n_hyp]
+
+    def pose_solve_device(self):
+        """device addresses (solutions, world_to_camera) of the last map_pose_solve: the second is what map_pose_score takes with
+        POSE_SCORE_DEVICE_POSES"""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self.L, self.L.cape_pose_solve_device(self.h, C.byref(a), C.byref(b)), "cape_pose_solve_device")
+        return a.value, b.value
+
+    def map_pose_select(self, n_frames, stream=0):
+        """cape_map_pose_select: per frame the RANSAC bookkeeping over the current score rows and solution rows.  The results are
+        pose_selection's."""
+        _check(self.L, self.L.cape_map_pose_select(self.h, n_frames, C.c_void_p(stream)), "cape_map_pose_select")
+
+    def pose_selection(self, n_frames):
+        """POSE_SELECTION_DTYPE[n_frames] of the last map_pose_select"""
+        rows = np.zeros(max(n_frames, 1), POSE_SELECTION_DTYPE)
+        _check(self.L, self.L.cape_copy_pose_selection(self.h, n_frames, rows.ctypes.data_as(C.c_void_p)), "cape_copy_pose_selection")
+        return rows[:n_frames]
 
     # ---- the polygon half of the map update (needs map_kalman of the batch) ----
     def map_union(self, n_frames, stream=0):
