@@ -1,7 +1,9 @@
 """cape_map_pose_solve and cape_map_pose_select on the device against their host twins cape_host_pose_solve / cape_host_pose_select,
 which compile the same rules header (csrc/cape_pose_solve.h).  The minimiser is + - x / sqrt in one order, no transcendental function:
 solution rows, the pose buffer and the selection rows must equal the twin's BIT FOR BIT, on the device's own match.  The score rows in
-the middle of the chain are cape_map_pose_score's and are held to what tests/test_gpu_pose_score.py holds them to.
+the middle of the chain are cape_map_pose_score's and are held to what tests/test_gpu_pose_score.py holds them to.  The same holds off
+the default path: the parameter sets and camera bases of tests/test_pose_solve_host.py, a lane that takes the pivoted rank-deficient
+branch among lanes that do not, and a lane whose first evaluation overflows.
 
 Every test prints its figures before it asserts (`pytest -s`)."""
 import ctypes as C
@@ -10,7 +12,7 @@ import math
 import numpy as np
 import pytest
 from test_gpu_pose_score import _compare_with_twin, _det_planes, _hypotheses, _tracks_for
-from test_pose_solve_host import pose_of
+from test_pose_solve_host import BASES, CONVERGED, PARAMETER_SETS, STATUSES, pose_of
 
 pytestmark = pytest.mark.gpu
 
@@ -18,11 +20,12 @@ W = 128
 EYE = (np.eye(3), np.zeros(3))
 
 
-def _x_of(w2c):
-    """x[6] of a world-to-camera matrix under the identity camera basis: the position, then the coefficients (w, x, y) / (1 + z) of
-    get_optimization_coefficients_from_quaternion"""
-    R = w2c[:3, :3].T
-    p = -(R @ w2c[:3, 3])
+def _x_of(w2c, C=np.eye(3)):
+    """x[6] of a world-to-camera matrix under the camera basis C (world-to-camera rotation M^T with M = C R, position pw = C p): the
+    position p, then the coefficients (w, x, y) / (1 + z) of get_optimization_coefficients_from_quaternion for R"""
+    M = w2c[:3, :3].T
+    R = C.T @ M
+    p = C.T @ -(M @ w2c[:3, 3])
     w = math.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2.0
     q = np.array([w, (R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w)])
     return np.concatenate([p, q[:3] / max(1.0 + q[3], 0.001)])
@@ -35,11 +38,12 @@ def _words(kept_planes):
     return w
 
 
-def _starts(rng, base, n_hyp, shift=40.0, turn=0.03):
-    """(n, n_hyp, 6): per frame its own x perturbed by tens of mm and a few degrees (0.03 in a coefficient is about 3.4 degrees)"""
+def _starts(rng, base, n_hyp, shift=40.0, turn=0.03, C=np.eye(3)):
+    """(n, n_hyp, 6): per frame its own x under the basis C perturbed by tens of mm and a few degrees (0.03 in a coefficient is about
+    3.4 degrees)"""
     out = np.empty((len(base), n_hyp, 6))
     for f, T in enumerate(base):
-        x = _x_of(T)
+        x = _x_of(T, C)
         for h in range(n_hyp):
             out[f, h] = x + np.concatenate([rng.uniform(-shift, shift, 3), rng.uniform(-turn, turn, 3)])
     return out
@@ -302,6 +306,228 @@ def test_host_and_device_inputs_give_the_same_bytes(checker):
     assert rows.tobytes() == host_route[0].tobytes() and poses.tobytes() == host_route[1].tobytes() and (rows["status"] > 0).any()
     a, b = c.ex.pose_solve_device()
     assert a and b
+
+
+# ---- off the default path: the camera basis and the parameter sets of tests/test_pose_solve_host.py -------------------------------
+def _orientation_subsets(rng, det, match_row, sizes):
+    """(len(sizes), 4) words: subsets of the frame's matched kept planes of the given sizes, each holding three planes whose normals
+    are pairwise more than acos(0.9) apart (the checkerboard's four orientations: any three of them are independent), so that every
+    problem has a minimum the stop codes of the table can be asserted at"""
+    paired = match_row[match_row >= 0]
+    normals = np.array([det[i][0] for i in paired])
+    out = np.zeros((len(sizes), 4), np.uint32)
+    for h, size in enumerate(sizes):
+        order = rng.permutation(len(paired))
+        apart = []
+        for k in order:
+            if len(apart) < 3 and all(abs(float(normals[k] @ normals[j])) < 0.9 for j in apart):
+                apart.append(k)
+        assert len(apart) == 3
+        rest = [k for k in order if k not in apart][: max(0, min(size, len(paired)) - 3)]
+        out[h] = _words(paired[apart + rest])
+    return out
+
+
+OFF_SIZES = (3,) * 6 + (5,) * 5 + (39,) * 5  # 16 problems per frame
+
+
+def _noisy_map(det, seed=405):
+    """The checkerboard's own kept planes as a map that a solver has something to do on: lifted by a camera pose that is not the
+    identity (a turn of 0.05 about (1, 2, 3), 150 mm away), normals disturbed by 1e-3 and distances by 2 mm as make_frame of the
+    host test disturbs them.  Returns (map planes, the world-to-camera matrix they were lifted by).
+    (The fixture's own map is the exact lift under the identity pose: residuals that go to exactly 0 at x = 0, where gnorm, scaled
+    by fnorm, never falls below gtol and xnorm makes xtol unreachable -- MINPACK's stop codes of the host table do not occur on it.)"""
+    from test_gpu_map_match import _lift, _w2c
+
+    a = np.array([1.0, 2.0, 3.0]) / math.sqrt(14.0)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    R, o = np.eye(3) + math.sin(0.05) * K + (1.0 - math.cos(0.05)) * (K @ K), np.array([120.0, -80.0, 45.0])
+    rng = np.random.default_rng(seed)
+    planes = []
+    for k in det:
+        n, d, x, y, c, ring, holes = _lift(k, R, o)
+        n = n + rng.normal(scale=1e-3, size=3)
+        planes.append((n / np.linalg.norm(n), d + float(rng.normal(scale=2.0)), x, y, c, ring, holes))
+    return planes, _w2c(R, o)
+
+
+@pytest.mark.parametrize("name", list(PARAMETER_SETS))
+def test_parameter_sets_under_three_camera_bases(checker, name):
+    """one call per basis: the starts describe, under that basis, the pose the match was made under (perturbed), so the problems
+    converge to the same camera; rows and poses are the twin's bytes, the statuses those the reference has on the host"""
+    import cape_amd
+
+    c = checker
+    planes, w2c = _noisy_map(c.kept[1][0])
+    arrays, W2C = cape_amd.pack_map(planes[::-1]), np.stack([w2c] * 2)
+    try:
+        c.ex.upload_map(arrays)
+        c.ex.upload_tracks(c.tracks)
+        c.ex.match_map_wide(2, W2C, None, c.flags, c.st)
+        _, match, _, _ = c.ex.map_matches_wide(2)
+        assert 65 <= int((match[1] >= 0).sum()) <= W
+        rows_of = {}
+        for basis, Cb in BASES.items():
+            rng = np.random.default_rng(400)  # (the same subsets and the same perturbations under every basis)
+            assert np.abs(pose_of(_x_of(w2c, Cb), Cb) - w2c).max() < 1e-9, "the start's coefficients describe the match's pose"
+            x0 = _starts(rng, W2C, len(OFF_SIZES), C=Cb)
+            subsets = np.stack([np.zeros((len(OFF_SIZES), 4), np.uint32), _orientation_subsets(rng, c.kept[1][0], match[1], OFF_SIZES)])
+            params = cape_amd.pose_solve_params(camera_basis=Cb, **PARAMETER_SETS[name])
+            rows, poses = _solve_and_compare(c.ex, 2, c.st, arrays, c.tracks, c.kept, x0, subsets, params)
+            print(f"\n{name}, {basis}: {_summary(rows[1])}; flags {sorted(set(rows[1]['flags'].tolist()))}")
+            assert rows[1]["n_pairs_used"].tolist() == list(OFF_SIZES) and not rows[1]["flags"].any()
+            status = rows[1]["status"]
+            if name == "ftol=xtol=0":
+                assert np.isin(status, (6, 7, 8)).all() and (rows[1]["nfev"] < 400).all()
+            else:
+                assert np.isin(status, sorted(STATUSES[name])).all(), status.tolist()
+            for h in range(len(OFF_SIZES)):
+                assert np.array_equal(poses[1, h], pose_of(rows[1, h]["x"], Cb))
+            rows_of[basis] = (rows, poses)
+        # the basis is read: the same problems under another basis are other rows and other poses, bit for bit ...
+        for basis in ("permutation", "rotated"):
+            assert all(rows_of[basis][0][1, h].tobytes() != rows_of["identity"][0][1, h].tobytes() for h in range(len(OFF_SIZES)))
+            assert all(rows_of[basis][1][1, h].tobytes() != rows_of["identity"][1][1, h].tobytes() for h in range(len(OFF_SIZES)))
+        # ... of the same camera: where the iteration runs to its end the poses agree to what the tolerances leave
+        if STATUSES.get(name) == CONVERGED or name == "ftol=xtol=0":
+            apart = max(float(np.abs(rows_of[basis][1][1] - rows_of["identity"][1][1]).max()) for basis in ("permutation", "rotated"))
+            print(f"{name}: poses under the three bases at most {apart:.3e} apart")
+            assert apart < 1.0, "a millimetre: a transposed or mis-strided basis ends at another camera, metres away"
+    finally:
+        c.restore()
+
+
+# ---- the rank-deficient branch and NOT_FINITE on the device -------------------------------------------------------------------
+def _slabs_and_facets(width=640, height=480):
+    """a depth frame of six planes: in the upper half three fronto-parallel slabs side by side, constant depths near 800, 1500 and
+    2600 mm; in the lower half three tilted facets of the checkerboard's kind whose normals are independent.  With the noise of
+    test_gpu_match_wide._perforated_wall."""
+    from cape_amd import synth
+
+    intr = synth.DEFAULT_INTRINSICS
+    X, Y = np.meshgrid((np.arange(width) - intr["cx"]) / intr["fx"], (np.arange(height) - intr["cy"]) / intr["fy"])
+    z = np.zeros((height, width))
+    edges = [0, width // 3, 2 * width // 3, width]
+    for k, (d, (nx, ny)) in enumerate(zip((800.0, 1500.0, 2600.0), ((0.5, 0.0), (-0.5, 0.0), (0.0, 0.5)))):
+        cols = slice(edges[k], edges[k + 1])
+        z[: height // 2, cols] = d
+        z[height // 2:, cols] = (2000.0 + 240.0 * k) / (1.0 + nx * X[height // 2:, cols] + ny * Y[height // 2:, cols])
+    return np.round(z + np.random.default_rng(5).normal(0, 0.6, (height, width))).astype(np.float32)
+
+
+def _snap(v):
+    """the signed unit vector of v's largest component"""
+    out = np.zeros(3)
+    k = int(np.argmax(np.abs(v)))
+    out[k] = 1.0 if v[k] > 0 else -1.0
+    return out
+
+
+def _slab_pose():
+    """camera to world (R, o): a turn of 0.004 about (1, 2, 3) and a few millimetres.  Not the identity: at a minimum whose position or
+    whose last two coefficients are 0 the forward differences' steps sqrt(eps) |x_j| underflow against the residuals, the columns come
+    out exactly 0 and a full-rank problem takes the pivoted branch in its last iterations (as it does in MINPACK's fdjac2):
+    tests/test_pose_solve_host.py::test_the_slab_frame_of_the_device_test_on_the_host measures both on the twin."""
+    a = np.array([1.0, 2.0, 3.0]) / math.sqrt(14.0)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + math.sin(0.004) * K + (1.0 - math.cos(0.004)) * (K @ K), np.array([7.0, 5.0, 3.0])
+
+
+def _slab_map(det, pose=None):
+    """the map of a frame's own kept planes lifted by _slab_pose (or by `pose`), the fronto-parallel ones with normal and in-plane axes
+    snapped to exact unit vectors and d = -(n . c), which leaves their detections tilted by about 0.003 against them: returns (map
+    planes, the kept planes that are slabs)"""
+    from test_gpu_map_match import _lift
+
+    planes, slabs = [], []
+    for i, k in enumerate(det):
+        n, d, x, y, c, ring, holes = _lift(k, *(_slab_pose() if pose is None else pose))
+        if abs(n[2]) > 0.999:
+            n, x, y = _snap(n), _snap(x), _snap(y)
+            d = float(-(n @ c))
+            slabs.append(i)
+        planes.append((n, d, x, y, c, ring, holes))
+    return planes, slabs
+
+
+DEGENERATE_START = np.array([10.0, -20.0, 0.0, 1.0, 0.0, 0.0])
+
+
+@pytest.fixture(scope="module")
+def slabs():
+    """one 640 x 480 frame of three fronto-parallel slabs and three tilted facets against the map of its own kept planes, matched
+    under the pose the map was lifted by.  A problem over the three slabs alone has map normals (0, 0, +-1) exactly: the columns of
+    x and y are exactly 0 whatever the rotation, and from a start with the identity rotation the first coefficient's too -- the
+    pivoted qrfac, the nsing < 6 arms of lmpar and qrsolv and a pivot vector that is not the identity; its minimum is not at the
+    start's rotation.  The facets make the other problems of the same wave full rank.  (The slabs alone would not: with three
+    parallel planes every start is rank deficient.)"""
+    import cape_amd
+    from cape_amd import synth
+    from test_gpu_map_match import _w2c
+    from test_gpu_match_map_wide import _extract
+
+    s = _Set()
+    s.n = 1
+    s.ex, s.st = _extract(_slabs_and_facets()[None], 640, 480, synth.DEFAULT_INTRINSICS)
+    s.kept = s.ex.kept_planes(1)
+    det = s.kept[0][0]
+    planes, s.slabs = _slab_map(det)
+    assert len(det) == 6 and len(s.slabs) == 3
+    s.facets = [i for i in range(6) if i not in s.slabs]
+    s.arrays, s.tracks = cape_amd.pack_map(planes), _tracks_for(np.random.default_rng(410), len(planes))
+    s.W2C = _w2c(*_slab_pose())[None]
+    s.ex.upload_map(s.arrays)
+    s.ex.upload_tracks(s.tracks)
+    s.ex.match_map_wide(1, s.W2C, None, cape_amd.MATCH_ALLOW_INDEX0, s.st)
+    _, s.match, _, _ = s.ex.map_matches_wide(1)
+    assert sorted(s.match[0][:6].tolist()) == list(range(6)), "every plane finds itself"
+    yield s
+    s.ex.close()
+
+
+def _slab_problems(s, rng, lane):
+    """16 problems: the degenerate one over the three slabs in `lane`, around it the three facets with some of the slabs from starts
+    turned by a few degrees"""
+    x0 = _starts(rng, s.W2C, 16)
+    x0[0, lane] = DEGENERATE_START
+    subsets = np.array([[_words(s.facets + [i for i in s.slabs if rng.random() < 0.5]) for _ in range(16)]], np.uint32)
+    subsets[0, lane] = _words(s.slabs)
+    return x0, subsets
+
+
+def test_a_rank_deficient_lane_among_full_rank_lanes(slabs):
+    import cape_amd
+
+    s, lane = slabs, 5
+    x0, subsets = _slab_problems(s, np.random.default_rng(420), lane)
+    rows, poses = _solve_and_compare(s.ex, 1, s.st, s.arrays, s.tracks, s.kept, x0, subsets)
+    row = rows[0, lane]
+    print(f"\nslabs: {_summary(rows[0])}; flags {rows[0]['flags'].tolist()}; the degenerate lane: status {row['status']}, nfev {row['nfev']}, "
+          f"fnorm {row['fnorm0']:.4g} -> {row['fnorm']:.4g}, x {row['x'].tolist()}")
+    others = np.arange(16) != lane
+    assert row["flags"] == cape_amd.POSE_SOLVE_RANK_DEFICIENT and not rows[0, others]["flags"].any()
+    assert row["status"] > 0 and row["n_pairs_used"] == 3 and np.array_equal(row["x"][:2], DEGENERATE_START[:2])
+    assert np.isin(rows[0, others]["status"], (1, 2, 3)).all() and (rows[0, others]["n_pairs_used"] >= 3).all()
+    # alone it gives the bytes it gives in company
+    s.ex.map_pose_solve(1, x0[:, lane: lane + 1], subsets[:, lane: lane + 1], stream=s.st)
+    alone, alone_poses = s.ex.pose_solutions(1)
+    assert alone[0, 0].tobytes() == row.tobytes() and alone_poses[0, 0].tobytes() == poses[0, lane].tobytes()
+
+
+def test_a_lane_that_overflows_among_converging_lanes(slabs):
+    """x0[0] = 1e160: the residuals' squares overflow at the first evaluation -- CAPE_POSE_SOLVE_NOT_FINITE, arithmetic and no fault;
+    the infinite fnorm0 compares as bytes"""
+    import cape_amd
+
+    s, lane = slabs, 9
+    x0, subsets = _slab_problems(s, np.random.default_rng(430), 5)
+    x0[0, lane, 0] = 1e160
+    rows, poses = _solve_and_compare(s.ex, 1, s.st, s.arrays, s.tracks, s.kept, x0, subsets)
+    row = rows[0, lane]
+    print(f"\nslabs: {_summary(rows[0])}; the overflowing lane: status {row['status']}, nfev {row['nfev']}, fnorm0 {row['fnorm0']}")
+    assert row["status"] == cape_amd.POSE_SOLVE_NOT_FINITE and row["nfev"] == 1 and row["iterations"] == 0
+    assert np.array_equal(row["x"], x0[0, lane]) and np.isposinf(row["fnorm0"]) and np.array_equal(poses[0, lane], pose_of(x0[0, lane]))
+    assert (rows[0, np.arange(16) != lane]["status"] > 0).all()
 
 
 def test_no_pairs_a_flagged_frame_and_an_empty_map():

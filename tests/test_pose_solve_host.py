@@ -7,7 +7,13 @@ lmstr folds the Jacobian's rows by Givens rotations where lmdif factors the dens
 agree to rounding at every step and to the termination tolerances at the end, not bit for bit: the largest differences over this
 file's own problems were measured once (the *_MEASURED constants below) and ten times that is asserted -- ten and not two because the
 tail is heavy: reversing the row order in scipy alone, which changes rounding only, moves the end point by a median of 9e-8 mm but by
-up to 6.5e-4 mm.  The exact cases (statuses, refusals, the pivoted qrfac branch, the selection rule) are asserted as such.  CPU only."""
+up to 6.5e-4 mm.  The exact cases (statuses, refusals, the pivoted qrfac branch, the selection rule) are asserted as such.
+
+Off the default path the same comparison runs per parameter set (mode = 2, gtol, zero and loose tolerances, epsfcn, a step bound that
+binds) under three camera bases, with the stop codes MINPACK itself ends on; the two rank-deficient problems are compared with
+MINPACK in fnorm and in the coordinates that must not move; CAPE_POSE_SOLVE_NOT_FINITE is reached at both of its sites.  Every
+assertion on scipy alone stands in a test of its own, in front of the test that looks at the twin.  The blocks of the minimiser have
+tests/test_pose_lm_blocks_host.py.  CPU only."""
 import math
 
 import numpy as np
@@ -62,8 +68,9 @@ def _unit(rng):
     return v / np.linalg.norm(v)
 
 
-def make_frame(seed, n=128):
-    """a seeded synthetic map of n planes, all matched: (planes, map arrays, tracks, detections, the true x)"""
+def make_frame(seed, n=128, C=np.eye(3)):
+    """a seeded synthetic map of n planes, all matched, seen under the camera basis C: (planes, map arrays, tracks, detections, the true
+    x, the generator)"""
     import cape_amd
 
     rng = np.random.default_rng(seed)
@@ -76,7 +83,7 @@ def make_frame(seed, n=128):
         tracks[j]["id"] = 1000 + 7 * j
     arrays = (P, np.zeros(0, cape_amd.MAP_RING_DTYPE), np.zeros((0, 2)))
     x_true = np.concatenate([rng.uniform(-300.0, 300.0, 3), np.array([1.0, 0.0, 0.0]) + rng.uniform(-0.2, 0.2, 3)])
-    qn, qd = planes_to_camera(pose_of(x_true), planes)
+    qn, qd = planes_to_camera(pose_of(x_true, C), planes)
     qn = qn + rng.normal(scale=1e-3, size=qn.shape)
     detected = np.column_stack([qn / np.linalg.norm(qn, axis=1)[:, None], qd + rng.normal(scale=2.0, size=n)])
     return planes, arrays, tracks, detected, x_true, rng
@@ -152,6 +159,170 @@ def test_twin_against_scipy(problems):
         assert np.array_equal(p["pose"][3], [0, 0, 0, 1])
 
 
+# ---- off the default path: the camera basis, mode = 2, gtol, the stop codes of zero and of loose tolerances, epsfcn, the step bound
+PERMUTATION = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])  # a signed permutation: its products are exact
+ROTATED = np.array([[math.cos(0.3), -math.sin(0.3), 0.0], [math.sin(0.3), math.cos(0.3), 0.0], [0.0, 0.0, 1.0]]) @ PERMUTATION  # M = C R rounds
+BASES = {"identity": np.eye(3), "permutation": PERMUTATION, "rotated": ROTATED}
+OFF_SIZES = (3, 5, 39)
+SMALL_FACTOR = 0.01  # (0.1 and 1.0 never bind the first step on these problems: test_scipy_alone_off_the_defaults asserts that this one does)
+PARAMETER_SETS = {  # name: what both solvers are given beside the defaults; mode = 2 is scipy's diag = ones
+    "defaults": {},
+    # (with factor = 100 the step bound never binds on these problems, par stays 0 and the scaling never reaches the step: mode = 2
+    # alone gives the default's x and nfev bit for bit.  Under SMALL_FACTOR the bound binds and the scaling decides the step)
+    "mode=2": dict(mode=2, factor=SMALL_FACTOR),
+    "gtol=1e-3": dict(gtol=1e-3),
+    "ftol=xtol=0": dict(ftol=0.0, xtol=0.0),
+    "ftol=1e-4, xtol=0": dict(ftol=1e-4, xtol=0.0),
+    "ftol=0, xtol=1e-4": dict(ftol=0.0, xtol=1e-4),
+    "epsfcn=1e-8": dict(epsfcn=1e-8),
+    "small factor": dict(factor=SMALL_FACTOR),
+}
+CONVERGED = {1, 2, 3}
+STATUSES = {"defaults": CONVERGED, "mode=2": CONVERGED, "gtol=1e-3": {4}, "ftol=1e-4, xtol=0": {1}, "ftol=0, xtol=1e-4": {2}, "epsfcn=1e-8": CONVERGED,
+            "small factor": CONVERGED}  # ("ftol=xtol=0": the reference's own code, or both among the stringent-tolerance codes 6, 7, 8)
+# the two rows that stop early, far from the minimum (see test_twin_against_scipy_off_the_defaults)
+EARLY_STOP = ("gtol=1e-3", "ftol=1e-4, xtol=0")
+# the largest differences between the twin and scipy per parameter set, over the three bases x 24 problems (measured with this file on
+# the host; printed by test_twin_against_scipy_off_the_defaults before it asserts): |dposition| mm, |dcoefficient|, relative |dfnorm|
+OFF_DEFAULT_MEASURED = {
+    "defaults": (1.212e-04, 4.066e-10, 5.293e-11),
+    "mode=2": (1.383e-04, 5.620e-10, 4.190e-12),
+    "gtol=1e-3": (2.013e-04, 4.268e-10, 3.856e-10),
+    "ftol=xtol=0": (1.212e-04, 3.349e-10, 5.293e-11),
+    "ftol=1e-4, xtol=0": (1.121e-04, 3.809e-10, 3.822e-11),
+    "ftol=0, xtol=1e-4": (1.121e-04, 3.809e-10, 3.822e-11),
+    "epsfcn=1e-8": (1.057e-08, 9.797e-14, 9.680e-14),
+    "small factor": (9.817e-05, 4.717e-10, 7.310e-12),
+}
+
+
+def _scipy_arguments(given):
+    kw = dict(ftol=EPS, xtol=EPS, gtol=0.0, maxfev=400, epsfcn=None, factor=100)
+    kw.update({k: v for k, v in given.items() if k != "mode"})
+    if given.get("mode") == 2:
+        kw["diag"] = np.ones(6)
+    return kw
+
+
+@pytest.fixture(scope="module")
+def off_default_frames():
+    """per basis FRAMES seeded frames whose detections were made under that basis, each with one problem per size of OFF_SIZES"""
+    out = {}
+    for basis, C in BASES.items():
+        out[basis] = []
+        for f in range(FRAMES):
+            planes, arrays, tracks, detected, x_true, rng = make_frame(200 + f, C=C)
+            picks = [np.sort(rng.choice(len(planes), size, replace=False)) for size in OFF_SIZES]
+            starts = np.array([x_true + np.concatenate([_unit(rng) * rng.uniform(20.0, 60.0), rng.uniform(-0.02, 0.02, 3)]) for _ in OFF_SIZES])
+            out[basis].append(dict(planes=planes, arrays=arrays, tracks=tracks, detected=detected, picks=picks, starts=starts))
+    return out
+
+
+@pytest.fixture(scope="module")
+def off_default_reference(off_default_frames):
+    """scipy alone: {(parameter set, basis): [per problem x, fnorm, nfev, ier, x0]}"""
+    from scipy.optimize import leastsq
+
+    out = {}
+    for basis, frames in off_default_frames.items():
+        for name, given in PARAMETER_SETS.items():
+            rows = []
+            for fr in frames:
+                for pick, x0 in zip(fr["picks"], fr["starts"]):
+                    ref = leastsq(residuals, x0, args=(fr["planes"][pick], fr["detected"][pick], BASES[basis]), full_output=True, **_scipy_arguments(given))
+                    rows.append(dict(x0=x0, x=ref[0], fnorm=float(np.linalg.norm(ref[2]["fvec"])), nfev=int(ref[2]["nfev"]), ier=int(ref[4])))
+            out[name, basis] = rows
+    return out
+
+
+def _twin_rows(host, frames, C, given):
+    rows, poses = [], []
+    for fr in frames:
+        r, p, _ = host.host_pose_solve(fr["arrays"], fr["tracks"], np.arange(len(fr["planes"]), dtype=np.int32), fr["detected"], fr["starts"],
+                                       np.array([words_of(pick) for pick in fr["picks"]], np.uint32), params=host.pose_solve_params(camera_basis=C, **given))
+        rows.extend(r)
+        poses.extend(p)
+    return rows, poses
+
+
+@pytest.fixture(scope="module")
+def off_default_twin(host, off_default_frames):
+    return {(name, basis): _twin_rows(host, off_default_frames[basis], BASES[basis], given) for basis in BASES for name, given in PARAMETER_SETS.items()}
+
+
+def test_scipy_alone_off_the_defaults(off_default_reference):
+    # (the reference alone, before the twin is looked at: every row of the table holds for MINPACK itself)
+    ref = off_default_reference
+    for (name, basis), rows in ref.items():
+        ier, nfev = sorted({r["ier"] for r in rows}), [r["nfev"] for r in rows]
+        print(f"scipy, {name}, {basis}: ier {ier}, nfev {min(nfev)}..{max(nfev)}")
+        assert len(rows) == FRAMES * len(OFF_SIZES)
+        if name == "ftol=xtol=0":
+            assert set(ier) <= {6, 7, 8} and max(nfev) < 400
+        else:
+            assert set(ier) <= STATUSES[name], (name, basis, ier)
+        travel = [float(np.linalg.norm(r["x"][:3] - r["x0"][:3])) for r in rows]
+        assert max(travel) >= 30.0
+    for basis in BASES:
+        # the step bound of SMALL_FACTOR binds: it costs the reference evaluations; and the two early stops end before the default does
+        default = [r["nfev"] for r in ref["defaults", basis]]
+        assert any(a != b for a, b in zip([r["nfev"] for r in ref["small factor", basis]], default)), basis
+        # ... and under that bound the scaling is read: diag = 1 gives another iterate than the columns' norms on every problem
+        assert all(not np.array_equal(a["x"], b["x"]) for a, b in zip(ref["mode=2", basis], ref["small factor", basis])), basis
+        assert any(a["nfev"] != b["nfev"] for a, b in zip(ref["mode=2", basis], ref["small factor", basis])), basis
+        for name in EARLY_STOP:
+            assert all(a["nfev"] <= b for a, b in zip(ref[name, basis], default)) and any(a["nfev"] < b for a, b in zip(ref[name, basis], default))
+
+
+def test_twin_against_scipy_off_the_defaults(off_default_reference, off_default_twin):
+    """every parameter set under every basis: the statuses the reference has, distances as test_twin_against_scipy takes them.  The two
+    early stops (gtol = 1e-3; ftol = 1e-4 with xtol = 0) end where the iteration is still moving, and still need no more than the
+    others: the twin stops at the reference's own evaluation, which is asserted, and the two are compared in full like every row"""
+    failures = []
+    for name in PARAMETER_SETS:
+        d_pos = d_coef = d_fnorm = 0.0
+        for basis in BASES:
+            ref, (rows, poses) = off_default_reference[name, basis], off_default_twin[name, basis]
+            for p, row in zip(ref, rows):
+                d_pos = max(d_pos, float(np.abs(row["x"][:3] - p["x"][:3]).max()))
+                d_coef = max(d_coef, float(np.abs(row["x"][3:] - p["x"][3:]).max()))
+                d_fnorm = max(d_fnorm, abs(float(row["fnorm"]) - p["fnorm"]) / p["fnorm"])
+            statuses = sorted({int(r["status"]) for r in rows})
+            nfev = [int(r["nfev"]) for r in rows]
+            print(f"twin, {name}, {basis}: statuses {statuses}, nfev {min(nfev)}..{max(nfev)}; scipy ier {sorted({p['ier'] for p in ref})}, "
+                  f"nfev equal on {sum(int(r['nfev']) == p['nfev'] for p, r in zip(ref, rows))} of {len(rows)}")
+            for p, row in zip(ref, rows):
+                if name == "ftol=xtol=0":
+                    assert row["status"] == p["ier"] or {int(row["status"]), p["ier"]} <= {6, 7, 8}
+                    assert row["nfev"] < 400
+                else:
+                    assert int(row["status"]) in STATUSES[name], (name, basis, int(row["status"]))
+                if name in EARLY_STOP:
+                    assert row["status"] == p["ier"] and row["nfev"] == p["nfev"]
+                assert row["flags"] == 0 and row["fnorm"] <= row["fnorm0"] and row["iterations"] >= 1
+        want = OFF_DEFAULT_MEASURED[name]
+        print(f"twin vs scipy, {name}: |dposition| {d_pos:.3e} mm, |dcoefficient| {d_coef:.3e}, relative |dfnorm| {d_fnorm:.3e}")
+        if not (d_pos <= 10 * want[0] and d_coef <= 10 * want[1] and d_fnorm <= 10 * want[2]):
+            failures.append(name)
+        # the bound stays orders of magnitude below what the solver has to travel: one that does not move fails
+        assert 10 * want[0] <= 60.0 * 1e-3 and 10 * want[1] <= 0.02 * 1e-3
+    assert not failures, failures
+
+
+def test_the_camera_basis_is_read(host, off_default_frames, off_default_twin):
+    rows, poses = off_default_twin["defaults", "rotated"]
+    for row, pose in zip(rows, poses):
+        # the pose that goes with the row is the pose of its x under the basis, to the bit
+        assert np.array_equal(pose, pose_of(row["x"], ROTATED)) and not np.array_equal(pose, pose_of(row["x"]))
+    # the same inputs under the identity basis: another problem, another result
+    other, _ = _twin_rows(host, off_default_frames["rotated"], np.eye(3), {})
+    # (the minimum's fnorm is the same up to rounding: every rigid transform has coefficients under either basis)
+    assert all(not np.array_equal(a["x"], b["x"]) and a.tobytes() != b.tobytes() for a, b in zip(rows, other))
+    # ... and the permutation, whose products are exact, gives the pose of its x too
+    rows, poses = off_default_twin["defaults", "permutation"]
+    assert all(np.array_equal(pose, pose_of(row["x"], PERMUTATION)) for row, pose in zip(rows, poses))
+
+
 def test_maxfev_of_seven_ends_with_status_five(host):
     from scipy.optimize import leastsq
 
@@ -222,6 +393,150 @@ def test_parallel_planes_take_the_pivoted_qrfac_branch(host):
     planes, arrays2, tracks2, det2, x_true, rng = make_frame(9)
     _, _, none = host.host_pose_solve(arrays2, tracks2, np.arange(128, dtype=np.int32), det2, x_true[None], np.array([words_of([1, 2, 3])], np.uint32))
     assert none == 0
+
+
+def _tilted(a, b, d):
+    n = np.array([a, b, 1.0])
+    return [*(n / math.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])), d]
+
+
+# three parallel map planes and a start with the identity rotation under the identity basis.  Untilted: the Jacobian's columns of x, y
+# and of the first coefficient (the rotation about the common normal) are exactly 0 at the start and stay so: rank 3.  Tilted: the
+# detections lean by about 0.01 off the axis, each its own way, so the minimum is not at the start's rotation and the solver leaves
+# the exactly degenerate configuration with its first step; x and y stay unobservable (a plane's distance does not depend on them).
+PARALLEL_MAP = np.array([[0.0, 0.0, 1.0, 800.0], [0.0, 0.0, 1.0, 1500.0], [0.0, 0.0, 1.0, 2600.0]])
+PARALLEL_START = np.array([10.0, -20.0, 0.0, 1.0, 0.0, 0.0])
+RANK_DEFICIENT = {
+    "untilted": np.array([[0.0, 0.0, 1.0, 790.0], [0.0, 0.0, 1.0, 1492.0], [0.0, 0.0, 1.0, 2589.0]]),
+    "tilted": np.array([_tilted(0.01, 0.0, 790.0), _tilted(0.0, 0.01, 1492.0), _tilted(-0.007, -0.007, 2589.0)]),
+}
+
+
+@pytest.fixture(scope="module")
+def rank_deficient_reference():
+    from scipy.optimize import leastsq
+
+    out = {}
+    for name, detected in RANK_DEFICIENT.items():
+        ref = leastsq(residuals, PARALLEL_START, args=(PARALLEL_MAP, detected), full_output=True, ftol=EPS, xtol=EPS, gtol=0.0, maxfev=400)
+        out[name] = dict(x=ref[0], ier=int(ref[4]), nfev=int(ref[2]["nfev"]), fnorm0=float(np.linalg.norm(residuals(PARALLEL_START, PARALLEL_MAP, detected))),
+                         fnorm=float(np.linalg.norm(ref[2]["fvec"])))
+    return out
+
+
+def test_scipy_alone_on_the_rank_deficient_problems(rank_deficient_reference):
+    # (the reference alone, before the twin is looked at)
+    for name, ref in rank_deficient_reference.items():
+        print(f"scipy, {name}: ier {ref['ier']}, nfev {ref['nfev']}, fnorm {ref['fnorm0']:.4g} -> {ref['fnorm']:.4g}, x {ref['x'].tolist()}")
+        assert ref["ier"] == 1 and ref["fnorm"] < 0.8 * ref["fnorm0"]
+        assert np.array_equal(ref["x"][:2], PARALLEL_START[:2]), "MINPACK gives the unobservable directions a zero step"
+    # the tilted problem's minimum is not at the start's rotation, and its iteration is the longer one
+    assert np.abs(rank_deficient_reference["tilted"]["x"][3:] - PARALLEL_START[3:]).max() > 1e-3
+    assert np.abs(rank_deficient_reference["untilted"]["x"][3:] - PARALLEL_START[3:]).max() < 1e-9
+    assert rank_deficient_reference["tilted"]["nfev"] > rank_deficient_reference["untilted"]["nfev"]
+
+
+@pytest.mark.parametrize("name", list(RANK_DEFICIENT))
+def test_rank_deficient_problems_against_scipy(host, rank_deficient_reference, name):
+    """x[3:] is not compared: the minimum is a one-parameter family, the rotation about the common normal is free"""
+    import cape_amd
+
+    ref = rank_deficient_reference[name]
+    P = np.zeros(3, cape_amd.MAP_PLANE_DTYPE)
+    P["normal"], P["d"] = PARALLEL_MAP[:, :3], PARALLEL_MAP[:, 3]
+    tracks = np.zeros(3, cape_amd.MAP_TRACK_DTYPE)
+    tracks["covariance"] = np.eye(4)
+    arrays = (P, np.zeros(0, cape_amd.MAP_RING_DTYPE), np.zeros((0, 2)))
+    rows, poses, n_rank_deficient = host.host_pose_solve(arrays, tracks, np.arange(3, dtype=np.int32), RANK_DEFICIENT[name], PARALLEL_START[None],
+                                                         np.array([words_of(range(3))], np.uint32))
+    row = rows[0]
+    d_fnorm = abs(float(row["fnorm"]) - ref["fnorm"]) / ref["fnorm"]
+    print(f"twin, {name}: status {row['status']}, nfev {row['nfev']}, fnorm {row['fnorm0']:.4g} -> {row['fnorm']:.4g}, x {row['x'].tolist()}; "
+          f"relative |dfnorm| {d_fnorm:.3e}, scipy nfev {ref['nfev']}")
+    assert n_rank_deficient == 1 and row["flags"] == host.POSE_SOLVE_RANK_DEFICIENT
+    assert row["status"] in (1, 2, 3) and row["fnorm0"] == ref["fnorm0"]
+    assert d_fnorm <= 10 * OFF_DEFAULT_MEASURED["defaults"][2]
+    assert np.array_equal(row["x"][:2], PARALLEL_START[:2]), "the unobservable directions get a zero step"
+    assert np.array_equal(poses[0], pose_of(row["x"]))
+
+
+def test_not_finite_at_the_start_and_at_the_first_trial_point(host):
+    """CAPE_POSE_SOLVE_NOT_FINITE has two sites.  The start: x[0] = 1e160 is a finite start (no refusal) whose residuals' squares
+    overflow at the very first evaluation.  The trial point: a start of 2e154 in x[2] has a finite fnorm (about 1e154, its square below
+    DBL_MAX) and a Jacobian whose coefficient columns are of that order too, and the first step's x + p is not finite, so it is not
+    evaluated: nfev = 7.  (Found by a search on the twin over starts of 1e150 .. 2.2e154 in one position coordinate: some tens of
+    some thousands of starts ended there, all of them above 1.2e154 and at the first trial point; none ended on a trial fnorm.)"""
+    planes, arrays, tracks, detected, x_true, rng = make_frame(400)
+    match = np.arange(128, dtype=np.int32)
+    starts = np.tile(x_true, (3, 1))
+    starts[0, 0], starts[1, 2] = 1e160, 2e154
+    subsets = np.array([words_of([3, 40, 99])] * 3, np.uint32)
+    rows, poses, _ = host.host_pose_solve(arrays, tracks, match, detected, starts, subsets)
+    print(f"not finite: statuses {rows['status'].tolist()}, nfev {rows['nfev'].tolist()}, fnorm0 {rows['fnorm0'].tolist()}, fnorm {rows['fnorm'].tolist()}")
+    a, b, c = rows
+    assert a["status"] == host.POSE_SOLVE_NOT_FINITE == -6 and a["nfev"] == 1 and a["iterations"] == 0
+    assert np.array_equal(a["x"], starts[0]) and np.isposinf(a["fnorm0"]) and a["n_pairs_used"] == 3 and a["flags"] == 0
+    assert b["status"] == host.POSE_SOLVE_NOT_FINITE and b["nfev"] == 7 and b["iterations"] == 0
+    assert np.array_equal(b["x"], starts[1]) and np.isfinite(b["fnorm0"]) and b["fnorm"] == b["fnorm0"] > 1e153
+    assert c["status"] in (1, 2, 3), "the same problem from a start near the minimum converges"
+    for row, pose, x0 in zip(rows, poses, starts):
+        assert np.array_equal(pose, pose_of(x0 if row["status"] < 0 else row["x"]))
+
+
+def test_the_slab_frame_of_the_device_test_on_the_host(host, oracle_mod):
+    """the `slabs` fixture of tests/test_gpu_pose_solve.py without a device: the oracle's extraction of its depth frame, the polygon
+    oracle's outlines, the host map matcher and the twin.  A change to the frame that loses a plane or a pair is found here, and so
+    is what the fixture's pose is for: measured on the twin, a full-rank problem whose minimum is the identity pose ends in the
+    pivoted branch, the same problem lifted by _slab_pose does not."""
+    import polygon_oracle_py as P
+    from cape_amd import synth
+    from test_gpu_map_match import _w2c
+    from test_gpu_pose_score import _det_planes
+    from test_gpu_pose_solve import DEGENERATE_START, _slab_map, _slab_pose, _slab_problems, _slabs_and_facets, _starts
+
+    P.build()
+    found = oracle_mod.Oracle(640, 480, cylinders=False, **synth.DEFAULT_INTRINSICS).run(_slabs_and_facets())
+    det = []
+    for k in range(len(found.planes)):
+        seg = found.segments[int(found.planes[k][19])]
+        normal = np.array(seg[0:3])
+        pol = P.Polygon.from_points(np.asarray(found.boundary[k]), normal, normal * (-float(seg[3])))
+        assert not pol.threw and pol.valid and pol.boundary_length() >= 3
+        det.append((np.array(found.planes[k][0:3]), float(found.planes[k][3]), np.array(pol.x_axis), np.array(pol.y_axis), np.array(pol.center),
+                    np.array(pol.ring), float(pol.area)))
+    planes, slabs = _slab_map(det)
+    assert len(det) == 6 and len(slabs) == 3 == sum(abs(k[0][2]) > 0.999 for k in det)
+    assert all(np.array_equal(np.abs(planes[i][0]), [0.0, 0.0, 1.0]) for i in slabs)
+    w2c = _w2c(*_slab_pose())
+    arrays = host.pack_map(planes)
+    match, _ = host.host_match_map(arrays, det, w2c, None, host.MATCH_ALLOW_INDEX0)
+    assert sorted(int(v) for v in match) == list(range(6)), "six pairs"
+    tracks = np.zeros(6, host.MAP_TRACK_DTYPE)
+    tracks["covariance"] = np.eye(4)
+
+    class Frame:
+        pass
+
+    s = Frame()
+    s.W2C, s.slabs, s.facets = w2c[None], slabs, [i for i in range(6) if i not in slabs]
+    x0, subsets = _slab_problems(s, np.random.default_rng(420), 5)
+    rows, _, n_rank_deficient = host.host_pose_solve(arrays, tracks, np.asarray(match, np.int32), _det_planes(det), x0[0], subsets[0])
+    print(f"slabs on the host: statuses {rows['status'].tolist()}, flags {rows['flags'].tolist()}, nfev {rows['nfev'].tolist()}")
+    assert n_rank_deficient == 1 and rows[5]["flags"] == host.POSE_SOLVE_RANK_DEFICIENT and not rows[np.arange(16) != 5]["flags"].any()
+    assert rows[5]["status"] > 0 and np.array_equal(rows[5]["x"][:2], DEGENERATE_START[:2]) and np.isin(rows["status"], (1, 2, 3)).all()
+    # the three facets alone, their map the exact lift of the detections: full rank, the minimum at the lifting pose.  Lifted by the
+    # identity the iterate's position and last two coefficients go to 0, the steps sqrt(eps) |x_j| with them, a column's forward
+    # differences come out exactly 0 and the last iterations pivot; lifted by _slab_pose they do not
+    facets = np.array([words_of(s.facets)] * 4, np.uint32)
+    for name, pose, flagged in (("identity", (np.eye(3), np.zeros(3)), True), ("_slab_pose", _slab_pose(), False)):
+        exact, _ = _slab_map(det, pose)
+        m, _ = host.host_match_map(host.pack_map(exact), det, _w2c(*pose), None, host.MATCH_ALLOW_INDEX0)
+        starts = _starts(np.random.default_rng(421), _w2c(*pose)[None], 4)[0]
+        rows, _, _ = host.host_pose_solve(host.pack_map(exact), tracks, np.asarray(m, np.int32), _det_planes(det), starts, facets)
+        print(f"facets lifted by {name}: statuses {rows['status'].tolist()}, flags {rows['flags'].tolist()}, fnorm {rows['fnorm'].tolist()}, "
+              f"|x| at the end {np.abs(rows['x'][:, [0, 1, 2, 4, 5]]).max(axis=1).tolist()}")
+        assert np.isin(rows["status"], (1, 2, 3)).all() and (rows["fnorm"] < 1e-3).all()
+        assert ((rows["flags"] == host.POSE_SOLVE_RANK_DEFICIENT) == flagged).all()
 
 
 def _rows(host, entries, n_pairs):
