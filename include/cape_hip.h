@@ -1388,6 +1388,80 @@ int cape_map_pose_select(cape_handle h, int32_t n_frames, void* stream);
 /* Synchronous copy of the last cape_map_pose_select (n_frames rows).  CAPE_ERR_CAPACITY: more frames than it covered, or not current. */
 int cape_copy_pose_selection(cape_handle h, int32_t n_frames, cape_pose_selection* selection);
 
+/* THE POSE'S COVARIANCE after the refit: Pose_Optimization::compute_pose_variance (pose_optimization.cpp:361-437), the statement that
+ * makes a pose usable (local_map.hpp:118 refuses the map update without a valid pose covariance; CAPE_MEASURE_BAD_POSE_COV here).  The
+ * chain goes on, on the same stream without a host wait:
+ *   ... -> cape_map_pose_solve(CAPE_POSE_SOLVE_FROM_SELECTION) -> cape_map_pose_covariance(CAPE_POSE_COVARIANCE_FROM_SOLUTION).
+ * Per frame and iteration i < n_iterations every pair of the subset gets its map plane varied by four standard-normal deviates z times
+ * the feature row's stddev (n' = n + z[0..2] stddev[0..2], divided by its norm where that is > 0; d' = d + z[3] stddev[3]), and the
+ * problem is minimised again from x on the varied planes with cape_map_pose_solve's minimiser, parameters and guards.  A sample counts
+ * when its status is > 0 and its x holds no NaN.  The pose vector of a sample is x[0..2] followed by Eigen's eulerAngles(0, 1, 2) of
+ * the rotation of the three coefficients, the first angle in [0, pi] (the reference's own fold: samples that straddle 0 land near 0
+ * and near pi).  Over the successes in ascending iteration order: mean = sum / n_ok; covariance = sum (v - mean)(v - mean)^T /
+ * (n_ok - 1) + 0.001 I, then is_covariance_valid.  n_ok = 1 divides by zero as the reference does: CAPE_POSE_COVARIANCE_INVALID.
+ * The deviates are Philox4x32-10 words keyed by `seed` at the counter (frame + frame_base, iteration, pair slot, block 0 / 1), turned
+ * into four uniforms in (0, 1] and two Box-Muller pairs -- NOT the reference's mt19937 stream, which its own tbb::parallel_for leaves
+ * unordered -- or, with CAPE_POSE_COVARIANCE_TABLE, the caller's table [n_iterations][128 pair slots][4] shared by all frames of the
+ * call.  Rules: csrc/cape_pose_covariance.h; host twin: cape_host_pose_covariance (host/cape_host_map.h).  With a table everything
+ * up to a sample's x is + - x / sqrt and equals the twin bit for bit; the three angles go through atan2, sin and cos.
+ * covariance[0..2][0..2], the position block, is what cape_map_measure takes as pose_covariance. */
+enum /* flags of cape_map_pose_covariance (DEVICE_INPUT also of cape_pose_draw_deviates: `out` is device memory) */
+{
+    CAPE_POSE_COVARIANCE_DEVICE_INPUT = 1u << 0,  /* x, subsets and deviates are DEVICE memory, read in place when the kernels run */
+    CAPE_POSE_COVARIANCE_FROM_SOLUTION = 1u << 1, /* x of the last cape_map_pose_solve(CAPE_POSE_SOLVE_FROM_SELECTION) and the subset of
+                                                     that selection's inlier_words, both read in device memory when the kernels run */
+    CAPE_POSE_COVARIANCE_TABLE = 1u << 2,         /* read `deviates`; otherwise Philox */
+    CAPE_POSE_COVARIANCE_KEEP_SAMPLES = 1u << 3,  /* keep every sample's solution row for cape_copy_pose_covariance_samples:
+                                                     CAPE_ERR_CAPACITY beyond CAPE_POSE_COVARIANCE_MAX_KEPT rows */
+    CAPE_POSE_DRAW_UNIFORMS = 1u << 4             /* cape_pose_draw_deviates only: the four uniforms instead of the four normals */
+};
+enum /* cape_pose_covariance.status */
+{
+    CAPE_POSE_COVARIANCE_VALID = 1,
+    /* -1 .. -7: the CAPE_POSE_SOLVE_* refusal of the frame (its pairs, its flags, its x; with FROM_SOLUTION the refit's own status):
+       no sample ran, mean and covariance are 0 */
+    CAPE_POSE_COVARIANCE_TOO_MANY_FAILED = -16, /* n_ok < n_iterations / 2 (integer division): mean and covariance are 0 */
+    CAPE_POSE_COVARIANCE_INVALID = -17,         /* is_covariance_valid refused the matrix, which is reported as computed */
+    CAPE_POSE_COVARIANCE_NO_SOLUTION = -18      /* FROM_SOLUTION on a refit row whose status is 0 */
+};
+#define CAPE_POSE_COVARIANCE_MAX_KEPT (1 << 22)             /* sample rows (96 bytes each) a call may keep */
+#define CAPE_POSE_COVARIANCE_DEFAULT_BUDGET (256ull << 20)  /* bytes of the varied-plane slab: 4096 x n_iterations per frame */
+typedef struct cape_pose_covariance /* 368 bytes, one per frame */
+{
+    double mean[6];        /* position, then the three Euler angles */
+    double covariance[36]; /* row-major */
+    int32_t n_ok;          /* samples that count */
+    int32_t n_iterations;
+    int32_t status;        /* CAPE_POSE_COVARIANCE_* or a CAPE_POSE_SOLVE_* refusal */
+    uint32_t flags;        /* CAPE_MATCH_EXACT_OVERFLOW and CAPE_POSE_SCORE_INVALID_FEATURE of the frame */
+    int32_t nfev_min, nfev_max; /* over the samples that ran */
+    int64_t nfev_sum;
+} cape_pose_covariance;
+/* x: 6 doubles per frame; subsets: 4 uint32 per frame (cape_map_pose_solve's indexing); deviates: the table -- HOST memory read before
+ * the call returns, or device memory with CAPE_POSE_COVARIANCE_DEVICE_INPUT.  With FROM_SOLUTION x and subsets are not read and a
+ * current refit and selection covering n_frames are needed (CAPE_ERR_CAPACITY otherwise).  The varied planes live in a slab of the
+ * handle, [frame][128][4][iteration], within a byte budget (cape_set_pose_covariance_budget): a call whose frames do not fit is
+ * enqueued in chunks of frames without a host wait; CAPE_ERR_CAPACITY if one frame alone (4096 x n_iterations bytes) does not fit.
+ * Needs what cape_map_pose_solve needs and is invalidated by what invalidates it.  CAPE_ERR_INVALID_ARGUMENT: what cape_map_pose_solve
+ * refuses, n_iterations < 1, CAPE_POSE_COVARIANCE_TABLE with a NULL table, an unknown flag.  Nothing but the call's own buffers is
+ * written.  Asynchronous on `stream`. */
+int cape_map_pose_covariance(cape_handle h, int32_t n_frames, int32_t n_iterations, const double* x, const uint32_t* subsets,
+                             const double* deviates, uint64_t seed, uint32_t frame_base, const cape_pose_solve_params* params, uint32_t flags,
+                             void* stream);
+/* Synchronous copy of the last cape_map_pose_covariance (n_frames rows).  CAPE_ERR_CAPACITY: more frames than it covered, or not current. */
+int cape_copy_pose_covariance(cape_handle h, int32_t n_frames, cape_pose_covariance* rows);
+/* ... and of its sample rows (n_frames x n_iterations of that call; rows of a refused frame are 0): the call must have had
+ * CAPE_POSE_COVARIANCE_KEEP_SAMPLES, else CAPE_ERR_INVALID_ARGUMENT. */
+int cape_copy_pose_covariance_samples(cape_handle h, int32_t n_frames, cape_pose_solution* samples);
+/* Device pointer of the result rows.  CAPE_ERR_CAPACITY when no cape_map_pose_covariance is current. */
+int cape_pose_covariance_device(cape_handle h, const cape_pose_covariance** rows);
+/* The table [n_iterations][128][4] of the deviates a call with `seed` draws for frame index `frame` (= frame_base + the frame of the
+ * call), through the device function that call uses; to host memory, or to device memory with CAPE_POSE_COVARIANCE_DEVICE_INPUT.
+ * Synchronous: the table is there when the call returns.  CAPE_POSE_DRAW_UNIFORMS: the four uniforms instead of the normals. */
+int cape_pose_draw_deviates(cape_handle h, uint64_t seed, uint32_t frame, int32_t n_iterations, double* out, uint32_t flags);
+/* The byte budget of the varied-plane slab (0: CAPE_POSE_COVARIANCE_DEFAULT_BUDGET).  Takes effect with the next call. */
+int cape_set_pose_covariance_budget(cape_handle h, uint64_t bytes);
+
 /* A stream of the handle's device for callers that do not link the HIP runtime themselves (the overlay): non-blocking, so the
  * work of several handles driven from several host threads overlaps instead of meeting on the legacy null stream.  Pass it as
  * the `stream` argument of the calls below; destroy it before the handle. */

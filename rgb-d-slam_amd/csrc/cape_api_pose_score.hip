@@ -14,14 +14,6 @@ constexpr uint32_t kPoseScoreFlags = CAPE_POSE_SCORE_DEVICE_POSES | CAPE_POSE_SC
 constexpr size_t kPoseResidualsBudget = (size_t)1 << 30; // bytes of the per-pair table at most, like kMapAreasBudget
 constexpr size_t kPoseResidualDoubles = (size_t)CAPE_MATCH_MAP_WIDE_MAX_PLANES * 7; // of one (frame, hypothesis)
 
-// the results of the last cape_map_pose_score still describe the current batch and match (a cape_extract ends the match; every other
-// call that replaces an input says so through invalidate_frame_results)
-bool pose_scores_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseScore;
-    return P.frames > 0 && h->mapWide.matchFrames >= P.frames;
-}
-
 } // namespace
 
 extern "C" {

@@ -12,24 +12,6 @@ namespace {
 
 constexpr uint32_t kPoseSolveFlags = CAPE_POSE_SOLVE_DEVICE_INPUT | CAPE_POSE_SOLVE_FROM_SELECTION;
 
-// the results of the last cape_map_pose_solve / cape_map_pose_select still describe the current batch and match (a cape_extract ends
-// the match; every other call that replaces an input says so through invalidate_frame_results)
-bool pose_solutions_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseSolve;
-    return P.frames > 0 && h->mapWide.matchFrames >= P.frames;
-}
-bool pose_selection_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseSolve;
-    return P.selectFrames > 0 && h->mapWide.matchFrames >= P.selectFrames;
-}
-bool pose_scores_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseScore;
-    return P.frames > 0 && h->mapWide.matchFrames >= P.frames;
-}
-
 } // namespace
 
 extern "C" {

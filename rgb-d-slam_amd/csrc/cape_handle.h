@@ -15,6 +15,7 @@
 #include "cape_map_step.h"
 #include "cape_pose_score.h"
 #include "cape_pose_solve.h"
+#include "cape_pose_covariance.h"
 
 namespace cape {
 // every launcher returns the error of its own launch(es) (hipGetLastError right behind hipLaunchKernelGGL)
@@ -48,6 +49,9 @@ hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStrea
 hipError_t launch_map_pose_pairs(const PoseScoreParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_pose_solve(const PoseSolveParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_pose_select(const PoseSelectParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_pose_covariance_chunk(const PoseCovParams& p, hipStream_t stream); // vary, then the varied solve, of p.chunkFrames frames
+hipError_t launch_map_pose_covariance_reduce(const PoseCovParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_pose_draw_deviates(uint64_t seed, uint32_t frameIndex, int nIterations, bool uniforms, double* out, hipStream_t stream);
 hipError_t launch_map_union(const MapUnionParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_ring_union(const RingUnionParams& p, hipStream_t stream);
 hipError_t launch_map_union_holes(const MapUnionParams& p, cape_plane_union_rings* ringRows /* frames x 128 */, int nFrames, hipStream_t stream);
@@ -646,17 +650,40 @@ struct cape_handle_s
         bool fromSelection = false; // ... and whether they came from the selection
         int selectFrames = 0;    // frames of the last cape_map_pose_select (0: none current)
     } poseSolve;
+
+    // cape_map_pose_covariance: the samples of the last call and what it made of them.  Buffers of its own, like PoseSolve's: the pairs
+    // kernel in front of the vary kernel writes frameInfo and features HERE.
+    struct PoseCovariance
+    {
+        Buffer<unsigned char> input; // the call's x (frames x 6 doubles), then its subsets (x 4 words), unless device memory
+        cape::abi::PinnedTwin inputTwin;
+        Buffer<double> table;        // the call's deviates (iterations x 128 x 4), unless device memory
+        cape::abi::PinnedTwin tableTwin;
+        Buffer<int4> frameInfo;             // frames: n_pairs, n_invalid, flags, 0
+        Buffer<cape_pose_feature> features; // frames x 128
+        Buffer<unsigned char> frameRows;    // frames x cape::PoseCovFrame: x, subset and refusal as the vary kernel resolved them
+        Buffer<double> slab;                // the varied planes of a chunk of frames, [frame][128][4][iteration], within `budget` bytes
+        Buffer<unsigned char> samples;      // frames x iterations x cape::PoseCovSample
+        Buffer<cape_pose_solution> kept;    // CAPE_POSE_COVARIANCE_KEEP_SAMPLES: frames x iterations
+        Buffer<cape_pose_covariance> rows;  // frames
+        Buffer<double> drawn;               // cape_pose_draw_deviates to host memory: the table on its way
+        unsigned long long budget = 0;      // bytes of the slab (0: CAPE_POSE_COVARIANCE_DEFAULT_BUDGET)
+        int frames = 0;                     // frames of the last call (0: none for the current batch, map, tracks and match)
+        int iterations = 0;                 // iterations per frame of that call
+        bool keptSamples = false;           // ... and whether it kept the sample rows
+    } poseCovariance;
 };
 
 namespace cape::abi {
 // What a replaced input of the map update's per-frame results invalidates, for every call that replaces one (the batch's polygons,
 // the wide match, the measurements, the map, its tracks): the results of cape_map_kalman -- and with them the unions' -- and those of
-// cape_map_pose_score, cape_map_pose_solve and cape_map_pose_select.  (A cape_extract ends the wide match and the measurements themselves: both results are checked against them.)
+// cape_map_pose_score, cape_map_pose_solve, cape_map_pose_select and cape_map_pose_covariance.  (A cape_extract ends the wide match and the measurements themselves: both results are checked against them.)
 inline void invalidate_frame_results(cape_handle_s* h)
 {
     h->kalman.kalmanFrames = 0;
     h->poseScore.frames = 0;
     h->poseSolve.frames = h->poseSolve.selectFrames = 0;
+    h->poseCovariance.frames = 0;
 }
 } // namespace cape::abi
 

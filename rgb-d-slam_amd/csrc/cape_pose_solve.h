@@ -83,8 +83,8 @@ CAPE_POSE_FN bool pose_solve_settings(const cape_pose_solve_params* p, PoseSolve
 
 CAPE_POSE_FN bool pose_finite(double v) { return fabs(v) <= DBL_MAX; } // (a NaN compares false)
 
-// ---- the pose of x: T[12] = the first three rows of the row-major world-to-camera matrix
-CAPE_POSE_FN void pose_from_coefficients(const double x[6], const double C[9], double T[12])
+// ---- the rotation of x's three coefficients, before the camera basis (row-major)
+CAPE_POSE_FN void pose_rotation_from_coefficients(const double x[6], double R[9])
 {
     const double alpha = (x[3] * x[3] + x[4] * x[4]) + x[5] * x[5];
     const double divider = 1.0 / (alpha + 1);
@@ -93,7 +93,15 @@ CAPE_POSE_FN void pose_from_coefficients(const double x[6], const double C[9], d
     qw = qw / norm, qx = qx / norm, qy = qy / norm, qz = qz / norm;
     const double tx = 2.0 * qx, ty = 2.0 * qy, tz = 2.0 * qz;
     const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx, tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-    const double R[9] = {1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1.0 - (txx + tyy)};
+    R[0] = 1.0 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+    R[3] = txy + twz, R[4] = 1.0 - (txx + tzz), R[5] = tyz - twx;
+    R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1.0 - (txx + tyy);
+}
+// ---- the pose of x: T[12] = the first three rows of the row-major world-to-camera matrix
+CAPE_POSE_FN void pose_from_coefficients(const double x[6], const double C[9], double T[12])
+{
+    double R[9];
+    pose_rotation_from_coefficients(x, R);
     double M[9], pw[3];
     CAPE_POSE_UNROLL
     for (int r = 0; r < 3; ++r)
@@ -126,6 +134,9 @@ struct PoseSolveRows
     const int* kept;      // the pair's kept plane
     int nPairs;
     unsigned long long subsetLo, subsetHi; // bit i: the pair of kept plane i (Lo), i + 64 (Hi) takes part
+    // the map plane of pair k: the row's own.  Another source of rows (cape_pose_covariance.h: a lane's varied planes) derives from this
+    // struct and answers with four values of its own in `own`
+    CAPE_POSE_FN const double* map_plane(int k, double*) const { return planes + 8 * k + 4; }
 };
 CAPE_POSE_FN bool pose_solve_takes(const PoseSolveRows& rows, int k)
 {
@@ -133,21 +144,22 @@ CAPE_POSE_FN bool pose_solve_takes(const PoseSolveRows& rows, int k)
     return (((i < 64 ? rows.subsetLo : rows.subsetHi) >> (i & 63)) & 1ull) != 0ull;
 }
 // the three residuals of pair k under T
-template <class PlaneToCamera>
-CAPE_POSE_FN void pose_solve_pair(const PoseSolveRows& rows, int k, const double T[12], const PlaneToCamera& planeToCamera, double r[3])
+template <class Rows, class PlaneToCamera>
+CAPE_POSE_FN void pose_solve_pair(const Rows& rows, int k, const double T[12], const PlaneToCamera& planeToCamera, double r[3])
 {
     const double* row = rows.planes + 8 * k;
     const double cn[3] = {row[0], row[1], row[2]};
-    double qn[3], qd, reduced[3];
-    planeToCamera(T, row + 4, row[7], qn, qd);
+    double qn[3], qd, reduced[3], own[4];
+    const double* map = rows.map_plane(k, own);
+    planeToCamera(T, map, map[3], qn, qd);
     pose_pair_reduced(cn, row[3], qn, qd, reduced);
     CAPE_POSE_UNROLL
     for (int c = 0; c < 3; ++c)
         r[c] = reduced[c] * 1.0 / 3.0;
 }
 // the norm of the residual vector at x: one evaluation
-template <class PlaneToCamera>
-CAPE_POSE_FN double pose_solve_fnorm(const PoseSolveRows& rows, const double x[6], const double C[9], const PlaneToCamera& planeToCamera)
+template <class Rows, class PlaneToCamera>
+CAPE_POSE_FN double pose_solve_fnorm(const Rows& rows, const double x[6], const double C[9], const PlaneToCamera& planeToCamera)
 {
     double T[12];
     pose_from_coefficients(x, C, T);
@@ -575,8 +587,8 @@ CAPE_POSE_FN int pose_solve_refusal(const PoseSolveRows& rows, int nInvalid, uin
 }
 
 // ---- lmstr over fdjac2: one problem from x0; T = the pose of the row's x
-template <class PlaneToCamera>
-CAPE_POSE_FN cape_pose_solution pose_solve_problem(const PoseSolveRows& rows, int nInvalid, uint32_t frameFlags, const double x0[6],
+template <class Rows, class PlaneToCamera>
+CAPE_POSE_FN cape_pose_solution pose_solve_problem(const Rows& rows, int nInvalid, uint32_t frameFlags, const double x0[6],
                                                    const PoseSolveSettings& S, const PlaneToCamera& planeToCamera, double T[12])
 {
     cape_pose_solution out;

@@ -238,6 +238,29 @@ int cape_host_pose_solve(const cape_host_map* map, const int32_t* match, const c
 int cape_host_pose_select(int32_t n_hypotheses, const cape_pose_score* scores, const cape_pose_solution* solutions,
                           cape_pose_selection* selection_out);
 
+/* The twin of cape_map_pose_covariance (include/cape_hip.h) for ONE frame (host/pose_covariance.cpp), on the rules of
+ * csrc/cape_pose_covariance.h that the kernels compile too: vary, a minimisation per iteration, the reduction.  map, match, detected,
+ * frame_flags: as cape_host_pose_score takes them.  x: 6 doubles and subset: 4 words; or, with `solution` and `selection` given (both or
+ * neither), the refit's row and the selection it came from (CAPE_POSE_COVARIANCE_FROM_SOLUTION).  deviates: the table
+ * [n_iterations][128][4], or NULL for Philox keyed by `seed` at frame index `frame_index` (= frame_base + the frame of the device's call).
+ * Outputs, any may be NULL: row_out, samples_out[n_iterations] (the solution rows; 0 for a refused frame), vectors_out[n_iterations x 6]
+ * (the pose vectors the reduction reads).  With a table everything equals the device bit for bit except the three Euler angles of a
+ * vector and what the reduction makes of them, which are this host's libm's.  Returns 0, or CAPE_ERR_INVALID_ARGUMENT. */
+int cape_host_pose_covariance(const cape_host_map* map, const int32_t* match, const cape_host_planes* detected, uint32_t frame_flags,
+                              int32_t n_iterations, const double* x, const uint32_t* subset, const cape_pose_solution* solution,
+                              const cape_pose_selection* selection, const double* deviates, uint64_t seed, uint32_t frame_index,
+                              const cape_pose_solve_params* params, cape_pose_covariance* row_out, cape_pose_solution* samples_out,
+                              double* vectors_out);
+/* The twin of cape_pose_draw_deviates: the table [n_iterations][128][4] of frame index `frame`; flags: 0 or CAPE_POSE_DRAW_UNIFORMS.  The
+ * uniforms equal the device's bit for bit; the normals go through this host's log, cos and sin. */
+int cape_host_pose_draw_deviates(uint64_t seed, uint32_t frame, int32_t n_iterations, double* out, uint32_t flags);
+/* Single statements of csrc/cape_pose_covariance.h, for the tests: a Philox4x32-10 block; the variation of a map plane; the pose vector
+ * of x (and, if asked for, the rotation matrix its angles are taken of); Eigen's eulerAngles(0, 1, 2) of a row-major rotation. */
+void cape_host_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
+void cape_host_pose_vary_plane(const double* map_plane4, const double* stddev4, const double* z4, double* out4);
+void cape_host_pose_vector(const double* x6, double* vector6_out, double* rotation9_out);
+void cape_host_euler_angles_012(const double* rotation9, double* angles3_out);
+
 #ifdef __cplusplus
 }
 #endif

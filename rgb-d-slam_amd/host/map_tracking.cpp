@@ -49,6 +49,8 @@ void propagate(const double* S, int n, const double* J, int m, double eps, doubl
 
 bool is_covariance_valid(const double* M, int n) noexcept
 {
+    if (n < 1 || n > kMaxCovarianceSize)
+        return false;
     for (int i = 0; i < n * n; ++i)
         if (!std::isfinite(M[i]))
             return false; // "invalid values"
@@ -66,7 +68,7 @@ bool is_covariance_valid(const double* M, int n) noexcept
     if (!(diff <= prec * prec * std::min(a, b)))
         return false; // "not symetrical"
     // selfadjointView<Upper>().ldlt(): Eigen's unblocked LDLT with diagonal pivoting on the transpose's lower triangle
-    double m[4 * 4];
+    double m[kMaxCovarianceSize * kMaxCovarianceSize]; // (the exchange and the elimination below are written for any n)
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j)
             m[i * n + j] = M[j * n + i];
@@ -78,7 +80,7 @@ bool is_covariance_valid(const double* M, int n) noexcept
         INDEFINITE
     } sign = ZERO;
     bool ok = true, foundZeroPivot = false;
-    double temp[4];
+    double temp[kMaxCovarianceSize];
     for (int k = 0; k < n; ++k)
     {
         int big = k;

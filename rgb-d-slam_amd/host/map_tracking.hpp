@@ -15,6 +15,7 @@
 namespace rgbd_slam::map_tracking {
 
 // Eigen::isApprox on N x N (Frobenius) and is_covariance_valid: finite, isApprox(transpose), LDLT of the upper triangle isPositive
+constexpr int kMaxCovarianceSize = 6; // 3: a pose's position block; 4: a plane; 6: a pose (cape_host_pose_covariance)
 bool is_covariance_valid(const double* M, int n) noexcept;
 
 // PlaneCoordinates(vector4) / operator=: the normal normalised (once per call), d as is

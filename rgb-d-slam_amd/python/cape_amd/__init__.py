@@ -304,6 +304,16 @@ POSE_SOLVE_BAD_START, POSE_SOLVE_NOT_FINITE, POSE_SOLVE_NO_SELECTION = -5, -6, -
 POSE_SOLVE_RANK_DEFICIENT = 1 << 9
 POSE_SELECT_NO_CONSENSUS, POSE_SELECT_EARLY_STOP = 1, 2
 
+# cape_map_pose_covariance: compute_pose_variance behind the refit (cape_pose_covariance, one per frame)
+POSE_COVARIANCE_DTYPE = np.dtype([("mean", "<f8", 6), ("covariance", "<f8", (6, 6)), ("n_ok", "<i4"), ("n_iterations", "<i4"), ("status", "<i4"),
+                                  ("flags", "<u4"), ("nfev_min", "<i4"), ("nfev_max", "<i4"), ("nfev_sum", "<i8")], align=True)
+assert POSE_COVARIANCE_DTYPE.itemsize == 368
+POSE_COVARIANCE_DEVICE_INPUT, POSE_COVARIANCE_FROM_SOLUTION, POSE_COVARIANCE_TABLE, POSE_COVARIANCE_KEEP_SAMPLES = 1, 2, 4, 8
+POSE_DRAW_UNIFORMS = 16
+POSE_COVARIANCE_VALID, POSE_COVARIANCE_TOO_MANY_FAILED, POSE_COVARIANCE_INVALID, POSE_COVARIANCE_NO_SOLUTION = 1, -16, -17, -18
+POSE_COVARIANCE_MAX_KEPT = 1 << 22
+POSE_COVARIANCE_DEFAULT_BUDGET = 256 << 20
+
 
 def pose_solve_params(ftol=None, xtol=None, gtol=0.0, factor=100.0, epsfcn=0.0, maxfev=400, mode=1, camera_basis=None):
     """a cape_pose_solve_params row: the defaults of Eigen::LevenbergMarquardt and the identity camera basis unless given"""
@@ -361,6 +371,15 @@ def _host_library():
         L.cape_host_pose_score.argtypes = [Map, i32, Planes, C.c_uint32, C.c_int32, f64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cape_host_pose_solve.argtypes = [Map, i32, Planes, C.c_uint32, C.c_int32, f64, C.POINTER(C.c_uint32)] + [C.c_void_p] * 5
         L.cape_host_pose_select.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cape_host_pose_covariance.argtypes = ([Map, i32, Planes, C.c_uint32, C.c_int32] + [C.c_void_p] * 5 + [C.c_uint64, C.c_uint32] +
+                                                [C.c_void_p] * 4)
+        L.cape_host_pose_draw_deviates.argtypes = [C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint32]
+        for name in ("cape_host_philox4x32_10", "cape_host_pose_vary_plane", "cape_host_pose_vector", "cape_host_euler_angles_012"):
+            getattr(L, name).restype = None
+        L.cape_host_philox4x32_10.argtypes = [C.c_void_p] * 3
+        L.cape_host_pose_vary_plane.argtypes = [C.c_void_p] * 4
+        L.cape_host_pose_vector.argtypes = [C.c_void_p] * 3
+        L.cape_host_euler_angles_012.argtypes = [C.c_void_p] * 2
         L.cape_host_polygon_union_cut.argtypes = L.cape_host_polygon_union.argtypes
         L.cape_host_kalman_update.argtypes = [C.c_void_p] * 6
         L.cape_host_plane_frame.argtypes = [C.c_void_p, C.c_void_p]
@@ -584,6 +603,83 @@ def host_pose_select(scores, solutions):
     if rc != 0:
         raise CapeError(f"cape_host_pose_select failed ({rc})")
     return out[0]
+
+
+def host_pose_covariance(map_arrays, tracks, match, detected_planes, n_iterations, x=None, subset=None, deviates=None, seed=0, frame_index=0,
+                         params=None, frame_flags=0, solution=None, selection=None):
+    """cape_host_pose_covariance of libcape_primitives.so: the twin of Extractor.map_pose_covariance for ONE frame -- every pair of the
+    subset varied per iteration, the minimisation from x on the varied planes, the reduction, on the rules the kernels compile too.
+
+    map_arrays, tracks, match, detected_planes, frame_flags: as host_pose_score takes them; x: 6 doubles; subset: 4 uint32 words; or
+    solution and selection: the refit's POSE_SOLUTION_DTYPE row and the POSE_SELECTION_DTYPE row it came from
+    (POSE_COVARIANCE_FROM_SOLUTION); deviates: a table (n_iterations, 128, 4) or None for Philox keyed by seed at frame_index.
+    Returns (row: POSE_COVARIANCE_DTYPE scalar, samples: POSE_SOLUTION_DTYPE[n_iterations], vectors: float64[n_iterations, 6])."""
+    L = _host_library()
+    src, src_view = _map_arrays(map_arrays, np.ascontiguousarray(tracks, MAP_TRACK_DTYPE))
+    n_map = len(src["planes"])
+    if len(src["tracks"]) != n_map:
+        raise CapeError("host_pose_covariance: one track per map plane")
+    M = np.ascontiguousarray(match, np.int32).reshape(-1)
+    if len(M) != n_map:
+        raise CapeError("host_pose_covariance: one match per map plane")
+    D = np.ascontiguousarray(detected_planes, np.float64).reshape(-1, 4)
+    det_view = _view(cape_host_planes, dict(planes=D), n=len(D))
+    X = None if x is None else np.ascontiguousarray(x, np.float64).reshape(6)
+    S = None if subset is None else np.ascontiguousarray(subset, np.uint32).reshape(4)
+    sol = None if solution is None else np.ascontiguousarray(solution, POSE_SOLUTION_DTYPE).reshape(1)
+    sel = None if selection is None else np.ascontiguousarray(selection, POSE_SELECTION_DTYPE).reshape(1)
+    Z = None if deviates is None else np.ascontiguousarray(deviates, np.float64)
+    if Z is not None and Z.size != n_iterations * POSE_SCORE_MAX_PAIRS * 4:
+        raise CapeError("host_pose_covariance: the table holds n_iterations x 128 x 4 deviates")
+    P = None if params is None else np.ascontiguousarray(params, POSE_SOLVE_PARAMS_DTYPE).reshape(1)
+    row = np.zeros(1, POSE_COVARIANCE_DTYPE)
+    samples = np.zeros(max(n_iterations, 1), POSE_SOLUTION_DTYPE)
+    vectors = np.zeros((max(n_iterations, 1), 6), np.float64)
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    rc = L.cape_host_pose_covariance(C.byref(src_view), _as(M, C.c_int32), C.byref(det_view), frame_flags, n_iterations, ptr(X), ptr(S), ptr(sol),
+                                     ptr(sel), ptr(Z), seed, frame_index, ptr(P), row.ctypes.data, samples.ctypes.data, vectors.ctypes.data)
+    if rc != 0:
+        raise CapeError(f"cape_host_pose_covariance failed ({rc})")
+    return row[0], samples[:n_iterations], vectors[:n_iterations]
+
+
+def host_pose_draw_deviates(seed, frame, n_iterations, uniforms=False):
+    """cape_host_pose_draw_deviates: the table float64[n_iterations, 128, 4] of the deviates (or, with uniforms, of the uniforms in (0, 1])
+    a call keyed by seed draws for frame index `frame`"""
+    out = np.zeros((max(n_iterations, 1), POSE_SCORE_MAX_PAIRS, 4), np.float64)
+    rc = _host_library().cape_host_pose_draw_deviates(seed, frame, n_iterations, out.ctypes.data, POSE_DRAW_UNIFORMS if uniforms else 0)
+    if rc != 0:
+        raise CapeError(f"cape_host_pose_draw_deviates failed ({rc})")
+    return out[:n_iterations]
+
+
+def host_philox4x32_10(counter, key):
+    """one Philox4x32-10 block of csrc/cape_pose_covariance.h: counter (4 words), key (2 words) -> uint32[4]"""
+    c, k, out = np.ascontiguousarray(counter, np.uint32).reshape(4), np.ascontiguousarray(key, np.uint32).reshape(2), np.zeros(4, np.uint32)
+    _host_library().cape_host_philox4x32_10(c.ctypes.data, k.ctypes.data, out.ctypes.data)
+    return out
+
+
+def host_pose_vary_plane(map_plane, stddev, z):
+    """pose_vary_plane of csrc/cape_pose_covariance.h: the varied (normal, d) of a map plane under four deviates"""
+    a, b, c = (np.ascontiguousarray(v, np.float64).reshape(4) for v in (map_plane, stddev, z))
+    out = np.zeros(4)
+    _host_library().cape_host_pose_vary_plane(a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data)
+    return out
+
+
+def host_pose_vector(x):
+    """(PoseBase::get_vector of x: position then eulerAngles(0, 1, 2); the 3 x 3 rotation of x's coefficients the angles are taken of)"""
+    X, v, R = np.ascontiguousarray(x, np.float64).reshape(6), np.zeros(6), np.zeros((3, 3))
+    _host_library().cape_host_pose_vector(X.ctypes.data, v.ctypes.data, R.ctypes.data)
+    return v, R
+
+
+def host_euler_angles_012(rotation):
+    """Eigen 3.4's eulerAngles(0, 1, 2) of a 3 x 3 rotation as csrc/cape_pose_covariance.h restates it"""
+    R, out = np.ascontiguousarray(rotation, np.float64).reshape(3, 3), np.zeros(3)
+    _host_library().cape_host_euler_angles_012(R.ctypes.data, out.ctypes.data)
+    return out
 
 
 def _union_rings(rows, slab):
@@ -977,6 +1073,8 @@ EXPORTED_SYMBOLS = [
     "cape_map_step_visible", "cape_map_step_skip_words",
     "cape_map_pose_score", "cape_copy_pose_scores", "cape_pose_score_device",
     "cape_map_pose_solve", "cape_copy_pose_solutions", "cape_pose_solve_device", "cape_map_pose_select", "cape_copy_pose_selection",
+    "cape_map_pose_covariance", "cape_copy_pose_covariance", "cape_copy_pose_covariance_samples", "cape_pose_covariance_device",
+    "cape_pose_draw_deviates", "cape_set_pose_covariance_budget",
     "cape_build_polygons", "cape_device_polygons", "cape_copy_polygons", "cape_debug_polygon",
     "cape_last_error", "cape_version", "cape_debug_eval", "cape_debug_cycles", "cape_debug_rectify_flagged", "cape_copy_seed_sequence",
     "cape_debug_polygon_queue", "cape_set_log_callback", "cape_log_records", "cape_debug_match_lists", "cape_debug_map_match_lists", "cape_set_rng_seed",
@@ -1100,6 +1198,12 @@ def load_library():
     L.cape_pose_solve_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_map_pose_select.argtypes = [vp, C.c_int32, vp]
     L.cape_copy_pose_selection.argtypes = [vp, C.c_int32, vp]
+    L.cape_map_pose_covariance.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint32, vp]
+    L.cape_copy_pose_covariance.argtypes = [vp, C.c_int32, vp]
+    L.cape_copy_pose_covariance_samples.argtypes = [vp, C.c_int32, vp]
+    L.cape_pose_covariance_device.argtypes = [vp, C.POINTER(vp)]
+    L.cape_pose_draw_deviates.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int32, vp, C.c_uint32]
+    L.cape_set_pose_covariance_budget.argtypes = [vp, C.c_uint64]
     L.cape_build_polygons.argtypes = [vp, C.c_int32, vp]
     L.cape_device_polygons.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.cape_copy_polygons.argtypes = [vp, C.c_int32, vp, vp]
@@ -1624,6 +1728,79 @@ class Extractor:
         rows = np.zeros(max(n_frames, 1), POSE_SELECTION_DTYPE)
         _check(self.L, self.L.cape_copy_pose_selection(self.h, n_frames, rows.ctypes.data_as(C.c_void_p)), "cape_copy_pose_selection")
         return rows[:n_frames]
+
+    # ---- the pose's covariance behind the refit: vary, solve on the varied planes, reduce ----
+    def map_pose_covariance(self, n_frames, n_iterations=100, x=None, subsets=None, deviates=None, seed=0, frame_base=0, params=None, flags=0,
+                            stream=0):
+        """cape_map_pose_covariance: per frame of [0, n_frames) n_iterations minimisations from x over the subset's pairs, each on map planes
+        varied by the tracks' standard deviations, and the sample covariance of the resulting pose vectors plus 0.001 I.  x: (n_frames, 6);
+        subsets: (n_frames, 4) uint32 words; with POSE_COVARIANCE_FROM_SOLUTION neither is read: x and the subset come from the last
+        map_pose_solve(POSE_SOLVE_FROM_SELECTION) and its selection.  deviates: with POSE_COVARIANCE_TABLE a table (n_iterations, 128, 4)
+        shared by the frames; otherwise Philox keyed by seed at (frame + frame_base, iteration, pair slot).  With
+        POSE_COVARIANCE_DEVICE_INPUT x, subsets and deviates are device addresses (int).  POSE_COVARIANCE_KEEP_SAMPLES keeps the sample
+        rows for pose_covariance_samples.  params: a pose_solve_params(...) row or None.  The results are pose_covariance's."""
+        P = None if params is None else np.ascontiguousarray(params, POSE_SOLVE_PARAMS_DTYPE).reshape(1)
+        pp = None if P is None else P.ctypes.data_as(C.c_void_p)
+        device = bool(flags & POSE_COVARIANCE_DEVICE_INPUT)
+        xp = sp = zp = None
+        keep = []
+        if not flags & POSE_COVARIANCE_FROM_SOLUTION:
+            if device and not isinstance(x, np.ndarray):
+                xp, sp = C.c_void_p(int(x)), C.c_void_p(int(subsets))
+            else:
+                X, S = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(subsets, np.uint32)
+                if X.size != n_frames * 6 or S.size != n_frames * 4:
+                    raise CapeError("map_pose_covariance: x must hold n_frames x 6 doubles and subsets x 4 words")
+                xp, sp = X.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p)
+                keep += [X, S]
+        if deviates is not None:
+            if device and not isinstance(deviates, np.ndarray):
+                zp = C.c_void_p(int(deviates))
+            else:
+                Z = np.ascontiguousarray(deviates, np.float64)
+                if Z.size != n_iterations * POSE_SCORE_MAX_PAIRS * 4:
+                    raise CapeError("map_pose_covariance: the table holds n_iterations x 128 x 4 deviates")
+                zp = Z.ctypes.data_as(C.c_void_p)
+                keep.append(Z)
+        _check(self.L, self.L.cape_map_pose_covariance(self.h, n_frames, n_iterations, xp, sp, zp, seed, frame_base, pp, flags, C.c_void_p(stream)),
+               "cape_map_pose_covariance")
+        self.pose_covariance_iterations = n_iterations
+
+    def pose_covariance(self, n_frames):
+        """POSE_COVARIANCE_DTYPE[n_frames] of the last map_pose_covariance; covariance[:3, :3] is what map_measure takes as pose_covariance"""
+        rows = np.zeros(max(n_frames, 1), POSE_COVARIANCE_DTYPE)
+        _check(self.L, self.L.cape_copy_pose_covariance(self.h, n_frames, rows.ctypes.data_as(C.c_void_p)), "cape_copy_pose_covariance")
+        return rows[:n_frames]
+
+    def pose_covariance_samples(self, n_frames):
+        """POSE_SOLUTION_DTYPE[n_frames, n_iterations]: the sample rows of the last map_pose_covariance(POSE_COVARIANCE_KEEP_SAMPLES)"""
+        n_it = getattr(self, "pose_covariance_iterations", 0)
+        rows = np.zeros((n_frames, max(n_it, 1)), POSE_SOLUTION_DTYPE)
+        _check(self.L, self.L.cape_copy_pose_covariance_samples(self.h, n_frames, rows.ctypes.data_as(C.c_void_p)), "cape_copy_pose_covariance_samples")
+        return rows[:, :n_it]
+
+    def pose_covariance_device(self):
+        """device address of the rows of the last map_pose_covariance"""
+        a = C.c_void_p()
+        _check(self.L, self.L.cape_pose_covariance_device(self.h, C.byref(a)), "cape_pose_covariance_device")
+        return a.value
+
+    def pose_draw_deviates(self, seed, frame, n_iterations, out=None, uniforms=False):
+        """cape_pose_draw_deviates: the table float64[n_iterations, 128, 4] a map_pose_covariance keyed by seed draws for frame index
+        `frame` (= frame_base + the frame of the call); out: a device address (int) to fill instead (returns None then)"""
+        flags = POSE_DRAW_UNIFORMS if uniforms else 0
+        if out is not None:
+            _check(self.L, self.L.cape_pose_draw_deviates(self.h, seed, frame, n_iterations, C.c_void_p(int(out)), flags | POSE_COVARIANCE_DEVICE_INPUT),
+                   "cape_pose_draw_deviates")
+            return None
+        table = np.zeros((max(n_iterations, 1), POSE_SCORE_MAX_PAIRS, 4), np.float64)
+        _check(self.L, self.L.cape_pose_draw_deviates(self.h, seed, frame, n_iterations, table.ctypes.data_as(C.c_void_p), flags), "cape_pose_draw_deviates")
+        return table[:n_iterations]
+
+    def set_pose_covariance_budget(self, n_bytes):
+        """cape_set_pose_covariance_budget: the bytes the varied-plane slab may take (0: the default); a call whose frames do not fit runs
+        in chunks of frames"""
+        _check(self.L, self.L.cape_set_pose_covariance_budget(self.h, n_bytes), "cape_set_pose_covariance_budget")
 
     # ---- the polygon half of the map update (needs map_kalman of the batch) ----
     def map_union(self, n_frames, stream=0):
