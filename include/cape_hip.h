@@ -1280,7 +1280,9 @@ typedef struct cape_pose_feature /* 112 bytes, one per pair k < 128 of a frame, 
  * current for the map -- otherwise CAPE_ERR_CAPACITY.  CAPE_ERR_INVALID_ARGUMENT: NULL handle or poses, n_frames < 0,
  * n_hypotheses < 1, unknown flag.  A frame the wide match flagged CAPE_MATCH_EXACT_OVERFLOW reports that flag, n_pairs = 0 and zeros;
  * an empty map succeeds with n_pairs = 0 everywhere.  Nothing is written into the map, the tracks, the matches or any other call's
- * results: the buffers are the handle's own, grown on demand.  What invalidates cape_map_kalman's results -- a later cape_extract,
+ * results: the buffers are the handle's own, grown on demand.  The feature rows are shared with cape_map_pose_solve and
+ * cape_map_pose_covariance: whichever of the three runs first on a batch, map, tracks and match builds them, a call over more frames
+ * builds them again in place with the bytes they hold, and their address (cape_pose_score_device) never changes.  What invalidates cape_map_kalman's results -- a later cape_extract,
  * cape_build_polygons, cape_map_upload, cape_map_upload_tracks, cape_match_map_wide, cape_map_measure, or a cape_map_commit,
  * cape_map_maintain or cape_map_step[_visible] that changes the map -- invalidates these.  Asynchronous on `stream`. */
 int cape_map_pose_score(cape_handle h, int32_t n_frames, int32_t n_hypotheses, const double* world_to_camera, uint32_t flags, void* stream);
@@ -1371,7 +1373,8 @@ typedef struct cape_pose_selection /* 96 bytes, one per frame */
  * [R t; 0 0 0 1]: the layout cape_map_pose_score takes with CAPE_POSE_SCORE_DEVICE_POSES.  Needs what cape_map_pose_score needs and is
  * invalidated by what invalidates it; a later cape_map_pose_solve replaces the rows.  CAPE_ERR_INVALID_ARGUMENT: NULL handle, NULL x0
  * or subsets without CAPE_POSE_SOLVE_FROM_SELECTION, n_frames < 0, n_hypotheses < 1, unknown flag, a parameter that is NaN or negative,
- * maxfev < 1, a mode other than 1 and 2.  Nothing but the call's own buffers is written.  Asynchronous on `stream`. */
+ * maxfev < 1, a mode other than 1 and 2.  Nothing but the call's own buffers is written, and, where they do not cover n_frames yet,
+ * the feature rows it shares with cape_map_pose_score -- with the bytes that call gives them.  Asynchronous on `stream`. */
 int cape_map_pose_solve(cape_handle h, int32_t n_frames, int32_t n_hypotheses, const double* x0, const uint32_t* subsets,
                         const cape_pose_solve_params* params, uint32_t flags, void* stream);
 /* Synchronous copy of the last cape_map_pose_solve: solutions (n_frames x n_hypotheses of that call) and poses (x 16 doubles).  Either
@@ -1444,7 +1447,8 @@ typedef struct cape_pose_covariance /* 368 bytes, one per frame */
  * enqueued in chunks of frames without a host wait; CAPE_ERR_CAPACITY if one frame alone (4096 x n_iterations bytes) does not fit.
  * Needs what cape_map_pose_solve needs and is invalidated by what invalidates it.  CAPE_ERR_INVALID_ARGUMENT: what cape_map_pose_solve
  * refuses, n_iterations < 1, CAPE_POSE_COVARIANCE_TABLE with a NULL table, an unknown flag.  Nothing but the call's own buffers is
- * written.  Asynchronous on `stream`. */
+ * written, and, where they do not cover n_frames yet, the feature rows it shares with cape_map_pose_score -- with the bytes that
+ * call gives them.  Asynchronous on `stream`. */
 int cape_map_pose_covariance(cape_handle h, int32_t n_frames, int32_t n_iterations, const double* x, const uint32_t* subsets,
                              const double* deviates, uint64_t seed, uint32_t frame_base, const cape_pose_solve_params* params, uint32_t flags,
                              void* stream);

@@ -356,27 +356,8 @@ inline void adopt_map(cape_handle_s* h, MapSet& from, const MapSizes& sizes)
     M.tracksN = sizes.planes; // the set's tracks are those of the new map
 }
 
-// the results of the last cape_map_pose_solve / cape_map_pose_select still describe the current batch and match (a cape_extract ends
-// the match; every other call that replaces an input says so through invalidate_frame_results)
-inline bool pose_solutions_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseSolve;
-    return P.frames > 0 && h->mapWide.matchFrames >= P.frames;
-}
-inline bool pose_selection_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseSolve;
-    return P.selectFrames > 0 && h->mapWide.matchFrames >= P.selectFrames;
-}
-inline bool pose_scores_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseScore;
-    return P.frames > 0 && h->mapWide.matchFrames >= P.frames;
-}
-
-
 // What a changed map invalidates, for every call that changes it: the words cape_map_visibility decided for the old map, the wide
-// match against it and what cape_map_kalman (and with it the unions) and cape_map_pose_score made of that.  An upload brings no tracks, and ends the words
+// match against it and what cape_map_kalman (and with it the unions) and the pose stage made of that.  An upload brings no tracks, and ends the words
 // of cape_map_step_visible too; behind a commit, a maintenance or a step those words stay readable -- they stand for the map that
 // step found -- and the new set's tracks are current (adopt_map).
 inline void invalidate_for_new_map(cape_handle_s* h, bool uploaded = false)

@@ -1,10 +1,11 @@
 // C ABI, host side: the pose's covariance behind the refit -- compute_pose_variance as vary, solve on the varied planes and reduce
 // (cape_pose_covariance.hip).  It reads what cape_map_pose_solve reads and, with CAPE_POSE_COVARIANCE_FROM_SOLUTION, that call's refit rows
-// and selection in device memory; it writes only the buffers of cape_handle_s::PoseCovariance.
+// and selection in device memory; it writes the buffers of cape_handle_s::PoseCovariance and, where they are not current, the stage's pair
+// rows (enqueue_pose_pairs).
 #include <algorithm>
 #include <cstring>
 
-#include "cape_api_map.h"
+#include "cape_api_pose.h"
 
 using namespace cape::abi;
 
@@ -14,12 +15,6 @@ constexpr uint32_t kPoseCovarianceFlags = CAPE_POSE_COVARIANCE_DEVICE_INPUT | CA
                                           CAPE_POSE_COVARIANCE_KEEP_SAMPLES;
 constexpr uint32_t kPoseDrawFlags = CAPE_POSE_COVARIANCE_DEVICE_INPUT | CAPE_POSE_DRAW_UNIFORMS;
 constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
-
-bool pose_covariance_live(const cape_handle_s* h)
-{
-    const auto& P = h->poseCovariance;
-    return P.frames > 0 && h->mapWide.matchFrames >= P.frames;
-}
 
 } // namespace
 
@@ -46,13 +41,9 @@ int cape_map_pose_covariance(cape_handle h, int32_t n_frames, int32_t n_iteratio
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null x or subsets");
     auto& P = h->poseCovariance;
     const auto& S = h->poseSolve;
-    const auto& W = h->mapWide;
-    const int nMap = h->maps.n;
     P.frames = 0;
-    if (nMap < 0 || h->maps.tracksN != nMap)
-        return fail(CAPE_ERR_CAPACITY, "no tracks for the uploaded map (cape_map_upload, then cape_map_upload_tracks)");
-    if (!h->kalman.matchedThisMap || W.matchN != nMap || n_frames > W.matchFrames)
-        return fail(CAPE_ERR_CAPACITY, "no cape_match_map_wide of the current batch against the uploaded map covers n_frames");
+    if (const int rc = check_pose_inputs(h, n_frames); rc != CAPE_OK)
+        return rc;
     if (fromSolution && (!pose_solutions_live(h) || !S.fromSelection || n_frames > S.frames || !pose_selection_live(h) || n_frames > S.selectFrames))
         return fail(CAPE_ERR_CAPACITY, "no current cape_map_pose_solve(CAPE_POSE_SOLVE_FROM_SELECTION) covers n_frames");
     const size_t iterations = (size_t)n_iterations, groups = (iterations + cape::kPoseCovGroupIterations - 1) / cape::kPoseCovGroupIterations;
@@ -73,24 +64,21 @@ int cape_map_pose_covariance(cape_handle h, int32_t n_frames, int32_t n_iteratio
     CAPE_ON_DEVICE(h);
     CAPE_SETTLE_RESULTS(h);
     const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them
-    const size_t xBytes = (size_t)n_frames * 6 * sizeof(double), inputBytes = xBytes + (size_t)n_frames * 4 * sizeof(uint32_t);
     const size_t tableDoubles = iterations * WP * 4;
-    const bool upload = !fromSolution && !deviceInput, uploadTable = fromTable && !deviceInput;
-    if (upload && P.input.size() < inputBytes)
-    {
-        // (the pinned twin has the size of its device buffer: both are replaced)
-        CAPE_HIP_TRY(drain());
-        P.inputTwin = PinnedTwin{};
-        CAPE_HIP_TRY(P.input.alloc(inputBytes));
-    }
+    const PoseInputRoute route = fromSolution ? PoseInputRoute::kFromResults : deviceInput ? PoseInputRoute::kDevice : PoseInputRoute::kHost;
+    const bool uploadTable = fromTable && !deviceInput;
+    if (route == PoseInputRoute::kHost)
+        if (const int rc = reserve_pose_input(h, P, (size_t)n_frames); rc != CAPE_OK)
+            return rc;
     if (uploadTable && P.table.size() < tableDoubles)
     {
+        // (the pinned twin has the size of its device buffer: both are replaced)
         CAPE_HIP_TRY(drain());
         P.tableTwin = PinnedTwin{};
         CAPE_HIP_TRY(P.table.alloc(tableDoubles));
     }
-    CAPE_HIP_TRY(P.frameInfo.grow((size_t)n_frames, drain));
-    CAPE_HIP_TRY(P.features.grow((size_t)n_frames * WP, drain));
+    if (const int rc = reserve_pose_pairs(h); rc != CAPE_OK)
+        return rc;
     CAPE_HIP_TRY(P.frameRows.grow((size_t)n_frames * sizeof(cape::PoseCovFrame), drain));
     CAPE_HIP_TRY(P.slab.grow(chunk * frameDoubles, drain));
     CAPE_HIP_TRY(P.samples.grow(sampleRows * sizeof(cape::PoseCovSample), drain));
@@ -101,42 +89,20 @@ int cape_map_pose_covariance(cape_handle h, int32_t n_frames, int32_t n_iteratio
     StreamScope streamScope(h, stream);
     if (streamScope.rc() != CAPE_OK)
         return streamScope.rc();
-    if (upload)
-        CAPE_HIP_TRY(P.inputTwin.upload(P.input, inputBytes, P.input.size(), stream, [&](void* stage) {
-            std::memcpy(stage, x, xBytes);
-            std::memcpy(static_cast<unsigned char*>(stage) + xBytes, subsets, inputBytes - xBytes);
-        }));
+    cape::PoseCovParams p{};
+    if (const int rc = bind_pose_input(P, route, (size_t)n_frames, x, subsets, stream, &p.x, &p.subsets); rc != CAPE_OK)
+        return rc;
     if (uploadTable)
         CAPE_HIP_TRY(P.tableTwin.upload(P.table, tableDoubles * sizeof(double), P.table.size() * sizeof(double), stream,
                                         [&](void* stage) { std::memcpy(stage, deviates, tableDoubles * sizeof(double)); }));
     if (keep) // (the rows of a refused frame are never written)
         CAPE_HIP_TRY(hipMemsetAsync(P.kept, 0, sampleRows * sizeof(cape_pose_solution), stream));
-    // ---- the frame's pairs and feature rows: the pairs kernel of cape_map_pose_score, into this call's rows
-    cape::PoseScoreParams pairs{};
-    pairs.mapPlanes = h->maps.front.planes;
-    pairs.tracks = h->maps.front.tracks;
-    pairs.tags = h->maps.front.tags;
-    pairs.nMap = nMap;
-    pairs.matchFrames = W.frames;
-    pairs.match = W.match;
-    pairs.kept = W.kept;
-    pairs.records = h->res.records;
-    pairs.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the batch's records, then the spill pool's)
-    pairs.frameInfo = P.frameInfo;
-    pairs.features = P.features;
-    CAPE_HIP_TRY(cape::launch_map_pose_pairs(pairs, n_frames, stream));
-    cape::PoseCovParams p{};
-    p.frameInfo = P.frameInfo;
-    p.features = P.features;
+    if (const int rc = enqueue_pose_pairs(h, n_frames, stream); rc != CAPE_OK)
+        return rc;
+    p.frameInfo = h->posePairs.frameInfo;
+    p.features = h->posePairs.features;
     if (fromSolution)
         p.solutions = S.solutions, p.selection = S.selection;
-    else if (deviceInput)
-        p.x = x, p.subsets = subsets;
-    else
-    {
-        p.x = reinterpret_cast<const double*>(P.input.get());
-        p.subsets = reinterpret_cast<const uint32_t*>(P.input.get() + xBytes);
-    }
     p.table = !fromTable ? nullptr : (deviceInput ? deviates : P.table.get());
     p.seed = seed;
     p.frameBase = frame_base;
@@ -163,32 +129,19 @@ int cape_map_pose_covariance(cape_handle h, int32_t n_frames, int32_t n_iteratio
 
 int cape_copy_pose_covariance(cape_handle h, int32_t n_frames, cape_pose_covariance* rows)
 {
-    if (!h || n_frames < 0)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
-    const auto& P = h->poseCovariance;
-    if (n_frames > (pose_covariance_live(h) ? P.frames : 0))
-        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_pose_covariance on the current batch, map, tracks and match");
-    if (n_frames == 0)
-        return CAPE_OK;
-    CAPE_ON_DEVICE(h);
-    CAPE_HIP_TRY(drain_handle(h));
-    CAPE_HIP_TRY(copy_out(rows, P.rows, 0, (size_t)n_frames));
+    CAPE_POSE_COPY_OUT(h, n_frames, pose_covariance_live(h) ? h->poseCovariance.frames : 0,
+                       "n_frames exceeds the frames of the last cape_map_pose_covariance on the current batch, map, tracks and match");
+    CAPE_HIP_TRY(copy_out(rows, h->poseCovariance.rows, 0, (size_t)n_frames));
     return CAPE_OK;
 }
 
 int cape_copy_pose_covariance_samples(cape_handle h, int32_t n_frames, cape_pose_solution* samples)
 {
-    if (!h || n_frames < 0)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    CAPE_POSE_COPY_OUT(h, n_frames, pose_covariance_live(h) ? h->poseCovariance.frames : 0,
+                       "n_frames exceeds the frames of the last cape_map_pose_covariance on the current batch, map, tracks and match",
+                       if (!h->poseCovariance.keptSamples)
+                           return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_map_pose_covariance did not keep its samples (CAPE_POSE_COVARIANCE_KEEP_SAMPLES)"));
     const auto& P = h->poseCovariance;
-    if (n_frames > (pose_covariance_live(h) ? P.frames : 0))
-        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_pose_covariance on the current batch, map, tracks and match");
-    if (n_frames == 0)
-        return CAPE_OK;
-    if (!P.keptSamples)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_map_pose_covariance did not keep its samples (CAPE_POSE_COVARIANCE_KEEP_SAMPLES)");
-    CAPE_ON_DEVICE(h);
-    CAPE_HIP_TRY(drain_handle(h));
     CAPE_HIP_TRY(copy_out(samples, P.kept, 0, (size_t)n_frames * (size_t)P.iterations));
     return CAPE_OK;
 }

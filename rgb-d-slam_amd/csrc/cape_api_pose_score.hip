@@ -1,10 +1,10 @@
 // C ABI, host side: the stage between the match and the update -- a batch of pose hypotheses per frame scored against the frame's
 // map matches (cape_pose_score.hip).  It reads the front map, its tracks, the batch's records and the last cape_match_map_wide and
-// writes only the buffers of cape_handle_s::PoseScore.
+// writes the buffers of cape_handle_s::PoseScore and, where they are not current, the stage's pair rows (enqueue_pose_pairs).
 #include <algorithm>
 #include <cstring>
 
-#include "cape_api_map.h"
+#include "cape_api_pose.h"
 
 using namespace cape::abi;
 
@@ -20,7 +20,6 @@ extern "C" {
 
 int cape_map_pose_score(cape_handle h, int32_t n_frames, int32_t n_hypotheses, const double* world_to_camera, uint32_t flags, void* stream_)
 {
-    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
     // (what needs no handle comes first)
     if (n_hypotheses < 1)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "n_hypotheses must be at least 1");
@@ -31,13 +30,9 @@ int cape_map_pose_score(cape_handle h, int32_t n_frames, int32_t n_hypotheses, c
     if (!world_to_camera && n_frames > 0)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null poses");
     auto& P = h->poseScore;
-    const auto& W = h->mapWide;
-    const int nMap = h->maps.n;
     P.frames = 0;
-    if (nMap < 0 || h->maps.tracksN != nMap)
-        return fail(CAPE_ERR_CAPACITY, "no tracks for the uploaded map (cape_map_upload, then cape_map_upload_tracks)");
-    if (!h->kalman.matchedThisMap || W.matchN != nMap || n_frames > W.matchFrames)
-        return fail(CAPE_ERR_CAPACITY, "no cape_match_map_wide of the current batch against the uploaded map covers n_frames");
+    if (const int rc = check_pose_inputs(h, n_frames); rc != CAPE_OK)
+        return rc;
     const size_t rowsPerFrame = (size_t)n_hypotheses, rows = (size_t)n_frames * rowsPerFrame;
     const bool keep = (flags & CAPE_POSE_SCORE_RESIDUALS) != 0, devicePoses = (flags & CAPE_POSE_SCORE_DEVICE_POSES) != 0;
     if (keep && rows > kPoseResidualsBudget / (kPoseResidualDoubles * sizeof(double)))
@@ -57,8 +52,8 @@ int cape_map_pose_score(cape_handle h, int32_t n_frames, int32_t n_hypotheses, c
         P.posesTwin = PinnedTwin{};
         CAPE_HIP_TRY(P.poses.alloc(poseDoubles));
     }
-    CAPE_HIP_TRY(P.frameInfo.grow((size_t)n_frames, drain));
-    CAPE_HIP_TRY(P.features.grow((size_t)n_frames * WP, drain));
+    if (const int rc = reserve_pose_pairs(h); rc != CAPE_OK)
+        return rc;
     CAPE_HIP_TRY(P.scores.grow(rows, drain));
     if (keep)
         CAPE_HIP_TRY(P.residuals.grow(rows * kPoseResidualDoubles, drain));
@@ -71,20 +66,13 @@ int cape_map_pose_score(cape_handle h, int32_t n_frames, int32_t n_hypotheses, c
                                         [&](void* stage) { std::memcpy(stage, world_to_camera, poseDoubles * sizeof(double)); }));
     if (keep) // (rows beyond a frame's pairs read as zeros)
         CAPE_HIP_TRY(hipMemsetAsync(P.residuals, 0, rows * kPoseResidualDoubles * sizeof(double), stream));
+    if (const int rc = enqueue_pose_pairs(h, n_frames, stream); rc != CAPE_OK)
+        return rc;
     cape::PoseScoreParams p{};
-    p.mapPlanes = h->maps.front.planes;
-    p.tracks = h->maps.front.tracks;
-    p.tags = h->maps.front.tags;
-    p.nMap = nMap;
-    p.matchFrames = W.frames;
-    p.match = W.match;
-    p.kept = W.kept;
-    p.records = h->res.records;
-    p.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the batch's records, then the spill pool's)
+    p.frameInfo = h->posePairs.frameInfo;
+    p.features = h->posePairs.features;
     p.poses = devicePoses ? world_to_camera : P.poses.get();
     p.nHypotheses = n_hypotheses;
-    p.frameInfo = P.frameInfo;
-    p.features = P.features;
     p.scores = P.scores;
     p.residuals = keep ? P.residuals.get() : nullptr;
     CAPE_HIP_TRY(cape::launch_map_pose_score(p, n_frames, stream));
@@ -96,21 +84,14 @@ int cape_map_pose_score(cape_handle h, int32_t n_frames, int32_t n_hypotheses, c
 
 int cape_copy_pose_scores(cape_handle h, int32_t n_frames, cape_pose_score* scores, cape_pose_feature* features, double* residuals)
 {
-    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
-    if (!h || n_frames < 0)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    CAPE_POSE_COPY_OUT(h, n_frames, pose_scores_live(h) ? h->poseScore.frames : 0,
+                       "n_frames exceeds the frames of the last cape_map_pose_score on the current batch, map, tracks and match",
+                       if (residuals && !h->poseScore.keptResiduals)
+                           return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_map_pose_score did not keep the residual table (CAPE_POSE_SCORE_RESIDUALS)"));
     const auto& P = h->poseScore;
-    if (n_frames > (pose_scores_live(h) ? P.frames : 0))
-        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_pose_score on the current batch, map, tracks and match");
-    if (residuals && n_frames > 0 && !P.keptResiduals)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "the last cape_map_pose_score did not keep the residual table (CAPE_POSE_SCORE_RESIDUALS)");
-    if (n_frames == 0)
-        return CAPE_OK;
-    CAPE_ON_DEVICE(h);
-    CAPE_HIP_TRY(drain_handle(h));
     const size_t rows = (size_t)n_frames * (size_t)P.hypotheses;
     CAPE_HIP_TRY(copy_out(scores, P.scores, 0, rows));
-    CAPE_HIP_TRY(copy_out(features, P.features, 0, (size_t)n_frames * WP));
+    CAPE_HIP_TRY(copy_out(features, h->posePairs.features, 0, (size_t)n_frames * CAPE_MATCH_MAP_WIDE_MAX_PLANES)); // (the shared rows cover the score's frames)
     CAPE_HIP_TRY(copy_out(residuals, P.residuals, 0, rows * kPoseResidualDoubles));
     return CAPE_OK;
 }
@@ -124,7 +105,7 @@ int cape_pose_score_device(cape_handle h, const cape_pose_score** scores, const 
     if (scores)
         *scores = h->poseScore.scores;
     if (features)
-        *features = h->poseScore.features;
+        *features = h->posePairs.features;
     return CAPE_OK;
 }
 

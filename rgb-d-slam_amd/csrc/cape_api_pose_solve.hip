@@ -1,10 +1,11 @@
 // C ABI, host side: the pose solver between the match and the update -- Levenberg-Marquardt per (frame, hypothesis) on the frame's
 // map matches, the RANSAC bookkeeping over the scored hypotheses and the refit from the selection (cape_pose_solve.hip).  It reads what
-// cape_map_pose_score reads, that call's score rows for the selection, and writes only the buffers of cape_handle_s::PoseSolve.
+// cape_map_pose_score reads, that call's score rows for the selection, and writes the buffers of cape_handle_s::PoseSolve and, where
+// they are not current, the stage's pair rows (enqueue_pose_pairs).
 #include <algorithm>
 #include <cstring>
 
-#include "cape_api_map.h"
+#include "cape_api_pose.h"
 
 using namespace cape::abi;
 
@@ -19,7 +20,6 @@ extern "C" {
 int cape_map_pose_solve(cape_handle h, int32_t n_frames, int32_t n_hypotheses, const double* x0, const uint32_t* subsets,
                         const cape_pose_solve_params* params, uint32_t flags, void* stream_)
 {
-    constexpr size_t WP = CAPE_MATCH_MAP_WIDE_MAX_PLANES;
     // (what needs no handle comes first)
     if (n_hypotheses < 1)
         return fail(CAPE_ERR_INVALID_ARGUMENT, "n_hypotheses must be at least 1");
@@ -36,16 +36,12 @@ int cape_map_pose_solve(cape_handle h, int32_t n_frames, int32_t n_hypotheses, c
     if (!fromSelection && n_frames > 0 && (!x0 || !subsets))
         return fail(CAPE_ERR_INVALID_ARGUMENT, "null x0 or subsets");
     auto& P = h->poseSolve;
-    const auto& W = h->mapWide;
-    const int nMap = h->maps.n;
     const int selectFrames = pose_selection_live(h) ? P.selectFrames : 0;
     P.frames = 0;
     if (!fromSelection) // (the selection was made over the rows this call replaces)
         P.selectFrames = 0;
-    if (nMap < 0 || h->maps.tracksN != nMap)
-        return fail(CAPE_ERR_CAPACITY, "no tracks for the uploaded map (cape_map_upload, then cape_map_upload_tracks)");
-    if (!h->kalman.matchedThisMap || W.matchN != nMap || n_frames > W.matchFrames)
-        return fail(CAPE_ERR_CAPACITY, "no cape_match_map_wide of the current batch against the uploaded map covers n_frames");
+    if (const int rc = check_pose_inputs(h, n_frames); rc != CAPE_OK)
+        return rc;
     if (fromSelection && n_frames > selectFrames)
         return fail(CAPE_ERR_CAPACITY, "no current cape_map_pose_select covers n_frames");
     const size_t rowsPerFrame = (size_t)n_hypotheses, rows = (size_t)n_frames * rowsPerFrame;
@@ -56,54 +52,26 @@ int cape_map_pose_solve(cape_handle h, int32_t n_frames, int32_t n_hypotheses, c
     CAPE_ON_DEVICE(h);
     CAPE_SETTLE_RESULTS(h);
     const auto drain = [h] { return drain_handle(h); }; // an earlier call may still be working in them
-    const size_t x0Bytes = rows * 6 * sizeof(double), inputBytes = x0Bytes + rows * 4 * sizeof(uint32_t);
-    const bool upload = !fromSelection && !deviceInput;
-    if (upload && P.input.size() < inputBytes)
-    {
-        // (the pinned twin has the size of its device buffer: both are replaced)
-        CAPE_HIP_TRY(drain());
-        P.inputTwin = PinnedTwin{};
-        CAPE_HIP_TRY(P.input.alloc(inputBytes));
-    }
-    CAPE_HIP_TRY(P.frameInfo.grow((size_t)n_frames, drain));
-    CAPE_HIP_TRY(P.features.grow((size_t)n_frames * WP, drain));
+    const PoseInputRoute route = fromSelection ? PoseInputRoute::kFromResults : deviceInput ? PoseInputRoute::kDevice : PoseInputRoute::kHost;
+    if (route == PoseInputRoute::kHost)
+        if (const int rc = reserve_pose_input(h, P, rows); rc != CAPE_OK)
+            return rc;
+    if (const int rc = reserve_pose_pairs(h); rc != CAPE_OK)
+        return rc;
     CAPE_HIP_TRY(P.solutions.grow(rows, drain));
     CAPE_HIP_TRY(P.poses.grow(rows * 16, drain));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     StreamScope streamScope(h, stream);
     if (streamScope.rc() != CAPE_OK)
         return streamScope.rc();
-    if (upload)
-        CAPE_HIP_TRY(P.inputTwin.upload(P.input, inputBytes, P.input.size(), stream, [&](void* stage) {
-            std::memcpy(stage, x0, x0Bytes);
-            std::memcpy(static_cast<unsigned char*>(stage) + x0Bytes, subsets, inputBytes - x0Bytes);
-        }));
-    // ---- the frame's pairs and feature rows: the pairs kernel of cape_map_pose_score, into this call's rows
-    cape::PoseScoreParams pairs{};
-    pairs.mapPlanes = h->maps.front.planes;
-    pairs.tracks = h->maps.front.tracks;
-    pairs.tags = h->maps.front.tags;
-    pairs.nMap = nMap;
-    pairs.matchFrames = W.frames;
-    pairs.match = W.match;
-    pairs.kept = W.kept;
-    pairs.records = h->res.records;
-    pairs.nRecords = h->cfg.max_batch + h->chain.spillRecords; // (the batch's records, then the spill pool's)
-    pairs.frameInfo = P.frameInfo;
-    pairs.features = P.features;
-    CAPE_HIP_TRY(cape::launch_map_pose_pairs(pairs, n_frames, stream));
     cape::PoseSolveParams p{};
-    p.frameInfo = P.frameInfo;
-    p.features = P.features;
-    if (fromSelection)
-        p.selection = P.selection;
-    else if (deviceInput)
-        p.x0 = x0, p.subsets = subsets;
-    else
-    {
-        p.x0 = reinterpret_cast<const double*>(P.input.get());
-        p.subsets = reinterpret_cast<const uint32_t*>(P.input.get() + x0Bytes);
-    }
+    if (const int rc = bind_pose_input(P, route, rows, x0, subsets, stream, &p.x0, &p.subsets); rc != CAPE_OK)
+        return rc;
+    if (const int rc = enqueue_pose_pairs(h, n_frames, stream); rc != CAPE_OK)
+        return rc;
+    p.frameInfo = h->posePairs.frameInfo;
+    p.features = h->posePairs.features;
+    p.selection = fromSelection ? P.selection.get() : nullptr;
     p.nProblems = n_hypotheses;
     p.settings = settings;
     p.solutions = P.solutions;
@@ -117,15 +85,9 @@ int cape_map_pose_solve(cape_handle h, int32_t n_frames, int32_t n_hypotheses, c
 
 int cape_copy_pose_solutions(cape_handle h, int32_t n_frames, cape_pose_solution* solutions, double* world_to_camera)
 {
-    if (!h || n_frames < 0)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
+    CAPE_POSE_COPY_OUT(h, n_frames, pose_solutions_live(h) ? h->poseSolve.frames : 0,
+                       "n_frames exceeds the frames of the last cape_map_pose_solve on the current batch, map, tracks and match");
     const auto& P = h->poseSolve;
-    if (n_frames > (pose_solutions_live(h) ? P.frames : 0))
-        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_pose_solve on the current batch, map, tracks and match");
-    if (n_frames == 0)
-        return CAPE_OK;
-    CAPE_ON_DEVICE(h);
-    CAPE_HIP_TRY(drain_handle(h));
     const size_t rows = (size_t)n_frames * (size_t)P.problems;
     CAPE_HIP_TRY(copy_out(solutions, P.solutions, 0, rows));
     CAPE_HIP_TRY(copy_out(world_to_camera, P.poses, 0, rows * 16));
@@ -180,16 +142,9 @@ int cape_map_pose_select(cape_handle h, int32_t n_frames, void* stream_)
 
 int cape_copy_pose_selection(cape_handle h, int32_t n_frames, cape_pose_selection* selection)
 {
-    if (!h || n_frames < 0)
-        return fail(CAPE_ERR_INVALID_ARGUMENT, "bad handle / frame count");
-    const auto& P = h->poseSolve;
-    if (n_frames > (pose_selection_live(h) ? P.selectFrames : 0))
-        return fail(CAPE_ERR_CAPACITY, "n_frames exceeds the frames of the last cape_map_pose_select on the current batch, map, tracks and match");
-    if (n_frames == 0)
-        return CAPE_OK;
-    CAPE_ON_DEVICE(h);
-    CAPE_HIP_TRY(drain_handle(h));
-    CAPE_HIP_TRY(copy_out(selection, P.selection, 0, (size_t)n_frames));
+    CAPE_POSE_COPY_OUT(h, n_frames, pose_selection_live(h) ? h->poseSolve.selectFrames : 0,
+                       "n_frames exceeds the frames of the last cape_map_pose_select on the current batch, map, tracks and match");
+    CAPE_HIP_TRY(copy_out(selection, h->poseSolve.selection, 0, (size_t)n_frames));
     return CAPE_OK;
 }
 

@@ -45,8 +45,8 @@ hipError_t launch_map_visibility(const MapVisibilityParams& p, int nFrames, hipS
 hipError_t launch_map_step_visibility(const MapVisibilityParams& p, const MapTrackState* tracks, hipStream_t stream);
 hipError_t launch_map_measure(const MapMeasureParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_kalman(const MapKalmanParams& p, int nFrames, hipStream_t stream);
-hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStream_t stream);
-hipError_t launch_map_pose_pairs(const PoseScoreParams& p, int nFrames, hipStream_t stream);
+hipError_t launch_map_pose_pairs(const PosePairsParams& p, int nFrames, hipStream_t stream); // the pair rows alone (enqueue_pose_pairs)
+hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStream_t stream); // the score kernel alone
 hipError_t launch_map_pose_solve(const PoseSolveParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_pose_select(const PoseSelectParams& p, int nFrames, hipStream_t stream);
 hipError_t launch_map_pose_covariance_chunk(const PoseCovParams& p, hipStream_t stream); // vary, then the varied solve, of p.chunkFrames frames
@@ -619,14 +619,23 @@ struct cape_handle_s
         int n = -1;                    // map planes the words of the last cape_map_step_visible stand for (-1: none since cape_map_upload)
     } mapStepVisible;
 
+    // The pair rows of the pose stage: what the pairs kernel makes of the batch's records, the front map, its tracks and the last
+    // cape_match_map_wide, for cape_map_pose_score, cape_map_pose_solve and cape_map_pose_covariance alike.  Allocated once, for
+    // max_batch frames (a wide match covers no more): never reallocated, so the address cape_pose_score_device hands out stays valid.
+    // enqueue_pose_pairs (cape_api_pose.h) is their only writer.
+    struct PosePairs
+    {
+        Buffer<int4> frameInfo;             // max_batch: n_pairs, n_invalid, flags, 0
+        Buffer<cape_pose_feature> features; // max_batch x 128
+        int frames = 0;                     // the rows describe frames [0, frames) (0: none for the current batch, map, tracks and match)
+    } posePairs;
+
     // cape_map_pose_score: the pose hypotheses of the last call and what it made of them.  Buffers of its own, grown on demand behind
-    // drain_handle: no other call writes them, and the call writes nothing else.
+    // drain_handle: no other call writes them, and the call writes nothing else but the pair rows.
     struct PoseScore
     {
         Buffer<double> poses; // the poses of the call (frames x hypotheses x 16), unless they are the caller's device memory
         cape::abi::PinnedTwin posesTwin;
-        Buffer<int4> frameInfo;             // frames: n_pairs, n_invalid, flags, 0 (the pairs kernel's, read by the score kernel)
-        Buffer<cape_pose_feature> features; // frames x 128
         Buffer<cape_pose_score> scores;     // frames x hypotheses
         Buffer<double> residuals;           // CAPE_POSE_SCORE_RESIDUALS: frames x hypotheses x 128 x 7
         int frames = 0;                     // frames of the last cape_map_pose_score (0: none for the current batch, map, tracks and match)
@@ -635,13 +644,11 @@ struct cape_handle_s
     } poseScore;
 
     // cape_map_pose_solve / cape_map_pose_select: the problems of the last solve, what it made of them and the last selection over
-    // them.  Buffers of its own, like PoseScore's: the pairs kernel in front of the solve writes frameInfo and features HERE.
+    // them.  Buffers of its own, like PoseScore's; the pair rows it reads are posePairs'.
     struct PoseSolve
     {
         Buffer<unsigned char> input; // the call's x0 (frames x problems x 6 doubles), then its subsets (x 4 words), unless device memory
         cape::abi::PinnedTwin inputTwin;
-        Buffer<int4> frameInfo;             // frames: n_pairs, n_invalid, flags, 0
-        Buffer<cape_pose_feature> features; // frames x 128
         Buffer<cape_pose_solution> solutions; // frames x problems
         Buffer<double> poses;                 // frames x problems x 16
         Buffer<cape_pose_selection> selection; // frames
@@ -651,16 +658,14 @@ struct cape_handle_s
         int selectFrames = 0;    // frames of the last cape_map_pose_select (0: none current)
     } poseSolve;
 
-    // cape_map_pose_covariance: the samples of the last call and what it made of them.  Buffers of its own, like PoseSolve's: the pairs
-    // kernel in front of the vary kernel writes frameInfo and features HERE.
+    // cape_map_pose_covariance: the samples of the last call and what it made of them.  Buffers of its own, like PoseSolve's; the pair
+    // rows it reads are posePairs'.
     struct PoseCovariance
     {
         Buffer<unsigned char> input; // the call's x (frames x 6 doubles), then its subsets (x 4 words), unless device memory
         cape::abi::PinnedTwin inputTwin;
         Buffer<double> table;        // the call's deviates (iterations x 128 x 4), unless device memory
         cape::abi::PinnedTwin tableTwin;
-        Buffer<int4> frameInfo;             // frames: n_pairs, n_invalid, flags, 0
-        Buffer<cape_pose_feature> features; // frames x 128
         Buffer<unsigned char> frameRows;    // frames x cape::PoseCovFrame: x, subset and refusal as the vary kernel resolved them
         Buffer<double> slab;                // the varied planes of a chunk of frames, [frame][128][4][iteration], within `budget` bytes
         Buffer<unsigned char> samples;      // frames x iterations x cape::PoseCovSample
@@ -677,10 +682,11 @@ struct cape_handle_s
 namespace cape::abi {
 // What a replaced input of the map update's per-frame results invalidates, for every call that replaces one (the batch's polygons,
 // the wide match, the measurements, the map, its tracks): the results of cape_map_kalman -- and with them the unions' -- and those of
-// cape_map_pose_score, cape_map_pose_solve, cape_map_pose_select and cape_map_pose_covariance.  (A cape_extract ends the wide match and the measurements themselves: both results are checked against them.)
+// cape_map_pose_score, cape_map_pose_solve, cape_map_pose_select and cape_map_pose_covariance, with the pair rows they share.  (A cape_extract ends the wide match and the measurements themselves: both results are checked against them.)
 inline void invalidate_frame_results(cape_handle_s* h)
 {
     h->kalman.kalmanFrames = 0;
+    h->posePairs.frames = 0;
     h->poseScore.frames = 0;
     h->poseSolve.frames = h->poseSolve.selectFrames = 0;
     h->poseCovariance.frames = 0;

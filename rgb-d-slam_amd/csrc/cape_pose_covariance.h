@@ -166,8 +166,7 @@ CAPE_POSE_FN PoseCovFrame pose_cov_frame(const PoseSolveRows& frameRows, int nIn
         F.words[c] = selection ? selection->inlier_words[c] : words[c];
     F.nPairs = frameRows.nPairs, F.nInvalid = nInvalid, F.frameFlags = frameFlags;
     PoseSolveRows rows = frameRows;
-    rows.subsetLo = (unsigned long long)F.words[0] | ((unsigned long long)F.words[1] << 32);
-    rows.subsetHi = (unsigned long long)F.words[2] | ((unsigned long long)F.words[3] << 32);
+    pose_subset(F.words, rows.subsetLo, rows.subsetHi);
     int nUsed;
     F.refusal = pose_solve_refusal(rows, nInvalid, frameFlags, F.x, nUsed);
     if (solution && solution->status <= 0) // (the refit's own refusal, CAPE_POSE_SOLVE_NO_SELECTION among them, goes first)

@@ -1,7 +1,7 @@
 // cape_map_pose_covariance: compute_pose_variance on the device, one more stage on the stream behind the refit.  The statements are those
-// of cape_pose_covariance.h (and, for a sample, of cape_pose_solve.h), which the host twin cape_host_pose_covariance compiles too.  The
-// pairs kernel of cape_pose_score.hip runs in front (launch_map_pose_pairs, into this call's own rows); then, per chunk of frames that
-// fits the slab's byte budget, vary and solve; at the end one reduce over all frames.
+// of cape_pose_covariance.h (and, for a sample, of cape_pose_solve.h), which the host twin cape_host_pose_covariance compiles too.  It
+// reads the pose stage's shared pair rows (the pairs kernel of cape_pose_score.hip, enqueue_pose_pairs); per chunk of frames that fits the
+// slab's byte budget, vary and solve; at the end one reduce over all frames.
 //
 //   cape_pose_vary_kernel : one workgroup of 256 lanes per (frame, 256 iterations), a lane per iteration.  Lane 0 of the frame's first
 //        workgroup resolves the frame's x, subset and refusal (pose_cov_frame) for the kernels behind it.  Every lane walks the frame's
@@ -36,29 +36,6 @@ constexpr int WP = kPoseScoreMaxPairs;
 constexpr int kReduceFrames = 4; // frames (waves) of a reduce workgroup
 static_assert(sizeof(cape_pose_covariance) == 368 && sizeof(cape_pose_covariance) % 16 == 0, "the layout of include/cape_hip.h, 16-byte rows");
 static_assert(sizeof(PoseCovSample) == 64 && sizeof(PoseCovFrame) == 80, "the rows of cape_pose_covariance.h");
-
-// (the carve of cape_pose_solve.hip: what a lane reads of a feature row through LDS)
-struct PoseCovLayout
-{
-    size_t planes, kept, bytes;
-};
-__host__ __device__ constexpr PoseCovLayout pose_cov_layout()
-{
-    Layout l;
-    PoseCovLayout o{};
-    o.planes = l.take<double>((size_t)WP * 8, 16);
-    o.kept = l.take<int>((size_t)WP, 16);
-    o.bytes = l.end(16);
-    return o;
-}
-
-struct DevicePlaneToCamera
-{
-    __device__ __forceinline__ void operator()(const double* T, const double* normal, double d, double qn[3], double& qd) const
-    {
-        plane_to_camera(T, normal, d, qn, qd);
-    }
-};
 
 __device__ __forceinline__ int clamp_pairs(int n) { return n < 0 ? 0 : (n < WP ? n : WP); }
 
@@ -106,8 +83,8 @@ __global__ __launch_bounds__(kPoseCovGroupIterations) void cape_pose_vary_kernel
     }
     if (iteration >= p.nIterations)
         return;
-    const unsigned long long lo = (unsigned long long)words[0] | ((unsigned long long)words[1] << 32);
-    const unsigned long long hi = (unsigned long long)words[2] | ((unsigned long long)words[3] << 32);
+    unsigned long long lo, hi;
+    pose_subset(words, lo, hi);
     double* column = p.slab + (size_t)blockIdx.x * WP * 4 * (size_t)p.nIterations + iteration;
     const uint32_t frameIndex = (uint32_t)frame + p.frameBase;
 #pragma unroll 1
@@ -129,24 +106,15 @@ __global__ __launch_bounds__(kPoseCovGroupIterations) void cape_pose_vary_kernel
 __global__ __launch_bounds__(kPoseCovGroupIterations) void cape_pose_solve_varied_kernel(PoseCovParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr PoseCovLayout lay = pose_cov_layout();
-    double* s_planes = carve_at<double>(smem, lay.planes);
-    int* s_kept = carve_at<int>(smem, lay.kept);
     const int frame = p.firstFrame + blockIdx.x;
     const int iteration = blockIdx.y * kPoseCovGroupIterations + threadIdx.x;
     const PoseCovFrame& F = p.frames[frame];
     if (F.refusal != 0) // (the whole workgroup: no lane reaches the barrier)
         return;
     const int nPairs = clamp_pairs(F.nPairs);
-    if ((int)threadIdx.x < nPairs)
-    {
-        const cape_pose_feature& row = p.features[(size_t)frame * WP + threadIdx.x];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            s_planes[8 * threadIdx.x + c] = row.matched[c], s_planes[8 * threadIdx.x + 4 + c] = row.map_plane[c];
-        s_kept[threadIdx.x] = row.kept_plane;
-    }
-    __syncthreads();
+    double* s_planes;
+    int* s_kept;
+    pose_rows_stage(smem, p.features + (size_t)frame * WP, nPairs, s_planes, s_kept);
     if (iteration >= p.nIterations)
         return;
     double x0[6];
@@ -155,24 +123,15 @@ __global__ __launch_bounds__(kPoseCovGroupIterations) void cape_pose_solve_varie
         x0[c] = F.x[c];
     PoseVariedRows rows;
     rows.planes = s_planes, rows.kept = s_kept, rows.nPairs = nPairs;
-    rows.subsetLo = (unsigned long long)F.words[0] | ((unsigned long long)F.words[1] << 32);
-    rows.subsetHi = (unsigned long long)F.words[2] | ((unsigned long long)F.words[3] << 32);
+    const uint32_t words[4] = {F.words[0], F.words[1], F.words[2], F.words[3]}; // (a copy, as in cape_pose_solve_kernel: handed over in
+    pose_subset(words, rows.subsetLo, rows.subsetHi);                           // place, the kernel spills 15 more SGPRs)
     rows.varied = p.slab + (size_t)blockIdx.x * WP * 4 * (size_t)p.nIterations + iteration;
     rows.stride = (size_t)p.nIterations;
     double T[12];
     const cape_pose_solution r = pose_solve_problem(rows, F.nInvalid, F.frameFlags, x0, p.settings, DevicePlaneToCamera{}, T);
     const size_t at = (size_t)frame * (size_t)p.nIterations + iteration;
     if (p.kept)
-    {
-        double* out = reinterpret_cast<double*>(p.kept + at);
-#pragma unroll
-        for (int c = 0; c < 6; ++c)
-            out[c] = r.x[c];
-        out[6] = r.fnorm0, out[7] = r.fnorm;
-        uint4* tail = reinterpret_cast<uint4*>(out + 8);
-        tail[0] = make_uint4((unsigned)r.status, (unsigned)r.nfev, (unsigned)r.iterations, (unsigned)r.n_pairs_used);
-        tail[1] = make_uint4(r.flags, 0u, 0u, 0u);
-    }
+        store_pose_solution(p.kept + at, r);
     const PoseCovSample s = pose_cov_sample(r);
     double* out = reinterpret_cast<double*>(p.samples + at);
 #pragma unroll
@@ -249,7 +208,7 @@ hipError_t launch_map_pose_covariance_chunk(const PoseCovParams& p, hipStream_t 
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return e;
-    hipLaunchKernelGGL(cape_pose_solve_varied_kernel, dim3(p.chunkFrames, groups), dim3(kPoseCovGroupIterations), pose_cov_layout().bytes, stream, p);
+    hipLaunchKernelGGL(cape_pose_solve_varied_kernel, dim3(p.chunkFrames, groups), dim3(kPoseCovGroupIterations), pose_rows_layout().bytes, stream, p);
     return hipGetLastError();
 }
 

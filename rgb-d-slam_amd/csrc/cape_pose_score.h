@@ -150,8 +150,8 @@ CAPE_POSE_FN cape_pose_score pose_score_row(const PoseScoreSums& S, int32_t nPai
 }
 
 #if defined(__HIPCC__)
-// what the two kernels read and write (cape_pose_score.hip)
-struct PoseScoreParams
+// what the pairs kernel reads, and the pair rows it writes (cape_pose_score.hip)
+struct PosePairsParams
 {
     // the front map and its tracks
     const cape_map_plane* mapPlanes;
@@ -164,14 +164,19 @@ struct PoseScoreParams
     const uint2* kept;    // frames x 128: (record, segment in that record) of kept plane i
     const cape_frame_record* records;
     int nRecords;
-    // the call
-    const double* poses; // frames x hypotheses x 16
-    int nHypotheses;
-    // results
+    // the pair rows
     int4* frameInfo;             // per frame: n_pairs, n_invalid, flags, 0
     cape_pose_feature* features; // frames x 128
-    cape_pose_score* scores;     // frames x hypotheses
-    double* residuals;           // frames x hypotheses x 128 x 7, or null
+};
+// what the score kernel reads and writes
+struct PoseScoreParams
+{
+    const int4* frameInfo;             // the pair rows
+    const cape_pose_feature* features;
+    const double* poses; // frames x hypotheses x 16
+    int nHypotheses;
+    cape_pose_score* scores; // frames x hypotheses
+    double* residuals;       // frames x hypotheses x 128 x 7, or null
 };
 #endif
 

@@ -1,7 +1,8 @@
 // cape_map_pose_score: the plane cost function of the pose solver (PlaneOptimizationFeature, map_primitive.cpp:15-85) for a batch of
 // pose hypotheses per frame, on the match of the last cape_match_map_wide, the front map and its tracks.  The statements are those of
-// cape_pose_score.h, which the host twin cape_host_pose_score compiles too.  Two kernels on the call's stream; both write only the
-// call's own result buffers.
+// cape_pose_score.h, which the host twin cape_host_pose_score compiles too.  Two kernels: the pairs kernel writes the pose stage's shared
+// pair rows, for this call and for the solve and the covariance behind it, and runs only where they are not current (enqueue_pose_pairs,
+// cape_api_pose.h); the score kernel writes only the call's own result buffers.
 //
 //   cape_pose_pairs_kernel : one wavefront per frame, four per workgroup, no barrier, no LDS.
 //        Lanes over the map planes 64 at a time: lane l reads match[f][chunk + l]; a ballot and a count of the bits below the lane
@@ -27,7 +28,7 @@
 #include "cape_layout.h"
 #include "cape_map_camera.h"
 #include "cape_map_commit.h"
-#include "cape_pose_score.h"
+#include "cape_pose_solve.h" // (the carve and the staging of the rows, shared with the solve kernels)
 
 namespace cape {
 
@@ -39,24 +40,9 @@ static_assert(WP == 128, "a lane zeroes rows k and k + 64");
 static_assert(sizeof(cape_pose_score) == 48 && sizeof(cape_pose_feature) == 112, "the layouts of include/cape_hip.h");
 static_assert(sizeof(cape_pose_score) % 16 == 0 && sizeof(cape_pose_feature) % 16 == 0, "16-byte stores");
 
-// what a lane of the score kernel reads of a feature row: (cn, cd), the map plane, the kept plane
-struct PoseScoreLayout
-{
-    size_t planes, kept, bytes;
-};
-__host__ __device__ constexpr PoseScoreLayout pose_score_layout()
-{
-    Layout l;
-    PoseScoreLayout o{};
-    o.planes = l.take<double>((size_t)WP * 8, 16);
-    o.kept = l.take<int>((size_t)WP, 16);
-    o.bytes = l.end(16);
-    return o;
-}
-
 } // namespace
 
-__global__ __launch_bounds__(64 * kPairsFrames) void cape_pose_pairs_kernel(PoseScoreParams p, int nFrames)
+__global__ __launch_bounds__(64 * kPairsFrames) void cape_pose_pairs_kernel(PosePairsParams p, int nFrames)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int frame = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kPairsFrames + wave));
@@ -117,23 +103,13 @@ __global__ __launch_bounds__(64 * kPairsFrames) void cape_pose_pairs_kernel(Pose
 __global__ __launch_bounds__(kPoseScoreGroupHypotheses) void cape_pose_score_kernel(PoseScoreParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr PoseScoreLayout lay = pose_score_layout();
-    double* s_planes = carve_at<double>(smem, lay.planes);
-    int* s_kept = carve_at<int>(smem, lay.kept);
     const int frame = blockIdx.x;
     const int hyp = blockIdx.y * kPoseScoreGroupHypotheses + threadIdx.x; // the workgroup's offset, then the lane
     const int4 info = p.frameInfo[frame];
     const int nPairs = info.x < WP ? info.x : WP;
-    // ---- the frame's rows, once per workgroup
-    if ((int)threadIdx.x < nPairs)
-    {
-        const cape_pose_feature& F = p.features[(size_t)frame * WP + threadIdx.x];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            s_planes[8 * threadIdx.x + c] = F.matched[c], s_planes[8 * threadIdx.x + 4 + c] = F.map_plane[c];
-        s_kept[threadIdx.x] = F.kept_plane;
-    }
-    __syncthreads();
+    double* s_planes;
+    int* s_kept;
+    pose_rows_stage(smem, p.features + (size_t)frame * WP, nPairs, s_planes, s_kept);
     if (hyp >= p.nHypotheses) // (idle lanes of the frame's last workgroup store nothing)
         return;
     const size_t at = (size_t)frame * p.nHypotheses + hyp;
@@ -170,8 +146,7 @@ __global__ __launch_bounds__(kPoseScoreGroupHypotheses) void cape_pose_score_ker
     out[2] = make_uint4(r.inlier_words[0], r.inlier_words[1], r.inlier_words[2], r.inlier_words[3]);
 }
 
-// the pairs kernel alone: frameInfo and features of p (cape_map_pose_solve runs it in front of its own kernel, into its own rows)
-hipError_t launch_map_pose_pairs(const PoseScoreParams& p, int nFrames, hipStream_t stream)
+hipError_t launch_map_pose_pairs(const PosePairsParams& p, int nFrames, hipStream_t stream)
 {
     hipLaunchKernelGGL(cape_pose_pairs_kernel, dim3((nFrames + kPairsFrames - 1) / kPairsFrames), dim3(64 * kPairsFrames), 0, stream, p, nFrames);
     return hipGetLastError();
@@ -179,11 +154,8 @@ hipError_t launch_map_pose_pairs(const PoseScoreParams& p, int nFrames, hipStrea
 
 hipError_t launch_map_pose_score(const PoseScoreParams& p, int nFrames, hipStream_t stream)
 {
-    hipError_t e = launch_map_pose_pairs(p, nFrames, stream);
-    if (e != hipSuccess)
-        return e;
     const int groups = (p.nHypotheses + kPoseScoreGroupHypotheses - 1) / kPoseScoreGroupHypotheses;
-    hipLaunchKernelGGL(cape_pose_score_kernel, dim3(nFrames, groups), dim3(kPoseScoreGroupHypotheses), pose_score_layout().bytes, stream, p);
+    hipLaunchKernelGGL(cape_pose_score_kernel, dim3(nFrames, groups), dim3(kPoseScoreGroupHypotheses), pose_rows_layout().bytes, stream, p);
     return hipGetLastError();
 }
 

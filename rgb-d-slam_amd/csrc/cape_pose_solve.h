@@ -37,6 +37,8 @@
 #include "cape_pose_score.h"
 
 #if defined(__HIPCC__)
+#include "cape_layout.h"     // the LDS carve and plane_to_camera of the device's steps at the end of this file
+#include "cape_map_camera.h"
 #define CAPE_POSE_UNROLL _Pragma("unroll")
 #else
 #define CAPE_POSE_UNROLL
@@ -138,10 +140,24 @@ struct PoseSolveRows
     // struct and answers with four values of its own in `own`
     CAPE_POSE_FN const double* map_plane(int k, double*) const { return planes + 8 * k + 4; }
 };
+// a subset's four words (cape_map_pose_solve's `subsets`, a selection's or a score's inlier_words) as the rows' two halves
+CAPE_POSE_FN void pose_subset(const uint32_t words[4], unsigned long long& lo, unsigned long long& hi)
+{
+    lo = (unsigned long long)words[0] | ((unsigned long long)words[1] << 32);
+    hi = (unsigned long long)words[2] | ((unsigned long long)words[3] << 32);
+}
 CAPE_POSE_FN bool pose_solve_takes(const PoseSolveRows& rows, int k)
 {
     const int i = rows.kept[k];
     return (((i < 64 ? rows.subsetLo : rows.subsetHi) >> (i & 63)) & 1ull) != 0ull;
+}
+// row k of `planes` and `kept` from the pair's feature row: the two planes and the kept plane, 68 of its 112 bytes
+CAPE_POSE_FN void pose_rows_fill(const cape_pose_feature& F, int k, double* planes, int* kept)
+{
+    CAPE_POSE_UNROLL
+    for (int c = 0; c < 4; ++c)
+        planes[8 * k + c] = F.matched[c], planes[8 * k + 4 + c] = F.map_plane[c];
+    kept[k] = F.kept_plane; // (it selects a subset bit; no address is formed from it)
 }
 // the three residuals of pair k under T
 template <class Rows, class PlaneToCamera>
@@ -905,6 +921,53 @@ CAPE_POSE_FN cape_pose_selection pose_select_frame(const cape_pose_score* scores
 }
 
 #if defined(__HIPCC__)
+// ---- the device's steps around a problem, one copy for the score, solve and varied-solve kernels
+// what a lane reads of the frame's feature rows through LDS (the reasons are in the header of cape_pose_score.hip): 8 doubles and the
+// kept plane per pair.  The launch's dynamic LDS is this carve's `bytes`.
+struct PoseRowsLayout
+{
+    size_t planes, kept, bytes;
+};
+__host__ __device__ constexpr PoseRowsLayout pose_rows_layout()
+{
+    constexpr int WP = kPoseScoreMaxPairs;
+    Layout l;
+    PoseRowsLayout o{};
+    o.planes = l.take<double>((size_t)WP * 8, 16);
+    o.kept = l.take<int>((size_t)WP, 16);
+    o.bytes = l.end(16);
+    return o;
+}
+// the frame's rows into the carve, once per workgroup: lane k stages pair k, then the barrier -- every lane of the workgroup calls it
+__device__ __forceinline__ void pose_rows_stage(unsigned char* smem, const cape_pose_feature* frameFeatures, int nPairs, double*& planes, int*& kept)
+{
+    constexpr PoseRowsLayout lay = pose_rows_layout();
+    planes = carve_at<double>(smem, lay.planes);
+    kept = carve_at<int>(smem, lay.kept);
+    if ((int)threadIdx.x < nPairs)
+        pose_rows_fill(frameFeatures[threadIdx.x], (int)threadIdx.x, planes, kept);
+    __syncthreads();
+}
+struct DevicePlaneToCamera
+{
+    __device__ __forceinline__ void operator()(const double* T, const double* normal, double d, double qn[3], double& qd) const
+    {
+        plane_to_camera(T, normal, d, qn, qd);
+    }
+};
+// a 96-byte solution row: eight doubles, then two 16-byte stores
+__device__ __forceinline__ void store_pose_solution(cape_pose_solution* at, const cape_pose_solution& r)
+{
+    double* out = reinterpret_cast<double*>(at);
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+        out[c] = r.x[c];
+    out[6] = r.fnorm0, out[7] = r.fnorm;
+    uint4* tail = reinterpret_cast<uint4*>(out + 8);
+    tail[0] = make_uint4((unsigned)r.status, (unsigned)r.nfev, (unsigned)r.iterations, (unsigned)r.n_pairs_used);
+    tail[1] = make_uint4(r.flags, 0u, 0u, 0u);
+}
+
 // what the solve and select kernels read and write (cape_pose_solve.hip)
 struct PoseSolveParams
 {

@@ -1,7 +1,7 @@
 // cape_map_pose_solve / cape_map_pose_select: the pose solver on the pairs of cape_map_pose_score -- Levenberg-Marquardt per (frame,
 // hypothesis) and the RANSAC bookkeeping over a frame's scored hypotheses.  The statements are those of cape_pose_solve.h, which the
-// host twins cape_host_pose_solve / cape_host_pose_select compile too.  The pairs kernel of cape_pose_score.hip runs in front of the
-// solve (launch_map_pose_pairs, into the solve's own rows); all kernels write only the call's own result buffers.
+// host twins cape_host_pose_solve / cape_host_pose_select compile too.  The solve reads the pose stage's shared pair rows
+// (the pairs kernel of cape_pose_score.hip, enqueue_pose_pairs); both kernels write only the call's own result buffers.
 //
 //   cape_pose_solve_kernel : one lane per problem, one workgroup of four waves per (frame, 256 problems), as in the score kernel.
 //        The frame's feature rows -- the two planes and the kept plane -- are copied to LDS once per workgroup (the reasons are in
@@ -31,51 +31,18 @@ constexpr int kSelectFrames = 4; // frames (waves) of a select workgroup
 static_assert(sizeof(cape_pose_solution) == 96 && sizeof(cape_pose_selection) == 96, "the layouts of include/cape_hip.h");
 static_assert(sizeof(cape_pose_solution) % 16 == 0 && sizeof(cape_pose_selection) % 16 == 0, "16-byte rows");
 
-// what a lane of the solve kernel reads of a feature row: (cn, cd), the map plane, the kept plane
-struct PoseSolveLayout
-{
-    size_t planes, kept, bytes;
-};
-__host__ __device__ constexpr PoseSolveLayout pose_solve_layout()
-{
-    Layout l;
-    PoseSolveLayout o{};
-    o.planes = l.take<double>((size_t)WP * 8, 16);
-    o.kept = l.take<int>((size_t)WP, 16);
-    o.bytes = l.end(16);
-    return o;
-}
-
-struct DevicePlaneToCamera
-{
-    __device__ __forceinline__ void operator()(const double* T, const double* normal, double d, double qn[3], double& qd) const
-    {
-        plane_to_camera(T, normal, d, qn, qd);
-    }
-};
-
 } // namespace
 
 __global__ __launch_bounds__(kPoseSolveGroupProblems) void cape_pose_solve_kernel(PoseSolveParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr PoseSolveLayout lay = pose_solve_layout();
-    double* s_planes = carve_at<double>(smem, lay.planes);
-    int* s_kept = carve_at<int>(smem, lay.kept);
     const int frame = blockIdx.x;
     const int problem = blockIdx.y * kPoseSolveGroupProblems + threadIdx.x; // the workgroup's offset, then the lane
     const int4 info = p.frameInfo[frame];
     const int nPairs = info.x < 0 ? 0 : (info.x < WP ? info.x : WP);
-    // ---- the frame's rows, once per workgroup
-    if ((int)threadIdx.x < nPairs)
-    {
-        const cape_pose_feature& F = p.features[(size_t)frame * WP + threadIdx.x];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            s_planes[8 * threadIdx.x + c] = F.matched[c], s_planes[8 * threadIdx.x + 4 + c] = F.map_plane[c];
-        s_kept[threadIdx.x] = F.kept_plane; // (it selects a subset bit; no address is formed from it)
-    }
-    __syncthreads();
+    double* s_planes;
+    int* s_kept;
+    pose_rows_stage(smem, p.features + (size_t)frame * WP, nPairs, s_planes, s_kept);
     if (problem >= p.nProblems) // (idle lanes of the frame's last workgroup store nothing)
         return;
     const size_t at = (size_t)frame * p.nProblems + problem;
@@ -104,20 +71,12 @@ __global__ __launch_bounds__(kPoseSolveGroupProblems) void cape_pose_solve_kerne
     }
     PoseSolveRows rows;
     rows.planes = s_planes, rows.kept = s_kept, rows.nPairs = selected ? nPairs : 0;
-    rows.subsetLo = (unsigned long long)words[0] | ((unsigned long long)words[1] << 32);
-    rows.subsetHi = (unsigned long long)words[2] | ((unsigned long long)words[3] << 32);
+    pose_subset(words, rows.subsetLo, rows.subsetHi);
     double T[12];
     cape_pose_solution r = pose_solve_problem(rows, info.y, (uint32_t)info.z, x0, p.settings, DevicePlaneToCamera{}, T);
     if (!selected)
         r.status = CAPE_POSE_SOLVE_NO_SELECTION;
-    double* out = reinterpret_cast<double*>(p.solutions + at);
-#pragma unroll
-    for (int c = 0; c < 6; ++c)
-        out[c] = r.x[c];
-    out[6] = r.fnorm0, out[7] = r.fnorm;
-    uint4* tail = reinterpret_cast<uint4*>(out + 8);
-    tail[0] = make_uint4((unsigned)r.status, (unsigned)r.nfev, (unsigned)r.iterations, (unsigned)r.n_pairs_used);
-    tail[1] = make_uint4(r.flags, 0u, 0u, 0u);
+    store_pose_solution(p.solutions + at, r);
     double* pose = p.poses + at * 16;
 #pragma unroll
     for (int c = 0; c < 12; ++c)
@@ -138,7 +97,7 @@ __global__ __launch_bounds__(64 * kSelectFrames) void cape_pose_select_kernel(Po
 hipError_t launch_map_pose_solve(const PoseSolveParams& p, int nFrames, hipStream_t stream)
 {
     const int groups = (p.nProblems + kPoseSolveGroupProblems - 1) / kPoseSolveGroupProblems;
-    hipLaunchKernelGGL(cape_pose_solve_kernel, dim3(nFrames, groups), dim3(kPoseSolveGroupProblems), pose_solve_layout().bytes, stream, p);
+    hipLaunchKernelGGL(cape_pose_solve_kernel, dim3(nFrames, groups), dim3(kPoseSolveGroupProblems), pose_rows_layout().bytes, stream, p);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // cape_host_pose_covariance / cape_host_pose_draw_deviates (cape_host_map.h): the host twins of cape_map_pose_covariance and
-// cape_pose_draw_deviates for ONE frame -- the pair list and the feature rows as cape_host_pose_score builds them, the frame's x, subset
+// cape_pose_draw_deviates for ONE frame -- the pair list and the rows of pose_pairs.h, which cape_host_pose_score builds too, the frame's x, subset
 // and refusal, the varied planes of every iteration in the device's slab layout [pair][component][iteration], every sample through
 // pose_solve_problem and the reduction, all on the rules of csrc/cape_pose_covariance.h, which the kernels compile too.  Serial: iteration
 // after iteration; a caller that wants frames side by side calls it from threads of its own.
@@ -7,9 +7,8 @@
 #include <vector>
 
 #include "boundary_polygon.hpp"
-#include "cape_hip.h"
-#include "cape_host_map.h"
 #include "map_tracking.hpp"
+#include "pose_pairs.h"
 #include "../csrc/cape_pose_covariance.h" // the rules, shared with the kernels
 
 namespace {
@@ -36,30 +35,18 @@ extern "C" int cape_host_pose_covariance(const cape_host_map* map, const int32_t
 {
     constexpr int WP = cape::kPoseScoreMaxPairs;
     cape::PoseSolveSettings settings;
-    if (!map || !detected || map->n_planes < 0 || detected->n < 0 || detected->n > WP || n_iterations < 1 ||
-        (frame_flags & ~(uint32_t)CAPE_MATCH_EXACT_OVERFLOW) || !cape::pose_solve_settings(params, settings))
+    if (n_iterations < 1 || !cape::pose_solve_settings(params, settings))
         return CAPE_ERR_INVALID_ARGUMENT;
     if ((solution != nullptr) != (selection != nullptr) || (!solution && (!x || !subset)))
         return CAPE_ERR_INVALID_ARGUMENT;
-    std::vector<cape_pose_score> scoreRow(1);
-    std::vector<cape_pose_feature> features((size_t)WP);
-    static const double kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    // the pairs, the feature rows, n_pairs and n_invalid: those of the score twin
-    const int rc = cape_host_pose_score(map, match, detected, frame_flags, 1, kIdentity, scoreRow.data(), features.data(), nullptr);
-    if (rc != CAPE_OK)
+    cape_host::PosePairs P;
+    if (const int rc = cape_host::build_pose_pairs(map, match, detected, frame_flags, P); rc != CAPE_OK)
         return rc;
-    std::vector<double> planes((size_t)WP * 8);
-    std::vector<int> kept((size_t)WP);
-    const int nPairs = scoreRow[0].n_pairs;
-    for (int k = 0; k < nPairs; ++k)
-    {
-        for (int c = 0; c < 4; ++c)
-            planes[8 * (size_t)k + c] = features[k].matched[c], planes[8 * (size_t)k + 4 + c] = features[k].map_plane[c];
-        kept[k] = features[k].kept_plane;
-    }
+    const std::vector<cape_pose_feature>& features = P.features;
+    const int nPairs = P.nPairs;
     cape::PoseSolveRows frameRows;
-    frameRows.planes = planes.data(), frameRows.kept = kept.data(), frameRows.nPairs = nPairs, frameRows.subsetLo = frameRows.subsetHi = 0ull;
-    const cape::PoseCovFrame F = cape::pose_cov_frame(frameRows, scoreRow[0].n_invalid, frame_flags & CAPE_MATCH_EXACT_OVERFLOW, x, subset, solution, selection);
+    frameRows.planes = P.planes.data(), frameRows.kept = P.kept.data(), frameRows.nPairs = nPairs, frameRows.subsetLo = frameRows.subsetHi = 0ull;
+    const cape::PoseCovFrame F = cape::pose_cov_frame(frameRows, P.nInvalid, frame_flags & CAPE_MATCH_EXACT_OVERFLOW, x, subset, solution, selection);
     const size_t n = (size_t)n_iterations;
     std::vector<cape::PoseCovSample> samples(n);
     std::memset(samples.data(), 0, n * sizeof(cape::PoseCovSample));
@@ -71,8 +58,7 @@ extern "C" int cape_host_pose_covariance(const cape_host_map* map, const int32_t
     {
         cape::PoseVariedRows rows;
         static_cast<cape::PoseSolveRows&>(rows) = frameRows;
-        rows.subsetLo = (unsigned long long)F.words[0] | ((unsigned long long)F.words[1] << 32);
-        rows.subsetHi = (unsigned long long)F.words[2] | ((unsigned long long)F.words[3] << 32);
+        cape::pose_subset(F.words, rows.subsetLo, rows.subsetHi);
         // ---- vary: the slab of the frame, [pair][component][iteration]
         std::vector<double> slab((size_t)WP * 4 * n);
         for (size_t i = 0; i < n; ++i)

@@ -1678,27 +1678,40 @@ class Extractor:
         return features
 
     # ---- the pose solver on the same pairs: LM per (frame, hypothesis), the RANSAC selection, the refit from it ----
+    @staticmethod
+    def _pose_inputs(params, x, subsets, read, device, rows, message):
+        """What map_pose_solve and map_pose_covariance hand over alike: (params pointer, x pointer, subsets pointer, the arrays behind
+        them, to be kept until the call returns).  x / subsets: not looked at unless `read`; device addresses (int) with `device`, else
+        host arrays of rows x 6 doubles and rows x 4 words -- CapeError(message) otherwise."""
+        P = None if params is None else np.ascontiguousarray(params, POSE_SOLVE_PARAMS_DTYPE).reshape(1)
+        pp = None if P is None else P.ctypes.data_as(C.c_void_p)
+        if not read:
+            return pp, None, None, [P]
+        if device:
+            return pp, C.c_void_p(int(x)), C.c_void_p(int(subsets)), [P]
+        X, S = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(subsets, np.uint32)
+        if X.size != rows * 6 or S.size != rows * 4:
+            raise CapeError(message)
+        return pp, X.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p), [P, X, S]
+
     def map_pose_solve(self, n_frames, x0=None, subsets=None, params=None, flags=0, n_hypotheses=None, stream=0):
         """cape_map_pose_solve: per frame of [0, n_frames) and per hypothesis one Levenberg-Marquardt minimisation over the pairs of the
         last match_map_wide that the subset names.  x0: (n_frames, n_hypotheses, 6) position then the three quaternion coefficients;
         subsets: (n_frames, n_hypotheses, 4) uint32 words, bit i = the pair of kept plane i; with POSE_SOLVE_DEVICE_INPUT both are device
         addresses (int) and n_hypotheses is given; with POSE_SOLVE_FROM_SELECTION neither is read and one problem per frame comes from
         the last map_pose_select.  params: a pose_solve_params(...) row or None.  The results are pose_solutions'."""
-        P = None if params is None else np.ascontiguousarray(params, POSE_SOLVE_PARAMS_DTYPE).reshape(1)
-        pp = None if P is None else P.ctypes.data_as(C.c_void_p)
-        if flags & POSE_SOLVE_FROM_SELECTION:
-            n_hypotheses, xp, sp = 1, None, None
-        elif flags & POSE_SOLVE_DEVICE_INPUT and not isinstance(x0, np.ndarray):
+        device = bool(flags & POSE_SOLVE_DEVICE_INPUT) and not isinstance(x0, np.ndarray)
+        read = not flags & POSE_SOLVE_FROM_SELECTION
+        if not read:
+            n_hypotheses = 1
+        elif device:
             if n_hypotheses is None:
                 raise CapeError("map_pose_solve: n_hypotheses is required with device addresses")
-            xp, sp = C.c_void_p(int(x0)), C.c_void_p(int(subsets))
         else:
-            X = np.ascontiguousarray(x0, np.float64)
-            S = np.ascontiguousarray(subsets, np.uint32)
-            n_hypotheses = X.size // (6 * n_frames) if n_hypotheses is None and n_frames > 0 else (n_hypotheses or 0)
-            if X.size != n_frames * n_hypotheses * 6 or S.size != n_frames * n_hypotheses * 4:
-                raise CapeError("map_pose_solve: x0 must hold n_frames x n_hypotheses x 6 doubles and subsets x 4 words")
-            xp, sp = X.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p)
+            x0 = np.ascontiguousarray(x0, np.float64)
+            n_hypotheses = x0.size // (6 * n_frames) if n_hypotheses is None and n_frames > 0 else (n_hypotheses or 0)
+        pp, xp, sp, keep = self._pose_inputs(params, x0, subsets, read, device, n_frames * n_hypotheses,
+                                             "map_pose_solve: x0 must hold n_frames x n_hypotheses x 6 doubles and subsets x 4 words")
         _check(self.L, self.L.cape_map_pose_solve(self.h, n_frames, n_hypotheses, xp, sp, pp, flags, C.c_void_p(stream)), "cape_map_pose_solve")
         self.pose_solve_hypotheses = n_hypotheses
 
@@ -1739,20 +1752,10 @@ class Extractor:
         shared by the frames; otherwise Philox keyed by seed at (frame + frame_base, iteration, pair slot).  With
         POSE_COVARIANCE_DEVICE_INPUT x, subsets and deviates are device addresses (int).  POSE_COVARIANCE_KEEP_SAMPLES keeps the sample
         rows for pose_covariance_samples.  params: a pose_solve_params(...) row or None.  The results are pose_covariance's."""
-        P = None if params is None else np.ascontiguousarray(params, POSE_SOLVE_PARAMS_DTYPE).reshape(1)
-        pp = None if P is None else P.ctypes.data_as(C.c_void_p)
         device = bool(flags & POSE_COVARIANCE_DEVICE_INPUT)
-        xp = sp = zp = None
-        keep = []
-        if not flags & POSE_COVARIANCE_FROM_SOLUTION:
-            if device and not isinstance(x, np.ndarray):
-                xp, sp = C.c_void_p(int(x)), C.c_void_p(int(subsets))
-            else:
-                X, S = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(subsets, np.uint32)
-                if X.size != n_frames * 6 or S.size != n_frames * 4:
-                    raise CapeError("map_pose_covariance: x must hold n_frames x 6 doubles and subsets x 4 words")
-                xp, sp = X.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p)
-                keep += [X, S]
+        pp, xp, sp, keep = self._pose_inputs(params, x, subsets, not flags & POSE_COVARIANCE_FROM_SOLUTION, device and not isinstance(x, np.ndarray), n_frames,
+                                             "map_pose_covariance: x must hold n_frames x 6 doubles and subsets x 4 words")
+        zp = None
         if deviates is not None:
             if device and not isinstance(deviates, np.ndarray):
                 zp = C.c_void_p(int(deviates))

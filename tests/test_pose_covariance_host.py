@@ -338,6 +338,16 @@ def test_refusals_are_the_frames(host, frame39):
         assert row["status"] == want and row["n_ok"] == 0
 
 
+def test_a_match_entry_out_of_range_is_an_invalid_argument(host, frame39):
+    """the pair builder the three twins share checks the match against the detected planes: an entry >= detected->n"""
+    f = frame39
+    for entry in (39, 128, 2 ** 31 - 1):
+        match = f["match"].copy()
+        match[20] = entry
+        with pytest.raises(host.CapeError, match=r"cape_host_pose_covariance failed \(-1\)"):  # CAPE_ERR_INVALID_ARGUMENT
+            host.host_pose_covariance(f["arrays"], f["tracks"], match, f["detected"], 5, f["x"], f["words"])
+
+
 # ---- statistical sanity: the position block against first-order propagation ------------------------------------------------------------
 N_SAMPLES = 500
 BOUND = 6.0 * math.sqrt(2.0 / (N_SAMPLES - 1))  # six standard errors of a sample variance, relative

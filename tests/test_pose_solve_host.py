@@ -368,6 +368,19 @@ def test_refusals(host):
             host.host_pose_solve(arrays, tracks, match, detected, starts[3:4], subsets[3:4], params=host.pose_solve_params(**bad_params))
 
 
+def test_a_match_entry_out_of_range_is_an_invalid_argument(host):
+    """the pair builder the three twins share checks the match against the detected planes: an entry >= detected->n"""
+    planes, arrays, tracks, detected, x_true, rng = make_frame(8, n=12)
+    subsets = np.array([words_of(range(12))], np.uint32)
+    rows, _, _ = host.host_pose_solve(arrays, tracks, np.arange(12, dtype=np.int32), detected, x_true[None], subsets)
+    assert rows[0]["status"] in (1, 2, 3)  # (the frame itself solves)
+    for entry in (12, 128, 2 ** 31 - 1):
+        match = np.arange(12, dtype=np.int32)
+        match[7] = entry
+        with pytest.raises(host.CapeError, match=r"cape_host_pose_solve failed \(-1\)"):  # CAPE_ERR_INVALID_ARGUMENT
+            host.host_pose_solve(arrays, tracks, match, detected, x_true[None], subsets)
+
+
 def test_parallel_planes_take_the_pivoted_qrfac_branch(host):
     """three pairs whose map planes are parallel, seen from a start with the identity rotation: the residuals do not depend on the two
     in-plane coordinates at all, their forward differences are exactly 0, R has zero diagonal entries and lmstr calls qrfac"""
